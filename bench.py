@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the EM hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1 needs one process per GPU: either the caller provides them
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
@@ -17,19 +17,28 @@ the frames are shards of ONE joint fit: every iteration all-reduces the (7 J + 2
 statistics over RCCL before the (redundant, identical) M-step -- weak scaling, `value` = frames x iterations
 / second.
 
-Timing: W untimed warm-up steps, then blocks of exactly K steps, each bracketed by a barrier +
-stream synchronisation on both sides and reduced with MAX over the ranks.  Blocks repeat until at least
-MIN_TIMED_S of timed work has accumulated (the chip needs tens of milliseconds of load before its clocks
-settle; a single 20-step block lasts 8 ms); `value` / `ms_per_step` are those of the MEDIAN block, the first
-(un-settled) block and the spread are reported next to it.
+Timing: a fixed internal clock warm-up (CLOCK_WARMUP_STEPS fused iterations on a scratch fit), W untimed
+warm-up steps, then ONE block of exactly K timed steps, bracketed by a barrier + stream synchronisation on
+both sides and reduced with MAX over the ranks; `ms_per_step` = block / K.  `--min-time S` repeats K-step
+blocks until at least S seconds of timed work (and three blocks) have accumulated and reports the MEDIAN
+block, the first (un-settled) block and the spread next to it.
 
-The JSON line also carries
+--dump-outputs DIR: after the timed steps, what the timed path returns to its caller after its last step --
+the fitted model (mu, cov, w, inv_std) and the log-likelihood of every iteration of the timed fit -- as
+DIR/<name>.npy (float32 / float64).  The inputs are fixed by the seeds, so two builds can be compared output
+for output.
+
+A plain run prints the headline alone.  --full adds (behind the same headline)
+  fused_kernel / roofline_fused / allreduce_us   one more K-step block under the hipEvent profiler -- a fit of its
+                  own from the initial parameters; the legs below get the model of the timed steps (W + K x blocks
+                  iterations; up to round 6 the profiled block continued the timed fit, one block more)
   roofline        the materialising E-step kernel (the API's e_step(): writes log_resp[N,J]): HBM bound,
                   achieved = algorithmic bytes (12N + 4NJ + 4N + 28J) / mean hipEvent time
   roofline_fused  the kernel the timed step spends its time in (VALU bound): fp32 FLOP/s against the vector
                   peak and VALU instructions per cycle per SIMD, instruction counts read from the code object
   fullcov / tree_1M / hgmm / kmeans_init / registration / bunny    the other hot kernels at their configs
   cpu_baseline    the NumPy oracle (same op sequence as the reference's CPU path) on this box's host cores
+  N > 1           the sharded HGMM build and the same joint fit over the one-shot peer exchange (`peer_exchange`)
 """
 import argparse
 import json
@@ -51,8 +60,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s mea
 FP32_VECTOR_PEAK_TF = 157.3  # MI355X_MICROARCH.md: peak FP32 vector (spec)
 FP64_VECTOR_PEAK_TF = 78.6   # half the fp32 rate (valubench: v_fma_f64 issues at the v_pk_fma_f32 rate)
 SPEC_CLOCK_HZ = 2.4e9
-MIN_TIMED_S = 1.0            # timed blocks repeat until this much timed work has accumulated
-MAX_BLOCKS = 400
+MAX_BLOCKS = 400             # --min-time: at most this many timed blocks
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 CLOCK_WARMUP_STEPS = int(os.environ.get("HGMM_BENCH_CLOCK_WARMUP", "250"))   # untimed fused iterations before the W + K x blocks
 RCCL_INIT_FAILED = 17        # exit code of a rank whose RCCL communicator could not be created
 
@@ -820,7 +829,7 @@ def replica_pairs_leg(ctx):
     pairs, eight contexts x 32 pairs per launch set on this GPU (the mode's defaults), no communicator -- run as a process
     of its own (it creates its own contexts and threads)."""
     cmd = [sys.executable, os.path.abspath(__file__), "--mode", "pairs", "--steps", "20", "--warmup", "2", "--min-time", "3.0",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
@@ -940,9 +949,31 @@ def choose_collective(ctx, rank, world, order, token, hosts, round0=1):
     return None, failed, ctx
 
 
-def timed_fit(ctx, args, world, init):
-    """The timed region: W warm-up steps, then blocks of exactly K fused EM iterations, each bracketed by barrier +
-    stream synchronisation, MAX over ranks; one more block under the hipEvent profiler; the fitted model."""
+def enough_blocks(blocks, min_time, share=1.0):
+    """One timed block by default; with --min-time S, blocks repeat until share x S seconds and three blocks."""
+    if min_time is None:
+        return True
+    return (sum(blocks) >= share * min_time and len(blocks) >= 3) or len(blocks) >= MAX_BLOCKS
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, float64 kept float64 (integers too), everything else float32."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iu" else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def timed_fit(ctx, args, world, init, profile=False):
+    """The timed region: W warm-up steps, then one block of exactly K fused EM iterations (--min-time: blocks of K until
+    enough_blocks), bracketed by barrier + stream synchronisation, MAX over ranks; the fitted model after the last timed
+    step.  profile: one more K-step fit from the same start under the hipEvent profiler (not part of the timing)."""
     mu0, cov0, w0 = init
 
     def barrier():
@@ -950,7 +981,7 @@ def timed_fit(ctx, args, world, init):
         ctx.allreduce([0.0])
 
     K, W = args.steps, args.warmup
-    cap = W + K * (MAX_BLOCKS + 2) + 8
+    cap = W + K * (MAX_BLOCKS + 1) + 8
     # the chip's clocks need tens of milliseconds of load to settle and the driver's --warmup (5 steps = 1.7 ms) does not
     # provide them: a fixed internal warm-up of CLOCK_WARMUP_STEPS fused iterations on a scratch fit (not part of any count,
     # the timed fit below starts from the initial parameters again) makes `value` independent of --warmup
@@ -968,19 +999,24 @@ def timed_fit(ctx, args, world, init):
         barrier()
         dt_local = time.perf_counter() - t0
         blocks.append(float(ctx.allreduce([dt_local], op="max")[0]))        # identical on every rank
-        if (sum(blocks) >= args.min_time and len(blocks) >= 3) or len(blocks) >= MAX_BLOCKS:
+        if enough_blocks(blocks, args.min_time):
             break
-    # one more block under the hipEvent profiler (not part of the timing): kernel and all-reduce durations
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    ctx.flat_train_step(K)
-    barrier()
-    ctx.profile_enable(False)
-    fused_ms, fused_n = ctx.profile_get("flat_fused")
-    ar_ms, ar_n = ctx.profile_get("allreduce") if (world > 1 or args._world1_comm) else (0.0, 0)
     inv, mu, w, cov, lls, conv, n_it = ctx.flat_train_end()
-    assert n_it == W + K * (len(blocks) + 1), (n_it, W, K, len(blocks))
+    assert n_it == W + K * len(blocks), (n_it, W, K, len(blocks))
     assert np.isfinite(lls).all()
+    fused_ms = fused_n = ar_ms = ar_n = None
+    if profile:
+        # one more block under the hipEvent profiler (not part of the timing): kernel and all-reduce durations
+        ctx.flat_train_begin(0.0, mu0, cov0, w0, "diag", "W", lls_capacity=K + 8)
+        barrier()
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        ctx.flat_train_step(K)
+        barrier()
+        ctx.profile_enable(False)
+        fused_ms, fused_n = ctx.profile_get("flat_fused")
+        ar_ms, ar_n = ctx.profile_get("allreduce") if (world > 1 or args._world1_comm) else (0.0, 0)
+        ctx.flat_train_end()
     # every rank must hold the same model after the joint fit: checksum of (mu, cov, w, inv) as raw 32-bit words
     # (exact in float64), all-reduced with max and with min -- equal on all ranks iff max == min
     words = np.concatenate([np.ascontiguousarray(a).view(np.uint32).ravel() for a in (mu, cov, w, inv)]).astype(np.float64)
@@ -1001,7 +1037,7 @@ def collective_world1_leg(ctx, args, init, base_it_per_s):
     call per iteration; `it_per_s` against `it_per_s_no_communicator` also shows what the enqueue costs the host."""
     out = {"payload_bytes": 8 * (7 * 1024 + 2), "it_per_s_no_communicator": base_it_per_s}
     a2 = argparse.Namespace(**vars(args))
-    a2.min_time = min(args.min_time, 0.3)
+    a2.min_time = 0.3 if args.min_time is None else min(args.min_time, 0.3)
     a2._world1_comm = True
     for kind in ("rccl", "ipc"):
         try:
@@ -1010,7 +1046,7 @@ def collective_world1_leg(ctx, args, init, base_it_per_s):
             else:
                 ctx.comm_init_ipc(1, 0, "hgmm_bench_w1_%d" % os.getpid())
             try:
-                r = timed_fit(ctx, a2, 1, init)
+                r = timed_fit(ctx, a2, 1, init, profile=True)
             finally:
                 ctx.comm_destroy()
             med = float(np.median(r["blocks"]))
@@ -1157,15 +1193,18 @@ def rank_main(args):
     ctx.set_points(frame)
 
     K, W = args.steps, args.warmup
-    fit = timed_fit(ctx, args, world, (mu0, cov0, w0))
+    full = args.full
+    fit = timed_fit(ctx, args, world, (mu0, cov0, w0), profile=full)
     blocks, consistent = fit["blocks"], fit["consistent"]
     inv, mu, w, cov = fit["model"]
     lls = fit["lls"]
     fused_ms, fused_n, ar_ms, ar_n = fit["fused_ms"], fit["fused_n"], fit["ar_ms"], fit["ar_n"]
     if not consistent:
         sys.stderr.write("rank %d: model checksums differ across ranks: max %s min %s\n" % (rank, fit["checksum"], fit["checksum_lo"]))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mu": mu, "cov": cov, "w": w, "inv_std": inv, "lls": lls})
     sharded_tree = None
-    if world > 1 and "sharded_tree" not in args.skip:
+    if full and world > 1 and "sharded_tree" not in args.skip:
         try:                                        # every rank calls it or none does (args.skip is the same everywhere)
             sharded_tree = sharded_tree_leg(ctx, rank, world)
         except Exception as e:
@@ -1173,7 +1212,7 @@ def rank_main(args):
         ctx.set_points(frame)
     # --collective auto: the same joint fit once more over the one-shot peer exchange, reported beside the RCCL figure
     second = None
-    if world > 1 and requested == "auto" and kind in ("rccl", "host") and len(hosts) == 1 and not rehearsal_host_only:
+    if full and world > 1 and requested == "auto" and kind in ("rccl", "host") and len(hosts) == 1 and not rehearsal_host_only:
         _run_with_timeout(ctx.comm_destroy, 60.0)
         k2, failed2, ctx2 = choose_collective(ctx, rank, world, ["ipc"], token, hosts, round0=8)
         if ctx2 is not ctx:                             # (the peer-exchange attach hung: carry on with the fresh context)
@@ -1182,7 +1221,7 @@ def rank_main(args):
         f2 = None
         if k2 == "ipc":
             try:                                    # a side leg on hardware it has never seen must not lose the headline line
-                f2 = timed_fit(ctx, args, world, (mu0, cov0, w0))
+                f2 = timed_fit(ctx, args, world, (mu0, cov0, w0), profile=True)
             except Exception as e:                  # (a peer's slice that never arrives fails every rank alike, after ~20 s)
                 sys.stderr.write("rank %d: the peer-exchange leg failed: %r\n" % (rank, e))
                 second = {"collective": COLLECTIVES["ipc"], "error": "the joint fit failed: %r" % (e,)}
@@ -1206,7 +1245,7 @@ def rank_main(args):
     out = None
     if rank == 0:
         med = float(np.median(blocks))
-        fused_avg_ms = fused_ms / max(fused_n, 1)
+        fused_avg_ms = fused_ms / max(fused_n, 1) if full else None
         collective = COLLECTIVES.get(kind)
         out = {
             "metric": "EM iterations/sec (N points x J components); E-step achieved HBM GB/s",
@@ -1230,16 +1269,17 @@ def rank_main(args):
                        "median_block_ms": med * 1e3, "first_block_it_per_s": world * K / blocks[0],
                        "min_block_it_per_s": world * K / max(blocks), "max_block_it_per_s": world * K / min(blocks),
                        "rule": "value = world x K / median block; every block = K steps between barrier+sync pairs, "
-                               "MAX over ranks"},
+                               "MAX over ranks; one block unless --min-time"},
             "it_per_s_per_gpu": K / med,
             "rank_consistency": {"identical_model_on_all_ranks": fit["consistent"], "checksum": fit["checksum"],
                                  "rule": "sum of the raw 32-bit words of (mu, cov, w, inv_std), plain and position-"
                                          "weighted, all-reduced with max and min over the ranks"},
-            "fused_kernel": {"avg_ms": fused_avg_ms, "launches": fused_n,
-                             "pairs_per_s": N_POINTS * J_COMP / (fused_avg_ms * 1e-3) if fused_avg_ms else None,
-                             "last_lls": float(lls[-1])},
         }
-        if world > 1:
+        if full:
+            out["fused_kernel"] = {"avg_ms": fused_avg_ms, "launches": fused_n,
+                                   "pairs_per_s": N_POINTS * J_COMP / (fused_avg_ms * 1e-3) if fused_avg_ms else None,
+                                   "last_lls": float(lls[-1])}
+        if full and world > 1:
             out["allreduce_us"] = 1e3 * ar_ms / max(ar_n, 1)
             out["allreduce_payload_bytes"] = 8 * (7 * 1024 + 2)        # 7 statistics x Jpad(=1024) + sum lpn + n
             out["allreduce_launches"] = ar_n
@@ -1253,13 +1293,13 @@ def rank_main(args):
         if not consistent:
             out["error"] = "ranks ended the joint fit with different parameters"
 
-    # ---- rank-0 legs (every N): the materialising E-step's roofline; N = 1: the other hot kernels at their configs ----
-    if rank == 0:
+    # ---- --full, rank-0 legs (every N): the materialising E-step's roofline; N = 1: the other hot kernels at their configs ----
+    if rank == 0 and full:
         lr = ctx.empty((N_POINTS, J_COMP), np.float32)
         out["roofline"] = estep_roofline_leg(ctx, lr, (mu0, cov0, w0), (inv, mu, w), args)
         if world > 1:
             out["roofline"]["scope"] = "one launch on rank 0's GPU after the joint fit (the kernel is rank-local)"
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and full:
         # (from the INITIAL parameters, as a caller's own loop starts: inv_cov0 = 1 / sqrt(cov0), gmm_impl.py:122)
         out["materialised_iteration"] = materialised_iteration_leg(ctx, lr, (1.0 / np.sqrt(cov0)).astype(np.float32), mu0, w0)
         out["predict"] = predict_leg(ctx, (inv, mu, w))
@@ -1310,20 +1350,21 @@ def rank_main(args):
                 out[name] = leg(ctx)
             except Exception as e:                                    # a side leg must not lose the headline line
                 out[name] = {"error": repr(e)}
-    if rank == 0 and world == 1 and "collective" not in args.skip:
+    if rank == 0 and world == 1 and full and "collective" not in args.skip:
         try:
             ctx.set_points(frame)
             out["collective_world1"] = collective_world1_leg(ctx, args, (mu0, cov0, w0), out["it_per_s_per_gpu"])
         except Exception as e:
             out["collective_world1"] = {"error": repr(e)}
     if rank == 0:
-        if not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_main()
-            if world > 1:
-                out["cpu_baseline"]["scope"] = "timed on rank 0's host cores after the joint fit (other ranks idle)"
-        else:
-            out["cpu_baseline"] = None
-        out = split_legs(out, args)
+        if full:
+            if not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_main()
+                if world > 1:
+                    out["cpu_baseline"]["scope"] = "timed on rank 0's host cores after the joint fit (other ranks idle)"
+            else:
+                out["cpu_baseline"] = None
+            out = split_legs(out, args)
         guard.restore()
         print(json.dumps(out))
         sys.stdout.flush()
@@ -1458,6 +1499,7 @@ def pairs_main(args):
     active = {"kind": args.scan_dtype}
     K, W = args.steps, args.warmup
     iters, errs, starts, done = [], [], [], []
+    last = [None] * C                                 # per context: (pair indices, results, iterations) of its last timed step
     failures = []
 
     def worker(wi, q_in, q_out):
@@ -1480,6 +1522,7 @@ def pairs_main(args):
                         if n_steps > 0 and active["kind"] == args.scan_dtype:   # (negative: warm-up, nothing recorded)
                             iters.extend(n_its)
                             done.extend((r.transformation, k) for r, k in zip(results, ks))    # judged after the timing
+                            last[wi] = (ks, results, n_its)
                         step += 1
                     c.synchronize()
                     q_out.put(wi)
@@ -1515,12 +1558,19 @@ def pairs_main(args):
         dt_local = time.perf_counter() - t0
         barrier()
         blocks.append(float(group.allgather_f64([dt_local]).max()))          # identical on every rank
-        if (sum(blocks) >= args.min_time and len(blocks) >= 3) or len(blocks) >= MAX_BLOCKS:
+        if enough_blocks(blocks, args.min_time):
             break
-    # the other kind of scans, timed the same way (half the time)
+    if rank == 0 and args.dump_outputs:
+        # the transformations (and iteration counts) of the last timed step, context by context, pair by pair
+        rows = [(k, r, n) for ks, results, n_its in last for k, r, n in zip(ks, results, n_its)]
+        dump_outputs(args.dump_outputs, {"pair_index": [k for k, _, _ in rows],
+                                         "rot": [np.asarray(r.transformation.rot, np.float64) for _, r, _ in rows],
+                                         "t": [np.asarray(r.transformation.t, np.float64) for _, r, _ in rows],
+                                         "registration_iterations": [n for _, _, n in rows]})
+    # --full: the other kind of scans, timed the same way (half the time)
     other_kind = "float64" if args.scan_dtype == "float32" else "float32"
     other_blocks = []
-    if not args.no_other_dtype:
+    if args.full and not args.no_other_dtype:
         active["kind"] = other_kind
         run_steps(-max(W, 1))
         while True:
@@ -1530,7 +1580,7 @@ def pairs_main(args):
             dt_local = time.perf_counter() - t0
             barrier()
             other_blocks.append(float(group.allgather_f64([dt_local]).max()))
-            if (sum(other_blocks) >= 0.5 * args.min_time and len(other_blocks) >= 3) or len(other_blocks) >= MAX_BLOCKS:
+            if enough_blocks(other_blocks, args.min_time, share=0.5):
                 break
         active["kind"] = args.scan_dtype
     for q in q_ins:
@@ -1552,13 +1602,15 @@ def pairs_main(args):
     mine = np.array([np.max(errs), np.mean(errs), np.mean(starts), float(np.sum(iters)), float(len(iters))])
     allr = group.allgather_f64(mine)
     ok = bool(allr[:, 0].max() < 0.006)
-    # kernel time of one pair under the hipEvent profiler (not part of the timing)
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    register_pair(ctx, kinds[args.scan_dtype][0], kinds[args.scan_dtype][1][0])
-    ctx.synchronize()
-    ctx.profile_enable(False)
-    prof = {k: ctx.profile_get(k) for k in ("tree_estep", "tree_loglik", "tree_reg")}
+    # --full: kernel time of one pair under the hipEvent profiler (not part of the timing)
+    prof = None
+    if args.full:
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        register_pair(ctx, kinds[args.scan_dtype][0], kinds[args.scan_dtype][1][0])
+        ctx.synchronize()
+        ctx.profile_enable(False)
+        prof = {k: ctx.profile_get(k) for k in ("tree_estep", "tree_loglik", "tree_reg")}
     out = None
     if rank == 0:
         med = float(np.median(blocks))
@@ -1598,7 +1650,7 @@ def pairs_main(args):
             "accuracy": {"mean_misalignment_before_mm": 1e3 * float(allr[:, 2].mean()),
                          "mean_misalignment_after_mm": 1e3 * float(allr[:, 1].mean()),
                          "max_misalignment_after_mm": 1e3 * float(allr[:, 0].max()), "bound_mm": 6.0, "ok": ok},
-            "kernels_ms_per_pair": {k: {"ms": v[0], "launches": v[1]} for k, v in prof.items()},
+            "kernels_ms_per_pair": {k: {"ms": v[0], "launches": v[1]} for k, v in prof.items()} if prof else None,
             "host_phases_ms_per_batch": ({k: float(np.mean([p[k] for p in PHASES if p])) for k in PHASES[-1]}
                                          if PHASES and PHASES[-1] else None),
             "h2d_note": "every pair's two clouds are uploaded from host arrays through the reference's host-array API (float32 "
@@ -1611,7 +1663,7 @@ def pairs_main(args):
         }
         if not ok:
             out["error"] = "a registered pair ended more than 6 mm from its ground truth"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = pairs_cpu_baseline()
             except Exception as e:
@@ -1635,8 +1687,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--min-time", type=float, default=MIN_TIMED_S,
-                    help="timed K-step blocks repeat until this many seconds of timed work (default 1.0)")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="timed K-step blocks repeat until this many seconds of timed work and three blocks, `value` "
+                         "from the median block (default: one block of exactly --steps steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the profiled block, rooflines, the side legs, the CPU baseline, the N > 1 "
+                         "side fits; --mode pairs: the other scan type, per-pair kernel times, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--mode", default="fit", choices=["fit", "pairs"],
                     help="fit (default): the headline joint EM fit, frames sharded over the GPUs with an all-reduce of the "
                          "sufficient statistics; pairs: independent scan pairs, one registration_gmmtree per GPU and step, "

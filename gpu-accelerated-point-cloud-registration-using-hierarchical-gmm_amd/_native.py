@@ -502,6 +502,7 @@ class Context:
         self.h = h
         self.device_id = device_id
         self.nranks, self.rank = 1, 0
+        self.comm_attached = False             # a communicator (of any size, one rank included) is attached
         self._points_handles = set()          # clouds created through points_create and not destroyed yet
         self._arena = None                    # (pointer, free slab indices) of the small-array pool
         self._freed = {}                      # size -> pointers of dead arrays kept for reuse (_free)
@@ -1216,17 +1217,20 @@ class Context:
         buf = C.create_string_buffer(bytes(unique_id), 128)
         self._check(self.lib.hgmm_comm_init_rank(self.h, int(nranks), int(rank), buf))
         self.nranks, self.rank = int(nranks), int(rank)
+        self.comm_attached = True
 
     def comm_init_host(self, nranks, rank, name: str):
         """Host shared-memory communicator (tests on a single-GPU box; see include/hgmm.h)."""
         self._check(self.lib.hgmm_comm_init_host(self.h, int(nranks), int(rank), name.encode()))
         self.nranks, self.rank = int(nranks), int(rank)
+        self.comm_attached = True
 
     def comm_init_ipc(self, nranks, rank, name: str):
         """One-shot peer exchange over mapped peer memory (hipIpc; the ranks are processes of one node, see
         include/hgmm.h): every all-reduce is one kernel per rank, all ranks end with bitwise the same sums."""
         self._check(self.lib.hgmm_comm_init_ipc(self.h, int(nranks), int(rank), name.encode()))
         self.nranks, self.rank = int(nranks), int(rank)
+        self.comm_attached = True
 
     def comm_stats(self):
         """-> (all-reduces this context has enqueued on its communicator, level-iterations of hgmm_tree_build enqueued
@@ -1238,6 +1242,7 @@ class Context:
     def comm_destroy(self):
         self._check(self.lib.hgmm_comm_destroy(self.h))
         self.nranks, self.rank = 1, 0
+        self.comm_attached = False
 
     def allreduce(self, values, op="sum"):
         a = np.ascontiguousarray(values, dtype=np.float64).copy()

@@ -180,8 +180,9 @@ class KMeans:
         first = True
         while n_iter < self.max_iter:
             pending = None
-            if ranks == 1:
-                # the loop runs on the device until a stop rule fires or a cluster comes up empty
+            if ranks == 1 and not getattr(ctx, "comm_attached", False):
+                # the loop runs on the device until a stop rule fires or a cluster comes up empty (the library's loop is for a
+                # context without a communicator; one attached, even of one rank, takes the step-by-step path below)
                 centres, done_it, strict, pending = ctx.kmeans_lloyd(centres, self.max_iter - n_iter, tol_abs,
                                                                      reset_labels=first)
                 n_iter += done_it

@@ -79,10 +79,15 @@ class FakeContext:
     def flat_train_step(self, iters):
         self.n_it += iters
 
+    @staticmethod
+    def fitted_model(J, n_it):
+        """What flat_train_end returns: (inv, mu, w, cov, lls), every array with values of its own."""
+        base = np.arange(J * 3, dtype=np.float32).reshape(J, 3)
+        return (base + 1.0, base + 1.0e4, np.arange(J, dtype=np.float32) + 2.0e4, base + 3.0e4,
+                np.arange(n_it, dtype=np.float32) - 1.0e3)
+
     def flat_train_end(self):
-        J = self.J
-        z = np.zeros((J, 3), np.float32)
-        return z, z, np.zeros(J, np.float32), z, np.zeros(self.n_it, np.float32), False, self.n_it
+        return self.fitted_model(self.J, self.n_it) + (False, self.n_it)
 
     def flat_train(self, max_iter, tol, mu, cov, w, cov_type="diag", variant="W"):
         z = np.zeros_like(np.asarray(mu, dtype=np.float32))
@@ -128,7 +133,7 @@ def _rank_main(rank, world, port, q):
     hgmm_amd.Context = FakeContext
     bench.N_POINTS = 2000                       # keep the synthetic frames tiny
     bench.synth_frame = lambda seed, n=2000: np.random.RandomState(seed).rand(n, 3).astype(np.float32)
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--min-time", "0"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--min-time", "0", "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -186,19 +191,19 @@ def test_bench_two_rank_flow():
 HELPER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_bench_fake_rank.py")
 
 
-def _run_launcher(n, mode, extra_args=()):
+def _run_launcher(n, mode, extra_args=(), base_args=("--min-time", "0")):
     """python -c 'bench.launch_ranks / self_launch' in a child so that rank 0's inherited stdout can be captured."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys, types; sys.path.insert(0, %r); import bench\n"
             "args = types.SimpleNamespace(gpus=%d)\n"
-            "argv = ['--gpus', '%d', '--steps', '2', '--warmup', '1', '--min-time', '0'] + %r\n"
+            "argv = ['--gpus', '%d', '--steps', '2', '--warmup', '1'] + %r + %r\n"
             "bench.__file__ = %r\n"
             "import os\n"
             "orig = bench.launch_ranks\n"
             "bench.launch_ranks = lambda n, argv, script=None, **kw: orig(n, argv, script=%r, **kw)\n"
             "sys.exit(bench.self_launch(args, argv) if %r == 'self' else bench.launch_ranks(%d, argv))\n"
-            % (root, n, n, list(extra_args), HELPER, HELPER, mode, n))
+            % (root, n, n, list(base_args), list(extra_args), HELPER, HELPER, mode, n))
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
@@ -206,7 +211,7 @@ def _run_launcher(n, mode, extra_args=()):
 
 
 def test_self_launch_two_ranks():
-    r = _run_launcher(2, "self")
+    r = _run_launcher(2, "self", ["--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -223,7 +228,7 @@ def test_ranks_of_an_external_launcher_fall_back_in_place_when_rccl_is_unavailab
     """Started by something that is not bench.py's own launcher (torchrun in the driver's N > 1 runs): no restart is
     possible, every rank moves on to the next backend -- host shared memory, the one that needs nothing from the GPUs'
     interconnect -- and the line is still produced; the peer exchange is timed beside it as the side leg."""
-    r = _run_launcher(2, "plain", ["--skip", "RCCL_BROKEN"])
+    r = _run_launcher(2, "plain", ["--full", "--skip", "RCCL_BROKEN"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -237,7 +242,7 @@ def test_fallback_chain_keeps_the_line_when_the_peer_exchange_is_unavailable_too
     """Neither RCCL nor the peer exchange: the headline runs on host shared memory and the side leg reports that the
     exchange could not be set up -- under bench.py's own launcher as under an external one."""
     for mode in ("self", "plain"):
-        r = _run_launcher(2, mode, ["--skip", "RCCL_AND_IPC_BROKEN"])
+        r = _run_launcher(2, mode, ["--full", "--skip", "RCCL_AND_IPC_BROKEN"])
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
         assert len(lines) == 1, r.stdout
@@ -247,7 +252,7 @@ def test_fallback_chain_keeps_the_line_when_the_peer_exchange_is_unavailable_too
 
 
 def test_explicit_collective_is_used_alone():
-    r = _run_launcher(2, "plain", ["--collective", "ipc"])
+    r = _run_launcher(2, "plain", ["--full", "--collective", "ipc"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][0])
     assert "peer exchange" in d["config"]["collective"] and "fallback" not in d["config"] and "peer_exchange" not in d
@@ -306,7 +311,7 @@ def test_pairs_mode_two_ranks_without_a_communicator():
 
 
 def test_pairs_mode_single_rank_carries_a_cpu_baseline():
-    r = _run_launcher(1, "plain", ["--mode", "pairs"])
+    r = _run_launcher(1, "plain", ["--full", "--mode", "pairs"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["n_gpus"] == 1 and d["cpu_baseline"]["kind"] == "port" and d["mode"] == "pairs"
@@ -330,3 +335,40 @@ def test_stdout_carries_the_json_line_only():
     assert r.returncode == 0, r.stderr
     assert r.stdout.strip() == '{"the": "line"}', r.stdout
     assert "banner through C stdio" in r.stderr and "raw write to fd 1" in r.stderr and "teardown chatter" in r.stderr
+
+
+def _json_line(r):
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_model(tmp_path):
+    """A plain run (no --min-time, no --full): ONE block of exactly --steps timed steps, the headline and nothing measured
+    beside it; --dump-outputs writes the model after the last timed step and the log-likelihood of every iteration."""
+    dump = str(tmp_path / "out")
+    d = _json_line(_run_launcher(1, "plain", ["--dump-outputs", dump], base_args=()))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["timing"]["blocks"] == 1
+    assert abs(d["ms_per_step"] * d["steps"] - d["timing"]["median_block_ms"]) <= 1e-9 * d["timing"]["median_block_ms"]
+    for k in ("roofline", "roofline_fused", "fused_kernel", "cpu_baseline", "legs", "summary", "collective_world1"):
+        assert k not in d
+    assert sorted(os.listdir(dump)) == ["cov.npy", "inv_std.npy", "lls.npy", "mu.npy", "w.npy"]
+    inv, mu, w, cov, lls = FakeContext.fitted_model(800, 1 + 2)      # the timed fit: warm-up + timed iterations
+    for name, want in (("inv_std", inv), ("mu", mu), ("w", w), ("cov", cov), ("lls", lls)):
+        got = np.load(os.path.join(dump, name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, want), name
+
+
+def test_pairs_mode_plain_run_dumps_the_last_step(tmp_path):
+    """--mode pairs without --full: one block of --steps steps, no side timings; --dump-outputs writes the transformations
+    of the pairs of the last timed step, context by context."""
+    dump = str(tmp_path / "out")
+    d = _json_line(_run_launcher(1, "plain", ["--mode", "pairs", "--contexts-per-gpu", "2", "--batch", "3",
+                                               "--dump-outputs", dump], base_args=()))
+    assert d["timing"]["blocks"] == 1 and d["other_scan_dtype"] is None and d["cpu_baseline"] is None
+    rot, t = np.load(os.path.join(dump, "rot.npy")), np.load(os.path.join(dump, "t.npy"))
+    assert rot.dtype == np.float64 and rot.shape == (2 * 3, 3, 3) and t.shape == (2 * 3, 3)
+    assert np.load(os.path.join(dump, "pair_index.npy")).shape == (2 * 3,)

@@ -42,6 +42,34 @@ def test_fit_matches_reference_init(ctx, bunny, name):
     np.testing.assert_allclose(km.inertia_, float(g[name + "_inertia"]), rtol=1e-12)
 
 
+@pytest.mark.parametrize("name", ["blobs", "bunny"])
+def test_fit_under_a_one_rank_communicator(bunny, name):
+    """A context with a communicator of ONE rank attached (host shared memory): the library's device-resident Lloyd loop
+    takes no communicator, so the fit runs step by step -- and must be the fit of a context without one (same seeds,
+    labels and iteration count, centres to summation-order noise) and the reference's."""
+    import os
+    import hgmm_amd
+    from hgmm_amd.kmeans import KMeans
+    g = load_golden("kmeans_init.npz")
+    X, k = _case(g, name, bunny)
+    plain = hgmm_amd.Context(0)
+    ref = KMeans(n_clusters=k, random_state=1, max_iter=50, n_init=1, ctx=plain).fit(X)
+    plain.close()
+    c = hgmm_amd.Context(0)
+    c.comm_init_host(1, 0, "hgmm_km_w1_%s_%d" % (name, os.getpid()))
+    assert c.comm_attached and c.nranks == 1
+    km = KMeans(n_clusters=k, random_state=1, max_iter=50, n_init=1, ctx=c).fit(X)
+    c.comm_destroy()
+    assert not c.comm_attached
+    c.close()
+    assert np.array_equal(km.init_indices_, ref.init_indices_) and km.n_iter_ == ref.n_iter_
+    assert np.array_equal(km.labels_, ref.labels_)
+    np.testing.assert_allclose(km.cluster_centers_, ref.cluster_centers_, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(km.inertia_, ref.inertia_, rtol=1e-10)
+    assert km.n_iter_ == int(g[name + "_n_iter"]) and np.array_equal(km.labels_, g[name + "_labels"])
+    np.testing.assert_allclose(km.cluster_centers_, g[name + "_centres"], rtol=0, atol=1e-12)
+
+
 def test_relocation_of_empty_clusters(ctx):
     from hgmm_amd.kmeans import KMeans
     g = load_golden("kmeans_init.npz")

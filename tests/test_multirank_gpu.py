@@ -2,8 +2,9 @@
 
   * on ONE GPU the ranks are joined by the host shared-memory communicator (hgmm_comm_init_host -- the same
     all-reduce call sites as RCCL, which does not accept two ranks on one device);
-  * with >= 2 GPUs visible the same comparison runs over RCCL (one rank per GPU, unique id shipped over the
-    package's plain-TCP bootstrap) -- skipped on a single-GPU box.
+  * over RCCL the same comparison runs with one rank per visible GPU (unique id shipped over the package's
+    plain-TCP bootstrap) -- on a single-GPU box with a communicator of one rank; the tests that need two ranks on
+    two GPUs, or eight, skip there.
 
 Every sharded fit must reproduce the single-context fit on the whole cloud: same iteration counts and hard
 labels, parameters equal to summation-order noise."""
@@ -200,12 +201,20 @@ def _ipc_timeout_worker(rank, name, q):
 
 
 def test_configs4_eight_frames_joint_fit_matches_oracle_fixture():
-    """BASELINE configs[4] ITSELF -- 8 frames x 1M points, J = 800, one frame per rank, one joint fit with an all-reduce of
-    the sufficient statistics per iteration -- with the 8 ranks sharing the box's ONE GPU (joined by the one-shot peer
-    exchange: each rank maps the seven other exchange buffers): the data path of the 8-GPU run at full size against
-    oracle.flat_em's float64 EM on the 8M points together (tests/golden/flat_uniform8x1M_J800_oracle.npz,
-    tools/gen_oracle_fixtures.py --only flat8x1m).  All eight ranks must end with bitwise the same model."""
-    _full_frames_joint_fit("ipc", 8)
+    """BASELINE configs[4] ITSELF -- 8 frames x 1M points, J = 800, one joint fit with an all-reduce of the sufficient
+    statistics per iteration -- on the box's ONE GPU, joined by the one-shot peer exchange: the data path of the 8-GPU run
+    at full size against oracle.flat_em's float64 EM on the 8M points together (tests/golden/flat_uniform8x1M_J800_oracle.npz,
+    tools/gen_oracle_fixtures.py --only flat8x1m).  All ranks must end with bitwise the same model.
+    The exchange takes one rank per process, and no more than five processes (pytest included) may hold the GPU at once:
+    four ranks, two frames each (frames r and r + 4).  The eight-rank form of the same fit is the next test."""
+    _full_frames_joint_fit("ipc", 4, frames=8)
+
+
+def test_configs4_eight_ranks_host_communicator_matches_oracle_fixture():
+    """The same fit with one frame per rank: eight ranks on the ONE GPU, as four processes of two ranks each (one thread and
+    one context per rank), joined by the host shared-memory communicator -- the backend that accepts two ranks in one
+    process.  Against the same fixture; all eight ranks must end with bitwise the same model."""
+    _full_frames_joint_fit("host", 8, ranks_per_process=2)
 
 
 @pytest.mark.parametrize("backend", ["ipc", "host"])
@@ -218,17 +227,20 @@ def test_two_full_frames_joint_fit_matches_oracle_fixture(backend):
     _full_frames_joint_fit(backend, 2)
 
 
-def _full_frames_joint_fit(backend, world):
+def _full_frames_joint_fit(backend, world, ranks_per_process=1, frames=None):
+    """`frames` (default: `world`) 1M-point frames dealt round-robin over `world` ranks, one joint fit."""
+    frames = frames or world
     port = _free_port() if backend == "rccl" else None
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "flat_uniform%dx1M_J800_oracle.npz" % world))
-    assert int(g["frames"]) == world
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "flat_uniform%dx1M_J800_oracle.npz" % frames))
+    assert int(g["frames"]) == frames
     name = "hgmm_%dx1m_%s_%d" % (world, backend, os.getpid())
     mpc = mp.get_context("spawn")
     q = mpc.Queue()
-    procs = [mpc.Process(target=_joint_fit_worker, args=(r, name, q, backend, world, port)) for r in range(world)]
+    groups = [list(range(r, min(r + ranks_per_process, world))) for r in range(0, world, ranks_per_process)]
+    procs = [mpc.Process(target=_joint_fit_ranks, args=(ranks, name, q, backend, world, port, frames)) for ranks in groups]
     for p in procs:
         p.start()
-    got = dict(q.get(timeout=300) for _ in procs)
+    got = dict(q.get(timeout=300) for _ in range(world))
     assert not any(isinstance(v, str) for v in got.values()), got
     for p in procs:
         p.join(60)
@@ -248,12 +260,26 @@ def _full_frames_joint_fit(backend, world):
             assert np.array_equal(a, b)
 
 
-def _joint_fit_worker(rank, name, q, backend, world=2, rccl_port=None):
+def _joint_fit_ranks(ranks, name, q, backend, world, rccl_port, frames):
+    """One process: the given ranks, each on a thread of its own (a single rank runs on the process's main thread)."""
+    if len(ranks) == 1:
+        return _joint_fit_worker(ranks[0], name, q, backend, world, rccl_port, frames)
+    import threading
+    import hgmm_amd  # noqa: F401 -- once, before the threads: two threads importing it at once can see it half-initialised
+    threads = [threading.Thread(target=_joint_fit_worker, args=(r, name, q, backend, world, rccl_port, frames)) for r in ranks]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+
+
+def _joint_fit_worker(rank, name, q, backend, world=2, rccl_port=None, frames=None):
     try:
         import hgmm_amd
         N, J = 1_000_000, 800
         frame0 = np.random.RandomState(0).rand(N, 3).astype(np.float32)
-        frame = frame0 if rank == 0 else np.random.RandomState(rank).rand(N, 3).astype(np.float32)
+        mine = list(range(frames or world))[rank::world]           # the frames (seeds) this rank holds
+        frame = np.concatenate([frame0 if f == 0 else np.random.RandomState(f).rand(N, 3).astype(np.float32) for f in mine])
         idx = np.random.RandomState(100).choice(N, J, replace=False)
         mu0 = frame0[idx].copy()
         w0 = (np.ones(J) / J).astype(np.float32)
@@ -318,11 +344,9 @@ def _ipc_collectives_worker(rank, name, q, device=0, world=2):
 
 def test_rccl_ranks_on_all_gpus():
     """Same comparison over RCCL / xGMI, one rank per GPU on min(8, visible GPUs) of them (the driver's 8-GPU node runs
-    world = 8; a 1-GPU box skips): every family's sharded fit against the single-context fit on the whole cloud."""
-    n = _gpu_count()
-    if n < 2:
-        pytest.skip("needs >= 2 GPUs (found %d)" % n)
-    _ranks_match_single_context(_free_port(), backend="rccl", world=min(8, n))
+    world = 8; a 1-GPU box runs world = 1, a communicator of one rank behind the same call sites): every family's
+    sharded fit against the single-context fit on the whole cloud."""
+    _ranks_match_single_context(_free_port(), backend="rccl", world=min(8, _gpu_count()))
 
 
 def test_rccl_two_ranks_two_gpus():
@@ -336,11 +360,9 @@ def test_rccl_two_ranks_two_gpus():
 def test_peer_exchange_ranks_on_all_gpus():
     """The one-shot peer exchange ACROSS min(8, visible GPUs) GPUs (each rank maps every other rank's exchange buffer
     over xGMI through its hipIpc handle): the collectives by themselves, bitwise equal on all ranks and equal to the
-    host's sums in rank order.  Needs two GPUs (the driver's multi-GPU node; a 1-GPU box skips)."""
-    n = _gpu_count()
-    if n < 2:
-        pytest.skip("needs >= 2 GPUs (found %d)" % n)
-    world = min(8, n)
+    host's sums in rank order.  (A 1-GPU box runs world = 1: the exchange kernel with one rank; the two- and three-rank
+    tests above run it with peers on that GPU.)"""
+    world = min(8, _gpu_count())
     name = "hgmm_ipc%d_%d" % (world, os.getpid())
     mpc = mp.get_context("spawn")
     q = mpc.Queue()
@@ -370,7 +392,7 @@ def test_configs4_over_rccl_on_eight_gpus():
     """BASELINE configs[4] AS WRITTEN: 8 frames x 1M points, J = 800, one frame per GPU on 8 x MI355X, the (7 J + 2)
     float64 sufficient statistics all-reduced by RCCL over xGMI before every M-step -- against oracle.flat_em's float64
     EM on the 8M points together (tests/golden/flat_uniform8x1M_J800_oracle.npz).  Skips below 8 GPUs (the 8-ranks-on-
-    one-GPU test above runs the same data path through the peer exchange there)."""
+    one-GPU test above runs the same data path through the host shared-memory communicator there)."""
     n = _gpu_count()
     if n < 8:
         pytest.skip("needs 8 GPUs (found %d)" % n)
@@ -378,11 +400,10 @@ def test_configs4_over_rccl_on_eight_gpus():
 
 
 def test_two_full_frames_over_rccl_on_two_gpus():
-    """configs[4] in small over RCCL: two 1M-point frames on two GPUs against the 2M-point oracle fixture."""
-    n = _gpu_count()
-    if n < 2:
-        pytest.skip("needs >= 2 GPUs (found %d)" % n)
-    _full_frames_joint_fit("rccl", 2)
+    """configs[4] in small over RCCL: two 1M-point frames on two GPUs against the 2M-point oracle fixture.  The frames are
+    dealt over min(2, visible GPUs) ranks, one rank per GPU: a 1-GPU box runs both frames on one rank behind a one-rank
+    RCCL communicator, against the same fixture with the same tolerances."""
+    _full_frames_joint_fit("rccl", min(2, _gpu_count()), frames=2)
 
 
 def _two_ranks_match_single_context(rccl_port, backend="host"):

@@ -121,42 +121,51 @@ def test_voxel_down_sample_properties(bunny):
     np.testing.assert_allclose(one, P.mean(0)[None], rtol=1e-12)
 
 
-REF = "/root/reference"
+SCANS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scans")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout only exists in the build container")
-def test_readers_on_the_reference_s_own_files(bunny):
+def _scan(name, tmp_path):
+    """Path of one of the reference's point-cloud files as it ships (tests/golden/scans/: the PLY files are stored
+    xz-compressed and unpacked here byte for byte)."""
+    if not name.endswith(".ply"):
+        return os.path.join(SCANS, name)
+    import lzma
+    path = os.path.join(str(tmp_path), name)
+    with lzma.open(os.path.join(SCANS, name + ".xz")) as src, open(path, "wb") as dst:
+        dst.write(src.read())
+    return path
+
+
+def test_readers_on_the_reference_s_own_files(bunny, tmp_path):
     """the package's readers on the files the reference ships, against fixtures that were written
     by an independent parse (tools/gen_golden.py: read_ply_vertices / gen_waymo_frames) -- ASCII PLY with a range
-    grid after the vertex block, binary PCD, and the organised binary_compressed (LZF) PCD with NaN holes."""
+    grid after the vertex block, binary PCD, and the organised binary_compressed (LZF) PCD with NaN holes.
+    (The reference ships bunny.pcd three times and waymo1 / waymo2.pcd twice, byte-identical copies: each is kept once.)"""
     from conftest import GOLDEN
     from hgmm_amd.pointcloud_io import read_point_cloud, read_pcd
-    P = read_point_cloud(os.path.join(REF, "data/bun000.ply"))
+    P = read_point_cloud(_scan("bun000.ply", tmp_path))
     assert P.dtype == np.float64 and np.array_equal(P.astype(np.float32), bunny)
-    P45 = read_point_cloud(os.path.join(REF, "data/bun045.ply"))
+    bun045 = _scan("bun045.ply", tmp_path)
+    P45 = read_point_cloud(bun045)
     assert np.array_equal(P45.astype(np.float32), np.load(os.path.join(GOLDEN, "bun045_xyz.npy")))
     # in-test independent parse of the PLY vertex block (header says how many lines to take)
-    lines = open(os.path.join(REF, "data/bun045.ply")).read().split("\n")
+    lines = open(bun045).read().split("\n")
     n_v = int([l for l in lines if l.startswith("element vertex")][0].split()[-1])
     body = lines[lines.index("end_header") + 1:][:n_v]
     raw = np.array([[float(v) for v in l.split()[:3]] for l in body])
     assert np.array_equal(P45, raw)
-    # the three copies of bunny.pcd (512 x 400 organised grid, LZF-compressed, 164544 NaN holes) hold exactly the
-    # vertices of bun000.ply, in the same order
-    for sub in ("gmmreg_gpu", "hgmm", "gmm_waymo/data"):
-        path = os.path.join(REF, "src/python", sub, "bunny.pcd")
-        Q = read_point_cloud(path)
-        assert np.array_equal(Q.astype(np.float32), bunny)
-        full = read_pcd(path, drop_nan=False)
-        assert full.shape == (204800, 3) and int(np.isnan(full).any(axis=1).sum()) == 204800 - 40256
+    # bunny.pcd (512 x 400 organised grid, LZF-compressed, 164544 NaN holes) holds exactly the vertices of bun000.ply,
+    # in the same order
+    path = _scan("bunny.pcd", tmp_path)
+    Q = read_point_cloud(path)
+    assert np.array_equal(Q.astype(np.float32), bunny)
+    full = read_pcd(path, drop_nan=False)
+    assert full.shape == (204800, 3) and int(np.isnan(full).any(axis=1).sum()) == 204800 - 40256
     frames = np.load(os.path.join(GOLDEN, "waymo_frames.npz"))
     for k in (1, 2, 5, 10, 50):
-        W = read_point_cloud(os.path.join(REF, "src/python/gmmreg_gpu/waymo%d.pcd" % k))
+        W = read_point_cloud(_scan("waymo%d.pcd" % k, tmp_path))
         assert W.dtype == np.float64 and np.array_equal(W.astype(np.float32), frames["waymo%d" % k])
-    for k in (1, 2):                                     # the hgmm directory holds copies of two of them
-        W = read_point_cloud(os.path.join(REF, "src/python/hgmm/waymo%d.pcd" % k))
-        assert np.array_equal(W.astype(np.float32), frames["waymo%d" % k])
-    D = read_point_cloud(os.path.join(REF, "src/python/gmm_waymo/data/dragon.ply"))
+    D = read_point_cloud(_scan("dragon.ply", tmp_path))
     assert D.shape == (41841, 3) and np.isfinite(D).all()
 
 

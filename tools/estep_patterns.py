@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-grid breakdown of the materialising E-step's launches in a rocprofv3 kernel trace of `python bench.py`.
+"""Per-grid breakdown of the materialising E-step's launches in a rocprofv3 kernel trace of `python bench.py --full`.
 
     python tools/estep_patterns.py gpurun_out/prof_r03/kt/kt_kernel_trace.csv
 

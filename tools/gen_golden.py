@@ -31,6 +31,42 @@ import numpy as np
 
 REF = "/root/reference"
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+PART_BYTES = 768 << 10       # a committed file stays below 1 MiB: larger fixtures are written in parts (save_golden)
+
+
+def save_golden(name, **arrays):
+    """np.savez_compressed(OUT/name, **arrays) -- or, when the arrays hold more than PART_BYTES, OUT/<stem>.part<i>.npz
+    files of at most PART_BYTES of array data each, an array larger than that cut along its first axis into pieces
+    <key>@<j>.  tests/conftest.py's load_golden(name) puts the parts back together."""
+    stem = name[:-len(".npz")]
+    for i in range(1000):
+        part = os.path.join(OUT, "%s.part%d.npz" % (stem, i))
+        if not os.path.exists(part):
+            break
+        os.remove(part)
+    if os.path.exists(os.path.join(OUT, name)):
+        os.remove(os.path.join(OUT, name))
+    arrays = {k: np.asarray(a) for k, a in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) <= PART_BYTES:
+        np.savez_compressed(os.path.join(OUT, name), **arrays)
+        return
+    items = []
+    for k, a in arrays.items():
+        if a.nbytes > PART_BYTES:
+            rows = max(1, PART_BYTES // a[:1].nbytes)
+            items += [("%s@%d" % (k, j), a[s:s + rows]) for j, s in enumerate(range(0, len(a), rows))]
+        else:
+            items.append((k, a))
+    parts, cur, size = [], {}, 0
+    for k, a in items:
+        if cur and size + a.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = a
+        size += a.nbytes
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(OUT, "%s.part%d.npz" % (stem, i)), **p)
 
 
 # ---------------------------------------------------------------------------
@@ -186,7 +222,7 @@ def gen_flat_bunny(W, G, pts, flavours=(("W", "diag"),)):
                 out[tag + "_noise_max_abs_dresp"] = np.float64(np.abs(np.exp(lr32.astype(np.float64)) - r64).max())
             out["predict"] = mod.predict(X, inv, mu, w, **kw).astype(np.uint16)
             name = "flat_bunny_J%d.npz" % J if base else "flat_bunny_J%d_%s_%s.npz" % (J, variant, cov_type)
-            np.savez_compressed(os.path.join(OUT, name), **out)
+            save_golden(name, **out)
             print(name, "lls[-1]", lls[-1], "fp32-vs-fp64 noise", out["final_noise_max_abs_dresp"])
 
 
