@@ -512,6 +512,7 @@ class Context:
         self._scalar_dev = None
         self._scalar_next = 0
         self._scalar_owner = [None] * 64
+        self._forest_LT = None                # (L, T) of the resident forest (tree_build_batch); tree_get_nodes_batch checks it
 
     # -- plumbing ---------------------------------------------------------------------
     def _check(self, rc):
@@ -1036,14 +1037,22 @@ class Context:
         qcap = int(q_capacity or L * min(max_iters_per_level, 4096)) if want_trace else 0
         q = np.zeros((B, qcap)) if want_trace else None
         qlen = np.zeros(B, np.int32) if want_trace else None
+        self._forest_LT = None
         self._check(self.lib.hgmm_tree_build_batch(self.h, B, cnt, int(L), float(ls), float(ld), _ptr(init_mu), float(sig2),
                                                    int(max_iters_per_level), _ptr(pi), _ptr(mu), _ptr(cov), _ptr(iters),
                                                    _ptr(q), qcap, _ptr(qlen)))
+        self._forest_LT = (int(L), T)             # (the node tables hgmm_tree_get_nodes_batch copies out are [T] long)
         traces = [q[b, :qlen[b]].copy() for b in range(B)] if want_trace else None
         return (pi, mu, cov), iters, traces
 
     def tree_get_nodes_batch(self, b, L):
-        T = 8 * (8 ** L - 1) // 7
+        """Node tables of tree b of the resident forest; L must be the depth it was built with."""
+        forest = self._forest_LT
+        if forest is None:
+            raise HgmmError("tree_get_nodes_batch: no forest built on this context")
+        if int(L) != forest[0]:
+            raise ValueError("tree_get_nodes_batch: the resident forest has L = %d, not %d" % (forest[0], int(L)))
+        T = forest[1]
         pi, mu, cov = np.empty(T), np.empty((T, 3)), np.empty((T, 3, 3))
         self._check(self.lib.hgmm_tree_get_nodes_batch(self.h, int(b), _ptr(pi), _ptr(mu), _ptr(cov)))
         return pi, mu, cov

@@ -342,3 +342,80 @@ def register(target, pi, mu, cov, max_level, lc=0.01, maxiter=20, tol=1.0e-4):
             break
         q_prev = q
     return rot.T, -rot.T @ t, q, trace
+
+
+# ---------------------------------------------------------------------------
+# test helpers for deep trees (nothing above depends on them)
+# ---------------------------------------------------------------------------
+
+RegDescent = namedtuple('RegDescent', ['node', 'contrib', 'gap', 'den_margin', 'gamma_margin', 'cplx_margin'])
+
+
+def reg_descent(points, pi, mu, cov, max_level, lc):
+    """The decisions of :func:`reg_e_step`, per target point and level, with the margins that decide them.
+
+    All arrays are [N, max_level]; entries of levels a point does not reach (it stopped above) are -1 / False / inf.
+      node         the child the point moves to (j0 + argmax gamma; j0 itself when den <= EPS)
+      contrib      whether that (point, node) pair adds to the moments (not stopped, gamma >= EPS)
+      gap          (g_max - g_second) / g_max of the eight children (inf when den <= EPS: the first child is forced)
+      den_margin   |den - EPS| / EPS            (which side of the normaliser test)
+      gamma_margin |gamma_chosen - EPS| / EPS   (inf where the point stops: gamma is not used there)
+      cplx_margin  |complexity(cov_node) - lc| / lc
+    A small margin means that a different but equally valid rounding can take the other branch."""
+    points = np.asarray(points, dtype=np.float64)
+    n = len(points)
+    ok, inv, coef = node_prep(cov)
+    cplx = complexity(cov)
+    shape = (n, max_level)
+    node = -np.ones(shape, dtype=np.int64)
+    contrib = np.zeros(shape, dtype=bool)
+    gap, den_m, gam_m, cplx_m = (np.full(shape, np.inf) for _ in range(4))
+    search = -np.ones(n, dtype=np.int64)
+    alive = np.ones(n, dtype=bool)
+    for l in range(max_level):
+        idx = np.nonzero(alive)[0]
+        if len(idx) == 0:
+            break
+        x = points[idx]
+        j0 = child(search[idx])
+        kid = j0[:, None] + np.arange(N_NODE)[None, :]
+        g = pi[kid] * pdf_pairs(x[:, None, :], mu[kid], inv[kid], coef[kid])
+        den = g.sum(axis=1)
+        good = den > EPS
+        gamma = np.where(good[:, None], g / np.where(good, den, 1.0)[:, None], 0.0)
+        am = np.argmax(gamma, axis=1)
+        s = j0 + am
+        top2 = np.sort(g, axis=1)[:, -2:]
+        gap[idx, l] = np.where(good, (top2[:, 1] - top2[:, 0]) / np.where(good, top2[:, 1], 1.0), np.inf)
+        den_m[idx, l] = np.abs(den - EPS) / EPS
+        cplx_m[idx, l] = np.abs(cplx[s] - lc) / lc
+        node[idx, l] = s
+        search[idx] = s
+        stop = cplx[s] <= lc
+        gs = gamma[np.arange(len(idx)), am]
+        gam_m[idx, l] = np.where(stop, np.inf, np.abs(gs - EPS) / EPS)
+        contrib[idx, l] = ~stop & ~(gs < EPS)
+        alive[idx[stop]] = False
+    return RegDescent(node, contrib, gap, den_m, gam_m, cplx_m)
+
+
+def reg_near_ties(desc, rel=1e-9):
+    """[N] bool: the points whose descent (:func:`reg_descent`) has a margin below ``rel`` at some level."""
+    m = np.minimum(np.minimum(desc.gap, desc.den_margin), np.minimum(desc.gamma_margin, desc.cplx_margin))
+    return (m < rel).any(axis=1)
+
+
+def reg_normal_equations(m0, m1, mu, cov):
+    """A^T A [6,6], A^T b [6], b^T b and the stacked (A, b) of :func:`reg_m_step`'s least-squares system, built with one
+    batched ``eigh`` over the nodes with m0 >= float32 eps instead of a Python loop over all T nodes (the rows of nodes
+    without mass are zero in reg_m_step and are left out here)."""
+    live = np.nonzero(~(m0 < F32_EPS))[0]
+    lam, vec = np.linalg.eigh(cov[live])
+    s = m1[live] / m0[live][:, None]
+    nT = np.transpose(vec * np.sqrt(m0[live][:, None] / lam)[:, None, :], (0, 2, 1))     # rows: scaled eigenvectors
+    A = np.empty((len(live), 3, 6))
+    A[:, :, :3] = np.cross(s[:, None, :], nT)
+    A[:, :, 3:] = nT
+    b = np.einsum('nij,nj->ni', nT, mu[live]) - np.einsum('nij,nj->ni', nT, s)
+    A, b = A.reshape(-1, 6), b.reshape(-1)
+    return A.T @ A, A.T @ b, float(b @ b), A, b

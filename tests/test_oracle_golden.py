@@ -103,6 +103,48 @@ def test_hgmm_registration_matches_reference():
         np.testing.assert_allclose(q, g[tag + "final_q"], rtol=1e-6)
 
 
+def test_hgmm_L4_build_and_registration_match_reference():
+    """L = 4 (4680 nodes): the reference's own build on bun000[::8], its registration E-step moments for two rotations
+    and its 5-iteration registration trace (tests/golden/hgmm_reg_L4.part*.npz, tools/gen_golden.py --only reg4).  Level 3
+    (nodes >= 584) is reached by the descent, so the oracle is pinned where the library's deep registration path runs."""
+    g = load_golden("hgmm_reg_L4.npz")
+    P, L, lc = g["points"], int(g["L"]), float(g["lambda_c"])
+    pi, mu, cov, tr = hgmm_tree.build_tree(P, L, float(g["ls"]), float(g["ld"]), g["init_idx"], float(g["sig2"]))
+    assert list(tr.iters_per_level) == list(g["iters_per_level"])
+    np.testing.assert_allclose(tr.q, g["q_trace"], rtol=1e-9, atol=1e-6)
+    for l in range(L):
+        assert np.array_equal(tr.current_idx_per_level[l], g["current_idx_L%d" % l])
+    np.testing.assert_allclose(pi, g["pi"], rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(mu, g["mu"], rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(cov, g["cov"], rtol=1e-7, atol=1e-13)
+    pi, mu, cov = g["pi"], g["mu"], g["cov"]
+    for deg in (10, 30):
+        tag = "rot%d_" % deg
+        target = g[tag + "target"]
+        desc = hgmm_tree.reg_descent(target, pi, mu, cov, L, lc)
+        assert (desc.contrib & (desc.node >= hgmm_tree.level(3))).sum() > 500
+        m0, m1, m2 = hgmm_tree.reg_e_step(target, pi, mu, cov, L, lc)
+        np.testing.assert_allclose(m0, g[tag + "m0"], rtol=1e-9, atol=1e-12)
+        np.testing.assert_allclose(m1, g[tag + "m1"], rtol=1e-9, atol=1e-12)
+        np.testing.assert_allclose(m2, g[tag + "m2"], rtol=1e-9, atol=1e-12)
+        # the vectorised normal equations == the system of reg_m_step's loop
+        ata, atb, btb, A, b = hgmm_tree.reg_normal_equations(m0, m1, mu, cov)
+        x_ref = np.linalg.lstsq(A, b, rcond=-1)[0]
+        rot1, t1, _ = hgmm_tree.reg_m_step(m0, m1, m2, mu, cov, np.identity(3), np.zeros(3))
+        r_x, t_x = hgmm_tree.twist_mul(x_ref, np.identity(3), np.zeros(3))
+        np.testing.assert_allclose(r_x, rot1, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(t_x, t1, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(np.linalg.solve(ata, atb), x_ref, rtol=0, atol=1e-9)
+        rot, t, q, trace = hgmm_tree.register(target, pi, mu, cov, L, lc, maxiter=5, tol=1e-4)
+        assert len(trace) == len(g[tag + "iter_rot"])
+        for k, (r_k, t_k, _, _, _, _) in enumerate(trace):
+            np.testing.assert_allclose(r_k.T, g[tag + "iter_rot"][k], rtol=0, atol=1e-8)
+            np.testing.assert_allclose(-r_k.T @ t_k, g[tag + "iter_t"][k], rtol=0, atol=1e-8)
+        np.testing.assert_allclose(rot, g[tag + "final_rot"], rtol=0, atol=1e-8)
+        np.testing.assert_allclose(t, g[tag + "final_t"], rtol=0, atol=1e-8)
+        np.testing.assert_allclose(q, g[tag + "final_q"], rtol=1e-6)
+
+
 def test_fullcov_flat_matches_reference():
     """Flat full-covariance EM == one tree level with branching J."""
     g = load_golden("fullcov_flat.npz")

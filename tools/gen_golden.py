@@ -7,7 +7,7 @@ modules for packages this image lacks and that the EM path does not actually use
 (cupy -> NumPy array module, open3d, transformations); nothing from the reference
 is written into this repository -- the fixtures hold only inputs and outputs.
 
-    python tools/gen_golden.py [--only flat|bunny|hgmm|hgmm3|reg|fullcov|gmmreg]
+    python tools/gen_golden.py [--only flat|bunny|hgmm|hgmm3|reg|reg4|fullcov|gmmreg]
 
 Outputs (all small .npz, float arrays):
     bun000_xyz.npy                vertex block of data/bun000.ply (reference data file)
@@ -16,6 +16,7 @@ Outputs (all small .npz, float arrays):
     hgmm_build_L2.npz             CPU twin buildGMMTree on bun000[::20], L=2
     hgmm_build_L3.npz             same on bun000[::40], L=3
     hgmm_reg_L2.npz               gmmTreeRegESTep moments + GMMTree.registration trace
+    hgmm_reg_L4.part*.npz         CPU twin buildGMMTree on bun000[::8], L=4, then the same records as hgmm_reg_L2
     fullcov_flat.npz              CPU twin with n_node=J, one level (flat full-cov EM)
     gmmreg_l2.npz                 L2 GMMReg: d_rot, Gauss transform, cost/gradient, one registration
 """
@@ -300,12 +301,13 @@ def gen_hgmm_build(ns, cp, pts, L, stride, name):
     return nodes, P
 
 
-def gen_hgmm_reg(ns, cp, nodes, P, L):
+def gen_hgmm_reg(ns, cp, nodes, P, L, name="hgmm_reg_L2.npz", extra=None):
     import warnings
     warnings.simplefilter("ignore")
     lc = 0.01
     pi, mu, cov = nodes_to_arrays(nodes)
     out = {"points": P, "L": np.int32(L), "lambda_c": np.float64(lc), "pi": pi, "mu": mu, "cov": cov}
+    out.update(extra or {})
     for deg in (10, 30):
         th = np.deg2rad(float(deg))
         Rz = np.array([[np.cos(th), -np.sin(th), 0], [np.sin(th), np.cos(th), 0], [0, 0, 1.0]])
@@ -330,7 +332,66 @@ def gen_hgmm_reg(ns, cp, nodes, P, L):
         out[tag + "final_t"] = np.array(res.transformation.t)
         out[tag + "final_q"] = np.asarray(res.q, dtype=np.float64)
         print("reg", deg, "iters", len(trace), "q", res.q)
-    np.savez_compressed(os.path.join(OUT, "hgmm_reg_L2.npz"), **out)
+    if name == "hgmm_reg_L2.npz":
+        np.savez_compressed(os.path.join(OUT, name), **out)
+    else:
+        save_golden(name, **out)
+
+
+@contextlib.contextmanager
+def chunked_loglik(ns, workers=8):
+    """The CPU twin's logLikelihoodValue is a pure-Python loop over (point, node) pairs: at L = 4 the last level has 4096
+    nodes, minutes per call.  It is a sum over points, so this runs the reference's own function on ``workers`` slices of
+    the points in forked processes and adds the slices' q in slice order (a different summation order than one pass:
+    ~1e-16 relative, far below the build's stop threshold ls = 80)."""
+    import multiprocessing as mp
+    orig = ns["logLikelihoodValue"]
+    ctx = mp.get_context("fork")
+
+    def ll(nodes, data, j0, j1):
+        if len(data) < 4 * workers:
+            return orig(nodes, data, j0, j1)
+        cuts = np.linspace(0, len(data), workers + 1).astype(int)
+        _LL_STATE.update(ll=orig, nodes=nodes)      # (read by the forked workers)
+        with ctx.Pool(workers) as pool:
+            parts = pool.map(_ll_slice, [(data[a:b], j0, j1) for a, b in zip(cuts[:-1], cuts[1:])])
+        q = 0.0
+        for v in parts:
+            q = q + v
+        return q
+    ns["logLikelihoodValue"] = ll
+    try:
+        yield
+    finally:
+        ns["logLikelihoodValue"] = orig
+
+
+_LL_STATE = {}
+
+
+def _ll_slice(args):
+    data, j0, j1 = args
+    return _LL_STATE["ll"](_LL_STATE["nodes"], data, j0, j1)
+
+
+def gen_hgmm_reg4(ns, cp, pts):
+    """L = 4 (4680 nodes): the CPU twin's own build, then its registration E-step and a 5-iteration registration.  The
+    build draws the initial means as points[randint(nTotal)], so it needs at least nTotal = 4680 points: bun000[::8]
+    (5032).  Levels 0-3 of the tree are all reached, and level 3 (nodes 584 ..) is where the deep registration path of the
+    library starts."""
+    import warnings
+    warnings.simplefilter("ignore")
+    L, ls, ld = 4, 80.0, 1.0e-4
+    P = np.ascontiguousarray(pts[::8])
+    with chunked_loglik(ns):
+        nodes, idxs, qs, iters, cur_levels = run_build(ns, cp, P, L, ls, ld)
+    extra = {"ls": np.float64(ls), "ld": np.float64(ld), "sig2": np.float64(0.00034), "init_idx": idxs.astype(np.int32),
+             "q_trace": qs, "iters_per_level": iters}
+    for l, c in enumerate(cur_levels):
+        extra["current_idx_L%d" % l] = c
+    pi = nodes_to_arrays(nodes)[0]
+    print("hgmm L4 build: N", len(P), "iters", iters, "q_last", qs[-1], "dead nodes", int((pi == 0).sum()))
+    gen_hgmm_reg(ns, cp, nodes, P, L, name="hgmm_reg_L4.npz", extra=extra)
 
 
 def gen_fullcov(ns, cp, pts):
@@ -535,7 +596,7 @@ def main():
         gen_kmeans(G, pts)
     if want("gmmreg"):
         gen_gmmreg(pts)
-    if want("hgmm") or want("reg") or want("hgmm3") or want("fullcov"):
+    if want("hgmm") or want("reg") or want("reg4") or want("hgmm3") or want("fullcov"):
         ns = load_cpu_twin(cp)
         if want("hgmm") or want("reg"):
             nodes, P = gen_hgmm_build(ns, cp, pts, 2, 20, "hgmm_build_L2.npz")
@@ -545,6 +606,8 @@ def main():
             gen_fullcov(ns, cp, pts)
         if want("hgmm3"):
             gen_hgmm_build(ns, cp, pts, 3, 40, "hgmm_build_L3.npz")
+        if want("reg4"):
+            gen_hgmm_reg4(ns, cp, pts)
 
 
 if __name__ == "__main__":
