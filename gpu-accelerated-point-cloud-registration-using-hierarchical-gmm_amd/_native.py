@@ -20,7 +20,10 @@ COV_TYPES = {"diag": 0, "spherical": 1}
 VARIANTS = {"W": 0, "G": 1}
 KERNEL_IDS = {"flat_estep": 0, "flat_fused": 1, "flat_mstep": 2, "tree_estep": 3,
               "tree_loglik": 4, "tree_reg": 5, "util_fill": 6, "full_pass": 7, "full_moments": 8,
-              "kmeans_assign": 9, "kmeans_accum": 10, "allreduce": 11, "full_fused": 12}
+              "kmeans_assign": 9, "kmeans_accum": 10, "allreduce": 11, "full_fused": 12, "tree_score": 13}
+# default inlier bound of the tree score: the 0.99 quantile of chi-square with three degrees of freedom (the squared
+# Mahalanobis distance of a point drawn from its own Gaussian)
+CHI2_3_99 = 11.344866730144373
 
 
 class HgmmError(RuntimeError):
@@ -150,6 +153,8 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_set_targets_batch_f32", [ctx, C.c_int, C.POINTER(_vp), _i64p])
         _sig(lib, "hgmm_tree_register_batch", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
                                                _vp, _vp, _vp])
+        _sig(lib, "hgmm_tree_score", [ctx, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp])
+        _sig(lib, "hgmm_tree_score_batch", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp])
         _lib = lib
         return lib
 
@@ -512,6 +517,8 @@ class Context:
         self._scalar_dev = None
         self._scalar_next = 0
         self._scalar_owner = [None] * 64
+        self._tgt_n = None                    # points of the resident registration target (tree_set_target)
+        self._tgt_B = None                    # targets of the resident batch (tree_set_targets_batch)
         self._forest_LT = None                # (L, T) of the resident forest (tree_build_batch); tree_get_nodes_batch checks it
 
     # -- plumbing ---------------------------------------------------------------------
@@ -955,6 +962,7 @@ class Context:
         if t.ndim != 2 or t.shape[1] != 3:
             raise ValueError("target must be [M,3]")
         self._check(self.lib.hgmm_tree_set_target(self.h, _ptr(t), t.shape[0]))
+        self._tgt_n = int(t.shape[0])
 
     def tree_reg_estep(self, T, rot=None, t=None, scale=1.0, lambda_c=0.01):
         rot = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3, 3)
@@ -1060,7 +1068,9 @@ class Context:
     def tree_set_targets_batch(self, targets):
         arrs, ptrs, counts, all32 = self._cloud_list(targets, "tree_set_targets_batch")
         entry = self.lib.hgmm_tree_set_targets_batch_f32 if all32 else self.lib.hgmm_tree_set_targets_batch
+        self._tgt_B = None
         self._check(entry(self.h, len(arrs), ptrs, counts))
+        self._tgt_B = len(arrs)
         return arrs
 
     def tree_register_batch(self, rot, t, scale=1.0, lambda_c=0.01, max_iter=20, tol=1.0e-4, q_prev=None, want_trace=False):
@@ -1078,6 +1088,48 @@ class Context:
                                                       _ptr(trace)))
         traces = [trace[b, :iters[b]] for b in range(B)] if want_trace else None
         return rot, t, iters, q, status, traces
+
+    def tree_score(self, rot=None, t=None, scale=1.0, lambda_c=0.01, maha2_max=CHI2_3_99, want=("node", "maha2", "logp")):
+        """Score of the resident target, moved by ``y = scale * rot @ x + t``, against the resident tree (hgmm_tree_score):
+        every point descends as in the registration E-step and is scored at the last node it reaches (``lambda_c < 0``: always
+        a node of the last level).  -> (summary[8], {name: array for name in want}) with ``node`` int32 [n], ``maha2`` and
+        ``logp`` float64 [n]; the summary's slots are described in include/hgmm.h.  The arrays are sized by the target this
+        context uploaded, never by an argument."""
+        want = tuple(want)
+        for w in want:
+            if w not in ("node", "maha2", "logp"):
+                raise ValueError("tree_score: unknown output %r" % (w,))
+        n = self._tgt_n
+        if n is None:
+            raise HgmmError("tree_score: no target resident (call tree_set_target first)")
+        rot = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3, 3)
+        t = None if t is None else np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        node = np.empty(n, np.int32) if "node" in want else None
+        maha2 = np.empty(n) if "maha2" in want else None
+        logp = np.empty(n) if "logp" in want else None
+        summary = np.empty(8)
+        self._check(self.lib.hgmm_tree_score(self.h, _ptr(rot), _ptr(t), float(scale), float(lambda_c), float(maha2_max),
+                                             _ptr(node), _ptr(maha2), _ptr(logp), _ptr(summary)))
+        arrays = {"node": node, "maha2": maha2, "logp": logp}
+        return summary, {k: arrays[k] for k in want}
+
+    def tree_score_batch(self, rot=None, t=None, scale=1.0, lambda_c=0.01, maha2_max=CHI2_3_99):
+        """:meth:`tree_score`'s summary for every (tree b, target b) pair of the resident forest in one launch
+        (hgmm_tree_score_batch), each bitwise the serial call's on that pair.  ``rot`` [B,3,3], ``t`` [B,3] (None: identity).
+        -> summaries [B,8].  B is the number of targets this context uploaded."""
+        B = self._tgt_B or 0
+        if rot is not None:
+            rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 3, 3)
+            if B and rot.shape[0] != B:
+                raise ValueError("tree_score_batch: %d poses for %d resident targets" % (rot.shape[0], B))
+        if t is not None:
+            t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3)
+            if B and t.shape[0] != B:
+                raise ValueError("tree_score_batch: %d translations for %d resident targets" % (t.shape[0], B))
+        summary = np.empty((max(B, 1), 8))
+        self._check(self.lib.hgmm_tree_score_batch(self.h, B, _ptr(rot) if B else None, _ptr(t) if B else None, float(scale),
+                                                   float(lambda_c), float(maha2_max), _ptr(summary)))
+        return summary[:B]
 
     @staticmethod
     def _node_tables(pi, mu, cov):

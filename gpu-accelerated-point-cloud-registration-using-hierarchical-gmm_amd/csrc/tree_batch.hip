@@ -261,6 +261,31 @@ __global__ __launch_bounds__(CH) void forest_reg_estep_kernel(const double* __re
                              fix_scale, momq + (size_t)NMQ * T * b, lds);
 }
 
+// the score of every pair (tree_score_body), pair b's workgroups starting at the pair's first point as in the kernel above --
+// the serial call's grouping, so its shares and its summary are the serial call's bit for bit.  Reads the pose and the
+// target's place from the pairs table, NOT `active`: every pair is scored.  partial: [B][gx][6]
+__global__ __launch_bounds__(CH) void forest_score_kernel(const double* __restrict__ tg, int64_t tg_pad,
+                                                          const ForestRegPair* __restrict__ tab,
+                                                          const double* __restrict__ prep, int T, int L, double lambda_c,
+                                                          double maha2_max, double* __restrict__ partial, int gx) {
+    const int item = (int)blockIdx.x;
+    const int b = item / gx, bx = item - b * gx;
+    const ForestRegPair* pr = tab + b;
+    const int first = pr->tg_first, count = pr->tg_count;
+    if ((int64_t)bx * CH >= count) return;
+    const Rigid tf = pr->tf;
+    const int64_t li = (int64_t)bx * CH + threadIdx.x;
+    tree_score_body(first + li, li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, maha2_max,
+                    nullptr, nullptr, nullptr, partial + (size_t)SCORE_NSUM * item);
+}
+__global__ __launch_bounds__(CH) void forest_score_finish_kernel(const double* __restrict__ partial,
+                                                                 const ForestRegPair* __restrict__ tab, int gx,
+                                                                 double* __restrict__ summary) {
+    const int b = blockIdx.x;
+    const int count = tab[b].tg_count;
+    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * b, (count + CH - 1) / CH, (double)count, summary + 8 * b);
+}
+
 __global__ __launch_bounds__(256) void forest_reg_normal_kernel(unsigned long long* __restrict__ momq,
                                                                 const ForestRegPair* __restrict__ tab,
                                                                 const double* __restrict__ prep, int T,
@@ -897,5 +922,50 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
             }
         }
     }
+    return HGMM_OK;
+}
+
+// hgmm_tree_score on every pair (tree b, target b) of the resident forest, summaries only: include/hgmm.h
+extern "C" int hgmm_tree_score_batch(hgmm_ctx* c, int B, const double* rot, const double* t, double scale, double lambda_c,
+                                     double maha2_max, double* summary_out) {
+    HGMM_ENTER(c);
+    if (!summary_out) return fail(c, HGMM_ERR_ARG, "tree_score (batch): summary_out is NULL");
+    if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "tree_score (batch): maha2_max is NaN");
+    if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "tree_score (batch): independent pairs take no communicator");
+    ForestState& F = c->forest;
+    if (!F.nodes_ready) return fail(c, HGMM_ERR_STATE, "tree_score (batch): no forest (hgmm_tree_build_batch first)");
+    if (B != F.B || B != F.tg_B)
+        return fail(c, HGMM_ERR_STATE, "tree_score (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
+    const int T = F.T, L = F.L;
+    ForestRegPair* d_tab = c->fr_reg.as<ForestRegPair>();          // (sized for B pairs by hgmm_tree_set_targets_batch)
+    std::vector<ForestRegPair> tab(B);
+    int64_t longest = 0;
+    for (int b = 0; b < B; ++b) {
+        ForestRegPair& pr = tab[b];
+        std::memset(&pr, 0, sizeof pr);
+        pr.tg_first = (int)F.tg_first[b];
+        pr.tg_count = (int)F.tg_counts[b];
+        for (int i = 0; i < 9; ++i) pr.tf.r[i] = rot ? rot[9 * b + i] : ((i % 4 == 0) ? 1.0 : 0.0);
+        for (int i = 0; i < 3; ++i) pr.tf.t[i] = t ? t[3 * b + i] : 0.0;
+        pr.tf.s = scale;
+        longest = std::max(longest, F.tg_counts[b]);
+    }
+    const unsigned gx = nblk(longest, CH);
+    HGMM_TRY(ensure(c, c->scratch, sizeof(double) * ((size_t)SCORE_NSUM * gx + 8) * B));
+    double* partial = c->scratch.as<double>();
+    double* d_sum = partial + (size_t)SCORE_NSUM * gx * B;
+    void* st = nullptr;
+    HGMM_TRY(stage_reserve(c, sizeof(ForestRegPair) * B, &st));
+    std::memcpy(st, tab.data(), sizeof(ForestRegPair) * B);
+    HGMM_HIP(c, hipMemcpyAsync(d_tab, st, sizeof(ForestRegPair) * B, hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope prof(c, HGMM_K_TREE_SCORE);
+        forest_score_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(c->fr_tg.as<double>(), F.tg_pad, d_tab, c->fr_prep.as<double>(),
+                                                                   T, L, lambda_c, maha2_max, partial, (int)gx);
+    }
+    forest_score_finish_kernel<<<B, CH, 0, c->stream>>>(partial, d_tab, (int)gx, d_sum);
+    HGMM_HIP(c, hipGetLastError());
+    HGMM_HIP(c, hipMemcpyAsync(summary_out, d_sum, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
     return HGMM_OK;
 }

@@ -1438,6 +1438,55 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {          // exa
     return (long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned int)lo);
 }
 
+// y = s R x + t of the registration E-step and of the score
+// (explicit fused operations: the serial and the batched kernel must round alike whatever the compiler would pick)
+__device__ __forceinline__ void rigid_apply(const Rigid& tf, const double a, const double b, const double c, double& x0,
+                                            double& x1, double& x2) {
+    x0 = fma(tf.s, fma(tf.r[2], c, fma(tf.r[1], b, tf.r[0] * a)), tf.t[0]);
+    x1 = fma(tf.s, fma(tf.r[5], c, fma(tf.r[4], b, tf.r[3] * a)), tf.t[1]);
+    x2 = fma(tf.s, fma(tf.r[8], c, fma(tf.r[7], b, tf.r[6] * a)), tf.t[2]);
+}
+
+// One level of the registration descent for one point y = (x0, x1, x2): among the eight children j0 .. j0 + 7 the
+// first maximum of g_k = pi_k N(y; k), or the first child when their sum is <= eps (C:178-187).  Returns the child;
+// best = its responsibility g / sum (0 when the sum is <= eps).  tree_reg_estep_body and tree_score_body both call
+// this, so that a point takes the same branch in both for the same bits.
+__device__ __forceinline__ int64_t reg_descend_level(const double x0, const double x1, const double x2,
+                                                     const double* __restrict__ prep, const int64_t j0,
+                                                     const double* __restrict__ exp_tab, double& best) {
+    double g[8];
+    double den = 0.0;
+    // (round 6: the build E-step's arithmetic -- two interleaved table exponentials of four instead of eight
+    //  library calls -- and ONE division: only the largest responsibility is used, and g_k / den is monotone in g_k)
+    double yv[8], wE[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const double* pr = prep + PREP_N * (j0 + k);
+        const double d0 = x0 - pr[6], d1 = x1 - pr[7], d2 = x2 - pr[8];
+        yv[k] = -0.5 * sym3_quad(pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], d0, d1, d2);
+        wE[k] = pr[9];
+    }
+    const double ya[4] = {yv[0], yv[1], yv[2], yv[3]}, yb[4] = {yv[4], yv[5], yv[6], yv[7]};
+    double ea[4], eb[4];
+    exp_nonpos4(ya, ea, exp_tab);
+    exp_nonpos4(yb, eb, exp_tab);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const double ev = k < 4 ? ea[k & 3] : eb[k & 3];
+        g[k] = (wE[k] == 0.0 || yv[k] < -745.0) ? 0.0 : wE[k] * ev;     // (below the range the library exp is exactly 0)
+        den += g[k];
+    }
+    const bool good = den > TREE_EPS;
+    int am = 0;
+    double gbest = -1.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (g[k] > gbest) { gbest = g[k]; am = k; }                     // first maximum (C:187 argmax)
+    if (!good) am = 0;                                                  // all responsibilities are 0: the first child
+    best = good ? gbest / den : 0.0;
+    return j0 + am;
+}
+
 // (i: the thread's target point in `tg`, alive: it exists; prep / momq: the node table and the sums of THIS tree)
 constexpr int REG_LDS_NODES = 584;                       // levels 0..2 (8 + 64 + 512 nodes)
 template <int NMQ>
@@ -1452,54 +1501,17 @@ __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive,
     for (int e = threadIdx.x; e < lds_nodes * NMQ; e += CH) tab[e] = 0ull;
     __syncthreads();
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
-    if (alive) {
-        const double a = tg[i], b = tg[n_pad + i], c = tg[2 * n_pad + i];
-        // (explicit fused operations: the serial and the batched kernel must round alike whatever the compiler would pick)
-        x0 = fma(tf.s, fma(tf.r[2], c, fma(tf.r[1], b, tf.r[0] * a)), tf.t[0]);
-        x1 = fma(tf.s, fma(tf.r[5], c, fma(tf.r[4], b, tf.r[3] * a)), tf.t[1]);
-        x2 = fma(tf.s, fma(tf.r[8], c, fma(tf.r[7], b, tf.r[6] * a)), tf.t[2]);
-    }
+    if (alive) rigid_apply(tf, tg[i], tg[n_pad + i], tg[2 * n_pad + i], x0, x1, x2);
     int64_t search = -1;
     for (int l = 0; l < L; ++l) {
         if (!__any(alive)) break;
         const int64_t j0 = 8 * (search + 1);
-        double g[8];
-        double den = 0.0;
-        if (alive) {
-            // (round 6: the build E-step's arithmetic -- two interleaved table exponentials of four instead of eight
-            //  library calls -- and ONE division: only the largest responsibility is used, and g_k / den is monotone in g_k)
-            double yv[8], wE[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const double* pr = prep + PREP_N * (j0 + k);
-                const double d0 = x0 - pr[6], d1 = x1 - pr[7], d2 = x2 - pr[8];
-                yv[k] = -0.5 * sym3_quad(pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], d0, d1, d2);
-                wE[k] = pr[9];
-            }
-            const double ya[4] = {yv[0], yv[1], yv[2], yv[3]}, yb[4] = {yv[4], yv[5], yv[6], yv[7]};
-            double ea[4], eb[4];
-            exp_nonpos4(ya, ea, exp_tab);
-            exp_nonpos4(yb, eb, exp_tab);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const double ev = k < 4 ? ea[k & 3] : eb[k & 3];
-                g[k] = (wE[k] == 0.0 || yv[k] < -745.0) ? 0.0 : wE[k] * ev;     // (below the range the library exp is exactly 0)
-                den += g[k];
-            }
-        }
         double gs = 0.0;
         int64_t s = 0;
         bool contribute = false;
         if (alive) {
-            const bool good = den > TREE_EPS;
-            int am = 0;
-            double gbest = -1.0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (g[k] > gbest) { gbest = g[k]; am = k; }                     // first maximum (C:187 argmax)
-            if (!good) am = 0;                                                  // all responsibilities are 0: the first child
-            const double best = good ? gbest / den : 0.0;
-            s = j0 + am;
+            double best;
+            s = reg_descend_level(x0, x1, x2, prep, j0, exp_tab, best);
             search = s;
             if (prep[PREP_N * s + 11] <= lambda_c) {       // complexity(cov_s) <= lambda_c: stop
                 alive = false;
@@ -1542,6 +1554,105 @@ __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive,
         const unsigned long long v = tab[e];
         if (v != 0ull) atomicAdd(momq + e, v);
     }
+}
+
+
+// ------------------------------------------------------------------------------------------
+// score of a moved target against the tree (hgmm_tree_score / hgmm_tree_score_batch; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------
+// The descent of tree_reg_estep_body (same pose, same reg_descend_level, same stop test), but what is kept is per POINT:
+// the last node s the point reached, maha2 = (y - mu_s)^T Sigma_s^-1 (y - mu_s) and
+// logp = log(pi_s coef_s) - maha2 / 2.  A dead node (prep[9] = pi coef = 0: pi = 0 or det < eps) gives +inf / -inf; a
+// point with a non-finite coordinate gives NaN for both, whatever node the comparisons took it to, so it is never an inlier.
+//   * log(pi_s coef_s) is taken PER POINT from prep[9] (one log() of a value the descent has loaded anyway) rather than from
+//     a new slot of the prep table: PREP_N, the table's builders and every kernel that indexes it stay as they are, and so
+//     do their register counts and results.
+//   * No fixed-point sums, no LDS node table, no atomics: a lane stores up to 4 + 8 + 8 bytes (each array only when asked
+//     for), and the workgroup adds its six sums (SCORE_NSUM: inliers, their maha2, |y - mu_s|^2 and logp; dead-node points;
+//     points that stopped above the leaf level) -- DPP wave sums, then the four waves in order through LDS -- into
+//     partial[0..5].  tree_score_finish_body adds the workgroups' shares in a fixed order, so the eight numbers depend on
+//     the points and their grouping into 256-point workgroups alone: the same for a pair alone and inside a batch.
+// i: the point's place in `tg`; o: its place in the output arrays; alive: the point exists.
+constexpr int SCORE_NSUM = 6;
+__device__ __forceinline__ void tree_score_body(const int64_t i, const int64_t o, bool alive,
+                                                const double* __restrict__ tg, int64_t n_pad, const Rigid& tf,
+                                                const double* __restrict__ prep, int L, double lambda_c, double maha2_max,
+                                                int32_t* __restrict__ node_out, double* __restrict__ maha2_out,
+                                                double* __restrict__ logp_out, double* __restrict__ partial) {
+    __shared__ double exp_tab[EXP_TAB_N];
+    __shared__ double sh[CH / 64][SCORE_NSUM];
+    exp_tab_load(exp_tab);
+    __syncthreads();
+    const bool exists = alive;
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
+    if (alive) rigid_apply(tf, tg[i], tg[n_pad + i], tg[2 * n_pad + i], x0, x1, x2);
+    int64_t search = -1;
+    for (int l = 0; l < L; ++l) {
+        if (!__any(alive)) break;
+        if (alive) {
+            double best;
+            search = reg_descend_level(x0, x1, x2, prep, 8 * (search + 1), exp_tab, best);
+            if (prep[PREP_N * search + 11] <= lambda_c) alive = false;      // complexity(cov_s) <= lambda_c: stop
+        }
+    }
+    double acc[SCORE_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (exists) {
+        const double* pr = prep + PREP_N * search;
+        const double d0 = x0 - pr[6], d1 = x1 - pr[7], d2 = x2 - pr[8];
+        const double w = pr[9];
+        const bool dead = !(w > 0.0);
+        double m2 = sym3_quad(pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], d0, d1, d2);
+        double lp = log(dead ? 1.0 : w) - 0.5 * m2;
+        if (dead) { m2 = INFINITY; lp = -INFINITY; }
+        if (!(fabs(x0) + fabs(x1) + fabs(x2) < INFINITY)) { m2 = NAN; lp = NAN; }
+        if (node_out) node_out[o] = (int32_t)search;
+        if (maha2_out) maha2_out[o] = m2;
+        if (logp_out) logp_out[o] = lp;
+        if (m2 <= maha2_max) {
+            acc[0] = 1.0;
+            acc[1] = m2;
+            acc[2] = d0 * d0 + d1 * d1 + d2 * d2;
+            acc[3] = lp;
+        }
+        acc[4] = dead ? 1.0 : 0.0;
+        acc[5] = (search < level_first(L - 1)) ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < SCORE_NSUM; ++k) {
+        const double v = wave_sum_f64(acc[k]);
+        if (lane_id() == 0) sh[wave_in_block()][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < SCORE_NSUM) {
+        double v = sh[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < CH / 64; ++w) v += sh[w][threadIdx.x];
+        partial[threadIdx.x] = v;
+    }
+}
+
+// The shares partial[nb][SCORE_NSUM] of one target's workgroups -> its summary[8]: ONE workgroup; thread t adds the shares
+// t, t + 256, ... in index order, then the wave sum and the four waves in order -- a function of nb alone.
+__device__ __forceinline__ void tree_score_finish_body(const double* __restrict__ partial, int nb, double n_points,
+                                                       double* __restrict__ summary) {
+    __shared__ double sh[CH / 64][SCORE_NSUM];
+    double acc[SCORE_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nb; b += CH)
+#pragma unroll
+        for (int k = 0; k < SCORE_NSUM; ++k) acc[k] += partial[(size_t)SCORE_NSUM * b + k];
+#pragma unroll
+    for (int k = 0; k < SCORE_NSUM; ++k) {
+        const double v = wave_sum_f64(acc[k]);
+        if (lane_id() == 0) sh[wave_in_block()][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < SCORE_NSUM) {
+        double v = sh[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < CH / 64; ++w) v += sh[w][threadIdx.x];
+        summary[1 + threadIdx.x] = v;
+    }
+    if (threadIdx.x == 0) { summary[0] = n_points; summary[7] = 0.0; }
 }
 
 

@@ -455,6 +455,22 @@ __global__ __launch_bounds__(CH) void tree_reg_estep_kernel(const double* __rest
     tree_reg_estep_body<NMQ>(i, i < n, tg, n_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq, tab);
 }
 
+// score of the resident target against the resident tree (tree_score_body, csrc/tree_device.h): workgroup b writes its six
+// sums to partial[b]; tree_score_finish_kernel (one workgroup) adds them in a fixed order into summary[8]
+__global__ __launch_bounds__(CH) void tree_score_kernel(const double* __restrict__ tg, int64_t n, int64_t n_pad, Rigid tf,
+                                                        const double* __restrict__ prep, int L, double lambda_c,
+                                                        double maha2_max, int32_t* __restrict__ node_out,
+                                                        double* __restrict__ maha2_out, double* __restrict__ logp_out,
+                                                        double* __restrict__ partial) {
+    const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
+    tree_score_body(i, i, i < n, tg, n_pad, tf, prep, L, lambda_c, maha2_max, node_out, maha2_out, logp_out,
+                    partial + (size_t)SCORE_NSUM * blockIdx.x);
+}
+__global__ __launch_bounds__(CH) void tree_score_finish_kernel(const double* __restrict__ partial, int nb, double n_points,
+                                                               double* __restrict__ summary) {
+    tree_score_finish_body(partial, nb, n_points, summary);
+}
+
 // fixed point -> float64, still centred: cm[T][NMQ] = (m0, c1 = sum gamma (x - mu), C2 = sum gamma (x - mu)(x - mu)^T)
 template <int NMQ>
 __global__ void tree_reg_unpack_kernel(const unsigned long long* __restrict__ momq, int64_t T, double d,
@@ -1256,6 +1272,51 @@ extern "C" int hgmm_tree_register(hgmm_ctx* c, double* rot, double* t, double sc
         *iters_out = it + 1;
         if (st == 1) { *status_out = 1; return HGMM_OK; }
     }
+    return HGMM_OK;
+}
+
+// Score of the resident target, moved by (rot, t, scale), against the resident tree: include/hgmm.h.  The descent is the
+// registration E-step's (gmmTreeRegESTep, hgmm_cupy_cpu_working.py:202-228); the score has no counterpart in the reference.
+extern "C" int hgmm_tree_score(hgmm_ctx* c, const double* rot, const double* t, double scale, double lambda_c,
+                               double maha2_max, int32_t* node_out, double* maha2_out, double* logp_out,
+                               double* summary_out) {
+    HGMM_ENTER(c);
+    if (!summary_out) return fail(c, HGMM_ERR_ARG, "tree_score: summary_out is NULL");
+    if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "tree_score: maha2_max is NaN");
+    if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "tree_score: sharded targets are not scored (no communicator)");
+    if (!c->tree.nodes_ready) return fail(c, HGMM_ERR_STATE, "tree_score: no tree (build or set_nodes first)");
+    if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "tree_score: call hgmm_tree_set_target first");
+    Rigid tf;
+    for (int i = 0; i < 9; ++i) tf.r[i] = rot ? rot[i] : ((i % 4 == 0) ? 1.0 : 0.0);
+    for (int i = 0; i < 3; ++i) tf.t[i] = t ? t[i] : 0.0;
+    tf.s = scale;
+    const int64_t n = c->tgt_n, n_pad = c->tgt_pad;
+    const unsigned nb = nblk(n, CH);
+    // scratch: [nb][6] shares | summary[8] | maha2[n_pad] | logp[n_pad] | node[n_pad]  (each array only when asked for)
+    const size_t head = (size_t)SCORE_NSUM * nb + 8;
+    HGMM_TRY(ensure(c, c->scratch, sizeof(double) * (head + (maha2_out ? n_pad : 0) + (logp_out ? n_pad : 0)) +
+                                       sizeof(int32_t) * (node_out ? n_pad : 0)));
+    double* partial = c->scratch.as<double>();
+    double* d_sum = partial + (size_t)SCORE_NSUM * nb;
+    double* at = d_sum + 8;
+    double* d_maha = nullptr;
+    double* d_logp = nullptr;
+    if (maha2_out) { d_maha = at; at += n_pad; }
+    if (logp_out) { d_logp = at; at += n_pad; }
+    int32_t* d_node = node_out ? reinterpret_cast<int32_t*>(at) : nullptr;
+    {
+        ProfScope prof(c, HGMM_K_TREE_SCORE);
+        tree_score_kernel<<<nb, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, n_pad, tf, c->t_prep.as<double>(), c->tree.L,
+                                                    lambda_c, maha2_max, d_node, d_maha, d_logp, partial);
+    }
+    tree_score_finish_kernel<<<1, CH, 0, c->stream>>>(partial, (int)nb, (double)n, d_sum);
+    HGMM_HIP(c, hipGetLastError());
+    StagedDownloads dl(c);
+    dl.add(summary_out, d_sum, sizeof(double) * 8);
+    dl.add(node_out, d_node, sizeof(int32_t) * n);
+    dl.add(maha2_out, d_maha, sizeof(double) * n);
+    dl.add(logp_out, d_logp, sizeof(double) * n);
+    HGMM_HIP(c, dl.finish());
     return HGMM_OK;
 }
 

@@ -22,7 +22,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .._native import Context, default_context
+from .._native import CHI2_3_99, Context, default_context
 
 eps = np.float32(1.0e-15)     # hgmm_gpu.py:29
 n_node = 8                    # hgmm_gpu.py:30
@@ -207,6 +207,44 @@ def _small_lapack():
 
 EstepResult = namedtuple('EstepResult', ['momentZero', 'momentOne', 'momentTwo'])
 MstepResult = namedtuple('MstepResult', ['transformation', 'q'])
+# what registration() returns with return_score=True: MstepResult's two fields, then the TreeScore at the final pose
+ScoredResult = namedtuple('ScoredResult', ['transformation', 'q', 'score'])
+
+# Score of a cloud against a tree (Context.tree_score; no counterpart in the reference).  fitness = share of the points
+# whose squared Mahalanobis distance to their node is within the inlier bound; inlier_rmse = rms Euclidean distance of the
+# inliers to their nodes' means; mahalanobis_rms = rms Mahalanobis distance of the inliers; mean_log_density = mean over the
+# inliers of log(pi_s N(y; s)); n_dead = points whose node has pi = 0 or a singular covariance; n_above_leaf = points that
+# stopped above the last level; node / maha2 / logp = the per-point arrays, or None where they were not asked for.
+TreeScore = namedtuple('TreeScore', ['fitness', 'inlier_rmse', 'mahalanobis_rms', 'mean_log_density', 'n_points',
+                                     'n_inliers', 'n_dead', 'n_above_leaf', 'node', 'maha2', 'logp'])
+
+
+def tree_score_from_summary(summary, arrays=None):
+    """The eight sums of ``hgmm_tree_score`` (+ the per-point arrays, a dict or None) -> :class:`TreeScore`.
+
+    With NO inlier there is nothing to average: fitness is 0.0, ``inlier_rmse`` and ``mahalanobis_rms`` are +inf and
+    ``mean_log_density`` is -inf ("infinitely far"), so no field is ever NaN through a division by zero and a threshold
+    test on any of them rejects such a cloud."""
+    s = np.asarray(summary, dtype=np.float64).reshape(8)
+    arrays = arrays or {}
+    n, n_in = int(s[0]), int(s[1])
+    if n_in > 0:
+        rmse, mrms, mld = float(np.sqrt(s[3] / s[1])), float(np.sqrt(s[2] / s[1])), float(s[4] / s[1])
+    else:
+        rmse, mrms, mld = float("inf"), float("inf"), float("-inf")
+    return TreeScore(float(s[1] / s[0]) if n > 0 else 0.0, rmse, mrms, mld, n, n_in, int(s[5]), int(s[6]),
+                     arrays.get("node"), arrays.get("maha2"), arrays.get("logp"))
+
+
+def node_level(node):
+    """Tree level (0 = the root's eight children) of node indices: level l holds the nodes 8 (8^l - 1) / 7 .. 8 (8^(l+1) - 1) / 7 - 1."""
+    node = np.asarray(node, dtype=np.int64)
+    lvl = np.zeros(node.shape, dtype=np.int64)
+    first = 8                                    # first node of level 1
+    while np.any(node >= first):
+        lvl += node >= first
+        first = 8 * first + 8
+    return lvl if lvl.ndim else int(lvl)
 
 
 class GMMTree():
@@ -383,8 +421,53 @@ class GMMTree():
         self.n_iter_ = it
         return MstepResult(self._tf_result.inverse(), np.array([q]) if q is not None else np.array([]))
 
-    def registration(self, target, maxiter=20, tol=1.0e-4):
-        """-> MstepResult(tf.inverse(), q)   (hgmm_gpu.py:754-768)."""
+    def _score_resident(self, maha2_max=CHI2_3_99, per_point=True, lambda_c=None):
+        """TreeScore of the RESIDENT target against the resident tree at the loop's own pose ``self._tf_result``."""
+        tf = self._tf_result
+        summary, arrays = self._ctx.tree_score(tf.rot, tf.t, tf.scale, self._lambda_c if lambda_c is None else lambda_c,
+                                               maha2_max, ("node", "maha2", "logp") if per_point else ())
+        return tree_score_from_summary(summary, arrays)
+
+    def score(self, target, transformation=None, maha2_max=CHI2_3_99, per_point=True):
+        """How well does this tree explain ``target``?  -> :class:`TreeScore` (``hgmm_tree_score``).
+
+        ``transformation`` is WHAT :meth:`registration` RETURNED -- the inverse of the pose that moves the target onto the
+        tree -- so ``gt.score(target, gt.registration(target).transformation)`` is the natural call; None: the target as
+        given.  Every point descends the tree as in the registration E-step with this tree's ``lambda_c`` and is scored at the
+        node it stops at.  The returned object is inverted again here, and ``-R (-R^T t)`` rounds: the result agrees with
+        ``registration(..., return_score=True)`` (which uses the loop's own pose) to rounding, not bit for bit.
+        ``per_point=False`` leaves ``node`` / ``maha2`` / ``logp`` None (nothing N-long is stored or downloaded)."""
+        self._ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
+        self._ctx.tree_set_target(_points(target))
+        self._target_id = None
+        rot = t = None
+        scale = 1.0
+        if transformation is not None:
+            pose = transformation.inverse()
+            rot, t, scale = pose.rot, pose.t, pose.scale
+        summary, arrays = self._ctx.tree_score(rot, t, scale, self._lambda_c, maha2_max,
+                                               ("node", "maha2", "logp") if per_point else ())
+        return tree_score_from_summary(summary, arrays)
+
+    def predict(self, points):
+        """Node of the LAST level that explains each point (int32 [N]): the descent of the registration E-step without its
+        stop rule (``lambda_c < 0``) -- the tree's counterpart of the flat models' ``predict``.  These are the labels of the
+        finished tree; the build's own ``currentIdx`` assigns a point within the parent chosen one level up with that
+        level's parameters, and need not agree."""
+        self._ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
+        self._ctx.tree_set_target(_points(points))
+        self._target_id = None
+        return self._ctx.tree_score(lambda_c=-1.0, want=("node",))[1]["node"]
+
+    def registration(self, target, maxiter=20, tol=1.0e-4, return_score=False, maha2_max=CHI2_3_99):
+        """-> MstepResult(tf.inverse(), q)   (hgmm_gpu.py:754-768).  ``return_score=True``: ScoredResult(tf.inverse(), q,
+        score) with the :class:`TreeScore` of the target at the final pose, taken with the loop's own (R, t)."""
+        res = self._registration(target, maxiter, tol)
+        if return_score:
+            return ScoredResult(res.transformation, res.q, self._score_resident(maha2_max))
+        return res
+
+    def _registration(self, target, maxiter, tol):
         self._ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
         self._ctx.tree_set_target(_points(target))
         if self._device_mstep and not self._callbacks:
@@ -438,11 +521,11 @@ def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
     return src, tgt @ rot.T + np.asarray(translation)
 
 
-def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], **kargs):
-    """hgmm_gpu.py:802-807."""
+def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, **kargs):
+    """hgmm_gpu.py:802-807.  ``return_score=True``: ScoredResult(transformation, q, score) -- see :meth:`GMMTree.registration`."""
     gt = GMMTree(_points(source), **kargs)
     gt.set_callbacks(callbacks)
-    return gt.registration(_points(target), maxiter, tol)
+    return gt.registration(_points(target), maxiter, tol, return_score=return_score)
 
 
 BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this size (csrc/tree_batch.hip)
@@ -450,7 +533,7 @@ BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this 
 
 def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | None = None, tree_level=5, lambda_c=0.01,
                                ls=20, ld=1.0e-4, sig2=0.004, init_idx=None, return_info=False, pdf_dtype=None,
-                               solve_on_device=False):
+                               solve_on_device=False, score=False):
     """``[registration_gmmtree(s, t, maxiter, tol, tree_level=..., ...) for s, t in pairs]`` (hgmm_gpu.py:802-807 per pair)
     with ALL pairs in the same launches: the B source clouds are one resident forest (``hgmm_tree_build_batch``: levels in
     lock-step, one stop rule per cloud), the B targets are registered against their trees together
@@ -462,6 +545,11 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     ``pdf_dtype``: the arithmetic of the build's stop rule, as in :class:`GMMTree` -- default: each SOURCE's own type
     (float32 scans, the type of the reference's GPU file, hgmm_gpu.py:472: float32 pdfs; anything else float64); pairs
     of either kind in one call run as two batches.  Tables, E-step, moments and the registration are float64 either way.
+
+    ``score=True`` (with ``return_info``): ``info["score"]`` holds one :class:`TreeScore` per pair, of the target at the pose
+    its loop ended at (no per-point arrays) -- one ``hgmm_tree_score_batch`` call after the registration; pairs that ran or
+    finished serially are scored through the serial entry.  The same numbers, bit for bit, as
+    ``registration_gmmtree(..., return_score=True).score``.
 
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
@@ -476,29 +564,37 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
         out = [None] * len(pairs)
         info = {"build_iters": np.full((len(pairs), tree_level), -1, np.int32), "registration_iters": [None] * len(pairs),
                 "status": [None] * len(pairs)}
+        if score:
+            info["score"] = [None] * len(pairs)
         for k in big:
             gt = GMMTree(pairs[k][0], tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, init_idx=init_idx, ctx=ctx,
                          solve_on_device=solve_on_device)
             out[k] = gt.registration(_points(pairs[k][1]), maxiter, tol)
             info["registration_iters"][k], info["status"][k] = int(gt.n_iter_), 0
+            if score:
+                info["score"][k] = gt._score_resident(per_point=False)
         rest = [k for k in range(len(pairs)) if k not in set(big)]
         if rest:
             r, inf = registration_gmmtree_batch([pairs[k] for k in rest], maxiter, tol, ctx, tree_level, lambda_c, ls, ld, sig2,
-                                                init_idx, True, pdf_dtype, solve_on_device)
+                                                init_idx, True, pdf_dtype, solve_on_device, score)
             for j, k in enumerate(rest):
                 out[k] = r[j]
                 info["build_iters"][k] = inf["build_iters"][j]
                 info["registration_iters"][k], info["status"][k] = inf["registration_iters"][j], inf["status"][j]
+                if score:
+                    info["score"][k] = inf["score"][j]
         return (out, info) if return_info else out
     if pdf_dtype is None:
         kinds = [np.dtype(np.float32) if _points(s).dtype == np.float32 else np.dtype(np.float64) for s, _ in pairs]
         if len(set(kinds)) > 1:                                   # one batch per kind, results back in the caller's order
             out, info = [None] * len(pairs), {"build_iters": [None] * len(pairs), "registration_iters": [None] * len(pairs),
                                               "status": [None] * len(pairs)}
+            if score:
+                info["score"] = [None] * len(pairs)
             for kind in sorted(set(kinds), key=str):
                 sel = [k for k, v in enumerate(kinds) if v == kind]
                 r, inf = registration_gmmtree_batch([pairs[k] for k in sel], maxiter, tol, ctx, tree_level, lambda_c, ls, ld,
-                                                    sig2, init_idx, True, kind, solve_on_device)
+                                                    sig2, init_idx, True, kind, solve_on_device, score)
                 for j, k in enumerate(sel):
                     out[k] = r[j]
                     for key in info:
@@ -534,6 +630,12 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     else:
         rot, t, iters, q, status, _ = ctx.tree_register_batch(rot0, np.zeros((B, 3)), 1.0, lambda_c, maxiter, tol)
     clock.append(time.perf_counter())
+    # (the batch is scored first: finishing a pair serially below moves the context's serial tree and target, not the forest)
+    scores = None
+    if score:
+        sums = ctx.tree_score_batch(rot, t, 1.0, lambda_c)
+        scores = [tree_score_from_summary(sums[b]) for b in range(B)]
+    clock.append(time.perf_counter())
     out = []
     reg_iters = [int(v) for v in iters]
     for b in range(B):
@@ -545,6 +647,8 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
             ctx.tree_set_target(tgts[b])
             res = gt._registration_in_library(maxiter, tol, _resume=(int(iters[b]), None if np.isnan(q[b]) else float(q[b]), True))
             reg_iters[b] = int(gt.n_iter_)
+            if score:                                                 # (its pose moved on: the serial entry, at the final pose)
+                scores[b] = gt._score_resident(per_point=False)
             out.append(res)
             continue
         tf = RigidTransformation(rot[b].copy(), t[b].copy())
@@ -552,9 +656,12 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     if return_info:
         clock.append(time.perf_counter())
         # wall time of the call's phases, ms: host preparation (type conversion, initial means), upload of the sources, forest
-        # build, upload of the targets, batched registration, result objects
-        phases = dict(zip(("prepare", "sources_up", "build", "targets_up", "register", "results"),
+        # build, upload of the targets, batched registration, score (0 unless asked for), result objects
+        phases = dict(zip(("prepare", "sources_up", "build", "targets_up", "register", "score", "results"),
                           (1e3 * np.diff(clock)).tolist()))
-        return out, {"build_iters": build_iters, "registration_iters": reg_iters, "status": [int(v) for v in status],
-                     "phases_ms": phases}
+        info = {"build_iters": build_iters, "registration_iters": reg_iters, "status": [int(v) for v in status],
+                "phases_ms": phases}
+        if score:
+            info["score"] = scores
+        return out, info
     return out

@@ -105,7 +105,7 @@ class ReplicaPool:
 
 
 def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: int = 20, tol: float = 1.0e-4,
-                   method: str = "gmmtree", pool: ReplicaPool | None = None, batch: int = 1, **kargs):
+                   method: str = "gmmtree", pool: ReplicaPool | None = None, batch: int = 1, score: bool = False, **kargs):
     """Register every (source, target) pair of ``pairs`` -- arrays [N,3] or objects with ``.points`` -- with
     ``registration_gmmtree`` (``method='gmmtree'``, hgmm/hgmm_gpu.py:802-807; ``kargs`` = GMMTree's: tree_level,
     lambda_c, ls, sig2, ...) or ``registration_gmmreg`` (``method='gmmreg'``, gmmreg_gpu/gmmreg.py:149-157; it has no
@@ -115,22 +115,33 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
     ``batch`` > 1 (gmmtree only): every context takes ``batch`` pairs at a time through the SAME launches
     (``registration_gmmtree_batch``: the trees built as one forest, the targets registered together) -- a 40 k-point pair
     alone is a chain of ~350 small launches that leaves the chip idle; results are bitwise those of ``batch=1``.  Two
-    contexts per device let one batch's uploads and 6 x 6 solves overlap the other's kernels."""
+    contexts per device let one batch's uploads and 6 x 6 solves overlap the other's kernels.
+
+    ``score=True`` (gmmtree only): every result is a ``ScoredResult(transformation, q, score)`` with the ``TreeScore`` of the
+    target at the pose the loop ended at (``registration_gmmtree(..., return_score=True)``; with ``batch`` > 1
+    ``registration_gmmtree_batch(..., score=True)``: the same numbers without the per-point arrays)."""
     pairs = list(pairs)
     if method == "gmmtree":
-        from .hgmm.hgmm_gpu import registration_gmmtree, registration_gmmtree_batch
+        from .hgmm.hgmm_gpu import ScoredResult, registration_gmmtree, registration_gmmtree_batch
 
         if int(batch) > 1:
             def one(ctx, chunk):
-                return registration_gmmtree_batch(chunk, maxiter=maxiter, tol=tol, ctx=ctx, **kargs)
+                if not score:
+                    return registration_gmmtree_batch(chunk, maxiter=maxiter, tol=tol, ctx=ctx, **kargs)
+                res, info = registration_gmmtree_batch(chunk, maxiter=maxiter, tol=tol, ctx=ctx, return_info=True, score=True, **kargs)
+                return [ScoredResult(r.transformation, r.q, sc) for r, sc in zip(res, info["score"])]
         else:
             def one(ctx, pair):
-                return registration_gmmtree(pair[0], pair[1], maxiter=maxiter, tol=tol, ctx=ctx, **kargs)
+                if not score:
+                    return registration_gmmtree(pair[0], pair[1], maxiter=maxiter, tol=tol, ctx=ctx, **kargs)
+                return registration_gmmtree(pair[0], pair[1], maxiter=maxiter, tol=tol, ctx=ctx, return_score=True, **kargs)
     elif method == "gmmreg":
         from .gmmreg_gpu.gmmreg import registration_gmmreg
 
         if int(batch) > 1:
             raise ValueError("batch > 1 is implemented for method='gmmtree' only")
+        if score:
+            raise ValueError("score=True is implemented for method='gmmtree' only")
         if maxiter != 20 or tol != 1.0e-4:
             raise ValueError("registration_gmmreg takes neither maxiter nor tol (its optimiser's settings live in "
                              "L2DistRegistration); leave them at their defaults")

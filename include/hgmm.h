@@ -62,7 +62,8 @@ enum hgmm_kernel_id {
     HGMM_K_KMEANS_ACCUM = 10, /* KMeans initialiser: per-cluster sums */
     HGMM_K_ALLREDUCE = 11,    /* the sufficient-statistics all-reduce (RCCL / host backend), N > 1 only */
     HGMM_K_FULL_FUSED = 12,   /* full-cov flat EM, one pass: denominators + arg-max + q + fp64-MFMA statistics */
-    HGMM_K_COUNT = 13
+    HGMM_K_TREE_SCORE = 13,   /* HGMM score of a moved target (tree descent, per-point outputs + summary) */
+    HGMM_K_COUNT = 14
 };
 
 /* ---- lifecycle ------------------------------------------------------------------ */
@@ -334,6 +335,38 @@ int hgmm_tree_set_targets_batch_f32(hgmm_ctx* ctx, int B, const float* const* xy
 int hgmm_tree_register_batch(hgmm_ctx* ctx, int B, double* rot, double* t, double scale, double lambda_c,
                              int max_iter, double tol, double* q_prev_inout, int32_t* iters_out,
                              int32_t* status_out, double* trace);
+/* ---- score of a cloud against a tree: labels, Mahalanobis distance, fitness ---------------------------------------------
+ * "Did the registration work?"  The reference has no counterpart of the score itself (GMMTree.registration returns the
+ * transformation and the least-squares residual q only); the DESCENT it is taken along is gmmTreeRegESTep's
+ * (hgmm_cupy_cpu_working.py:202-228 == hgmm_gpu.py:550-577), by the device function the registration E-step itself calls:
+ * every point y = scale * R x + t of the resident target (hgmm_tree_set_target; rot / t NULL = identity, as
+ * hgmm_tree_reg_estep) moves level by level to the first maximum of pi_k N(y; k) over the eight children (the first child
+ * when their sum is <= 1e-15) and stops at a node whose complexity is <= lambda_c, at the latest on level L - 1.  Its node s
+ * is the last node reached; lambda_c < 0 therefore labels every point by a node of the last level ("predict").
+ * Per point (each array may be NULL):
+ *   node  [n] int32    index into the node tables (its level follows from the index)
+ *   maha2 [n] float64  (y - mu_s)^T Sigma_s^-1 (y - mu_s); +inf when node s is dead (pi_s = 0 or det Sigma_s < 1e-15)
+ *   logp  [n] float64  log pi_s - log((2 pi)^3 det Sigma_s) / 2 - maha2 / 2, formed in log space; -inf for a dead node.
+ *                      The path's own term of the level's mixture density: a lower bound of it.
+ * A point with a NaN or infinite coordinate (after the pose) gets maha2 = logp = NaN and whatever node the comparisons of
+ * the descent led to (NaN compares false: the first child at every level); it is never an inlier and adds to slot 0 only
+ * (and to slots 5 / 6 if its node is dead / above the last level).
+ * summary [8] (always written), inlier_i = maha2_i <= maha2_max:
+ *   [0] n   [1] inliers   [2] sum of maha2 over inliers   [3] sum of |y - mu_s|^2 over inliers   [4] sum of logp over inliers
+ *   [5] points whose node is dead   [6] points that stopped above level L - 1   [7] 0 (reserved)
+ * fitness = [1] / [0], inlier rmse = sqrt([3] / [1]), Mahalanobis rms = sqrt([2] / [1]), mean log density = [4] / [1] are the
+ * caller's to form.  Deterministic: every 256-point workgroup adds its own six sums and one workgroup adds the workgroups'
+ * shares in a fixed order (no floating-point atomics), so two calls return the same bits.
+ * hgmm_tree_score_batch: the same for all B pairs (tree b, target b) of the resident forest (hgmm_tree_build_batch +
+ * hgmm_tree_set_targets_batch) at the poses rot [B][9], t [B][3] (NULL = identity) in one launch, summaries [B][8] only
+ * (the per-point arrays of one member: the serial entry) -- bit for bit the serial entry's summary on that pair alone.
+ * Every pair is scored, also one that left hgmm_tree_register_batch with status 2.
+ * Errors: HGMM_ERR_STATE without a tree / target / forest + targets or under a communicator (sharded targets are not
+ * scored); HGMM_ERR_ARG when maha2_max is NaN or summary_out is NULL.                                                     */
+int hgmm_tree_score(hgmm_ctx* ctx, const double* rot, const double* t, double scale, double lambda_c, double maha2_max,
+                    int32_t* node_out, double* maha2_out, double* logp_out, double* summary_out /* [8] */);
+int hgmm_tree_score_batch(hgmm_ctx* ctx, int B, const double* rot /* [B,9] */, const double* t /* [B,3] */, double scale,
+                          double lambda_c, double maha2_max, double* summary_out /* [B,8] */);
 /* The steps buildGMMTree is made of, one at a time (reference function granularity).  Node tables
  * hold T nodes (any T >= 8, need not be a complete tree).
  * hgmm_tree_estep  <- gmmTreeEStep()       hgmm_cupy_cpu_working.py:162-191: parent_idx[N] arbitrary
