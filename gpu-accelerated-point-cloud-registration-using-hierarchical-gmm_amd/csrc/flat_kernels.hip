@@ -1682,7 +1682,7 @@ int stage_reserve(hgmm_ctx* c, size_t bytes, void** out) {            // (declar
     c->h_stage_off += bytes;
     return HGMM_OK;
 }
-static int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {
+int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {       // (declared in hgmm_ctx.h)
     void* st = nullptr;
     HGMM_TRY(stage_reserve(c, bytes, &st));
     std::memcpy(st, host, bytes);

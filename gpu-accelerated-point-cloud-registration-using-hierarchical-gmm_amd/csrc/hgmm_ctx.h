@@ -97,6 +97,29 @@ enum ConfigKey {
 struct ConfigSpec { const char* name; int dflt, lo, hi; };
 extern const ConfigSpec CONFIG_SPECS[CFG_COUNT];
 
+// The context's pinned, coherent hand-over block (tree_host.h: hand_over): what a running kernel stores there at system
+// scope the polling host sees at once.  For B pairs / clouds:
+//   [0, 32)  two control-word slots (TreeCtl) of the batch scheme's asynchronous copies
+//   [64 ..)  B progress words  (stopped << 32 | iterations)  of the builds and of the registration loop on the device
+//   then     B sequence words + (256-aligned) B x 28 numbers: the registration's normal equations on their way to the host
+struct TreeCtl;                            // tree_device.h
+template <class T> struct HostDev { T* host; T* dev; };   // one location, as the host and as the device address it
+struct HandOver {
+    char* host = nullptr;
+    char* dev = nullptr;
+    size_t cap = 0;
+    int B = 0;
+    unsigned long long seq = 0;            // sequence number of the last hand-over through the block
+    static size_t seq_off(int B) { return 64 + (((size_t)B * 8 + 63) & ~(size_t)63); }
+    static size_t out_off(int B) { return (seq_off(B) + (size_t)B * 8 + 255) & ~(size_t)255; }
+    static size_t bytes(int B) { return out_off(B) + (size_t)B * 28 * sizeof(double); }
+    template <class T> HostDev<T> at(size_t off) const { return {reinterpret_cast<T*>(host + off), reinterpret_cast<T*>(dev + off)}; }
+    TreeCtl* ctl_slot(int s) const { return reinterpret_cast<TreeCtl*>(host + 16 * (size_t)s); }   // (host side only: copy targets)
+    HostDev<unsigned long long> progress(int b) const { return at<unsigned long long>(64 + (size_t)b * 8); }
+    HostDev<unsigned long long> sequence(int b) const { return at<unsigned long long>(seq_off(B) + (size_t)b * 8); }
+    HostDev<double> out28(int b) const { return at<double>(out_off(B) + (size_t)b * 28 * sizeof(double)); }
+};
+
 struct HostComm;                           // hgmm_api.hip
 struct IpcComm;                            // hgmm_api.hip: one-shot peer-to-peer exchange over mapped peer memory
 
@@ -106,8 +129,7 @@ struct TreeState {
     bool nodes_ready = false;
     bool pdf_f32 = false;             // hgmm_tree_set_precision: the level log-likelihood's pdfs in float32 (large clouds)
     double mu_rmax = -1.0;            // largest |mu_j| of the node table (< 0: not known on the host yet)
-    bool momq_dirty = true;           // the fixed-point moment words hold sums nobody has cleared yet
-    unsigned long long reg_seq = 0;   // sequence number of the last registration system handed over in pinned memory
+    bool momq_clean = false;          // every word of t_momq is zero (tree_host.h: MomqScope)
     unsigned long long surplus_iterations = 0;   // (communicator) level-iterations enqueued behind a level's stop, all builds
 };
 
@@ -122,10 +144,7 @@ struct ForestState {
     std::vector<int64_t> tg_counts, tg_first;
     std::vector<double> tg_rmax;          // largest |x| per target
     int64_t tg_pad = 0;
-    bool momq_clean = false;              // every word of fr_momq is zero
-    unsigned long long seq = 0;           // sequence number of the last hand-over through pinned memory
-    void* host = nullptr;                 // pinned, coherent: progress words of the build, hand-over of the registration
-    size_t host_cap = 0;
+    bool momq_clean = false;              // every word of fr_momq is zero (tree_host.h: MomqScope)
 };
 
 }  // namespace hgmm
@@ -184,8 +203,8 @@ struct hgmm_ctx {
     hgmm::DevBuf t_pi, t_mu, t_cov;           // double node tables [T], [T,3], [T,9]
     hgmm::DevBuf t_prep;                      // double [T][12] : inv(6) coef logc pi mu(3) -> see tree_kernels
     hgmm::DevBuf t_cplx;                      // double [T]
-    void* tree_hctl = nullptr;                // pinned host copy of the level control words (2 slots)
-    hipEvent_t tree_ev[2] = {nullptr, nullptr};
+    hgmm::HandOver hand;                      // pinned hand-over block of the tree / forest drivers
+    hipEvent_t tree_ev[2] = {nullptr, nullptr};   // the batch scheme's events, one per control-word slot (tree_host.h: tree_batch_events)
     hgmm::DevBuf exp_tab2;                    // double [2048] 2^(j/2048) for the throughput kernels' exp (tree_kernels.hip)
     hgmm::DevBuf t_tickets;                   // uint: two-level arrival counters of the last-workgroup reductions, 4 KB apart
     hgmm::DevBuf t_flags;                     // int [4] tree flags + uint64 executed-pair counter (tree_kernels.hip)
@@ -253,6 +272,8 @@ struct hgmm_ctx {
 namespace hgmm {
 // a region of the context's pinned staging ring (flat_kernels.hip); reused only after a stream synchronisation
 int stage_reserve(hgmm_ctx* c, size_t bytes, void** out);
+// `bytes` of host memory on their way to `dev`: copied into a region of the ring, one DMA packet behind the stream's work
+int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes);
 constexpr size_t STAGE_RING_BYTES = 4u << 20;
 
 }  // namespace hgmm
@@ -272,8 +293,8 @@ inline hipError_t ctx_stream_sync(hgmm_ctx* c) {
 namespace hgmm {
 
 // Results of an API call on their way to the caller's (pageable) arrays: every add() enqueues ONE asynchronous DMA into
-// the pinned ring behind the kernels already on the stream (large arrays, or whatever no longer fits half the ring, go
-// straight to their destination), finish() synchronises once and hands the ring's regions out with plain memcpys.
+// the pinned ring behind the kernels already on the stream (arrays above `limit` bytes, or whatever no longer fits half the
+// ring, go straight to their destination), finish() synchronises once and hands the ring's regions out with plain memcpys.
 // (Copied straight into pageable memory each array is staged by the runtime and waited for in turn, ~17 us apiece.)
 struct StagedDownloads {
     hgmm_ctx* c;
@@ -281,11 +302,12 @@ struct StagedDownloads {
     std::vector<Pending> pending;
     size_t staged = 0;
     hipError_t e = hipSuccess;
-    explicit StagedDownloads(hgmm_ctx* ctx) : c(ctx) {}
+    size_t limit;
+    explicit StagedDownloads(hgmm_ctx* ctx, size_t per_array_limit = 256u << 10) : c(ctx), limit(per_array_limit) {}
     void add(void* dst, const void* dev_src, size_t bytes) {
         if (e != hipSuccess || !dst || bytes == 0) return;
         void* st = nullptr;
-        if (bytes <= (256u << 10) && staged + bytes + 256 <= STAGE_RING_BYTES / 2 && stage_reserve(c, bytes, &st) == 0) {
+        if (bytes <= limit && staged + bytes + 256 <= STAGE_RING_BYTES / 2 && stage_reserve(c, bytes, &st) == 0) {
             staged += (bytes + 255) & ~(size_t)255;
             e = hipMemcpyAsync(st, dev_src, bytes, hipMemcpyDeviceToHost, c->stream);
             pending.push_back({dst, st, bytes});
@@ -360,7 +382,7 @@ struct ProfScope {
 };
 int profile_collect(hgmm_ctx* c);
 
-// sub-system entry points implemented in flat_kernels.hip / tree_kernels.hip
+// sub-system entry points implemented in flat_kernels.hip
 int allreduce_f64_dev(hgmm_ctx* c, double* dev, size_t n);
 int allreduce_f64_oop(hgmm_ctx* c, const double* src, double* dst, size_t n);
 int allreduce_i64_dev(hgmm_ctx* c, long long* dev, size_t n);      // exact (integer) sum, in place

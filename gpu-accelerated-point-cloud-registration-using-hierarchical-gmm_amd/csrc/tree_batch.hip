@@ -21,7 +21,7 @@
 // (csrc/tree_device.h), the chunks, blocks and orders of summation are the serial ones, the host steps are the same inline
 // functions -- so trees, iteration counts, q traces and (R, t) are bitwise those of hgmm_tree_build / hgmm_tree_register
 // (tests/test_tree_batch_gpu.py).
-#include "tree_device.h"
+#include "tree_host.h"
 
 namespace hgmm {
 
@@ -321,25 +321,6 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// pinned, coherent host block: [0, 8 B) progress words of the build / sequence words of the registration, then the
-// registration's 28 numbers per pair
-static int forest_host(hgmm_ctx* c, int B, unsigned long long** words, double** out28) {
-    const size_t want = (size_t)B * (8 + 28 * 8) + 256;
-    if (!c->forest.host || c->forest.host_cap < want) {
-        HGMM_HIP(c, ctx_stream_sync(c));
-        if (c->forest.host) HGMM_HIP(c, hipHostFree(c->forest.host));
-        c->forest.host = nullptr;
-        HGMM_HIP(c, hipHostMalloc(&c->forest.host, want, hipHostMallocMapped | hipHostMallocCoherent));
-        c->forest.host_cap = want;
-        std::memset(c->forest.host, 0, want);
-    }
-    *words = static_cast<unsigned long long*>(c->forest.host);
-    *out28 = reinterpret_cast<double*>(static_cast<char*>(c->forest.host) + (((size_t)B * 8 + 255) & ~(size_t)255));
-    return HGMM_OK;
-}
-
-static int64_t forest_T(int L) { return level_first(L); }
-
 // The registration loop of B pairs with the device on its own (reg_device_solve): every iteration is two launches -- the
 // E-step of all pairs, then per pair the normal equations + reg_device_step -- enqueued by a host that only follows the
 // pairs' progress words and keeps a few iterations ahead of the slowest running pair; launches behind a pair's stop
@@ -357,81 +338,39 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
     ForestRegPair* d_tab = c->fr_reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
     double* d_trace = trace ? c->fr_trace.as<double>() : nullptr;
-    unsigned long long* words = nullptr;
-    double* unused28 = nullptr;
-    HGMM_TRY(forest_host(c, B, &words, &unused28));
-    void* d_words = nullptr;
-    HGMM_HIP(c, hipHostGetDevicePointer(&d_words, words, 0));
+    HandOver* hand = nullptr;
+    HGMM_TRY(hand_over(c, B, &hand));
+    const HostDev<unsigned long long> words = hand->progress(0);
     std::vector<ForestRegPair> tab(B);
     int64_t longest = 0;
     for (int b = 0; b < B; ++b) {
-        ForestRegPair& pr = tab[b];
-        std::memset(&pr, 0, sizeof pr);
-        pr.active = 1;
-        pr.tg_first = (int)tg_first[b];
-        pr.tg_count = (int)tg_counts[b];
-        for (int i = 0; i < 9; ++i) pr.tf.r[i] = rot[9 * b + i];
-        for (int i = 0; i < 3; ++i) pr.tf.t[i] = t[3 * b + i];
-        pr.tf.s = scale;
-        double D = 1.0;
-        int Fb = 0;
-        reg_encoding(reg_extent(pr.tf, tg_rmax[b], mu_rmax[b]), (double)tg_counts[b], &D, &Fb);
-        pr.inv_d = 1.0 / D;
-        pr.fix_scale = std::ldexp(1.0, Fb);
-        pr.d_ext = D;
-        pr.inv_scale = std::ldexp(1.0, -Fb);
-        pr.tg_rmax = tg_rmax[b];
-        pr.mu_rmax = mu_rmax[b];
+        ForestRegPair& pr = tab[b] = reg_pair(tg_first[b], tg_counts[b]);
+        reg_pair_fill(pr, rigid_from(rot + 9 * b, t + 3 * b, scale), tg_rmax[b], mu_rmax[b]);
         pr.has_q = (q_prev_inout[b] == q_prev_inout[b]) ? 1 : 0;              // (NaN: no previous q)
         pr.q_prev = pr.has_q ? q_prev_inout[b] : 0.0;
         longest = std::max(longest, tg_counts[b]);
-        __atomic_store_n(words + b, 0ull, __ATOMIC_RELAXED);
+        __atomic_store_n(words.host + b, 0ull, __ATOMIC_RELAXED);
     }
-    {
-        void* st = nullptr;
-        HGMM_TRY(stage_reserve(c, sizeof(ForestRegPair) * B, &st));
-        std::memcpy(st, tab.data(), sizeof(ForestRegPair) * B);
-        HGMM_HIP(c, hipMemcpyAsync(d_tab, st, sizeof(ForestRegPair) * B, hipMemcpyHostToDevice, c->stream));
-    }
+    HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
     const int ahead = 3;
     int enq = 0;
     unsigned spins = 0;
     while (true) {
-        bool all_done = true;
-        int it_min = 0x7fffffff;
-        unsigned long long sig = 0;
-        for (int b = 0; b < B; ++b) {
-            const unsigned long long w = __atomic_load_n(words + b, __ATOMIC_RELAXED);
-            sig += w;
-            if (w >> 32) continue;
-            all_done = false;
-            it_min = std::min(it_min, (int)(w & 0xffffffffull));
-        }
-        if (all_done) break;
-        if (enq < max_iter && enq - it_min < ahead) {
+        const Progress pg = scan_progress(words.host, B);
+        if (pg.all_done) break;
+        if (enq < max_iter && enq - pg.it_min < ahead) {
             {
                 ProfScope prof(c, HGMM_K_TREE_REG);
                 forest_reg_estep_kernel<4><<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c, momq,
                                                                                                   (int)nblk(longest, CH));
             }
-            forest_reg_solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace,
-                                                             static_cast<unsigned long long*>(d_words));
+            forest_reg_solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace, words.dev);
             HGMM_HIP(c, hipGetLastError());
             ++enq;
             spins = 0;
             continue;
         }
-        __builtin_ia32_pause();
-        if ((++spins & 0x3fff) == 0) {
-            const hipError_t qe = hipStreamQuery(c->stream);
-            if (qe != hipSuccess && qe != hipErrorNotReady)
-                return fail(c, HGMM_ERR_HIP, "registration (device loop): device error: %s", hipGetErrorString(qe));
-            if (qe == hipSuccess) {
-                unsigned long long sig2 = 0;
-                for (int b = 0; b < B; ++b) sig2 += __atomic_load_n(words + b, __ATOMIC_ACQUIRE);
-                if (sig2 == sig) return fail(c, HGMM_ERR_STATE, "registration (device loop): no progress (%d iterations enqueued)", enq);
-            }
-        }
+        HGMM_TRY(device_watch(c, &spins, words.host, B, pg.sig, "registration (device loop, %d iterations enqueued)", enq));
     }
     std::vector<double> trace_host(trace ? (size_t)13 * max_iter * B : 0);
     {
@@ -483,7 +422,7 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         if (sum != n) return fail(c, HGMM_ERR_ARG, "tree build (batch): the counts add up to %lld, the resident cloud has %lld points",
                                   (long long)sum, (long long)n);
     }
-    const int64_t T = forest_T(L);
+    const int64_t T = level_first(L);
     const int64_t TT = T * B;
     int64_t P8 = 1;
     for (int i = 0; i < L - 1; ++i) P8 *= 8;                   // parents of one cloud at the last level
@@ -512,12 +451,10 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         HGMM_TRY(ensure(c, c->t_xs3, sizeof(double) * 3 * n_pad));
         xs_c = c->t_xs3.as<double>();
     }
-    unsigned long long* words = nullptr;
-    double* unused28 = nullptr;
-    HGMM_TRY(forest_host(c, B, &words, &unused28));
-    void* dp = nullptr;
-    HGMM_HIP(c, hipHostGetDevicePointer(&dp, words, 0));
-    unsigned long long* words_dev = static_cast<unsigned long long*>(dp);
+    HandOver* hand = nullptr;
+    HGMM_TRY(hand_over(c, B, &hand));
+    unsigned long long* const words = hand->progress(0).host;
+    unsigned long long* const words_dev = hand->progress(0).dev;
 
     double* d_pi = c->fr_pi.as<double>();
     double* d_mu = c->fr_mu.as<double>();
@@ -549,12 +486,7 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     HGMM_HIP(c, hipGetLastError());
     std::vector<int> first(B + 1, 0);
     for (int b = 0; b < B; ++b) first[b + 1] = first[b] + (int)counts[b];
-    {
-        void* st = nullptr;
-        HGMM_TRY(stage_reserve(c, sizeof(int) * (B + 1), &st));
-        std::memcpy(st, first.data(), sizeof(int) * (B + 1));
-        HGMM_HIP(c, hipMemcpyAsync(seg_a, st, sizeof(int) * (B + 1), hipMemcpyHostToDevice, c->stream));
-    }
+    HGMM_TRY(stage_h2d(c, seg_a, first.data(), sizeof(int) * (B + 1)));
 
     const double* xs_cur = xs_a;
     int* seg_cur = seg_a;
@@ -588,16 +520,8 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
             ll_stride = std::max(ll_stride, llblocks);
         }
         if (l == 0) ll_stride = 0;                              // no log-likelihood workgroups at level 0
-        {
-            void* st = nullptr;
-            rc = stage_reserve(c, sizeof(ForestCloud) * B, &st);
-            if (rc != HGMM_OK) break;
-            std::memcpy(st, table.data(), sizeof(ForestCloud) * B);
-            if (hipMemcpyAsync(d_clouds, st, sizeof(ForestCloud) * B, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-                rc = fail(c, HGMM_ERR_HIP, "tree build (batch): upload of the cloud table failed");
-                break;
-            }
-        }
+        rc = stage_h2d(c, d_clouds, table.data(), sizeof(ForestCloud) * B);
+        if (rc != HGMM_OK) break;
         const ForestArgs fa{d_clouds, B, (int)T, 3 * l, ls, max_iters_per_level, trace_base, trace_cap, L, l, words_dev};
         tree_chunks_kernel<<<1, 1024, 0, c->stream>>>(seg_cur, P, chunk_first, chunk_desc, n_chunks_dev);
         const unsigned grid_chunks = (unsigned)(n / CH + P + 1);
@@ -643,18 +567,9 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         int enq = 0;
         unsigned spins = 0;
         while (rc == HGMM_OK) {
-            bool all_done = true;
-            int it_min = 0x7fffffff;
-            unsigned long long sig = 0;
-            for (int b = 0; b < B; ++b) {
-                const unsigned long long w = __atomic_load_n(words + b, __ATOMIC_RELAXED);
-                sig += w;
-                if (w >> 32) continue;
-                all_done = false;
-                it_min = std::min(it_min, (int)(w & 0xffffffffull));
-            }
-            if (all_done) break;
-            if (enq < max_iters_per_level && enq - it_min < ahead_iters) {
+            const Progress pg = scan_progress(words, B);
+            if (pg.all_done) break;
+            if (enq < max_iters_per_level && enq - pg.it_min < ahead_iters) {
                 rc = enqueue_iteration(enq);
                 ++enq;
                 if (rc == HGMM_OK && enq == max_iters_per_level) {
@@ -664,18 +579,7 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
                 spins = 0;
                 continue;
             }
-            __builtin_ia32_pause();
-            if ((++spins & 0x3fff) == 0) {                      // every ~16k polls: is the device still alive?
-                const hipError_t qe = hipStreamQuery(c->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady) {
-                    rc = fail(c, HGMM_ERR_HIP, "tree build (batch): device error: %s", hipGetErrorString(qe));
-                } else if (qe == hipSuccess) {
-                    unsigned long long sig2_ = 0;
-                    for (int b = 0; b < B; ++b) sig2_ += __atomic_load_n(words + b, __ATOMIC_ACQUIRE);
-                    if (sig2_ == sig)
-                        rc = fail(c, HGMM_ERR_STATE, "tree build (batch): level %d made no progress (%d iterations enqueued)", l, enq);
-                }
-            }
+            rc = device_watch(c, &spins, words, B, pg.sig, "tree build (batch): level %d (%d iterations enqueued)", l, enq);
         }
         if (rc != HGMM_OK) break;
         for (int b = 0; b < B; ++b) level_iters[(size_t)b * L + l] = (int)(__atomic_load_n(words + b, __ATOMIC_ACQUIRE) & 0xffffffffull);
@@ -823,23 +727,20 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
         return fail(c, HGMM_ERR_STATE, "registration (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
     const int T = F.T, L = F.L;
     const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
-    if (c->fr_momq.cap < momq_bytes || !c->fr_momq.p) F.momq_clean = false;
-    HGMM_TRY(ensure(c, c->fr_momq, momq_bytes));
-    if (!F.momq_clean) {
-        HGMM_HIP(c, hipMemsetAsync(c->fr_momq.p, 0, c->fr_momq.cap, c->stream));
-        F.momq_clean = true;
+    if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
+        MomqScope sums(F.momq_clean);
+        HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
+        HGMM_TRY(forest_register_on_device(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(),
+                                           F.tg_rmax.data(), F.mu_rmax.data(), c->fr_prep.as<double>(), T, L,
+                                           c->fr_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
+                                           q_prev_inout, iters_out, status_out, trace));
+        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
+        return HGMM_OK;
     }
-    if (c->cfg[CFG_REG_DEVICE_SOLVE])
-        return forest_register_on_device(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(),
-                                         F.tg_rmax.data(), F.mu_rmax.data(), c->fr_prep.as<double>(), T, L,
-                                         c->fr_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                         q_prev_inout, iters_out, status_out, trace);
-    unsigned long long* words = nullptr;
-    double* h_out = nullptr;
-    HGMM_TRY(forest_host(c, B, &words, &h_out));
-    void *d_words = nullptr, *d_hout = nullptr;
-    HGMM_HIP(c, hipHostGetDevicePointer(&d_words, words, 0));
-    HGMM_HIP(c, hipHostGetDevicePointer(&d_hout, h_out, 0));
+    HandOver* hand = nullptr;
+    HGMM_TRY(hand_over(c, B, &hand));
+    const HostDev<unsigned long long> words = hand->sequence(0);
+    const HostDev<double> h_out = hand->out28(0);
     ForestRegPair* d_tab = c->fr_reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
     std::vector<ForestRegPair> tab(B);
@@ -853,28 +754,13 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
     int n_active = B;
     for (int it = 0; it < max_iter && n_active > 0; ++it) {
         for (int b = 0; b < B; ++b) {
-            ForestRegPair& pr = tab[b];
-            std::memset(&pr, 0, sizeof pr);
-            pr.active = active[b];
-            pr.tg_first = (int)F.tg_first[b];
-            pr.tg_count = (int)F.tg_counts[b];
-            if (!active[b]) continue;
-            for (int i = 0; i < 9; ++i) pr.tf.r[i] = rot[9 * b + i];
-            for (int i = 0; i < 3; ++i) pr.tf.t[i] = t[3 * b + i];
-            pr.tf.s = scale;
-            double D = 1.0;
-            int Fb = 0;
-            reg_encoding(reg_extent(pr.tf, F.tg_rmax[b], F.mu_rmax[b]), (double)F.tg_counts[b], &D, &Fb);
-            pr.inv_d = 1.0 / D;
-            pr.fix_scale = std::ldexp(1.0, Fb);
-            pr.d_ext = D;
-            pr.inv_scale = std::ldexp(1.0, -Fb);
+            tab[b] = reg_pair(F.tg_first[b], F.tg_counts[b]);
+            if (active[b]) reg_pair_fill(tab[b], rigid_from(rot + 9 * b, t + 3 * b, scale), F.tg_rmax[b], F.mu_rmax[b]);
         }
-        void* st = nullptr;
-        HGMM_TRY(stage_reserve(c, sizeof(ForestRegPair) * B, &st));
-        std::memcpy(st, tab.data(), sizeof(ForestRegPair) * B);
-        HGMM_HIP(c, hipMemcpyAsync(d_tab, st, sizeof(ForestRegPair) * B, hipMemcpyHostToDevice, c->stream));
-        const unsigned long long seq = ++F.seq;
+        HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
+        const unsigned long long seq = ++hand->seq;
+        MomqScope sums(F.momq_clean);                  // (one memset before the first iteration; every later one finds the words zero)
+        HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
         {
             ProfScope prof(c, HGMM_K_TREE_REG);
             forest_reg_estep_kernel<4><<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(
@@ -882,8 +768,7 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
                 (int)nblk(longest, CH));
         }
         forest_reg_normal_kernel<<<B, 256, 0, c->stream>>>(c->fr_momq.as<unsigned long long>(), d_tab, c->fr_prep.as<double>(), T,
-                                                          d_out, static_cast<double*>(d_hout),
-                                                          static_cast<unsigned long long*>(d_words), seq);
+                                                          d_out, h_out.dev, words.dev, seq);
         HGMM_HIP(c, hipGetLastError());
         // every active pair's normal equations arrive with its own sequence word; each is solved as soon as it is there
         std::vector<char> pending(active);
@@ -891,13 +776,16 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
         unsigned spins = 0;
         while (n_pending > 0) {
             bool progressed = false;
+            unsigned long long seen = 0;                   // signature of the sequence words as this pass read them
             for (int b = 0; b < B; ++b) {
-                if (!pending[b] || __atomic_load_n(words + b, __ATOMIC_ACQUIRE) != seq) continue;
+                const unsigned long long w = __atomic_load_n(words.host + b, __ATOMIC_ACQUIRE);
+                seen += w;
+                if (!pending[b] || w != seq) continue;
                 pending[b] = 0;
                 --n_pending;
                 progressed = true;
                 double q = 0.0;
-                const int stp = reg_host_step(h_out + 28 * b, rot + 9 * b, t + 3 * b, q_prev_inout + b, tol, &q);
+                const int stp = reg_host_step(h_out.host + 28 * b, rot + 9 * b, t + 3 * b, q_prev_inout + b, tol, &q);
                 if (stp == 2) { status_out[b] = 2; active[b] = 0; --n_active; continue; }
                 if (trace) {
                     double* tr = trace + ((size_t)b * max_iter + it) * 13;
@@ -909,18 +797,9 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
                 if (stp == 1) { status_out[b] = 1; active[b] = 0; --n_active; }
             }
             if (progressed) { spins = 0; continue; }
-            __builtin_ia32_pause();
-            if ((++spins & 0x3fff) == 0) {
-                const hipError_t qe = hipStreamQuery(c->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady)
-                    return fail(c, HGMM_ERR_HIP, "registration (batch): device error: %s", hipGetErrorString(qe));
-                if (qe == hipSuccess) {
-                    bool still = false;
-                    for (int b = 0; b < B; ++b) still = still || (pending[b] && __atomic_load_n(words + b, __ATOMIC_ACQUIRE) != seq);
-                    if (still) return fail(c, HGMM_ERR_STATE, "registration (batch): the normal-equation kernel did not report (sequence %llu)", seq);
-                }
-            }
+            HGMM_TRY(device_watch(c, &spins, words.host, B, seen, "registration (batch): the normal-equation kernel (sequence %llu)", seq));
         }
+        sums.consumed();                               // every active pair has reported: its kernel zeroed the words it read
     }
     return HGMM_OK;
 }
@@ -941,23 +820,15 @@ extern "C" int hgmm_tree_score_batch(hgmm_ctx* c, int B, const double* rot, cons
     std::vector<ForestRegPair> tab(B);
     int64_t longest = 0;
     for (int b = 0; b < B; ++b) {
-        ForestRegPair& pr = tab[b];
-        std::memset(&pr, 0, sizeof pr);
-        pr.tg_first = (int)F.tg_first[b];
-        pr.tg_count = (int)F.tg_counts[b];
-        for (int i = 0; i < 9; ++i) pr.tf.r[i] = rot ? rot[9 * b + i] : ((i % 4 == 0) ? 1.0 : 0.0);
-        for (int i = 0; i < 3; ++i) pr.tf.t[i] = t ? t[3 * b + i] : 0.0;
-        pr.tf.s = scale;
+        tab[b] = reg_pair(F.tg_first[b], F.tg_counts[b]);
+        tab[b].tf = rigid_from(rot ? rot + 9 * b : nullptr, t ? t + 3 * b : nullptr, scale);
         longest = std::max(longest, F.tg_counts[b]);
     }
     const unsigned gx = nblk(longest, CH);
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * ((size_t)SCORE_NSUM * gx + 8) * B));
     double* partial = c->scratch.as<double>();
     double* d_sum = partial + (size_t)SCORE_NSUM * gx * B;
-    void* st = nullptr;
-    HGMM_TRY(stage_reserve(c, sizeof(ForestRegPair) * B, &st));
-    std::memcpy(st, tab.data(), sizeof(ForestRegPair) * B);
-    HGMM_HIP(c, hipMemcpyAsync(d_tab, st, sizeof(ForestRegPair) * B, hipMemcpyHostToDevice, c->stream));
+    HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
         forest_score_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(c->fr_tg.as<double>(), F.tg_pad, d_tab, c->fr_prep.as<double>(),

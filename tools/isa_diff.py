@@ -5,7 +5,12 @@
 
 Extracts the device code objects (llvm-objdump --offloading), disassembles them and compares the instruction streams
 kernel by kernel (addresses and branch targets stripped).  Used to show that a refactoring left the serial kernels'
-code untouched (round 6: the device building blocks moved into csrc/tree_device.h and gained FOREST template flags)."""
+code untouched (round 6: the device building blocks moved into csrc/tree_device.h and gained FOREST template flags).
+
+An address also hides in the pc-relative pair  s_getpc_b64 s[N:N+1] ; s_add_u32 sN, sN, <literal> ; s_addc_u32 ...  that
+reaches a constant table of the code object: the literal is the table's distance from the instruction, and it moves
+when kernels join or leave the translation unit (csrc/fullcov_kernels.hip split off csrc/tree_kernels.hip).  It is
+stripped like a branch target, in exactly that position; so is the padding behind the last kernel of a section."""
 import hashlib
 import os
 import re
@@ -40,7 +45,13 @@ def kernels(path):
                     continue
                 ins = line.split("//")[0].strip()
                 ins = re.sub(r"\b(s_cbranch_\w+|s_branch)\s+\S+", r"\1 L", ins)
+                m = re.match(r"s_getpc_b64 s\[(\d+):\d+\]$", out[name][-1]) if out[name] else None
+                if m:
+                    ins = re.sub(r"^(s_add_u32 s%s, s%s), (0x[0-9a-f]+|-?\d+)$" % (m.group(1), m.group(1)), r"\1, PCREL", ins)
                 out[name].append(ins)
+            for body in out.values():                      # padding behind a section's last kernel
+                while body and body[-1] in ("...", "s_nop 0", "s_code_end"):
+                    body.pop()
         return out
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
