@@ -155,6 +155,9 @@ def load_library(path: str = LIB_PATH):
                                                _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_score", [ctx, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_score_batch", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp])
+        _sig(lib, "hgmm_tree_register_multi", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
+                                               _vp, _vp, _vp])
+        _sig(lib, "hgmm_tree_score_multi", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp])
         _lib = lib
         return lib
 
@@ -1130,6 +1133,34 @@ class Context:
         self._check(self.lib.hgmm_tree_score_batch(self.h, B, _ptr(rot) if B else None, _ptr(t) if B else None, float(scale),
                                                    float(lambda_c), float(maha2_max), _ptr(summary)))
         return summary[:B]
+
+    # -- multi-start: K start poses of the serial pair per launch set (hgmm_tree_register_multi / hgmm_tree_score_multi) ----
+    def tree_register_multi(self, rot, t, scale=1.0, lambda_c=0.01, max_iter=20, tol=1.0e-4, q_prev=None, want_trace=False):
+        """:meth:`tree_register` from K start poses at once on the resident tree and target (hgmm_tree_register_multi), each
+        hypothesis bitwise the serial call from that start.  ``rot`` [K,3,3], ``t`` [K,3].
+        -> (rot [K,3,3], t [K,3], iterations [K], q [K] (NaN: none), status [K], traces or None)."""
+        rot = np.array(rot, dtype=np.float64).reshape(-1, 3, 3)
+        K = rot.shape[0]
+        t = np.array(t, dtype=np.float64).reshape(K, 3)
+        q = np.full(K, np.nan) if q_prev is None else np.array(q_prev, dtype=np.float64).reshape(K)
+        iters, status = np.zeros(K, np.int32), np.zeros(K, np.int32)
+        trace = np.zeros((max(K, 1), max(int(max_iter), 1), 13)) if want_trace else None
+        self._check(self.lib.hgmm_tree_register_multi(self.h, K, _ptr(rot) if K else None, _ptr(t) if K else None, float(scale),
+                                                      float(lambda_c), int(max_iter), float(tol), _ptr(q), _ptr(iters),
+                                                      _ptr(status), _ptr(trace)))
+        traces = [trace[k, :iters[k]] for k in range(K)] if want_trace else None
+        return rot, t, iters, q, status, traces
+
+    def tree_score_multi(self, rot, t, scale=1.0, lambda_c=0.01, maha2_max=CHI2_3_99):
+        """:meth:`tree_score`'s summary of the resident target at K poses in one launch (hgmm_tree_score_multi), each bitwise
+        the serial call's at that pose.  ``rot`` [K,3,3], ``t`` [K,3]  -> summaries [K,8]."""
+        rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 3, 3)
+        K = rot.shape[0]
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(K, 3)
+        summary = np.empty((max(K, 1), 8))
+        self._check(self.lib.hgmm_tree_score_multi(self.h, K, _ptr(rot) if K else None, _ptr(t) if K else None, float(scale),
+                                                   float(lambda_c), float(maha2_max), _ptr(summary)))
+        return summary[:K]
 
     @staticmethod
     def _node_tables(pi, mu, cov):

@@ -130,6 +130,7 @@ struct TreeState {
     bool pdf_f32 = false;             // hgmm_tree_set_precision: the level log-likelihood's pdfs in float32 (large clouds)
     double mu_rmax = -1.0;            // largest |mu_j| of the node table (< 0: not known on the host yet)
     bool momq_clean = false;          // every word of t_momq is zero (tree_host.h: MomqScope)
+    bool multi_momq_clean = false;    // ... of tm_momq, the sums of hgmm_tree_register_multi's K hypotheses
     unsigned long long surplus_iterations = 0;   // (communicator) level-iterations enqueued behind a level's stop, all builds
 };
 
@@ -235,6 +236,9 @@ struct hgmm_ctx {
     bool ff_clocks_on = false;
     hgmm::DevBuf ff_origin;                   // double [256][3] partial coordinate sums: origin of the float32 full-covariance statistics
     hgmm::DevBuf fr_reg;                      // per-pair registration table + the 28 numbers per pair + per-pair r2max words
+    // multi-start (hgmm_tree_register_multi / _score_multi): K start poses on the SERIAL tree and target, buffers of their own
+    hgmm::DevBuf tm_momq;                     // uint64 [K][T][4] registration sums, one slice per hypothesis
+    hgmm::DevBuf tm_reg;                      // per-hypothesis registration table + the 28 numbers per hypothesis
 
     // ---- KMeans initialiser (float64, on x_soa64) -----------------------------------
     hgmm::DevBuf km_closest;                  // double [n_pad] k-means++: min squared distance so far

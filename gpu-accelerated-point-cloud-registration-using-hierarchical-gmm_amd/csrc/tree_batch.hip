@@ -318,6 +318,77 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
     }
 }
 
+// ---- multi-start: K start poses of ONE pair per launch set (hgmm_tree_register_multi / hgmm_tree_score_multi) -----------------
+// The forest's registration kernels with the tree and the target SHARED: `prep` is the one resident tree's table, every table
+// entry names the same target (tg_first = 0, tg_count = n), and what hypothesis k owns is its entry (pose, encoding, loop
+// state) and slice k of the [K][T][NMQ] sums.  Same argument lists as the forest kernels, so the host loops below launch either
+// set.  A workgroup serves ONE hypothesis: its LDS table of levels 0..2 would have to be flushed per hypothesis otherwise,
+// and the 24 B / point a second hypothesis would save come out of L2 anyway.
+template <int NMQ>
+__global__ __launch_bounds__(CH) void tree_reg_multi_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
+                                                                  const ForestRegPair* __restrict__ tab,
+                                                                  const double* __restrict__ prep, int T, int L,
+                                                                  double lambda_c, unsigned long long* __restrict__ momq, int gx) {
+    __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
+    const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x K items: hypothesis k, chunk bx)
+    const int k = item / gx, bx = item - k * gx;
+    const ForestRegPair* pr = tab + k;
+    const int active = pr->active, count = pr->tg_count;
+    if (!active || (int64_t)bx * CH >= count) return;
+    const Rigid tf = pr->tf;
+    const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
+    const int64_t i = (int64_t)bx * CH + threadIdx.x;
+    tree_reg_estep_body<NMQ>(i, i < count, tg, tg_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq + (size_t)NMQ * T * k, lds);
+}
+
+__global__ __launch_bounds__(256) void tree_reg_multi_normal_kernel(unsigned long long* __restrict__ momq,
+                                                                    const ForestRegPair* __restrict__ tab,
+                                                                    const double* __restrict__ prep, int T,
+                                                                    double* __restrict__ out, double* host_out,
+                                                                    unsigned long long* host_seq, unsigned long long seq) {
+    const int k = blockIdx.x;
+    const ForestRegPair* pr = tab + k;
+    if (!pr->active) return;
+    tree_reg_normal_body(momq + (size_t)4 * T * k, pr->d_ext, pr->inv_scale, prep, T, out + 28 * k, host_out + 28 * k,
+                         host_seq + k, seq);
+}
+
+// reg_device_solve: forest_reg_solve_kernel on the shared tree
+__global__ __launch_bounds__(256) void tree_reg_multi_solve_kernel(unsigned long long* __restrict__ momq, ForestRegPair* tab,
+                                                                   const double* __restrict__ prep, int T,
+                                                                   double* __restrict__ out, double tol, int max_iter,
+                                                                   double* __restrict__ trace, unsigned long long* host_words) {
+    const int k = blockIdx.x;
+    ForestRegPair* pr = tab + k;
+    if (!pr->active) return;
+    tree_reg_normal_body(momq + (size_t)4 * T * k, pr->d_ext, pr->inv_scale, prep, T, out + 28 * k, nullptr, nullptr, 0ull);
+    __syncthreads();                                         // (the 28 sums are in `out`, written by this workgroup)
+    if (threadIdx.x == 0) {
+        const int it = pr->it;
+        reg_device_step(out + 28 * k, pr, tol, max_iter, trace ? trace + ((size_t)k * max_iter + it) * 13 : nullptr);
+        __hip_atomic_store(host_words + k, ((unsigned long long)(pr->active ? 0 : 1) << 32) | (unsigned long long)(unsigned)pr->it,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// the score of every hypothesis: tree_score_kernel's grouping (workgroups start at the target's first point), partial [K][gx][6]
+__global__ __launch_bounds__(CH) void tree_score_multi_kernel(const double* __restrict__ tg, int64_t n, int64_t tg_pad,
+                                                              const ForestRegPair* __restrict__ tab,
+                                                              const double* __restrict__ prep, int L, double lambda_c,
+                                                              double maha2_max, double* __restrict__ partial, int gx) {
+    const int item = (int)blockIdx.x;
+    const int k = item / gx, bx = item - k * gx;
+    const Rigid tf = tab[k].tf;
+    const int64_t i = (int64_t)bx * CH + threadIdx.x;
+    tree_score_body(i, i, i < n, tg, tg_pad, tf, prep, L, lambda_c, maha2_max, nullptr, nullptr, nullptr,
+                    partial + (size_t)SCORE_NSUM * item);
+}
+__global__ __launch_bounds__(CH) void tree_score_multi_finish_kernel(const double* __restrict__ partial, int gx, double n_points,
+                                                                     double* __restrict__ summary) {
+    const int k = blockIdx.x;
+    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * k, gx, n_points, summary + 8 * k);
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -329,13 +400,16 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
                               const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
                               int L, unsigned long long* momq, double* rot, double* t, double scale, double lambda_c,
                               int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                              double* trace) {
+                              double* trace, bool shared_tree, DevBuf* table) {
     for (int b = 0; b < B; ++b) { iters_out[b] = 0; status_out[b] = 0; }
     if (max_iter < 1) return HGMM_OK;
-    HGMM_TRY(ensure(c, c->fr_reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
+    DevBuf& reg = table ? *table : c->fr_reg;
+    HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
     const size_t trace_bytes = trace ? sizeof(double) * 13 * (size_t)max_iter * B : 0;
     if (trace) HGMM_TRY(ensure(c, c->fr_trace, trace_bytes));
-    ForestRegPair* d_tab = c->fr_reg.as<ForestRegPair>();
+    const auto estep_kernel = shared_tree ? tree_reg_multi_estep_kernel<4> : forest_reg_estep_kernel<4>;
+    const auto solve_kernel = shared_tree ? tree_reg_multi_solve_kernel : forest_reg_solve_kernel;
+    ForestRegPair* d_tab = reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
     double* d_trace = trace ? c->fr_trace.as<double>() : nullptr;
     HandOver* hand = nullptr;
@@ -361,10 +435,10 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
         if (enq < max_iter && enq - pg.it_min < ahead) {
             {
                 ProfScope prof(c, HGMM_K_TREE_REG);
-                forest_reg_estep_kernel<4><<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c, momq,
-                                                                                                  (int)nblk(longest, CH));
+                estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c, momq,
+                                                                                    (int)nblk(longest, CH));
             }
-            forest_reg_solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace, words.dev);
+            solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace, words.dev);
             HGMM_HIP(c, hipGetLastError());
             ++enq;
             spins = 0;
@@ -716,32 +790,23 @@ extern "C" int hgmm_tree_set_targets_batch_f32(hgmm_ctx* c, int B, const float* 
     return set_targets_batch<float>(c, B, xyz, counts);
 }
 
-extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double* t, double scale, double lambda_c,
-                                        int max_iter, double tol, double* q_prev_inout, int32_t* iters_out,
-                                        int32_t* status_out, double* trace) {
-    HGMM_ENTER(c);
-    if (!rot || !t || !q_prev_inout || !iters_out || !status_out) return fail(c, HGMM_ERR_ARG, "tree_register (batch): NULL argument");
-    ForestState& F = c->forest;
-    if (!F.nodes_ready) return fail(c, HGMM_ERR_STATE, "registration (batch): no forest (hgmm_tree_build_batch first)");
-    if (B != F.B || B != F.tg_B)
-        return fail(c, HGMM_ERR_STATE, "registration (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
-    const int T = F.T, L = F.L;
+// The registration loop of B pairs with the 6 x 6 solves on the host (the default): per iteration one E-step launch and one
+// normal-equations launch for all pairs still running, each pair's 28 numbers solved as soon as its sequence word arrives.
+// The arguments are forest_register_on_device's; `momq` / `momq_clean`: the set's sums and their MomqScope flag.
+static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t tg_pad, const int64_t* tg_first,
+                                   const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
+                                   int L, DevBuf& momq, bool& momq_clean, double* rot, double* t, double scale, double lambda_c,
+                                   int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
+                                   double* trace, bool shared_tree, DevBuf& reg) {
     const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
-    if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
-        MomqScope sums(F.momq_clean);
-        HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
-        HGMM_TRY(forest_register_on_device(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(),
-                                           F.tg_rmax.data(), F.mu_rmax.data(), c->fr_prep.as<double>(), T, L,
-                                           c->fr_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, iters_out, status_out, trace));
-        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
-        return HGMM_OK;
-    }
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, B, &hand));
     const HostDev<unsigned long long> words = hand->sequence(0);
     const HostDev<double> h_out = hand->out28(0);
-    ForestRegPair* d_tab = c->fr_reg.as<ForestRegPair>();
+    HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
+    const auto estep_kernel = shared_tree ? tree_reg_multi_estep_kernel<4> : forest_reg_estep_kernel<4>;
+    const auto normal_kernel = shared_tree ? tree_reg_multi_normal_kernel : forest_reg_normal_kernel;
+    ForestRegPair* d_tab = reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
     std::vector<ForestRegPair> tab(B);
     std::vector<char> active(B, 1);
@@ -749,26 +814,24 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
     for (int b = 0; b < B; ++b) {
         iters_out[b] = 0;
         status_out[b] = 0;                                        // 0: budget used up, 1: |dq| < tol, 2: host M-step needed
-        longest = std::max(longest, F.tg_counts[b]);
+        longest = std::max(longest, tg_counts[b]);
     }
     int n_active = B;
     for (int it = 0; it < max_iter && n_active > 0; ++it) {
         for (int b = 0; b < B; ++b) {
-            tab[b] = reg_pair(F.tg_first[b], F.tg_counts[b]);
-            if (active[b]) reg_pair_fill(tab[b], rigid_from(rot + 9 * b, t + 3 * b, scale), F.tg_rmax[b], F.mu_rmax[b]);
+            tab[b] = reg_pair(tg_first[b], tg_counts[b]);
+            if (active[b]) reg_pair_fill(tab[b], rigid_from(rot + 9 * b, t + 3 * b, scale), tg_rmax[b], mu_rmax[b]);
         }
         HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
         const unsigned long long seq = ++hand->seq;
-        MomqScope sums(F.momq_clean);                  // (one memset before the first iteration; every later one finds the words zero)
-        HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
+        MomqScope sums(momq_clean);                  // (one memset before the first iteration; every later one finds the words zero)
+        HGMM_TRY(sums.open(c, momq, momq_bytes));
         {
             ProfScope prof(c, HGMM_K_TREE_REG);
-            forest_reg_estep_kernel<4><<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(
-                c->fr_tg.as<double>(), F.tg_pad, d_tab, c->fr_prep.as<double>(), T, L, lambda_c, c->fr_momq.as<unsigned long long>(),
-                (int)nblk(longest, CH));
+            estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c,
+                                                                                momq.as<unsigned long long>(), (int)nblk(longest, CH));
         }
-        forest_reg_normal_kernel<<<B, 256, 0, c->stream>>>(c->fr_momq.as<unsigned long long>(), d_tab, c->fr_prep.as<double>(), T,
-                                                          d_out, h_out.dev, words.dev, seq);
+        normal_kernel<<<B, 256, 0, c->stream>>>(momq.as<unsigned long long>(), d_tab, prep, T, d_out, h_out.dev, words.dev, seq);
         HGMM_HIP(c, hipGetLastError());
         // every active pair's normal equations arrive with its own sequence word; each is solved as soon as it is there
         std::vector<char> pending(active);
@@ -802,6 +865,32 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
         sums.consumed();                               // every active pair has reported: its kernel zeroed the words it read
     }
     return HGMM_OK;
+}
+
+extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double* t, double scale, double lambda_c,
+                                        int max_iter, double tol, double* q_prev_inout, int32_t* iters_out,
+                                        int32_t* status_out, double* trace) {
+    HGMM_ENTER(c);
+    if (!rot || !t || !q_prev_inout || !iters_out || !status_out) return fail(c, HGMM_ERR_ARG, "tree_register (batch): NULL argument");
+    ForestState& F = c->forest;
+    if (!F.nodes_ready) return fail(c, HGMM_ERR_STATE, "registration (batch): no forest (hgmm_tree_build_batch first)");
+    if (B != F.B || B != F.tg_B)
+        return fail(c, HGMM_ERR_STATE, "registration (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
+    const int T = F.T, L = F.L;
+    const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
+    if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
+        MomqScope sums(F.momq_clean);
+        HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
+        HGMM_TRY(forest_register_on_device(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(),
+                                           F.tg_rmax.data(), F.mu_rmax.data(), c->fr_prep.as<double>(), T, L,
+                                           c->fr_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
+                                           q_prev_inout, iters_out, status_out, trace));
+        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
+        return HGMM_OK;
+    }
+    return forest_register_on_host(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(), F.tg_rmax.data(),
+                                   F.mu_rmax.data(), c->fr_prep.as<double>(), T, L, c->fr_momq, F.momq_clean, rot, t, scale,
+                                   lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out, trace, false, c->fr_reg);
 }
 
 // hgmm_tree_score on every pair (tree b, target b) of the resident forest, summaries only: include/hgmm.h
@@ -838,5 +927,79 @@ extern "C" int hgmm_tree_score_batch(hgmm_ctx* c, int B, const double* rot, cons
     HGMM_HIP(c, hipGetLastError());
     HGMM_HIP(c, hipMemcpyAsync(summary_out, d_sum, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, c->stream));
     HGMM_HIP(c, ctx_stream_sync(c));
+    return HGMM_OK;
+}
+
+// ---- multi-start: K start poses of the SERIAL pair (hgmm_tree_build / _set_nodes + hgmm_tree_set_target): include/hgmm.h ------
+// what both entries ask of the context
+static int multi_state(hgmm_ctx* c, const char* what, int K) {
+    if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "%s: start poses of one pair take no communicator", what);
+    if (!c->tree.nodes_ready) return fail(c, HGMM_ERR_STATE, "%s: no tree (build or set_nodes first)", what);
+    if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "%s: no target (call hgmm_tree_set_target first)", what);
+    if (K < 1 || K > 4096) return fail(c, HGMM_ERR_ARG, "%s: K = %d start poses outside 1..4096", what, K);
+    if ((uint64_t)nblk(c->tgt_n, CH) * (uint64_t)K > 0x7fffffffull)                // (the grid: one workgroup per pose and chunk)
+        return fail(c, HGMM_ERR_ARG, "%s: %d start poses x %lld target points is too large", what, K, (long long)c->tgt_n);
+    return HGMM_OK;
+}
+
+extern "C" int hgmm_tree_register_multi(hgmm_ctx* c, int K, double* rot, double* t, double scale, double lambda_c,
+                                        int max_iter, double tol, double* q_prev_inout, int32_t* iters_out,
+                                        int32_t* status_out, double* trace) {
+    HGMM_ENTER(c);
+    HGMM_TRY(multi_state(c, "tree_register (multi)", K));
+    if (!rot || !t) return fail(c, HGMM_ERR_ARG, "tree_register (multi): rot / t is NULL (K start poses are the call's input)");
+    if (!q_prev_inout || !iters_out || !status_out) return fail(c, HGMM_ERR_ARG, "tree_register (multi): NULL output argument");
+    HGMM_TRY(tree_mu_rmax_resident(c));
+    const int T = c->tree.T, L = c->tree.L;
+    // every hypothesis names the same target and the same tree: the loops and reg_pair_fill take them per registration
+    const std::vector<int64_t> first(K, 0), counts(K, c->tgt_n);
+    const std::vector<double> tg_rmax(K, c->tgt_rmax), mu_rmax(K, c->tree.mu_rmax);
+    const double* tg = c->tgt_soa64.as<double>();
+    const double* prep = c->t_prep.as<double>();
+    if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
+        MomqScope sums(c->tree.multi_momq_clean);
+        HGMM_TRY(sums.open(c, c->tm_momq, sizeof(unsigned long long) * 4 * (size_t)T * K));
+        HGMM_TRY(forest_register_on_device(c, K, tg, c->tgt_pad, first.data(), counts.data(), tg_rmax.data(), mu_rmax.data(), prep,
+                                           T, L, c->tm_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
+                                           q_prev_inout, iters_out, status_out, trace, true, &c->tm_reg));
+        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
+        return HGMM_OK;
+    }
+    return forest_register_on_host(c, K, tg, c->tgt_pad, first.data(), counts.data(), tg_rmax.data(), mu_rmax.data(), prep, T, L,
+                                   c->tm_momq, c->tree.multi_momq_clean, rot, t, scale, lambda_c, max_iter, tol, q_prev_inout,
+                                   iters_out, status_out, trace, true, c->tm_reg);
+}
+
+extern "C" int hgmm_tree_score_multi(hgmm_ctx* c, int K, const double* rot, const double* t, double scale, double lambda_c,
+                                     double maha2_max, double* summary_out) {
+    HGMM_ENTER(c);
+    HGMM_TRY(multi_state(c, "tree_score (multi)", K));
+    if (!rot || !t) return fail(c, HGMM_ERR_ARG, "tree_score (multi): rot / t is NULL (K poses are the call's input)");
+    if (!summary_out) return fail(c, HGMM_ERR_ARG, "tree_score (multi): summary_out is NULL");
+    if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "tree_score (multi): maha2_max is NaN");
+    const int64_t n = c->tgt_n;
+    const unsigned gx = nblk(n, CH);
+    std::vector<ForestRegPair> tab(K);
+    for (int k = 0; k < K; ++k) {
+        tab[k] = reg_pair(0, n);
+        tab[k].tf = rigid_from(rot + 9 * k, t + 3 * k, scale);
+    }
+    HGMM_TRY(ensure(c, c->tm_reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)K + 512));
+    HGMM_TRY(ensure(c, c->scratch, sizeof(double) * ((size_t)SCORE_NSUM * gx + 8) * K));
+    ForestRegPair* d_tab = c->tm_reg.as<ForestRegPair>();
+    double* partial = c->scratch.as<double>();
+    double* d_sum = partial + (size_t)SCORE_NSUM * gx * K;
+    HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * K));
+    {
+        ProfScope prof(c, HGMM_K_TREE_SCORE);
+        tree_score_multi_kernel<<<gx * (unsigned)K, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, c->tgt_pad, d_tab,
+                                                                       c->t_prep.as<double>(), c->tree.L, lambda_c, maha2_max,
+                                                                       partial, (int)gx);
+    }
+    tree_score_multi_finish_kernel<<<K, CH, 0, c->stream>>>(partial, (int)gx, (double)n, d_sum);
+    HGMM_HIP(c, hipGetLastError());
+    StagedDownloads dl(c);
+    dl.add(summary_out, d_sum, sizeof(double) * 8 * K);
+    HGMM_HIP(c, dl.finish());
     return HGMM_OK;
 }

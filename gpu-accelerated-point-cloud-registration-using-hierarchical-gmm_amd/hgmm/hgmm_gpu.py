@@ -17,6 +17,7 @@ to the Numba file's (seed 72, sig2 = 0.004, hgmm_gpu.py:469-477) and can be over
 from __future__ import annotations
 
 import contextlib
+import itertools
 import time
 from collections import namedtuple
 
@@ -234,6 +235,45 @@ def tree_score_from_summary(summary, arrays=None):
         rmse, mrms, mld = float("inf"), float("inf"), float("-inf")
     return TreeScore(float(s[1] / s[0]) if n > 0 else 0.0, rmse, mrms, mld, n, n_in, int(s[5]), int(s[6]),
                      arrays.get("node"), arrays.get("maha2"), arrays.get("logp"))
+
+
+class MultiStartResult(ScoredResult):
+    """What :meth:`GMMTree.registration_multistart` returns for the winner: a :class:`ScoredResult` that also says which start
+    won (``best_index_``) and how many iterations its loop took (``n_iter_``)."""
+    best_index_ = None
+    n_iter_ = None
+
+
+def best_hypothesis(summaries, rot, t):
+    """The winner among K registered hypotheses, deterministic: most inliers (summary[1], an integer), then the smaller sum of
+    the inliers' squared Mahalanobis distances (summary[2]), then the lower index.  A hypothesis whose pose (rot[k], t[k]) is
+    not finite loses to every finite one.  ``summaries`` [K,8] as :meth:`Context.tree_score_multi` returns them.  -> index."""
+    s = np.asarray(summaries, dtype=np.float64).reshape(-1, 8)
+    K = len(s)
+    if K < 1:
+        raise ValueError("best_hypothesis: no hypotheses")
+    rot, t = np.asarray(rot, dtype=np.float64).reshape(K, 9), np.asarray(t, dtype=np.float64).reshape(K, 3)
+    finite = np.isfinite(rot).all(axis=1) & np.isfinite(t).all(axis=1)
+
+    def key(k):
+        if not finite[k]:
+            return (1, 0.0, 0.0, k)
+        inliers = s[k, 1] if np.isfinite(s[k, 1]) else -1.0
+        spread = s[k, 2] if np.isfinite(s[k, 2]) else np.inf
+        return (0, -inliers, spread, k)
+    return min(range(K), key=key)
+
+
+def rotation_starts(angles_deg=(-15, 0, 15), centre=None):
+    """Start poses for :meth:`GMMTree.registration_multistart`: the rotations Rz(az) Ry(ay) Rx(ax) for (ax, ay, az) in
+    ``itertools.product(angles_deg, repeat=3)`` order, each taken about ``centre`` (None: the origin), i.e. t = c - R c.
+    -> list of :class:`RigidTransformation`; with the default angles 27 poses, index 13 the identity."""
+    c = np.zeros(3) if centre is None else np.asarray(centre, dtype=np.float64).reshape(3)
+    out = []
+    for ax, ay, az in itertools.product(angles_deg, repeat=3):
+        rot = euler_matrix_xyz(*np.deg2rad([float(ax), float(ay), float(az)]))
+        out.append(RigidTransformation(rot, c - rot @ c))
+    return out
 
 
 def node_level(node):
@@ -467,6 +507,54 @@ class GMMTree():
             return ScoredResult(res.transformation, res.q, self._score_resident(maha2_max))
         return res
 
+    def registration_multistart(self, target, starts, maxiter=20, tol=1.0e-4, maha2_max=CHI2_3_99, return_all=False):
+        """:meth:`registration` from K start poses in the launches of one (``hgmm_tree_register_multi``), scored together
+        (``hgmm_tree_score_multi``); the best one wins (:func:`best_hypothesis`).  The registration is a local method: from
+        the identity a target turned by 30 degrees ends in a wrong minimum, and the score tells -- a grid of starts
+        (:func:`rotation_starts`) turns that into a success.
+
+        ``starts`` are initial values of the loop's OWN pose y = s R x + t, which moves the TARGET onto the tree -- what the
+        identity is in :meth:`registration` -- not the inverted object that :meth:`registration` returns; they share one
+        scale.  Every hypothesis is bit for bit what the serial loop gives from that start; one whose normal equations turn
+        ill-conditioned is finished through the serial path like a pair that leaves a batch.
+
+        -> :class:`MultiStartResult` (a ``ScoredResult(tf.inverse(), q, score)``) of the winner, with ``best_index_`` and
+        ``n_iter_`` (also set on this object); with ``return_all`` also a list of K ``ScoredResult``s -- only the winner's
+        score carries the per-point arrays (one serial ``hgmm_tree_score``)."""
+        starts = list(starts)
+        if not starts:
+            raise ValueError("registration_multistart: no start poses")
+        scale = float(starts[0].scale)
+        if any(float(s.scale) != scale for s in starts):
+            raise ValueError("registration_multistart: the start poses must share one scale")
+        ctx = self._ctx
+        ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
+        ctx.tree_set_target(_points(target))
+        rot0 = np.stack([np.asarray(s.rot, dtype=np.float64).reshape(3, 3) for s in starts])
+        t0 = np.stack([np.asarray(s.t, dtype=np.float64).reshape(3) for s in starts])
+        with (ctx.config(reg_device_solve=1) if self._solve_on_device else contextlib.nullcontext()):
+            rot, t, iters, q, status, _ = ctx.tree_register_multi(rot0, t0, scale, self._lambda_c, maxiter, tol)
+        iters = [int(v) for v in iters]
+        for k in np.nonzero(status == 2)[0]:                      # finish this hypothesis through the serial entries
+            self._tf_result = RigidTransformation(rot[k].copy(), t[k].copy(), scale)
+            res = self._registration_in_library(maxiter, tol, _resume=(iters[k], None if np.isnan(q[k]) else float(q[k]), True))
+            rot[k], t[k] = self._tf_result.rot, self._tf_result.t
+            q[k] = float(res.q[0]) if np.size(res.q) else np.nan
+            iters[k] = int(self.n_iter_)
+        sums = ctx.tree_score_multi(rot, t, scale, self._lambda_c, maha2_max)
+        best = best_hypothesis(sums, rot, t)
+        poses = [RigidTransformation(rot[k].copy(), t[k].copy(), scale) for k in range(len(starts))]
+        qs = [np.array([q[k]]) if not np.isnan(q[k]) else np.array([]) for k in range(len(starts))]
+        self._tf_result = poses[best]
+        self.best_index_, self.n_iter_ = int(best), iters[best]
+        winner = MultiStartResult(poses[best].inverse(), qs[best], self._score_resident(maha2_max))
+        winner.best_index_, winner.n_iter_ = int(best), iters[best]
+        if not return_all:
+            return winner
+        every = [winner if k == best else ScoredResult(poses[k].inverse(), qs[k], tree_score_from_summary(sums[k]))
+                 for k in range(len(starts))]
+        return winner, every
+
     def _registration(self, target, maxiter, tol):
         self._ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
         self._ctx.tree_set_target(_points(target))
@@ -521,9 +609,12 @@ def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
     return src, tgt @ rot.T + np.asarray(translation)
 
 
-def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, **kargs):
-    """hgmm_gpu.py:802-807.  ``return_score=True``: ScoredResult(transformation, q, score) -- see :meth:`GMMTree.registration`."""
+def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, starts=None, **kargs):
+    """hgmm_gpu.py:802-807.  ``return_score=True``: ScoredResult(transformation, q, score) -- see :meth:`GMMTree.registration`.
+    ``starts`` (a list of start poses, e.g. :func:`rotation_starts`): :meth:`GMMTree.registration_multistart`'s result."""
     gt = GMMTree(_points(source), **kargs)
+    if starts is not None:
+        return gt.registration_multistart(_points(target), starts, maxiter, tol)
     gt.set_callbacks(callbacks)
     return gt.registration(_points(target), maxiter, tol, return_score=return_score)
 

@@ -367,6 +367,30 @@ int hgmm_tree_score(hgmm_ctx* ctx, const double* rot, const double* t, double sc
                     int32_t* node_out, double* maha2_out, double* logp_out, double* summary_out /* [8] */);
 int hgmm_tree_score_batch(hgmm_ctx* ctx, int B, const double* rot /* [B,9] */, const double* t /* [B,3] */, double scale,
                           double lambda_c, double maha2_max, double* summary_out /* [B,8] */);
+/* ---- multi-start: K start poses of ONE pair per launch set ---------------------------------------------------------------
+ * hgmm_tree_register is a local method: it follows the twist updates from its start to the nearest minimum.  These entries
+ * run it from K starts at once on the SERIAL state -- the tree of hgmm_tree_build / hgmm_tree_set_nodes and the target of
+ * hgmm_tree_set_target, both resident once -- and score the K outcomes, so that the caller keeps the start the score likes
+ * best.  They neither read nor disturb a resident forest or the serial entries' own sums.
+ * hgmm_tree_register_multi   <- K x hgmm_tree_register from (rot[k], t[k]): rot [K][9], t [K][3], q_prev [K] (NaN: none)
+ *                            updated in place; iters [K]; status [K] with hgmm_tree_register's codes 0 / 1 / 2 (a hypothesis
+ *                            that stops costs the remaining launches one load; one that meets status 2 leaves at that
+ *                            iteration and the caller finishes it through the serial entries, as a pair of a batch); trace
+ *                            (optional) [K][max_iter][13].  One E-step launch of K x ceil(n / 256) workgroups and one
+ *                            normal-equations launch of K workgroups per iteration; the 6 x 6 solves on the host unless the
+ *                            context's reg_device_solve option is set (then one device thread per hypothesis).
+ * hgmm_tree_score_multi      <- K x hgmm_tree_score at the poses rot [K][9], t [K][3], summaries [K][8] only (the per-point
+ *                            arrays of one pose: the serial entry).
+ * The moments are 64-bit fixed-point integer sums and the score's shares are added in a fixed order, so hypothesis k comes out
+ * bit for bit as the serial entry from that start / at that pose.
+ * Errors: HGMM_ERR_STATE without a tree or a target, or under a communicator; HGMM_ERR_ARG for K < 1 (or > 4096), NULL
+ * rot / t (the poses are the input: no identity default), NULL outputs, a NaN maha2_max.                                   */
+int hgmm_tree_register_multi(hgmm_ctx* ctx, int K, double* rot /* [K,9] */, double* t /* [K,3] */, double scale,
+                             double lambda_c, int max_iter, double tol, double* q_prev_inout /* [K], NaN = none */,
+                             int32_t* iters_out /* [K] */, int32_t* status_out /* [K] */,
+                             double* trace /* optional [K,max_iter,13] */);
+int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, const double* t /* [K,3] */, double scale,
+                          double lambda_c, double maha2_max, double* summary_out /* [K,8] */);
 /* The steps buildGMMTree is made of, one at a time (reference function granularity).  Node tables
  * hold T nodes (any T >= 8, need not be a complete tree).
  * hgmm_tree_estep  <- gmmTreeEStep()       hgmm_cupy_cpu_working.py:162-191: parent_idx[N] arbitrary
