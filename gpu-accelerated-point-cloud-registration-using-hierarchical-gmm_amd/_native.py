@@ -24,6 +24,8 @@ KERNEL_IDS = {"flat_estep": 0, "flat_fused": 1, "flat_mstep": 2, "tree_estep": 3
 # default inlier bound of the tree score: the 0.99 quantile of chi-square with three degrees of freedom (the squared
 # Mahalanobis distance of a point drawn from its own Gaussian)
 CHI2_3_99 = 11.344866730144373
+# the 0.999 quantile: a suggested ``maha2_gate`` of the registration E-step (Context.tree_set_reg_gate), not a default
+CHI2_3_999 = 16.27
 
 
 class HgmmError(RuntimeError):
@@ -106,6 +108,8 @@ def load_library(path: str = LIB_PATH):
                                       _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)])
         _sig(lib, "hgmm_tree_set_nodes", [ctx, C.c_int, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_set_precision", [ctx, C.c_int])
+        _sig(lib, "hgmm_tree_set_reg_gate", [ctx, C.c_double])
+        _sig(lib, "hgmm_tree_get_reg_gate", [ctx, _f64p])
         _sig(lib, "hgmm_tree_set_target", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_reg_estep", [ctx, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_reg_normal", [ctx, _vp, _vp, C.c_double, C.c_double, _vp])
@@ -951,6 +955,21 @@ class Context:
         self._check(self.lib.hgmm_tree_set_precision(self.h, 1 if dt == np.dtype(np.float32) else 0))
         self.tree_dtype = dt
         return self
+
+    def tree_set_reg_gate(self, maha2_gate):
+        """Mahalanobis gate of the registration E-step (hgmm_tree_set_reg_gate): a (point, node) pair whose squared
+        Mahalanobis distance exceeds ``maha2_gate`` adds nothing to that node's moments; the descent is unchanged.
+        ``np.inf`` (the default of a context): off.  Honoured by tree_reg_estep, tree_reg_normal, tree_register,
+        tree_register_multi and tree_register_batch, not by the scores; in force until set again.  The library refuses
+        NaN and values <= 0 (HgmmError) and keeps the previous gate.  ``CHI2_3_999`` is a reasonable value."""
+        self._check(self.lib.hgmm_tree_set_reg_gate(self.h, float(maha2_gate)))
+        return self
+
+    def tree_get_reg_gate(self):
+        """The gate in force (hgmm_tree_get_reg_gate); ``inf``: off."""
+        g = C.c_double()
+        self._check(self.lib.hgmm_tree_get_reg_gate(self.h, C.byref(g)))
+        return float(g.value)
 
     def tree_set_nodes(self, L, pi, mu, cov):
         T = 8 * (8 ** L - 1) // 7

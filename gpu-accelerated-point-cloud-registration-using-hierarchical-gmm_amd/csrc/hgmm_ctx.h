@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -128,6 +129,7 @@ struct TreeState {
     int T = 0;
     bool nodes_ready = false;
     bool pdf_f32 = false;             // hgmm_tree_set_precision: the level log-likelihood's pdfs in float32 (large clouds)
+    double reg_gate = INFINITY;       // hgmm_tree_set_reg_gate: squared Mahalanobis gate of the registration E-step (+inf: off)
     double mu_rmax = -1.0;            // largest |mu_j| of the node table (< 0: not known on the host yet)
     bool momq_clean = false;          // every word of t_momq is zero (tree_host.h: MomqScope)
     bool multi_momq_clean = false;    // ... of tm_momq, the sums of hgmm_tree_register_multi's K hypotheses

@@ -243,11 +243,13 @@ __global__ void forest_target_kernel(const IN* __restrict__ aos, int64_t n, int6
     if (lane_id() == 0 && bits != 0ull) atomicMax(r2max_bits, bits);
 }
 
-template <int NMQ>
+// (GATED: hgmm_tree_set_reg_gate's finite gate, tree_reg_estep_body; the gate-off instantiations do not read the argument)
+template <int NMQ, bool GATED = false>
 __global__ __launch_bounds__(CH) void forest_reg_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                               const ForestRegPair* __restrict__ tab,
                                                               const double* __restrict__ prep, int T, int L,
-                                                              double lambda_c, unsigned long long* __restrict__ momq, int gx) {
+                                                              double lambda_c, unsigned long long* __restrict__ momq, int gx,
+                                                              double maha2_gate) {
     __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
     const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x B items)
     const int b = item / gx, bx = item - b * gx;
@@ -257,8 +259,8 @@ __global__ __launch_bounds__(CH) void forest_reg_estep_kernel(const double* __re
     const Rigid tf = pr->tf;
     const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
     const int64_t li = (int64_t)bx * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ>(first + li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, inv_d,
-                             fix_scale, momq + (size_t)NMQ * T * b, lds);
+    tree_reg_estep_body<NMQ, GATED>(first + li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, inv_d,
+                                    fix_scale, momq + (size_t)NMQ * T * b, lds, maha2_gate);
 }
 
 // the score of every pair (tree_score_body), pair b's workgroups starting at the pair's first point as in the kernel above --
@@ -324,11 +326,12 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
 // state) and slice k of the [K][T][NMQ] sums.  Same argument lists as the forest kernels, so the host loops below launch either
 // set.  A workgroup serves ONE hypothesis: its LDS table of levels 0..2 would have to be flushed per hypothesis otherwise,
 // and the 24 B / point a second hypothesis would save come out of L2 anyway.
-template <int NMQ>
+template <int NMQ, bool GATED = false>
 __global__ __launch_bounds__(CH) void tree_reg_multi_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                                   const ForestRegPair* __restrict__ tab,
                                                                   const double* __restrict__ prep, int T, int L,
-                                                                  double lambda_c, unsigned long long* __restrict__ momq, int gx) {
+                                                                  double lambda_c, unsigned long long* __restrict__ momq, int gx,
+                                                                  double maha2_gate) {
     __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
     const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x K items: hypothesis k, chunk bx)
     const int k = item / gx, bx = item - k * gx;
@@ -338,7 +341,8 @@ __global__ __launch_bounds__(CH) void tree_reg_multi_estep_kernel(const double* 
     const Rigid tf = pr->tf;
     const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
     const int64_t i = (int64_t)bx * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ>(i, i < count, tg, tg_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq + (size_t)NMQ * T * k, lds);
+    tree_reg_estep_body<NMQ, GATED>(i, i < count, tg, tg_pad, tf, prep, L, lambda_c, inv_d, fix_scale,
+                                    momq + (size_t)NMQ * T * k, lds, maha2_gate);
 }
 
 __global__ __launch_bounds__(256) void tree_reg_multi_normal_kernel(unsigned long long* __restrict__ momq,
@@ -392,6 +396,11 @@ __global__ __launch_bounds__(CH) void tree_score_multi_finish_kernel(const doubl
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// the E-step of the batched / multi-start registration loops: forest or shared tree, gate off or on (hgmm_tree_set_reg_gate)
+static auto reg_estep_kernel_for(bool shared_tree, bool gated) -> decltype(&forest_reg_estep_kernel<4, false>) {
+    if (gated) return shared_tree ? tree_reg_multi_estep_kernel<4, true> : forest_reg_estep_kernel<4, true>;
+    return shared_tree ? tree_reg_multi_estep_kernel<4, false> : forest_reg_estep_kernel<4, false>;
+}
 // The registration loop of B pairs with the device on its own (reg_device_solve): every iteration is two launches -- the
 // E-step of all pairs, then per pair the normal equations + reg_device_step -- enqueued by a host that only follows the
 // pairs' progress words and keeps a few iterations ahead of the slowest running pair; launches behind a pair's stop
@@ -407,7 +416,8 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
     HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
     const size_t trace_bytes = trace ? sizeof(double) * 13 * (size_t)max_iter * B : 0;
     if (trace) HGMM_TRY(ensure(c, c->fr_trace, trace_bytes));
-    const auto estep_kernel = shared_tree ? tree_reg_multi_estep_kernel<4> : forest_reg_estep_kernel<4>;
+    const double gate = c->tree.reg_gate;                    // (hgmm_tree_set_reg_gate; finite: the gated instantiations)
+    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate));
     const auto solve_kernel = shared_tree ? tree_reg_multi_solve_kernel : forest_reg_solve_kernel;
     ForestRegPair* d_tab = reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
@@ -436,7 +446,7 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
             {
                 ProfScope prof(c, HGMM_K_TREE_REG);
                 estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c, momq,
-                                                                                    (int)nblk(longest, CH));
+                                                                                    (int)nblk(longest, CH), gate);
             }
             solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace, words.dev);
             HGMM_HIP(c, hipGetLastError());
@@ -804,7 +814,8 @@ static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t
     const HostDev<unsigned long long> words = hand->sequence(0);
     const HostDev<double> h_out = hand->out28(0);
     HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
-    const auto estep_kernel = shared_tree ? tree_reg_multi_estep_kernel<4> : forest_reg_estep_kernel<4>;
+    const double gate = c->tree.reg_gate;                    // (hgmm_tree_set_reg_gate; finite: the gated instantiations)
+    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate));
     const auto normal_kernel = shared_tree ? tree_reg_multi_normal_kernel : forest_reg_normal_kernel;
     ForestRegPair* d_tab = reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
@@ -829,7 +840,8 @@ static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t
         {
             ProfScope prof(c, HGMM_K_TREE_REG);
             estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c,
-                                                                                momq.as<unsigned long long>(), (int)nblk(longest, CH));
+                                                                                momq.as<unsigned long long>(), (int)nblk(longest, CH),
+                                                                                gate);
         }
         normal_kernel<<<B, 256, 0, c->stream>>>(momq.as<unsigned long long>(), d_tab, prep, T, d_out, h_out.dev, words.dev, seq);
         HGMM_HIP(c, hipGetLastError());

@@ -1488,13 +1488,19 @@ __device__ __forceinline__ int64_t reg_descend_level(const double x0, const doub
 }
 
 // (i: the thread's target point in `tg`, alive: it exists; prep / momq: the node table and the sums of THIS tree)
+// GATED (hgmm_tree_set_reg_gate; no counterpart in the reference): a (point, node) pair that would contribute adds its
+// terms only if (y - mu_s)^T Sigma_s^-1 (y - mu_s) <= maha2_gate -- tree_score_body's maha2, on the difference the encoding
+// takes anyway.  The descent is NOT gated: the point moves on to its arg-max child and stops where it stops without the
+// gate; a NaN form fails the comparison.  A compile-time switch, so that the gate-off instantiations are the code they
+// were: the argument is not read there.
 constexpr int REG_LDS_NODES = 584;                       // levels 0..2 (8 + 64 + 512 nodes)
-template <int NMQ>
+template <int NMQ, bool GATED = false>
 __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive, const double* __restrict__ tg,
                                                     int64_t n_pad, const Rigid& tf, const double* __restrict__ prep, int L,
                                                     double lambda_c, double inv_d, double fix_scale,
                                                     unsigned long long* __restrict__ momq,
-                                                    unsigned long long* __restrict__ tab /* LDS [REG_LDS_NODES * NMQ] */) {
+                                                    unsigned long long* __restrict__ tab /* LDS [REG_LDS_NODES * NMQ] */,
+                                                    double maha2_gate = INFINITY) {
     const int lds_nodes = (int)(level_first(L < 3 ? L : 3));
     __shared__ double exp_tab[EXP_TAB_N];                  // the build's exponential (exp_nonpos4): 17 instructions per value
     exp_tab_load(exp_tab);
@@ -1518,6 +1524,13 @@ __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive,
             } else {
                 gs = best;
                 contribute = !(gs < TREE_EPS);
+            }
+        }
+        if constexpr (GATED) {
+            if (contribute) {
+                const double* pr = prep + PREP_N * s;
+                const double d0 = x0 - pr[6], d1 = x1 - pr[7], d2 = x2 - pr[8];
+                contribute = sym3_quad(pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], d0, d1, d2) <= maha2_gate;
             }
         }
         // this lane's contribution in fixed point, about the node's mean, in units of D

@@ -444,15 +444,16 @@ __global__ void tree_unsort_kernel(const int* __restrict__ perm, const int* __re
 }
 
 
-template <int NMQ>
+// (GATED: hgmm_tree_set_reg_gate's finite gate, tree_reg_estep_body; the gate-off instantiations do not read the argument)
+template <int NMQ, bool GATED = false>
 __global__ __launch_bounds__(CH) void tree_reg_estep_kernel(const double* __restrict__ tg, int64_t n,
                                                             int64_t n_pad, Rigid tf,
                                                             const double* __restrict__ prep, int L,
                                                             double lambda_c, double inv_d, double fix_scale,
-                                                            unsigned long long* __restrict__ momq) {
+                                                            unsigned long long* __restrict__ momq, double maha2_gate) {
     __shared__ unsigned long long tab[REG_LDS_NODES * NMQ];
     const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ>(i, i < n, tg, n_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq, tab);
+    tree_reg_estep_body<NMQ, GATED>(i, i < n, tg, n_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq, tab, maha2_gate);
 }
 
 // score of the resident target against the resident tree (tree_score_body, csrc/tree_device.h): workgroup b writes its six
@@ -1017,6 +1018,20 @@ extern "C" int hgmm_tree_set_precision(hgmm_ctx* c, int precision) {
     return HGMM_OK;
 }
 
+extern "C" int hgmm_tree_set_reg_gate(hgmm_ctx* c, double maha2_gate) {
+    HGMM_ENTER(c);
+    if (!(maha2_gate > 0.0))                                      // (NaN fails the comparison too)
+        return fail(c, HGMM_ERR_ARG, "hgmm_tree_set_reg_gate: the gate must be > 0 (+inf: off), got %g", maha2_gate);
+    c->tree.reg_gate = maha2_gate;
+    return HGMM_OK;
+}
+extern "C" int hgmm_tree_get_reg_gate(hgmm_ctx* c, double* maha2_gate_out) {
+    HGMM_ENTER(c);
+    if (!c || !maha2_gate_out) return c ? fail(c, HGMM_ERR_ARG, "maha2_gate_out is NULL") : HGMM_ERR_ARG;
+    *maha2_gate_out = c->tree.reg_gate;
+    return HGMM_OK;
+}
+
 extern "C" int hgmm_tree_set_nodes(hgmm_ctx* c, int L, const double* pi, const double* mu, const double* cov) {
     HGMM_ENTER(c);
     if (!c || !pi || !mu || !cov) return c ? fail(c, HGMM_ERR_ARG, "NULL node table") : HGMM_ERR_ARG;
@@ -1083,9 +1098,11 @@ static int reg_estep_fixed(hgmm_ctx* c, MomqScope& sums, const double* rot, cons
     unsigned long long* mq = c->t_momq.as<unsigned long long>();
     {
         ProfScope prof(c, HGMM_K_TREE_REG);
-        tree_reg_estep_kernel<NMQ><<<nblk(c->tgt_n, CH), CH, 0, c->stream>>>(
-            c->tgt_soa64.as<double>(), c->tgt_n, c->tgt_pad, tf, c->t_prep.as<double>(), c->tree.L, lambda_c, 1.0 / D,
-            std::ldexp(1.0, F), mq);
+        const double gate = c->tree.reg_gate;
+        const auto kernel = std::isfinite(gate) ? tree_reg_estep_kernel<NMQ, true> : tree_reg_estep_kernel<NMQ, false>;
+        kernel<<<nblk(c->tgt_n, CH), CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), c->tgt_n, c->tgt_pad, tf,
+                                                         c->t_prep.as<double>(), c->tree.L, lambda_c, 1.0 / D,
+                                                         std::ldexp(1.0, F), mq, gate);
     }
     HGMM_HIP(c, hipGetLastError());
     if (c->comm_on()) HGMM_TRY(allreduce_i64_dev(c, reinterpret_cast<long long*>(mq), (size_t)NMQ * T));

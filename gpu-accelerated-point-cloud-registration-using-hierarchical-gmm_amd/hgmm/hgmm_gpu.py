@@ -23,7 +23,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .._native import CHI2_3_99, Context, default_context
+from .._native import CHI2_3_99, CHI2_3_999, Context, default_context
 
 eps = np.float32(1.0e-15)     # hgmm_gpu.py:29
 n_node = 8                    # hgmm_gpu.py:30
@@ -50,6 +50,32 @@ def complexity(cov):
 
 def _points(x):
     return np.asarray(x.points if hasattr(x, "points") else x)
+
+
+def _gate_arg(maha2_gate):
+    """The mirrors' ``maha2_gate`` argument -> None (the mirror leaves the context's gate alone: off unless the caller set one
+    on the context) or a float > 0 (``inf``: off for this call).  Anything else is refused here, before the library is touched."""
+    if maha2_gate is None:
+        return None
+    g = float(maha2_gate)
+    if not g > 0.0:                                  # (NaN fails the comparison too)
+        raise ValueError("maha2_gate must be > 0 (np.inf or None: no gate), got %r" % (maha2_gate,))
+    return g
+
+
+@contextlib.contextmanager
+def _reg_gate(ctx, gate):
+    """``Context.tree_set_reg_gate(gate)`` for the calls inside, the context's previous gate afterwards (as buildGMMTree does
+    with the precision): a shared ``default_context()`` is never left gated.  ``gate`` None: nothing is touched."""
+    if gate is None:
+        yield
+        return
+    prev = ctx.tree_get_reg_gate()
+    ctx.tree_set_reg_gate(gate)
+    try:
+        yield
+    finally:
+        ctx.tree_set_reg_gate(prev)
 
 
 def buildGMMTree(points, maxTreeLevel, ls, ld, sig2=0.004, seed=72, init_idx=None,
@@ -291,10 +317,17 @@ class GMMTree():
     """GMM tree registration (hgmm_gpu.py:669-768).
 
     Args mirror the reference; ``ls`` / ``ld`` / ``sig2`` / ``init_idx`` expose the constants it
-    hard-codes (20, 1e-4, 0.004, seed 72)."""
+    hard-codes (20, 1e-4, 0.004, seed 72).
+
+    ``maha2_gate`` (no counterpart in the reference; default None: no gate): the Mahalanobis gate of the registration
+    E-step (``Context.tree_set_reg_gate``) for this object's registrations -- a (point, node) pair further than this
+    squared Mahalanobis distance from the node adds nothing to its moments, which keeps clutter and the non-overlapping
+    part of a scan from pulling the nodes.  ``CHI2_3_999`` is a reasonable value.  It is set on the context for the
+    object's own calls only; the context's previous gate is restored after each."""
 
     def __init__(self, source=None, tree_level=5, lambda_c=0.01, ls=20, ld=1.0e-4, sig2=0.004,
-                 init_idx=None, ctx: Context | None = None, verbose=False, solve_on_device=False):
+                 init_idx=None, ctx: Context | None = None, verbose=False, solve_on_device=False, maha2_gate=None):
+        self._maha2_gate = _gate_arg(maha2_gate)
         self._source = None
         self._tree_level = tree_level
         self._lambda_c = lambda_c
@@ -346,13 +379,14 @@ class GMMTree():
         """With ``target`` given: E-step on that (already transformed) cloud, like the reference.
         Inside :meth:`registration` the resident target is transformed on the device instead."""
         T = len(self._mixingCoeff)
-        if target is not None:
-            self._ctx.tree_set_target(_points(target))
-            self._target_id = None
-            m = self._ctx.tree_reg_estep(T, lambda_c=self._lambda_c)
-        else:
-            tf = self._tf_result
-            m = self._ctx.tree_reg_estep(T, tf.rot, tf.t, tf.scale, self._lambda_c)
+        with _reg_gate(self._ctx, self._maha2_gate):
+            if target is not None:
+                self._ctx.tree_set_target(_points(target))
+                self._target_id = None
+                m = self._ctx.tree_reg_estep(T, lambda_c=self._lambda_c)
+            else:
+                tf = self._tf_result
+                m = self._ctx.tree_reg_estep(T, tf.rot, tf.t, tf.scale, self._lambda_c)
         return EstepResult(*m)
 
     def _node_eig(self):
@@ -499,10 +533,19 @@ class GMMTree():
         self._target_id = None
         return self._ctx.tree_score(lambda_c=-1.0, want=("node",))[1]["node"]
 
-    def registration(self, target, maxiter=20, tol=1.0e-4, return_score=False, maha2_max=CHI2_3_99):
+    def registration(self, target, maxiter=20, tol=1.0e-4, return_score=False, maha2_max=CHI2_3_99, maha2_gate=None):
         """-> MstepResult(tf.inverse(), q)   (hgmm_gpu.py:754-768).  ``return_score=True``: ScoredResult(tf.inverse(), q,
-        score) with the :class:`TreeScore` of the target at the final pose, taken with the loop's own (R, t)."""
-        res = self._registration(target, maxiter, tol)
+        score) with the :class:`TreeScore` of the target at the final pose, taken with the loop's own (R, t).
+        ``maha2_gate``: the E-step's Mahalanobis gate for this call (default None: the object's own, see the class)."""
+        gate = _gate_arg(maha2_gate)
+        prev_gate = self._maha2_gate
+        if gate is not None:
+            self._maha2_gate = gate                  # (the host M-step's expectation_step inside the loop follows it too)
+        try:
+            with _reg_gate(self._ctx, self._maha2_gate):
+                res = self._registration(target, maxiter, tol)
+        finally:
+            self._maha2_gate = prev_gate
         if return_score:
             return ScoredResult(res.transformation, res.q, self._score_resident(maha2_max))
         return res
@@ -520,7 +563,12 @@ class GMMTree():
 
         -> :class:`MultiStartResult` (a ``ScoredResult(tf.inverse(), q, score)``) of the winner, with ``best_index_`` and
         ``n_iter_`` (also set on this object); with ``return_all`` also a list of K ``ScoredResult``s -- only the winner's
-        score carries the per-point arrays (one serial ``hgmm_tree_score``)."""
+        score carries the per-point arrays (one serial ``hgmm_tree_score``).  The object's ``maha2_gate`` (see the class)
+        applies to every hypothesis."""
+        with _reg_gate(self._ctx, self._maha2_gate):
+            return self._registration_multistart(target, starts, maxiter, tol, maha2_max, return_all)
+
+    def _registration_multistart(self, target, starts, maxiter, tol, maha2_max, return_all):
         starts = list(starts)
         if not starts:
             raise ValueError("registration_multistart: no start poses")
@@ -611,7 +659,8 @@ def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
 
 def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, starts=None, **kargs):
     """hgmm_gpu.py:802-807.  ``return_score=True``: ScoredResult(transformation, q, score) -- see :meth:`GMMTree.registration`.
-    ``starts`` (a list of start poses, e.g. :func:`rotation_starts`): :meth:`GMMTree.registration_multistart`'s result."""
+    ``starts`` (a list of start poses, e.g. :func:`rotation_starts`): :meth:`GMMTree.registration_multistart`'s result.
+    ``maha2_gate=`` (among :class:`GMMTree`'s arguments): the registration E-step's Mahalanobis gate, with or without ``starts``."""
     gt = GMMTree(_points(source), **kargs)
     if starts is not None:
         return gt.registration_multistart(_points(target), starts, maxiter, tol)
@@ -624,7 +673,7 @@ BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this 
 
 def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | None = None, tree_level=5, lambda_c=0.01,
                                ls=20, ld=1.0e-4, sig2=0.004, init_idx=None, return_info=False, pdf_dtype=None,
-                               solve_on_device=False, score=False):
+                               solve_on_device=False, score=False, maha2_gate=None):
     """``[registration_gmmtree(s, t, maxiter, tol, tree_level=..., ...) for s, t in pairs]`` (hgmm_gpu.py:802-807 per pair)
     with ALL pairs in the same launches: the B source clouds are one resident forest (``hgmm_tree_build_batch``: levels in
     lock-step, one stop rule per cloud), the B targets are registered against their trees together
@@ -642,8 +691,12 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     finished serially are scored through the serial entry.  The same numbers, bit for bit, as
     ``registration_gmmtree(..., return_score=True).score``.
 
+    ``maha2_gate`` (default None: no gate): the registration E-step's Mahalanobis gate for every pair, as in
+    :class:`GMMTree`; pairs that run or finish serially are registered under it too.  The context's own gate is restored.
+
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
+    gate = _gate_arg(maha2_gate)
     ctx = ctx or default_context()
     pairs = list(pairs)
     if not pairs:
@@ -659,7 +712,7 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
             info["score"] = [None] * len(pairs)
         for k in big:
             gt = GMMTree(pairs[k][0], tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, init_idx=init_idx, ctx=ctx,
-                         solve_on_device=solve_on_device)
+                         solve_on_device=solve_on_device, maha2_gate=gate)
             out[k] = gt.registration(_points(pairs[k][1]), maxiter, tol)
             info["registration_iters"][k], info["status"][k] = int(gt.n_iter_), 0
             if score:
@@ -667,7 +720,7 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
         rest = [k for k in range(len(pairs)) if k not in set(big)]
         if rest:
             r, inf = registration_gmmtree_batch([pairs[k] for k in rest], maxiter, tol, ctx, tree_level, lambda_c, ls, ld, sig2,
-                                                init_idx, True, pdf_dtype, solve_on_device, score)
+                                                init_idx, True, pdf_dtype, solve_on_device, score, gate)
             for j, k in enumerate(rest):
                 out[k] = r[j]
                 info["build_iters"][k] = inf["build_iters"][j]
@@ -685,7 +738,7 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
             for kind in sorted(set(kinds), key=str):
                 sel = [k for k, v in enumerate(kinds) if v == kind]
                 r, inf = registration_gmmtree_batch([pairs[k] for k in sel], maxiter, tol, ctx, tree_level, lambda_c, ls, ld,
-                                                    sig2, init_idx, True, kind, solve_on_device, score)
+                                                    sig2, init_idx, True, kind, solve_on_device, score, gate)
                 for j, k in enumerate(sel):
                     out[k] = r[j]
                     for key in info:
@@ -715,35 +768,37 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     ctx.tree_set_targets_batch(tgts)
     clock.append(time.perf_counter())
     rot0 = np.tile(np.identity(3), (B, 1, 1))
-    if solve_on_device:                                          # (per-context option reg_device_solve for this call)
-        with ctx.config(reg_device_solve=1):
+    with _reg_gate(ctx, gate):                                   # (the batch AND the pairs finished serially below)
+        if solve_on_device:                                          # (per-context option reg_device_solve for this call)
+            with ctx.config(reg_device_solve=1):
+                rot, t, iters, q, status, _ = ctx.tree_register_batch(rot0, np.zeros((B, 3)), 1.0, lambda_c, maxiter, tol)
+        else:
             rot, t, iters, q, status, _ = ctx.tree_register_batch(rot0, np.zeros((B, 3)), 1.0, lambda_c, maxiter, tol)
-    else:
-        rot, t, iters, q, status, _ = ctx.tree_register_batch(rot0, np.zeros((B, 3)), 1.0, lambda_c, maxiter, tol)
-    clock.append(time.perf_counter())
-    # (the batch is scored first: finishing a pair serially below moves the context's serial tree and target, not the forest)
-    scores = None
-    if score:
-        sums = ctx.tree_score_batch(rot, t, 1.0, lambda_c)
-        scores = [tree_score_from_summary(sums[b]) for b in range(B)]
-    clock.append(time.perf_counter())
-    out = []
-    reg_iters = [int(v) for v in iters]
-    for b in range(B):
-        if status[b] == 2:                                        # finish this pair through the serial entries
-            gt = GMMTree(tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, ctx=ctx, solve_on_device=solve_on_device)
-            gt.set_nodes(*ctx.tree_get_nodes_batch(b, tree_level))
-            gt._tf_result = RigidTransformation(rot[b], t[b])
-            ctx.tree_set_nodes(tree_level, gt._mixingCoeff, gt._mean, gt._covar)
-            ctx.tree_set_target(tgts[b])
-            res = gt._registration_in_library(maxiter, tol, _resume=(int(iters[b]), None if np.isnan(q[b]) else float(q[b]), True))
-            reg_iters[b] = int(gt.n_iter_)
-            if score:                                                 # (its pose moved on: the serial entry, at the final pose)
-                scores[b] = gt._score_resident(per_point=False)
-            out.append(res)
-            continue
-        tf = RigidTransformation(rot[b].copy(), t[b].copy())
-        out.append(MstepResult(tf.inverse(), np.array([q[b]]) if not np.isnan(q[b]) else np.array([])))
+        clock.append(time.perf_counter())
+        # (the batch is scored first: finishing a pair serially below moves the context's serial tree and target, not the forest)
+        scores = None
+        if score:
+            sums = ctx.tree_score_batch(rot, t, 1.0, lambda_c)
+            scores = [tree_score_from_summary(sums[b]) for b in range(B)]
+        clock.append(time.perf_counter())
+        out = []
+        reg_iters = [int(v) for v in iters]
+        for b in range(B):
+            if status[b] == 2:                                        # finish this pair through the serial entries
+                gt = GMMTree(tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, ctx=ctx,
+                             solve_on_device=solve_on_device, maha2_gate=gate)
+                gt.set_nodes(*ctx.tree_get_nodes_batch(b, tree_level))
+                gt._tf_result = RigidTransformation(rot[b], t[b])
+                ctx.tree_set_nodes(tree_level, gt._mixingCoeff, gt._mean, gt._covar)
+                ctx.tree_set_target(tgts[b])
+                res = gt._registration_in_library(maxiter, tol, _resume=(int(iters[b]), None if np.isnan(q[b]) else float(q[b]), True))
+                reg_iters[b] = int(gt.n_iter_)
+                if score:                                                 # (its pose moved on: the serial entry, at the final pose)
+                    scores[b] = gt._score_resident(per_point=False)
+                out.append(res)
+                continue
+            tf = RigidTransformation(rot[b].copy(), t[b].copy())
+            out.append(MstepResult(tf.inverse(), np.array([q[b]]) if not np.isnan(q[b]) else np.array([])))
     if return_info:
         clock.append(time.perf_counter())
         # wall time of the call's phases, ms: host preparation (type conversion, initial means), upload of the sources, forest

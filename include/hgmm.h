@@ -300,6 +300,25 @@ int hgmm_tree_reg_normal(hgmm_ctx* ctx, const double* rot, const double* t, doub
  * decided on the Cholesky pivots (smallest pivot <= 1e-11 largest diagonal entry).  Not under a communicator.      */
 int hgmm_tree_register(hgmm_ctx* ctx, double* rot, double* t, double scale, double lambda_c, int max_iter, double tol,
                        double* q_prev_inout, int* iters_out, int* status_out, double* trace);
+/* Mahalanobis GATE of the registration E-step (robustness to clutter and partial overlap).  The reference has no counterpart:
+ * gmmTreeRegESTep (hgmm_cupy_cpu_working.py:202-228 == hgmm_gpu.py:550-577), the function whose accumulation this restricts,
+ * normalises the eight children's responsibilities among themselves, so a point that belongs to none of them still gets
+ * gamma ~ 1 for the least bad child and pulls that node's moments with full weight.  With a finite gate a target point
+ * y = scale * R x + t that would contribute to node s at a level (it has not stopped there and its responsibility is >= 1e-15)
+ * contributes iff
+ *     (y - mu_s)^T Sigma_s^-1 (y - mu_s) <= maha2_gate,
+ * the quantity hgmm_tree_score reports as maha2.  The DESCENT is not gated: a point gated out at a coarse level still moves
+ * to its arg-max child, may contribute at a finer level and stops where it stops without the gate.  A point with a
+ * non-finite coordinate (NaN form) contributes nothing under a finite gate.  The sums stay the deterministic fixed-point
+ * sums of the ungated E-step.  maha2_gate = +inf (the default): off -- the ungated kernels run and every result is what it
+ * was, bit for bit.  NaN or a gate <= 0: HGMM_ERR_ARG, the previous gate stays.  Suggested values: the chi-square quantiles
+ * of 3 degrees of freedom (11.34 = 99 %, 16.27 = 99.9 %).
+ * Honoured by every entry that runs the registration E-step -- hgmm_tree_reg_estep, hgmm_tree_reg_normal,
+ * hgmm_tree_register, hgmm_tree_register_multi, hgmm_tree_register_batch, with reg_device_solve and under a communicator
+ * alike (the gate is per point: the ranks' shards still add up exactly) -- and by nothing else: hgmm_tree_score* keep their
+ * own maha2_max argument, the build has no such step.  Stays in force for the context until set again. */
+int hgmm_tree_set_reg_gate(hgmm_ctx* ctx, double maha2_gate);
+int hgmm_tree_get_reg_gate(hgmm_ctx* ctx, double* maha2_gate_out);
 /* ---- batched HGMM: B independent scan pairs per launch set ("forest") ------------------------------------------------
  * The reference's unit of work is ONE pair -- registration_gmmtree(source, target) (hgmm/hgmm_gpu.py:802-807) =
  * buildGMMTree(source) (hgmm_gpu.py:466-548) + GMMTree.registration(target) (hgmm_gpu.py:754-768, E-step 550-577) -- a
