@@ -48,21 +48,34 @@ constexpr int BLOCK = WAVES_PER_BLOCK * 64;
 //   c2_j = log2(e) * ( -0.5 * 3 * log(2 pi) + sum_d log(inv_std_jd + eps) + log(w_j [+ eps]) )
 // (estimate_log_prob / estimate_log_prob_spherical / e_step, gmm_waymo gmm_impl.py:53-116)
 // ------------------------------------------------------------------------------------------
+// (the pieces of pack_values: flat_boundary_kernel spreads them over the lanes of a component)
+__device__ inline float pack_g(float inv) {
+    const double l2e = 1.4426950408889634074;
+    const double i = inv;
+    return (float)(0.5 * l2e * i * i);
+}
+__device__ inline float pack_const(double half_log_det, double lw) {
+    const double l2e = 1.4426950408889634074;
+    const double log2pi = (double)1.8378770351409912f;   // reference casts log(2 pi) to float32
+    const double cc = (-0.5 * 3.0 * log2pi + half_log_det + lw) * l2e;
+    return (cc != cc) ? NEG_INF : (float)cc;
+}
+// (a component only counts towards the fused kernel's origin with a usable mean and a positive, finite weight)
+__device__ inline bool pack_usable(bool valid, float wj, float m0, float m1, float m2) {
+    return valid && wj > 0.f && wj < 3.0e38f && fabsf(m0) < 3.0e38f && fabsf(m1) < 3.0e38f && fabsf(m2) < 3.0e38f;
+}
 // (m, i: the component's mean and inverse standard deviations, spherical already expanded to three axes)
 __device__ inline void pack_values(int j, bool valid, int Jpad, int variant, const float (&m)[3], const float (&i)[3],
                                    float wj, float* pack) {
     float m0 = 0.f, m1 = 0.f, m2 = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f, c = NEG_INF;
     if (valid) {
         const double eps = (double)FLAT_EPS;
-        const double l2e = 1.4426950408889634074;
         const double i0 = i[0], i1 = i[1], i2 = i[2];
-        const double log2pi = (double)1.8378770351409912f;   // reference casts log(2 pi) to float32
         double half_log_det = log(i0 + eps) + log(i1 + eps) + log(i2 + eps);
         double lw = (variant == HGMM_VARIANT_W) ? log((double)wj + eps) : log((double)wj);
-        double cc = (-0.5 * 3.0 * log2pi + half_log_det + lw) * l2e;
         m0 = m[0]; m1 = m[1]; m2 = m[2];
-        g0 = (float)(0.5 * l2e * i0 * i0); g1 = (float)(0.5 * l2e * i1 * i1); g2 = (float)(0.5 * l2e * i2 * i2);
-        c = (cc != cc) ? NEG_INF : (float)cc;
+        g0 = pack_g(i[0]); g1 = pack_g(i[1]); g2 = pack_g(i[2]);
+        c = pack_const(half_log_det, lw);
     }
     pack[(PK_MU + 0) * Jpad + j] = m0;
     pack[(PK_MU + 1) * Jpad + j] = m1;
@@ -71,9 +84,7 @@ __device__ inline void pack_values(int j, bool valid, int Jpad, int variant, con
     pack[(PK_G + 1) * Jpad + j] = g1;
     pack[(PK_G + 2) * Jpad + j] = g2;
     pack[PK_C * Jpad + j] = c;
-    // (a component only counts towards the fused kernel's origin with a usable mean and a positive, finite weight)
-    const bool usable = valid && wj > 0.f && wj < 3.0e38f && fabsf(m0) < 3.0e38f && fabsf(m1) < 3.0e38f && fabsf(m2) < 3.0e38f;
-    pack[PK_W * Jpad + j] = usable ? wj : 0.f;
+    pack[PK_W * Jpad + j] = pack_usable(valid, wj, m0, m1, m2) ? wj : 0.f;
 }
 __device__ inline void pack_component(int j, int J, int Jpad, int cov_type, int variant,
                                       const float* mu, const float* inv, const float* w,
@@ -818,7 +829,7 @@ template <int NSLOT>
 __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     const float* __restrict__ X, const float* __restrict__ pack, int64_t n, int J, int Jpad,
     float* __restrict__ partials, double* __restrict__ lpn_partials,
-    const int* __restrict__ done_flag, int allow_const_shift) {
+    const int* __restrict__ done_flag, int allow_const_shift, int comp_major) {
     if (done_flag && *done_flag) return;
     constexpr int K = NSLOT;
     constexpr int KP = K / 2;          // full pairs
@@ -1011,15 +1022,17 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
         }
     }
 
-    __shared__ float sh[FLAT_NSTAT * NSLOT * 64];
+    // (a statistic's LDS row is padded by 8 words: the component-major copy below has a wave read 8 components x 8
+    //  rows at once, and NSLOT * 64 words apart all rows of a component would share one bank)
+    constexpr int ST = NSLOT * 64, STP = ST + 8;
+    __shared__ float sh[FLAT_NSTAT * STP];
     __shared__ double shl[WAVES_PER_BLOCK];
     const int w = wave_in_block();
-    constexpr int ST = NSLOT * 64;
     if (lane == 0) shl[w] = lsum;
     auto put = [&](int k, bool first, float v0, float v1, float v2, float v3, float v4, float v5, float v6) {
         float* q = sh + k * 64 + lane;
-        if (first) { q[0 * ST] = v0; q[1 * ST] = v1; q[2 * ST] = v2; q[3 * ST] = v3; q[4 * ST] = v4; q[5 * ST] = v5; q[6 * ST] = v6; }
-        else { q[0 * ST] += v0; q[1 * ST] += v1; q[2 * ST] += v2; q[3 * ST] += v3; q[4 * ST] += v4; q[5 * ST] += v5; q[6 * ST] += v6; }
+        if (first) { q[0 * STP] = v0; q[1 * STP] = v1; q[2 * STP] = v2; q[3 * STP] = v3; q[4 * STP] = v4; q[5 * STP] = v5; q[6 * STP] = v6; }
+        else { q[0 * STP] += v0; q[1 * STP] += v1; q[2 * STP] += v2; q[3 * STP] += v3; q[4 * STP] += v4; q[5 * STP] += v5; q[6 * STP] += v6; }
     };
     for (int turn = 0; turn < WAVES_PER_BLOCK; ++turn) {
         if (w == turn) {
@@ -1032,10 +1045,20 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
         }
         __syncthreads();
     }
-    float* outp = partials + (size_t)blockIdx.x * FLAT_NSTAT * Jpad;
-    for (int idx = threadIdx.x; idx < FLAT_NSTAT * ST; idx += BLOCK) {
-        const int st = idx / ST, j = idx % ST;
-        outp[st * Jpad + j] = sh[idx];
+    if (comp_major) {
+        // [block][Jpad][8]: a component's 7 statistics + one pad word are 32 contiguous bytes, 8 components -- what a
+        // workgroup of flat_boundary_kernel owns -- 256 (the train loop without a communicator; kernel-uniform)
+        float* outp = partials + (size_t)blockIdx.x * FLAT_CM_STRIDE * Jpad;
+        for (int idx = threadIdx.x; idx < FLAT_CM_STRIDE * ST; idx += BLOCK) {
+            const int j = idx / FLAT_CM_STRIDE, st = idx % FLAT_CM_STRIDE;
+            outp[idx] = st < FLAT_NSTAT ? sh[st * STP + j] : 0.f;
+        }
+    } else {
+        float* outp = partials + (size_t)blockIdx.x * FLAT_NSTAT * Jpad;
+        for (int idx = threadIdx.x; idx < FLAT_NSTAT * ST; idx += BLOCK) {
+            const int st = idx / ST, j = idx % ST;
+            outp[st * Jpad + j] = sh[st * STP + j];
+        }
     }
     if (threadIdx.x == 0) {
         double t = 0.0;
@@ -1460,10 +1483,30 @@ __global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_kernel(
 // ------------------------------------------------------------------------------------------
 struct FlatComponent { float mu[3], cov[3], inv[3], w; };
 
+// (the pieces of finalize_values: flat_boundary_kernel gives each axis of a component a lane of its own)
+__device__ inline void finalize_counts(double s0, int variant, double& nk, double& den) {
+    const double eps = (double)FLAT_EPS;
+    nk = (variant == HGMM_VARIANT_W) ? s0 + eps : s0;
+    den = (variant == HGMM_VARIANT_W) ? nk : nk + eps;
+}
+__device__ inline void finalize_axis(double s0, double a, double b, double c, double den, int variant, double& m_out,
+                                     double& v_out) {
+    const double sx = a + c * s0;
+    const double sxx = b + 2.0 * c * a + c * c * s0;
+    const double m = sx / den;
+    double v = sxx / den - m * m;
+    if (variant == HGMM_VARIANT_W) v += 1e-6; else v = v < 0.0 ? 0.0 : v;
+    m_out = m;
+    v_out = v;
+}
+__device__ inline float finalize_inv(float cov, int variant) {
+    const double eps = (double)FLAT_EPS;
+    const double cv = (double)cov;
+    return (float)((variant == HGMM_VARIANT_W) ? 1.0 / (sqrt(cv + 1e-6) + eps) : 1.0 / (sqrt(cv) + eps));
+}
 // the new parameters of component j, rounded to the reference's storage type (float32) before inv_std is derived
 __device__ inline FlatComponent finalize_values(int j, const double* __restrict__ stats,
                                                 const float* __restrict__ centre, int Jpad, int cov_type, int variant) {
-    const double eps = (double)FLAT_EPS;
     const double n_total = stats[FLAT_NSTAT * Jpad + 1];
     const double s0 = stats[0 * Jpad + j];
     double st_a[3], st_b[3], ce[3];
@@ -1473,20 +1516,10 @@ __device__ inline FlatComponent finalize_values(int j, const double* __restrict_
         st_a[d] = stats[(1 + d) * Jpad + j];
         st_b[d] = stats[(4 + d) * Jpad + j];
     }
-    double nmu[3], ncov[3];
-    const double nk = (variant == HGMM_VARIANT_W) ? s0 + eps : s0;
-    const double den = (variant == HGMM_VARIANT_W) ? nk : nk + eps;
+    double nmu[3], ncov[3], nk, den;
+    finalize_counts(s0, variant, nk, den);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const double c = ce[d], a = st_a[d], b = st_b[d];
-        const double sx = a + c * s0;
-        const double sxx = b + 2.0 * c * a + c * c * s0;
-        const double m = sx / den;
-        double v = sxx / den - m * m;
-        if (variant == HGMM_VARIANT_W) v += 1e-6; else v = v < 0.0 ? 0.0 : v;
-        nmu[d] = m;
-        ncov[d] = v;
-    }
+    for (int d = 0; d < 3; ++d) finalize_axis(s0, st_a[d], st_b[d], ce[d], den, variant, nmu[d], ncov[d]);
     FlatComponent r;
     if (cov_type == HGMM_COV_SPHERICAL) {
         const float sph = (float)((ncov[0] + ncov[1] + ncov[2]) / 3.0);
@@ -1499,10 +1532,7 @@ __device__ inline FlatComponent finalize_values(int j, const double* __restrict_
     for (int d = 0; d < 3; ++d) r.mu[d] = (float)nmu[d];
     r.w = (float)(nk / n_total);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const double cv = (double)r.cov[d];
-        r.inv[d] = (float)((variant == HGMM_VARIANT_W) ? 1.0 / (sqrt(cv + 1e-6) + eps) : 1.0 / (sqrt(cv) + eps));
-    }
+    for (int d = 0; d < 3; ++d) r.inv[d] = finalize_inv(r.cov[d], variant);
     return r;
 }
 __device__ inline void store_component(int j, const FlatComponent& r, int cov_type, float* mu, float* cov, float* w,
@@ -1522,16 +1552,19 @@ __device__ inline void finalize_component(int j, const double* __restrict__ stat
     store_component(j, finalize_values(j, stats, centre, Jpad, cov_type, variant), cov_type, mu, cov, w, inv);
 }
 
-__device__ inline void ctl_update(const double* __restrict__ stats, int Jpad, float* lls, int lls_cap,
-                                  float tol, int* ctl, float* ctl_f, int* stop_out) {
-    const double n_total = stats[FLAT_NSTAT * Jpad + 1];
-    const float ll = (float)(stats[FLAT_NSTAT * Jpad] / n_total);
+__device__ inline void ctl_apply(double sum_lpn, double n_total, float* lls, int lls_cap, float tol, int* ctl,
+                                 float* ctl_f, int* stop_out) {
+    const float ll = (float)(sum_lpn / n_total);
     const int it = ctl[1];
     if (it < lls_cap) lls[it] = ll;
     const float change = ll - ctl_f[0];          // prev starts at -inf (gmm_impl.py:120)
     ctl_f[0] = ll;
     ctl[1] = it + 1;
     if (fabsf(change) < tol) { *stop_out = 1; ctl[2] = 1; }
+}
+__device__ inline void ctl_update(const double* __restrict__ stats, int Jpad, float* lls, int lls_cap,
+                                  float tol, int* ctl, float* ctl_f, int* stop_out) {
+    ctl_apply(stats[FLAT_NSTAT * Jpad], stats[FLAT_NSTAT * Jpad + 1], lls, lls_cap, tol, ctl, ctl_f, stop_out);
 }
 
 // M-step + next packed table + stop rule in one launch (Jpad <= 1024: Jpad / 256 workgroups, a component per thread).
@@ -1560,6 +1593,143 @@ __global__ __launch_bounds__(256) void flat_finalize_kernel(const double* __rest
     if (j < J) store_component(j, r, cov_type, mu, cov, w, inv);
     if (pack && j < Jpad) pack_values(j, j < J, Jpad, variant, r.mu, r.inv, r.w, pack);
     if (j == 0 && ctl) ctl_update(stats, Jpad, lls, lls_cap, tol, ctl, ctl_f, stop_next);
+}
+
+// Everything between two iterations of the train loop in ONE launch: flat_reduce_kernel's sums, flat_finalize_kernel's
+// M-step, the next packed table and the stop rule -- bit for bit what the two launches compute.  NOT the default: it
+// measured 2 - 3 us slower per iteration than the two launches (enqueue_em_iteration has the figures).
+//   * Jpad / 8 workgroups of 256 threads, 8 components each, over the COMPONENT-MAJOR partials [block][Jpad][8] of the
+//     fused kernel: thread (slice s, component c) adds, in float64, the blocks b = s (mod 32) in increasing b -- the
+//     reduction kernel's slices and order -- with two 16-byte loads per block; the 8 components of a block are 256
+//     contiguous bytes.  As there, every load of a batch is issued before the first add.
+//   * the 32 slice sums meet in LDS in slice order 0..31 (one thread per component and statistic, which also writes
+//     f_stats), and the M-step runs on them where they are: no second launch that re-reads them from memory.
+//   * four lanes per component: one per axis and one for the weight.  The axes are independent in finalize_values
+//     (the spherical mean and the table's constant take the three axes' values by lane exchange, in the same order), so
+//     a lane's chain of fp64 divides, square roots and logarithms is a third of a component's.
+//   * one more workgroup sums the log-normaliser partials in the order of the reduction kernel's 1024 threads -- each
+//     wave plays four of its sixteen, then the sixteen totals are added in turn -- and applies the stop rule.
+// The stop flag: as in flat_finalize_kernel (double-buffered by parity, a vector load, gates only the stores).
+constexpr int BND_COMP = 8;               // components per workgroup
+constexpr int BND_BATCH = RED_BATCH;      // partial blocks a thread has in flight (two 16-byte loads each)
+__global__ __launch_bounds__(BND_COMP * RED_SLICES) void flat_boundary_kernel(
+    const float* __restrict__ partials, const double* __restrict__ lpn_partials, int nblocks, int valid_j, int J,
+    int Jpad, int cov_type, int variant, double n_total, double* __restrict__ stats, float* mu, float* cov, float* w,
+    float* inv, float* pack, float* lls, int lls_cap, float tol, int* ctl, float* ctl_f,
+    const int* stop /*never null*/, int* stop_next /*never null*/) {
+    int lane_zero = 0;
+    asm volatile("" : "+v"(lane_zero));                      // (see flat_reduce_kernel)
+    const int done = __hip_atomic_load(stop + lane_zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __shared__ double sh[RED_SLICES * BND_COMP * FLAT_NSTAT];
+    __shared__ double tot[BND_COMP * FLAT_NSTAT];
+    if ((int)blockIdx.x == Jpad / BND_COMP) {
+        // last workgroup: virtual thread vw * 64 + lane of flat_reduce_kernel's 1024
+        const int lane = lane_id();
+        for (int vw = wave_in_block(); vw < RED_IDX * RED_SLICES / 64; vw += BND_COMP * RED_SLICES / 64) {
+            double acc = 0.0;
+            for (int b = vw * 64 + lane; b < nblocks; b += RED_IDX * RED_SLICES) acc += lpn_partials[b];
+            acc = wave_sum_f64(acc);
+            if (lane == 0) sh[vw] = acc;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (done) {
+                *stop_next = 1;                               // stays stopped
+            } else {
+                double t = 0.0;
+                for (int vw = 0; vw < RED_IDX * RED_SLICES / 64; ++vw) t += sh[vw];
+                stats[FLAT_NSTAT * Jpad] = t;
+                stats[FLAT_NSTAT * Jpad + 1] = n_total;
+                ctl_apply(t, n_total, lls, lls_cap, tol, ctl, ctl_f, stop_next);
+            }
+        }
+        return;
+    }
+    const int j0 = blockIdx.x * BND_COMP;
+    // the M-step's lane roles (wave 0; its upper half mirrors the lower one and stores nothing)
+    const int mc = (threadIdx.x % (BND_COMP * 4)) >> 2, role = threadIdx.x & 3, axis = role < 3 ? role : 0;
+    const int mj = j0 + mc;
+    // the statistics were centred about the means the E-step used = rows PK_MU.. of pack; fetched with the partials
+    const double ce = (double)pack[(PK_MU + axis) * Jpad + mj];
+
+    const int cl = threadIdx.x % BND_COMP, slice = threadIdx.x / BND_COMP;
+    double acc[FLAT_NSTAT];
+#pragma unroll
+    for (int k = 0; k < FLAT_NSTAT; ++k) acc[k] = 0.0;
+    if (j0 < valid_j) {                                       // (valid_j is a multiple of 64: uniform over the workgroup)
+        const float4* src = reinterpret_cast<const float4*>(partials) + (size_t)(j0 + cl) * (FLAT_CM_STRIDE / 4);
+        const size_t bstride = (size_t)Jpad * (FLAT_CM_STRIDE / 4);
+        for (int b0 = slice; b0 < nblocks; b0 += BND_BATCH * RED_SLICES) {
+            float4 lo[BND_BATCH], hi[BND_BATCH];
+#pragma unroll
+            for (int u = 0; u < BND_BATCH; ++u) {
+                const int b = b0 + u * RED_SLICES;
+                const float4* p = src + (size_t)(b < nblocks ? b : nblocks - 1) * bstride;
+                lo[u] = p[0];
+                hi[u] = p[1];
+            }
+#pragma unroll
+            for (int u = 0; u < BND_BATCH; ++u) {
+                const bool in = b0 + u * RED_SLICES < nblocks;
+                acc[0] += in ? (double)lo[u].x : 0.0;
+                acc[1] += in ? (double)lo[u].y : 0.0;
+                acc[2] += in ? (double)lo[u].z : 0.0;
+                acc[3] += in ? (double)lo[u].w : 0.0;
+                acc[4] += in ? (double)hi[u].x : 0.0;
+                acc[5] += in ? (double)hi[u].y : 0.0;
+                acc[6] += in ? (double)hi[u].z : 0.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < FLAT_NSTAT; ++k) sh[(slice * BND_COMP + cl) * FLAT_NSTAT + k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < BND_COMP * FLAT_NSTAT) {
+        const int c2 = threadIdx.x / FLAT_NSTAT, st = threadIdx.x % FLAT_NSTAT;
+        double t = 0.0;
+#pragma unroll
+        for (int s = 0; s < RED_SLICES; ++s) t += sh[(s * BND_COMP + c2) * FLAT_NSTAT + st];
+        tot[threadIdx.x] = t;
+        if (!done) stats[st * Jpad + j0 + c2] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+
+    const double s0 = tot[mc * FLAT_NSTAT];
+    const double sa = tot[mc * FLAT_NSTAT + 1 + axis], sb = tot[mc * FLAT_NSTAT + 4 + axis];
+    double nk, den, m, v;
+    finalize_counts(s0, variant, nk, den);
+    finalize_axis(s0, sa, sb, ce, den, variant, m, v);
+    const int base = (int)threadIdx.x & ~3;
+    float cov_f = (float)v;
+    if (cov_type == HGMM_COV_SPHERICAL) {
+        const double v0 = __shfl(v, base), v1 = __shfl(v, base + 1), v2 = __shfl(v, base + 2);
+        cov_f = (float)((v0 + v1 + v2) / 3.0);
+    }
+    const float mu_f = (float)m;
+    const float w_f = (float)(nk / n_total);
+    const float inv_f = finalize_inv(cov_f, variant);
+    // the table: ONE logarithm per lane (an axis' inverse standard deviation, or the weight), gathered on the weight's lane
+    const double eps = (double)FLAT_EPS;
+    const double larg = role < 3 ? (double)inv_f + eps : (variant == HGMM_VARIANT_W ? (double)w_f + eps : (double)w_f);
+    const double lg = log(larg);
+    const double lg0 = __shfl(lg, base), lg1 = __shfl(lg, base + 1), lg2 = __shfl(lg, base + 2);
+    const float m0 = __shfl(mu_f, base), m1 = __shfl(mu_f, base + 1), m2 = __shfl(mu_f, base + 2);
+    if (done || threadIdx.x >= BND_COMP * 4) return;
+    const bool valid = mj < J;
+    if (role < 3) {
+        if (valid) {
+            mu[3 * mj + role] = mu_f;
+            if (cov_type == HGMM_COV_DIAG) { cov[3 * mj + role] = cov_f; inv[3 * mj + role] = inv_f; }
+            else if (role == 0) { cov[mj] = cov_f; inv[mj] = inv_f; }
+        }
+        pack[(PK_MU + role) * Jpad + mj] = valid ? mu_f : 0.f;
+        pack[(PK_G + role) * Jpad + mj] = valid ? pack_g(inv_f) : 0.f;
+    } else {
+        if (valid) w[mj] = w_f;
+        pack[PK_C * Jpad + mj] = valid ? pack_const(lg0 + lg1 + lg2, lg) : NEG_INF;
+        pack[PK_W * Jpad + mj] = pack_usable(valid, w_f, m0, m1, m2) ? w_f : 0.f;
+    }
 }
 
 // many workgroups (large J): the stop rule moves to flat_ctl_kernel, launched afterwards, so no
@@ -1647,7 +1817,7 @@ static int flat_setup(hgmm_ctx* c, int cov_type, int variant, int J) {
     HGMM_TRY(ensure(c, c->f_hint, sizeof(float) * 3 * Jpad));
     // grid_for() never launches more than min(FLAT_MAX_BLOCKS, 8 workgroups per CU)
     const size_t max_blocks = std::min<size_t>(FLAT_MAX_BLOCKS, (size_t)c->cus * 8);
-    HGMM_TRY(ensure(c, c->f_partials, sizeof(float) * max_blocks * FLAT_NSTAT * Jpad));
+    HGMM_TRY(ensure(c, c->f_partials, sizeof(float) * max_blocks * FLAT_CM_STRIDE * Jpad));    // (the larger of the two layouts)
     HGMM_TRY(ensure(c, c->f_lpn_partials,
                     sizeof(double) * std::max<size_t>(FLAT_MAX_BLOCKS, (size_t)((c->n + 255) / 256))));
     HGMM_TRY(ensure(c, c->f_stats, sizeof(double) * (FLAT_NSTAT * Jpad + 2)));
@@ -2113,7 +2283,8 @@ static int launch_estep(hgmm_ctx* c, float* log_resp, float* lpn, int32_t* argma
     return HGMM_OK;
 }
 
-static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* valid_j) {
+// comp_major: the partials' layout, [block][Jpad][8] for flat_boundary_kernel instead of [block][7][Jpad] for flat_reduce_kernel
+static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* valid_j, bool comp_major) {
     c->flat.last_kernel = 3;
     const FlatState& f = c->flat;
     if (!done_flag) done_flag = c->f_ctl.as<int>() + 16;        // always 0 (flat_setup)
@@ -2153,7 +2324,7 @@ static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* v
 #define FUSED_CASE(S)                                                                           \
     do {                                                                                        \
         flat_fused_pk_kernel<S><<<grid, BLOCK, 0, c->stream>>>(X, pk, c->n, f.J, f.Jpad, part,  \
-                                                              lp, done_flag, 1);              \
+                                                              lp, done_flag, 1, comp_major ? 1 : 0); \
         *valid_j = S * 64;                                                                      \
     } while (0)
     ProfScope prof(c, HGMM_K_FLAT_FUSED);
@@ -2265,16 +2436,38 @@ static int enqueue_em_iteration(hgmm_ctx* c) {
     // stop flag of this iteration / of the next one (see flat_finalize_kernel): ctl[0] and ctl[3] in turn
     int* stop = ctl + ((f.launched & 1) ? 3 : 0);
     int* stop_next = ctl + ((f.launched & 1) ? 0 : 3);
-    HGMM_TRY(launch_fused(c, stop, &grid, &valid_j));
+    // Between two iterations: the reduction and the M-step, two launches.  Three merges into ONE launch have been built
+    // and measured; none was faster (N = 1e6, J = 800 unless said otherwise):
+    //  * a ticketed last workgroup running the M-step: all components in one 256-thread workgroup are a serial tail
+    //    that costs what the launch saved (0.4253 vs 0.4254 ms per iteration);
+    //  * round 4, a workgroup owns 8 components and sums their statistics over the stat-major partials in the reduction's
+    //    own slices and order: 32-byte pieces scattered over 512 blocks (0.3465 vs 0.3416 ms; bun000 J = 100 0.45 vs
+    //    0.385 ms per 20-iteration fit);
+    //  * round 7, flat_boundary_kernel: the same ownership over COMPONENT-MAJOR partials the fused kernel writes for it
+    //    (a workgroup's 8 components are 256 contiguous bytes of every block) and the M-step on four lanes per
+    //    component.  Bit for bit the two launches' fit -- and 12.3 us per launch against 5.6 + 4.9 us for reduce +
+    //    finalize under the kernel tracer, 2 - 3 us MORE per iteration on the clock (0.3338 vs 0.3319 ms and 0.3353 vs
+    //    0.3323 ms in two sessions), bun000 J = 100 unchanged at ~0.39 ms per 20-iteration fit.  Its 104 workgroups pull
+    //    the 27 MB of partials more slowly than the reduction's 183 x 1024 threads do; 4 components per workgroup (208
+    //    workgroups) gets to 0.3337 ms, 2 per workgroup or 32 blocks in flight per thread are slower again.  What a second
+    //    launch costs on a busy stream is less than the ~4.5 us floor of a lone kernel.  profiles/r07/boundary_ab.md.
+    // The third form stays reachable (HGMM_FLAT_BOUNDARY=1 at context creation, never under a communicator, whose
+    // all-reduce sits between the reduction and the M-step): tests/test_flat_boundary_gpu.py holds it to the default
+    // bit for bit, so that the next attempt starts from a working kernel and its number.
+    const bool one_launch = c->flat_boundary == 1 && !c->comm_on();
+    HGMM_TRY(launch_fused(c, stop, &grid, &valid_j, one_launch));
+    if (one_launch) {
+        ProfScope prof(c, HGMM_K_FLAT_BOUNDARY);
+        flat_boundary_kernel<<<f.Jpad / BND_COMP + 1, BND_COMP * RED_SLICES, 0, c->stream>>>(
+            c->f_partials.as<float>(), c->f_lpn_partials.as<double>(), grid, valid_j, f.J, f.Jpad, f.cov_type, f.variant,
+            (double)c->n, c->f_stats.as<double>(), c->f_mu.as<float>(), c->f_cov.as<float>(), c->f_w.as<float>(),
+            c->f_inv.as<float>(), c->f_pack.as<float>(), c->f_lls.as<float>(), f.lls_cap, f.tol, ctl, ctl_f, stop,
+            stop_next);
+        HGMM_HIP(c, hipGetLastError());
+        f.launched++;
+        return HGMM_OK;
+    }
     HGMM_TRY(launch_reduce(c, grid, valid_j, true, stop));
-    // (reduction + finalisation in ONE launch -- the last workgroup to finish, found by a ticket, runs the
-    //  M-step -- was measured no faster: 0.4253 vs 0.4254 ms per iteration at C3, 35 - 36 k vs 38 k it/s
-    //  on bun000 J = 100: the serial tail in one 256-thread workgroup costs what the launch saved.  Round 4 tried the form
-    //  WITHOUT a hand-over -- a workgroup owns 8 components, adds up their 7 statistics over all partial blocks in the
-    //  reduction kernel's own slices and orders (the same fit bit for bit) and runs their M-step: slower again, 0.3465 vs
-    //  0.3416 ms per iteration at C3 and 0.45 vs 0.385 ms per 20-iteration fit on bun000 J = 100 -- 100 workgroups reading
-    //  32-byte pieces of 512 partial blocks take longer than the 225 well-coalesced workgroups of the reduction kernel
-    //  plus a launch.)
     // the statistics were centred about the means the E-step used = rows PK_MU.. of pack
     flat_finalize_kernel<<<f.Jpad / 256, 256, 0, c->stream>>>(
         c->f_stats.as<double>(), c->f_pack.as<float>() + PK_MU * f.Jpad, f.J, f.Jpad, f.cov_type,
@@ -2745,7 +2938,7 @@ extern "C" int hgmm_flat_stats(hgmm_ctx* c, int cov_type, int variant, int J, co
         HGMM_TRY(chunk_statistics(c, nullptr, &grid));
         HGMM_TRY(launch_reduce(c, grid, c->flat.nchunks * CH_J, true, nullptr, n_lpn));
     } else {
-        HGMM_TRY(launch_fused(c, nullptr, &grid, &valid_j));
+        HGMM_TRY(launch_fused(c, nullptr, &grid, &valid_j, false));
         HGMM_TRY(launch_reduce(c, grid, valid_j, true, nullptr));
     }
     const FlatState& f = c->flat;

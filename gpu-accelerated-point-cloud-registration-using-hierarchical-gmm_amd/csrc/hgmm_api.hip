@@ -648,13 +648,19 @@ static int config_find(const char* name) {
 }
 // defaults, then HGMM_<NAME> from the environment (the library's one getenv)
 static void config_init(hgmm_ctx* c) {
-    for (int k = 0; k < CFG_COUNT; ++k) {
-        const ConfigSpec& sp = CONFIG_SPECS[k];
-        c->cfg[k] = sp.dflt;
+    // One name more than the table has: HGMM_FLAT_BOUNDARY (2, the default: reduce + finalize launches between two flat
+    // EM iterations; 1: flat_boundary_kernel, the one-launch form that measured no faster).  Fixed for the context's
+    // life and no option of hgmm_config_*: it selects a measured rejection that is kept for tests/test_flat_boundary_gpu.py
+    // and the A/B of profiles/r07, not an operating mode.
+    static const ConfigSpec flat_boundary = {"flat_boundary", 2, 1, 2};
+    for (int k = 0; k <= CFG_COUNT; ++k) {
+        const ConfigSpec& sp = k < CFG_COUNT ? CONFIG_SPECS[k] : flat_boundary;
+        int& value = k < CFG_COUNT ? c->cfg[k] : c->flat_boundary;
+        value = sp.dflt;
         std::string var = "HGMM_";
         for (const char* p = sp.name; *p; ++p) var += (char)std::toupper((unsigned char)*p);
         const char* v = std::getenv(var.c_str());
-        if (v && *v) c->cfg[k] = std::max(sp.lo, std::min(sp.hi, atoi(v)));
+        if (v && *v) value = std::max(sp.lo, std::min(sp.hi, atoi(v)));
     }
 }
 }  // namespace hgmm

@@ -17,6 +17,7 @@ namespace hgmm {
 
 constexpr float FLAT_EPS = 1e-8f;     // gmm_waymo gmm_impl.py:15 / gmmreg_gpu gmm_impl.py:16
 constexpr int FLAT_NSTAT = 7;         // s0, a[3], b[3]
+constexpr int FLAT_CM_STRIDE = 8;     // floats per component of a component-major partial: the 7 statistics + one pad = 32 bytes
 constexpr int FLAT_MAX_J = 1024;      // single-pass kernels (all parameters of a lane in registers)
 constexpr int FLAT_MAX_J_CHUNKED = 16384;  // chunked path (832-component chunks)
 constexpr int FLAT_MAX_BLOCKS = 2048; // persistent grid upper bound (partials buffer)
@@ -162,6 +163,8 @@ struct hgmm_points {
 
 struct hgmm_ctx {
     int cfg[hgmm::CFG_COUNT] = {};    // hgmm::ConfigKey -> value (hgmm_create: defaults, then the environment)
+    int flat_boundary = 2;            // launches between two flat EM iterations: 2 reduce + finalize, 1 flat_boundary_kernel (measured
+                                      // no faster; HGMM_FLAT_BOUNDARY, read with the options in hgmm_create)
     int device = 0;
     int cus = 256;
     int wall_khz = 0;                 // rate of wall_clock64() on this device (StorePacer, flat_kernels.hip)
@@ -185,7 +188,7 @@ struct hgmm_ctx {
     hgmm::DevBuf f_block;                     // float [10][Jpad]: the allocation behind the four arrays below
     hgmm::DevBuf f_mu, f_cov, f_w, f_inv;     // float model parameters (reference layout): NON-OWNING slices of f_block
     hgmm::DevBuf f_pack;                      // float [PK_ROWS = 8][Jpad] packed E-step params (flat_kernels.hip: mu, g, c, w)
-    hgmm::DevBuf f_partials;                  // float [blocks][7][Jpad]
+    hgmm::DevBuf f_partials;                  // float [blocks][7][Jpad], or [blocks][Jpad][8] from the train loop's fused kernel
     hgmm::DevBuf f_lpn_partials;              // double [blocks]
     hgmm::DevBuf f_stats;                     // double [7*Jpad + 2]  (+ sum lpn, + n)
     hgmm::DevBuf f_lls;                       // float [cap]

@@ -63,7 +63,8 @@ enum hgmm_kernel_id {
     HGMM_K_ALLREDUCE = 11,    /* the sufficient-statistics all-reduce (RCCL / host backend), N > 1 only */
     HGMM_K_FULL_FUSED = 12,   /* full-cov flat EM, one pass: denominators + arg-max + q + fp64-MFMA statistics */
     HGMM_K_TREE_SCORE = 13,   /* HGMM score of a moved target (tree descent, per-point outputs + summary) */
-    HGMM_K_COUNT = 14
+    HGMM_K_FLAT_BOUNDARY = 14, /* flat EM between two iterations: reduction + M-step + next table + stop rule */
+    HGMM_K_COUNT = 15
 };
 
 /* ---- lifecycle ------------------------------------------------------------------ */
