@@ -112,6 +112,7 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_set_reg_gate", [ctx, C.c_double])
         _sig(lib, "hgmm_tree_get_reg_gate", [ctx, _f64p])
         _sig(lib, "hgmm_tree_set_target", [ctx, _vp, C.c_int64])
+        _sig(lib, "hgmm_tree_set_target_weights", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_reg_estep", [ctx, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_reg_normal", [ctx, _vp, _vp, C.c_double, C.c_double, _vp])
         _sig(lib, "hgmm_tree_node_complexity", [ctx, _vp])
@@ -156,6 +157,7 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_get_nodes_batch", [ctx, C.c_int, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_set_targets_batch", [ctx, C.c_int, C.POINTER(_vp), _i64p])
         _sig(lib, "hgmm_tree_set_targets_batch_f32", [ctx, C.c_int, C.POINTER(_vp), _i64p])
+        _sig(lib, "hgmm_tree_set_target_weights_batch", [ctx, C.c_int, C.POINTER(_vp), _i64p])
         _sig(lib, "hgmm_tree_register_batch", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
                                                _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_score", [ctx, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp])
@@ -987,6 +989,22 @@ class Context:
         self._check(self.lib.hgmm_tree_set_target(self.h, _ptr(t), t.shape[0]))
         self._tgt_n = int(t.shape[0])
 
+    def tree_set_target_weights(self, w):
+        """Per-point weights ``w`` [n] >= 0 of the resident target (hgmm_tree_set_target_weights): point i adds ``w[i] * gamma``
+        where it added ``gamma`` -- in tree_reg_estep, tree_reg_normal, tree_register, tree_register_multi and in the
+        summaries of tree_score / tree_score_multi (slot 0: the sum of ``w``); the descent, the stop rule and the gate do not
+        see them.  ``None``: no weights.  They belong to the target :meth:`tree_set_target` uploaded -- a new target drops
+        them.  The library refuses a wrong length, a NaN, infinite or negative weight and all-zero weights (HgmmError, naming
+        the index) and keeps the previous weights."""
+        if w is None:
+            self._check(self.lib.hgmm_tree_set_target_weights(self.h, None, 0))
+            return self
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim != 1:
+            raise ValueError("weights must be [M], got %s" % (w.shape,))
+        self._check(self.lib.hgmm_tree_set_target_weights(self.h, _ptr(w), w.shape[0]))
+        return self
+
     def tree_reg_estep(self, T, rot=None, t=None, scale=1.0, lambda_c=0.01):
         rot = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3, 3)
         t = None if t is None else np.ascontiguousarray(t, dtype=np.float64).reshape(3)
@@ -1088,13 +1106,37 @@ class Context:
         self._check(self.lib.hgmm_tree_get_nodes_batch(self.h, int(b), _ptr(pi), _ptr(mu), _ptr(cov)))
         return pi, mu, cov
 
-    def tree_set_targets_batch(self, targets):
+    def tree_set_targets_batch(self, targets, weights=None):
+        """The B targets of the resident forest's pairs (hgmm_tree_set_targets_batch[_f32]).  ``weights`` (a list of B arrays
+        [N_b] or None entries; default None: no weights): per-point weights of the targets as in
+        :meth:`tree_set_target_weights` (hgmm_tree_set_target_weights_batch) -- a pair whose entry is None stays unweighted."""
         arrs, ptrs, counts, all32 = self._cloud_list(targets, "tree_set_targets_batch")
         entry = self.lib.hgmm_tree_set_targets_batch_f32 if all32 else self.lib.hgmm_tree_set_targets_batch
         self._tgt_B = None
         self._check(entry(self.h, len(arrs), ptrs, counts))
         self._tgt_B = len(arrs)
+        self._tgt_counts = [int(a.shape[0]) for a in arrs]
+        if weights is not None:
+            self.tree_set_target_weights_batch(weights)
         return arrs
+
+    def tree_set_target_weights_batch(self, weights):
+        """Weights of the resident batch targets (hgmm_tree_set_target_weights_batch): a list of B arrays [N_b] or None
+        entries (that pair stays unweighted); ``None``: no weights at all."""
+        if weights is None:
+            self._check(self.lib.hgmm_tree_set_target_weights_batch(self.h, 0, None, None))
+            return self
+        ws = [None if w is None else np.ascontiguousarray(w, dtype=np.float64) for w in weights]
+        for w in ws:
+            if w is not None and w.ndim != 1:
+                raise ValueError("weights must be [N_b], got %s" % (w.shape,))
+        ptrs = (_vp * max(len(ws), 1))(*[None if w is None else w.ctypes.data for w in ws])
+        # (the library compares every count with the resident target's; a None entry names no count of its own)
+        resident = getattr(self, "_tgt_counts", None) or []
+        counts = (C.c_int64 * max(len(ws), 1))(*[(resident[b] if b < len(resident) else 0) if w is None else w.shape[0]
+                                                 for b, w in enumerate(ws)])
+        self._check(self.lib.hgmm_tree_set_target_weights_batch(self.h, len(ws), ptrs, counts))
+        return self
 
     def tree_register_batch(self, rot, t, scale=1.0, lambda_c=0.01, max_iter=20, tol=1.0e-4, q_prev=None, want_trace=False):
         """Up to ``max_iter`` registration iterations of every (tree b, target b) pair of the resident forest in the same

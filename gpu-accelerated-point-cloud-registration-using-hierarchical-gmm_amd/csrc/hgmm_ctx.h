@@ -149,6 +149,8 @@ struct ForestState {
     std::vector<double> tg_rmax;          // largest |x| per target
     int64_t tg_pad = 0;
     bool momq_clean = false;              // every word of fr_momq is zero (tree_host.h: MomqScope)
+    bool tg_weighted = false;             // hgmm_tree_set_target_weights_batch: fr_tg_w holds a weight per target point
+    std::vector<double> tg_wsum;          // (tg_weighted) sum of the weights per target; an unweighted pair: its count
 };
 
 }  // namespace hgmm
@@ -228,6 +230,9 @@ struct hgmm_ctx {
     hgmm::DevBuf tgt_soa64;                   // double [3][m_pad] registration target
     int64_t tgt_n = 0, tgt_pad = 0;
     double tgt_rmax = 0.0;                    // largest |x| of the target (extent bound of the fixed-point moments)
+    hgmm::DevBuf tgt_w;                       // double [m_pad] per-point weights of the target (hgmm_tree_set_target_weights)
+    bool tgt_weighted = false;                // tgt_w is in force (a new target drops it)
+    double tgt_wsum = 0.0;                    // (tgt_weighted) sum of the weights, on the host in index order
 
     // ---- forest (batched trees: tree_batch.hip) ------------------------------------
     hgmm::ForestState forest;
@@ -236,6 +241,7 @@ struct hgmm_ctx {
     hgmm::DevBuf fr_q;                        // double: the clouds' shares of q
     hgmm::DevBuf fr_trace;                    // double [B][L][trace_cap]
     hgmm::DevBuf fr_tg;                       // double [3][tg_pad] the targets, back to back
+    hgmm::DevBuf fr_tg_w;                     // double [tg_pad] their weights (forest.tg_weighted; 1.0 for an unweighted pair)
     hgmm::DevBuf fr_momq;                     // uint64 [B T][4] registration sums
     hgmm::DevBuf ff_clocks;                   // int64 [8][4] phase clocks of the one-pass full-covariance kernels (armed: ff_clocks_on)
     bool ff_clocks_on = false;

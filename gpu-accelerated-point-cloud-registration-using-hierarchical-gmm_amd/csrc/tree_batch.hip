@@ -244,12 +244,13 @@ __global__ void forest_target_kernel(const IN* __restrict__ aos, int64_t n, int6
 }
 
 // (GATED: hgmm_tree_set_reg_gate's finite gate, tree_reg_estep_body; the gate-off instantiations do not read the argument)
-template <int NMQ, bool GATED = false>
+// (WEIGHTED: hgmm_tree_set_target_weights_batch's array w [tg_pad], indexed like the points; likewise never read without)
+template <int NMQ, bool GATED = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void forest_reg_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                               const ForestRegPair* __restrict__ tab,
                                                               const double* __restrict__ prep, int T, int L,
                                                               double lambda_c, unsigned long long* __restrict__ momq, int gx,
-                                                              double maha2_gate) {
+                                                              double maha2_gate, const double* __restrict__ w) {
     __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
     const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x B items)
     const int b = item / gx, bx = item - b * gx;
@@ -259,17 +260,19 @@ __global__ __launch_bounds__(CH) void forest_reg_estep_kernel(const double* __re
     const Rigid tf = pr->tf;
     const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
     const int64_t li = (int64_t)bx * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ, GATED>(first + li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, inv_d,
-                                    fix_scale, momq + (size_t)NMQ * T * b, lds, maha2_gate);
+    tree_reg_estep_body<NMQ, GATED, WEIGHTED>(first + li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c,
+                                              inv_d, fix_scale, momq + (size_t)NMQ * T * b, lds, maha2_gate, w);
 }
 
 // the score of every pair (tree_score_body), pair b's workgroups starting at the pair's first point as in the kernel above --
 // the serial call's grouping, so its shares and its summary are the serial call's bit for bit.  Reads the pose and the
 // target's place from the pairs table, NOT `active`: every pair is scored.  partial: [B][gx][6]
+template <bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void forest_score_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                           const ForestRegPair* __restrict__ tab,
                                                           const double* __restrict__ prep, int T, int L, double lambda_c,
-                                                          double maha2_max, double* __restrict__ partial, int gx) {
+                                                          double maha2_max, double* __restrict__ partial, int gx,
+                                                          const double* __restrict__ w) {
     const int item = (int)blockIdx.x;
     const int b = item / gx, bx = item - b * gx;
     const ForestRegPair* pr = tab + b;
@@ -277,15 +280,16 @@ __global__ __launch_bounds__(CH) void forest_score_kernel(const double* __restri
     if ((int64_t)bx * CH >= count) return;
     const Rigid tf = pr->tf;
     const int64_t li = (int64_t)bx * CH + threadIdx.x;
-    tree_score_body(first + li, li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, maha2_max,
-                    nullptr, nullptr, nullptr, partial + (size_t)SCORE_NSUM * item);
+    tree_score_body<WEIGHTED>(first + li, li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, maha2_max,
+                              nullptr, nullptr, nullptr, partial + (size_t)SCORE_NSUM * item, w);
 }
 __global__ __launch_bounds__(CH) void forest_score_finish_kernel(const double* __restrict__ partial,
                                                                  const ForestRegPair* __restrict__ tab, int gx,
                                                                  double* __restrict__ summary) {
     const int b = blockIdx.x;
     const int count = tab[b].tg_count;
-    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * b, (count + CH - 1) / CH, (double)count, summary + 8 * b);
+    // (tg_wsum: the pair's weight sum, (double)count without weights -- reg_pair)
+    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * b, (count + CH - 1) / CH, tab[b].tg_wsum, summary + 8 * b);
 }
 
 __global__ __launch_bounds__(256) void forest_reg_normal_kernel(unsigned long long* __restrict__ momq,
@@ -326,12 +330,12 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
 // state) and slice k of the [K][T][NMQ] sums.  Same argument lists as the forest kernels, so the host loops below launch either
 // set.  A workgroup serves ONE hypothesis: its LDS table of levels 0..2 would have to be flushed per hypothesis otherwise,
 // and the 24 B / point a second hypothesis would save come out of L2 anyway.
-template <int NMQ, bool GATED = false>
+template <int NMQ, bool GATED = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_reg_multi_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                                   const ForestRegPair* __restrict__ tab,
                                                                   const double* __restrict__ prep, int T, int L,
                                                                   double lambda_c, unsigned long long* __restrict__ momq, int gx,
-                                                                  double maha2_gate) {
+                                                                  double maha2_gate, const double* __restrict__ w) {
     __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
     const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x K items: hypothesis k, chunk bx)
     const int k = item / gx, bx = item - k * gx;
@@ -341,8 +345,8 @@ __global__ __launch_bounds__(CH) void tree_reg_multi_estep_kernel(const double* 
     const Rigid tf = pr->tf;
     const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
     const int64_t i = (int64_t)bx * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ, GATED>(i, i < count, tg, tg_pad, tf, prep, L, lambda_c, inv_d, fix_scale,
-                                    momq + (size_t)NMQ * T * k, lds, maha2_gate);
+    tree_reg_estep_body<NMQ, GATED, WEIGHTED>(i, i < count, tg, tg_pad, tf, prep, L, lambda_c, inv_d, fix_scale,
+                                              momq + (size_t)NMQ * T * k, lds, maha2_gate, w);
 }
 
 __global__ __launch_bounds__(256) void tree_reg_multi_normal_kernel(unsigned long long* __restrict__ momq,
@@ -376,16 +380,18 @@ __global__ __launch_bounds__(256) void tree_reg_multi_solve_kernel(unsigned long
 }
 
 // the score of every hypothesis: tree_score_kernel's grouping (workgroups start at the target's first point), partial [K][gx][6]
+template <bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_score_multi_kernel(const double* __restrict__ tg, int64_t n, int64_t tg_pad,
                                                               const ForestRegPair* __restrict__ tab,
                                                               const double* __restrict__ prep, int L, double lambda_c,
-                                                              double maha2_max, double* __restrict__ partial, int gx) {
+                                                              double maha2_max, double* __restrict__ partial, int gx,
+                                                              const double* __restrict__ w) {
     const int item = (int)blockIdx.x;
     const int k = item / gx, bx = item - k * gx;
     const Rigid tf = tab[k].tf;
     const int64_t i = (int64_t)bx * CH + threadIdx.x;
-    tree_score_body(i, i, i < n, tg, tg_pad, tf, prep, L, lambda_c, maha2_max, nullptr, nullptr, nullptr,
-                    partial + (size_t)SCORE_NSUM * item);
+    tree_score_body<WEIGHTED>(i, i, i < n, tg, tg_pad, tf, prep, L, lambda_c, maha2_max, nullptr, nullptr, nullptr,
+                              partial + (size_t)SCORE_NSUM * item, w);
 }
 __global__ __launch_bounds__(CH) void tree_score_multi_finish_kernel(const double* __restrict__ partial, int gx, double n_points,
                                                                      double* __restrict__ summary) {
@@ -396,10 +402,15 @@ __global__ __launch_bounds__(CH) void tree_score_multi_finish_kernel(const doubl
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// the E-step of the batched / multi-start registration loops: forest or shared tree, gate off or on (hgmm_tree_set_reg_gate)
-static auto reg_estep_kernel_for(bool shared_tree, bool gated) -> decltype(&forest_reg_estep_kernel<4, false>) {
-    if (gated) return shared_tree ? tree_reg_multi_estep_kernel<4, true> : forest_reg_estep_kernel<4, true>;
-    return shared_tree ? tree_reg_multi_estep_kernel<4, false> : forest_reg_estep_kernel<4, false>;
+// the E-step of the batched / multi-start registration loops: forest or shared tree, gate off or on (hgmm_tree_set_reg_gate),
+// without or with per-point weights of the target (hgmm_tree_set_target_weights[_batch])
+static auto reg_estep_kernel_for(bool shared_tree, bool gated, bool weighted) -> decltype(&forest_reg_estep_kernel<4, false, false>) {
+    if (weighted) {
+        if (gated) return shared_tree ? tree_reg_multi_estep_kernel<4, true, true> : forest_reg_estep_kernel<4, true, true>;
+        return shared_tree ? tree_reg_multi_estep_kernel<4, false, true> : forest_reg_estep_kernel<4, false, true>;
+    }
+    if (gated) return shared_tree ? tree_reg_multi_estep_kernel<4, true, false> : forest_reg_estep_kernel<4, true, false>;
+    return shared_tree ? tree_reg_multi_estep_kernel<4, false, false> : forest_reg_estep_kernel<4, false, false>;
 }
 // The registration loop of B pairs with the device on its own (reg_device_solve): every iteration is two launches -- the
 // E-step of all pairs, then per pair the normal equations + reg_device_step -- enqueued by a host that only follows the
@@ -409,7 +420,7 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
                               const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
                               int L, unsigned long long* momq, double* rot, double* t, double scale, double lambda_c,
                               int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                              double* trace, bool shared_tree, DevBuf* table) {
+                              double* trace, bool shared_tree, DevBuf* table, const double* tg_w, const double* tg_wsum) {
     for (int b = 0; b < B; ++b) { iters_out[b] = 0; status_out[b] = 0; }
     if (max_iter < 1) return HGMM_OK;
     DevBuf& reg = table ? *table : c->fr_reg;
@@ -417,7 +428,7 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
     const size_t trace_bytes = trace ? sizeof(double) * 13 * (size_t)max_iter * B : 0;
     if (trace) HGMM_TRY(ensure(c, c->fr_trace, trace_bytes));
     const double gate = c->tree.reg_gate;                    // (hgmm_tree_set_reg_gate; finite: the gated instantiations)
-    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate));
+    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate), tg_w != nullptr);
     const auto solve_kernel = shared_tree ? tree_reg_multi_solve_kernel : forest_reg_solve_kernel;
     ForestRegPair* d_tab = reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
@@ -428,7 +439,7 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
     std::vector<ForestRegPair> tab(B);
     int64_t longest = 0;
     for (int b = 0; b < B; ++b) {
-        ForestRegPair& pr = tab[b] = reg_pair(tg_first[b], tg_counts[b]);
+        ForestRegPair& pr = tab[b] = reg_pair(tg_first[b], tg_counts[b], tg_w ? tg_wsum : nullptr, b);
         reg_pair_fill(pr, rigid_from(rot + 9 * b, t + 3 * b, scale), tg_rmax[b], mu_rmax[b]);
         pr.has_q = (q_prev_inout[b] == q_prev_inout[b]) ? 1 : 0;              // (NaN: no previous q)
         pr.q_prev = pr.has_q ? q_prev_inout[b] : 0.0;
@@ -446,7 +457,7 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
             {
                 ProfScope prof(c, HGMM_K_TREE_REG);
                 estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c, momq,
-                                                                                    (int)nblk(longest, CH), gate);
+                                                                                    (int)nblk(longest, CH), gate, tg_w);
             }
             solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace, words.dev);
             HGMM_HIP(c, hipGetLastError());
@@ -749,6 +760,7 @@ static int set_targets_batch(hgmm_ctx* c, int B, const IN* const* xyz, const int
     if (B < 1 || B > 4096 || !xyz || !counts) return fail(c, HGMM_ERR_ARG, "targets (batch): B = %d", B);
     ForestState& F = c->forest;
     F.tg_B = 0;
+    F.tg_weighted = false;                                 // (hgmm_tree_set_target_weights_batch: new targets drop the weights)
     int64_t total = 0, longest = 0;
     for (int b = 0; b < B; ++b) {
         if (!xyz[b] || counts[b] < 1) return fail(c, HGMM_ERR_ARG, "targets (batch): target %d is empty", b);
@@ -800,6 +812,45 @@ extern "C" int hgmm_tree_set_targets_batch_f32(hgmm_ctx* c, int B, const float* 
     return set_targets_batch<float>(c, B, xyz, counts);
 }
 
+// per-point weights of the resident targets (include/hgmm.h): fr_tg_w [tg_pad] parallel to fr_tg; an unweighted pair of a
+// weighted batch gets 1.0 per point and its count as the sum -- gamma * 1.0 is gamma, so it keeps its unweighted bits
+extern "C" int hgmm_tree_set_target_weights_batch(hgmm_ctx* c, int B, const double* const* w, const int64_t* counts) {
+    HGMM_ENTER(c);
+    const char* what = "hgmm_tree_set_target_weights_batch";
+    ForestState& F = c->forest;
+    if (F.tg_B < 1) return fail(c, HGMM_ERR_STATE, "%s: no targets (call hgmm_tree_set_targets_batch first)", what);
+    if (!w) { F.tg_weighted = false; return HGMM_OK; }
+    if (B != F.tg_B) return fail(c, HGMM_ERR_ARG, "%s: B = %d, but %d targets are resident", what, B, F.tg_B);
+    if (!counts) return fail(c, HGMM_ERR_ARG, "%s: counts is NULL", what);
+    std::vector<double> sums(B), padded((size_t)F.tg_pad, 0.0);
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] != F.tg_counts[b])
+            return fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident target %d has %lld points", what, b,
+                        (long long)counts[b], b, (long long)F.tg_counts[b]);
+        double* dst = padded.data() + F.tg_first[b];
+        if (!w[b]) {
+            std::fill(dst, dst + counts[b], 1.0);
+            sums[b] = (double)counts[b];
+            continue;
+        }
+        char label[96];
+        snprintf(label, sizeof label, "%s (target %d)", what, b);
+        HGMM_TRY(check_target_weights(c, label, w[b], counts[b], &sums[b]));
+        std::copy(w[b], w[b] + counts[b], dst);
+        any = true;
+    }
+    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
+    F.tg_weighted = false;
+    if (!any) return HGMM_OK;
+    HGMM_TRY(ensure(c, c->fr_tg_w, sizeof(double) * padded.size()));
+    HGMM_HIP(c, hipMemcpyAsync(c->fr_tg_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    F.tg_wsum = sums;
+    F.tg_weighted = true;
+    return HGMM_OK;
+}
+
 // The registration loop of B pairs with the 6 x 6 solves on the host (the default): per iteration one E-step launch and one
 // normal-equations launch for all pairs still running, each pair's 28 numbers solved as soon as its sequence word arrives.
 // The arguments are forest_register_on_device's; `momq` / `momq_clean`: the set's sums and their MomqScope flag.
@@ -807,7 +858,7 @@ static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t
                                    const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
                                    int L, DevBuf& momq, bool& momq_clean, double* rot, double* t, double scale, double lambda_c,
                                    int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                                   double* trace, bool shared_tree, DevBuf& reg) {
+                                   double* trace, bool shared_tree, DevBuf& reg, const double* tg_w, const double* tg_wsum) {
     const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, B, &hand));
@@ -815,7 +866,7 @@ static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t
     const HostDev<double> h_out = hand->out28(0);
     HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
     const double gate = c->tree.reg_gate;                    // (hgmm_tree_set_reg_gate; finite: the gated instantiations)
-    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate));
+    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate), tg_w != nullptr);
     const auto normal_kernel = shared_tree ? tree_reg_multi_normal_kernel : forest_reg_normal_kernel;
     ForestRegPair* d_tab = reg.as<ForestRegPair>();
     double* d_out = reinterpret_cast<double*>(d_tab + B);
@@ -830,7 +881,7 @@ static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t
     int n_active = B;
     for (int it = 0; it < max_iter && n_active > 0; ++it) {
         for (int b = 0; b < B; ++b) {
-            tab[b] = reg_pair(tg_first[b], tg_counts[b]);
+            tab[b] = reg_pair(tg_first[b], tg_counts[b], tg_w ? tg_wsum : nullptr, b);
             if (active[b]) reg_pair_fill(tab[b], rigid_from(rot + 9 * b, t + 3 * b, scale), tg_rmax[b], mu_rmax[b]);
         }
         HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
@@ -841,7 +892,7 @@ static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t
             ProfScope prof(c, HGMM_K_TREE_REG);
             estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c,
                                                                                 momq.as<unsigned long long>(), (int)nblk(longest, CH),
-                                                                                gate);
+                                                                                gate, tg_w);
         }
         normal_kernel<<<B, 256, 0, c->stream>>>(momq.as<unsigned long long>(), d_tab, prep, T, d_out, h_out.dev, words.dev, seq);
         HGMM_HIP(c, hipGetLastError());
@@ -890,19 +941,22 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
         return fail(c, HGMM_ERR_STATE, "registration (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
     const int T = F.T, L = F.L;
     const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
+    const double* tg_w = F.tg_weighted ? c->fr_tg_w.as<double>() : nullptr;      // (hgmm_tree_set_target_weights_batch)
+    const double* tg_wsum = F.tg_weighted ? F.tg_wsum.data() : nullptr;
     if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
         MomqScope sums(F.momq_clean);
         HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
         HGMM_TRY(forest_register_on_device(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(),
                                            F.tg_rmax.data(), F.mu_rmax.data(), c->fr_prep.as<double>(), T, L,
                                            c->fr_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, iters_out, status_out, trace));
+                                           q_prev_inout, iters_out, status_out, trace, false, nullptr, tg_w, tg_wsum));
         sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
         return HGMM_OK;
     }
     return forest_register_on_host(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(), F.tg_rmax.data(),
                                    F.mu_rmax.data(), c->fr_prep.as<double>(), T, L, c->fr_momq, F.momq_clean, rot, t, scale,
-                                   lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out, trace, false, c->fr_reg);
+                                   lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out, trace, false, c->fr_reg, tg_w,
+                                   tg_wsum);
 }
 
 // hgmm_tree_score on every pair (tree b, target b) of the resident forest, summaries only: include/hgmm.h
@@ -921,7 +975,7 @@ extern "C" int hgmm_tree_score_batch(hgmm_ctx* c, int B, const double* rot, cons
     std::vector<ForestRegPair> tab(B);
     int64_t longest = 0;
     for (int b = 0; b < B; ++b) {
-        tab[b] = reg_pair(F.tg_first[b], F.tg_counts[b]);
+        tab[b] = reg_pair(F.tg_first[b], F.tg_counts[b], F.tg_weighted ? F.tg_wsum.data() : nullptr, b);
         tab[b].tf = rigid_from(rot ? rot + 9 * b : nullptr, t ? t + 3 * b : nullptr, scale);
         longest = std::max(longest, F.tg_counts[b]);
     }
@@ -932,8 +986,10 @@ extern "C" int hgmm_tree_score_batch(hgmm_ctx* c, int B, const double* rot, cons
     HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
-        forest_score_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(c->fr_tg.as<double>(), F.tg_pad, d_tab, c->fr_prep.as<double>(),
-                                                                   T, L, lambda_c, maha2_max, partial, (int)gx);
+        const auto kernel = F.tg_weighted ? forest_score_kernel<true> : forest_score_kernel<false>;
+        kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(c->fr_tg.as<double>(), F.tg_pad, d_tab, c->fr_prep.as<double>(), T, L,
+                                                      lambda_c, maha2_max, partial, (int)gx,
+                                                      F.tg_weighted ? c->fr_tg_w.as<double>() : nullptr);
     }
     forest_score_finish_kernel<<<B, CH, 0, c->stream>>>(partial, d_tab, (int)gx, d_sum);
     HGMM_HIP(c, hipGetLastError());
@@ -968,18 +1024,21 @@ extern "C" int hgmm_tree_register_multi(hgmm_ctx* c, int K, double* rot, double*
     const std::vector<double> tg_rmax(K, c->tgt_rmax), mu_rmax(K, c->tree.mu_rmax);
     const double* tg = c->tgt_soa64.as<double>();
     const double* prep = c->t_prep.as<double>();
+    // (hgmm_tree_set_target_weights: the K hypotheses share the one weight array and its sum)
+    const double* tg_w = c->tgt_weighted ? c->tgt_w.as<double>() : nullptr;
+    const std::vector<double> tg_wsum(K, c->tgt_wsum);
     if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
         MomqScope sums(c->tree.multi_momq_clean);
         HGMM_TRY(sums.open(c, c->tm_momq, sizeof(unsigned long long) * 4 * (size_t)T * K));
         HGMM_TRY(forest_register_on_device(c, K, tg, c->tgt_pad, first.data(), counts.data(), tg_rmax.data(), mu_rmax.data(), prep,
                                            T, L, c->tm_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, iters_out, status_out, trace, true, &c->tm_reg));
+                                           q_prev_inout, iters_out, status_out, trace, true, &c->tm_reg, tg_w, tg_wsum.data()));
         sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
         return HGMM_OK;
     }
     return forest_register_on_host(c, K, tg, c->tgt_pad, first.data(), counts.data(), tg_rmax.data(), mu_rmax.data(), prep, T, L,
                                    c->tm_momq, c->tree.multi_momq_clean, rot, t, scale, lambda_c, max_iter, tol, q_prev_inout,
-                                   iters_out, status_out, trace, true, c->tm_reg);
+                                   iters_out, status_out, trace, true, c->tm_reg, tg_w, tg_wsum.data());
 }
 
 extern "C" int hgmm_tree_score_multi(hgmm_ctx* c, int K, const double* rot, const double* t, double scale, double lambda_c,
@@ -1004,11 +1063,12 @@ extern "C" int hgmm_tree_score_multi(hgmm_ctx* c, int K, const double* rot, cons
     HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * K));
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
-        tree_score_multi_kernel<<<gx * (unsigned)K, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, c->tgt_pad, d_tab,
-                                                                       c->t_prep.as<double>(), c->tree.L, lambda_c, maha2_max,
-                                                                       partial, (int)gx);
+        const auto kernel = c->tgt_weighted ? tree_score_multi_kernel<true> : tree_score_multi_kernel<false>;
+        kernel<<<gx * (unsigned)K, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, c->tgt_pad, d_tab, c->t_prep.as<double>(),
+                                                      c->tree.L, lambda_c, maha2_max, partial, (int)gx,
+                                                      c->tgt_weighted ? c->tgt_w.as<double>() : nullptr);
     }
-    tree_score_multi_finish_kernel<<<K, CH, 0, c->stream>>>(partial, (int)gx, (double)n, d_sum);
+    tree_score_multi_finish_kernel<<<K, CH, 0, c->stream>>>(partial, (int)gx, c->tgt_weighted ? c->tgt_wsum : (double)n, d_sum);
     HGMM_HIP(c, hipGetLastError());
     StagedDownloads dl(c);
     dl.add(summary_out, d_sum, sizeof(double) * 8 * K);

@@ -1493,14 +1493,18 @@ __device__ __forceinline__ int64_t reg_descend_level(const double x0, const doub
 // takes anyway.  The descent is NOT gated: the point moves on to its arg-max child and stops where it stops without the
 // gate; a NaN form fails the comparison.  A compile-time switch, so that the gate-off instantiations are the code they
 // were: the argument is not read there.
+// WEIGHTED (hgmm_tree_set_target_weights; no counterpart in the reference): the point's weight w[i] >= 0 -- one 8-byte load
+// next to its coordinates, `w` parallel to `tg` -- scales what it adds, gs <- gs * w, AFTER the descent, the stop rule, the
+// 1e-15 floor (tested on gamma, not on w gamma) and the gate, none of which sees the weight; a zero weight adds nothing and
+// issues no atomics.  The same compile-time pattern: the unweighted instantiations never read the pointer.
 constexpr int REG_LDS_NODES = 584;                       // levels 0..2 (8 + 64 + 512 nodes)
-template <int NMQ, bool GATED = false>
+template <int NMQ, bool GATED = false, bool WEIGHTED = false>
 __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive, const double* __restrict__ tg,
                                                     int64_t n_pad, const Rigid& tf, const double* __restrict__ prep, int L,
                                                     double lambda_c, double inv_d, double fix_scale,
                                                     unsigned long long* __restrict__ momq,
                                                     unsigned long long* __restrict__ tab /* LDS [REG_LDS_NODES * NMQ] */,
-                                                    double maha2_gate = INFINITY) {
+                                                    double maha2_gate = INFINITY, const double* __restrict__ w = nullptr) {
     const int lds_nodes = (int)(level_first(L < 3 ? L : 3));
     __shared__ double exp_tab[EXP_TAB_N];                  // the build's exponential (exp_nonpos4): 17 instructions per value
     exp_tab_load(exp_tab);
@@ -1508,6 +1512,10 @@ __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive,
     __syncthreads();
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
     if (alive) rigid_apply(tf, tg[i], tg[n_pad + i], tg[2 * n_pad + i], x0, x1, x2);
+    double wi = 0.0;
+    if constexpr (WEIGHTED) {
+        if (alive) wi = w[i];
+    }
     int64_t search = -1;
     for (int l = 0; l < L; ++l) {
         if (!__any(alive)) break;
@@ -1532,6 +1540,10 @@ __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive,
                 const double d0 = x0 - pr[6], d1 = x1 - pr[7], d2 = x2 - pr[8];
                 contribute = sym3_quad(pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], d0, d1, d2) <= maha2_gate;
             }
+        }
+        if constexpr (WEIGHTED) {
+            gs *= wi;
+            contribute = contribute && wi > 0.0;
         }
         // this lane's contribution in fixed point, about the node's mean, in units of D
         long long q[NMQ];
@@ -1586,12 +1598,16 @@ __device__ __forceinline__ void tree_reg_estep_body(const int64_t i, bool alive,
 //     partial[0..5].  tree_score_finish_body adds the workgroups' shares in a fixed order, so the eight numbers depend on
 //     the points and their grouping into 256-point workgroups alone: the same for a pair alone and inside a batch.
 // i: the point's place in `tg`; o: its place in the output arrays; alive: the point exists.
+// WEIGHTED (hgmm_tree_set_target_weights): the point's six terms are multiplied by its weight weights[i] before the wave sums (a zero
+// weight adds nothing); what is stored per point is not weighted.  The unweighted instantiation never reads the pointer.
 constexpr int SCORE_NSUM = 6;
+template <bool WEIGHTED = false>
 __device__ __forceinline__ void tree_score_body(const int64_t i, const int64_t o, bool alive,
                                                 const double* __restrict__ tg, int64_t n_pad, const Rigid& tf,
                                                 const double* __restrict__ prep, int L, double lambda_c, double maha2_max,
                                                 int32_t* __restrict__ node_out, double* __restrict__ maha2_out,
-                                                double* __restrict__ logp_out, double* __restrict__ partial) {
+                                                double* __restrict__ logp_out, double* __restrict__ partial,
+                                                const double* __restrict__ weights = nullptr) {
     __shared__ double exp_tab[EXP_TAB_N];
     __shared__ double sh[CH / 64][SCORE_NSUM];
     exp_tab_load(exp_tab);
@@ -1629,6 +1645,11 @@ __device__ __forceinline__ void tree_score_body(const int64_t i, const int64_t o
         }
         acc[4] = dead ? 1.0 : 0.0;
         acc[5] = (search < level_first(L - 1)) ? 1.0 : 0.0;
+        if constexpr (WEIGHTED) {
+            const double wi = weights[i];
+#pragma unroll
+            for (int k = 0; k < SCORE_NSUM; ++k) acc[k] = wi > 0.0 ? acc[k] * wi : 0.0;
+        }
     }
 #pragma unroll
     for (int k = 0; k < SCORE_NSUM; ++k) {
@@ -1646,6 +1667,7 @@ __device__ __forceinline__ void tree_score_body(const int64_t i, const int64_t o
 
 // The shares partial[nb][SCORE_NSUM] of one target's workgroups -> its summary[8]: ONE workgroup; thread t adds the shares
 // t, t + 256, ... in index order, then the wave sum and the four waves in order -- a function of nb alone.
+// n_points: summary[0] -- the number of points, or the sum of their weights under hgmm_tree_set_target_weights.
 __device__ __forceinline__ void tree_score_finish_body(const double* __restrict__ partial, int nb, double n_points,
                                                        double* __restrict__ summary) {
     __shared__ double sh[CH / 64][SCORE_NSUM];
@@ -1998,7 +2020,8 @@ __host__ __device__ inline double reg_extent(const Rigid& tf, double tgt_rmax, d
     return fabs(tf.s) * sqrt(rn) * tgt_rmax + sqrt(tn) + mu_rmax;
 }
 // encoding of the registration E-step's fixed-point sums: D = the extent rounded up to a power of two, F fractional bits
-// such that n_all terms cannot overflow 62 bits
+// such that n_all terms cannot overflow 62 bits (n_all: the number of target points over all ranks, or the sum of their
+// weights under hgmm_tree_set_target_weights -- a term is w gamma <= w)
 __host__ __device__ inline void reg_encoding(double ext, double n_all, double* D_out, int* F_out) {
     if (!(ext > 0.0) || !(ext < 1.0e300)) ext = 1.0;              // (not positive, NaN or infinite)
     int e2 = 0;
@@ -2018,6 +2041,7 @@ struct ForestRegPair {
     int active, pad;
     double q_prev, tg_rmax, mu_rmax;     // q of the previous iteration (valid with has_q), extent bounds of the encoding
     int has_q, it, status, pad2;         // iterations done; 0: running / budget used up, 1: |dq| < tol, 2: ill-conditioned
+    double tg_wsum;                      // n_all of reg_encoding: the sum of the target's weights, (double)tg_count without weights
 };
 
 // The host side of a registration iteration (reg_host_step) done by ONE device thread (per-context option
@@ -2115,7 +2139,7 @@ __device__ inline void reg_device_step(const double* __restrict__ o, ForestRegPa
     if (stop || it + 1 >= max_iter) { pr->active = 0; return; }
     double D = 1.0;
     int F = 0;
-    reg_encoding(reg_extent(tf, pr->tg_rmax, pr->mu_rmax), (double)pr->tg_count, &D, &F);
+    reg_encoding(reg_extent(tf, pr->tg_rmax, pr->mu_rmax), pr->tg_wsum, &D, &F);
     pr->inv_d = 1.0 / D;
     pr->fix_scale = ldexp(1.0, F);
     pr->d_ext = D;
@@ -2125,11 +2149,13 @@ __device__ inline void reg_device_step(const double* __restrict__ o, ForestRegPa
 // the registration loop on the device alone (tree_batch.hip; hgmm_tree_register uses it with B = 1 on the serial buffers).
 // shared_tree: the B registrations are start poses of ONE pair (hgmm_tree_register_multi) -- `prep` is one tree's table and
 // every entry of tg_first / tg_counts names the same target; `table` (NULL: fr_reg) holds the B entries and 28 B numbers.
+// tg_w (device, parallel to tg; NULL: no weights) / tg_wsum (host [B], with tg_w): hgmm_tree_set_target_weights[_batch].
 int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg_pad, const int64_t* tg_first,
                               const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
                               int L, unsigned long long* momq, double* rot, double* t, double scale, double lambda_c,
                               int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                              double* trace, bool shared_tree = false, hgmm::DevBuf* table = nullptr);
+                              double* trace, bool shared_tree = false, hgmm::DevBuf* table = nullptr,
+                              const double* tg_w = nullptr, const double* tg_wsum = nullptr);
 
 // ---- kernels defined in tree_kernels.hip that the batched path (tree_batch.hip) launches as they are -----------------
 constexpr int OFF_BLOCK = 256;

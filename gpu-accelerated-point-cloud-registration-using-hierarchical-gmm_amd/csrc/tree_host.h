@@ -123,11 +123,13 @@ inline Rigid rigid_from(const double* rot, const double* t, double scale) {
     return tf;
 }
 // a pair's table entry: its target's slice, everything else zero (a pair that takes no part)
-inline ForestRegPair reg_pair(int64_t tg_first, int64_t tg_count) {
+// (tg_wsum: the targets' weight sums, NULL without weights -- the count then, as a double)
+inline ForestRegPair reg_pair(int64_t tg_first, int64_t tg_count, const double* tg_wsum = nullptr, int b = 0) {
     ForestRegPair pr;
     std::memset(&pr, 0, sizeof pr);
     pr.tg_first = (int)tg_first;
     pr.tg_count = (int)tg_count;
+    pr.tg_wsum = tg_wsum ? tg_wsum[b] : (double)tg_count;
     return pr;
 }
 // ... of a pair that takes part: its transform and the fixed-point encoding of its next E-step
@@ -136,7 +138,7 @@ inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, double tg_rmax, do
     pr.tf = tf;
     double D = 1.0;
     int F = 0;
-    reg_encoding(reg_extent(tf, tg_rmax, mu_rmax), (double)pr.tg_count, &D, &F);
+    reg_encoding(reg_extent(tf, tg_rmax, mu_rmax), pr.tg_wsum, &D, &F);
     pr.inv_d = 1.0 / D;
     pr.fix_scale = std::ldexp(1.0, F);
     pr.d_ext = D;
@@ -144,6 +146,8 @@ inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, double tg_rmax, do
     pr.tg_rmax = tg_rmax;
     pr.mu_rmax = mu_rmax;
 }
+// (tree_kernels.hip) one cloud's weights for hgmm_tree_set_target_weights[_batch]: finite, >= 0, not all zero; their sum
+int check_target_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out);
 // largest |mu_j| of the resident tree; a tree built on the device has not shown its means to the host yet
 inline int tree_mu_rmax_resident(hgmm_ctx* c) {
     if (c->tree.mu_rmax >= 0.0) return HGMM_OK;

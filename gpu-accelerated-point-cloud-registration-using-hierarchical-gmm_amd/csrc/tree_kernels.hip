@@ -445,27 +445,38 @@ __global__ void tree_unsort_kernel(const int* __restrict__ perm, const int* __re
 
 
 // (GATED: hgmm_tree_set_reg_gate's finite gate, tree_reg_estep_body; the gate-off instantiations do not read the argument)
-template <int NMQ, bool GATED = false>
+// (WEIGHTED: hgmm_tree_set_target_weights' array w [n_pad], likewise: the unweighted instantiations do not read the pointer)
+template <int NMQ, bool GATED = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_reg_estep_kernel(const double* __restrict__ tg, int64_t n,
                                                             int64_t n_pad, Rigid tf,
                                                             const double* __restrict__ prep, int L,
                                                             double lambda_c, double inv_d, double fix_scale,
-                                                            unsigned long long* __restrict__ momq, double maha2_gate) {
+                                                            unsigned long long* __restrict__ momq, double maha2_gate,
+                                                            const double* __restrict__ w) {
     __shared__ unsigned long long tab[REG_LDS_NODES * NMQ];
     const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ, GATED>(i, i < n, tg, n_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq, tab, maha2_gate);
+    tree_reg_estep_body<NMQ, GATED, WEIGHTED>(i, i < n, tg, n_pad, tf, prep, L, lambda_c, inv_d, fix_scale, momq, tab,
+                                              maha2_gate, w);
+}
+// the instantiation for the context's gate and weights
+template <int NMQ>
+static auto tree_reg_estep_kernel_for(bool gated, bool weighted) -> decltype(&tree_reg_estep_kernel<NMQ, false, false>) {
+    if (weighted) return gated ? tree_reg_estep_kernel<NMQ, true, true> : tree_reg_estep_kernel<NMQ, false, true>;
+    return gated ? tree_reg_estep_kernel<NMQ, true, false> : tree_reg_estep_kernel<NMQ, false, false>;
 }
 
 // score of the resident target against the resident tree (tree_score_body, csrc/tree_device.h): workgroup b writes its six
 // sums to partial[b]; tree_score_finish_kernel (one workgroup) adds them in a fixed order into summary[8]
+// (WEIGHTED: hgmm_tree_set_target_weights' array w [n_pad]; the unweighted instantiation does not read the pointer)
+template <bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_score_kernel(const double* __restrict__ tg, int64_t n, int64_t n_pad, Rigid tf,
                                                         const double* __restrict__ prep, int L, double lambda_c,
                                                         double maha2_max, int32_t* __restrict__ node_out,
                                                         double* __restrict__ maha2_out, double* __restrict__ logp_out,
-                                                        double* __restrict__ partial) {
+                                                        double* __restrict__ partial, const double* __restrict__ w) {
     const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
-    tree_score_body(i, i, i < n, tg, n_pad, tf, prep, L, lambda_c, maha2_max, node_out, maha2_out, logp_out,
-                    partial + (size_t)SCORE_NSUM * blockIdx.x);
+    tree_score_body<WEIGHTED>(i, i, i < n, tg, n_pad, tf, prep, L, lambda_c, maha2_max, node_out, maha2_out, logp_out,
+                              partial + (size_t)SCORE_NSUM * blockIdx.x, w);
 }
 __global__ __launch_bounds__(CH) void tree_score_finish_kernel(const double* __restrict__ partial, int nb, double n_points,
                                                                double* __restrict__ summary) {
@@ -1068,6 +1079,42 @@ extern "C" int hgmm_tree_set_target(hgmm_ctx* c, const double* xyz, int64_t n) {
     HGMM_HIP(c, ctx_stream_sync(c));
     c->tgt_n = n;
     c->tgt_pad = n_pad;
+    c->tgt_weighted = false;                                    // (hgmm_tree_set_target_weights: a new target drops them)
+    return HGMM_OK;
+}
+
+// what both weight entries ask of one cloud's weights: finite, >= 0, not all zero; *sum_out: their sum in index order
+int hgmm::check_target_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out) {
+    double sum = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(w[i] >= 0.0) || !(w[i] < INFINITY))                 // (NaN fails the first comparison)
+            return fail(c, HGMM_ERR_ARG, "%s: weight %lld is %g (weights must be finite and >= 0)", what, (long long)i, w[i]);
+        sum += w[i];
+    }
+    if (!(sum > 0.0)) return fail(c, HGMM_ERR_ARG, "%s: all %lld weights are zero", what, (long long)n);
+    if (!(sum < INFINITY)) return fail(c, HGMM_ERR_ARG, "%s: the weights' sum is not finite", what);
+    *sum_out = sum;
+    return HGMM_OK;
+}
+
+extern "C" int hgmm_tree_set_target_weights(hgmm_ctx* c, const double* w, int64_t n) {
+    HGMM_ENTER(c);
+    if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "hgmm_tree_set_target_weights: no target (call hgmm_tree_set_target first)");
+    if (!w) { c->tgt_weighted = false; return HGMM_OK; }
+    if (n != c->tgt_n)
+        return fail(c, HGMM_ERR_ARG, "hgmm_tree_set_target_weights: %lld weights, but the resident target has %lld points",
+                    (long long)n, (long long)c->tgt_n);
+    double sum = 0.0;
+    HGMM_TRY(check_target_weights(c, "hgmm_tree_set_target_weights", w, n, &sum));
+    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
+    c->tgt_weighted = false;
+    std::vector<double> padded((size_t)c->tgt_pad, 0.0);
+    std::copy(w, w + n, padded.begin());
+    HGMM_TRY(ensure(c, c->tgt_w, sizeof(double) * padded.size()));
+    HGMM_HIP(c, hipMemcpyAsync(c->tgt_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    c->tgt_wsum = sum;
+    c->tgt_weighted = true;
     return HGMM_OK;
 }
 
@@ -1089,7 +1136,7 @@ static int reg_estep_fixed(hgmm_ctx* c, MomqScope& sums, const double* rot, cons
         HGMM_TRY(hgmm_comm_allreduce_f64(c, &e, 1, 1));
         ext = e;
     }
-    double n_all = (double)c->tgt_n;
+    double n_all = c->tgt_weighted ? c->tgt_wsum : (double)c->tgt_n;     // (weights: this rank's shard's, like its points)
     if (c->comm_on()) HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_all, 1, 0));
     double D = 1.0;
     int F = 0;
@@ -1099,10 +1146,11 @@ static int reg_estep_fixed(hgmm_ctx* c, MomqScope& sums, const double* rot, cons
     {
         ProfScope prof(c, HGMM_K_TREE_REG);
         const double gate = c->tree.reg_gate;
-        const auto kernel = std::isfinite(gate) ? tree_reg_estep_kernel<NMQ, true> : tree_reg_estep_kernel<NMQ, false>;
+        const auto kernel = tree_reg_estep_kernel_for<NMQ>(std::isfinite(gate), c->tgt_weighted);
         kernel<<<nblk(c->tgt_n, CH), CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), c->tgt_n, c->tgt_pad, tf,
                                                          c->t_prep.as<double>(), c->tree.L, lambda_c, 1.0 / D,
-                                                         std::ldexp(1.0, F), mq, gate);
+                                                         std::ldexp(1.0, F), mq, gate,
+                                                         c->tgt_weighted ? c->tgt_w.as<double>() : nullptr);
     }
     HGMM_HIP(c, hipGetLastError());
     if (c->comm_on()) HGMM_TRY(allreduce_i64_dev(c, reinterpret_cast<long long*>(mq), (size_t)NMQ * T));
@@ -1185,7 +1233,9 @@ extern "C" int hgmm_tree_register(hgmm_ctx* c, double* rot, double* t, double sc
         HGMM_TRY(forest_register_on_device(c, 1, c->tgt_soa64.as<double>(), c->tgt_pad, &first, &count, &c->tgt_rmax,
                                            &c->tree.mu_rmax, c->t_prep.as<double>(), (int)T, c->tree.L,
                                            c->t_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, &it32, &st32, trace));
+                                           q_prev_inout, &it32, &st32, trace, false, nullptr,
+                                           c->tgt_weighted ? c->tgt_w.as<double>() : nullptr,
+                                           c->tgt_weighted ? &c->tgt_wsum : nullptr));
         sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
         *iters_out = it32;
         *status_out = st32;
@@ -1238,10 +1288,12 @@ extern "C" int hgmm_tree_score(hgmm_ctx* c, const double* rot, const double* t, 
     int32_t* d_node = node_out ? reinterpret_cast<int32_t*>(at) : nullptr;
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
-        tree_score_kernel<<<nb, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, n_pad, tf, c->t_prep.as<double>(), c->tree.L,
-                                                    lambda_c, maha2_max, d_node, d_maha, d_logp, partial);
+        const auto kernel = c->tgt_weighted ? tree_score_kernel<true> : tree_score_kernel<false>;
+        kernel<<<nb, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, n_pad, tf, c->t_prep.as<double>(), c->tree.L, lambda_c,
+                                         maha2_max, d_node, d_maha, d_logp, partial,
+                                         c->tgt_weighted ? c->tgt_w.as<double>() : nullptr);
     }
-    tree_score_finish_kernel<<<1, CH, 0, c->stream>>>(partial, (int)nb, (double)n, d_sum);
+    tree_score_finish_kernel<<<1, CH, 0, c->stream>>>(partial, (int)nb, c->tgt_weighted ? c->tgt_wsum : (double)n, d_sum);
     HGMM_HIP(c, hipGetLastError());
     StagedDownloads dl(c);
     dl.add(summary_out, d_sum, sizeof(double) * 8);

@@ -63,6 +63,46 @@ def _gate_arg(maha2_gate):
     return g
 
 
+WeightedPoints = namedtuple("WeightedPoints", ["points", "weights"])
+WeightedPoints.__doc__ = """A target cloud with one weight >= 0 per point: ``WeightedPoints(points [N,3], weights [N])``.  Every
+entry that takes a target takes this in its place (any object with ``.points`` and ``.weights`` does) -- the way to hand
+weights to :meth:`GMMTree.registration_multistart` and :meth:`GMMTree.score`, whose argument lists are the reference-side
+ones; an explicit ``weights=`` / ``target_weights=`` argument, where there is one, takes precedence."""
+
+
+def _weights_arg(weights, n):
+    """The mirrors' ``weights`` argument for a target of ``n`` points -> None (no weights) or a float64 array [n], every entry
+    finite and >= 0 and not all of them zero.  Anything else is refused here, before the library is touched."""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] != int(n):
+        raise ValueError("weights must be one per target point: expected shape (%d,), got %s" % (int(n), w.shape))
+    bad = np.nonzero(~(np.isfinite(w) & (w >= 0.0)))[0]
+    if len(bad):
+        raise ValueError("weights must be finite and >= 0: weight %d is %r" % (int(bad[0]), float(w[bad[0]])))
+    if not w.sum() > 0.0:
+        raise ValueError("weights must not all be zero")
+    return w
+
+
+def _target_weights(target, weights=None):
+    """The weights that go with ``target``: the explicit argument, else the target's own ``.weights`` (WeightedPoints), else
+    None -- checked against the target's length."""
+    if weights is None:
+        weights = getattr(target, "weights", None)
+    return _weights_arg(weights, len(_points(target)))
+
+
+def _set_target(ctx, target, weights=None):
+    """Upload ``target`` as the context's resident registration target, with its weights if it has any.  A new target drops
+    the weights of the previous one in the library, so a target is never registered under another one's weights."""
+    w = _target_weights(target, weights)
+    ctx.tree_set_target(_points(target))
+    if w is not None:
+        ctx.tree_set_target_weights(w)
+
+
 @contextlib.contextmanager
 def _reg_gate(ctx, gate):
     """``Context.tree_set_reg_gate(gate)`` for the calls inside, the context's previous gate afterwards (as buildGMMTree does
@@ -251,15 +291,17 @@ def tree_score_from_summary(summary, arrays=None):
 
     With NO inlier there is nothing to average: fitness is 0.0, ``inlier_rmse`` and ``mahalanobis_rms`` are +inf and
     ``mean_log_density`` is -inf ("infinitely far"), so no field is ever NaN through a division by zero and a threshold
-    test on any of them rejects such a cloud."""
+    test on any of them rejects such a cloud.  Under per-point weights of the target the sums are weighted: ``n``,
+    ``n_inliers`` and the two other counts are then sums of weights (floats unless they happen to be whole numbers)."""
     s = np.asarray(summary, dtype=np.float64).reshape(8)
     arrays = arrays or {}
-    n, n_in = int(s[0]), int(s[1])
+    count = lambda v: int(v) if v == int(v) else float(v)      # (a sum of weights need not be a whole number)
+    n, n_in = count(s[0]), count(s[1])
     if n_in > 0:
         rmse, mrms, mld = float(np.sqrt(s[3] / s[1])), float(np.sqrt(s[2] / s[1])), float(s[4] / s[1])
     else:
         rmse, mrms, mld = float("inf"), float("inf"), float("-inf")
-    return TreeScore(float(s[1] / s[0]) if n > 0 else 0.0, rmse, mrms, mld, n, n_in, int(s[5]), int(s[6]),
+    return TreeScore(float(s[1] / s[0]) if n > 0 else 0.0, rmse, mrms, mld, n, n_in, count(s[5]), count(s[6]),
                      arrays.get("node"), arrays.get("maha2"), arrays.get("logp"))
 
 
@@ -323,7 +365,14 @@ class GMMTree():
     E-step (``Context.tree_set_reg_gate``) for this object's registrations -- a (point, node) pair further than this
     squared Mahalanobis distance from the node adds nothing to its moments, which keeps clutter and the non-overlapping
     part of a scan from pulling the nodes.  ``CHI2_3_999`` is a reasonable value.  It is set on the context for the
-    object's own calls only; the context's previous gate is restored after each."""
+    object's own calls only; the context's previous gate is restored after each.
+
+    Per-point WEIGHTS of a target (no counterpart in the reference; ``Context.tree_set_target_weights``): a target point
+    with weight w adds ``w * gamma`` where it added ``gamma`` -- a voxel centroid with its count
+    (``voxel_down_sample(..., return_counts=True)``), a return weighted by range, the caller's own M-estimator weights.
+    ``registration(..., weights=)`` takes them as an argument; every method that takes a target (``registration``,
+    ``registration_multistart``, ``score``, ``expectation_step``) takes a :class:`WeightedPoints` in its place.  The
+    descent, the stop rule and the gate do not see them; the per-point arrays of a score are not weighted, its sums are."""
 
     def __init__(self, source=None, tree_level=5, lambda_c=0.01, ls=20, ld=1.0e-4, sig2=0.004,
                  init_idx=None, ctx: Context | None = None, verbose=False, solve_on_device=False, maha2_gate=None):
@@ -381,7 +430,7 @@ class GMMTree():
         T = len(self._mixingCoeff)
         with _reg_gate(self._ctx, self._maha2_gate):
             if target is not None:
-                self._ctx.tree_set_target(_points(target))
+                _set_target(self._ctx, target)
                 self._target_id = None
                 m = self._ctx.tree_reg_estep(T, lambda_c=self._lambda_c)
             else:
@@ -510,9 +559,11 @@ class GMMTree():
         given.  Every point descends the tree as in the registration E-step with this tree's ``lambda_c`` and is scored at the
         node it stops at.  The returned object is inverted again here, and ``-R (-R^T t)`` rounds: the result agrees with
         ``registration(..., return_score=True)`` (which uses the loop's own pose) to rounding, not bit for bit.
-        ``per_point=False`` leaves ``node`` / ``maha2`` / ``logp`` None (nothing N-long is stored or downloaded)."""
+        ``per_point=False`` leaves ``node`` / ``maha2`` / ``logp`` None (nothing N-long is stored or downloaded).
+        A :class:`WeightedPoints` target: the sums behind the score are weighted (``n`` is the sum of the weights), the
+        per-point arrays are not."""
         self._ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
-        self._ctx.tree_set_target(_points(target))
+        _set_target(self._ctx, target)
         self._target_id = None
         rot = t = None
         scale = 1.0
@@ -533,17 +584,21 @@ class GMMTree():
         self._target_id = None
         return self._ctx.tree_score(lambda_c=-1.0, want=("node",))[1]["node"]
 
-    def registration(self, target, maxiter=20, tol=1.0e-4, return_score=False, maha2_max=CHI2_3_99, maha2_gate=None):
+    def registration(self, target, maxiter=20, tol=1.0e-4, return_score=False, maha2_max=CHI2_3_99, maha2_gate=None,
+                     weights=None):
         """-> MstepResult(tf.inverse(), q)   (hgmm_gpu.py:754-768).  ``return_score=True``: ScoredResult(tf.inverse(), q,
         score) with the :class:`TreeScore` of the target at the final pose, taken with the loop's own (R, t).
-        ``maha2_gate``: the E-step's Mahalanobis gate for this call (default None: the object's own, see the class)."""
+        ``maha2_gate``: the E-step's Mahalanobis gate for this call (default None: the object's own, see the class).
+        ``weights`` [N] >= 0 (default None: the target's own if it is a :class:`WeightedPoints`, else none): per-point
+        weights of the target, see the class; the score of ``return_score`` is taken under them too."""
+        weights = _target_weights(target, weights)   # (refused before anything is uploaded)
         gate = _gate_arg(maha2_gate)
         prev_gate = self._maha2_gate
         if gate is not None:
             self._maha2_gate = gate                  # (the host M-step's expectation_step inside the loop follows it too)
         try:
             with _reg_gate(self._ctx, self._maha2_gate):
-                res = self._registration(target, maxiter, tol)
+                res = self._registration(target, maxiter, tol, weights)
         finally:
             self._maha2_gate = prev_gate
         if return_score:
@@ -564,7 +619,7 @@ class GMMTree():
         -> :class:`MultiStartResult` (a ``ScoredResult(tf.inverse(), q, score)``) of the winner, with ``best_index_`` and
         ``n_iter_`` (also set on this object); with ``return_all`` also a list of K ``ScoredResult``s -- only the winner's
         score carries the per-point arrays (one serial ``hgmm_tree_score``).  The object's ``maha2_gate`` (see the class)
-        applies to every hypothesis."""
+        applies to every hypothesis, and so do the weights of a :class:`WeightedPoints` target (one array, shared)."""
         with _reg_gate(self._ctx, self._maha2_gate):
             return self._registration_multistart(target, starts, maxiter, tol, maha2_max, return_all)
 
@@ -577,7 +632,7 @@ class GMMTree():
             raise ValueError("registration_multistart: the start poses must share one scale")
         ctx = self._ctx
         ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
-        ctx.tree_set_target(_points(target))
+        _set_target(ctx, target)
         rot0 = np.stack([np.asarray(s.rot, dtype=np.float64).reshape(3, 3) for s in starts])
         t0 = np.stack([np.asarray(s.t, dtype=np.float64).reshape(3) for s in starts])
         with (ctx.config(reg_device_solve=1) if self._solve_on_device else contextlib.nullcontext()):
@@ -603,9 +658,9 @@ class GMMTree():
                  for k in range(len(starts))]
         return winner, every
 
-    def _registration(self, target, maxiter, tol):
+    def _registration(self, target, maxiter, tol, weights=None):
         self._ctx.tree_set_nodes(self._tree_level, self._mixingCoeff, self._mean, self._covar)
-        self._ctx.tree_set_target(_points(target))
+        _set_target(self._ctx, target, weights)
         if self._device_mstep and not self._callbacks:
             return self._registration_in_library(maxiter, tol)
         q = None
@@ -660,12 +715,16 @@ def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
 def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, starts=None, **kargs):
     """hgmm_gpu.py:802-807.  ``return_score=True``: ScoredResult(transformation, q, score) -- see :meth:`GMMTree.registration`.
     ``starts`` (a list of start poses, e.g. :func:`rotation_starts`): :meth:`GMMTree.registration_multistart`'s result.
-    ``maha2_gate=`` (among :class:`GMMTree`'s arguments): the registration E-step's Mahalanobis gate, with or without ``starts``."""
+    ``maha2_gate=`` (among :class:`GMMTree`'s arguments): the registration E-step's Mahalanobis gate, with or without ``starts``.
+    ``target_weights=`` [N] >= 0 (a keyword of this function, not of :class:`GMMTree`; default: the target's own if it is a
+    :class:`WeightedPoints`): per-point weights of the target, with or without ``starts``."""
+    weights = _target_weights(target, kargs.pop("target_weights", None))
     gt = GMMTree(_points(source), **kargs)
     if starts is not None:
-        return gt.registration_multistart(_points(target), starts, maxiter, tol)
+        tgt = _points(target) if weights is None else WeightedPoints(_points(target), weights)
+        return gt.registration_multistart(tgt, starts, maxiter, tol)
     gt.set_callbacks(callbacks)
-    return gt.registration(_points(target), maxiter, tol, return_score=return_score)
+    return gt.registration(_points(target), maxiter, tol, return_score=return_score, weights=weights)
 
 
 BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this size (csrc/tree_batch.hip)
@@ -673,7 +732,7 @@ BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this 
 
 def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | None = None, tree_level=5, lambda_c=0.01,
                                ls=20, ld=1.0e-4, sig2=0.004, init_idx=None, return_info=False, pdf_dtype=None,
-                               solve_on_device=False, score=False, maha2_gate=None):
+                               solve_on_device=False, score=False, maha2_gate=None, target_weights=None):
     """``[registration_gmmtree(s, t, maxiter, tol, tree_level=..., ...) for s, t in pairs]`` (hgmm_gpu.py:802-807 per pair)
     with ALL pairs in the same launches: the B source clouds are one resident forest (``hgmm_tree_build_batch``: levels in
     lock-step, one stop rule per cloud), the B targets are registered against their trees together
@@ -694,6 +753,10 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     ``maha2_gate`` (default None: no gate): the registration E-step's Mahalanobis gate for every pair, as in
     :class:`GMMTree`; pairs that run or finish serially are registered under it too.  The context's own gate is restored.
 
+    ``target_weights`` (default None: none): a list with one entry per pair -- per-point weights [N_b] >= 0 of that pair's
+    target as in :class:`GMMTree`, or None for a pair without (a target that is a :class:`WeightedPoints` brings its own);
+    the scores of ``score=True`` are taken under them, and pairs that run or finish serially follow them too.
+
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
     gate = _gate_arg(maha2_gate)
@@ -701,6 +764,10 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     pairs = list(pairs)
     if not pairs:
         return ([], {}) if return_info else []
+    if target_weights is not None and len(target_weights) != len(pairs):
+        raise ValueError("target_weights must have one entry (an array or None) per pair: %d entries for %d pairs"
+                         % (len(target_weights), len(pairs)))
+    ws = [_target_weights(pairs[k][1], None if target_weights is None else target_weights[k]) for k in range(len(pairs))]
     big = [k for k, (s, _) in enumerate(pairs) if len(_points(s)) >= BATCH_MAX_POINTS]
     if big:
         # a cloud of >= 400 000 points fills the chip by itself and takes the serial build's four-points-per-thread
@@ -713,14 +780,14 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
         for k in big:
             gt = GMMTree(pairs[k][0], tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, init_idx=init_idx, ctx=ctx,
                          solve_on_device=solve_on_device, maha2_gate=gate)
-            out[k] = gt.registration(_points(pairs[k][1]), maxiter, tol)
+            out[k] = gt.registration(_points(pairs[k][1]), maxiter, tol, weights=ws[k])
             info["registration_iters"][k], info["status"][k] = int(gt.n_iter_), 0
             if score:
                 info["score"][k] = gt._score_resident(per_point=False)
         rest = [k for k in range(len(pairs)) if k not in set(big)]
         if rest:
             r, inf = registration_gmmtree_batch([pairs[k] for k in rest], maxiter, tol, ctx, tree_level, lambda_c, ls, ld, sig2,
-                                                init_idx, True, pdf_dtype, solve_on_device, score, gate)
+                                                init_idx, True, pdf_dtype, solve_on_device, score, gate, [ws[k] for k in rest])
             for j, k in enumerate(rest):
                 out[k] = r[j]
                 info["build_iters"][k] = inf["build_iters"][j]
@@ -738,7 +805,8 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
             for kind in sorted(set(kinds), key=str):
                 sel = [k for k, v in enumerate(kinds) if v == kind]
                 r, inf = registration_gmmtree_batch([pairs[k] for k in sel], maxiter, tol, ctx, tree_level, lambda_c, ls, ld,
-                                                    sig2, init_idx, True, kind, solve_on_device, score, gate)
+                                                    sig2, init_idx, True, kind, solve_on_device, score, gate,
+                                                    [ws[k] for k in sel])
                 for j, k in enumerate(sel):
                     out[k] = r[j]
                     for key in info:
@@ -765,7 +833,10 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     finally:
         ctx.tree_set_precision(prev)
     clock.append(time.perf_counter())
-    ctx.tree_set_targets_batch(tgts)
+    if any(w is not None for w in ws):
+        ctx.tree_set_targets_batch(tgts, weights=ws)
+    else:
+        ctx.tree_set_targets_batch(tgts)
     clock.append(time.perf_counter())
     rot0 = np.tile(np.identity(3), (B, 1, 1))
     with _reg_gate(ctx, gate):                                   # (the batch AND the pairs finished serially below)
@@ -790,7 +861,7 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
                 gt.set_nodes(*ctx.tree_get_nodes_batch(b, tree_level))
                 gt._tf_result = RigidTransformation(rot[b], t[b])
                 ctx.tree_set_nodes(tree_level, gt._mixingCoeff, gt._mean, gt._covar)
-                ctx.tree_set_target(tgts[b])
+                _set_target(ctx, tgts[b], ws[b])
                 res = gt._registration_in_library(maxiter, tol, _resume=(int(iters[b]), None if np.isnan(q[b]) else float(q[b]), True))
                 reg_iters[b] = int(gt.n_iter_)
                 if score:                                                 # (its pose moved on: the serial entry, at the final pose)

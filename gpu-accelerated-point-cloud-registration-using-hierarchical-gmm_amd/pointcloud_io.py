@@ -158,10 +158,13 @@ def read_point_cloud(path) -> np.ndarray:
     raise ValueError("unsupported point-cloud format: %s" % path)
 
 
-def voxel_down_sample(points, voxel_size: float) -> np.ndarray:
+def voxel_down_sample(points, voxel_size: float, return_counts: bool = False):
     """One point per occupied voxel = the mean of the points inside it (what Open3D's
     ``voxel_down_sample`` computes: grid origin at ``min_bound - voxel_size / 2``).  Output order
-    is by voxel index (Open3D's order is hash-map dependent; the set of points is what matters)."""
+    is by voxel index (Open3D's order is hash-map dependent; the set of points is what matters).
+    ``return_counts=True``: -> (centroids, counts) with the number of points each centroid stands for
+    (int64, summing to ``len(points)``) -- the weights that let a registration against the centroids
+    see the scan's density (``GMMTree.registration(centroids, weights=counts)``)."""
     P = np.asarray(points, dtype=np.float64)
     if voxel_size <= 0:
         raise ValueError("voxel_size must be positive")
@@ -171,4 +174,5 @@ def voxel_down_sample(points, voxel_size: float) -> np.ndarray:
     inv = inv.reshape(-1)
     out = np.zeros((len(cnt), 3))
     np.add.at(out, inv, P)
-    return out / cnt[:, None]
+    out = out / cnt[:, None]
+    return (out, cnt.astype(np.int64)) if return_counts else out

@@ -411,6 +411,31 @@ int hgmm_tree_register_multi(hgmm_ctx* ctx, int K, double* rot /* [K,9] */, doub
                              double* trace /* optional [K,max_iter,13] */);
 int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, const double* t /* [K,3] */, double scale,
                           double lambda_c, double maha2_max, double* summary_out /* [K,8] */);
+/* Per-point WEIGHTS of the registration target.  The reference has no counterpart: gmmTreeRegESTep
+ * (hgmm_cupy_cpu_working.py:202-228 == hgmm_gpu.py:550-577) counts every target point as one unit of evidence, although its
+ * own pipeline voxel-downsamples the scans first (run_gmm_static.py:28).  A target point i with weight w_i >= 0 adds
+ * w_i * gamma to a node's moments where it added gamma -- a voxel centroid with its count, a return weighted by range or
+ * incidence, the caller's own M-estimator weights (e.g. from hgmm_tree_score's maha2).  Everything else is what it was: the
+ * DESCENT, the stop rule and the Mahalanobis gate do not see the weight, the 1e-15 floor is tested on gamma (not on
+ * w_i gamma), the sums stay the deterministic fixed-point sums, whose encoding takes the sum of the weights (a float64 sum
+ * on the host, in index order; all-reduced under a communicator) where it took the number of points.  A zero weight adds
+ * nothing.  w == 1 everywhere gives the unweighted results bit for bit, w == 2 everywhere exactly twice the moments.
+ * The weights ATTACH TO THE RESIDENT TARGET: hgmm_tree_set_target (serial, multi-start) resp.
+ * hgmm_tree_set_targets_batch[_f32] (batch) first -- HGMM_ERR_STATE without one -- and uploading a new target drops them.
+ * w == NULL: no weights (the unweighted kernels run, every result what it was, bit for bit); in the batch w[b] == NULL leaves
+ * pair b unweighted (bitwise its unweighted results).  n resp. counts[b] must equal the resident counts; a NaN, infinite or
+ * negative weight (hgmm_last_error names its index) and a cloud whose weights are all zero are refused: HGMM_ERR_ARG, and
+ * the previous weights stay in force.
+ * Honoured by hgmm_tree_reg_estep, hgmm_tree_reg_normal, hgmm_tree_register, hgmm_tree_register_multi (the K hypotheses share
+ * the one array), hgmm_tree_register_batch -- with reg_device_solve, with a finite gate and under a communicator alike (each
+ * rank holds the weights of its shard) -- and by the summaries of hgmm_tree_score, hgmm_tree_score_batch and
+ * hgmm_tree_score_multi: summary[0] = sum of w, summary[1..6] = the w-weighted sums of what they are without weights, added in
+ * the same fixed order; the per-point arrays node / maha2 / logp are not weighted.  NOT honoured by the build (hgmm_tree_build*:
+ * weights of a SOURCE cloud are a different feature) nor by any flat, full-covariance or KMeans entry: they ignore them.     */
+int hgmm_tree_set_target_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
+int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
+                                       const double* const* w /* w == NULL: none; w[b] == NULL: pair b unweighted */,
+                                       const int64_t* counts);
 /* The steps buildGMMTree is made of, one at a time (reference function granularity).  Node tables
  * hold T nodes (any T >= 8, need not be a complete tree).
  * hgmm_tree_estep  <- gmmTreeEStep()       hgmm_cupy_cpu_working.py:162-191: parent_idx[N] arbitrary
