@@ -113,6 +113,7 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_get_reg_gate", [ctx, _f64p])
         _sig(lib, "hgmm_tree_set_target", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_set_target_weights", [ctx, _vp, C.c_int64])
+        _sig(lib, "hgmm_tree_set_source_weights", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_reg_estep", [ctx, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_reg_normal", [ctx, _vp, _vp, C.c_double, C.c_double, _vp])
         _sig(lib, "hgmm_tree_node_complexity", [ctx, _vp])
@@ -158,6 +159,7 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_set_targets_batch", [ctx, C.c_int, C.POINTER(_vp), _i64p])
         _sig(lib, "hgmm_tree_set_targets_batch_f32", [ctx, C.c_int, C.POINTER(_vp), _i64p])
         _sig(lib, "hgmm_tree_set_target_weights_batch", [ctx, C.c_int, C.POINTER(_vp), _i64p])
+        _sig(lib, "hgmm_tree_set_source_weights_batch", [ctx, C.c_int, C.POINTER(_vp), _i64p])
         _sig(lib, "hgmm_tree_register_batch", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
                                                _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_score", [ctx, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp])
@@ -1005,6 +1007,22 @@ class Context:
         self._check(self.lib.hgmm_tree_set_target_weights(self.h, _ptr(w), w.shape[0]))
         return self
 
+    def tree_set_source_weights(self, w):
+        """Per-point weights ``w`` [n] >= 0 of the resident cloud for :meth:`tree_build` (hgmm_tree_set_source_weights): point
+        i counts as ``w[i]`` points -- the moments are ``sum w gamma (1, x, x x^T)``, ``pi = m0 / sum(w)`` and a level's
+        log-likelihood is ``sum w log(...)``; the partition (arg-max) and the 1e-15 floor do not see them.  ``None``: no
+        weights.  They belong to the cloud :meth:`set_points` uploaded (or the bound handle): whatever changes the resident
+        cloud drops them.  Nothing but the build reads them.  The library refuses a wrong length, a NaN, infinite or negative
+        weight and all-zero weights (HgmmError, naming the index) and keeps the previous weights."""
+        if w is None:
+            self._check(self.lib.hgmm_tree_set_source_weights(self.h, None, 0))
+            return self
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim != 1:
+            raise ValueError("weights must be [N], got %s" % (w.shape,))
+        self._check(self.lib.hgmm_tree_set_source_weights(self.h, _ptr(w), w.shape[0]))
+        return self
+
     def tree_reg_estep(self, T, rot=None, t=None, scale=1.0, lambda_c=0.01):
         rot = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3, 3)
         t = None if t is None else np.ascontiguousarray(t, dtype=np.float64).reshape(3)
@@ -1058,15 +1076,39 @@ class Context:
         counts = (C.c_int64 * len(arrs))(*[a.shape[0] for a in arrs])
         return arrs, ptrs, counts, all32
 
-    def set_points_batch(self, clouds):
+    def set_points_batch(self, clouds, weights=None):
         """B clouds [N_b,3] become ONE resident cloud, cloud after cloud, each uploaded from its own array
-        (hgmm_set_points_batch_f64 / _f32).  -> the arrays that were uploaded (their lengths are the forest's counts)."""
+        (hgmm_set_points_batch_f64 / _f32).  -> the arrays that were uploaded (their lengths are the forest's counts).
+        ``weights`` (a list of B arrays [N_b] or None entries; default None: no weights): per-point weights of the clouds for
+        :meth:`tree_build_batch`, uploaded after them (:meth:`tree_set_source_weights_batch`)."""
         arrs, ptrs, counts, all32 = self._cloud_list(clouds, "set_points_batch")
         entry = self.lib.hgmm_set_points_batch_f32 if all32 else self.lib.hgmm_set_points_batch_f64
+        self._batch_counts = None
         self._check(entry(self.h, len(arrs), ptrs, counts))
         self.n = int(sum(a.shape[0] for a in arrs))
         self._batch_counts = [a.shape[0] for a in arrs]
+        if weights is not None:
+            self.tree_set_source_weights_batch(weights)
         return arrs
+
+    def tree_set_source_weights_batch(self, weights):
+        """Weights of the resident forest cloud's members for :meth:`tree_build_batch` (hgmm_tree_set_source_weights_batch): a
+        list of B arrays [N_b] or None entries (that cloud stays unweighted, bit for bit); ``None``: no weights at all.  As
+        :meth:`tree_set_source_weights`: a new resident cloud drops them, a refused upload keeps the previous ones."""
+        if weights is None:
+            self._check(self.lib.hgmm_tree_set_source_weights_batch(self.h, 0, None, None))
+            return self
+        ws = [None if w is None else np.ascontiguousarray(w, dtype=np.float64) for w in weights]
+        for w in ws:
+            if w is not None and w.ndim != 1:
+                raise ValueError("weights must be [N_b], got %s" % (w.shape,))
+        ptrs = (_vp * max(len(ws), 1))(*[None if w is None else w.ctypes.data for w in ws])
+        # (the library compares every count with the resident cloud's; a None entry names no count of its own)
+        resident = getattr(self, "_batch_counts", None) or []
+        counts = (C.c_int64 * max(len(ws), 1))(*[(resident[b] if b < len(resident) else 0) if w is None else w.shape[0]
+                                                 for b, w in enumerate(ws)])
+        self._check(self.lib.hgmm_tree_set_source_weights_batch(self.h, len(ws), ptrs, counts))
+        return self
 
     def tree_build_batch(self, counts, L, ls, ld, init_mu, sig2, max_iters_per_level=1000, want_tables=True,
                          want_trace=False, q_capacity=None):

@@ -743,7 +743,8 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->km_closest, &c->km_block, &c->km_centres, &c->km_ids, &c->km_rand, &c->km_labels,
                       &c->km_mind2, &c->km_partial, &c->km_out, &c->gt_buf, &c->t_momq, &c->t_flags, &c->exp_tab2, &c->t_tickets,
                       &c->fr_pi, &c->fr_mu, &c->fr_cov, &c->fr_prep, &c->fr_mom, &c->fr_clouds, &c->fr_q, &c->fr_trace, &c->fr_tg,
-                      &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w, &c->fr_tg_w};
+                      &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w, &c->fr_tg_w,
+                      &c->src_w, &c->fr_src_w, &c->t_w2, &c->t_w3};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -864,6 +865,9 @@ static void bind_points(hgmm_ctx* c, hgmm_points* p) {
     c->flat.active = false;
     c->tree.nodes_ready = false;
     c->km_labels_n = -1;              // labels / distances of the previous cloud are void
+    c->src_weighted = false;          // hgmm_tree_set_source_weights[_batch]: the weights belonged to the previous cloud
+    c->forest.src_weighted = false;
+    c->forest.src_counts.clear();
 }
 
 static int points_alloc(hgmm_ctx* c, hgmm_points* p, int64_t n) {
@@ -958,6 +962,7 @@ static int set_points_batch(hgmm_ctx* c, int B, const IN* const* xyz, const int6
     HGMM_HIP(c, ctx_stream_sync(c));
     bind_points(c, p);
     c->have_f32 = false;
+    c->forest.src_counts.assign(counts, counts + B);     // (hgmm_tree_set_source_weights_batch checks its counts against these)
     return HGMM_OK;
 }
 extern "C" int hgmm_set_points_batch_f64(hgmm_ctx* c, int B, const double* const* xyz, const int64_t* counts) {

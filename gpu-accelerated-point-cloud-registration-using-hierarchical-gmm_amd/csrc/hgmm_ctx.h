@@ -151,6 +151,9 @@ struct ForestState {
     bool momq_clean = false;              // every word of fr_momq is zero (tree_host.h: MomqScope)
     bool tg_weighted = false;             // hgmm_tree_set_target_weights_batch: fr_tg_w holds a weight per target point
     std::vector<double> tg_wsum;          // (tg_weighted) sum of the weights per target; an unweighted pair: its count
+    std::vector<int64_t> src_counts;      // hgmm_set_points_batch_*: the resident cloud's members (empty: not a batch cloud)
+    bool src_weighted = false;            // hgmm_tree_set_source_weights_batch: fr_src_w holds a weight per source point
+    std::vector<double> src_wsum;         // (src_weighted) sum of the weights per cloud; an unweighted cloud: its count
 };
 
 }  // namespace hgmm
@@ -183,6 +186,11 @@ struct hgmm_ctx {
     hgmm_points* bound = nullptr;     // nullptr: nothing resident yet
     bool have_f32 = false, have_f64 = false;
     int64_t n_pad = 0;
+    // per-point weights of the resident cloud (hgmm_tree_set_source_weights: the tree build alone reads them); whatever
+    // changes the resident cloud drops them (hgmm_api.hip: bind_points)
+    hgmm::DevBuf src_w;               // double [n_pad], parallel to x_soa64 (level-0 order)
+    bool src_weighted = false;        // src_w is in force
+    double src_wsum = 0.0;            // (src_weighted) sum of the weights, on the host in index order
 
     // ---- flat EM ----------------------------------------------------------------
     hgmm::FlatState flat;
@@ -221,6 +229,7 @@ struct hgmm_ctx {
     hgmm::DevBuf t_parent, t_current;         // int32 [n]
     hgmm::DevBuf t_perm;                      // int32 [n]  points sorted by parent
     hgmm::DevBuf t_xs3;                       // double [3][n_pad] third coordinate buffer (L > 2)
+    hgmm::DevBuf t_w2, t_w3;                  // double [n_pad] the source weights' ping-pong beside t_parent / t_xs3 (weighted builds only)
     hgmm::DevBuf t_seg;                       // int32 segment tables
     hgmm::DevBuf t_chunks;                    // int32 chunk descriptors
     hgmm::DevBuf t_partials;                  // double per-chunk partial moments
@@ -242,6 +251,7 @@ struct hgmm_ctx {
     hgmm::DevBuf fr_trace;                    // double [B][L][trace_cap]
     hgmm::DevBuf fr_tg;                       // double [3][tg_pad] the targets, back to back
     hgmm::DevBuf fr_tg_w;                     // double [tg_pad] their weights (forest.tg_weighted; 1.0 for an unweighted pair)
+    hgmm::DevBuf fr_src_w;                    // double [n_pad] the source clouds' weights (forest.src_weighted; 1.0 for an unweighted cloud)
     hgmm::DevBuf fr_momq;                     // uint64 [B T][4] registration sums
     hgmm::DevBuf ff_clocks;                   // int64 [8][4] phase clocks of the one-pass full-covariance kernels (armed: ff_clocks_on)
     bool ff_clocks_on = false;

@@ -46,10 +46,11 @@ __global__ void forest_prep_kernel(const double* __restrict__ pi, const double* 
 //  bunny scans went from 8.9 to 13.9 ms, 3650 -> 2740 pairs/s.  Eight widely spaced streams through the point arrays cost
 //  more than the scalar loads' ~800-cycle misses; the grid order stays.)
 // launch 0 of a level: the E-step of every chunk of every cloud
-template <bool HALF>
+// (WEIGHTED: hgmm_tree_set_source_weights_batch -- ea.w, the forest's weights in the order of ea.xs)
+template <bool HALF, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH, 7) void forest_estep_kernel(TreeEstepArgs ea, ForestArgs fa) {
     __shared__ double smem[tree_estep_lds<HALF>()];
-    tree_estep_body<HALF, true>((int)blockIdx.x, ea, NO_FOLLOW, smem, &fa);
+    tree_estep_body<HALF, true, WEIGHTED>((int)blockIdx.x, ea, NO_FOLLOW, smem, &fa);
 }
 
 // One wave per child node of the level, all clouds: tree_moments_kernel with the cloud's own stop flag, point count and --
@@ -122,7 +123,8 @@ __global__ __launch_bounds__(64) void forest_moments8_kernel(const double* __res
 //  scans -- the kernel keeps the fp64 pipe ~80 % busy at any of them, profiles/r06/pmc_sq_batch32.txt.  float32 pdfs: the
 //  launch is latency chains of E-step workgroups for the larger part -- six waves at 80 registers, still without spills)
 // F32: the log-likelihood workgroups evaluate their pdfs in float32 (hgmm_tree_set_precision; tree_loglik_f32_body)
-template <bool F32>
+// WEIGHTED: both halves read ea.w (the log-likelihood's points are the E-step's, in the same order)
+template <bool F32, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH, F32 ? 6 : 5) void forest_ll_estep_kernel(const double* __restrict__ xs, int64_t n_pad,
                                                              const double* __restrict__ prep, int64_t lb, int n_level,
                                                              double* __restrict__ block_q, const int* __restrict__ flags,
@@ -140,11 +142,11 @@ __global__ __launch_bounds__(CH, F32 ? 6 : 5) void forest_ll_estep_kernel(const 
         if (bx >= gx || stop_flag) return;
         const TreeLoglikArgs la{xs, (int64_t)pt_first + pt_count, n_pad, prep, (int64_t)b * fa.T + lb, n_level, per_chunk,
                                 nullptr, block_q + q_first, nullptr, nullptr, nullptr, NO_STOP, flags + b, nullptr, nullptr,
-                                (int64_t)pt_first, q_count};
-        if constexpr (F32) tree_loglik_f32_body<2, true>(bx, 0, gx, gy, la, smem);
-        else tree_loglik_body<2, false, true>(bx, 0, gx, gy, la, smem);
+                                (int64_t)pt_first, q_count, WEIGHTED ? ea.w : nullptr};
+        if constexpr (F32) tree_loglik_f32_body<2, true, WEIGHTED>(bx, 0, gx, gy, la, smem);
+        else tree_loglik_body<2, false, true, WEIGHTED>(bx, 0, gx, gy, la, smem);
     } else if (with_estep) {
-        tree_estep_body<true, true>(w - n_ll, ea, NO_FOLLOW, smem, &fa);
+        tree_estep_body<true, true, WEIGHTED>(w - n_ll, ea, NO_FOLLOW, smem, &fa);
     }
 }
 
@@ -185,12 +187,15 @@ __global__ __launch_bounds__(CH) void forest_hist_kernel(const int* __restrict__
         hist[c * 8 + threadIdx.x] = t;
     }
 }
+// (WEIGHTED: the weights travel with the coordinates, as in tree_scatter_kernel)
+template <bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void forest_scatter_kernel(const double* __restrict__ xs, int64_t n_pad,
                                                             const int* __restrict__ cur0, const int* __restrict__ cur1,
                                                             const int* __restrict__ chunk_desc,
                                                             const int* __restrict__ n_chunks,
                                                             const int* __restrict__ chunk_off, double* __restrict__ xs_new,
-                                                            ForestArgs fa) {
+                                                            ForestArgs fa, const double* __restrict__ wts = nullptr,
+                                                            double* __restrict__ wts_new = nullptr) {
     const int c = blockIdx.x;
     if (c >= *n_chunks) return;
     const int seg = chunk_desc[3 * c], begin = chunk_desc[3 * c + 1], end = chunk_desc[3 * c + 2];
@@ -216,6 +221,7 @@ __global__ __launch_bounds__(CH) void forest_scatter_kernel(const double* __rest
     xs_new[dst] = xs[i];
     xs_new[n_pad + dst] = xs[n_pad + i];
     xs_new[2 * n_pad + dst] = xs[2 * n_pad + i];
+    if constexpr (WEIGHTED) wts_new[dst] = wts[i];
 }
 
 // targets: [n,3] rows -> the forest's structure of arrays at `first`, and the largest |x|^2 of the cloud (the same
@@ -517,6 +523,10 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         if (sum != n) return fail(c, HGMM_ERR_ARG, "tree build (batch): the counts add up to %lld, the resident cloud has %lld points",
                                   (long long)sum, (long long)n);
     }
+    // hgmm_tree_set_source_weights_batch: the WEIGHTED instantiations, the weights on the coordinates' ping-pong
+    const bool weighted = c->forest.src_weighted;
+    if (weighted && (c->forest.src_counts.size() != (size_t)B || !std::equal(counts, counts + B, c->forest.src_counts.begin())))
+        return fail(c, HGMM_ERR_ARG, "tree build (batch): the resident source weights were set for other cloud sizes");
     const int64_t T = level_first(L);
     const int64_t TT = T * B;
     int64_t P8 = 1;
@@ -538,6 +548,7 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * 3 * TT));
     HGMM_TRY(ensure(c, c->t_current, sizeof(int) * 2 * n_pad));
     HGMM_TRY(ensure(c, c->t_parent, sizeof(double) * 3 * n_pad));
+    if (weighted) HGMM_TRY(ensure(c, c->t_w2, sizeof(double) * n_pad));
     HGMM_TRY(ensure(c, c->t_seg, sizeof(int) * (2 * (8 * maxP + 2) + 2 * (maxP + 2) + 8)));
     HGMM_TRY(ensure(c, c->t_chunks, sizeof(int) * (size_t)(3 + 8 + 8) * max_chunks));
     HGMM_TRY(ensure(c, c->t_partials, sizeof(double) * (size_t)8 * NMOM * max_chunks));
@@ -545,7 +556,11 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     if (L > 2) {
         HGMM_TRY(ensure(c, c->t_xs3, sizeof(double) * 3 * n_pad));
         xs_c = c->t_xs3.as<double>();
+        if (weighted) HGMM_TRY(ensure(c, c->t_w3, sizeof(double) * n_pad));
     }
+    double* w_b = weighted ? c->t_w2.as<double>() : nullptr;
+    double* w_c = (weighted && L > 2) ? c->t_w3.as<double>() : nullptr;
+    const double* w_cur = weighted ? c->fr_src_w.as<double>() : nullptr;
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, B, &hand));
     unsigned long long* const words = hand->progress(0).host;
@@ -611,7 +626,7 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
             // (level 0: the E-step stores the shares, one per chunk -- a cloud's chunks are consecutive, TreeEstepArgs::q_shares)
             fc.q_count = (l == 0 || chunks > 1) ? (int)nblk(counts[b], CH) : llblocks;
             q_at += fc.q_count;
-            fc.n_total = (double)counts[b];
+            fc.n_total = weighted ? c->forest.src_wsum[b] : (double)counts[b];     // (an unweighted member: its count)
             ll_stride = std::max(ll_stride, llblocks);
         }
         if (l == 0) ll_stride = 0;                              // no log-likelihood workgroups at level 0
@@ -623,10 +638,11 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         for (int b = 0; b < B; ++b) __atomic_store_n(words + b, 0ull, __ATOMIC_RELAXED);
         auto enqueue_iteration = [&](int e) -> int {
             const TreeEstepArgs ea_now{xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l, partials,
-                                       (e & 1) ? cur1 : cur0, nullptr};
+                                       (e & 1) ? cur1 : cur0, nullptr, nullptr, w_cur};
+            const auto estep = weighted ? forest_estep_kernel<true, true> : forest_estep_kernel<true, false>;
             if (e == 0) {
                 ProfScope prof(c, HGMM_K_TREE_ESTEP);
-                forest_estep_kernel<true><<<grid_chunks, CH, 0, c->stream>>>(ea_now, fa);
+                estep<<<grid_chunks, CH, 0, c->stream>>>(ea_now, fa);
             }
             if (l > 0)
                 forest_moments8_kernel<<<(unsigned)(B * n_level / 8), 64, 0, c->stream>>>(partials, chunk_first, n_level, d_mom, lb, ld,
@@ -639,18 +655,18 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
                 // (level 0: behind the budget's last iteration the E-step runs for the shares of q alone)
                 const int with_estep = (e + 1 < max_iters_per_level || l == 0) ? 1 : 0;
                 const TreeEstepArgs ea_next{xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l, partials,
-                                            ((e + 1) & 1) ? cur1 : cur0, nullptr, l == 0 ? block_q : nullptr};
+                                            ((e + 1) & 1) ? cur1 : cur0, nullptr, l == 0 ? block_q : nullptr, w_cur};
                 const unsigned g = (unsigned)(B * ll_stride) + (with_estep ? grid_chunks : 0u);
                 if (l == 0)
                     // (level 0 is E-step workgroups only: the plain E-step kernel -- 72 registers instead of the fused kernel's
                     //  92-96, one more wave per SIMD for a launch that is a chain of trips to memory)
-                    forest_estep_kernel<true><<<grid_chunks, CH, 0, c->stream>>>(ea_next, fa);
-                else if (c->tree.pdf_f32)
-                    forest_ll_estep_kernel<true><<<g, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, lb, n_level, block_q, d_flags,
-                                                                         fa, ll_stride, ea_next, with_estep);
-                else
-                    forest_ll_estep_kernel<false><<<g, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, lb, n_level, block_q, d_flags,
-                                                                          fa, ll_stride, ea_next, with_estep);
+                    estep<<<grid_chunks, CH, 0, c->stream>>>(ea_next, fa);
+                else {
+                    const auto fused = weighted ? (c->tree.pdf_f32 ? forest_ll_estep_kernel<true, true> : forest_ll_estep_kernel<false, true>)
+                                                : (c->tree.pdf_f32 ? forest_ll_estep_kernel<true, false> : forest_ll_estep_kernel<false, false>);
+                    fused<<<g, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, lb, n_level, block_q, d_flags, fa, ll_stride, ea_next,
+                                                   with_estep);
+                }
             }
             const hipError_t le = hipGetLastError();
             if (le != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build (batch): kernel launch failed: %s", hipGetErrorString(le));
@@ -683,10 +699,13 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
             int* seg_next = (seg_cur == seg_a) ? seg_b : seg_a;
             tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(hist, chunk_first, seg_cur, P, chunk_off, seg_next);
             double* xs_next = (xs_cur == xs_b) ? xs_c : xs_b;   // A -> B -> C -> B -> ... (the resident cloud is never overwritten)
-            forest_scatter_kernel<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, cur0, cur1, chunk_desc, n_chunks_dev, chunk_off,
-                                                                    xs_next, fa);
+            double* w_next = (xs_next == xs_b) ? w_b : w_c;     // (the weights' buffers pair up with the coordinates')
+            const auto scatter = weighted ? forest_scatter_kernel<true> : forest_scatter_kernel<false>;
+            scatter<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, cur0, cur1, chunk_desc, n_chunks_dev, chunk_off, xs_next, fa,
+                                                       w_cur, w_next);
             if (hipGetLastError() != hipSuccess) { rc = fail(c, HGMM_ERR_HIP, "tree build (batch): partition launch failed"); break; }
             xs_cur = xs_next;
+            w_cur = weighted ? w_next : nullptr;
             seg_cur = seg_next;
             P *= 8;
         }
@@ -848,6 +867,49 @@ extern "C" int hgmm_tree_set_target_weights_batch(hgmm_ctx* c, int B, const doub
     HGMM_HIP(c, ctx_stream_sync(c));
     F.tg_wsum = sums;
     F.tg_weighted = true;
+    return HGMM_OK;
+}
+
+// per-point weights of the resident forest cloud (include/hgmm.h): fr_src_w [n_pad] parallel to x_soa64; an unweighted cloud of
+// a weighted batch gets 1.0 per point and its count as the sum, so that it keeps its unweighted bits
+extern "C" int hgmm_tree_set_source_weights_batch(hgmm_ctx* c, int B, const double* const* w, const int64_t* counts) {
+    HGMM_ENTER(c);
+    const char* what = "hgmm_tree_set_source_weights_batch";
+    ForestState& F = c->forest;
+    if (!c->have_f64 || c->n <= 0 || F.src_counts.empty())
+        return fail(c, HGMM_ERR_STATE, "%s: no forest cloud (call hgmm_set_points_batch_f64 / _f32 first)", what);
+    if (!w) { F.src_weighted = false; return HGMM_OK; }
+    if (B != (int)F.src_counts.size())
+        return fail(c, HGMM_ERR_ARG, "%s: B = %d, but %d clouds are resident", what, B, (int)F.src_counts.size());
+    if (!counts) return fail(c, HGMM_ERR_ARG, "%s: counts is NULL", what);
+    std::vector<double> sums(B), padded((size_t)c->n_pad, 0.0);
+    bool any = false;
+    int64_t at = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] != F.src_counts[b])
+            return fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident cloud %d has %lld points", what, b,
+                        (long long)counts[b], b, (long long)F.src_counts[b]);
+        double* dst = padded.data() + at;
+        at += counts[b];
+        if (!w[b]) {
+            std::fill(dst, dst + counts[b], 1.0);
+            sums[b] = (double)counts[b];
+            continue;
+        }
+        char label[96];
+        snprintf(label, sizeof label, "%s (cloud %d)", what, b);
+        HGMM_TRY(check_target_weights(c, label, w[b], counts[b], &sums[b]));
+        std::copy(w[b], w[b] + counts[b], dst);
+        any = true;
+    }
+    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
+    F.src_weighted = false;
+    if (!any) return HGMM_OK;
+    HGMM_TRY(ensure(c, c->fr_src_w, sizeof(double) * padded.size()));
+    HGMM_HIP(c, hipMemcpyAsync(c->fr_src_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    F.src_wsum = sums;
+    F.src_weighted = true;
     return HGMM_OK;
 }
 

@@ -271,6 +271,15 @@ __device__ __forceinline__ double log_pos_f64(double x) {
     return dk * LN2_HI - ((hfsq - (s * (hfsq + R) + dk * LN2_LO)) - f);
 }
 
+// w * l for a point's weighted logarithm (hgmm_tree_set_source_weights), rounded on its own.  The product is followed by a sum
+// (over the thread's points, over the wave), and whether the compiler contracts product and first addition into one fma is its
+// choice per kernel: the serial build and the forest take the logarithm in different kernels and must agree bit for bit.
+__device__ __forceinline__ double weighted_log(double w, double l) {
+    double r;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(w), "v"(l));
+    return r;
+}
+
 // ------------------------------------------------------------------------------------------
 // per-node preparation
 // ------------------------------------------------------------------------------------------
@@ -470,6 +479,9 @@ struct TreeEstepArgs {
     // is a sum over the very eight terms iteration e + 1's E-step forms from the same parameters.  With q_shares set the
     // E-step stores its chunk's share of it (chunk c -> q_shares[c]) and no log-likelihood workgroup runs for the level.
     double* q_shares = nullptr;
+    // WEIGHTED instantiations (hgmm_tree_set_source_weights): w [n_pad], the points' weights in the order of `xs` -- the
+    // partition carries them along with the coordinates; the unweighted instantiations never read the pointer
+    const double* w = nullptr;
 };
 // A FOREST (tree_batch.hip): B independent clouds whose points lie back to back in one resident cloud and whose trees are
 // built by the same launches.  At level l the forest has B 8^l parent segments; segment p belongs to cloud p >> 3 l and is
@@ -505,7 +517,9 @@ __device__ __forceinline__ TreeFollow forest_follow(const ForestArgs& fa, int b,
 //  fragment reads have landed in registers -- 20.6 KB per workgroup in the two-pass form, seven workgroups per CU)
 template <bool HALF>
 constexpr int tree_estep_lds() { return EXP_TAB_N + 4 + (CH / 64) * (8 + NMOM) * (HALF ? ES_LD / 2 + 1 : ES_LD); }
-template <bool HALF, bool FOREST = false>
+// WEIGHTED (hgmm_tree_set_source_weights): point i counts as w_i points -- the moments are sum w gamma (1, x, x x^T) and the
+// level-0 share of q is sum w log(...).  The floor is tested on gamma and the arg-max is taken before the weight comes in.
+template <bool HALF, bool FOREST = false, bool WEIGHTED = false>
 __device__ __forceinline__ void tree_estep_body(const int c, const TreeEstepArgs& a, const TreeFollow& follow,
                                                 double* __restrict__ smem, const ForestArgs* fa = nullptr) {
     const double* __restrict__ xs = a.xs;
@@ -530,6 +544,7 @@ __device__ __forceinline__ void tree_estep_body(const int c, const TreeEstepArgs
     const int i = begin + (int)threadIdx.x;
     const bool active = i < end;
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
+    [[maybe_unused]] double wt = 0.0;              // (WEIGHTED) this point's weight: requested with its coordinates
     int pl = p;                                    // the parent's index within its cloud's level
     int64_t node_off = 0;                          // first node of the cloud's tree
     if constexpr (FOREST) {
@@ -539,6 +554,7 @@ __device__ __forceinline__ void tree_estep_body(const int c, const TreeEstepArgs
         node_off = (int64_t)b * fa->T;
         stop_flag = fa->clouds[b].done;
         if (active) { x0 = xs[i]; x1 = xs[n_pad + i]; x2 = xs[2 * n_pad + i]; }
+        if constexpr (WEIGHTED) { if (active) wt = a.w[i]; }
         if (stop_flag) return;                     // (a forest's E-steps never follow: launch e = 0 and the speculative ones)
     } else {
         if (follow.q_blocks) {
@@ -556,6 +572,15 @@ __device__ __forceinline__ void tree_estep_body(const int c, const TreeEstepArgs
     const int64_t j0 = node_off + 8 * (parent_node + 1);
     if constexpr (!FOREST) {
         if (active) { x0 = xs[i]; x1 = xs[n_pad + i]; x2 = xs[2 * n_pad + i]; }
+        if constexpr (WEIGHTED) { if (active) wt = a.w[i]; }
+    }
+    // (WEIGHTED) The weight is wanted behind the exponentials only, and this kernel has no register to spare across them
+    // (the forest's 72 would spill, the fused kernel's 128 would lose a wave per SIMD): it waits in the first row of the wave's
+    // own gamma block, which nobody touches before the contraction -- one 8-byte LDS store and load per point, same lane.
+    [[maybe_unused]] double* wpark = nullptr;
+    if constexpr (WEIGHTED) {
+        wpark = smem + EXP_TAB_N + 4 + wave_in_block() * (8 * (HALF ? ES_LD / 2 + 1 : ES_LD)) + lane_id();
+        *wpark = wt;
     }
     __syncthreads();                               // exp_tab
 
@@ -585,12 +610,15 @@ __device__ __forceinline__ void tree_estep_body(const int c, const TreeEstepArgs
             den += g[k];
         }
     }
+    if constexpr (WEIGHTED) wt = *wpark;
     if (a.q_shares) {                                  // (kernel-uniform)
         // wL = wE, or 0 where pi < eps (prep_node): the log-likelihood leaves those nodes out, the E-step does not
         double den_l = 0.0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) den_l += (prep[PREP_N * (j0 + k) + 10] == 0.0) ? 0.0 : g[k];
-        const double lq = wave_sum_f64(active ? log_pos_f64(fmax(den_l, TREE_EPS)) : 0.0);
+        double lq1 = active ? log_pos_f64(fmax(den_l, TREE_EPS)) : 0.0;
+        if constexpr (WEIGHTED) lq1 = weighted_log(wt, lq1);   // (the clamp keeps the logarithm finite: a zero weight is an absent point)
+        const double lq = wave_sum_f64(lq1);
         if (lane_id() == 0) sh_follow[wave_in_block()] = lq;      // (read behind the barrier in front of the partials)
     }
     // gamma = g / den if den > eps else 0; arg-max = first maximum  (C:174-187)
@@ -605,6 +633,7 @@ __device__ __forceinline__ void tree_estep_body(const int c, const TreeEstepArgs
         g[k] = g[k] * inv_den;
         if (g[k] > best) { best = g[k]; am = k; }
         if (g[k] < TREE_EPS || !active) g[k] = 0.0;      // accumulate() ignores gamma < eps (C:100)
+        if constexpr (WEIGHTED) g[k] *= wt;              // (behind the floor and the arg-max: neither sees the weight)
     }
     if (active) cur_sorted[i] = (int)(j0 + am);
 
@@ -803,6 +832,7 @@ struct TreeLoglikArgs {
     double* partial; double* block_q; unsigned int* ticket; double* q_out; const int* done; TreeStop stop;
     const int* flags; unsigned long long* pair_count; const double* exp2_tab;
     int64_t i_base = 0; int q_count = 0;     // forest: the cloud's first point (n = one past its last), its number of q shares
+    const double* w = nullptr;               // WEIGHTED instantiations: the points' weights [n_pad] in the order of `xs`
 };
 // (bx, by) of a (gx, gy) grid: blockIdx / gridDim in tree_loglik_kernel, a slice of a 1-d grid in tree_ll_estep_kernel
 // LDS of one log-likelihood workgroup, in doubles: node tile, exp table, the waves' q / boxes / lref, the waves' counts (ints)
@@ -812,7 +842,10 @@ constexpr int tree_loglik_lds() { return LL_TILE * 10 + (BIGTAB ? EXP_TAB2_N : E
 // sums in chunk order, then forms the shares of q the serial build's finish kernel would (one per 256 points) -- the serial
 // sums in the serial order, without the serial form's [chunk][point] round trip (a forest fills the chip without
 // splitting the nodes); a node's parameters are requested only once its weight has turned out non-zero.
-template <int PTS, bool BIGTAB, bool FOREST = false>
+// WEIGHTED (hgmm_tree_set_source_weights): a point's logarithm enters q w_i times -- lq = w_i log max(sum, eps); the sums over
+// the nodes do not see the weight (and the [chunk][point] partial sums of the split form are unweighted: the finish kernel
+// applies it).
+template <int PTS, bool BIGTAB, bool FOREST = false, bool WEIGHTED = false>
 __device__ __forceinline__ void tree_loglik_body(const int bx, const int by, const int gx, const int gy,
                                                  const TreeLoglikArgs& a, double* __restrict__ smem) {
     const double* __restrict__ xs = a.xs;
@@ -1066,6 +1099,19 @@ __device__ __forceinline__ void tree_loglik_body(const int bx, const int by, con
         }
     }
     }
+    // (WEIGHTED) The weights are requested here, behind the tile loops: PTS doubles held across them cost the four-point
+    // instantiation a wave per SIMD (146 registers against 123).  The split form leaves them to its finish kernel.
+    // (addressed from the workgroup's uniform base with the thread's 32-bit offset: the 64-bit indices need not outlive the loops)
+    [[maybe_unused]] double wt[PTS];
+    if constexpr (WEIGHTED) {
+        const double* __restrict__ wb = a.w + i_first;
+        const int64_t left = n - i_first;
+#pragma unroll
+        for (int p = 0; p < PTS; ++p) {
+            const unsigned off = (unsigned)p * CH + threadIdx.x;
+            wt[p] = ((int64_t)off < left && (FOREST || gy == 1)) ? wb[off] : 0.0;
+        }
+    }
     if constexpr (FOREST) {
         if (gy > 1) {
             // the serial build's tree_loglik_finish_kernel: one share per 256 points = per p of this workgroup
@@ -1073,6 +1119,7 @@ __device__ __forceinline__ void tree_loglik_body(const int bx, const int by, con
 #pragma unroll
             for (int p = 0; p < PTS; ++p) {
                 double lq = active[p] ? log(fmax(totsum[p], TREE_EPS)) : 0.0;
+                if constexpr (WEIGHTED) lq = weighted_log(wt[p], lq);
                 lq = wave_sum_f64(lq);
                 if (p > 0) __syncthreads();                // the previous share has been summed
                 if (lane_id() == 0) shq[wave_in_block()] = lq;
@@ -1098,7 +1145,11 @@ __device__ __forceinline__ void tree_loglik_body(const int bx, const int by, con
     }
     double lq = 0.0;
 #pragma unroll
-    for (int p = 0; p < PTS; ++p) lq += active[p] ? log(fmax(tot[p], TREE_EPS)) : 0.0;
+    for (int p = 0; p < PTS; ++p) {
+        double l1 = active[p] ? log(fmax(tot[p], TREE_EPS)) : 0.0;
+        if constexpr (WEIGHTED) l1 = weighted_log(wt[p], l1);
+        lq += l1;
+    }
     lq = wave_sum_f64(lq);
     __syncthreads();                                       // (shq is not aliased, but keep the tile loop's last readers behind)
     if (lane_id() == 0) shq[wave_in_block()] = lq;
@@ -1154,7 +1205,7 @@ constexpr int tree_loglik_f32_lds() { return LL_TILE * 3 * 2 + (CH / 64) * (1 + 
 // PTS = 4 (clouds of >= 400 000 points) or 2 (small clouds); FOREST as in tree_loglik_body: the workgroup takes ALL node
 // chunks of its point block one after the other and forms the serial build's shares of q (the chunk sums -- float32 sums
 // widened to float64, exactly what the serial form parks in `partial` -- added in chunk order).
-template <int PTS, bool FOREST>
+template <int PTS, bool FOREST, bool WEIGHTED = false>
 __device__ __forceinline__ void tree_loglik_f32_body(const int bx, const int by, const int gx, const int gy,
                                                      const TreeLoglikArgs& a, double* __restrict__ smem) {
     static_assert(PTS == 2 || PTS == 4, "points go through the packed instructions two at a time");
@@ -1341,6 +1392,16 @@ __device__ __forceinline__ void tree_loglik_f32_body(const int bx, const int by,
         }
     }
     }
+    [[maybe_unused]] double wt[PTS];                       // (WEIGHTED: requested behind the tile loops, as in tree_loglik_body)
+    if constexpr (WEIGHTED) {
+        const double* __restrict__ wb = a.w + i_first;
+        const int64_t left = n - i_first;
+#pragma unroll
+        for (int p = 0; p < PTS; ++p) {
+            const unsigned off = (unsigned)p * CH + threadIdx.x;
+            wt[p] = ((int64_t)off < left && (FOREST || gy == 1)) ? wb[off] : 0.0;
+        }
+    }
     if constexpr (FOREST) {
         if (gy > 1) {
             // the serial build's tree_loglik_finish_kernel: one share per 256 points = per p of this workgroup
@@ -1348,6 +1409,7 @@ __device__ __forceinline__ void tree_loglik_f32_body(const int bx, const int by,
 #pragma unroll
             for (int p = 0; p < PTS; ++p) {
                 double lq = active[p] ? log_pos_f64(fmax(totsum[p], TREE_EPS)) : 0.0;
+                if constexpr (WEIGHTED) lq = weighted_log(wt[p], lq);
                 lq = wave_sum_f64(lq);
                 if (p > 0) __syncthreads();                // the previous share has been summed
                 if (lane_id() == 0) shq[wave_in_block()] = lq;
@@ -1376,7 +1438,11 @@ __device__ __forceinline__ void tree_loglik_f32_body(const int bx, const int by,
     }
     double lq = 0.0;
 #pragma unroll
-    for (int p = 0; p < PTS; ++p) lq += active[p] ? log_pos_f64(fmax((double)tot[p], TREE_EPS)) : 0.0;
+    for (int p = 0; p < PTS; ++p) {
+        double l1 = active[p] ? log_pos_f64(fmax((double)tot[p], TREE_EPS)) : 0.0;
+        if constexpr (WEIGHTED) l1 = weighted_log(wt[p], l1);
+        lq += l1;
+    }
     lq = wave_sum_f64(lq);
     __syncthreads();
     if (lane_id() == 0) shq[wave_in_block()] = lq;

@@ -146,7 +146,8 @@ inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, double tg_rmax, do
     pr.tg_rmax = tg_rmax;
     pr.mu_rmax = mu_rmax;
 }
-// (tree_kernels.hip) one cloud's weights for hgmm_tree_set_target_weights[_batch]: finite, >= 0, not all zero; their sum
+// (tree_kernels.hip) one cloud's weights for hgmm_tree_set_target_weights[_batch] and hgmm_tree_set_source_weights[_batch]:
+// finite, >= 0, not all zero; their sum
 int check_target_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out);
 // largest |mu_j| of the resident tree; a tree built on the device has not shown its means to the host yet
 inline int tree_mu_rmax_resident(hgmm_ctx* c) {

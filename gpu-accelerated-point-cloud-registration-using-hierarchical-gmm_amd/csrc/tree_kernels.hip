@@ -122,16 +122,20 @@ __global__ __launch_bounds__(CH) void tree_close_kernel(TreeFollow f) {
     (void)tree_follow(f, *f.done, sh4, true);
 }
 
-template <bool HALF>
+// (WEIGHTED: hgmm_tree_set_source_weights' array w [n_pad] in the order of xs; the unweighted instantiations do not read it)
+template <bool HALF, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_estep_kernel(
     const double* __restrict__ xs, int64_t n_pad, const double* __restrict__ prep,
     const int* __restrict__ chunk_desc, const int* __restrict__ n_chunks, int64_t parent_level_first,
     int level, double* __restrict__ partials, int* __restrict__ cur_sorted, const int* __restrict__ done,
-    TreeFollow follow = TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr}) {
+    TreeFollow follow = TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr},
+    const double* __restrict__ w = nullptr) {
     __shared__ double smem[tree_estep_lds<HALF>()];
-    tree_estep_body<HALF>((int)blockIdx.x,
-                          TreeEstepArgs{xs, n_pad, prep, chunk_desc, n_chunks, parent_level_first, level, partials, cur_sorted, done},
-                          follow, smem);
+    tree_estep_body<HALF, false, WEIGHTED>(
+        (int)blockIdx.x,
+        TreeEstepArgs{xs, n_pad, prep, chunk_desc, n_chunks, parent_level_first, level, partials, cur_sorted, done, nullptr,
+                      WEIGHTED ? w : nullptr},
+        follow, smem);
 }
 
 
@@ -202,7 +206,7 @@ __global__ void tree_mstep_kernel(const double* __restrict__ mom, int64_t lb, in
     mstep_node(mom + (size_t)cl * NMOM, lb + cl, n_points_total, ld, pi, mu, cov, prep, flags, with_complexity != 0);
 }
 
-template <int PTS, bool BIGTAB = false>
+template <int PTS, bool BIGTAB = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_loglik_kernel(const double* __restrict__ xs, int64_t n,
                                                          int64_t n_pad, const double* __restrict__ prep,
                                                          int64_t lb, int n_level_nodes, int nodes_per_chunk,
@@ -213,18 +217,20 @@ __global__ __launch_bounds__(CH) void tree_loglik_kernel(const double* __restric
                                                          const int* __restrict__ done, TreeStop stop,
                                                          const int* __restrict__ flags,
                                                          unsigned long long* __restrict__ pair_count,
-                                                         const double* __restrict__ exp2_tab = nullptr) {
+                                                         const double* __restrict__ exp2_tab = nullptr,
+                                                         const double* __restrict__ w = nullptr) {
     __shared__ double smem[tree_loglik_lds<BIGTAB>()];
-    tree_loglik_body<PTS, BIGTAB>((int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y,
-                                  TreeLoglikArgs{xs, n, n_pad, prep, lb, n_level_nodes, nodes_per_chunk, partial, block_q, ticket,
-                                                 q_out, done, stop, flags, pair_count, exp2_tab}, smem);
+    tree_loglik_body<PTS, BIGTAB, false, WEIGHTED>(
+        (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y,
+        TreeLoglikArgs{xs, n, n_pad, prep, lb, n_level_nodes, nodes_per_chunk, partial, block_q, ticket, q_out, done, stop, flags,
+                       pair_count, exp2_tab, 0, 0, WEIGHTED ? w : nullptr}, smem);
 }
 
 // (tree_loglik_f32_body, csrc/tree_device.h: the level log-likelihood with the pdfs in FLOAT32)
-template <int PTS>
+template <int PTS, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_loglik_f32_kernel(TreeLoglikArgs a) {
     __shared__ __attribute__((aligned(16))) double smem[tree_loglik_f32_lds()];
-    tree_loglik_f32_body<PTS, false>((int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y, a, smem);
+    tree_loglik_f32_body<PTS, false, WEIGHTED>((int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y, a, smem);
 }
 
 // One launch for two independent pieces of work on the same parameters (small clouds, single GPU): the level
@@ -236,7 +242,8 @@ __global__ __launch_bounds__(CH) void tree_loglik_f32_kernel(TreeLoglikArgs a) {
 // What it buys: the E-step's chain of trips to memory (5 - 6 us at C4) runs beside the log-likelihood's instead of
 // behind it, and a level-iteration is two or three launches instead of three or four.
 // F32: the log-likelihood workgroups evaluate their pdfs in float32 (hgmm_tree_set_precision; tree_loglik_f32_body)
-template <int PTS, bool F32 = false>
+// WEIGHTED: both halves read the weights (la.w == ea.w: the same cloud in the same order)
+template <int PTS, bool F32 = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_ll_estep_kernel(TreeLoglikArgs la, int gx, int gy, TreeEstepArgs ea) {
     // (one LDS block for whichever of the two a workgroup turns out to be; the E-step in its two-pass form -- the same
     //  sums bit for bit -- so that both need ~23 KB and the launch's workgroups are all resident at once)
@@ -246,29 +253,34 @@ __global__ __launch_bounds__(CH) void tree_ll_estep_kernel(TreeLoglikArgs la, in
     const int nll = gx * gy;
     const int b = (int)blockIdx.x;
     if (b < nll) {
-        if constexpr (F32) tree_loglik_f32_body<PTS, false>(b % gx, b / gx, gx, gy, la, smem);
-        else tree_loglik_body<PTS, false>(b % gx, b / gx, gx, gy, la, smem);
+        if constexpr (F32) tree_loglik_f32_body<PTS, false, WEIGHTED>(b % gx, b / gx, gx, gy, la, smem);
+        else tree_loglik_body<PTS, false, false, WEIGHTED>(b % gx, b / gx, gx, gy, la, smem);
     } else
-        tree_estep_body<true>(b - nll, ea, TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr}, smem);
+        tree_estep_body<true, false, WEIGHTED>(b - nll, ea, TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr}, smem);
 }
 
 
 // FASTLOG: the float32-pdf mode's logarithm (log_pos_f64, as in tree_loglik_f32_body's own finish for forests)
-template <bool FASTLOG = false>
+// WEIGHTED: lq = w_i log(...) -- the split form's partial sums are unweighted (tree_loglik_body)
+template <bool FASTLOG = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_loglik_finish_kernel(const double* __restrict__ partial, int64_t n,
                                                                 int64_t n_pad, int n_chunks,
                                                                 double* __restrict__ block_q,
                                                                 unsigned int* __restrict__ ticket,
                                                                 double* __restrict__ q_out,
-                                                                const int* __restrict__ done, TreeStop stop) {
+                                                                const int* __restrict__ done, TreeStop stop,
+                                                                const double* __restrict__ wts = nullptr) {
     if (done && *done) return;
     __shared__ double shq[CH / 64];
     const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
     double lq = 0.0;
     if (i < n) {
+        [[maybe_unused]] double wt = 0.0;
+        if constexpr (WEIGHTED) wt = wts[i];                 // (requested with the partial sums)
         double tot = 0.0;
         for (int c = 0; c < n_chunks; ++c) tot += partial[(size_t)c * n_pad + i];
         lq = FASTLOG ? log_pos_f64(fmax(tot, TREE_EPS)) : log(fmax(tot, TREE_EPS));
+        if constexpr (WEIGHTED) lq = weighted_log(wt, lq);
     }
     lq = wave_sum_f64(lq);
     if (lane_id() == 0) shq[wave_in_block()] = lq;
@@ -402,11 +414,13 @@ __global__ __launch_bounds__(OFF_BLOCK) void tree_offsets_kernel(const int* __re
 }
 
 // stable scatter of coordinates / permutation / (as the new parent) child index
+// (WEIGHTED: the points' weights travel with their coordinates, wts_new[dst] = wts[i]; the unweighted instantiation reads neither)
+template <bool WEIGHTED = false>
 __global__ __launch_bounds__(CH) void tree_scatter_kernel(
     const double* __restrict__ xs, int64_t n_pad, const int* __restrict__ perm,
     const int* __restrict__ cur_sorted, const int* __restrict__ chunk_desc,
     const int* __restrict__ n_chunks, const int* __restrict__ chunk_off, double* __restrict__ xs_new,
-    int* __restrict__ perm_new) {
+    int* __restrict__ perm_new, const double* __restrict__ wts = nullptr, double* __restrict__ wts_new = nullptr) {
     const int c = blockIdx.x;
     if (c >= *n_chunks) return;
     const int begin = chunk_desc[3 * c + 1], end = chunk_desc[3 * c + 2];
@@ -431,6 +445,7 @@ __global__ __launch_bounds__(CH) void tree_scatter_kernel(
     xs_new[n_pad + dst] = xs[n_pad + i];
     xs_new[2 * n_pad + dst] = xs[2 * n_pad + i];
     perm_new[dst] = perm[i];
+    if constexpr (WEIGHTED) wts_new[dst] = wts[i];
 }
 
 __global__ void tree_iota_kernel(int* perm, int64_t n) {
@@ -606,7 +621,7 @@ int ensure_exp_tab2(hgmm_ctx* c) {
 template <class K>
 static void ll_positional(K kernel, dim3 grid, hipStream_t stream, const TreeLoglikArgs& a, const double* exp2_tab) {
     kernel<<<grid, CH, 0, stream>>>(a.xs, a.n, a.n_pad, a.prep, a.lb, a.n_level_nodes, a.nodes_per_chunk, a.partial, a.block_q,
-                                    a.ticket, a.q_out, a.done, a.stop, a.flags, a.pair_count, exp2_tab);
+                                    a.ticket, a.q_out, a.done, a.stop, a.flags, a.pair_count, exp2_tab, a.w);
 }
 
 static int tree_prep(hgmm_ctx* c, int64_t jb, int64_t je) {
@@ -630,6 +645,11 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     if (L < 1 || L > 6) return fail(c, HGMM_ERR_ARG, "tree levels L = %d outside 1..6", L);
     if (!init_mu) return fail(c, HGMM_ERR_ARG, "init_mu is NULL");
     if (c->n > 0x7fffffff - 1024) return fail(c, HGMM_ERR_ARG, "too many points for 32-bit indices");
+    // hgmm_tree_set_source_weights: the WEIGHTED instantiations of the level's kernels, the weights on the coordinates' ping-pong
+    const bool weighted = c->src_weighted;
+    if (weighted && c->comm_on())
+        return fail(c, HGMM_ERR_STATE, "tree build: source weights are resident and the context has a communicator; sharded "
+                    "weighted builds are not supported (hgmm_tree_set_source_weights(ctx, NULL, 0) takes the weights off)");
     if (max_iters_per_level < 1) max_iters_per_level = 1;
     HGMM_HIP(c, hipSetDevice(c->device));
     HGMM_TRY(tree_alloc_nodes(c, L));
@@ -643,6 +663,7 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     HGMM_TRY(ensure(c, c->t_current, sizeof(int) * 2 * n_pad));              // two assignments (tree_ll_estep_kernel)
     HGMM_TRY(ensure(c, c->t_perm, sizeof(int) * 2 * n_pad));                 // ping-pong
     HGMM_TRY(ensure(c, c->t_parent, sizeof(double) * 3 * n_pad));            // second coordinate buffer
+    if (weighted) HGMM_TRY(ensure(c, c->t_w2, sizeof(double) * n_pad));       // ... and the weights' beside it
     HGMM_TRY(ensure(c, c->t_seg, sizeof(int) * (2 * (8 * maxP + 2) + 2 * (maxP + 2) + 8)));
     HGMM_TRY(ensure(c, c->t_chunks, sizeof(int) * (size_t)(3 + 8 + 8) * max_chunks));
     HGMM_TRY(ensure(c, c->t_partials, sizeof(double) * (size_t)8 * NMOM * max_chunks));
@@ -726,8 +747,8 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     HGMM_HIP(c, hipMemcpyAsync(seg_a, seg0, sizeof seg0, hipMemcpyHostToDevice, c->stream));
     HGMM_HIP(c, hipGetLastError());
 
-    // global point count (pi = m0 / N_total)
-    double n_total = (double)n;
+    // global point count (pi = m0 / N_total); with weights their sum: point i counts as w_i points
+    double n_total = weighted ? c->src_wsum : (double)n;
     if (c->comm_on()) {
         HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_total, 1, 0));
     }
@@ -738,7 +759,11 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     if (L > 2) {
         HGMM_TRY(ensure(c, c->t_xs3, sizeof(double) * 3 * n_pad));
         xs_c = c->t_xs3.as<double>();
+        if (weighted) HGMM_TRY(ensure(c, c->t_w3, sizeof(double) * n_pad));
     }
+    double* w_b = weighted ? c->t_w2.as<double>() : nullptr;
+    double* w_c = (weighted && L > 2) ? c->t_w3.as<double>() : nullptr;
+    const double* w_cur = weighted ? c->src_w.as<double>() : nullptr;     // (level-0 order, like x_soa64; never overwritten)
 
     const double* xs_cur = xs_a;
     int* perm_cur = perm_a;
@@ -800,14 +825,10 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
                 if (!overlap || e == 0) {
                     ProfScope prof(c, HGMM_K_TREE_ESTEP);
                     const TreeFollow fol = (use_follow && e >= 1) ? follow_of(e) : no_follow;
-                    if (estep_half)
-                        tree_estep_kernel<true><<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, chunk_desc,
-                                                                                  n_chunks_dev, parent_first, l, partials, cur,
-                                                                                  &ctl->done, fol);
-                    else
-                        tree_estep_kernel<false><<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, chunk_desc,
-                                                                                   n_chunks_dev, parent_first, l, partials, cur,
-                                                                                   &ctl->done, fol);
+                    const auto estep = weighted ? (estep_half ? tree_estep_kernel<true, true> : tree_estep_kernel<false, true>)
+                                                : (estep_half ? tree_estep_kernel<true, false> : tree_estep_kernel<false, false>);
+                    estep<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l,
+                                                             partials, cur, &ctl->done, fol, w_cur);
                 }
                 // single GPU: reduction, M-step and preparation of a node in one launch; with a
                 // communicator the all-reduce of the moments sits between reduction and M-step
@@ -840,36 +861,37 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
                     unsigned int* q_ticket = use_follow ? nullptr : q_ticket_buf;     // follow mode: plain stores of the shares
                     // (the positional kernels take the same list, field by field)
                     TreeLoglikArgs la{xs_cur, n, n_pad, d_prep, lb, n_level, per_chunk, ll_partial, block_q, q_ticket,
-                                      q_dev, &ctl->done, chunks > 1 ? no_stop : stop, flags_ptr(c), pairs_ptr(c), nullptr};
+                                      q_dev, &ctl->done, chunks > 1 ? no_stop : stop, flags_ptr(c), pairs_ptr(c), nullptr,
+                                      0, 0, w_cur};
                     const dim3 ll_grid(llblocks, chunks);
                     if (overlap && (e + 1 < max_iters_per_level || fused0)) {
                         // (level 0: no log-likelihood workgroups at all -- the E-step stores the shares of q; behind the
                         //  budget's last iteration it runs for those alone, its moments and assignment are never read)
                         la.stop = no_stop;
                         const TreeEstepArgs ea{xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l, partials,
-                                               curbuf[(e + 1) & 1], &ctl->done, fused0 ? block_q : nullptr};
+                                               curbuf[(e + 1) & 1], &ctl->done, fused0 ? block_q : nullptr, w_cur};
                         const int gx = fused0 ? 0 : llblocks, gy = fused0 ? 0 : chunks;
                         const unsigned g = (unsigned)(gx * gy) + grid_chunks;
-                        if (ll_pts == 2 && c->tree.pdf_f32) tree_ll_estep_kernel<2, true><<<g, CH, 0, c->stream>>>(la, gx, gy, ea);
-                        else if (ll_pts == 2) tree_ll_estep_kernel<2><<<g, CH, 0, c->stream>>>(la, gx, gy, ea);
-                        else tree_ll_estep_kernel<1><<<g, CH, 0, c->stream>>>(la, gx, gy, ea);
-                    } else if (c->tree.pdf_f32 && ll_pts >= 2) {
-                        if (ll_pts == 4) tree_loglik_f32_kernel<4><<<ll_grid, CH, 0, c->stream>>>(la);
-                        else tree_loglik_f32_kernel<2><<<ll_grid, CH, 0, c->stream>>>(la);
+                        // (ll_pts is 2 here: `overlap` excludes the four-point form)
+                        const auto fused = weighted ? (c->tree.pdf_f32 ? tree_ll_estep_kernel<2, true, true> : tree_ll_estep_kernel<2, false, true>)
+                                                    : (c->tree.pdf_f32 ? tree_ll_estep_kernel<2, true, false> : tree_ll_estep_kernel<2, false, false>);
+                        fused<<<g, CH, 0, c->stream>>>(la, gx, gy, ea);
+                    } else if (c->tree.pdf_f32) {
+                        const auto ll = weighted ? (ll_pts == 4 ? tree_loglik_f32_kernel<4, true> : tree_loglik_f32_kernel<2, true>)
+                                                 : (ll_pts == 4 ? tree_loglik_f32_kernel<4, false> : tree_loglik_f32_kernel<2, false>);
+                        ll<<<ll_grid, CH, 0, c->stream>>>(la);
                     } else if (ll_pts == 4) {
-                        ll_positional(tree_loglik_kernel<4, true>, ll_grid, c->stream, la, c->exp_tab2.as<double>());
-                    } else if (ll_pts == 2) {
-                        ll_positional(tree_loglik_kernel<2>, ll_grid, c->stream, la, nullptr);
+                        ll_positional(weighted ? tree_loglik_kernel<4, true, true> : tree_loglik_kernel<4, true, false>, ll_grid,
+                                      c->stream, la, c->exp_tab2.as<double>());
                     } else {
-                        ll_positional(tree_loglik_kernel<1>, ll_grid, c->stream, la, nullptr);
+                        ll_positional(weighted ? tree_loglik_kernel<2, false, true> : tree_loglik_kernel<2, false, false>, ll_grid,
+                                      c->stream, la, nullptr);
                     }
                     if (chunks > 1 && !fused0) {
-                        if (c->tree.pdf_f32 && ll_pts >= 2)
-                            tree_loglik_finish_kernel<true><<<pblocks, CH, 0, c->stream>>>(ll_partial, n, n_pad, chunks, block_q,
-                                                                                          q_ticket, q_dev, &ctl->done, stop);
-                        else
-                            tree_loglik_finish_kernel<false><<<pblocks, CH, 0, c->stream>>>(ll_partial, n, n_pad, chunks, block_q,
-                                                                                           q_ticket, q_dev, &ctl->done, stop);
+                        const auto finish = weighted ? (c->tree.pdf_f32 ? tree_loglik_finish_kernel<true, true> : tree_loglik_finish_kernel<false, true>)
+                                                     : (c->tree.pdf_f32 ? tree_loglik_finish_kernel<true, false> : tree_loglik_finish_kernel<false, false>);
+                        finish<<<pblocks, CH, 0, c->stream>>>(ll_partial, n, n_pad, chunks, block_q, q_ticket, q_dev, &ctl->done,
+                                                              stop, w_cur);
                     }
                 }
                 if (c->comm_on()) {
@@ -977,10 +999,13 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
             tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(hist, chunk_first, seg_cur, P, chunk_off, seg_next);
             double* xs_next = (xs_cur == xs_b) ? xs_c : xs_b;     // A -> B -> C -> B -> ...
             int* perm_next = (perm_cur == perm_a) ? perm_b : perm_a;
-            tree_scatter_kernel<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, perm_cur, cur, chunk_desc, n_chunks_dev,
-                                                                  chunk_off, xs_next, perm_next);
+            double* w_next = (xs_next == xs_b) ? w_b : w_c;       // (the weights' buffers pair up with the coordinates')
+            const auto scatter = weighted ? tree_scatter_kernel<true> : tree_scatter_kernel<false>;
+            scatter<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, perm_cur, cur, chunk_desc, n_chunks_dev, chunk_off, xs_next,
+                                                       perm_next, w_cur, w_next);
             HGMM_HIP(c, hipGetLastError());
             xs_cur = xs_next;
+            w_cur = weighted ? w_next : nullptr;
             perm_cur = perm_next;
             seg_cur = seg_next;
             P *= 8;
@@ -1115,6 +1140,28 @@ extern "C" int hgmm_tree_set_target_weights(hgmm_ctx* c, const double* w, int64_
     HGMM_HIP(c, ctx_stream_sync(c));
     c->tgt_wsum = sum;
     c->tgt_weighted = true;
+    return HGMM_OK;
+}
+
+// per-point weights of the resident cloud (include/hgmm.h): src_w [n_pad] parallel to x_soa64; hgmm_tree_build alone reads them
+extern "C" int hgmm_tree_set_source_weights(hgmm_ctx* c, const double* w, int64_t n) {
+    HGMM_ENTER(c);
+    const char* what = "hgmm_tree_set_source_weights";
+    if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "%s: no cloud (set or bind points first)", what);
+    if (!w) { c->src_weighted = false; return HGMM_OK; }
+    if (n != c->n)
+        return fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident cloud has %lld points", what, (long long)n, (long long)c->n);
+    double sum = 0.0;
+    HGMM_TRY(check_target_weights(c, what, w, n, &sum));
+    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
+    c->src_weighted = false;
+    std::vector<double> padded((size_t)c->n_pad, 0.0);
+    std::copy(w, w + n, padded.begin());
+    HGMM_TRY(ensure(c, c->src_w, sizeof(double) * padded.size()));
+    HGMM_HIP(c, hipMemcpyAsync(c->src_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    c->src_wsum = sum;
+    c->src_weighted = true;
     return HGMM_OK;
 }
 

@@ -64,20 +64,25 @@ def _gate_arg(maha2_gate):
 
 
 WeightedPoints = namedtuple("WeightedPoints", ["points", "weights"])
-WeightedPoints.__doc__ = """A target cloud with one weight >= 0 per point: ``WeightedPoints(points [N,3], weights [N])``.  Every
+WeightedPoints.__doc__ = """A cloud with one weight >= 0 per point: ``WeightedPoints(points [N,3], weights [N])``.  Every
 entry that takes a target takes this in its place (any object with ``.points`` and ``.weights`` does) -- the way to hand
 weights to :meth:`GMMTree.registration_multistart` and :meth:`GMMTree.score`, whose argument lists are the reference-side
-ones; an explicit ``weights=`` / ``target_weights=`` argument, where there is one, takes precedence."""
+ones; an explicit ``weights=`` / ``target_weights=`` argument, where there is one, takes precedence.
+
+As a SOURCE (``buildGMMTree``, ``GMMTree(source)``, ``set_source``, ``registration_gmmtree`` and the sources of
+``registration_gmmtree_batch``) it brings its weights to the tree build: point i counts as ``weights[i]`` points
+(``Context.tree_set_source_weights``).  Earlier versions accepted a WeightedPoints source and silently dropped its weights;
+pass ``source.points`` to build the unweighted tree.  An explicit ``weights=`` / ``source_weights=`` takes precedence."""
 
 
 def _weights_arg(weights, n):
-    """The mirrors' ``weights`` argument for a target of ``n`` points -> None (no weights) or a float64 array [n], every entry
+    """The mirrors' ``weights`` argument for a cloud (a target, or a source) of ``n`` points -> None (no weights) or a float64 array [n], every entry
     finite and >= 0 and not all of them zero.  Anything else is refused here, before the library is touched."""
     if weights is None:
         return None
     w = np.ascontiguousarray(weights, dtype=np.float64)
     if w.ndim != 1 or w.shape[0] != int(n):
-        raise ValueError("weights must be one per target point: expected shape (%d,), got %s" % (int(n), w.shape))
+        raise ValueError("weights must be one per point of the cloud: expected shape (%d,), got %s" % (int(n), w.shape))
     bad = np.nonzero(~(np.isfinite(w) & (w >= 0.0)))[0]
     if len(bad):
         raise ValueError("weights must be finite and >= 0: weight %d is %r" % (int(bad[0]), float(w[bad[0]])))
@@ -92,6 +97,15 @@ def _target_weights(target, weights=None):
     if weights is None:
         weights = getattr(target, "weights", None)
     return _weights_arg(weights, len(_points(target)))
+
+
+def _set_source(ctx, points, weights):
+    """Upload ``points`` (float64 [N,3]) as the context's resident cloud, then its weights if it has any (already checked by
+    :func:`_weights_arg`).  A new cloud drops the previous one's weights in the library, so a cloud is never built under
+    another one's weights."""
+    ctx.set_points(points)
+    if weights is not None:
+        ctx.tree_set_source_weights(weights)
 
 
 def _set_target(ctx, target, weights=None):
@@ -119,8 +133,14 @@ def _reg_gate(ctx, gate):
 
 
 def buildGMMTree(points, maxTreeLevel, ls, ld, sig2=0.004, seed=72, init_idx=None,
-                 max_iters_per_level=1000, ctx: Context | None = None, return_trace=False, dtype=None, pdf_dtype=None):
+                 max_iters_per_level=1000, ctx: Context | None = None, return_trace=False, dtype=None, pdf_dtype=None,
+                 weights=None):
     """-> (mixingCoeff[T], mean[T,3], covar[T,3,3])   (hgmm_gpu.py:466-548).
+
+    ``weights`` [N] >= 0 (no counterpart in the reference; default None: the points' own if they are a
+    :class:`WeightedPoints`, else none): point i counts as ``weights[i]`` points -- a voxel centroid with its count
+    (``voxel_down_sample(..., return_counts=True)``).  The moments, ``pi`` and the level log-likelihood behind the stop rule
+    ``ls`` are weighted; the partition and the 1e-15 floor are not (``Context.tree_set_source_weights``).
 
     ``init_idx`` (T indices into ``points``) overrides the reference's
     ``np.random.seed(72); randint(nTotal, size=nTotal)`` draw.
@@ -133,6 +153,7 @@ def buildGMMTree(points, maxTreeLevel, ls, ld, sig2=0.004, seed=72, init_idx=Non
     (``dtype=np.float64, pdf_dtype=<the points' type>``).  The context's own precision setting is restored afterwards."""
     ctx = ctx or default_context()
     raw = _points(points)
+    weights = _target_weights(points, weights)       # (refused before anything is uploaded)
     dt = np.dtype(dtype) if dtype is not None else (np.dtype(np.float32) if raw.dtype == np.float32 else np.dtype(np.float64))
     pdt = np.dtype(pdf_dtype) if pdf_dtype is not None else dt
     if dt not in (np.dtype(np.float32), np.dtype(np.float64)) or pdt not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -142,7 +163,7 @@ def buildGMMTree(points, maxTreeLevel, ls, ld, sig2=0.004, seed=72, init_idx=Non
     if init_idx is None:
         rs = np.random.RandomState(seed)
         init_idx = rs.randint(T, size=T)
-    ctx.set_points(P)
+    _set_source(ctx, P, weights)
     prev = getattr(ctx, "tree_dtype", np.dtype(np.float64))     # (a precision the caller set on the context survives this call)
     ctx.tree_set_precision(pdt)
     try:
@@ -372,10 +393,15 @@ class GMMTree():
     (``voxel_down_sample(..., return_counts=True)``), a return weighted by range, the caller's own M-estimator weights.
     ``registration(..., weights=)`` takes them as an argument; every method that takes a target (``registration``,
     ``registration_multistart``, ``score``, ``expectation_step``) takes a :class:`WeightedPoints` in its place.  The
-    descent, the stop rule and the gate do not see them; the per-point arrays of a score are not weighted, its sums are."""
+    descent, the stop rule and the gate do not see them; the per-point arrays of a score are not weighted, its sums are.
+
+    Per-point WEIGHTS of the source (``source_weights=``, ``set_source(source, weights=)``, or a :class:`WeightedPoints`
+    source; ``Context.tree_set_source_weights``): source point i counts as ``w_i`` points in the tree build, see
+    :func:`buildGMMTree`."""
 
     def __init__(self, source=None, tree_level=5, lambda_c=0.01, ls=20, ld=1.0e-4, sig2=0.004,
-                 init_idx=None, ctx: Context | None = None, verbose=False, solve_on_device=False, maha2_gate=None):
+                 init_idx=None, ctx: Context | None = None, verbose=False, solve_on_device=False, maha2_gate=None,
+                 source_weights=None):
         self._maha2_gate = _gate_arg(maha2_gate)
         self._source = None
         self._tree_level = tree_level
@@ -392,7 +418,9 @@ class GMMTree():
         self._solve_on_device = bool(solve_on_device)
         self._target_id = None
         if source is not None:
-            self.set_source(source)
+            self.set_source(source, source_weights)
+        elif source_weights is not None:
+            raise ValueError("source_weights without a source")
 
     @property
     def _ctx(self):
@@ -400,7 +428,10 @@ class GMMTree():
             self._ctx_arg = default_context()
         return self._ctx_arg
 
-    def set_source(self, source):
+    def set_source(self, source, weights=None):
+        """Build the tree of ``source``; ``weights`` [N] >= 0 (default None: the source's own if it is a
+        :class:`WeightedPoints`, else none) as in :func:`buildGMMTree`."""
+        weights = _target_weights(source, weights)   # (refused before anything is uploaded)
         self._source = _points(source)
         self._eig_cache = None                       # node covariances are about to change
         t1 = time.time()
@@ -410,7 +441,7 @@ class GMMTree():
         pdf = np.float32 if self._source.dtype == np.float32 else np.float64
         self._mixingCoeff, self._mean, self._covar = buildGMMTree(
             self._source, self._tree_level, self._ls, self._ld, sig2=self._sig2,
-            init_idx=self._init_idx, ctx=self._ctx, dtype=np.float64, pdf_dtype=pdf)
+            init_idx=self._init_idx, ctx=self._ctx, dtype=np.float64, pdf_dtype=pdf, weights=weights)
         if self._verbose:
             print("Build tree Time: ", time.time() - t1)
 
@@ -717,8 +748,11 @@ def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], r
     ``starts`` (a list of start poses, e.g. :func:`rotation_starts`): :meth:`GMMTree.registration_multistart`'s result.
     ``maha2_gate=`` (among :class:`GMMTree`'s arguments): the registration E-step's Mahalanobis gate, with or without ``starts``.
     ``target_weights=`` [N] >= 0 (a keyword of this function, not of :class:`GMMTree`; default: the target's own if it is a
-    :class:`WeightedPoints`): per-point weights of the target, with or without ``starts``."""
+    :class:`WeightedPoints`): per-point weights of the target, with or without ``starts``.
+    ``source_weights=`` [N] >= 0 (default: the source's own if it is a :class:`WeightedPoints`): per-point weights of the
+    source for the tree build, as in :func:`buildGMMTree`."""
     weights = _target_weights(target, kargs.pop("target_weights", None))
+    kargs["source_weights"] = _target_weights(source, kargs.pop("source_weights", None))
     gt = GMMTree(_points(source), **kargs)
     if starts is not None:
         tgt = _points(target) if weights is None else WeightedPoints(_points(target), weights)
@@ -732,7 +766,7 @@ BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this 
 
 def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | None = None, tree_level=5, lambda_c=0.01,
                                ls=20, ld=1.0e-4, sig2=0.004, init_idx=None, return_info=False, pdf_dtype=None,
-                               solve_on_device=False, score=False, maha2_gate=None, target_weights=None):
+                               solve_on_device=False, score=False, maha2_gate=None, target_weights=None, source_weights=None):
     """``[registration_gmmtree(s, t, maxiter, tol, tree_level=..., ...) for s, t in pairs]`` (hgmm_gpu.py:802-807 per pair)
     with ALL pairs in the same launches: the B source clouds are one resident forest (``hgmm_tree_build_batch``: levels in
     lock-step, one stop rule per cloud), the B targets are registered against their trees together
@@ -757,6 +791,11 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     target as in :class:`GMMTree`, or None for a pair without (a target that is a :class:`WeightedPoints` brings its own);
     the scores of ``score=True`` are taken under them, and pairs that run or finish serially follow them too.
 
+    ``source_weights`` (default None: none): likewise a list with one entry per pair -- per-point weights [N_b] >= 0 of that
+    pair's SOURCE for the tree build as in :func:`buildGMMTree`, or None for a pair without (a source that is a
+    :class:`WeightedPoints` brings its own); an unweighted pair's tree is bitwise its unweighted tree, and the pairs of
+    400 000 points or more that run serially are built under their weights too.
+
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
     gate = _gate_arg(maha2_gate)
@@ -768,6 +807,12 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
         raise ValueError("target_weights must have one entry (an array or None) per pair: %d entries for %d pairs"
                          % (len(target_weights), len(pairs)))
     ws = [_target_weights(pairs[k][1], None if target_weights is None else target_weights[k]) for k in range(len(pairs))]
+    if source_weights is not None and len(source_weights) != len(pairs):
+        raise ValueError("source_weights must have one entry (an array or None) per pair: %d entries for %d pairs"
+                         % (len(source_weights), len(pairs)))
+    sws = [_target_weights(pairs[k][0], None if source_weights is None else source_weights[k]) for k in range(len(pairs))]
+    # (from here on the weights travel as lists: the recursive calls below must not read a WeightedPoints' own a second time)
+    pairs = [(_points(s), t) for s, t in pairs]
     big = [k for k, (s, _) in enumerate(pairs) if len(_points(s)) >= BATCH_MAX_POINTS]
     if big:
         # a cloud of >= 400 000 points fills the chip by itself and takes the serial build's four-points-per-thread
@@ -779,7 +824,7 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
             info["score"] = [None] * len(pairs)
         for k in big:
             gt = GMMTree(pairs[k][0], tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, init_idx=init_idx, ctx=ctx,
-                         solve_on_device=solve_on_device, maha2_gate=gate)
+                         solve_on_device=solve_on_device, maha2_gate=gate, source_weights=sws[k])
             out[k] = gt.registration(_points(pairs[k][1]), maxiter, tol, weights=ws[k])
             info["registration_iters"][k], info["status"][k] = int(gt.n_iter_), 0
             if score:
@@ -787,7 +832,8 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
         rest = [k for k in range(len(pairs)) if k not in set(big)]
         if rest:
             r, inf = registration_gmmtree_batch([pairs[k] for k in rest], maxiter, tol, ctx, tree_level, lambda_c, ls, ld, sig2,
-                                                init_idx, True, pdf_dtype, solve_on_device, score, gate, [ws[k] for k in rest])
+                                                init_idx, True, pdf_dtype, solve_on_device, score, gate, [ws[k] for k in rest],
+                                                source_weights=[sws[k] for k in rest])
             for j, k in enumerate(rest):
                 out[k] = r[j]
                 info["build_iters"][k] = inf["build_iters"][j]
@@ -806,7 +852,7 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
                 sel = [k for k, v in enumerate(kinds) if v == kind]
                 r, inf = registration_gmmtree_batch([pairs[k] for k in sel], maxiter, tol, ctx, tree_level, lambda_c, ls, ld,
                                                     sig2, init_idx, True, kind, solve_on_device, score, gate,
-                                                    [ws[k] for k in sel])
+                                                    [ws[k] for k in sel], source_weights=[sws[k] for k in sel])
                 for j, k in enumerate(sel):
                     out[k] = r[j]
                     for key in info:
@@ -824,7 +870,10 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     idx = np.asarray(init_idx) if init_idx is not None else np.random.RandomState(72).randint(T, size=T)
     init_mu = np.stack([np.asarray(S[idx], dtype=np.float64) for S in srcs])
     clock.append(time.perf_counter())
-    ctx.set_points_batch(srcs)
+    if any(w is not None for w in sws):
+        ctx.set_points_batch(srcs, weights=sws)
+    else:
+        ctx.set_points_batch(srcs)
     clock.append(time.perf_counter())
     prev = getattr(ctx, "tree_dtype", np.dtype(np.float64))     # (a precision the caller set on the context survives this call)
     ctx.tree_set_precision(pdf_dtype)

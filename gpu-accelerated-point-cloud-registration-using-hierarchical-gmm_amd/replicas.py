@@ -111,6 +111,9 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
     lambda_c, ls, sig2, ...) or ``registration_gmmreg`` (``method='gmmreg'``, gmmreg_gpu/gmmreg.py:149-157; it has no
     iteration budget or tolerance of its own, so ``maxiter`` / ``tol`` other than the defaults are refused), the pairs
     fanned out over the pool's contexts.  -> the reference's per-pair results, in the order of ``pairs``.
+    Per-point weights travel with the pair: a source or target that is a ``WeightedPoints(points, weights)`` brings its own to
+    the tree build resp. the registration (``kargs`` go to every pair alike, so the per-pair lists ``source_weights=`` /
+    ``target_weights=`` of ``registration_gmmtree_batch`` are not for this function).
 
     ``batch`` > 1 (gmmtree only): every context takes ``batch`` pairs at a time through the SAME launches
     (``registration_gmmtree_batch``: the trees built as one forest, the targets registered together) -- a 40 k-point pair

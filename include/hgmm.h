@@ -431,10 +431,44 @@ int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, c
  * rank holds the weights of its shard) -- and by the summaries of hgmm_tree_score, hgmm_tree_score_batch and
  * hgmm_tree_score_multi: summary[0] = sum of w, summary[1..6] = the w-weighted sums of what they are without weights, added in
  * the same fixed order; the per-point arrays node / maha2 / logp are not weighted.  NOT honoured by the build (hgmm_tree_build*:
- * weights of a SOURCE cloud are a different feature) nor by any flat, full-covariance or KMeans entry: they ignore them.     */
+ * the weights of a SOURCE cloud are hgmm_tree_set_source_weights', below) nor by any flat, full-covariance or KMeans entry:
+ * they ignore them.                                                                                                         */
 int hgmm_tree_set_target_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
 int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
                                        const double* const* w /* w == NULL: none; w[b] == NULL: pair b unweighted */,
+                                       const int64_t* counts);
+/* Per-point weights of the SOURCE cloud, for the tree build.  The reference has no counterpart: buildGMMTree
+ * (hgmm_cupy_cpu_working.py:122-198) counts every source point as one unit of evidence, although its own pipeline
+ * voxel-downsamples both scans first (run_gmm_static.py:28).  A source point i with weight w_i >= 0 counts as w_i points.
+ * Three statements of the reference change and nothing else does:
+ *   gmmTreeEStep        (C:162-191, accumulate C:95-106)  the moments are sum_i w_i gamma_ij (1, x_i, x_i x_i^T); the 1e-15
+ *                       floor is tested on gamma (not on w_i gamma), and the arg-max child -- the partition -- does not see
+ *                       the weight;
+ *   mlEstimator         (C:109-119)  pi_j = m0_j / W with W = sum_i w_i (a float64 sum on the host, in index order) where it
+ *                       was m0_j / N; the m0 < ld rule, mu and cov are unchanged and see the weighted moments;
+ *   logLikelihoodValue  (C:72-85)    q = sum_i w_i log max(sum_j [pi_j >= eps] pi_j N(x_i; j), eps); the stop rule
+ *                       |q - q_prev| < ls is unchanged -- with counts as weights ls means for 2 000 centroids what it
+ *                       means for the 40 000 points they stand for.
+ * Integer weights are repetition (the build of (X, c) is the build of X with row i repeated c_i times, up to the order of
+ * summation); a zero weight makes a point absent: it is still partitioned, it adds nothing.  w == 1 everywhere gives the
+ * unweighted tree, iteration counts and q trace bit for bit; w == 2 everywhere with ls and ld doubled gives the unweighted
+ * tables and iteration counts at (ls, ld) bit for bit and exactly twice the q trace.  Non-finite coordinates are not covered.
+ * The weights ATTACH TO THE CLOUD THE CONTEXT IS WORKING ON: the serial entry to the float64 view of hgmm_set_points_* or of
+ * a bound handle, the batch entry to the resident forest cloud of hgmm_set_points_batch_* -- HGMM_ERR_STATE without one.
+ * Whatever changes the resident cloud drops them: hgmm_set_points_f32 / _f64, hgmm_points_bind (of another cloud),
+ * hgmm_set_points_batch_f32 / _f64, hgmm_points_destroy of the bound handle.
+ * w == NULL: no weights (the unweighted kernels run, every result what it was, bit for bit); in the batch w[b] == NULL leaves
+ * cloud b unweighted (bitwise its unweighted tree, next to weighted neighbours).  n resp. counts[b] must equal the resident
+ * counts; a NaN, infinite or negative weight (hgmm_last_error names its index) and a cloud whose weights are all zero are
+ * refused on the host before anything is touched: HGMM_ERR_ARG, and the previous weights stay in force.
+ * Honoured by hgmm_tree_build (serial entry) and hgmm_tree_build_batch (batch entry), in both precisions of
+ * hgmm_tree_set_precision, and by nothing else.  IGNORED by the stand-alone steps below (hgmm_tree_estep, hgmm_tree_mstep,
+ * hgmm_tree_loglik and the generic E-step kernel behind them), by every flat, full-covariance and KMeans entry, and by the
+ * registration and score entries (their weights are the TARGET's, above).  Under a communicator hgmm_tree_build with
+ * weights resident returns HGMM_ERR_STATE: sharded weighted builds are not supported.                                        */
+int hgmm_tree_set_source_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
+int hgmm_tree_set_source_weights_batch(hgmm_ctx* ctx, int B,
+                                       const double* const* w /* w == NULL: none; w[b] == NULL: cloud b unweighted */,
                                        const int64_t* counts);
 /* The steps buildGMMTree is made of, one at a time (reference function granularity).  Node tables
  * hold T nodes (any T >= 8, need not be a complete tree).
