@@ -1076,6 +1076,24 @@ class Context:
         counts = (C.c_int64 * len(arrs))(*[a.shape[0] for a in arrs])
         return arrs, ptrs, counts, all32
 
+    def _set_weights_batch(self, entry, weights, resident):
+        """hgmm_tree_set_source_weights_batch / _target_weights_batch: a list of B arrays [N_b] or None entries, or None for no
+        weights at all.  ``resident``: the members' counts this context uploaded, or None."""
+        if weights is None:
+            self._check(entry(self.h, 0, None, None))
+            return self
+        ws = [None if w is None else np.ascontiguousarray(w, dtype=np.float64) for w in weights]
+        for w in ws:
+            if w is not None and w.ndim != 1:
+                raise ValueError("weights must be [N_b], got %s" % (w.shape,))
+        ptrs = (_vp * max(len(ws), 1))(*[None if w is None else w.ctypes.data for w in ws])
+        # (the library compares every count with the resident member's; a None entry names no count of its own)
+        resident = resident or []
+        counts = (C.c_int64 * max(len(ws), 1))(*[(resident[b] if b < len(resident) else 0) if w is None else w.shape[0]
+                                                 for b, w in enumerate(ws)])
+        self._check(entry(self.h, len(ws), ptrs, counts))
+        return self
+
     def set_points_batch(self, clouds, weights=None):
         """B clouds [N_b,3] become ONE resident cloud, cloud after cloud, each uploaded from its own array
         (hgmm_set_points_batch_f64 / _f32).  -> the arrays that were uploaded (their lengths are the forest's counts).
@@ -1095,20 +1113,7 @@ class Context:
         """Weights of the resident forest cloud's members for :meth:`tree_build_batch` (hgmm_tree_set_source_weights_batch): a
         list of B arrays [N_b] or None entries (that cloud stays unweighted, bit for bit); ``None``: no weights at all.  As
         :meth:`tree_set_source_weights`: a new resident cloud drops them, a refused upload keeps the previous ones."""
-        if weights is None:
-            self._check(self.lib.hgmm_tree_set_source_weights_batch(self.h, 0, None, None))
-            return self
-        ws = [None if w is None else np.ascontiguousarray(w, dtype=np.float64) for w in weights]
-        for w in ws:
-            if w is not None and w.ndim != 1:
-                raise ValueError("weights must be [N_b], got %s" % (w.shape,))
-        ptrs = (_vp * max(len(ws), 1))(*[None if w is None else w.ctypes.data for w in ws])
-        # (the library compares every count with the resident cloud's; a None entry names no count of its own)
-        resident = getattr(self, "_batch_counts", None) or []
-        counts = (C.c_int64 * max(len(ws), 1))(*[(resident[b] if b < len(resident) else 0) if w is None else w.shape[0]
-                                                 for b, w in enumerate(ws)])
-        self._check(self.lib.hgmm_tree_set_source_weights_batch(self.h, len(ws), ptrs, counts))
-        return self
+        return self._set_weights_batch(self.lib.hgmm_tree_set_source_weights_batch, weights, getattr(self, "_batch_counts", None))
 
     def tree_build_batch(self, counts, L, ls, ld, init_mu, sig2, max_iters_per_level=1000, want_tables=True,
                          want_trace=False, q_capacity=None):
@@ -1165,36 +1170,33 @@ class Context:
     def tree_set_target_weights_batch(self, weights):
         """Weights of the resident batch targets (hgmm_tree_set_target_weights_batch): a list of B arrays [N_b] or None
         entries (that pair stays unweighted); ``None``: no weights at all."""
-        if weights is None:
-            self._check(self.lib.hgmm_tree_set_target_weights_batch(self.h, 0, None, None))
-            return self
-        ws = [None if w is None else np.ascontiguousarray(w, dtype=np.float64) for w in weights]
-        for w in ws:
-            if w is not None and w.ndim != 1:
-                raise ValueError("weights must be [N_b], got %s" % (w.shape,))
-        ptrs = (_vp * max(len(ws), 1))(*[None if w is None else w.ctypes.data for w in ws])
-        # (the library compares every count with the resident target's; a None entry names no count of its own)
-        resident = getattr(self, "_tgt_counts", None) or []
-        counts = (C.c_int64 * max(len(ws), 1))(*[(resident[b] if b < len(resident) else 0) if w is None else w.shape[0]
-                                                 for b, w in enumerate(ws)])
-        self._check(self.lib.hgmm_tree_set_target_weights_batch(self.h, len(ws), ptrs, counts))
-        return self
+        return self._set_weights_batch(self.lib.hgmm_tree_set_target_weights_batch, weights, getattr(self, "_tgt_counts", None))
 
     def tree_register_batch(self, rot, t, scale=1.0, lambda_c=0.01, max_iter=20, tol=1.0e-4, q_prev=None, want_trace=False):
         """Up to ``max_iter`` registration iterations of every (tree b, target b) pair of the resident forest in the same
         launches (hgmm_tree_register_batch), each bitwise :meth:`tree_register` on that pair.
         -> (rot [B,3,3], t [B,3], iterations [B], q [B] (NaN: none), status [B], traces or None)."""
+        return self._register_poses(self.lib.hgmm_tree_register_batch, rot, t, scale, lambda_c, max_iter, tol, q_prev, want_trace)
+
+    def _register_poses(self, entry, rot, t, scale, lambda_c, max_iter, tol, q_prev, want_trace):
+        """hgmm_tree_register_batch / _multi from n = len(rot) poses -> what :meth:`tree_register_batch` returns"""
         rot = np.array(rot, dtype=np.float64).reshape(-1, 3, 3)
-        B = rot.shape[0]
-        t = np.array(t, dtype=np.float64).reshape(B, 3)
-        q = np.full(B, np.nan) if q_prev is None else np.array(q_prev, dtype=np.float64).reshape(B)
-        iters, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        trace = np.zeros((B, max(int(max_iter), 1), 13)) if want_trace else None
-        self._check(self.lib.hgmm_tree_register_batch(self.h, B, _ptr(rot), _ptr(t), float(scale), float(lambda_c),
-                                                      int(max_iter), float(tol), _ptr(q), _ptr(iters), _ptr(status),
-                                                      _ptr(trace)))
-        traces = [trace[b, :iters[b]] for b in range(B)] if want_trace else None
+        n = rot.shape[0]
+        t = np.array(t, dtype=np.float64).reshape(n, 3)
+        q = np.full(n, np.nan) if q_prev is None else np.array(q_prev, dtype=np.float64).reshape(n)
+        iters, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        trace = np.zeros((max(n, 1), max(int(max_iter), 1), 13)) if want_trace else None
+        self._check(entry(self.h, n, _ptr(rot), _ptr(t), float(scale), float(lambda_c), int(max_iter), float(tol), _ptr(q),
+                          _ptr(iters), _ptr(status), _ptr(trace)))
+        traces = [trace[b, :iters[b]] for b in range(n)] if want_trace else None
         return rot, t, iters, q, status, traces
+
+    def _score_poses(self, entry, n, rot, t, scale, lambda_c, maha2_max):
+        """hgmm_tree_score_batch / _multi at n poses (``rot`` [n,3,3], ``t`` [n,3], or None) -> summaries [n,8]"""
+        summary = np.empty((max(n, 1), 8))
+        self._check(entry(self.h, n, _ptr(rot) if n else None, _ptr(t) if n else None, float(scale), float(lambda_c),
+                          float(maha2_max), _ptr(summary)))
+        return summary[:n]
 
     def tree_score(self, rot=None, t=None, scale=1.0, lambda_c=0.01, maha2_max=CHI2_3_99, want=("node", "maha2", "logp")):
         """Score of the resident target, moved by ``y = scale * rot @ x + t``, against the resident tree (hgmm_tree_score):
@@ -1233,27 +1235,14 @@ class Context:
             t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3)
             if B and t.shape[0] != B:
                 raise ValueError("tree_score_batch: %d translations for %d resident targets" % (t.shape[0], B))
-        summary = np.empty((max(B, 1), 8))
-        self._check(self.lib.hgmm_tree_score_batch(self.h, B, _ptr(rot) if B else None, _ptr(t) if B else None, float(scale),
-                                                   float(lambda_c), float(maha2_max), _ptr(summary)))
-        return summary[:B]
+        return self._score_poses(self.lib.hgmm_tree_score_batch, B, rot, t, scale, lambda_c, maha2_max)
 
     # -- multi-start: K start poses of the serial pair per launch set (hgmm_tree_register_multi / hgmm_tree_score_multi) ----
     def tree_register_multi(self, rot, t, scale=1.0, lambda_c=0.01, max_iter=20, tol=1.0e-4, q_prev=None, want_trace=False):
         """:meth:`tree_register` from K start poses at once on the resident tree and target (hgmm_tree_register_multi), each
         hypothesis bitwise the serial call from that start.  ``rot`` [K,3,3], ``t`` [K,3].
         -> (rot [K,3,3], t [K,3], iterations [K], q [K] (NaN: none), status [K], traces or None)."""
-        rot = np.array(rot, dtype=np.float64).reshape(-1, 3, 3)
-        K = rot.shape[0]
-        t = np.array(t, dtype=np.float64).reshape(K, 3)
-        q = np.full(K, np.nan) if q_prev is None else np.array(q_prev, dtype=np.float64).reshape(K)
-        iters, status = np.zeros(K, np.int32), np.zeros(K, np.int32)
-        trace = np.zeros((max(K, 1), max(int(max_iter), 1), 13)) if want_trace else None
-        self._check(self.lib.hgmm_tree_register_multi(self.h, K, _ptr(rot) if K else None, _ptr(t) if K else None, float(scale),
-                                                      float(lambda_c), int(max_iter), float(tol), _ptr(q), _ptr(iters),
-                                                      _ptr(status), _ptr(trace)))
-        traces = [trace[k, :iters[k]] for k in range(K)] if want_trace else None
-        return rot, t, iters, q, status, traces
+        return self._register_poses(self.lib.hgmm_tree_register_multi, rot, t, scale, lambda_c, max_iter, tol, q_prev, want_trace)
 
     def tree_score_multi(self, rot, t, scale=1.0, lambda_c=0.01, maha2_max=CHI2_3_99):
         """:meth:`tree_score`'s summary of the resident target at K poses in one launch (hgmm_tree_score_multi), each bitwise
@@ -1261,10 +1250,7 @@ class Context:
         rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 3, 3)
         K = rot.shape[0]
         t = np.ascontiguousarray(t, dtype=np.float64).reshape(K, 3)
-        summary = np.empty((max(K, 1), 8))
-        self._check(self.lib.hgmm_tree_score_multi(self.h, K, _ptr(rot) if K else None, _ptr(t) if K else None, float(scale),
-                                                   float(lambda_c), float(maha2_max), _ptr(summary)))
-        return summary[:K]
+        return self._score_poses(self.lib.hgmm_tree_score_multi, K, rot, t, scale, lambda_c, maha2_max)
 
     @staticmethod
     def _node_tables(pi, mu, cov):

@@ -249,31 +249,46 @@ __global__ void forest_target_kernel(const IN* __restrict__ aos, int64_t n, int6
     if (lane_id() == 0 && bits != 0ull) atomicMax(r2max_bits, bits);
 }
 
+// ---- registration and score of a SET of registrations (tree_host.h: RegSet) ------------------------------------------------
+// One table entry per registration b: its pose, fixed-point encoding and loop state, and slice b of the [B][T][NMQ] sums.
+// SHARED = false, the forest (hgmm_tree_register_batch / _score_batch): pair b has its own tree, `prep + PREP_N T b`, and
+// its own target, at tg_first of the back-to-back targets.  SHARED = true, start poses of ONE pair (hgmm_tree_register_multi /
+// _score_multi, hgmm_tree_register): `prep` is the one resident tree's table, every entry names the same target, which
+// starts at 0 -- tg_first is not loaded.  A workgroup serves ONE registration either way: its LDS table of levels 0..2 would
+// have to be flushed per start pose otherwise, and the 24 B / point a second pose would save come out of L2 anyway.
+template <bool SHARED>
+__device__ inline const double* reg_prep_of(const double* __restrict__ prep, int T, int b) {
+    if constexpr (SHARED) return prep;
+    else return prep + (size_t)PREP_N * T * b;
+}
+
 // (GATED: hgmm_tree_set_reg_gate's finite gate, tree_reg_estep_body; the gate-off instantiations do not read the argument)
-// (WEIGHTED: hgmm_tree_set_target_weights_batch's array w [tg_pad], indexed like the points; likewise never read without)
-template <int NMQ, bool GATED = false, bool WEIGHTED = false>
+// (WEIGHTED: hgmm_tree_set_target_weights[_batch]'s array w [tg_pad], indexed like the points; likewise never read without)
+template <int NMQ, bool SHARED, bool GATED, bool WEIGHTED>
 __global__ __launch_bounds__(CH) void forest_reg_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                               const ForestRegPair* __restrict__ tab,
                                                               const double* __restrict__ prep, int T, int L,
                                                               double lambda_c, unsigned long long* __restrict__ momq, int gx,
                                                               double maha2_gate, const double* __restrict__ w) {
     __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
-    const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x B items)
+    const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x B items: registration b, chunk bx)
     const int b = item / gx, bx = item - b * gx;
     const ForestRegPair* pr = tab + b;
-    const int active = pr->active, first = pr->tg_first, count = pr->tg_count;
+    int first = 0;
+    if constexpr (!SHARED) first = pr->tg_first;
+    const int active = pr->active, count = pr->tg_count;
     if (!active || (int64_t)bx * CH >= count) return;
     const Rigid tf = pr->tf;
     const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
     const int64_t li = (int64_t)bx * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ, GATED, WEIGHTED>(first + li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c,
+    tree_reg_estep_body<NMQ, GATED, WEIGHTED>(first + li, li < count, tg, tg_pad, tf, reg_prep_of<SHARED>(prep, T, b), L, lambda_c,
                                               inv_d, fix_scale, momq + (size_t)NMQ * T * b, lds, maha2_gate, w);
 }
 
-// the score of every pair (tree_score_body), pair b's workgroups starting at the pair's first point as in the kernel above --
-// the serial call's grouping, so its shares and its summary are the serial call's bit for bit.  Reads the pose and the
-// target's place from the pairs table, NOT `active`: every pair is scored.  partial: [B][gx][6]
-template <bool WEIGHTED = false>
+// the score of every registration (tree_score_body), b's workgroups starting at its target's first point as in the kernel
+// above -- the serial call's grouping, so its shares and its summary are the serial call's bit for bit.  Reads the pose and
+// the target's place from the table, NOT `active`: every entry is scored.  partial: [B][gx][6]
+template <bool SHARED, bool WEIGHTED>
 __global__ __launch_bounds__(CH) void forest_score_kernel(const double* __restrict__ tg, int64_t tg_pad,
                                                           const ForestRegPair* __restrict__ tab,
                                                           const double* __restrict__ prep, int T, int L, double lambda_c,
@@ -282,22 +297,26 @@ __global__ __launch_bounds__(CH) void forest_score_kernel(const double* __restri
     const int item = (int)blockIdx.x;
     const int b = item / gx, bx = item - b * gx;
     const ForestRegPair* pr = tab + b;
-    const int first = pr->tg_first, count = pr->tg_count;
+    int first = 0;
+    if constexpr (!SHARED) first = pr->tg_first;
+    const int count = pr->tg_count;
     if ((int64_t)bx * CH >= count) return;
     const Rigid tf = pr->tf;
     const int64_t li = (int64_t)bx * CH + threadIdx.x;
-    tree_score_body<WEIGHTED>(first + li, li, li < count, tg, tg_pad, tf, prep + (size_t)PREP_N * T * b, L, lambda_c, maha2_max,
+    tree_score_body<WEIGHTED>(first + li, li, li < count, tg, tg_pad, tf, reg_prep_of<SHARED>(prep, T, b), L, lambda_c, maha2_max,
                               nullptr, nullptr, nullptr, partial + (size_t)SCORE_NSUM * item, w);
 }
+// (nothing here depends on whose tree it was: one kernel for both kinds of set)
 __global__ __launch_bounds__(CH) void forest_score_finish_kernel(const double* __restrict__ partial,
                                                                  const ForestRegPair* __restrict__ tab, int gx,
                                                                  double* __restrict__ summary) {
     const int b = blockIdx.x;
     const int count = tab[b].tg_count;
-    // (tg_wsum: the pair's weight sum, (double)count without weights -- reg_pair)
+    // (tg_wsum: the target's weight sum, (double)count without weights -- reg_pair)
     tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * b, (count + CH - 1) / CH, tab[b].tg_wsum, summary + 8 * b);
 }
 
+template <bool SHARED>
 __global__ __launch_bounds__(256) void forest_reg_normal_kernel(unsigned long long* __restrict__ momq,
                                                                 const ForestRegPair* __restrict__ tab,
                                                                 const double* __restrict__ prep, int T,
@@ -306,12 +325,13 @@ __global__ __launch_bounds__(256) void forest_reg_normal_kernel(unsigned long lo
     const int b = blockIdx.x;
     const ForestRegPair* pr = tab + b;
     if (!pr->active) return;
-    tree_reg_normal_body(momq + (size_t)4 * T * b, pr->d_ext, pr->inv_scale, prep + (size_t)PREP_N * T * b, T, out + 28 * b,
+    tree_reg_normal_body(momq + (size_t)4 * T * b, pr->d_ext, pr->inv_scale, reg_prep_of<SHARED>(prep, T, b), T, out + 28 * b,
                          host_out + 28 * b, host_seq + b, seq);
 }
 
-// reg_device_solve: the normal equations of pair b, then -- one thread -- the host's part of the iteration (reg_device_step)
-// and the pair's progress word for the host: (left the loop << 32) | iterations done
+// reg_device_solve: the normal equations of registration b, then -- one thread -- the host's part of the iteration
+// (reg_device_step) and b's progress word for the host: (left the loop << 32) | iterations done
+template <bool SHARED>
 __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long long* __restrict__ momq, ForestRegPair* tab,
                                                                const double* __restrict__ prep, int T,
                                                                double* __restrict__ out, double tol, int max_iter,
@@ -319,7 +339,7 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
     const int b = blockIdx.x;
     ForestRegPair* pr = tab + b;
     if (!pr->active) return;
-    tree_reg_normal_body(momq + (size_t)4 * T * b, pr->d_ext, pr->inv_scale, prep + (size_t)PREP_N * T * b, T, out + 28 * b,
+    tree_reg_normal_body(momq + (size_t)4 * T * b, pr->d_ext, pr->inv_scale, reg_prep_of<SHARED>(prep, T, b), T, out + 28 * b,
                          nullptr, nullptr, 0ull);
     __syncthreads();                                         // (the 28 sums are in `out`, written by this workgroup)
     if (threadIdx.x == 0) {
@@ -330,129 +350,53 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
     }
 }
 
-// ---- multi-start: K start poses of ONE pair per launch set (hgmm_tree_register_multi / hgmm_tree_score_multi) -----------------
-// The forest's registration kernels with the tree and the target SHARED: `prep` is the one resident tree's table, every table
-// entry names the same target (tg_first = 0, tg_count = n), and what hypothesis k owns is its entry (pose, encoding, loop
-// state) and slice k of the [K][T][NMQ] sums.  Same argument lists as the forest kernels, so the host loops below launch either
-// set.  A workgroup serves ONE hypothesis: its LDS table of levels 0..2 would have to be flushed per hypothesis otherwise,
-// and the 24 B / point a second hypothesis would save come out of L2 anyway.
-template <int NMQ, bool GATED = false, bool WEIGHTED = false>
-__global__ __launch_bounds__(CH) void tree_reg_multi_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
-                                                                  const ForestRegPair* __restrict__ tab,
-                                                                  const double* __restrict__ prep, int T, int L,
-                                                                  double lambda_c, unsigned long long* __restrict__ momq, int gx,
-                                                                  double maha2_gate, const double* __restrict__ w) {
-    __shared__ unsigned long long lds[REG_LDS_NODES * NMQ];
-    const int item = (int)blockIdx.x;                  // (a one-dimensional grid of gx x K items: hypothesis k, chunk bx)
-    const int k = item / gx, bx = item - k * gx;
-    const ForestRegPair* pr = tab + k;
-    const int active = pr->active, count = pr->tg_count;
-    if (!active || (int64_t)bx * CH >= count) return;
-    const Rigid tf = pr->tf;
-    const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
-    const int64_t i = (int64_t)bx * CH + threadIdx.x;
-    tree_reg_estep_body<NMQ, GATED, WEIGHTED>(i, i < count, tg, tg_pad, tf, prep, L, lambda_c, inv_d, fix_scale,
-                                              momq + (size_t)NMQ * T * k, lds, maha2_gate, w);
-}
-
-__global__ __launch_bounds__(256) void tree_reg_multi_normal_kernel(unsigned long long* __restrict__ momq,
-                                                                    const ForestRegPair* __restrict__ tab,
-                                                                    const double* __restrict__ prep, int T,
-                                                                    double* __restrict__ out, double* host_out,
-                                                                    unsigned long long* host_seq, unsigned long long seq) {
-    const int k = blockIdx.x;
-    const ForestRegPair* pr = tab + k;
-    if (!pr->active) return;
-    tree_reg_normal_body(momq + (size_t)4 * T * k, pr->d_ext, pr->inv_scale, prep, T, out + 28 * k, host_out + 28 * k,
-                         host_seq + k, seq);
-}
-
-// reg_device_solve: forest_reg_solve_kernel on the shared tree
-__global__ __launch_bounds__(256) void tree_reg_multi_solve_kernel(unsigned long long* __restrict__ momq, ForestRegPair* tab,
-                                                                   const double* __restrict__ prep, int T,
-                                                                   double* __restrict__ out, double tol, int max_iter,
-                                                                   double* __restrict__ trace, unsigned long long* host_words) {
-    const int k = blockIdx.x;
-    ForestRegPair* pr = tab + k;
-    if (!pr->active) return;
-    tree_reg_normal_body(momq + (size_t)4 * T * k, pr->d_ext, pr->inv_scale, prep, T, out + 28 * k, nullptr, nullptr, 0ull);
-    __syncthreads();                                         // (the 28 sums are in `out`, written by this workgroup)
-    if (threadIdx.x == 0) {
-        const int it = pr->it;
-        reg_device_step(out + 28 * k, pr, tol, max_iter, trace ? trace + ((size_t)k * max_iter + it) * 13 : nullptr);
-        __hip_atomic_store(host_words + k, ((unsigned long long)(pr->active ? 0 : 1) << 32) | (unsigned long long)(unsigned)pr->it,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// the score of every hypothesis: tree_score_kernel's grouping (workgroups start at the target's first point), partial [K][gx][6]
-template <bool WEIGHTED = false>
-__global__ __launch_bounds__(CH) void tree_score_multi_kernel(const double* __restrict__ tg, int64_t n, int64_t tg_pad,
-                                                              const ForestRegPair* __restrict__ tab,
-                                                              const double* __restrict__ prep, int L, double lambda_c,
-                                                              double maha2_max, double* __restrict__ partial, int gx,
-                                                              const double* __restrict__ w) {
-    const int item = (int)blockIdx.x;
-    const int k = item / gx, bx = item - k * gx;
-    const Rigid tf = tab[k].tf;
-    const int64_t i = (int64_t)bx * CH + threadIdx.x;
-    tree_score_body<WEIGHTED>(i, i, i < n, tg, tg_pad, tf, prep, L, lambda_c, maha2_max, nullptr, nullptr, nullptr,
-                              partial + (size_t)SCORE_NSUM * item, w);
-}
-__global__ __launch_bounds__(CH) void tree_score_multi_finish_kernel(const double* __restrict__ partial, int gx, double n_points,
-                                                                     double* __restrict__ summary) {
-    const int k = blockIdx.x;
-    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * k, gx, n_points, summary + 8 * k);
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// the E-step of the batched / multi-start registration loops: forest or shared tree, gate off or on (hgmm_tree_set_reg_gate),
-// without or with per-point weights of the target (hgmm_tree_set_target_weights[_batch])
-static auto reg_estep_kernel_for(bool shared_tree, bool gated, bool weighted) -> decltype(&forest_reg_estep_kernel<4, false, false>) {
-    if (weighted) {
-        if (gated) return shared_tree ? tree_reg_multi_estep_kernel<4, true, true> : forest_reg_estep_kernel<4, true, true>;
-        return shared_tree ? tree_reg_multi_estep_kernel<4, false, true> : forest_reg_estep_kernel<4, false, true>;
-    }
-    if (gated) return shared_tree ? tree_reg_multi_estep_kernel<4, true, false> : forest_reg_estep_kernel<4, true, false>;
-    return shared_tree ? tree_reg_multi_estep_kernel<4, false, false> : forest_reg_estep_kernel<4, false, false>;
+// The E-step of a set's registration loops: shared tree or forest, gate off or on (hgmm_tree_set_reg_gate), without or with
+// per-point weights of the target (hgmm_tree_set_target_weights[_batch]).  The one place a further flag is added.
+using RegEstepKernel = decltype(&forest_reg_estep_kernel<4, false, false, false>);
+template <bool... FLAGS>
+static RegEstepKernel reg_estep_kernel_for() { return forest_reg_estep_kernel<4, FLAGS...>; }
+template <bool... FLAGS, class... REST>
+static RegEstepKernel reg_estep_kernel_for(bool flag, REST... rest) {
+    return flag ? reg_estep_kernel_for<FLAGS..., true>(rest...) : reg_estep_kernel_for<FLAGS..., false>(rest...);
 }
-// The registration loop of B pairs with the device on its own (reg_device_solve): every iteration is two launches -- the
-// E-step of all pairs, then per pair the normal equations + reg_device_step -- enqueued by a host that only follows the
-// pairs' progress words and keeps a few iterations ahead of the slowest running pair; launches behind a pair's stop
-// return at their first load.  tab_dev: B entries; out_dev: 28 B doubles.  The caller's arrays are filled at the end.
-int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg_pad, const int64_t* tg_first,
-                              const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
-                              int L, unsigned long long* momq, double* rot, double* t, double scale, double lambda_c,
-                              int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                              double* trace, bool shared_tree, DevBuf* table, const double* tg_w, const double* tg_wsum) {
+static RegEstepKernel reg_estep_kernel_for(const hgmm_ctx* c, const RegSet& set) {
+    return reg_estep_kernel_for<>(set.shared_tree, std::isfinite(c->tree.reg_gate), set.w != nullptr);
+}
+
+// The registration loop of a set with the device on its own (reg_device_solve): every iteration is two launches -- the
+// E-step of all registrations, then per registration the normal equations + reg_device_step -- enqueued by a host that only
+// follows the progress words and keeps a few iterations ahead of the slowest running one; launches behind a registration's
+// stop return at their first load.  The caller's arrays are filled at the end.  (register_set has opened the sums.)
+static int forest_register_on_device(hgmm_ctx* c, const RegSet& set, double* rot, double* t, double scale, double lambda_c,
+                                     int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
+                                     double* trace) {
+    const int B = set.B(), T = set.T;
     for (int b = 0; b < B; ++b) { iters_out[b] = 0; status_out[b] = 0; }
     if (max_iter < 1) return HGMM_OK;
-    DevBuf& reg = table ? *table : c->fr_reg;
-    HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
+    RegTable tb;
+    HGMM_TRY(reg_table(c, *set.table, B, &tb));
     const size_t trace_bytes = trace ? sizeof(double) * 13 * (size_t)max_iter * B : 0;
     if (trace) HGMM_TRY(ensure(c, c->fr_trace, trace_bytes));
-    const double gate = c->tree.reg_gate;                    // (hgmm_tree_set_reg_gate; finite: the gated instantiations)
-    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate), tg_w != nullptr);
-    const auto solve_kernel = shared_tree ? tree_reg_multi_solve_kernel : forest_reg_solve_kernel;
-    ForestRegPair* d_tab = reg.as<ForestRegPair>();
-    double* d_out = reinterpret_cast<double*>(d_tab + B);
+    const auto estep_kernel = reg_estep_kernel_for(c, set);
+    const auto solve_kernel = set.shared_tree ? forest_reg_solve_kernel<true> : forest_reg_solve_kernel<false>;
+    unsigned long long* momq = set.momq->as<unsigned long long>();
     double* d_trace = trace ? c->fr_trace.as<double>() : nullptr;
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, B, &hand));
     const HostDev<unsigned long long> words = hand->progress(0);
     std::vector<ForestRegPair> tab(B);
-    int64_t longest = 0;
     for (int b = 0; b < B; ++b) {
-        ForestRegPair& pr = tab[b] = reg_pair(tg_first[b], tg_counts[b], tg_w ? tg_wsum : nullptr, b);
-        reg_pair_fill(pr, rigid_from(rot + 9 * b, t + 3 * b, scale), tg_rmax[b], mu_rmax[b]);
+        ForestRegPair& pr = tab[b] = reg_pair(set.regs[b]);
+        reg_pair_fill(pr, rigid_from(rot + 9 * b, t + 3 * b, scale), set.regs[b]);
         pr.has_q = (q_prev_inout[b] == q_prev_inout[b]) ? 1 : 0;              // (NaN: no previous q)
         pr.q_prev = pr.has_q ? q_prev_inout[b] : 0.0;
-        longest = std::max(longest, tg_counts[b]);
         __atomic_store_n(words.host + b, 0ull, __ATOMIC_RELAXED);
     }
-    HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
+    HGMM_TRY(stage_h2d(c, tb.pairs, tab.data(), sizeof(ForestRegPair) * B));
+    const unsigned gx = set.gx();
     const int ahead = 3;
     int enq = 0;
     unsigned spins = 0;
@@ -462,10 +406,10 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
         if (enq < max_iter && enq - pg.it_min < ahead) {
             {
                 ProfScope prof(c, HGMM_K_TREE_REG);
-                estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c, momq,
-                                                                                    (int)nblk(longest, CH), gate, tg_w);
+                estep_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, T, set.L, lambda_c, momq,
+                                                                     (int)gx, c->tree.reg_gate, set.w);
             }
-            solve_kernel<<<B, 256, 0, c->stream>>>(momq, d_tab, prep, T, d_out, tol, max_iter, d_trace, words.dev);
+            solve_kernel<<<B, 256, 0, c->stream>>>(momq, tb.pairs, set.prep, T, tb.out, tol, max_iter, d_trace, words.dev);
             HGMM_HIP(c, hipGetLastError());
             ++enq;
             spins = 0;
@@ -476,7 +420,7 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
     std::vector<double> trace_host(trace ? (size_t)13 * max_iter * B : 0);
     {
         StagedDownloads dl(c);
-        dl.add(tab.data(), d_tab, sizeof(ForestRegPair) * B);
+        dl.add(tab.data(), tb.pairs, sizeof(ForestRegPair) * B);
         if (trace) dl.add(trace_host.data(), d_trace, trace_bytes);
         HGMM_HIP(c, dl.finish());
     }
@@ -489,6 +433,117 @@ int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg
         if (pr.has_q) q_prev_inout[b] = pr.q_prev;
         if (trace) std::memcpy(trace + (size_t)13 * max_iter * b, trace_host.data() + (size_t)13 * max_iter * b, sizeof(double) * 13 * (size_t)pr.it);
     }
+    return HGMM_OK;
+}
+
+// The registration loop of a set with the 6 x 6 solves on the host (the default): per iteration one E-step launch and one
+// normal-equations launch for all registrations still running, each one's 28 numbers solved as soon as its sequence word
+// arrives.  (register_set has opened the sums: every iteration's normal-equations kernel zeroes the words it read.)
+static int forest_register_on_host(hgmm_ctx* c, const RegSet& set, double* rot, double* t, double scale, double lambda_c,
+                                   int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
+                                   double* trace) {
+    const int B = set.B(), T = set.T;
+    HandOver* hand = nullptr;
+    HGMM_TRY(hand_over(c, B, &hand));
+    const HostDev<unsigned long long> words = hand->sequence(0);
+    const HostDev<double> h_out = hand->out28(0);
+    RegTable tb;
+    HGMM_TRY(reg_table(c, *set.table, B, &tb));
+    const auto estep_kernel = reg_estep_kernel_for(c, set);
+    const auto normal_kernel = set.shared_tree ? forest_reg_normal_kernel<true> : forest_reg_normal_kernel<false>;
+    unsigned long long* momq = set.momq->as<unsigned long long>();
+    std::vector<ForestRegPair> tab(B);
+    std::vector<char> active(B, 1);
+    for (int b = 0; b < B; ++b) {
+        iters_out[b] = 0;
+        status_out[b] = 0;                                        // 0: budget used up, 1: |dq| < tol, 2: host M-step needed
+    }
+    const unsigned gx = set.gx();
+    int n_active = B;
+    for (int it = 0; it < max_iter && n_active > 0; ++it) {
+        for (int b = 0; b < B; ++b) {
+            tab[b] = reg_pair(set.regs[b]);
+            if (active[b]) reg_pair_fill(tab[b], rigid_from(rot + 9 * b, t + 3 * b, scale), set.regs[b]);
+        }
+        HGMM_TRY(stage_h2d(c, tb.pairs, tab.data(), sizeof(ForestRegPair) * B));
+        const unsigned long long seq = ++hand->seq;
+        {
+            ProfScope prof(c, HGMM_K_TREE_REG);
+            estep_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, T, set.L, lambda_c, momq,
+                                                                 (int)gx, c->tree.reg_gate, set.w);
+        }
+        normal_kernel<<<B, 256, 0, c->stream>>>(momq, tb.pairs, set.prep, T, tb.out, h_out.dev, words.dev, seq);
+        HGMM_HIP(c, hipGetLastError());
+        // every active registration's normal equations arrive with its own sequence word; each is solved as soon as it is there
+        std::vector<char> pending(active);
+        int n_pending = n_active;
+        unsigned spins = 0;
+        while (n_pending > 0) {
+            bool progressed = false;
+            unsigned long long seen = 0;                   // signature of the sequence words as this pass read them
+            for (int b = 0; b < B; ++b) {
+                const unsigned long long w = __atomic_load_n(words.host + b, __ATOMIC_ACQUIRE);
+                seen += w;
+                if (!pending[b] || w != seq) continue;
+                pending[b] = 0;
+                --n_pending;
+                progressed = true;
+                double q = 0.0;
+                const int stp = reg_host_step(h_out.host + 28 * b, rot + 9 * b, t + 3 * b, q_prev_inout + b, tol, &q);
+                if (stp == 2) { status_out[b] = 2; active[b] = 0; --n_active; continue; }
+                if (trace) {
+                    double* tr = trace + ((size_t)b * max_iter + it) * 13;
+                    for (int i = 0; i < 9; ++i) tr[i] = rot[9 * b + i];
+                    for (int i = 0; i < 3; ++i) tr[9 + i] = t[3 * b + i];
+                    tr[12] = q;
+                }
+                iters_out[b] = it + 1;
+                if (stp == 1) { status_out[b] = 1; active[b] = 0; --n_active; }
+            }
+            if (progressed) { spins = 0; continue; }
+            HGMM_TRY(device_watch(c, &spins, words.host, B, seen, "registration (batch): the normal-equation kernel (sequence %llu)", seq));
+        }
+    }
+    return HGMM_OK;
+}
+
+int register_set(hgmm_ctx* c, const RegSet& set, double* rot, double* t, double scale, double lambda_c, int max_iter, double tol,
+                 double* q_prev_inout, int32_t* iters_out, int32_t* status_out, double* trace) {
+    MomqScope sums(*set.momq_clean);               // (one memset at the most; every later iteration finds the words zero)
+    HGMM_TRY(sums.open(c, *set.momq, set.momq_bytes));
+    const auto loop = c->cfg[CFG_REG_DEVICE_SOLVE] ? forest_register_on_device : forest_register_on_host;
+    HGMM_TRY(loop(c, set, rot, t, scale, lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out, trace));
+    sums.consumed();                               // every iteration's normal-equations / solve kernel zeroed what its E-step had added
+    return HGMM_OK;
+}
+
+int score_set(hgmm_ctx* c, const RegSet& set, const double* rot, const double* t, double scale, double lambda_c,
+              double maha2_max, double* summary_out) {
+    const int B = set.B();
+    RegTable tb;
+    HGMM_TRY(reg_table(c, *set.table, B, &tb));
+    std::vector<ForestRegPair> tab(B);
+    for (int b = 0; b < B; ++b) {
+        tab[b] = reg_pair(set.regs[b]);
+        tab[b].tf = rigid_from(rot ? rot + 9 * b : nullptr, t ? t + 3 * b : nullptr, scale);
+    }
+    const unsigned gx = set.gx();
+    HGMM_TRY(ensure(c, c->scratch, sizeof(double) * ((size_t)SCORE_NSUM * gx + 8) * B));
+    double* partial = c->scratch.as<double>();
+    double* d_sum = partial + (size_t)SCORE_NSUM * gx * B;
+    HGMM_TRY(stage_h2d(c, tb.pairs, tab.data(), sizeof(ForestRegPair) * B));
+    {
+        ProfScope prof(c, HGMM_K_TREE_SCORE);
+        const auto kernel = set.shared_tree ? (set.w ? forest_score_kernel<true, true> : forest_score_kernel<true, false>)
+                                            : (set.w ? forest_score_kernel<false, true> : forest_score_kernel<false, false>);
+        kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, set.T, set.L, lambda_c, maha2_max,
+                                                      partial, (int)gx, set.w);
+    }
+    forest_score_finish_kernel<<<B, CH, 0, c->stream>>>(partial, tb.pairs, (int)gx, d_sum);
+    HGMM_HIP(c, hipGetLastError());
+    StagedDownloads dl(c);
+    dl.add(summary_out, d_sum, sizeof(double) * 8 * B);
+    HGMM_HIP(c, dl.finish());
     return HGMM_OK;
 }
 
@@ -790,10 +845,9 @@ static int set_targets_batch(hgmm_ctx* c, int B, const IN* const* xyz, const int
     const int64_t pad = (total + 255) / 256 * 256;
     HGMM_TRY(ensure(c, c->fr_tg, sizeof(double) * 3 * pad));
     HGMM_TRY(ensure(c, c->scratch, sizeof(IN) * 3 * (size_t)total));
-    HGMM_TRY(ensure(c, c->fr_reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
-    // layout of fr_reg: [pairs table][28 B doubles][B r2max words]
-    unsigned long long* r2bits = reinterpret_cast<unsigned long long*>(c->fr_reg.as<char>() +
-                                                                     (sizeof(ForestRegPair) + 28 * sizeof(double)) * (size_t)B);
+    RegTable tb;
+    HGMM_TRY(reg_table(c, c->fr_reg, B, &tb));
+    unsigned long long* r2bits = tb.r2max;
     HGMM_HIP(c, hipMemsetAsync(r2bits, 0, sizeof(unsigned long long) * B, c->stream));
     F.tg_counts.assign(counts, counts + B);
     F.tg_first.assign(B, 0);
@@ -831,8 +885,7 @@ extern "C" int hgmm_tree_set_targets_batch_f32(hgmm_ctx* c, int B, const float* 
     return set_targets_batch<float>(c, B, xyz, counts);
 }
 
-// per-point weights of the resident targets (include/hgmm.h): fr_tg_w [tg_pad] parallel to fr_tg; an unweighted pair of a
-// weighted batch gets 1.0 per point and its count as the sum -- gamma * 1.0 is gamma, so it keeps its unweighted bits
+// per-point weights of the resident targets (include/hgmm.h): fr_tg_w [tg_pad] parallel to fr_tg (upload_weights)
 extern "C" int hgmm_tree_set_target_weights_batch(hgmm_ctx* c, int B, const double* const* w, const int64_t* counts) {
     HGMM_ENTER(c);
     const char* what = "hgmm_tree_set_target_weights_batch";
@@ -841,37 +894,12 @@ extern "C" int hgmm_tree_set_target_weights_batch(hgmm_ctx* c, int B, const doub
     if (!w) { F.tg_weighted = false; return HGMM_OK; }
     if (B != F.tg_B) return fail(c, HGMM_ERR_ARG, "%s: B = %d, but %d targets are resident", what, B, F.tg_B);
     if (!counts) return fail(c, HGMM_ERR_ARG, "%s: counts is NULL", what);
-    std::vector<double> sums(B), padded((size_t)F.tg_pad, 0.0);
-    bool any = false;
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] != F.tg_counts[b])
-            return fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident target %d has %lld points", what, b,
-                        (long long)counts[b], b, (long long)F.tg_counts[b]);
-        double* dst = padded.data() + F.tg_first[b];
-        if (!w[b]) {
-            std::fill(dst, dst + counts[b], 1.0);
-            sums[b] = (double)counts[b];
-            continue;
-        }
-        char label[96];
-        snprintf(label, sizeof label, "%s (target %d)", what, b);
-        HGMM_TRY(check_target_weights(c, label, w[b], counts[b], &sums[b]));
-        std::copy(w[b], w[b] + counts[b], dst);
-        any = true;
-    }
-    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
-    F.tg_weighted = false;
-    if (!any) return HGMM_OK;
-    HGMM_TRY(ensure(c, c->fr_tg_w, sizeof(double) * padded.size()));
-    HGMM_HIP(c, hipMemcpyAsync(c->fr_tg_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
-    HGMM_HIP(c, ctx_stream_sync(c));
-    F.tg_wsum = sums;
-    F.tg_weighted = true;
-    return HGMM_OK;
+    F.tg_wsum.resize(B);                               // (sums in force have this length already: they keep their values)
+    return upload_weights(c, what, "target", true, B, w, counts, F.tg_counts.data(), F.tg_pad, c->fr_tg_w, F.tg_wsum.data(),
+                          &F.tg_weighted);
 }
 
-// per-point weights of the resident forest cloud (include/hgmm.h): fr_src_w [n_pad] parallel to x_soa64; an unweighted cloud of
-// a weighted batch gets 1.0 per point and its count as the sum, so that it keeps its unweighted bits
+// per-point weights of the resident forest cloud (include/hgmm.h): fr_src_w [n_pad] parallel to x_soa64 (upload_weights)
 extern "C" int hgmm_tree_set_source_weights_batch(hgmm_ctx* c, int B, const double* const* w, const int64_t* counts) {
     HGMM_ENTER(c);
     const char* what = "hgmm_tree_set_source_weights_batch";
@@ -882,114 +910,9 @@ extern "C" int hgmm_tree_set_source_weights_batch(hgmm_ctx* c, int B, const doub
     if (B != (int)F.src_counts.size())
         return fail(c, HGMM_ERR_ARG, "%s: B = %d, but %d clouds are resident", what, B, (int)F.src_counts.size());
     if (!counts) return fail(c, HGMM_ERR_ARG, "%s: counts is NULL", what);
-    std::vector<double> sums(B), padded((size_t)c->n_pad, 0.0);
-    bool any = false;
-    int64_t at = 0;
-    for (int b = 0; b < B; ++b) {
-        if (counts[b] != F.src_counts[b])
-            return fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident cloud %d has %lld points", what, b,
-                        (long long)counts[b], b, (long long)F.src_counts[b]);
-        double* dst = padded.data() + at;
-        at += counts[b];
-        if (!w[b]) {
-            std::fill(dst, dst + counts[b], 1.0);
-            sums[b] = (double)counts[b];
-            continue;
-        }
-        char label[96];
-        snprintf(label, sizeof label, "%s (cloud %d)", what, b);
-        HGMM_TRY(check_target_weights(c, label, w[b], counts[b], &sums[b]));
-        std::copy(w[b], w[b] + counts[b], dst);
-        any = true;
-    }
-    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
-    F.src_weighted = false;
-    if (!any) return HGMM_OK;
-    HGMM_TRY(ensure(c, c->fr_src_w, sizeof(double) * padded.size()));
-    HGMM_HIP(c, hipMemcpyAsync(c->fr_src_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
-    HGMM_HIP(c, ctx_stream_sync(c));
-    F.src_wsum = sums;
-    F.src_weighted = true;
-    return HGMM_OK;
-}
-
-// The registration loop of B pairs with the 6 x 6 solves on the host (the default): per iteration one E-step launch and one
-// normal-equations launch for all pairs still running, each pair's 28 numbers solved as soon as its sequence word arrives.
-// The arguments are forest_register_on_device's; `momq` / `momq_clean`: the set's sums and their MomqScope flag.
-static int forest_register_on_host(hgmm_ctx* c, int B, const double* tg, int64_t tg_pad, const int64_t* tg_first,
-                                   const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
-                                   int L, DevBuf& momq, bool& momq_clean, double* rot, double* t, double scale, double lambda_c,
-                                   int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                                   double* trace, bool shared_tree, DevBuf& reg, const double* tg_w, const double* tg_wsum) {
-    const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
-    HandOver* hand = nullptr;
-    HGMM_TRY(hand_over(c, B, &hand));
-    const HostDev<unsigned long long> words = hand->sequence(0);
-    const HostDev<double> h_out = hand->out28(0);
-    HGMM_TRY(ensure(c, reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
-    const double gate = c->tree.reg_gate;                    // (hgmm_tree_set_reg_gate; finite: the gated instantiations)
-    const auto estep_kernel = reg_estep_kernel_for(shared_tree, std::isfinite(gate), tg_w != nullptr);
-    const auto normal_kernel = shared_tree ? tree_reg_multi_normal_kernel : forest_reg_normal_kernel;
-    ForestRegPair* d_tab = reg.as<ForestRegPair>();
-    double* d_out = reinterpret_cast<double*>(d_tab + B);
-    std::vector<ForestRegPair> tab(B);
-    std::vector<char> active(B, 1);
-    int64_t longest = 0;
-    for (int b = 0; b < B; ++b) {
-        iters_out[b] = 0;
-        status_out[b] = 0;                                        // 0: budget used up, 1: |dq| < tol, 2: host M-step needed
-        longest = std::max(longest, tg_counts[b]);
-    }
-    int n_active = B;
-    for (int it = 0; it < max_iter && n_active > 0; ++it) {
-        for (int b = 0; b < B; ++b) {
-            tab[b] = reg_pair(tg_first[b], tg_counts[b], tg_w ? tg_wsum : nullptr, b);
-            if (active[b]) reg_pair_fill(tab[b], rigid_from(rot + 9 * b, t + 3 * b, scale), tg_rmax[b], mu_rmax[b]);
-        }
-        HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
-        const unsigned long long seq = ++hand->seq;
-        MomqScope sums(momq_clean);                  // (one memset before the first iteration; every later one finds the words zero)
-        HGMM_TRY(sums.open(c, momq, momq_bytes));
-        {
-            ProfScope prof(c, HGMM_K_TREE_REG);
-            estep_kernel<<<nblk(longest, CH) * (unsigned)B, CH, 0, c->stream>>>(tg, tg_pad, d_tab, prep, T, L, lambda_c,
-                                                                                momq.as<unsigned long long>(), (int)nblk(longest, CH),
-                                                                                gate, tg_w);
-        }
-        normal_kernel<<<B, 256, 0, c->stream>>>(momq.as<unsigned long long>(), d_tab, prep, T, d_out, h_out.dev, words.dev, seq);
-        HGMM_HIP(c, hipGetLastError());
-        // every active pair's normal equations arrive with its own sequence word; each is solved as soon as it is there
-        std::vector<char> pending(active);
-        int n_pending = n_active;
-        unsigned spins = 0;
-        while (n_pending > 0) {
-            bool progressed = false;
-            unsigned long long seen = 0;                   // signature of the sequence words as this pass read them
-            for (int b = 0; b < B; ++b) {
-                const unsigned long long w = __atomic_load_n(words.host + b, __ATOMIC_ACQUIRE);
-                seen += w;
-                if (!pending[b] || w != seq) continue;
-                pending[b] = 0;
-                --n_pending;
-                progressed = true;
-                double q = 0.0;
-                const int stp = reg_host_step(h_out.host + 28 * b, rot + 9 * b, t + 3 * b, q_prev_inout + b, tol, &q);
-                if (stp == 2) { status_out[b] = 2; active[b] = 0; --n_active; continue; }
-                if (trace) {
-                    double* tr = trace + ((size_t)b * max_iter + it) * 13;
-                    for (int i = 0; i < 9; ++i) tr[i] = rot[9 * b + i];
-                    for (int i = 0; i < 3; ++i) tr[9 + i] = t[3 * b + i];
-                    tr[12] = q;
-                }
-                iters_out[b] = it + 1;
-                if (stp == 1) { status_out[b] = 1; active[b] = 0; --n_active; }
-            }
-            if (progressed) { spins = 0; continue; }
-            HGMM_TRY(device_watch(c, &spins, words.host, B, seen, "registration (batch): the normal-equation kernel (sequence %llu)", seq));
-        }
-        sums.consumed();                               // every active pair has reported: its kernel zeroed the words it read
-    }
-    return HGMM_OK;
+    F.src_wsum.resize(B);                              // (sums in force have this length already: they keep their values)
+    return upload_weights(c, what, "cloud", true, B, w, counts, F.src_counts.data(), c->n_pad, c->fr_src_w, F.src_wsum.data(),
+                          &F.src_weighted);
 }
 
 extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double* t, double scale, double lambda_c,
@@ -997,28 +920,11 @@ extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double*
                                         int32_t* status_out, double* trace) {
     HGMM_ENTER(c);
     if (!rot || !t || !q_prev_inout || !iters_out || !status_out) return fail(c, HGMM_ERR_ARG, "tree_register (batch): NULL argument");
-    ForestState& F = c->forest;
+    const ForestState& F = c->forest;
     if (!F.nodes_ready) return fail(c, HGMM_ERR_STATE, "registration (batch): no forest (hgmm_tree_build_batch first)");
     if (B != F.B || B != F.tg_B)
         return fail(c, HGMM_ERR_STATE, "registration (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
-    const int T = F.T, L = F.L;
-    const size_t momq_bytes = sizeof(unsigned long long) * 4 * (size_t)T * B;
-    const double* tg_w = F.tg_weighted ? c->fr_tg_w.as<double>() : nullptr;      // (hgmm_tree_set_target_weights_batch)
-    const double* tg_wsum = F.tg_weighted ? F.tg_wsum.data() : nullptr;
-    if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
-        MomqScope sums(F.momq_clean);
-        HGMM_TRY(sums.open(c, c->fr_momq, momq_bytes));
-        HGMM_TRY(forest_register_on_device(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(),
-                                           F.tg_rmax.data(), F.mu_rmax.data(), c->fr_prep.as<double>(), T, L,
-                                           c->fr_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, iters_out, status_out, trace, false, nullptr, tg_w, tg_wsum));
-        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
-        return HGMM_OK;
-    }
-    return forest_register_on_host(c, B, c->fr_tg.as<double>(), F.tg_pad, F.tg_first.data(), F.tg_counts.data(), F.tg_rmax.data(),
-                                   F.mu_rmax.data(), c->fr_prep.as<double>(), T, L, c->fr_momq, F.momq_clean, rot, t, scale,
-                                   lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out, trace, false, c->fr_reg, tg_w,
-                                   tg_wsum);
+    return register_set(c, reg_set_forest(c), rot, t, scale, lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out, trace);
 }
 
 // hgmm_tree_score on every pair (tree b, target b) of the resident forest, summaries only: include/hgmm.h
@@ -1028,36 +934,11 @@ extern "C" int hgmm_tree_score_batch(hgmm_ctx* c, int B, const double* rot, cons
     if (!summary_out) return fail(c, HGMM_ERR_ARG, "tree_score (batch): summary_out is NULL");
     if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "tree_score (batch): maha2_max is NaN");
     if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "tree_score (batch): independent pairs take no communicator");
-    ForestState& F = c->forest;
+    const ForestState& F = c->forest;
     if (!F.nodes_ready) return fail(c, HGMM_ERR_STATE, "tree_score (batch): no forest (hgmm_tree_build_batch first)");
     if (B != F.B || B != F.tg_B)
         return fail(c, HGMM_ERR_STATE, "tree_score (batch): %d pairs, but %d trees and %d targets are resident", B, F.B, F.tg_B);
-    const int T = F.T, L = F.L;
-    ForestRegPair* d_tab = c->fr_reg.as<ForestRegPair>();          // (sized for B pairs by hgmm_tree_set_targets_batch)
-    std::vector<ForestRegPair> tab(B);
-    int64_t longest = 0;
-    for (int b = 0; b < B; ++b) {
-        tab[b] = reg_pair(F.tg_first[b], F.tg_counts[b], F.tg_weighted ? F.tg_wsum.data() : nullptr, b);
-        tab[b].tf = rigid_from(rot ? rot + 9 * b : nullptr, t ? t + 3 * b : nullptr, scale);
-        longest = std::max(longest, F.tg_counts[b]);
-    }
-    const unsigned gx = nblk(longest, CH);
-    HGMM_TRY(ensure(c, c->scratch, sizeof(double) * ((size_t)SCORE_NSUM * gx + 8) * B));
-    double* partial = c->scratch.as<double>();
-    double* d_sum = partial + (size_t)SCORE_NSUM * gx * B;
-    HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * B));
-    {
-        ProfScope prof(c, HGMM_K_TREE_SCORE);
-        const auto kernel = F.tg_weighted ? forest_score_kernel<true> : forest_score_kernel<false>;
-        kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(c->fr_tg.as<double>(), F.tg_pad, d_tab, c->fr_prep.as<double>(), T, L,
-                                                      lambda_c, maha2_max, partial, (int)gx,
-                                                      F.tg_weighted ? c->fr_tg_w.as<double>() : nullptr);
-    }
-    forest_score_finish_kernel<<<B, CH, 0, c->stream>>>(partial, d_tab, (int)gx, d_sum);
-    HGMM_HIP(c, hipGetLastError());
-    HGMM_HIP(c, hipMemcpyAsync(summary_out, d_sum, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, c->stream));
-    HGMM_HIP(c, ctx_stream_sync(c));
-    return HGMM_OK;
+    return score_set(c, reg_set_forest(c), rot, t, scale, lambda_c, maha2_max, summary_out);
 }
 
 // ---- multi-start: K start poses of the SERIAL pair (hgmm_tree_build / _set_nodes + hgmm_tree_set_target): include/hgmm.h ------
@@ -1080,27 +961,8 @@ extern "C" int hgmm_tree_register_multi(hgmm_ctx* c, int K, double* rot, double*
     if (!rot || !t) return fail(c, HGMM_ERR_ARG, "tree_register (multi): rot / t is NULL (K start poses are the call's input)");
     if (!q_prev_inout || !iters_out || !status_out) return fail(c, HGMM_ERR_ARG, "tree_register (multi): NULL output argument");
     HGMM_TRY(tree_mu_rmax_resident(c));
-    const int T = c->tree.T, L = c->tree.L;
-    // every hypothesis names the same target and the same tree: the loops and reg_pair_fill take them per registration
-    const std::vector<int64_t> first(K, 0), counts(K, c->tgt_n);
-    const std::vector<double> tg_rmax(K, c->tgt_rmax), mu_rmax(K, c->tree.mu_rmax);
-    const double* tg = c->tgt_soa64.as<double>();
-    const double* prep = c->t_prep.as<double>();
-    // (hgmm_tree_set_target_weights: the K hypotheses share the one weight array and its sum)
-    const double* tg_w = c->tgt_weighted ? c->tgt_w.as<double>() : nullptr;
-    const std::vector<double> tg_wsum(K, c->tgt_wsum);
-    if (c->cfg[CFG_REG_DEVICE_SOLVE]) {
-        MomqScope sums(c->tree.multi_momq_clean);
-        HGMM_TRY(sums.open(c, c->tm_momq, sizeof(unsigned long long) * 4 * (size_t)T * K));
-        HGMM_TRY(forest_register_on_device(c, K, tg, c->tgt_pad, first.data(), counts.data(), tg_rmax.data(), mu_rmax.data(), prep,
-                                           T, L, c->tm_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, iters_out, status_out, trace, true, &c->tm_reg, tg_w, tg_wsum.data()));
-        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
-        return HGMM_OK;
-    }
-    return forest_register_on_host(c, K, tg, c->tgt_pad, first.data(), counts.data(), tg_rmax.data(), mu_rmax.data(), prep, T, L,
-                                   c->tm_momq, c->tree.multi_momq_clean, rot, t, scale, lambda_c, max_iter, tol, q_prev_inout,
-                                   iters_out, status_out, trace, true, c->tm_reg, tg_w, tg_wsum.data());
+    return register_set(c, reg_set_pair(c, K, true), rot, t, scale, lambda_c, max_iter, tol, q_prev_inout, iters_out, status_out,
+                        trace);
 }
 
 extern "C" int hgmm_tree_score_multi(hgmm_ctx* c, int K, const double* rot, const double* t, double scale, double lambda_c,
@@ -1110,30 +972,5 @@ extern "C" int hgmm_tree_score_multi(hgmm_ctx* c, int K, const double* rot, cons
     if (!rot || !t) return fail(c, HGMM_ERR_ARG, "tree_score (multi): rot / t is NULL (K poses are the call's input)");
     if (!summary_out) return fail(c, HGMM_ERR_ARG, "tree_score (multi): summary_out is NULL");
     if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "tree_score (multi): maha2_max is NaN");
-    const int64_t n = c->tgt_n;
-    const unsigned gx = nblk(n, CH);
-    std::vector<ForestRegPair> tab(K);
-    for (int k = 0; k < K; ++k) {
-        tab[k] = reg_pair(0, n);
-        tab[k].tf = rigid_from(rot + 9 * k, t + 3 * k, scale);
-    }
-    HGMM_TRY(ensure(c, c->tm_reg, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)K + 512));
-    HGMM_TRY(ensure(c, c->scratch, sizeof(double) * ((size_t)SCORE_NSUM * gx + 8) * K));
-    ForestRegPair* d_tab = c->tm_reg.as<ForestRegPair>();
-    double* partial = c->scratch.as<double>();
-    double* d_sum = partial + (size_t)SCORE_NSUM * gx * K;
-    HGMM_TRY(stage_h2d(c, d_tab, tab.data(), sizeof(ForestRegPair) * K));
-    {
-        ProfScope prof(c, HGMM_K_TREE_SCORE);
-        const auto kernel = c->tgt_weighted ? tree_score_multi_kernel<true> : tree_score_multi_kernel<false>;
-        kernel<<<gx * (unsigned)K, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, c->tgt_pad, d_tab, c->t_prep.as<double>(),
-                                                      c->tree.L, lambda_c, maha2_max, partial, (int)gx,
-                                                      c->tgt_weighted ? c->tgt_w.as<double>() : nullptr);
-    }
-    tree_score_multi_finish_kernel<<<K, CH, 0, c->stream>>>(partial, (int)gx, c->tgt_weighted ? c->tgt_wsum : (double)n, d_sum);
-    HGMM_HIP(c, hipGetLastError());
-    StagedDownloads dl(c);
-    dl.add(summary_out, d_sum, sizeof(double) * 8 * K);
-    HGMM_HIP(c, dl.finish());
-    return HGMM_OK;
+    return score_set(c, reg_set_pair(c, K, true), rot, t, scale, lambda_c, maha2_max, summary_out);
 }

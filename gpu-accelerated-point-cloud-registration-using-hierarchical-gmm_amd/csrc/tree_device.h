@@ -2212,17 +2212,6 @@ __device__ inline void reg_device_step(const double* __restrict__ o, ForestRegPa
     pr->inv_scale = ldexp(1.0, -F);
 }
 
-// the registration loop on the device alone (tree_batch.hip; hgmm_tree_register uses it with B = 1 on the serial buffers).
-// shared_tree: the B registrations are start poses of ONE pair (hgmm_tree_register_multi) -- `prep` is one tree's table and
-// every entry of tg_first / tg_counts names the same target; `table` (NULL: fr_reg) holds the B entries and 28 B numbers.
-// tg_w (device, parallel to tg; NULL: no weights) / tg_wsum (host [B], with tg_w): hgmm_tree_set_target_weights[_batch].
-int forest_register_on_device(::hgmm_ctx* c, int B, const double* tg, int64_t tg_pad, const int64_t* tg_first,
-                              const int64_t* tg_counts, const double* tg_rmax, const double* mu_rmax, const double* prep, int T,
-                              int L, unsigned long long* momq, double* rot, double* t, double scale, double lambda_c,
-                              int max_iter, double tol, double* q_prev_inout, int32_t* iters_out, int32_t* status_out,
-                              double* trace, bool shared_tree = false, hgmm::DevBuf* table = nullptr,
-                              const double* tg_w = nullptr, const double* tg_wsum = nullptr);
-
 // ---- kernels defined in tree_kernels.hip that the batched path (tree_batch.hip) launches as they are -----------------
 constexpr int OFF_BLOCK = 256;
 __global__ void tree_prep_kernel(const double* __restrict__ pi, const double* __restrict__ mu,

@@ -122,33 +122,6 @@ inline Rigid rigid_from(const double* rot, const double* t, double scale) {
     tf.s = scale;
     return tf;
 }
-// a pair's table entry: its target's slice, everything else zero (a pair that takes no part)
-// (tg_wsum: the targets' weight sums, NULL without weights -- the count then, as a double)
-inline ForestRegPair reg_pair(int64_t tg_first, int64_t tg_count, const double* tg_wsum = nullptr, int b = 0) {
-    ForestRegPair pr;
-    std::memset(&pr, 0, sizeof pr);
-    pr.tg_first = (int)tg_first;
-    pr.tg_count = (int)tg_count;
-    pr.tg_wsum = tg_wsum ? tg_wsum[b] : (double)tg_count;
-    return pr;
-}
-// ... of a pair that takes part: its transform and the fixed-point encoding of its next E-step
-inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, double tg_rmax, double mu_rmax) {
-    pr.active = 1;
-    pr.tf = tf;
-    double D = 1.0;
-    int F = 0;
-    reg_encoding(reg_extent(tf, tg_rmax, mu_rmax), pr.tg_wsum, &D, &F);
-    pr.inv_d = 1.0 / D;
-    pr.fix_scale = std::ldexp(1.0, F);
-    pr.d_ext = D;
-    pr.inv_scale = std::ldexp(1.0, -F);
-    pr.tg_rmax = tg_rmax;
-    pr.mu_rmax = mu_rmax;
-}
-// (tree_kernels.hip) one cloud's weights for hgmm_tree_set_target_weights[_batch] and hgmm_tree_set_source_weights[_batch]:
-// finite, >= 0, not all zero; their sum
-int check_target_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out);
 // largest |mu_j| of the resident tree; a tree built on the device has not shown its means to the host yet
 inline int tree_mu_rmax_resident(hgmm_ctx* c) {
     if (c->tree.mu_rmax >= 0.0) return HGMM_OK;
@@ -159,5 +132,124 @@ inline int tree_mu_rmax_resident(hgmm_ctx* c) {
     c->tree.mu_rmax = tree_mu_rmax(mu.data(), T);
     return HGMM_OK;
 }
+
+// ---- a set of B registrations: what the E-step, normal-equation, solve and score launches of tree_batch.hip work on ------
+// Either the pairs of the resident forest (hgmm_tree_register_batch / _score_batch) or B start poses of the serial pair
+// (hgmm_tree_register_multi / _score_multi; hgmm_tree_register's device loop with B = 1).
+struct RegSet {
+    struct One {
+        int64_t first, count;                  // its target's slice of `tg`
+        double rmax, mu_rmax;                  // largest |x| of the target, largest |mu_j| of the tree: reg_extent
+        double wsum;                           // sum of the target's weights; (double)count without
+    };
+    bool shared_tree = false;                  // one tree and one target for all (the SHARED kernels): prep is [T], not [B][T]
+    std::vector<One> regs;                     // [B]
+    const double* tg = nullptr;                // device: the targets' structure of arrays [3][tg_pad]
+    int64_t tg_pad = 0;
+    const double* w = nullptr;                 // device, parallel to tg: the targets' weights; NULL: none
+    const double* prep = nullptr;              // device: the node tables
+    int T = 0, L = 0;
+    DevBuf* momq = nullptr;                    // the fixed-point sums, slice b = [T][4] ...
+    bool* momq_clean = nullptr;                // ... their MomqScope flag ...
+    size_t momq_bytes = 0;                     // ... and what a use opens them at
+    DevBuf* table = nullptr;                   // RegTable
+    int B() const { return (int)regs.size(); }
+    unsigned gx() const {                      // chunks of the longest target: the launches are gx x B workgroups
+        int64_t longest = 0;
+        for (const One& r : regs) longest = std::max(longest, r.count);
+        return nblk(longest, CH);
+    }
+};
+// the resident forest's pairs (the caller has checked nodes_ready and B == F.B == F.tg_B)
+inline RegSet reg_set_forest(hgmm_ctx* c) {
+    const ForestState& F = c->forest;
+    RegSet s;
+    for (int b = 0; b < F.B; ++b)
+        s.regs.push_back({F.tg_first[b], F.tg_counts[b], F.tg_rmax[b], F.mu_rmax[b],
+                          F.tg_weighted ? F.tg_wsum[b] : (double)F.tg_counts[b]});
+    s.tg = c->fr_tg.as<double>();
+    s.tg_pad = F.tg_pad;
+    s.w = F.tg_weighted ? c->fr_tg_w.as<double>() : nullptr;
+    s.prep = c->fr_prep.as<double>();
+    s.T = F.T;
+    s.L = F.L;
+    s.momq = &c->fr_momq;
+    s.momq_clean = &c->forest.momq_clean;
+    s.momq_bytes = sizeof(unsigned long long) * 4 * (size_t)F.T * F.B;
+    s.table = &c->fr_reg;
+    return s;
+}
+// K start poses of the serial pair (the caller has checked the tree and the target; tree.mu_rmax: tree_mu_rmax_resident,
+// which the score does not need).  multi: on tm_momq / tm_reg, which leaves the serial call's state alone; otherwise
+// hgmm_tree_register's own buffers, K = 1 -- t_momq at the [T][NMOM] words every other use of it opens it at, and fr_reg.
+inline RegSet reg_set_pair(hgmm_ctx* c, int K, bool multi) {
+    RegSet s;
+    s.shared_tree = true;
+    s.regs.assign(K, {0, c->tgt_n, c->tgt_rmax, c->tree.mu_rmax, c->tgt_weighted ? c->tgt_wsum : (double)c->tgt_n});
+    s.tg = c->tgt_soa64.as<double>();
+    s.tg_pad = c->tgt_pad;
+    s.w = c->tgt_weighted ? c->tgt_w.as<double>() : nullptr;
+    s.prep = c->t_prep.as<double>();
+    s.T = c->tree.T;
+    s.L = c->tree.L;
+    s.momq = multi ? &c->tm_momq : &c->t_momq;
+    s.momq_clean = multi ? &c->tree.multi_momq_clean : &c->tree.momq_clean;
+    s.momq_bytes = sizeof(unsigned long long) * (multi ? 4 * (size_t)K : (size_t)NMOM) * s.T;
+    s.table = multi ? &c->tm_reg : &c->fr_reg;
+    return s;
+}
+// (tree_batch.hip) up to max_iter iterations of every registration of the set from (rot [B][9], t [B][3]), on the host's
+// solve or -- reg_device_solve -- the device's; the arguments are hgmm_tree_register_batch's.  Opens and closes the sums.
+int register_set(hgmm_ctx* c, const RegSet& set, double* rot, double* t, double scale, double lambda_c, int max_iter, double tol,
+                 double* q_prev_inout, int32_t* iters_out, int32_t* status_out, double* trace);
+// (tree_batch.hip) hgmm_tree_score's summary of every registration of the set at (rot, t; NULL: identity) -> summary_out [B][8]
+int score_set(hgmm_ctx* c, const RegSet& set, const double* rot, const double* t, double scale, double lambda_c,
+              double maha2_max, double* summary_out);
+
+// the device table of B registrations: [B entries][28 B doubles: the normal equations][B words: forest_target_kernel's r2max]
+struct RegTable {
+    ForestRegPair* pairs;
+    double* out;
+    unsigned long long* r2max;
+};
+inline int reg_table(hgmm_ctx* c, DevBuf& buf, int B, RegTable* tb) {
+    HGMM_TRY(ensure(c, buf, (sizeof(ForestRegPair) + 28 * sizeof(double) + sizeof(unsigned long long)) * (size_t)B + 512));
+    tb->pairs = buf.as<ForestRegPair>();
+    tb->out = reinterpret_cast<double*>(tb->pairs + B);
+    tb->r2max = reinterpret_cast<unsigned long long*>(tb->out + (size_t)28 * B);
+    return HGMM_OK;
+}
+// a registration's table entry: its target's slice and weight sum, everything else zero (one that takes no part)
+inline ForestRegPair reg_pair(const RegSet::One& r) {
+    ForestRegPair pr;
+    std::memset(&pr, 0, sizeof pr);
+    pr.tg_first = (int)r.first;
+    pr.tg_count = (int)r.count;
+    pr.tg_wsum = r.wsum;
+    return pr;
+}
+// ... of one that takes part: its transform and the fixed-point encoding of its next E-step
+inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, const RegSet::One& r) {
+    pr.active = 1;
+    pr.tf = tf;
+    double D = 1.0;
+    int F = 0;
+    reg_encoding(reg_extent(tf, r.rmax, r.mu_rmax), pr.tg_wsum, &D, &F);
+    pr.inv_d = 1.0 / D;
+    pr.fix_scale = std::ldexp(1.0, F);
+    pr.d_ext = D;
+    pr.inv_scale = std::ldexp(1.0, -F);
+    pr.tg_rmax = r.rmax;
+    pr.mu_rmax = r.mu_rmax;
+}
+// (tree_kernels.hip) what the four weight entries (hgmm_tree_set_target_weights[_batch], hgmm_tree_set_source_weights[_batch])
+// do once their own state checks have passed and w is not NULL.  `what`: the entry's name; `noun`: "target" / "cloud";
+// batch: the messages name the member (the serial entries: B = 1, no index).  The B members lie back to back in an array of
+// `pad` doubles, resident[b] points each.  In this order: counts[b] against resident[b]; every w[b] finite, >= 0 and not
+// all zero (a NULL member: 1.0 per point, its count as the sum -- gamma * 1.0 is gamma, so it keeps its unweighted bits);
+// a refusal up to here leaves the previous weights in force.  Then *in_force = false: what is left to fail is the device,
+// and then no weights are in force.  Upload into `dst`; sums[B] and *in_force = true (all members NULL: stays false).
+int upload_weights(hgmm_ctx* c, const char* what, const char* noun, bool batch, int B, const double* const* w,
+                   const int64_t* counts, const int64_t* resident, int64_t pad, DevBuf& dst, double* sums, bool* in_force);
 
 }  // namespace hgmm

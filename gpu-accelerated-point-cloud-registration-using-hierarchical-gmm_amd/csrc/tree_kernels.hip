@@ -1108,8 +1108,8 @@ extern "C" int hgmm_tree_set_target(hgmm_ctx* c, const double* xyz, int64_t n) {
     return HGMM_OK;
 }
 
-// what both weight entries ask of one cloud's weights: finite, >= 0, not all zero; *sum_out: their sum in index order
-int hgmm::check_target_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out) {
+// what the weight entries ask of one cloud's weights: finite, >= 0, not all zero; *sum_out: their sum in index order
+static int check_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out) {
     double sum = 0.0;
     for (int64_t i = 0; i < n; ++i) {
         if (!(w[i] >= 0.0) || !(w[i] < INFINITY))                 // (NaN fails the first comparison)
@@ -1122,25 +1122,48 @@ int hgmm::check_target_weights(hgmm_ctx* c, const char* what, const double* w, i
     return HGMM_OK;
 }
 
+// tree_host.h
+int hgmm::upload_weights(hgmm_ctx* c, const char* what, const char* noun, bool batch, int B, const double* const* w,
+                         const int64_t* counts, const int64_t* resident, int64_t pad, DevBuf& dst, double* sums, bool* in_force) {
+    std::vector<double> sum(B), padded((size_t)pad, 0.0);
+    bool any = false;
+    int64_t at = 0;
+    for (int b = 0; b < B; at += counts[b], ++b) {
+        if (counts[b] != resident[b])
+            return batch ? fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident %s %d has %lld points", what, b,
+                                (long long)counts[b], noun, b, (long long)resident[b])
+                         : fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident %s has %lld points", what,
+                                (long long)counts[b], noun, (long long)resident[b]);
+        double* slot = padded.data() + at;
+        if (!w[b]) {
+            std::fill(slot, slot + counts[b], 1.0);
+            sum[b] = (double)counts[b];
+            continue;
+        }
+        char label[96];
+        if (batch) snprintf(label, sizeof label, "%s (%s %d)", what, noun, b);
+        HGMM_TRY(check_weights(c, batch ? label : what, w[b], counts[b], &sum[b]));
+        std::copy(w[b], w[b] + counts[b], slot);
+        any = true;
+    }
+    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
+    *in_force = false;
+    if (!any) return HGMM_OK;
+    HGMM_TRY(ensure(c, dst, sizeof(double) * padded.size()));
+    HGMM_HIP(c, hipMemcpyAsync(dst.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    std::copy(sum.begin(), sum.end(), sums);
+    *in_force = true;
+    return HGMM_OK;
+}
+
+// per-point weights of the resident target (include/hgmm.h): tgt_w [tgt_pad] parallel to tgt_soa64
 extern "C" int hgmm_tree_set_target_weights(hgmm_ctx* c, const double* w, int64_t n) {
     HGMM_ENTER(c);
-    if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "hgmm_tree_set_target_weights: no target (call hgmm_tree_set_target first)");
+    const char* what = "hgmm_tree_set_target_weights";
+    if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "%s: no target (call hgmm_tree_set_target first)", what);
     if (!w) { c->tgt_weighted = false; return HGMM_OK; }
-    if (n != c->tgt_n)
-        return fail(c, HGMM_ERR_ARG, "hgmm_tree_set_target_weights: %lld weights, but the resident target has %lld points",
-                    (long long)n, (long long)c->tgt_n);
-    double sum = 0.0;
-    HGMM_TRY(check_target_weights(c, "hgmm_tree_set_target_weights", w, n, &sum));
-    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
-    c->tgt_weighted = false;
-    std::vector<double> padded((size_t)c->tgt_pad, 0.0);
-    std::copy(w, w + n, padded.begin());
-    HGMM_TRY(ensure(c, c->tgt_w, sizeof(double) * padded.size()));
-    HGMM_HIP(c, hipMemcpyAsync(c->tgt_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
-    HGMM_HIP(c, ctx_stream_sync(c));
-    c->tgt_wsum = sum;
-    c->tgt_weighted = true;
-    return HGMM_OK;
+    return upload_weights(c, what, "target", false, 1, &w, &n, &c->tgt_n, c->tgt_pad, c->tgt_w, &c->tgt_wsum, &c->tgt_weighted);
 }
 
 // per-point weights of the resident cloud (include/hgmm.h): src_w [n_pad] parallel to x_soa64; hgmm_tree_build alone reads them
@@ -1149,20 +1172,7 @@ extern "C" int hgmm_tree_set_source_weights(hgmm_ctx* c, const double* w, int64_
     const char* what = "hgmm_tree_set_source_weights";
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "%s: no cloud (set or bind points first)", what);
     if (!w) { c->src_weighted = false; return HGMM_OK; }
-    if (n != c->n)
-        return fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident cloud has %lld points", what, (long long)n, (long long)c->n);
-    double sum = 0.0;
-    HGMM_TRY(check_target_weights(c, what, w, n, &sum));
-    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
-    c->src_weighted = false;
-    std::vector<double> padded((size_t)c->n_pad, 0.0);
-    std::copy(w, w + n, padded.begin());
-    HGMM_TRY(ensure(c, c->src_w, sizeof(double) * padded.size()));
-    HGMM_HIP(c, hipMemcpyAsync(c->src_w.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
-    HGMM_HIP(c, ctx_stream_sync(c));
-    c->src_wsum = sum;
-    c->src_weighted = true;
-    return HGMM_OK;
+    return upload_weights(c, what, "cloud", false, 1, &w, &n, &c->n, c->n_pad, c->src_w, &c->src_wsum, &c->src_weighted);
 }
 
 // fixed-point moments of the resident target under (rot, t, scale) -> c->t_momq [T][NMQ] (all-reduced over the
@@ -1268,22 +1278,13 @@ extern "C" int hgmm_tree_register(hgmm_ctx* c, double* rot, double* t, double sc
     *iters_out = 0;
     *status_out = 0;                                  // 0: iteration budget used up, 1: |dq| < tol, 2: host M-step needed
     if (c->cfg[CFG_REG_DEVICE_SOLVE] && !c->comm_on()) {
-        // the loop on the device alone (forest_register_on_device: one pair on this context's tree and target)
+        // the loop on the device alone (register_set: one start pose of this context's pair, on the serial call's buffers)
         if (!c->tree.nodes_ready) return fail(c, HGMM_ERR_STATE, "registration: no tree (build or set_nodes first)");
         if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "registration: call hgmm_tree_set_target first");
-        const int64_t T = c->tree.T;
         HGMM_TRY(tree_mu_rmax_resident(c));
-        MomqScope sums(c->tree.momq_clean);
-        HGMM_TRY(sums.open(c, c->t_momq, sizeof(unsigned long long) * NMOM * T));
-        const int64_t first = 0, count = c->tgt_n;
         int32_t it32 = 0, st32 = 0;
-        HGMM_TRY(forest_register_on_device(c, 1, c->tgt_soa64.as<double>(), c->tgt_pad, &first, &count, &c->tgt_rmax,
-                                           &c->tree.mu_rmax, c->t_prep.as<double>(), (int)T, c->tree.L,
-                                           c->t_momq.as<unsigned long long>(), rot, t, scale, lambda_c, max_iter, tol,
-                                           q_prev_inout, &it32, &st32, trace, false, nullptr,
-                                           c->tgt_weighted ? c->tgt_w.as<double>() : nullptr,
-                                           c->tgt_weighted ? &c->tgt_wsum : nullptr));
-        sums.consumed();                              // every iteration's solve kernel zeroed what its E-step had added
+        HGMM_TRY(register_set(c, reg_set_pair(c, 1, false), rot, t, scale, lambda_c, max_iter, tol, q_prev_inout, &it32, &st32,
+                              trace));
         *iters_out = it32;
         *status_out = st32;
         return HGMM_OK;

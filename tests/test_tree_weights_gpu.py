@@ -5,8 +5,9 @@ and the gate do not see the weight.  The checks: the weighted E-step and the wei
 (tests/_weight_oracle.py) at the bounds of the unweighted and gated tests; w == 1 is bitwise the unweighted result on every
 entry, w == 2 exactly twice the moments, NULL and a new target take the weights off; a zero weight is an absent point; the
 batched and multi-start launches are bitwise the serial weighted call; the score's sums are the weighted sums of its own
-per-point arrays; on the project's real scan pair the count-weighted voxel centroids reach the full scan's pose; errors
-and state; two ranks with a shard of the weights each.
+per-point arrays, and the batched and multi-start scores take each member's chunk count and weight sum from its own table
+entry; on the project's real scan pair the count-weighted voxel centroids reach the full scan's pose; errors and state;
+two ranks with a shard of the weights each.
 
 Fixtures: hgmm_reg_L2.npz (2 013 points, T = 72: every node in the LDS table) and hgmm_reg_L4 (5 032 points, nodes beyond
 584 take the global atomics); neither point count is a multiple of the 256-point workgroup."""
@@ -372,6 +373,43 @@ def test_score_summary_is_the_weighted_sum_of_its_per_point_terms(ctx, records, 
     sc = gt.score(WeightedPoints(X, w))
     assert np.array_equal(sc.maha2, maha2) and sc.fitness == s[1] / s[0]
     assert gt.score(X).fitness == s0[1] / s0[0]                        # (and the next target is not scored under them)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_score_multi_and_batch_read_chunk_count_and_weight_sum_from_the_table(ctx, records, weighted):
+    """The score's finish step takes every member's number of 256-point chunks and its weight sum from the member's table
+    entry, for K poses of one pair as for B pairs.  K = 3 poses on targets of 256 points (a full last chunk) and of 257 (a
+    last chunk of one point); B = 3 pairs of 100, 256 and 257 points, so that each pair's own chunk count (1, 1, 2) is not
+    the launch's (2), the middle pair without weights.  Every summary is the serial call's, bit for bit."""
+    g = records[2]
+    P, X = g["points"], g["rot10_target"]
+    L, lc = int(g["L"]), float(g["lambda_c"])
+    T = hgmm_tree.n_total(L)
+    rot0, t0 = starts_for(X)
+    w_for = lambda n: weights_for(n) if weighted else None
+    for n in (256, 257):
+        w = w_for(n)
+        resident(ctx, g, X[:n], w)
+        m_sum = ctx.tree_score_multi(rot0, t0, 1.0, lc)
+        for k in range(3):
+            s_sum = ctx.tree_score(rot0[k], t0[k], 1.0, lc, want=())[0]
+            assert np.array_equal(m_sum[k], s_sum), (n, k)
+            assert s_sum[0] == (np.cumsum(w)[-1] if weighted else n) and (s_sum[0] != n) == weighted, (n, k)
+    targets = [X[:100], X[300:556], X[700:957]]
+    assert [len(tg) for tg in targets] == [100, 256, 257]
+    ws = [w_for(100), None, w_for(257)]
+    idx = np.random.RandomState(72).randint(T, size=T)
+    arrs = ctx.set_points_batch([P] * 3)
+    ctx.tree_build_batch([len(P)] * 3, L, 20.0, 1e-4, np.stack([a[idx] for a in arrs]), 0.004, want_tables=False)
+    ctx.tree_set_targets_batch(targets, weights=ws if weighted else None)
+    b_sum = ctx.tree_score_batch(rot0, t0, 1.0, lc)
+    for b, tg in enumerate(targets):
+        ctx.tree_set_nodes(L, *ctx.tree_get_nodes_batch(b, L))
+        ctx.tree_set_target(tg)
+        ctx.tree_set_target_weights(ws[b])
+        s_sum = ctx.tree_score(rot0[b], t0[b], 1.0, lc, want=())[0]
+        assert np.array_equal(b_sum[b], s_sum), b
+        assert s_sum[0] == (len(tg) if ws[b] is None else np.cumsum(ws[b])[-1]), b
 
 
 # ---------------------------------------------------------------------------------------------------------------------
