@@ -1044,7 +1044,7 @@ static bool fullcov_one_pass(const hgmm_ctx* c, int J16) {
 // `ctl` (device): the launches look at ctl->done first and the sum of q applies the stop rule `stop` -- for a loop whose
 // iterations are enqueued ahead of the host's knowledge (hgmm_fullcov_fit); then nothing is copied to the host here.
 static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_host, bool want_stats = true,
-                         const int* done = nullptr, TreeStop stop = TreeStop{nullptr, 0.0, 0, nullptr, 0}) {
+                         const int* done = nullptr, TreeStop stop = NO_STOP) {
     const int64_t tiles = (c->n + FT_P - 1) / FT_P;
     const int grid = (int)std::min<int64_t>(tiles, c->cus);             // 100+ KB of LDS: one workgroup per CU
     double* block_q = c->t_q.as<double>();
@@ -1148,7 +1148,7 @@ static int fullcov_pass(hgmm_ctx* c, int J, int* labels, double* q_host) {
                                                              c->t_prep.as<double>(), J, c->t_parent.as<double>(),
                                                              labels, block_q);
     }
-    tree_sum_kernel<<<1, 256, 0, c->stream>>>(block_q, (int)nblk(c->n, CH), q_dev, nullptr, TreeStop{nullptr, 0.0, 0, nullptr, 0});
+    tree_sum_kernel<<<1, 256, 0, c->stream>>>(block_q, (int)nblk(c->n, CH), q_dev, nullptr, NO_STOP);
     HGMM_HIP(c, hipGetLastError());
     if (c->comm_on()) HGMM_TRY(allreduce_f64_dev(c, q_dev, 1));
     if (q_host) {
@@ -1190,9 +1190,8 @@ extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const 
     double prev_q = 0.0;
     int it = 0, q_len = 0;
     if (one_pass && !c->comm_on()) {
-        // The stop rule on the device, the host one batch of iterations ahead (the scheme of hgmm_tree_build): the
-        // launches of an iteration look at ctl->done first, the sum of q applies |q - prev_q| < ls / the budget, and the
-        // host reads {done, iterations} through a pinned copy + an event while the next batch is already queued.
+        // The stop rule on the device, the host one batch of iterations ahead (run_batches): the launches of an iteration look
+        // at ctl->done first, the sum of q applies |q - prev_q| < ls / the budget.
         // (Waiting for q after every iteration left the device idle for ~0.1 ms per 1.7 ms iteration at N = 1e6.)
         double* q_dev = c->t_q.as<double>() + nblk(c->n, CH) + 2 * c->cus;
         TreeCtl* ctl = reinterpret_cast<TreeCtl*>(q_dev + 2);
@@ -1203,41 +1202,13 @@ extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const 
         const TreeStop stop{ctl, ls, max_iters, trace_dev, trace_cap};
         HandOver* hand = nullptr;
         HGMM_TRY(hand_over(c, 1, &hand));
-        HGMM_TRY(tree_batch_events(c));
-        TreeCtl* hp = hand->ctl_slot(0);
         const int batch = 4;
-        int enq = 0, slot = 0, rc = HGMM_OK;
-        auto enqueue_batch = [&](int s) -> int {
-            const int cnt = std::min(batch, max_iters - enq);
-            for (int b = 0; b < cnt; ++b) {
-                const int k = enq + b;                         // iteration k: labels into buffer (k + 1) & 1
-                tree_mstep_kernel<<<nblk(J, 256), 256, 0, c->stream>>>(c->t_mom.as<double>(), 0, J, n_total, ld, d_pi, d_mu,
-                                                                       d_cov, d_prep, flags_ptr(c), &ctl->done, 1);
-                const int r = fullcov_fused(c, J, J16, ((k + 1) & 1) ? lab_b : lab_a, nullptr, k + 1 < max_iters,
-                                            &ctl->done, stop);
-                if (r != HGMM_OK) return r;
-            }
-            enq += cnt;
-            if (hipMemcpyAsync(&hp[s], ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipEventRecord(c->tree_ev[s], c->stream) != hipSuccess)
-                return fail(c, HGMM_ERR_HIP, "full-covariance fit: device error: %s", hipGetErrorString(hipGetLastError()));
-            return HGMM_OK;
+        const auto enqueue_one = [&](int k) -> int {               // iteration k: labels into buffer (k + 1) & 1
+            tree_mstep_kernel<<<nblk(J, 256), 256, 0, c->stream>>>(c->t_mom.as<double>(), 0, J, n_total, ld, d_pi, d_mu,
+                                                                   d_cov, d_prep, flags_ptr(c), &ctl->done, 1);
+            return fullcov_fused(c, J, J16, ((k + 1) & 1) ? lab_b : lab_a, nullptr, k + 1 < max_iters, &ctl->done, stop);
         };
-        rc = enqueue_batch(slot);
-        while (rc == HGMM_OK) {
-            const bool ahead = enq < max_iters;
-            if (ahead) rc = enqueue_batch(slot ^ 1);
-            if (rc != HGMM_OK) break;
-            if (hipEventSynchronize(c->tree_ev[slot]) != hipSuccess) {
-                rc = fail(c, HGMM_ERR_HIP, "full-covariance fit: device error: %s", hipGetErrorString(hipGetLastError()));
-                break;
-            }
-            it = hp[slot].it;
-            if (hp[slot].done != 0) break;
-            if (!ahead) { rc = fail(c, HGMM_ERR_STATE, "full-covariance fit did not stop within its budget"); break; }
-            slot ^= 1;
-        }
-        HGMM_TRY(rc);
+        HGMM_TRY(run_batches(c, ctl, hand, max_iters, batch, enqueue_one, &it, "full-covariance fit"));
         q_len = it;
         lab_cur = ((it - 1) & 1) ? lab_b : lab_a;              // the arg-max of the E-step whose statistics the last M-step took
         if (q_trace_out && q_len > 0)

@@ -220,7 +220,7 @@ struct hgmm_ctx {
     hgmm::DevBuf t_prep;                      // double [T][12] : inv(6) coef logc pi mu(3) -> see tree_kernels
     hgmm::DevBuf t_cplx;                      // double [T]
     hgmm::HandOver hand;                      // pinned hand-over block of the tree / forest drivers
-    hipEvent_t tree_ev[2] = {nullptr, nullptr};   // the batch scheme's events, one per control-word slot (tree_host.h: tree_batch_events)
+    hipEvent_t tree_ev[2] = {nullptr, nullptr};   // the batch scheme's events, one per control-word slot (tree_host.h: run_batches)
     hgmm::DevBuf exp_tab2;                    // double [2048] 2^(j/2048) for the throughput kernels' exp (tree_kernels.hip)
     hgmm::DevBuf t_tickets;                   // uint: two-level arrival counters of the last-workgroup reductions, 4 KB apart
     hgmm::DevBuf t_flags;                     // int [4] tree flags + uint64 executed-pair counter (tree_kernels.hip)

@@ -25,9 +25,6 @@
 
 namespace hgmm {
 
-constexpr TreeFollow NO_FOLLOW{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr};
-constexpr TreeStop NO_STOP{nullptr, 0.0, 0, nullptr, 0};
-
 // ------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------
@@ -171,15 +168,8 @@ __global__ __launch_bounds__(CH) void forest_hist_kernel(const int* __restrict__
     const int seg = chunk_desc[3 * c], begin = chunk_desc[3 * c + 1], end = chunk_desc[3 * c + 2];
     const int it = fa.clouds[seg >> fa.shift].final_it;
     const int* __restrict__ cur = ((it - 1) & 1) ? cur1 : cur0;
-    const int i = begin + (int)threadIdx.x;
-    const int key = (i < end) ? (cur[i] & 7) : -1;
     __shared__ int sh[CH / 64][8];
-    const int w = wave_in_block();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const unsigned long long m = __ballot(key == k);
-        if (lane_id() == 0) sh[w][k] = __popcll(m);
-    }
+    tree_hist_waves(cur, begin, end, sh);
     __syncthreads();
     if (threadIdx.x < 8) {
         int t = 0;
@@ -201,27 +191,7 @@ __global__ __launch_bounds__(CH) void forest_scatter_kernel(const double* __rest
     const int seg = chunk_desc[3 * c], begin = chunk_desc[3 * c + 1], end = chunk_desc[3 * c + 2];
     const int it = fa.clouds[seg >> fa.shift].final_it;
     const int* __restrict__ cur = ((it - 1) & 1) ? cur1 : cur0;
-    const int i = begin + (int)threadIdx.x;
-    const bool active = i < end;
-    const int key = active ? (cur[i] & 7) : -1;
-    __shared__ int sh[CH / 64][8];
-    const int w = wave_in_block(), lane = lane_id();
-    int rank_in_wave = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const unsigned long long m = __ballot(key == k);
-        if (key == k) rank_in_wave = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) sh[w][k] = __popcll(m);
-    }
-    __syncthreads();
-    if (!active) return;
-    int before = 0;
-    for (int ww = 0; ww < w; ++ww) before += sh[ww][key];
-    const int dst = chunk_off[c * 8 + key] + before + rank_in_wave;
-    xs_new[dst] = xs[i];
-    xs_new[n_pad + dst] = xs[n_pad + i];
-    xs_new[2 * n_pad + dst] = xs[2 * n_pad + i];
-    if constexpr (WEIGHTED) wts_new[dst] = wts[i];
+    tree_scatter_body<WEIGHTED, false>(cur, c, begin, end, xs, n_pad, chunk_off, xs_new, nullptr, nullptr, wts, wts_new);
 }
 
 // targets: [n,3] rows -> the forest's structure of arrays at `first`, and the largest |x|^2 of the cloud (the same
@@ -355,15 +325,11 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
 // ------------------------------------------------------------------------------------------
 // The E-step of a set's registration loops: shared tree or forest, gate off or on (hgmm_tree_set_reg_gate), without or with
 // per-point weights of the target (hgmm_tree_set_target_weights[_batch]).  The one place a further flag is added.
-using RegEstepKernel = decltype(&forest_reg_estep_kernel<4, false, false, false>);
-template <bool... FLAGS>
-static RegEstepKernel reg_estep_kernel_for() { return forest_reg_estep_kernel<4, FLAGS...>; }
-template <bool... FLAGS, class... REST>
-static RegEstepKernel reg_estep_kernel_for(bool flag, REST... rest) {
-    return flag ? reg_estep_kernel_for<FLAGS..., true>(rest...) : reg_estep_kernel_for<FLAGS..., false>(rest...);
-}
-static RegEstepKernel reg_estep_kernel_for(const hgmm_ctx* c, const RegSet& set) {
-    return reg_estep_kernel_for<>(set.shared_tree, std::isfinite(c->tree.reg_gate), set.w != nullptr);
+struct RegEstepFamily { template <bool... FLAGS> static auto kernel() { return forest_reg_estep_kernel<4, FLAGS...>; } };
+struct RegSolveFamily { template <bool SHARED> static auto kernel() { return forest_reg_solve_kernel<SHARED>; } };
+struct ScoreFamily { template <bool SHARED, bool W> static auto kernel() { return forest_score_kernel<SHARED, W>; } };
+static auto reg_estep_kernel_for(const hgmm_ctx* c, const RegSet& set) {
+    return kernel_for<RegEstepFamily>(set.shared_tree, std::isfinite(c->tree.reg_gate), set.w != nullptr);
 }
 
 // The registration loop of a set with the device on its own (reg_device_solve): every iteration is two launches -- the
@@ -381,7 +347,7 @@ static int forest_register_on_device(hgmm_ctx* c, const RegSet& set, double* rot
     const size_t trace_bytes = trace ? sizeof(double) * 13 * (size_t)max_iter * B : 0;
     if (trace) HGMM_TRY(ensure(c, c->fr_trace, trace_bytes));
     const auto estep_kernel = reg_estep_kernel_for(c, set);
-    const auto solve_kernel = set.shared_tree ? forest_reg_solve_kernel<true> : forest_reg_solve_kernel<false>;
+    const auto solve_kernel = kernel_for<RegSolveFamily>(set.shared_tree);
     unsigned long long* momq = set.momq->as<unsigned long long>();
     double* d_trace = trace ? c->fr_trace.as<double>() : nullptr;
     HandOver* hand = nullptr;
@@ -397,26 +363,18 @@ static int forest_register_on_device(hgmm_ctx* c, const RegSet& set, double* rot
     }
     HGMM_TRY(stage_h2d(c, tb.pairs, tab.data(), sizeof(ForestRegPair) * B));
     const unsigned gx = set.gx();
-    const int ahead = 3;
-    int enq = 0;
-    unsigned spins = 0;
-    while (true) {
-        const Progress pg = scan_progress(words.host, B);
-        if (pg.all_done) break;
-        if (enq < max_iter && enq - pg.it_min < ahead) {
-            {
-                ProfScope prof(c, HGMM_K_TREE_REG);
-                estep_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, T, set.L, lambda_c, momq,
-                                                                     (int)gx, c->tree.reg_gate, set.w);
-            }
-            solve_kernel<<<B, 256, 0, c->stream>>>(momq, tb.pairs, set.prep, T, tb.out, tol, max_iter, d_trace, words.dev);
-            HGMM_HIP(c, hipGetLastError());
-            ++enq;
-            spins = 0;
-            continue;
+    const auto enqueue = [&](int) -> int {
+        {
+            ProfScope prof(c, HGMM_K_TREE_REG);
+            estep_kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, T, set.L, lambda_c, momq,
+                                                                 (int)gx, c->tree.reg_gate, set.w);
         }
-        HGMM_TRY(device_watch(c, &spins, words.host, B, pg.sig, "registration (device loop, %d iterations enqueued)", enq));
-    }
+        solve_kernel<<<B, 256, 0, c->stream>>>(momq, tb.pairs, set.prep, T, tb.out, tol, max_iter, d_trace, words.dev);
+        HGMM_HIP(c, hipGetLastError());
+        return HGMM_OK;
+    };
+    const int ahead = 3;
+    HGMM_TRY(follow_ahead(c, words.host, B, max_iter, ahead, enqueue, nothing_at_budget, nullptr, "registration (device loop)"));
     std::vector<double> trace_host(trace ? (size_t)13 * max_iter * B : 0);
     {
         StagedDownloads dl(c);
@@ -534,8 +492,7 @@ int score_set(hgmm_ctx* c, const RegSet& set, const double* rot, const double* t
     HGMM_TRY(stage_h2d(c, tb.pairs, tab.data(), sizeof(ForestRegPair) * B));
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
-        const auto kernel = set.shared_tree ? (set.w ? forest_score_kernel<true, true> : forest_score_kernel<true, false>)
-                                            : (set.w ? forest_score_kernel<false, true> : forest_score_kernel<false, false>);
+        const auto kernel = kernel_for<ScoreFamily>(set.shared_tree, set.w != nullptr);
         kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, set.T, set.L, lambda_c, maha2_max,
                                                       partial, (int)gx, set.w);
     }
@@ -546,6 +503,81 @@ int score_set(hgmm_ctx* c, const RegSet& set, const double* rot, const double* t
     HGMM_HIP(c, dl.finish());
     return HGMM_OK;
 }
+
+// ---- the kernel families of the forest build (kernel_for, tree_host.h; the last flag: WEIGHTED) ---------------------------
+// (the forest's E-step is always the two-pass form)
+struct ForestEstepFamily { template <bool W> static auto kernel() { return forest_estep_kernel<true, W>; } };
+struct ForestLlEstepFamily { template <bool F32, bool W> static auto kernel() { return forest_ll_estep_kernel<F32, W>; } };
+struct ForestScatterFamily { template <bool W> static auto kernel() { return forest_scatter_kernel<W>; } };
+
+// ---- one level of the forest build (hgmm_tree_build's BuildLevel in its one mode: overlapped, follow) ---------------------
+struct ForestLevel {
+    hgmm_ctx* c;
+    const BuildWorkspace& ws;
+    int l, P;                        // the level and the forest's parent segments
+    double ld;
+    int max_iters;
+    ForestArgs fa;
+    int ll_stride;                   // log-likelihood workgroups per cloud (the longest cloud's); level 0: none
+    int* d_flags;
+    // ---- set by prepare() ----
+    int64_t lb, parent_first;        // a cloud's first node of the level, n_level of them; ... of the level above
+    int n_level;
+    unsigned grid_chunks;
+
+    void prepare() {
+        lb = level_first(l);
+        n_level = (int)(level_first(l + 1) - lb);
+        parent_first = (l == 0) ? 0 : level_first(l - 1);
+        tree_chunks_kernel<<<1, 1024, 0, c->stream>>>(ws.seg, P, ws.chunk_first, ws.chunk_desc, ws.n_chunks_dev);
+        grid_chunks = (unsigned)(c->n / CH + P + 1);
+    }
+    int enqueue(int e) const {
+        const bool weighted = ws.w != nullptr;
+        const int64_t n_pad = c->n_pad;
+        const int B = fa.B;
+        double *d_pi = c->fr_pi.as<double>(), *d_mu = c->fr_mu.as<double>(), *d_cov = c->fr_cov.as<double>();
+        double *d_prep = c->fr_prep.as<double>(), *d_mom = c->fr_mom.as<double>(), *block_q = c->fr_q.as<double>();
+        const TreeEstepArgs ea_now{ws.xs, n_pad, d_prep, ws.chunk_desc, ws.n_chunks_dev, parent_first, l, ws.partials,
+                                   ws.cur[e & 1], nullptr, nullptr, ws.w};
+        const auto estep = kernel_for<ForestEstepFamily>(weighted);
+        if (e == 0) {
+            ProfScope prof(c, HGMM_K_TREE_ESTEP);
+            estep<<<grid_chunks, CH, 0, c->stream>>>(ea_now, fa);
+        }
+        if (l > 0)
+            forest_moments8_kernel<<<(unsigned)(B * n_level / 8), 64, 0, c->stream>>>(ws.partials, ws.chunk_first, n_level, d_mom, lb, ld,
+                                                                                     d_pi, d_mu, d_cov, d_prep, d_flags, fa, block_q, e);
+        else                                                    // (level 0: a wave per child, tree_moments8_kernel's note)
+            forest_moments_kernel<<<(unsigned)(B * n_level), 64, 0, c->stream>>>(ws.partials, ws.chunk_first, n_level, d_mom, lb, ld,
+                                                                                d_pi, d_mu, d_cov, d_prep, d_flags, fa, block_q, e);
+        {
+            ProfScope prof(c, HGMM_K_TREE_LOGLIK);
+            // (level 0: behind the budget's last iteration the E-step runs for the shares of q alone)
+            const int with_estep = (e + 1 < max_iters || l == 0) ? 1 : 0;
+            const TreeEstepArgs ea_next{ws.xs, n_pad, d_prep, ws.chunk_desc, ws.n_chunks_dev, parent_first, l, ws.partials,
+                                        ws.cur[(e + 1) & 1], nullptr, l == 0 ? block_q : nullptr, ws.w};
+            const unsigned g = (unsigned)(B * ll_stride) + (with_estep ? grid_chunks : 0u);
+            if (l == 0)
+                // (level 0 is E-step workgroups only: the plain E-step kernel -- 72 registers instead of the fused kernel's
+                //  92-96, one more wave per SIMD for a launch that is a chain of trips to memory)
+                estep<<<grid_chunks, CH, 0, c->stream>>>(ea_next, fa);
+            else {
+                const auto fused = kernel_for<ForestLlEstepFamily>(c->tree.pdf_f32, weighted);
+                fused<<<g, CH, 0, c->stream>>>(ws.xs, n_pad, d_prep, lb, n_level, block_q, d_flags, fa, ll_stride, ea_next, with_estep);
+            }
+        }
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build (batch): kernel launch failed: %s", hipGetErrorString(le));
+        return HGMM_OK;
+    }
+    // behind the budget's last iteration: one workgroup per cloud accounts for its q
+    int close() const {
+        forest_close_kernel<<<fa.B, CH, 0, c->stream>>>(fa, c->fr_q.as<double>(), max_iters);
+        if (hipGetLastError() != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build (batch): launch failed");
+        return HGMM_OK;
+    }
+};
 
 }  // namespace hgmm
 
@@ -588,7 +620,8 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     for (int i = 0; i < L - 1; ++i) P8 *= 8;                   // parents of one cloud at the last level
     const int64_t maxP = P8 * B;
     if (TT > 0x3fffffff || maxP > (1 << 24)) return fail(c, HGMM_ERR_ARG, "tree build (batch): %d clouds x %d levels is too large", B, L);
-    const int64_t max_chunks = n / CH + maxP + 8;
+    // (one mode: every cloud is small, so every level is an overlapped follow-mode level of the serial build)
+    const int ahead_iters = 2;                                  // iterations enqueued beyond the slowest running cloud (hgmm_tree_build)
     ForestState& F = c->forest;
     F.nodes_ready = false;
     HGMM_TRY(ensure(c, c->fr_pi, sizeof(double) * TT));
@@ -601,47 +634,17 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     const int trace_cap = std::min(max_iters_per_level, 4096);
     HGMM_TRY(ensure(c, c->fr_trace, sizeof(double) * (size_t)trace_cap * L * B));
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * 3 * TT));
-    HGMM_TRY(ensure(c, c->t_current, sizeof(int) * 2 * n_pad));
-    HGMM_TRY(ensure(c, c->t_parent, sizeof(double) * 3 * n_pad));
-    if (weighted) HGMM_TRY(ensure(c, c->t_w2, sizeof(double) * n_pad));
-    HGMM_TRY(ensure(c, c->t_seg, sizeof(int) * (2 * (8 * maxP + 2) + 2 * (maxP + 2) + 8)));
-    HGMM_TRY(ensure(c, c->t_chunks, sizeof(int) * (size_t)(3 + 8 + 8) * max_chunks));
-    HGMM_TRY(ensure(c, c->t_partials, sizeof(double) * (size_t)8 * NMOM * max_chunks));
-    double* xs_c = nullptr;
-    if (L > 2) {
-        HGMM_TRY(ensure(c, c->t_xs3, sizeof(double) * 3 * n_pad));
-        xs_c = c->t_xs3.as<double>();
-        if (weighted) HGMM_TRY(ensure(c, c->t_w3, sizeof(double) * n_pad));
-    }
-    double* w_b = weighted ? c->t_w2.as<double>() : nullptr;
-    double* w_c = (weighted && L > 2) ? c->t_w3.as<double>() : nullptr;
-    const double* w_cur = weighted ? c->fr_src_w.as<double>() : nullptr;
+    BuildWorkspace ws;
+    HGMM_TRY(ws.take(c, n, n_pad, maxP, L, c->x_soa64.as<double>(), weighted ? c->fr_src_w.as<double>() : nullptr));
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, B, &hand));
-    unsigned long long* const words = hand->progress(0).host;
-    unsigned long long* const words_dev = hand->progress(0).dev;
+    const HostDev<unsigned long long> words = hand->progress(0);
 
-    double* d_pi = c->fr_pi.as<double>();
-    double* d_mu = c->fr_mu.as<double>();
-    double* d_cov = c->fr_cov.as<double>();
+    double *d_pi = c->fr_pi.as<double>(), *d_mu = c->fr_mu.as<double>(), *d_cov = c->fr_cov.as<double>();
     double* d_prep = c->fr_prep.as<double>();
-    double* d_mom = c->fr_mom.as<double>();
     ForestCloud* d_clouds = c->fr_clouds.as<ForestCloud>();
     int* d_flags = reinterpret_cast<int*>(d_clouds + B);
-    double* block_q = c->fr_q.as<double>();
     double* trace_base = c->fr_trace.as<double>();
-    double* xs_a = c->x_soa64.as<double>();
-    double* xs_b = c->t_parent.as<double>();
-    int* cur0 = c->t_current.as<int>();
-    int* cur1 = cur0 + n_pad;
-    int* seg_a = c->t_seg.as<int>();
-    int* seg_b = seg_a + (8 * maxP + 2);
-    int* chunk_first = seg_b + (8 * maxP + 2);
-    int* n_chunks_dev = chunk_first + (maxP + 2) * 2;
-    int* chunk_desc = c->t_chunks.as<int>();
-    int* hist = chunk_desc + 3 * max_chunks;
-    int* chunk_off = hist + 8 * max_chunks;
-    double* partials = c->t_partials.as<double>();
 
     // node tables: pi = 1/8, mu = given, cov = sig2 I for every tree; per-cloud form flags start at zero
     HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * TT, hipMemcpyHostToDevice, c->stream));
@@ -651,19 +654,14 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     HGMM_HIP(c, hipGetLastError());
     std::vector<int> first(B + 1, 0);
     for (int b = 0; b < B; ++b) first[b + 1] = first[b] + (int)counts[b];
-    HGMM_TRY(stage_h2d(c, seg_a, first.data(), sizeof(int) * (B + 1)));
+    HGMM_TRY(stage_h2d(c, ws.seg, first.data(), sizeof(int) * (B + 1)));
 
-    const double* xs_cur = xs_a;
-    int* seg_cur = seg_a;
     int P = B;
     std::vector<int> level_iters((size_t)B * L, 0);
     std::vector<ForestCloud> table(B);
     int rc = HGMM_OK;
-    const int ahead_iters = 2;                                  // iterations enqueued beyond the slowest running cloud (hgmm_tree_build)
     for (int l = 0; l < L && rc == HGMM_OK; ++l) {
-        const int64_t lb = level_first(l), le = level_first(l + 1);
-        const int n_level = (int)(le - lb);
-        const int64_t parent_first = (l == 0) ? 0 : level_first(l - 1);
+        const int n_level = (int)(level_first(l + 1) - level_first(l));
         // the clouds' entries for this level: the decomposition the serial build would use for each of them
         int q_at = 0, ll_stride = 1;
         for (int b = 0; b < B; ++b) {
@@ -687,81 +685,27 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         if (l == 0) ll_stride = 0;                              // no log-likelihood workgroups at level 0
         rc = stage_h2d(c, d_clouds, table.data(), sizeof(ForestCloud) * B);
         if (rc != HGMM_OK) break;
-        const ForestArgs fa{d_clouds, B, (int)T, 3 * l, ls, max_iters_per_level, trace_base, trace_cap, L, l, words_dev};
-        tree_chunks_kernel<<<1, 1024, 0, c->stream>>>(seg_cur, P, chunk_first, chunk_desc, n_chunks_dev);
-        const unsigned grid_chunks = (unsigned)(n / CH + P + 1);
-        for (int b = 0; b < B; ++b) __atomic_store_n(words + b, 0ull, __ATOMIC_RELAXED);
-        auto enqueue_iteration = [&](int e) -> int {
-            const TreeEstepArgs ea_now{xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l, partials,
-                                       (e & 1) ? cur1 : cur0, nullptr, nullptr, w_cur};
-            const auto estep = weighted ? forest_estep_kernel<true, true> : forest_estep_kernel<true, false>;
-            if (e == 0) {
-                ProfScope prof(c, HGMM_K_TREE_ESTEP);
-                estep<<<grid_chunks, CH, 0, c->stream>>>(ea_now, fa);
-            }
-            if (l > 0)
-                forest_moments8_kernel<<<(unsigned)(B * n_level / 8), 64, 0, c->stream>>>(partials, chunk_first, n_level, d_mom, lb, ld,
-                                                                                         d_pi, d_mu, d_cov, d_prep, d_flags, fa, block_q, e);
-            else                                                    // (level 0: a wave per child, tree_moments8_kernel's note)
-                forest_moments_kernel<<<(unsigned)(B * n_level), 64, 0, c->stream>>>(partials, chunk_first, n_level, d_mom, lb, ld,
-                                                                                    d_pi, d_mu, d_cov, d_prep, d_flags, fa, block_q, e);
-            {
-                ProfScope prof(c, HGMM_K_TREE_LOGLIK);
-                // (level 0: behind the budget's last iteration the E-step runs for the shares of q alone)
-                const int with_estep = (e + 1 < max_iters_per_level || l == 0) ? 1 : 0;
-                const TreeEstepArgs ea_next{xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l, partials,
-                                            ((e + 1) & 1) ? cur1 : cur0, nullptr, l == 0 ? block_q : nullptr, w_cur};
-                const unsigned g = (unsigned)(B * ll_stride) + (with_estep ? grid_chunks : 0u);
-                if (l == 0)
-                    // (level 0 is E-step workgroups only: the plain E-step kernel -- 72 registers instead of the fused kernel's
-                    //  92-96, one more wave per SIMD for a launch that is a chain of trips to memory)
-                    estep<<<grid_chunks, CH, 0, c->stream>>>(ea_next, fa);
-                else {
-                    const auto fused = weighted ? (c->tree.pdf_f32 ? forest_ll_estep_kernel<true, true> : forest_ll_estep_kernel<false, true>)
-                                                : (c->tree.pdf_f32 ? forest_ll_estep_kernel<true, false> : forest_ll_estep_kernel<false, false>);
-                    fused<<<g, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, lb, n_level, block_q, d_flags, fa, ll_stride, ea_next,
-                                                   with_estep);
-                }
-            }
-            const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build (batch): kernel launch failed: %s", hipGetErrorString(le));
-            return HGMM_OK;
-        };
-        // The host keeps `ahead` iterations enqueued beyond the slowest cloud that is still running (every cloud's speaker
-        // stores (stopped << 32 | iterations) into its own word of pinned host memory) and leaves the level once every
-        // cloud has stopped.
-        int enq = 0;
-        unsigned spins = 0;
-        while (rc == HGMM_OK) {
-            const Progress pg = scan_progress(words, B);
-            if (pg.all_done) break;
-            if (enq < max_iters_per_level && enq - pg.it_min < ahead_iters) {
-                rc = enqueue_iteration(enq);
-                ++enq;
-                if (rc == HGMM_OK && enq == max_iters_per_level) {
-                    forest_close_kernel<<<B, CH, 0, c->stream>>>(fa, block_q, enq);
-                    if (hipGetLastError() != hipSuccess) rc = fail(c, HGMM_ERR_HIP, "tree build (batch): launch failed");
-                }
-                spins = 0;
-                continue;
-            }
-            rc = device_watch(c, &spins, words, B, pg.sig, "tree build (batch): level %d (%d iterations enqueued)", l, enq);
+        const ForestArgs fa{d_clouds, B, (int)T, 3 * l, ls, max_iters_per_level, trace_base, trace_cap, L, l, words.dev};
+        ForestLevel lv{c, ws, l, P, ld, max_iters_per_level, fa, ll_stride, d_flags};
+        lv.prepare();
+        for (int b = 0; b < B; ++b) __atomic_store_n(words.host + b, 0ull, __ATOMIC_RELAXED);
+        rc = follow_ahead(c, words.host, B, max_iters_per_level, ahead_iters, [&lv](int e) { return lv.enqueue(e); },
+                          [&lv] { return lv.close(); }, nullptr, "tree build (batch)");
+        if (rc != HGMM_OK) {
+            c->err += " (level " + std::to_string(l) + ")";
+            break;
         }
-        if (rc != HGMM_OK) break;
-        for (int b = 0; b < B; ++b) level_iters[(size_t)b * L + l] = (int)(__atomic_load_n(words + b, __ATOMIC_ACQUIRE) & 0xffffffffull);
+        for (int b = 0; b < B; ++b)
+            level_iters[(size_t)b * L + l] = (int)(__atomic_load_n(words.host + b, __ATOMIC_ACQUIRE) & 0xffffffffull);
         if (l + 1 < L) {
-            forest_hist_kernel<<<grid_chunks, CH, 0, c->stream>>>(cur0, cur1, chunk_desc, n_chunks_dev, hist, fa);
-            int* seg_next = (seg_cur == seg_a) ? seg_b : seg_a;
-            tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(hist, chunk_first, seg_cur, P, chunk_off, seg_next);
-            double* xs_next = (xs_cur == xs_b) ? xs_c : xs_b;   // A -> B -> C -> B -> ... (the resident cloud is never overwritten)
-            double* w_next = (xs_next == xs_b) ? w_b : w_c;     // (the weights' buffers pair up with the coordinates')
-            const auto scatter = weighted ? forest_scatter_kernel<true> : forest_scatter_kernel<false>;
-            scatter<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, cur0, cur1, chunk_desc, n_chunks_dev, chunk_off, xs_next, fa,
-                                                       w_cur, w_next);
+            // partition for the next level
+            forest_hist_kernel<<<lv.grid_chunks, CH, 0, c->stream>>>(ws.cur[0], ws.cur[1], ws.chunk_desc, ws.n_chunks_dev, ws.hist, lv.fa);
+            tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(ws.hist, ws.chunk_first, ws.seg, P, ws.chunk_off, ws.seg_next);
+            const auto scatter = kernel_for<ForestScatterFamily>(weighted);
+            scatter<<<lv.grid_chunks, CH, 0, c->stream>>>(ws.xs, n_pad, ws.cur[0], ws.cur[1], ws.chunk_desc, ws.n_chunks_dev,
+                                                          ws.chunk_off, ws.xs_next, lv.fa, ws.w, ws.w_next);
             if (hipGetLastError() != hipSuccess) { rc = fail(c, HGMM_ERR_HIP, "tree build (batch): partition launch failed"); break; }
-            xs_cur = xs_next;
-            w_cur = weighted ? w_next : nullptr;
-            seg_cur = seg_next;
+            ws.advance();
             P *= 8;
         }
     }
@@ -795,20 +739,12 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     F.counts.assign(counts, counts + B);
     F.mu_rmax.resize(B);
     for (int b = 0; b < B; ++b) F.mu_rmax[b] = tree_mu_rmax(mu_dst + (size_t)3 * T * b, T);
+    if (iters_out) std::copy(level_iters.begin(), level_iters.end(), iters_out);
     for (int b = 0; b < B; ++b) {
-        int at = 0;
-        for (int l = 0; l < L; ++l) {
-            const int it = level_iters[(size_t)b * L + l];
-            if (iters_out) iters_out[(size_t)b * L + l] = it;
-            if (q_trace_out) {
-                const int take = std::min(std::min(it, trace_cap), q_capacity - at);
-                if (take > 0)
-                    std::memcpy(q_trace_out + (size_t)b * q_capacity + at, trace_host.data() + ((size_t)b * L + l) * trace_cap,
-                                sizeof(double) * take);
-            }
-            at += it;
-        }
-        if (q_len_out) q_len_out[b] = at < q_capacity ? at : q_capacity;
+        const int q_len = gather_traces(&level_iters[(size_t)b * L], L, trace_cap, q_trace_out ? q_capacity : 0, [&](int at, int l, int take) {
+            std::memcpy(q_trace_out + (size_t)b * q_capacity + at, trace_host.data() + ((size_t)b * L + l) * trace_cap, sizeof(double) * take);
+        });
+        if (q_len_out) q_len_out[b] = q_len < q_capacity ? q_len : q_capacity;
     }
     F.nodes_ready = true;
     return HGMM_OK;

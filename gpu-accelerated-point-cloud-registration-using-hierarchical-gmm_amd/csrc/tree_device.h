@@ -1998,6 +1998,56 @@ inline int reg_host_step(const double* o, double* rot, double* t, double* q_prev
     return (qp == qp && std::fabs(q - qp) < tol) ? 1 : 0;                                   // (NaN: no previous q)
 }
 
+// ---- partition: regroup the (already parent-grouped) points by the child they were assigned to ------------------------------
+// The bodies of tree_hist_kernel / tree_scatter_kernel and of their forest twins, which differ in where `cur` comes from
+// (the assignment buffer of the chunk's own cloud) and in that a forest keeps no permutation.  c: the chunk, [begin, end) its
+// points; called by all CH threads of the chunk's workgroup.  (No __restrict__ on the bodies' pointers: the kernels'
+// arguments carry it, and a second set of scopes changed the forest kernels' load order.)
+// per chunk: 8-bin histogram of the child index, first half -- every wave's eight counts into sh [CH / 64][8] (LDS).  The
+// kernels add the waves' counts up themselves behind their barrier: with those five lines in here the compiler orders the
+// operands of one integer add differently, and the kernels' code is to stay what it was.
+__device__ __forceinline__ void tree_hist_waves(const int* cur, int begin, int end, int (*sh)[8]) {
+    const int i = begin + (int)threadIdx.x;
+    const int key = (i < end) ? (cur[i] & 7) : -1;
+    const int w = wave_in_block();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const unsigned long long m = __ballot(key == k);
+        if (lane_id() == 0) sh[w][k] = __popcll(m);
+    }
+}
+// stable scatter of coordinates / (PERM) permutation / (WEIGHTED) weights: wts_new[dst] = wts[i].  An instantiation without
+// a flag reads neither of that flag's pointers.
+template <bool WEIGHTED, bool PERM>
+__device__ __forceinline__ void tree_scatter_body(const int* cur, int c, int begin, int end,
+                                                  const double* xs, int64_t n_pad,
+                                                  const int* chunk_off, double* xs_new,
+                                                  const int* perm, int* perm_new,
+                                                  const double* wts, double* wts_new) {
+    const int i = begin + (int)threadIdx.x;
+    const bool active = i < end;
+    const int key = active ? (cur[i] & 7) : -1;
+    __shared__ int sh[CH / 64][8];
+    const int w = wave_in_block(), lane = lane_id();
+    int rank_in_wave = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const unsigned long long m = __ballot(key == k);
+        if (key == k) rank_in_wave = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) sh[w][k] = __popcll(m);
+    }
+    __syncthreads();
+    if (!active) return;
+    int before = 0;
+    for (int ww = 0; ww < w; ++ww) before += sh[ww][key];
+    const int dst = chunk_off[c * 8 + key] + before + rank_in_wave;
+    xs_new[dst] = xs[i];
+    xs_new[n_pad + dst] = xs[n_pad + i];
+    xs_new[2 * n_pad + dst] = xs[2 * n_pad + i];
+    if constexpr (PERM) perm_new[dst] = perm[i];
+    if constexpr (WEIGHTED) wts_new[dst] = wts[i];
+}
+
 // the lanes' shares of one node's moments: chunk partials of its parent, lane t takes chunks c0 + t, c0 + t + 64, ...
 // (tree_moments_kernel and its forest twin: the same order, then the same wave_sum_f64 per moment)
 __device__ __forceinline__ void tree_moments_gather(const double* __restrict__ partials, int c0, int c1, int k,

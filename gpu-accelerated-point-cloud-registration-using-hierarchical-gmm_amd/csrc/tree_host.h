@@ -1,6 +1,8 @@
 // Host side shared by the drivers of the tree, forest and full-covariance kernels (tree_kernels.hip, tree_batch.hip,
-// fullcov_kernels.hip): the pinned hand-over block, the watch of a host that follows the device through it, the guard
-// of the fixed-point moment sums, and the small blocks every registration entry point needs.  Host code only.
+// fullcov_kernels.hip): the pinned hand-over block and the watch of a host that follows the device through it, the
+// picker of a kernel's instantiation, the two host loops of a device-side stop rule (follow_ahead, run_batches), the
+// workspace and the trace hand-out of both builds, the guard of the fixed-point moment sums, and the small blocks every
+// registration entry point needs.  Host code only.
 #pragma once
 #include "tree_device.h"
 
@@ -18,6 +20,9 @@ __global__ void tree_expand_moments_kernel(const double* __restrict__ mom, int64
 int tree_flags(hgmm_ctx* c, bool reset);
 int ensure_exp_tab2(hgmm_ctx* c);
 inline int* flags_ptr(hgmm_ctx* c) { return c->t_flags.as<int>(); }
+// a launch that follows nothing / applies no stop rule
+constexpr TreeFollow NO_FOLLOW{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr};
+constexpr TreeStop NO_STOP{nullptr, 0.0, 0, nullptr, 0};
 
 // ---- the pinned hand-over block (layout and accessors: hgmm_ctx.h, HandOver) -----------------------------------------
 // The block for B pairs / clouds (the serial paths: B = 1).  It only grows; the device aliases are resolved here, once.
@@ -40,12 +45,6 @@ inline int hand_over(hgmm_ctx* c, int B, HandOver** out) {
         h.B = B;
     }
     *out = &h;
-    return HGMM_OK;
-}
-// the two events of the batch scheme (a copy of the control words into slot s, then event s)
-inline int tree_batch_events(hgmm_ctx* c) {
-    for (hipEvent_t& e : c->tree_ev)
-        if (!e) HGMM_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return HGMM_OK;
 }
 
@@ -87,6 +86,157 @@ __attribute__((format(printf, 6, 7))) inline int device_watch(hgmm_ctx* c, unsig
     va_end(ap);
     if (qe != hipSuccess) return fail(c, HGMM_ERR_HIP, "%s: device error: %s", what, hipGetErrorString(qe));
     return fail(c, HGMM_ERR_STATE, "%s: no progress (the stream is idle and the device has not reported)", what);
+}
+
+// ---- the instantiation of a kernel family for run-time flags -------------------------------------------------------------
+// kernel_for<FAMILY>(flag, flag, ...) is FAMILY::kernel<flag, flag, ...>(): a family is a struct whose static member
+// template `kernel` names the instantiation for its compile-time flags.  The one place a further flag is added.
+template <class FAMILY, bool... FLAGS>
+inline auto kernel_for() { return FAMILY::template kernel<FLAGS...>(); }
+template <class FAMILY, bool... FLAGS, class... REST>
+inline auto kernel_for(bool flag, REST... rest) {
+    return flag ? kernel_for<FAMILY, FLAGS..., true>(rest...) : kernel_for<FAMILY, FLAGS..., false>(rest...);
+}
+
+// ---- the two host loops of every device-side stop rule -----------------------------------------------------------------
+// The polled look-ahead loop (hgmm_tree_build: B = 1, ahead = tree_ahead; hgmm_tree_build_batch: 2; forest_register_on_device:
+// 3).  Every member's stop rule stores (stopped << 32 | iterations) into its progress word of pinned HOST memory; the host
+// keeps `ahead` iterations enqueued beyond the slowest member still running -- no copy, no event, no synchronisation, at
+// most `ahead` iterations of skipped launches behind a stop (run_batches below: 46 of them over C4's four levels, ~0.25 ms
+// of a 3.1 ms build, plus a control-word copy per batch) -- and returns once all have stopped.  The caller resets the
+// words before the loop's first launch (every launch that could write them is this loop's) and reads the counts from them
+// afterwards.  enqueue(e) -> status: iteration e, *enqueued (may be NULL) of them in all; on_budget_enqueued() fires once, right
+// after iteration budget - 1 (the builds' close launch).  A launch the runtime rejected would leave the words untouched for
+// ever: enqueue reports it (hipGetLastError) and the loop returns it before it polls again.  `what` names the loop.
+template <class Enqueue, class AtBudget>
+inline int follow_ahead(hgmm_ctx* c, const unsigned long long* words, int B, int budget, int ahead, Enqueue&& enqueue,
+                        AtBudget&& on_budget_enqueued, int* enqueued, const char* what) {
+    int enq = 0, rc = HGMM_OK;
+    unsigned spins = 0;
+    while (rc == HGMM_OK) {
+        const Progress pg = scan_progress(words, B);
+        if (pg.all_done) break;
+        if (enq < budget && enq - pg.it_min < ahead) {
+            rc = enqueue(enq);
+            ++enq;
+            if (rc == HGMM_OK && enq == budget) rc = on_budget_enqueued();
+            spins = 0;
+            continue;
+        }
+        if (enq >= budget && pg.it_min >= enq)                  // cannot happen (the budget's last iteration stops)
+            rc = fail(c, HGMM_ERR_STATE, "%s did not stop within its budget", what);
+        else                                                    // (seen: of the slowest member still running)
+            rc = device_watch(c, &spins, words, B, pg.sig, "%s (%d iterations enqueued, %d seen)", what, enq, pg.it_min);
+    }
+    if (enqueued) *enqueued = enq;
+    return rc;
+}
+inline int nothing_at_budget() { return HGMM_OK; }
+
+// The batch scheme (hgmm_tree_build with tree_ahead = 0: batches of 8; hgmm_fullcov_fit: of 4).  The control word {done,
+// iterations} stays on the device; the host enqueues `batch` iterations (enqueue_one(e) -> status, never beyond the budget),
+// a copy of the word into slot s of the pinned block and event s.  It stays ONE BATCH AHEAD: batch k + 1 is enqueued before
+// the host waits for batch k's verdict, so the device never idles at a batch boundary (round 2: enqueue, copy, synchronise,
+// enqueue -- 30-40 us of idle device per batch, a quarter of C4's build).  The price: when the loop stops, the batch enqueued
+// ahead runs as skipped launches (~1 us each).  *it: the iterations the loop took.
+template <class EnqueueOne>
+inline int run_batches(hgmm_ctx* c, const TreeCtl* ctl_dev, HandOver* hand, int budget, int batch, EnqueueOne&& enqueue_one, int* it,
+                       const char* what) {
+    for (hipEvent_t& e : c->tree_ev)                            // (one event per slot, made on first use)
+        if (!e) HGMM_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    TreeCtl* hp = hand->ctl_slot(0);
+    int enq = 0, slot = 0;
+    auto enqueue_batch = [&](int s) -> int {
+        const int cnt = std::min(batch, budget - enq);
+        for (int b = 0; b < cnt; ++b) HGMM_TRY(enqueue_one(enq + b));
+        enq += cnt;
+        if (hipMemcpyAsync(&hp[s], ctl_dev, sizeof(TreeCtl), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipEventRecord(c->tree_ev[s], c->stream) != hipSuccess)
+            return fail(c, HGMM_ERR_HIP, "%s: device error: %s", what, hipGetErrorString(hipGetLastError()));
+        return HGMM_OK;
+    };
+    HGMM_TRY(enqueue_batch(slot));
+    while (true) {
+        const bool ahead = enq < budget;
+        if (ahead) HGMM_TRY(enqueue_batch(slot ^ 1));
+        if (hipEventSynchronize(c->tree_ev[slot]) != hipSuccess)
+            return fail(c, HGMM_ERR_HIP, "%s: device error: %s", what, hipGetErrorString(hipGetLastError()));
+        *it = hp[slot].it;
+        if (hp[slot].done != 0) return HGMM_OK;
+        if (!ahead) return fail(c, HGMM_ERR_STATE, "%s did not stop within its budget", what);      // cannot happen; never spin
+        slot ^= 1;
+    }
+}
+
+// ---- the workspace of a tree build, serial or forest ----------------------------------------------------------------------
+// The partition's tables and the buffers the points travel through, for n points (n_pad: the arrays' stride) in at most
+// maxP parent segments at the last of L levels.  The resident cloud (level-0 order == sorted order at level 0) and its
+// weights are never overwritten: the first scatter goes A -> B (t_parent), later ones alternate between B and a third
+// buffer C (t_xs3); the weights' buffers (t_w2, t_w3) pair up with the coordinates'.
+struct BuildWorkspace {
+    int *chunk_first, *n_chunks_dev;            // t_seg: two segment tables [8 maxP + 2], chunk_first [2 (maxP + 2)], the chunk count
+    int *chunk_desc, *hist, *chunk_off;         // t_chunks: [max_chunks][3], then [max_chunks][8] twice
+    double* partials;                           // t_partials: [max_chunks][8][NMOM]
+    int* cur[2];                                // t_current: two assignments (iteration e of an overlapped level writes buffer e & 1)
+    // this level's points, weights (NULL: none) and segment table, and where the partition puts the next level's
+    const double *xs, *w;
+    double *xs_next, *w_next;
+    int *seg, *seg_next;
+    double *xs_b, *xs_c, *w_b, *w_c;            // the buffers B and C of the points and of the weights
+
+    // xs0 / w0: the resident cloud and its weights (w0 == NULL: an unweighted build)
+    int take(hgmm_ctx* c, int64_t n, int64_t n_pad, int64_t maxP, int L, const double* xs0, const double* w0) {
+        const bool weighted = w0 != nullptr;
+        const int64_t max_chunks = n / CH + maxP + 8;
+        HGMM_TRY(ensure(c, c->t_current, sizeof(int) * 2 * n_pad));
+        HGMM_TRY(ensure(c, c->t_parent, sizeof(double) * 3 * n_pad));
+        if (weighted) HGMM_TRY(ensure(c, c->t_w2, sizeof(double) * n_pad));
+        HGMM_TRY(ensure(c, c->t_seg, sizeof(int) * (2 * (8 * maxP + 2) + 2 * (maxP + 2) + 8)));
+        HGMM_TRY(ensure(c, c->t_chunks, sizeof(int) * (size_t)(3 + 8 + 8) * max_chunks));
+        HGMM_TRY(ensure(c, c->t_partials, sizeof(double) * (size_t)8 * NMOM * max_chunks));
+        if (L > 2) HGMM_TRY(ensure(c, c->t_xs3, sizeof(double) * 3 * n_pad));
+        if (L > 2 && weighted) HGMM_TRY(ensure(c, c->t_w3, sizeof(double) * n_pad));
+        seg = c->t_seg.as<int>();
+        seg_next = seg + (8 * maxP + 2);
+        chunk_first = seg_next + (8 * maxP + 2);
+        n_chunks_dev = chunk_first + (maxP + 2) * 2;
+        chunk_desc = c->t_chunks.as<int>();
+        hist = chunk_desc + 3 * max_chunks;
+        chunk_off = hist + 8 * max_chunks;
+        partials = c->t_partials.as<double>();
+        cur[0] = c->t_current.as<int>();
+        cur[1] = cur[0] + n_pad;
+        xs_b = c->t_parent.as<double>();
+        xs_c = L > 2 ? c->t_xs3.as<double>() : nullptr;
+        w_b = weighted ? c->t_w2.as<double>() : nullptr;
+        w_c = (weighted && L > 2) ? c->t_w3.as<double>() : nullptr;
+        xs = xs0;
+        w = w0;
+        xs_next = xs_b;
+        w_next = w_b;
+        return HGMM_OK;
+    }
+    // the partition has been enqueued: the next level's buffers become the current ones (A -> B -> C -> B -> ...)
+    void advance() {
+        xs = xs_next;
+        w = w_next;
+        std::swap(seg, seg_next);
+        xs_next = (xs == xs_b) ? xs_c : xs_b;
+        w_next = (xs == xs_b) ? w_c : w_b;
+    }
+};
+
+// The levels' q traces back to back, as both builds hand them out: copy(at, l, take) puts the first `take` = min(iters[l],
+// trace_cap) values of level l at position `at` of the caller's array, as far as q_capacity reaches.  Returns sum iters.
+template <class Copy>
+inline int gather_traces(const int* iters, int L, int trace_cap, int q_capacity, Copy&& copy) {
+    int at = 0;
+    for (int l = 0; l < L; ++l) {
+        const int take = std::min(std::min(iters[l], trace_cap), q_capacity - at);
+        if (take > 0) copy(at, l, take);
+        at += iters[l];
+    }
+    return at;
 }
 
 // ---- the fixed-point moment sums (t_momq, fr_momq) --------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "tree_host.h"
 
 #include <algorithm>
+#include <numeric>
 #include <type_traits>
 #include <cmath>
 #include <cstdlib>
@@ -32,7 +33,6 @@
 #include <vector>
 
 namespace hgmm {
-
 
 __global__ void tree_prep_kernel(const double* __restrict__ pi, const double* __restrict__ mu,
                                  const double* __restrict__ cov, int64_t j_begin, int64_t j_end,
@@ -128,8 +128,7 @@ __global__ __launch_bounds__(CH) void tree_estep_kernel(
     const double* __restrict__ xs, int64_t n_pad, const double* __restrict__ prep,
     const int* __restrict__ chunk_desc, const int* __restrict__ n_chunks, int64_t parent_level_first,
     int level, double* __restrict__ partials, int* __restrict__ cur_sorted, const int* __restrict__ done,
-    TreeFollow follow = TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr},
-    const double* __restrict__ w = nullptr) {
+    TreeFollow follow = NO_FOLLOW, const double* __restrict__ w = nullptr) {
     __shared__ double smem[tree_estep_lds<HALF>()];
     tree_estep_body<HALF, false, WEIGHTED>(
         (int)blockIdx.x,
@@ -137,7 +136,6 @@ __global__ __launch_bounds__(CH) void tree_estep_kernel(
                       WEIGHTED ? w : nullptr},
         follow, smem);
 }
-
 
 // fixed-order reduction of the chunk partials of one node (64 threads); with `fuse` the same
 // workgroup goes on to the node's M-step + preparation (single-GPU: no all-reduce in between)
@@ -147,8 +145,7 @@ __global__ __launch_bounds__(64) void tree_moments_kernel(const double* __restri
                                                           int fuse, int64_t lb, double n_points_total, double ld,
                                                           double* pi, double* mu, double* cov, double* prep,
                                                           int* __restrict__ flags, const int* __restrict__ done,
-                                                          TreeFollow follow = TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0,
-                                                                                         0, nullptr, 0, nullptr}) {
+                                                          TreeFollow follow = NO_FOLLOW) {
     const int cl = blockIdx.x;            // level-local child index
     if (cl >= n_level_nodes) return;
     const int p = cl >> 3, k = cl & 7;
@@ -256,9 +253,8 @@ __global__ __launch_bounds__(CH) void tree_ll_estep_kernel(TreeLoglikArgs la, in
         if constexpr (F32) tree_loglik_f32_body<PTS, false, WEIGHTED>(b % gx, b / gx, gx, gy, la, smem);
         else tree_loglik_body<PTS, false, false, WEIGHTED>(b % gx, b / gx, gx, gy, la, smem);
     } else
-        tree_estep_body<true, false, WEIGHTED>(b - nll, ea, TreeFollow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr}, smem);
+        tree_estep_body<true, false, WEIGHTED>(b - nll, ea, NO_FOLLOW, smem);
 }
-
 
 // FASTLOG: the float32-pdf mode's logarithm (log_pos_f64, as in tree_loglik_f32_body's own finish for forests)
 // WEIGHTED: lq = w_i log(...) -- the split form's partial sums are unweighted (tree_loglik_body)
@@ -304,7 +300,7 @@ __global__ void tree_ctl_kernel(const double* __restrict__ q_dev, TreeCtl* __res
 // (`done`: skip when the loop this launch belongs to has stopped; `stop`: apply the loop's stop rule to the sum)
 __global__ __launch_bounds__(256) void tree_sum_kernel(const double* __restrict__ v, int n, double* out,
                                                        const int* __restrict__ done = nullptr,
-                                                       TreeStop stop = TreeStop{nullptr, 0.0, 0, nullptr, 0}) {
+                                                       TreeStop stop = NO_STOP) {
     // single workgroup, fixed order
     const int stop_flag = done ? *done : 0;                // (requested together with the shares)
     __shared__ double sh[4];
@@ -332,15 +328,8 @@ __global__ __launch_bounds__(CH) void tree_hist_kernel(const int* __restrict__ c
     const int c = blockIdx.x;
     if (c >= *n_chunks) return;
     const int begin = chunk_desc[3 * c + 1], end = chunk_desc[3 * c + 2];
-    const int i = begin + (int)threadIdx.x;
-    const int key = (i < end) ? (cur_sorted[i] & 7) : -1;
     __shared__ int sh[CH / 64][8];
-    const int w = wave_in_block();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const unsigned long long m = __ballot(key == k);
-        if (lane_id() == 0) sh[w][k] = __popcll(m);
-    }
+    tree_hist_waves(cur_sorted, begin, end, sh);
     __syncthreads();
     if (threadIdx.x < 8) {
         int t = 0;
@@ -348,7 +337,6 @@ __global__ __launch_bounds__(CH) void tree_hist_kernel(const int* __restrict__ c
         hist[c * 8 + threadIdx.x] = t;
     }
 }
-
 
 // one WORKGROUP per parent: new segment sizes + per-chunk write offsets (relative to the parent's segment start,
 // children laid out k = 0..7 inside it).  Level 0 has ONE parent owning every chunk of the cloud (3907 at N = 1M):
@@ -424,28 +412,7 @@ __global__ __launch_bounds__(CH) void tree_scatter_kernel(
     const int c = blockIdx.x;
     if (c >= *n_chunks) return;
     const int begin = chunk_desc[3 * c + 1], end = chunk_desc[3 * c + 2];
-    const int i = begin + (int)threadIdx.x;
-    const bool active = i < end;
-    const int key = active ? (cur_sorted[i] & 7) : -1;
-    __shared__ int sh[CH / 64][8];
-    const int w = wave_in_block(), lane = lane_id();
-    int rank_in_wave = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const unsigned long long m = __ballot(key == k);
-        if (key == k) rank_in_wave = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) sh[w][k] = __popcll(m);
-    }
-    __syncthreads();
-    if (!active) return;
-    int before = 0;
-    for (int ww = 0; ww < w; ++ww) before += sh[ww][key];
-    const int dst = chunk_off[c * 8 + key] + before + rank_in_wave;
-    xs_new[dst] = xs[i];
-    xs_new[n_pad + dst] = xs[n_pad + i];
-    xs_new[2 * n_pad + dst] = xs[2 * n_pad + i];
-    perm_new[dst] = perm[i];
-    if constexpr (WEIGHTED) wts_new[dst] = wts[i];
+    tree_scatter_body<WEIGHTED, true>(cur_sorted, c, begin, end, xs, n_pad, chunk_off, xs_new, perm, perm_new, wts, wts_new);
 }
 
 __global__ void tree_iota_kernel(int* perm, int64_t n) {
@@ -457,7 +424,6 @@ __global__ void tree_unsort_kernel(const int* __restrict__ perm, const int* __re
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[perm[i]] = cur_sorted[i];
 }
-
 
 // (GATED: hgmm_tree_set_reg_gate's finite gate, tree_reg_estep_body; the gate-off instantiations do not read the argument)
 // (WEIGHTED: hgmm_tree_set_target_weights' array w [n_pad], likewise: the unweighted instantiations do not read the pointer)
@@ -475,10 +441,9 @@ __global__ __launch_bounds__(CH) void tree_reg_estep_kernel(const double* __rest
 }
 // the instantiation for the context's gate and weights
 template <int NMQ>
-static auto tree_reg_estep_kernel_for(bool gated, bool weighted) -> decltype(&tree_reg_estep_kernel<NMQ, false, false>) {
-    if (weighted) return gated ? tree_reg_estep_kernel<NMQ, true, true> : tree_reg_estep_kernel<NMQ, false, true>;
-    return gated ? tree_reg_estep_kernel<NMQ, true, false> : tree_reg_estep_kernel<NMQ, false, false>;
-}
+struct TreeRegEstepFamily { template <bool GATED, bool W> static auto kernel() { return tree_reg_estep_kernel<NMQ, GATED, W>; } };
+template <int NMQ>
+static auto tree_reg_estep_kernel_for(bool gated, bool weighted) { return kernel_for<TreeRegEstepFamily<NMQ>>(gated, weighted); }
 
 // score of the resident target against the resident tree (tree_score_body, csrc/tree_device.h): workgroup b writes its six
 // sums to partial[b]; tree_score_finish_kernel (one workgroup) adds them in a fixed order into summary[8]
@@ -632,6 +597,211 @@ static int tree_prep(hgmm_ctx* c, int64_t jb, int64_t je) {
     return HGMM_OK;
 }
 
+// ---- the kernel families of the build (kernel_for, tree_host.h; the last flag: WEIGHTED, hgmm_tree_set_source_weights) ----
+struct EstepFamily { template <bool HALF, bool W> static auto kernel() { return tree_estep_kernel<HALF, W>; } };
+// (two points per thread: `overlap` excludes the four-point form)
+struct LlEstepFamily { template <bool F32, bool W> static auto kernel() { return tree_ll_estep_kernel<2, F32, W>; } };
+struct LoglikF32Family { template <bool FOUR, bool W> static auto kernel() { return tree_loglik_f32_kernel<FOUR ? 4 : 2, W>; } };
+// (four points per thread come with the large exp table)
+struct LoglikFamily { template <bool FOUR, bool W> static auto kernel() { return tree_loglik_kernel<FOUR ? 4 : 2, FOUR, W>; } };
+struct LoglikFinishFamily { template <bool FASTLOG, bool W> static auto kernel() { return tree_loglik_finish_kernel<FASTLOG, W>; } };
+struct ScatterFamily { template <bool W> static auto kernel() { return tree_scatter_kernel<W>; } };
+
+// ---- how hgmm_tree_build runs a cloud: the five modes, decided here and nowhere else -------------------------------------
+struct BuildPlan { int ll_pts; bool estep_half; int batch_iters, ahead_iters; bool use_follow, overlap; };
+static BuildPlan build_plan(hgmm_ctx* c) {
+    BuildPlan p;
+    const int64_t n = c->n;
+    // points per thread in the log-likelihood kernel (N = 1e6, L = 4 build: 10.2 / 8.4 / 8.0 ms with 1 / 2 / 4)
+    // (one point per thread for small clouds was tried in round 3: C4 level 0 / 1 got slower, 11.5 / 16.0 vs 9.2 / 15.4 us --
+    //  these launches are chains of memory round trips, not arithmetic)
+    p.ll_pts = n >= 400000 ? 4 : 2;
+    // (a 64-point / node-split form of the log-likelihood for small clouds -- four waves of a workgroup sharing 64 points and
+    //  splitting the nodes, no finish pass -- was built and measured in round 3 and lost at every C4 level: 16.9 / 17.7 /
+    //  20.2 / 49 us per iteration against 8.9 / 14.8 / 19.1 / 22.4 for this form: eight times as many workgroups each read
+    //  the level's whole node table for the reach test; removed again, commit 7d926ef, DESIGN.md section 6)
+    // the E-step's LDS transpose in two passes (half the LDS, twice the resident workgroups) once a level has more chunks
+    // than the chip holds at a time
+    p.estep_half = n / CH > (int64_t)3 * c->cus;
+    // iterations enqueued per batch.  Round 2 (host waits at every batch boundary): 1/2/4/8/16 -> 6.8/6.3/5.6/5.1/5.3 ms @C4.
+    // With the host one batch ahead (run_batches) a level that stops at iteration k still has (ceil(k / B) + 1) B - k
+    // iterations enqueued behind the stop (46 over C4's four levels at B = 8, 22 at B = 4) -- but each of those is three
+    // launches that return at their first load, and a batch boundary (control-word copy + event) costs more than it
+    // saves: 2/4/8 -> 3.67/3.60/3.46 ms @C4, 5.12/5.07/5.02 @1M on one box.
+    p.batch_iters = 8;
+    // single GPU: progress word in pinned host memory, polled (follow_ahead); HGMM_TREE_AHEAD=0 -> the batch scheme
+    // (C4, one box: batch scheme 3.16-3.6 ms; 1 / 2 / 3 / 4 / 6 iterations ahead: 3.39 / 2.88 / 3.0 / 2.94 / 2.97 ms -- with one
+    //  the device waits for the host after every iteration; the host needs ~10 us to enqueue what the device runs in ~25)
+    // (under a communicator too, round 6: every rank reads the same reduced q, so every rank's stop rule says the same and
+    //  every rank's host can follow its own device's progress word)
+    p.ahead_iters = c->cfg[CFG_TREE_AHEAD];
+    // the stop rule inside the next launch (tree_follow) instead of a ticketed tail of the log-likelihood: needs the
+    // polled scheme with >= 2 iterations ahead (the verdict on iteration e is reached by launch e + 1)
+    p.use_follow = !c->comm_on() && p.ahead_iters >= 2 && !c->cfg[CFG_TREE_TICKETS];
+    // small clouds: iteration e + 1's (speculative) E-step rides in iteration e's log-likelihood launch and the moments
+    // kernel takes over the stop rule (tree_ll_estep_kernel); HGMM_TREE_OVERLAP=0 -> one launch each, as for large clouds
+    p.overlap = p.use_follow && p.ahead_iters > 0 && !p.estep_half && p.ll_pts != 4 && c->cfg[CFG_TREE_OVERLAP];
+    return p;
+}
+
+// ---- one level of the serial build: everything an iteration's launches take, and the iteration itself ------------------
+// The stop rule runs on the device; the host enqueues iterations ahead of it (follow_ahead / run_batches), so launches
+// overlap execution.  Kernels of iterations enqueued past the stop return immediately.  With a communicator the
+// all-reduces of the enqueued iterations cannot be predicated, so they run out of place: rank-local moments / q stay where
+// the (skipped) kernels left them, the reduced copies are rebuilt identically, the M-step and the stop rule read the
+// copies -- surplus iterations are idempotent and no per-iteration host round trip is needed.
+struct BuildLevel {
+    hgmm_ctx* c;
+    const BuildPlan& plan;
+    const BuildWorkspace& ws;
+    int l, P;                        // the level and its parent segments
+    double ls, ld, n_total;
+    int max_iters, trace_cap;
+    unsigned long long* host_word_dev;   // the progress word of the polled scheme; NULL: the batch scheme
+    // ---- set by prepare() ----
+    int64_t lb, parent_first;        // the level's first node, n_level of them; the first node of the level above
+    int n_level;
+    unsigned grid_chunks;
+    // small clouds do not have enough 256-point blocks to fill the chip: the level's nodes are split over gridDim.y of the
+    // log-likelihood launch (`chunks` of per_chunk nodes) and the per-chunk sums added in a second (fixed-order) kernel
+    int pblocks, llblocks;           // point blocks; the log-likelihood grid: ll_pts points per thread
+    int chunks, per_chunk;
+    double *ll_partial, *block_q, *q_dev, *trace_dev;
+    TreeCtl* ctl;
+    TreeLoopState* loop_state;       // two slots (tree_follow), right behind ctl
+    int* curbuf[2];                  // (overlap: iteration e's assignment is curbuf[e & 1]; else always the same buffer)
+    double *mom_g, *q_g;             // communicator: the reduced copies of the moments and of q
+
+    // the level's chunk table, its buffers, and a fresh stop rule
+    int prepare() {
+        const int64_t n = c->n;
+        lb = level_first(l);
+        n_level = (int)(level_first(l + 1) - lb);
+        parent_first = (l == 0) ? 0 : level_first(l - 1);
+        tree_chunks_kernel<<<1, 1024, 0, c->stream>>>(ws.seg, P, ws.chunk_first, ws.chunk_desc, ws.n_chunks_dev);
+        grid_chunks = (unsigned)(n / CH + P + 1);
+        pblocks = (int)nblk(n, CH);
+        llblocks = (int)nblk(n, CH * plan.ll_pts);
+        tree_ll_split(llblocks, n_level, c->cus, &chunks, &per_chunk);
+        ll_partial = nullptr;
+        if (chunks > 1) {
+            HGMM_TRY(ensure(c, c->t_llp, sizeof(double) * (size_t)chunks * c->n_pad));
+            ll_partial = c->t_llp.as<double>();
+        }
+        block_q = c->t_q.as<double>();
+        q_dev = block_q + pblocks;
+        ctl = reinterpret_cast<TreeCtl*>(q_dev + 2);
+        loop_state = reinterpret_cast<TreeLoopState*>(q_dev + 4);
+        trace_dev = c->t_qtrace.as<double>() + (size_t)l * trace_cap;
+        curbuf[0] = ws.cur[0];
+        curbuf[1] = plan.overlap ? ws.cur[1] : ws.cur[0];
+        // (ctl and the two loop-state slots of tree_follow behind it: 48 contiguous bytes)
+        HGMM_HIP(c, hipMemsetAsync(ctl, 0, sizeof(TreeCtl) + 2 * sizeof(TreeLoopState), c->stream));
+        mom_g = nullptr;
+        q_g = q_dev;
+        if (c->comm_on()) {
+            HGMM_TRY(ensure(c, c->comm_buf, sizeof(double) * ((size_t)NMOM * n_level + 8)));
+            mom_g = c->comm_buf.as<double>();
+            q_g = mom_g + (size_t)NMOM * n_level;
+        }
+        return HGMM_OK;
+    }
+    // level 0 of an overlapped build: q comes out of the (next iteration's) E-step, one share per chunk (TreeEstepArgs)
+    bool fused0() const { return plan.overlap && l == 0; }
+    // follow mode (single GPU, polled look-ahead): launch e of the E-step adds up the shares of q that iteration e - 1
+    // left behind and applies the stop rule itself (tree_follow); the log-likelihood kernels only store their shares
+    TreeFollow follow_of(int e) const {
+        const int q_shares = (fused0() || chunks > 1) ? pblocks : llblocks;
+        return TreeFollow{block_q, q_shares, loop_state + ((e - 1) & 1), loop_state + (e & 1), &ctl->done, ls,
+                          max_iters, trace_dev, trace_cap, host_word_dev};
+    }
+    // One EM iteration of the level, enqueued (every kernel looks at ctl->done first and returns at once when it has stopped)
+    int enqueue(int e) const {
+        const bool weighted = ws.w != nullptr;
+        const int64_t n = c->n, n_pad = c->n_pad;
+        double *d_pi = c->t_pi.as<double>(), *d_mu = c->t_mu.as<double>(), *d_cov = c->t_cov.as<double>();
+        double *d_prep = c->t_prep.as<double>(), *d_mom = c->t_mom.as<double>();
+        const bool overlap = plan.overlap, use_follow = plan.use_follow;
+        if (!overlap || e == 0) {
+            ProfScope prof(c, HGMM_K_TREE_ESTEP);
+            const TreeFollow fol = (use_follow && e >= 1) ? follow_of(e) : NO_FOLLOW;
+            const auto estep = kernel_for<EstepFamily>(plan.estep_half, weighted);
+            estep<<<grid_chunks, CH, 0, c->stream>>>(
+                ws.xs, n_pad, d_prep, ws.chunk_desc, ws.n_chunks_dev, parent_first, l, ws.partials, curbuf[e & 1], &ctl->done, fol, ws.w);
+        }
+        // single GPU: reduction, M-step and preparation of a node in one launch; with a communicator the all-reduce of the
+        // moments sits between reduction and M-step
+        // (small clouds below level 0: a wave per parent, same bits.  Level 0 is ONE parent with all of the cloud's chunks:
+        //  eight waves gathering side by side are 3 us quicker than one wave taking the eight rows in turn)
+        if (overlap && l > 0)
+            tree_moments8_kernel<<<n_level / 8, 64, 0, c->stream>>>(ws.partials, ws.chunk_first, d_mom + NMOM * lb, lb, n_total,
+                                                                    ld, d_pi, d_mu, d_cov, d_prep, flags_ptr(c), &ctl->done,
+                                                                    e >= 1 ? follow_of(e) : NO_FOLLOW);
+        else
+            tree_moments_kernel<<<n_level, 64, 0, c->stream>>>(ws.partials, ws.chunk_first, n_level, d_mom + NMOM * lb,
+                                                               c->comm_on() ? 0 : 1, lb, n_total, ld, d_pi, d_mu, d_cov,
+                                                               d_prep, flags_ptr(c), &ctl->done,
+                                                               (overlap && e >= 1) ? follow_of(e) : NO_FOLLOW);
+        if (c->comm_on()) {
+            HGMM_TRY(allreduce_f64_oop(c, d_mom + NMOM * lb, mom_g, (size_t)NMOM * n_level));
+            tree_mstep_kernel<<<nblk(n_level, 256), 256, 0, c->stream>>>(mom_g, lb, n_level, n_total, ld, d_pi,
+                                                                         d_mu, d_cov, d_prep, flags_ptr(c), &ctl->done, 0);
+        }
+        {
+            ProfScope prof(c, HGMM_K_TREE_LOGLIK);
+            // the last workgroup to finish adds up the per-block shares of q (store_block_q) ... and, on a single GPU, applies
+            // the level's stop rule (with a communicator q is all-reduced first and tree_ctl_kernel does it)
+            const TreeStop stop = (c->comm_on() || use_follow)
+                                      ? NO_STOP
+                                      : TreeStop{ctl, ls, max_iters, trace_dev, trace_cap, host_word_dev};
+            // follow mode: plain stores of the shares  (the tickets: zeroed by tree_flags; every launch leaves them zero)
+            unsigned int* q_ticket = use_follow ? nullptr : tickets_ptr(c);
+            // (the positional kernels take the same list, field by field)
+            TreeLoglikArgs la{ws.xs, n, n_pad, d_prep, lb, n_level, per_chunk, ll_partial, block_q, q_ticket,
+                              q_dev, &ctl->done, chunks > 1 ? NO_STOP : stop, flags_ptr(c), pairs_ptr(c), nullptr,
+                              0, 0, ws.w};
+            const dim3 ll_grid(llblocks, chunks);
+            const bool four = plan.ll_pts == 4;
+            if (overlap && (e + 1 < max_iters || fused0())) {
+                // (level 0: no log-likelihood workgroups at all -- the E-step stores the shares of q; behind the
+                //  budget's last iteration it runs for those alone, its moments and assignment are never read)
+                la.stop = NO_STOP;
+                const TreeEstepArgs ea{ws.xs, n_pad, d_prep, ws.chunk_desc, ws.n_chunks_dev, parent_first, l, ws.partials,
+                                       curbuf[(e + 1) & 1], &ctl->done, fused0() ? block_q : nullptr, ws.w};
+                const int gx = fused0() ? 0 : llblocks, gy = fused0() ? 0 : chunks;
+                const unsigned g = (unsigned)(gx * gy) + grid_chunks;
+                const auto fused = kernel_for<LlEstepFamily>(c->tree.pdf_f32, weighted);
+                fused<<<g, CH, 0, c->stream>>>(la, gx, gy, ea);
+            } else if (c->tree.pdf_f32) {
+                const auto ll = kernel_for<LoglikF32Family>(four, weighted);
+                ll<<<ll_grid, CH, 0, c->stream>>>(la);
+            } else {
+                ll_positional(kernel_for<LoglikFamily>(four, weighted), ll_grid, c->stream, la,
+                              four ? c->exp_tab2.as<double>() : nullptr);
+            }
+            if (chunks > 1 && !fused0()) {
+                const auto finish = kernel_for<LoglikFinishFamily>(c->tree.pdf_f32, weighted);
+                finish<<<pblocks, CH, 0, c->stream>>>(ll_partial, n, n_pad, chunks, block_q, q_ticket, q_dev, &ctl->done, stop, ws.w);
+            }
+        }
+        if (c->comm_on()) {
+            HGMM_TRY(allreduce_f64_oop(c, q_dev, q_g, 1));
+            tree_ctl_kernel<<<1, 1, 0, c->stream>>>(q_g, ctl, ls, max_iters, trace_dev, trace_cap, host_word_dev);
+        }
+        // a launch the runtime rejected (LDS / grid limits of another chip) would leave the progress word untouched
+        // for ever: the host loops must hear about it here
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build: kernel launch failed: %s", hipGetErrorString(le));
+        return HGMM_OK;
+    }
+    // follow mode: nobody follows the budget's last iteration -- one workgroup accounts for its q
+    int close() const {
+        tree_close_kernel<<<1, CH, 0, c->stream>>>(follow_of(max_iters));
+        if (hipGetLastError() != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build: launch failed");
+        return HGMM_OK;
+    }
+};
+
 }  // namespace hgmm
 
 using namespace hgmm;
@@ -653,372 +823,97 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     if (max_iters_per_level < 1) max_iters_per_level = 1;
     HGMM_HIP(c, hipSetDevice(c->device));
     HGMM_TRY(tree_alloc_nodes(c, L));
+    const BuildPlan plan = build_plan(c);
+    if (plan.ll_pts == 4) HGMM_TRY(ensure_exp_tab2(c));
+
     const int64_t T = c->tree.T;
     const int64_t n = c->n, n_pad = c->n_pad;
     int64_t maxP = 1;
     for (int i = 0; i < L - 1; ++i) maxP *= 8;                 // parents at the last level
-    const int64_t max_chunks = n / CH + maxP + 8;
-    // buffers
+    BuildWorkspace ws;
+    HGMM_TRY(ws.take(c, n, n_pad, maxP, L, c->x_soa64.as<double>(), weighted ? c->src_w.as<double>() : nullptr));
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * 3 * T));
-    HGMM_TRY(ensure(c, c->t_current, sizeof(int) * 2 * n_pad));              // two assignments (tree_ll_estep_kernel)
     HGMM_TRY(ensure(c, c->t_perm, sizeof(int) * 2 * n_pad));                 // ping-pong
-    HGMM_TRY(ensure(c, c->t_parent, sizeof(double) * 3 * n_pad));            // second coordinate buffer
-    if (weighted) HGMM_TRY(ensure(c, c->t_w2, sizeof(double) * n_pad));       // ... and the weights' beside it
-    HGMM_TRY(ensure(c, c->t_seg, sizeof(int) * (2 * (8 * maxP + 2) + 2 * (maxP + 2) + 8)));
-    HGMM_TRY(ensure(c, c->t_chunks, sizeof(int) * (size_t)(3 + 8 + 8) * max_chunks));
-    HGMM_TRY(ensure(c, c->t_partials, sizeof(double) * (size_t)8 * NMOM * max_chunks));
     HGMM_TRY(ensure(c, c->t_q, sizeof(double) * (nblk(n, CH) + 8)));
-
-    double* d_pi = c->t_pi.as<double>();
-    double* d_mu = c->t_mu.as<double>();
-    double* d_cov = c->t_cov.as<double>();
-    double* d_prep = c->t_prep.as<double>();
-    double* d_mom = c->t_mom.as<double>();
-    // coordinate ping-pong: A = x_soa64 (original order == sorted order at level 0), B = t_parent
-    double* xs_a = c->x_soa64.as<double>();
-    double* xs_b = c->t_parent.as<double>();
-    int* perm_a = c->t_perm.as<int>();
-    int* perm_b = perm_a + n_pad;
-    int* cur = c->t_current.as<int>();
-    int* seg_a = c->t_seg.as<int>();
-    int* seg_b = seg_a + (8 * maxP + 2);
-    int* chunk_first = seg_b + (8 * maxP + 2);
-    int* n_chunks_dev = chunk_first + (maxP + 2) * 2;
-    int* chunk_desc = c->t_chunks.as<int>();
-    int* hist = chunk_desc + 3 * max_chunks;
-    int* chunk_off = hist + 8 * max_chunks;
-    double* partials = c->t_partials.as<double>();
-    double* block_q = c->t_q.as<double>();
-    double* q_dev = block_q + nblk(n, CH);
-    unsigned int* q_ticket_buf = tickets_ptr(c);              // (zeroed by tree_alloc_nodes -> tree_flags; every launch leaves them zero)
-    TreeCtl* ctl = reinterpret_cast<TreeCtl*>(q_dev + 2);
-    TreeLoopState* loop_state = reinterpret_cast<TreeLoopState*>(q_dev + 4);     // two slots (tree_follow), right behind ctl
     const int trace_cap = std::min(max_iters_per_level, 1 << 20);
     HGMM_TRY(ensure(c, c->t_qtrace, sizeof(double) * (size_t)trace_cap * L));     // one segment per level, read back at the end
-    double* trace_base = c->t_qtrace.as<double>();
-    std::vector<int> level_iters(L, 0);
-    // points per thread in the log-likelihood kernel (N = 1e6, L = 4 build: 10.2 / 8.4 / 8.0 ms with 1 / 2 / 4)
-    // (one point per thread for small clouds was tried in round 3: C4 level 0 / 1 got slower, 11.5 / 16.0 vs 9.2 / 15.4 us --
-    //  these launches are chains of memory round trips, not arithmetic)
-    const int ll_pts = n >= 400000 ? 4 : 2;
-    // (a 64-point / node-split form of the log-likelihood for small clouds -- four waves of a workgroup sharing 64 points and
-    //  splitting the nodes, no finish pass -- was built and measured in round 3 and lost at every C4 level: 16.9 / 17.7 /
-    //  20.2 / 49 us per iteration against 8.9 / 14.8 / 19.1 / 22.4 for this form: eight times as many workgroups each read
-    //  the level's whole node table for the reach test; removed again, commit 7d926ef, DESIGN.md section 6)
-    if (ll_pts == 4) HGMM_TRY(ensure_exp_tab2(c));
-    // the E-step's LDS transpose in two passes (half the LDS, twice the resident workgroups) once a level has more chunks
-    // than the chip holds at a time
-    const bool estep_half = n / CH > (int64_t)3 * c->cus;
-    // iterations enqueued per batch.  Round 2 (host waits at every batch boundary): 1/2/4/8/16 -> 6.8/6.3/5.6/5.1/5.3 ms @C4.
-    // With the host one batch ahead (below) a level that stops at iteration k still has (ceil(k / B) + 1) B - k
-    // iterations enqueued behind the stop (46 over C4's four levels at B = 8, 22 at B = 4) -- but each of those is three
-    // launches that return at their first load, and a batch boundary (control-word copy + event) costs more than it
-    // saves: 2/4/8 -> 3.67/3.60/3.46 ms @C4, 5.12/5.07/5.02 @1M on one box.
-    const int batch_iters = 8;
-    // single GPU: progress word in pinned host memory, polled (see the level loop); HGMM_TREE_AHEAD=0 -> the batch scheme
-    // (C4, one box: batch scheme 3.16-3.6 ms; 1 / 2 / 3 / 4 / 6 iterations ahead: 3.39 / 2.88 / 3.0 / 2.94 / 2.97 ms -- with one
-    //  the device waits for the host after every iteration; the host needs ~10 us to enqueue what the device runs in ~25)
-    const int ahead_iters = c->cfg[CFG_TREE_AHEAD];
-    // the stop rule inside the next launch (tree_follow) instead of a ticketed tail of the log-likelihood: needs the
-    // polled scheme with >= 2 iterations ahead (the verdict on iteration e is reached by launch e + 1)
-    const bool use_follow = !c->comm_on() && ahead_iters >= 2 && !c->cfg[CFG_TREE_TICKETS];
-    // small clouds: iteration e + 1's (speculative) E-step rides in iteration e's log-likelihood launch and the moments
-    // kernel takes over the stop rule (tree_ll_estep_kernel); HGMM_TREE_OVERLAP=0 -> one launch each, as for large clouds
-    const bool overlap = use_follow && ahead_iters > 0 && !estep_half && ll_pts != 4 && c->cfg[CFG_TREE_OVERLAP];
-    int* curbuf[2] = {cur, overlap ? cur + n_pad : cur};
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, 1, &hand));
-    unsigned long long* host_word = nullptr;                   // host address / device address of the same pinned word
-    unsigned long long* host_word_dev = nullptr;
-    // (under a communicator too, round 6: every rank reads the same reduced q, so every rank's stop rule says the same and
-    //  every rank's host can follow its own device's progress word -- see the level loop)
-    if (ahead_iters > 0) {
-        host_word = hand->progress(0).host;
-        host_word_dev = hand->progress(0).dev;
-    } else {
-        HGMM_TRY(tree_batch_events(c));
-    }
+    const HostDev<unsigned long long> word = hand->progress(0);       // the polled scheme's progress word
+    double *d_pi = c->t_pi.as<double>(), *d_mu = c->t_mu.as<double>(), *d_cov = c->t_cov.as<double>();
+    int* perm_cur = c->t_perm.as<int>();
+    int* perm_next = perm_cur + n_pad;
+    double* trace_base = c->t_qtrace.as<double>();
 
     HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * T, hipMemcpyHostToDevice, c->stream));
     tree_init_nodes_kernel<<<nblk(T, 256), 256, 0, c->stream>>>(c->scratch.as<double>(), sig2, T, d_pi, d_mu, d_cov);
     HGMM_TRY(tree_prep(c, 0, T));
-    tree_iota_kernel<<<nblk(n, 256), 256, 0, c->stream>>>(perm_a, n);
+    tree_iota_kernel<<<nblk(n, 256), 256, 0, c->stream>>>(perm_cur, n);
     const int seg0[2] = {0, (int)n};
-    HGMM_HIP(c, hipMemcpyAsync(seg_a, seg0, sizeof seg0, hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, hipMemcpyAsync(ws.seg, seg0, sizeof seg0, hipMemcpyHostToDevice, c->stream));
     HGMM_HIP(c, hipGetLastError());
 
     // global point count (pi = m0 / N_total); with weights their sum: point i counts as w_i points
     double n_total = weighted ? c->src_wsum : (double)n;
-    if (c->comm_on()) {
-        HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_total, 1, 0));
-    }
+    if (c->comm_on()) HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_total, 1, 0));
 
-    // the resident cloud (x_soa64 = level-0 order) is never overwritten: the first scatter goes
-    // A -> B, later ones alternate between B and a third buffer C
-    double* xs_c = nullptr;
-    if (L > 2) {
-        HGMM_TRY(ensure(c, c->t_xs3, sizeof(double) * 3 * n_pad));
-        xs_c = c->t_xs3.as<double>();
-        if (weighted) HGMM_TRY(ensure(c, c->t_w3, sizeof(double) * n_pad));
-    }
-    double* w_b = weighted ? c->t_w2.as<double>() : nullptr;
-    double* w_c = (weighted && L > 2) ? c->t_w3.as<double>() : nullptr;
-    const double* w_cur = weighted ? c->src_w.as<double>() : nullptr;     // (level-0 order, like x_soa64; never overwritten)
-
-    const double* xs_cur = xs_a;
-    int* perm_cur = perm_a;
-    int* seg_cur = seg_a;
-    int P = 1;
-    int q_len = 0;
-    int rc = HGMM_OK;
+    std::vector<int> level_iters(L, 0);
+    int P = 1, rc = HGMM_OK;
     for (int l = 0; l < L && rc == HGMM_OK; ++l) {
-        const int64_t lb = level_first(l), le = level_first(l + 1);
-        const int n_level = (int)(le - lb);
-        const int64_t parent_first = (l == 0) ? 0 : level_first(l - 1);
-        double* trace_dev = trace_base + (size_t)l * trace_cap;
-        tree_chunks_kernel<<<1, 1024, 0, c->stream>>>(seg_cur, P, chunk_first, chunk_desc, n_chunks_dev);
-        const unsigned grid_chunks = (unsigned)(n / CH + P + 1);
-        // small clouds do not have enough 256-point blocks to fill the chip: split the level's nodes
-        // over gridDim.y and add the per-chunk sums in a second (fixed-order) kernel
-        const int pblocks = (int)nblk(n, CH);
-        const int llblocks = (int)nblk(n, CH * ll_pts);        // log-likelihood grid: ll_pts points per thread
-        int chunks = 1, per_chunk = n_level;
-        tree_ll_split(llblocks, n_level, c->cus, &chunks, &per_chunk);
-        double* ll_partial = nullptr;
-        if (chunks > 1) {
-            rc = ensure(c, c->t_llp, sizeof(double) * (size_t)chunks * n_pad);
-            if (rc != HGMM_OK) break;
-            ll_partial = c->t_llp.as<double>();
-        }
-        // The stop rule runs on the device (tree_ctl_kernel); the host enqueues `batch` iterations per
-        // synchronisation and reads {done, iterations} back, so launches overlap execution.  Kernels of
-        // iterations enqueued past the stop return immediately.  With a communicator the all-reduces of the
-        // enqueued iterations cannot be predicated, so they run out of place: rank-local moments / q stay where
-        // the (skipped) kernels left them, the reduced copies are rebuilt identically, the M-step and the stop
-        // rule read the copies -- surplus iterations are idempotent and no per-iteration host round trip is needed.
-        // (ctl and the two loop-state slots of tree_follow behind it: 48 contiguous bytes)
-        HGMM_HIP(c, hipMemsetAsync(ctl, 0, sizeof(TreeCtl) + 2 * sizeof(TreeLoopState), c->stream));
-        const int batch = batch_iters;
-        double* mom_g = nullptr;
-        double* q_g = q_dev;
-        if (c->comm_on()) {
-            rc = ensure(c, c->comm_buf, sizeof(double) * ((size_t)NMOM * n_level + 8));
-            if (rc != HGMM_OK) break;
-            mom_g = c->comm_buf.as<double>();
-            q_g = mom_g + (size_t)NMOM * n_level;
-        }
-        // One EM iteration of the level, enqueued (every kernel looks at ctl->done first and returns at once when the level
-        // has stopped).
-        // follow mode (single GPU, polled look-ahead): launch e of the E-step adds up the shares of q that iteration e - 1
-        // left behind and applies the stop rule itself (tree_follow); the log-likelihood kernels only store their shares
-        // level 0 of an overlapped build: q comes out of the (next iteration's) E-step, one share per chunk (TreeEstepArgs)
-        const bool fused0 = overlap && l == 0;
-        const int q_shares = (fused0 || chunks > 1) ? pblocks : llblocks;
-        auto follow_of = [&](int e) {
-            return TreeFollow{block_q, q_shares, loop_state + ((e - 1) & 1), loop_state + (e & 1), &ctl->done, ls,
-                              max_iters_per_level, trace_dev, trace_cap, host_word_dev};
-        };
-        auto enqueue_iteration = [&](int e) -> int {
-            int rc = HGMM_OK;
-            const TreeFollow no_follow{nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, 0, nullptr};
-            int* cur = curbuf[e & 1];                                      // (overlap: iteration e's assignment; else always the same)
-                if (!overlap || e == 0) {
-                    ProfScope prof(c, HGMM_K_TREE_ESTEP);
-                    const TreeFollow fol = (use_follow && e >= 1) ? follow_of(e) : no_follow;
-                    const auto estep = weighted ? (estep_half ? tree_estep_kernel<true, true> : tree_estep_kernel<false, true>)
-                                                : (estep_half ? tree_estep_kernel<true, false> : tree_estep_kernel<false, false>);
-                    estep<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l,
-                                                             partials, cur, &ctl->done, fol, w_cur);
-                }
-                // single GPU: reduction, M-step and preparation of a node in one launch; with a
-                // communicator the all-reduce of the moments sits between reduction and M-step
-                // (small clouds below level 0: a wave per parent, same bits.  Level 0 is ONE parent with all of the cloud's chunks:
-                //  eight waves gathering side by side are 3 us quicker than one wave taking the eight rows in turn)
-                if (overlap && l > 0)
-                    tree_moments8_kernel<<<n_level / 8, 64, 0, c->stream>>>(partials, chunk_first, d_mom + NMOM * lb, lb, n_total,
-                                                                            ld, d_pi, d_mu, d_cov, d_prep, flags_ptr(c), &ctl->done,
-                                                                            e >= 1 ? follow_of(e) : no_follow);
-                else
-                    tree_moments_kernel<<<n_level, 64, 0, c->stream>>>(partials, chunk_first, n_level, d_mom + NMOM * lb,
-                                                                       c->comm_on() ? 0 : 1, lb, n_total, ld, d_pi, d_mu, d_cov,
-                                                                       d_prep, flags_ptr(c), &ctl->done,
-                                                                       (overlap && e >= 1) ? follow_of(e) : no_follow);
-                if (c->comm_on()) {
-                    rc = allreduce_f64_oop(c, d_mom + NMOM * lb, mom_g, (size_t)NMOM * n_level);
-                    if (rc != HGMM_OK) return rc;
-                    tree_mstep_kernel<<<nblk(n_level, 256), 256, 0, c->stream>>>(mom_g, lb, n_level, n_total, ld, d_pi,
-                                                                                 d_mu, d_cov, d_prep, flags_ptr(c), &ctl->done, 0);
-                }
-                {
-                    ProfScope prof(c, HGMM_K_TREE_LOGLIK);
-                    // the last workgroup to finish adds up the per-block shares of q (store_block_q)
-                    // ... and, on a single GPU, applies the level's stop rule (with a communicator q is all-reduced
-                    // first and tree_ctl_kernel does it)
-                    const TreeStop no_stop{nullptr, 0.0, 0, nullptr, 0};
-                    const TreeStop stop = (c->comm_on() || use_follow)
-                                              ? no_stop
-                                              : TreeStop{ctl, ls, max_iters_per_level, trace_dev, trace_cap, host_word_dev};
-                    unsigned int* q_ticket = use_follow ? nullptr : q_ticket_buf;     // follow mode: plain stores of the shares
-                    // (the positional kernels take the same list, field by field)
-                    TreeLoglikArgs la{xs_cur, n, n_pad, d_prep, lb, n_level, per_chunk, ll_partial, block_q, q_ticket,
-                                      q_dev, &ctl->done, chunks > 1 ? no_stop : stop, flags_ptr(c), pairs_ptr(c), nullptr,
-                                      0, 0, w_cur};
-                    const dim3 ll_grid(llblocks, chunks);
-                    if (overlap && (e + 1 < max_iters_per_level || fused0)) {
-                        // (level 0: no log-likelihood workgroups at all -- the E-step stores the shares of q; behind the
-                        //  budget's last iteration it runs for those alone, its moments and assignment are never read)
-                        la.stop = no_stop;
-                        const TreeEstepArgs ea{xs_cur, n_pad, d_prep, chunk_desc, n_chunks_dev, parent_first, l, partials,
-                                               curbuf[(e + 1) & 1], &ctl->done, fused0 ? block_q : nullptr, w_cur};
-                        const int gx = fused0 ? 0 : llblocks, gy = fused0 ? 0 : chunks;
-                        const unsigned g = (unsigned)(gx * gy) + grid_chunks;
-                        // (ll_pts is 2 here: `overlap` excludes the four-point form)
-                        const auto fused = weighted ? (c->tree.pdf_f32 ? tree_ll_estep_kernel<2, true, true> : tree_ll_estep_kernel<2, false, true>)
-                                                    : (c->tree.pdf_f32 ? tree_ll_estep_kernel<2, true, false> : tree_ll_estep_kernel<2, false, false>);
-                        fused<<<g, CH, 0, c->stream>>>(la, gx, gy, ea);
-                    } else if (c->tree.pdf_f32) {
-                        const auto ll = weighted ? (ll_pts == 4 ? tree_loglik_f32_kernel<4, true> : tree_loglik_f32_kernel<2, true>)
-                                                 : (ll_pts == 4 ? tree_loglik_f32_kernel<4, false> : tree_loglik_f32_kernel<2, false>);
-                        ll<<<ll_grid, CH, 0, c->stream>>>(la);
-                    } else if (ll_pts == 4) {
-                        ll_positional(weighted ? tree_loglik_kernel<4, true, true> : tree_loglik_kernel<4, true, false>, ll_grid,
-                                      c->stream, la, c->exp_tab2.as<double>());
-                    } else {
-                        ll_positional(weighted ? tree_loglik_kernel<2, false, true> : tree_loglik_kernel<2, false, false>, ll_grid,
-                                      c->stream, la, nullptr);
-                    }
-                    if (chunks > 1 && !fused0) {
-                        const auto finish = weighted ? (c->tree.pdf_f32 ? tree_loglik_finish_kernel<true, true> : tree_loglik_finish_kernel<false, true>)
-                                                     : (c->tree.pdf_f32 ? tree_loglik_finish_kernel<true, false> : tree_loglik_finish_kernel<false, false>);
-                        finish<<<pblocks, CH, 0, c->stream>>>(ll_partial, n, n_pad, chunks, block_q, q_ticket, q_dev, &ctl->done,
-                                                              stop, w_cur);
-                    }
-                }
-                if (c->comm_on()) {
-                    rc = allreduce_f64_oop(c, q_dev, q_g, 1);
-                    if (rc != HGMM_OK) return rc;
-                    tree_ctl_kernel<<<1, 1, 0, c->stream>>>(q_g, ctl, ls, max_iters_per_level, trace_dev, trace_cap, host_word_dev);
-                }
-            // a launch the runtime rejected (LDS / grid limits of another chip) would leave the progress word untouched
-            // for ever: the loops below must hear about it here
-            const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return fail(c, HGMM_ERR_HIP, "tree build: kernel launch failed: %s", hipGetErrorString(le));
-            return HGMM_OK;
-        };
-        // The host stays ONE BATCH AHEAD of the device: batch k + 1 is enqueued before the host waits for batch k's
-        // verdict (an asynchronous copy of {done, iterations} into pinned memory + an event), so the device never idles
-        // at a batch boundary (round 2: enqueue, copy, synchronise, enqueue -- 30-40 us of idle device per batch, a
-        // quarter of C4's build).  The price: when a level stops, the batch enqueued ahead runs as skipped launches
-        // (~1 us each).  No batch is enqueued beyond the level's iteration budget.
+        BuildLevel lv{c, plan, ws, l, P, ls, ld, n_total, max_iters_per_level, trace_cap, plan.ahead_iters > 0 ? word.dev : nullptr};
+        rc = lv.prepare();
+        if (rc != HGMM_OK) break;
+        const auto enqueue = [&lv](int e) { return lv.enqueue(e); };
         int it = 0;
-        if (host_word) {
-            // Single GPU: the stop rule's last thread also stores (done << 32 | iterations) into a word of pinned HOST
-            // memory, and the host keeps `ahead` iterations enqueued beyond the last one it has seen finished -- no copy, no
-            // event, no synchronisation inside a level, and at most `ahead` iterations of skipped launches behind a stop
-            // (the batch scheme below: 46 of them over C4's four levels, ~0.25 ms of a 3.1 ms build, plus a control-word
-            // copy per batch).  The word is reset here: every launch that could write it belongs to this level.
-            __atomic_store_n(host_word, 0ull, __ATOMIC_RELAXED);
+        if (plan.ahead_iters > 0) {
+            // (the word is reset here: every launch that could write it belongs to this level)
+            __atomic_store_n(word.host, 0ull, __ATOMIC_RELAXED);
             int enq = 0;
-            unsigned spins = 0;
-            while (rc == HGMM_OK) {
-                const Progress pg = scan_progress(host_word, 1);              // (one word: its signature is the word)
-                it = (int)(pg.sig & 0xffffffffull);
-                if (pg.all_done) {                                              // the level has stopped after `it` iterations
-                    // Under a communicator every rank must have enqueued the SAME collectives when it leaves the level.
-                    // How far a rank's host had got when it saw the stop is a matter of timing; min(it + ahead, budget)
-                    // is not: each rank tops its queue up to exactly that many iterations (the surplus ones return at
-                    // their first load, their all-reduces run out of place on unchanged operands).  Round 5 looked at
-                    // the stop word once per 8 iterations, one batch behind: up to 15 surplus iterations per level,
-                    // 46 over C4's four levels; now `ahead` (2) per level, whatever the backend.
-                    if (c->comm_on()) {
-                        const int must = std::min(it + ahead_iters, max_iters_per_level);
-                        while (rc == HGMM_OK && enq < must) rc = enqueue_iteration(enq++);
-                        c->tree.surplus_iterations += (unsigned long long)(enq - it);
-                    }
-                    break;
-                }
-                if (enq < max_iters_per_level && enq - it < ahead_iters) {
-                    rc = enqueue_iteration(enq);
-                    ++enq;
-                    if (use_follow && rc == HGMM_OK && enq == max_iters_per_level) {
-                        // nobody follows the budget's last iteration: one workgroup accounts for its q
-                        tree_close_kernel<<<1, CH, 0, c->stream>>>(follow_of(enq));
-                        if (hipGetLastError() != hipSuccess) rc = fail(c, HGMM_ERR_HIP, "tree build: launch failed");
-                    }
-                    spins = 0;
-                    continue;
-                }
-                if (enq >= max_iters_per_level && it >= enq) {                // cannot happen (the budget's last iteration stops)
-                    rc = fail(c, HGMM_ERR_STATE, "tree build: level %d did not stop within its budget", l);
-                    break;
-                }
-                rc = device_watch(c, &spins, host_word, 1, pg.sig, "tree build: level %d (%d iterations enqueued, %d seen)", l, enq, it);
+            const auto close = [&lv, &plan] { return plan.use_follow ? lv.close() : HGMM_OK; };
+            rc = follow_ahead(c, word.host, 1, max_iters_per_level, plan.ahead_iters, enqueue, close, &enq, "tree build");
+            const unsigned long long w = __atomic_load_n(word.host, __ATOMIC_RELAXED);
+            it = (int)(w & 0xffffffffull);
+            // Under a communicator every rank must have enqueued the SAME collectives when it leaves the level.
+            // How far a rank's host had got when it saw the stop is a matter of timing; min(it + ahead, budget)
+            // is not: each rank tops its queue up to exactly that many iterations (the surplus ones return at
+            // their first load, their all-reduces run out of place on unchanged operands).  Round 5 looked at
+            // the stop word once per 8 iterations, one batch behind: up to 15 surplus iterations per level,
+            // 46 over C4's four levels; now `ahead` (2) per level, whatever the backend.
+            if (rc == HGMM_OK && c->comm_on()) {
+                const int must = std::min(it + plan.ahead_iters, max_iters_per_level);
+                while (rc == HGMM_OK && enq < must) rc = lv.enqueue(enq++);
+                c->tree.surplus_iterations += (unsigned long long)(enq - it);
             }
         } else {
-            TreeCtl* hp = hand->ctl_slot(0);
-            int enq = 0, slot = 0;
-            auto enqueue_batch = [&](int s) -> int {
-                const int cnt = std::min(batch, max_iters_per_level - enq);
-                for (int b = 0; b < cnt; ++b) {
-                    const int r = enqueue_iteration(enq + b);
-                    if (r != HGMM_OK) return r;
-                }
-                enq += cnt;
-                if (hipMemcpyAsync(&hp[s], ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipEventRecord(c->tree_ev[s], c->stream) != hipSuccess)
-                    return fail(c, HGMM_ERR_HIP, "tree build: device error: %s", hipGetErrorString(hipGetLastError()));
-                return HGMM_OK;
-            };
-            if (rc == HGMM_OK) rc = enqueue_batch(slot);
-            while (rc == HGMM_OK) {
-                const bool ahead = enq < max_iters_per_level;
-                if (ahead) rc = enqueue_batch(slot ^ 1);
-                if (rc != HGMM_OK) break;
-                if (hipEventSynchronize(c->tree_ev[slot]) != hipSuccess) {
-                    rc = fail(c, HGMM_ERR_HIP, "tree build: device error: %s", hipGetErrorString(hipGetLastError()));
-                    break;
-                }
-                it = hp[slot].it;
-                if (hp[slot].done != 0) break;
-                if (!ahead) {                      // cannot happen (the budget's last iteration sets done); never spin
-                    rc = fail(c, HGMM_ERR_STATE, "tree build: level %d did not stop within its budget", l);
-                    break;
-                }
-                slot ^= 1;
-            }
+            rc = run_batches(c, lv.ctl, hand, max_iters_per_level, plan.batch_iters, enqueue, &it, "tree build");
+        }
+        if (rc != HGMM_OK) {
+            c->err += " (level " + std::to_string(l) + ")";
+            break;
         }
         level_iters[l] = it;
-        if (rc != HGMM_OK) break;
-        int* cur = curbuf[(it - 1) & 1];                       // the assignment of the last iteration that counted
-        q_len += it;
+        int* cur = lv.curbuf[(it - 1) & 1];                    // the assignment of the last iteration that counted
         if (iters_per_level_out) iters_per_level_out[l] = it;
         if (l + 1 < L) {
             // partition for the next level
-            tree_hist_kernel<<<grid_chunks, CH, 0, c->stream>>>(cur, chunk_desc, n_chunks_dev, hist);
-            int* seg_next = (seg_cur == seg_a) ? seg_b : seg_a;
-            tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(hist, chunk_first, seg_cur, P, chunk_off, seg_next);
-            double* xs_next = (xs_cur == xs_b) ? xs_c : xs_b;     // A -> B -> C -> B -> ...
-            int* perm_next = (perm_cur == perm_a) ? perm_b : perm_a;
-            double* w_next = (xs_next == xs_b) ? w_b : w_c;       // (the weights' buffers pair up with the coordinates')
-            const auto scatter = weighted ? tree_scatter_kernel<true> : tree_scatter_kernel<false>;
-            scatter<<<grid_chunks, CH, 0, c->stream>>>(xs_cur, n_pad, perm_cur, cur, chunk_desc, n_chunks_dev, chunk_off, xs_next,
-                                                       perm_next, w_cur, w_next);
+            tree_hist_kernel<<<lv.grid_chunks, CH, 0, c->stream>>>(cur, ws.chunk_desc, ws.n_chunks_dev, ws.hist);
+            tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(ws.hist, ws.chunk_first, ws.seg, P, ws.chunk_off, ws.seg_next);
+            const auto scatter = kernel_for<ScatterFamily>(weighted);
+            scatter<<<lv.grid_chunks, CH, 0, c->stream>>>(
+                ws.xs, n_pad, perm_cur, cur, ws.chunk_desc, ws.n_chunks_dev, ws.chunk_off, ws.xs_next, perm_next, ws.w, ws.w_next);
             HGMM_HIP(c, hipGetLastError());
-            xs_cur = xs_next;
-            w_cur = weighted ? w_next : nullptr;
-            perm_cur = perm_next;
-            seg_cur = seg_next;
+            ws.advance();
+            std::swap(perm_cur, perm_next);
             P *= 8;
         } else if (leaf_idx_out) {
-            int* out_dev = (perm_cur == perm_a) ? perm_b : perm_a;
-            tree_unsort_kernel<<<nblk(n, 256), 256, 0, c->stream>>>(perm_cur, cur, n, out_dev);
-            if (hipMemcpyAsync(leaf_idx_out, out_dev, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            tree_unsort_kernel<<<nblk(n, 256), 256, 0, c->stream>>>(perm_cur, cur, n, perm_next);
+            if (hipMemcpyAsync(leaf_idx_out, perm_next, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
                 rc = fail(c, HGMM_ERR_HIP, "tree build: leaf index download failed");
         }
     }
     if (rc == HGMM_OK) {
         // the per-iteration M-steps skip the 'complexity' ratio (registration only): all nodes at once, now
-        tree_complexity_kernel<<<nblk(T, 256), 256, 0, c->stream>>>(d_cov, 0, T, d_prep);
+        tree_complexity_kernel<<<nblk(T, 256), 256, 0, c->stream>>>(d_cov, 0, T, c->t_prep.as<double>());
         // The node tables and the q traces come back through the context's pinned ring: every copy is a DMA packet that
         // queues at once, ONE synchronisation, then plain memcpys.  (Copied straight into the caller's pageable arrays
         // each of the 3 + L copies blocked the host for ~20 us while the runtime staged it: 5 % of a C4 build.)  Tables
@@ -1027,20 +922,15 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
         dl.add(pi_out, d_pi, sizeof(double) * T);
         dl.add(mu_out, d_mu, sizeof(double) * 3 * T);
         dl.add(cov_out, d_cov, sizeof(double) * 9 * T);
-        if (q_trace_out) {                                          // the levels' q traces, back to back
-            int at = 0;
-            for (int l = 0; l < L; ++l) {
-                const int take = std::min(std::min(level_iters[l], trace_cap), q_capacity - at);
-                if (take > 0) dl.add(q_trace_out + at, trace_base + (size_t)l * trace_cap, sizeof(double) * take);
-                at += level_iters[l];
-                if (at >= q_capacity) break;
-            }
-        }
+        gather_traces(level_iters.data(), L, trace_cap, q_trace_out ? q_capacity : 0, [&](int at, int l, int take) {
+            dl.add(q_trace_out + at, trace_base + (size_t)l * trace_cap, sizeof(double) * take);
+        });
         const hipError_t e = dl.finish();
         if (e != hipSuccess) rc = fail(c, HGMM_ERR_HIP, "tree build: download failed: %s", hipGetErrorString(e));
     } else {
         (void)ctx_stream_sync(c);
     }
+    const int q_len = std::accumulate(level_iters.begin(), level_iters.end(), 0);      // (of the levels that finished)
     if (q_len_out) *q_len_out = q_len < q_capacity ? q_len : q_capacity;
     if (rc == HGMM_OK) { c->tree.nodes_ready = true; c->tree.mu_rmax = -1.0; }
     return rc;
@@ -1626,7 +1516,7 @@ extern "C" int hgmm_tree_loglik(hgmm_ctx* c, int64_t T, const double* pi, const 
                                                                   c->t_prep.as<double>(), j_begin, n_level,
                                                                   (n_level + LL_TILE - 1) / LL_TILE * LL_TILE, nullptr,
                                                                   block_q, nullptr, nullptr, nullptr,
-                                                                  TreeStop{nullptr, 0.0, 0, nullptr, 0}, flags_ptr(c), nullptr);
+                                                                  NO_STOP, flags_ptr(c), nullptr);
     }
     tree_sum_kernel<<<1, 256, 0, c->stream>>>(block_q, pblocks, q_dev);
     HGMM_HIP(c, hipGetLastError());

@@ -64,6 +64,33 @@ def test_fullcov_component_layouts_vs_oracle(ctx, bunny, J):
     np.testing.assert_allclose(cov, o_cov, rtol=1e-6, atol=1e-14)
 
 
+@pytest.fixture(scope="module")
+def batch_boundary_case(bunny):
+    P = bunny[::30][:1300].astype(np.float64)
+    idx = np.random.RandomState(24).choice(len(P), 24, replace=False)
+    return P, idx
+
+
+@pytest.mark.parametrize("budget", [1, 4, 5, 9])
+def test_fullcov_batch_scheme_at_its_batch_boundaries(ctx, batch_boundary_case, budget):
+    """The fit enqueues its iterations in batches of 4, one batch ahead of the verdict it waits for (run_batches):
+    budgets of a single iteration, exactly one batch, a batch plus one, two batches plus one.  ls = 1e-30 never stops
+    the loop, so it ends on the budget's last iteration.  Tolerances: test_fullcov_component_layouts_vs_oracle's."""
+    P, idx = batch_boundary_case
+    J = 24
+    ctx.set_points(P)
+    pi, mu, cov, labels, q = ctx.fullcov_fit(J, 1e-30, 1e-4, P[idx], 0.0005, budget)
+    o_pi, o_mu, o_cov, o_q, o_cur = hgmm_tree.build_flat_fullcov(P, J, 1e-30, 1e-4, idx, 0.0005, max_iters=budget)
+    print("budget", budget, "iterations", len(q), "oracle", len(o_q))
+    assert len(o_q) == budget and np.isfinite(o_pi).all() and np.isfinite(o_mu).all() and np.isfinite(o_cov).all()
+    assert len(q) == budget
+    np.testing.assert_allclose(q, o_q, rtol=1e-9, atol=1e-6)
+    assert np.array_equal(labels, o_cur)
+    np.testing.assert_allclose(pi, o_pi, rtol=1e-9, atol=1e-13)
+    np.testing.assert_allclose(mu, o_mu, rtol=1e-8, atol=1e-11)
+    np.testing.assert_allclose(cov, o_cov, rtol=1e-6, atol=1e-14)
+
+
 def test_fullcov_estep_moments_layout(ctx, bunny):
     """hgmm_fullcov_estep: the 10-float statistics expanded to the reference's m0/m1/m2 layout."""
     P = bunny[::16].astype(np.float64)

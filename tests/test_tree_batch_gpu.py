@@ -269,6 +269,28 @@ def test_solve_on_device_through_the_mirrors(ctx, bunny):
     assert ctx.config_get("reg_device_solve") == 0
 
 
+@pytest.mark.parametrize("max_iter", [1, 2])
+def test_solve_on_device_with_a_budget_below_the_look_ahead(ctx, bunny, max_iter):
+    """The device registration loop keeps 3 iterations enqueued ahead of the slowest pair (follow_ahead): budgets of 1
+    and 2 end before the look-ahead is ever full.  tol = 0 stops nothing, so every pair takes the whole budget -- no
+    iteration beyond it is enqueued, none is missing -- and serial and batched are still bit for bit each other."""
+    from hgmm_amd.hgmm.hgmm_gpu import GMMTree, registration_gmmtree_batch
+    b = bunny.astype(np.float64)
+    srcs = [b[::5], b[::8], b[2::9]]
+    pairs = [(s, _moved(s, 4.0 + k, [0.3, 1, 0.2 * k], [0.002, -0.001 * k, 0.001])) for k, s in enumerate(srcs)]
+    kw = dict(tree_level=3, lambda_c=0.01, ls=20, sig2=0.004)
+    res, info = registration_gmmtree_batch(pairs, maxiter=max_iter, tol=0.0, ctx=ctx, return_info=True, solve_on_device=True, **kw)
+    print("max_iter", max_iter, "registration iterations per pair:", list(info["registration_iters"]))
+    assert list(info["registration_iters"]) == [max_iter] * len(pairs)
+    for k, (s, t) in enumerate(pairs):
+        gt = GMMTree(s, ctx=ctx, solve_on_device=True, **kw)
+        dev = gt.registration(t, max_iter, 0.0)
+        assert int(gt.n_iter_) == max_iter
+        assert np.array_equal(dev.transformation.rot, res[k].transformation.rot) and np.array_equal(dev.transformation.t, res[k].transformation.t)
+        assert np.array_equal(np.ravel(dev.q), np.ravel(res[k].q)), k
+    assert ctx.config_get("reg_device_solve") == 0
+
+
 def test_float32_clouds_are_widened_on_the_device_exactly(ctx, bunny):
     """hgmm_set_points_batch_f32 / hgmm_tree_set_targets_batch_f32: float32 rows in, widened to float64 on the device --
     trees and transformations bit for bit those of the float64 entries on the host-widened arrays."""

@@ -622,6 +622,35 @@ def test_stop_rule_in_the_next_launch_equals_the_ticketed_tail(ctx, bunny, monke
         assert list(a[4]) == [max_iters] * L
 
 
+@pytest.mark.parametrize("budget", [8, 9, 16, 17])
+def test_batch_scheme_at_its_batch_boundaries(ctx, bunny, budget):
+    """HGMM_TREE_AHEAD=0 enqueues a level in batches of 8 iterations, one batch ahead of the verdict it waits for
+    (run_batches): budgets of exactly one batch, a batch plus one, two batches, two plus one.  ls = 1e-30 never stops a
+    level (the float64 oracle uses the whole budget at both levels for all four), so every level ends on the budget's
+    last iteration -- the last of a full batch, or the only one of a batch of one.  The batch scheme and the ticketed
+    polled form are both non-overlapped: the same bits, q trace included; the default (overlapped) build forms level
+    0's q elsewhere and shares the tables and the leaves."""
+    P = bunny[::8].astype(np.float64)
+    assert len(P) == 5032
+    L = 2
+    T = hgmm_tree.n_total(L)
+    idx = np.random.RandomState(72).randint(T, size=T)
+    args = (P, L, 1e-30, 1e-4, idx, 0.004, budget)
+    default = build(ctx, *args)
+    with ctx.config(tree_tickets=1):
+        ticketed = build(ctx, *args)
+    with ctx.config(tree_ahead=0):
+        batched = build(ctx, *args)
+    print("budget", budget, "iterations per level:", *([int(v) for v in r[4]] for r in (batched, ticketed, default)))
+    for r in (batched, ticketed, default):
+        assert list(r[4]) == [budget, budget]
+    assert len(batched[5]) == 2 * budget
+    for x, y in zip(batched, ticketed):                                  # pi, mu, cov, leaves, iterations, q
+        assert np.array_equal(x, y)
+    for x, y in zip(batched[:4], default[:4]):
+        assert np.array_equal(x, y)
+
+
 # ---- float32 pdfs behind the stop rule (hgmm_tree_set_precision: the reference GPU file's type, hgmm_gpu.py:472-484) ----
 def _blobs(n, seed, k=40, spread=0.02):
     rs = np.random.RandomState(seed)
