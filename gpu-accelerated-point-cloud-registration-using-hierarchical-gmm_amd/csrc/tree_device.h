@@ -2137,15 +2137,19 @@ __host__ __device__ inline double reg_extent(const Rigid& tf, double tgt_rmax, d
 }
 // encoding of the registration E-step's fixed-point sums: D = the extent rounded up to a power of two, F fractional bits
 // such that n_all terms cannot overflow 62 bits (n_all: the number of target points over all ranks, or the sum of their
-// weights under hgmm_tree_set_target_weights -- a term is w gamma <= w)
+// weights under hgmm_tree_set_target_weights -- a term is w gamma <= w <= n_all).  F follows the exponent of n_all in both
+// directions: n_all < 2^e gives F = 62 - e, which is 62 - bits(n) for a count and grows as a weight sum falls below 1, so
+// that weights of any scale keep the same relative resolution (w 2^k: the same integers, moments exactly 2^k times).  F
+// stays where 2^F and 2^-F are finite normal numbers; n_all not positive, NaN or infinite is taken as 1.
 __host__ __device__ inline void reg_encoding(double ext, double n_all, double* D_out, int* F_out) {
     if (!(ext > 0.0) || !(ext < 1.0e300)) ext = 1.0;              // (not positive, NaN or infinite)
     int e2 = 0;
     (void)frexp(ext, &e2);                                        // ext < 2^e2
     *D_out = ldexp(1.0, e2);
     int nbits = 1;
-    while (ldexp(1.0, nbits) <= n_all) ++nbits;
-    *F_out = 62 - nbits;
+    if (n_all > 0.0 && n_all <= 1.7976931348623157e308) (void)frexp(n_all, &nbits);   // n_all < 2^nbits
+    const int F = 62 - nbits;
+    *F_out = F > 1022 ? 1022 : (F < -1022 ? -1022 : F);
 }
 
 // One pair of a batched registration (tree_batch.hip).  The first block is what the E-step and the normal-equation kernels

@@ -1434,13 +1434,9 @@ extern "C" int hgmm_tree_estep(hgmm_ctx* c, int64_t T, const double* pi, const d
         HGMM_TRY(hgmm_comm_allreduce_f64(c, &ext, 1, 1));
         HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_all, 1, 0));
     }
-    if (!(ext > 0.0) || !std::isfinite(ext)) ext = 1.0;
-    int e2x = 0;
-    (void)std::frexp(ext, &e2x);
-    const double D = std::ldexp(1.0, e2x);
-    int nbits = 1;
-    while (std::ldexp(1.0, nbits) <= n_all) ++nbits;
-    const int F = 62 - nbits;
+    double D = 1.0;
+    int F = 0;
+    reg_encoding(ext, n_all, &D, &F);
     {
         ProfScope prof(c, HGMM_K_TREE_ESTEP);
         tree_estep_generic_kernel<<<nblk(c->n, CH), CH, 0, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,

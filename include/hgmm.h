@@ -420,6 +420,12 @@ int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, c
  * w_i gamma), the sums stay the deterministic fixed-point sums, whose encoding takes the sum of the weights (a float64 sum
  * on the host, in index order; all-reduced under a communicator) where it took the number of points.  A zero weight adds
  * nothing.  w == 1 everywhere gives the unweighted results bit for bit, w == 2 everywhere exactly twice the moments.
+ * The moments are LINEAR IN THE WEIGHTS AT ANY POSITIVE SCALE: the encoding's fractional bits follow the exponent of the sum
+ * (sum < 2^e: 62 - e bits, above and below 1 alike), so weights in [0, 1] whose sum is far below 1 are summed at the relative
+ * resolution counts are; c w gives c times the moments of w to the same relative bound for any c > 0, and exactly so -- bit
+ * for bit -- when c is a power of two.  The registration M-step, however, READS WEIGHTS AS POINT COUNTS: like the
+ * reference's it leaves a node with m0 < float32 eps (1.19e-7) out of the twist system, so weights scaled down until the
+ * nodes' m0 reach that threshold lose nodes, and in the end the whole system (status 2).
  * The weights ATTACH TO THE RESIDENT TARGET: hgmm_tree_set_target (serial, multi-start) resp.
  * hgmm_tree_set_targets_batch[_f32] (batch) first -- HGMM_ERR_STATE without one -- and uploading a new target drops them.
  * w == NULL: no weights (the unweighted kernels run, every result what it was, bit for bit); in the batch w[b] == NULL leaves

@@ -5,11 +5,42 @@ the weights' tests.
 floor on the responsibility: ``gs = gs * w[idx][keep]``.  The descent, the stop rule and the floor itself do not see the
 weight; with ``w = None`` or ``w == 1`` the result is reg_e_step's bit for bit.  An optional Mahalanobis gate
 (hgmm_tree_set_reg_gate, as in tests/_gate_oracle.py) composes with it: the gate is decided on the pair, the weight scales
-what passes."""
+what passes.
+
+The helpers the weights' test files share are here too (this module is a helper, not a conftest): ``weights_for``,
+``resident``, ``loop5``, ``same_bits``."""
 import numpy as np
 
 from oracle import hgmm_tree
 from oracle.hgmm_tree import EPS, N_NODE, child, complexity, n_total, node_prep, pdf_pairs
+
+I3 = np.identity(3)
+
+
+def weights_for(n):
+    """the tests' weights unless stated otherwise: uniform in [0.25, 4), one in ten exactly zero"""
+    rs = np.random.RandomState(11)
+    w = rs.uniform(0.25, 4.0, n)
+    w[rs.uniform(size=n) < 0.1] = 0.0
+    return w
+
+
+def resident(ctx, g, target, w=None):
+    L = int(g["L"])
+    ctx.tree_set_nodes(L, g["pi"], g["mu"], g["cov"])
+    ctx.tree_set_target(target)
+    if w is not None:
+        ctx.tree_set_target_weights(w)
+    return L, float(g["lambda_c"]), hgmm_tree.n_total(L)
+
+
+def same_bits(a, b):
+    return all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
+
+
+def loop5(ctx, lc):
+    """five iterations from the identity, no stop rule -> (rot, t, iterations, q, status, trace [5, 13])"""
+    return ctx.tree_register(I3, np.zeros(3), 1.0, lc, 5, 0.0, None, want_trace=True)
 
 
 def weighted_reg_e_step(points, pi, mu, cov, max_level, lc, w=None, gate=np.inf):

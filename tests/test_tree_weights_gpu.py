@@ -23,6 +23,7 @@ from oracle import hgmm_tree
 
 import _gate_oracle
 import _weight_oracle
+from _weight_oracle import loop5, resident, same_bits, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -44,37 +45,11 @@ def records():
     return {2: load_golden("hgmm_reg_L2.npz"), 4: load_golden("hgmm_reg_L4.npz")}
 
 
-def weights_for(n):
-    """the tests' weights unless stated otherwise: uniform in [0.25, 4), one in ten exactly zero"""
-    rs = np.random.RandomState(11)
-    w = rs.uniform(0.25, 4.0, n)
-    w[rs.uniform(size=n) < 0.1] = 0.0
-    return w
-
-
 def rot_about(axis, deg):
     axis = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
     th = np.deg2rad(deg)
     K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
     return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
-
-
-def resident(ctx, g, target, w=None):
-    L = int(g["L"])
-    ctx.tree_set_nodes(L, g["pi"], g["mu"], g["cov"])
-    ctx.tree_set_target(target)
-    if w is not None:
-        ctx.tree_set_target_weights(w)
-    return L, float(g["lambda_c"]), hgmm_tree.n_total(L)
-
-
-def same_bits(a, b):
-    return all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
-
-
-def loop5(ctx, lc):
-    """five iterations from the identity, no stop rule -> (rot, t, iterations, q, status, trace [5, 13])"""
-    return ctx.tree_register(I3, np.zeros(3), 1.0, lc, 5, 0.0, None, want_trace=True)
 
 
 @pytest.fixture()
@@ -587,19 +562,19 @@ def test_status_2_host_fallback_follows_the_resident_weights(ctx, records):
 SPLIT = 2300
 
 
-def _rank_inputs():
+def _rank_inputs(scale=1.0):
     g = load_golden("hgmm_reg_L4.npz")
     X = g["rot10_target"]
     # multiples of 1/8 (some of them zero): both shards' sums and their total are exact, so the all-reduced sum of the
-    # weights is the single context's and the encodings agree
-    w = np.random.RandomState(11).randint(0, 33, len(X)) / 8.0
+    # weights is the single context's and the encodings agree.  ``scale`` (a power of two) keeps all of that exact.
+    w = np.random.RandomState(11).randint(0, 33, len(X)) / 8.0 * scale
     return g, X, w
 
 
-def _rank_worker(rank, name, q):
+def _rank_worker(rank, name, q, scale=1.0):
     try:
         import hgmm_amd
-        g, X, w = _rank_inputs()
+        g, X, w = _rank_inputs(scale)
         lo, hi = (0, SPLIT) if rank == 0 else (SPLIT, len(X))
         ctx = hgmm_amd.Context(0)
         ctx.comm_init_host(2, rank, name)
@@ -619,8 +594,11 @@ def _rank_worker(rank, name, q):
         raise
 
 
-def test_two_ranks_with_sharded_weights_match_the_single_context(ctx, records, gated):
-    g, X, w = _rank_inputs()
+@pytest.mark.parametrize("scale", [1.0, 2.0 ** -20], ids=["unscaled", "2^-20"])
+def test_two_ranks_with_sharded_weights_match_the_single_context(ctx, records, gated, scale):
+    """``scale`` 2^-20: the all-reduced sum of the weights is below 1 (about 2^-7), where the encoding's F follows the sum's
+    exponent above 61"""
+    g, X, w = _rank_inputs(scale)
     assert (w == 0).any() and w[:SPLIT].sum() + w[SPLIT:].sum() == w.sum()
     _, lc, T = resident(ctx, g, X, w)
     R, t = rot_about([0.2, 1.0, 0.1], 3.0), np.array([0.002, -0.001, 0.0015])
@@ -628,10 +606,10 @@ def test_two_ranks_with_sharded_weights_match_the_single_context(ctx, records, g
     gated(16.0)
     ref = ref + ctx.tree_reg_estep(T, R, t, 1.0, lc)
     assert not np.array_equal(ref[0], ref[3])
-    name = "hgmm_w_%d" % os.getpid()
+    name = "hgmm_w_%d_%d" % (os.getpid(), int(np.log2(scale)))
     mpc = mp.get_context("spawn")
     q = mpc.Queue()
-    procs = [mpc.Process(target=_rank_worker, args=(r, name, q)) for r in range(2)]
+    procs = [mpc.Process(target=_rank_worker, args=(r, name, q, scale)) for r in range(2)]
     for p in procs:
         p.start()
     got = dict(q.get(timeout=180) for _ in procs)
