@@ -20,11 +20,14 @@ class DevicePoints:
     gmm_waymo/src/gmm.py:73).  Pass it wherever the API takes ``X``.  Any number of them may be alive on a context
     (hgmm_points_*: each owns its device copy; using one binds it -- a pointer swap, nothing is uploaded again)."""
 
-    def __init__(self, X, ctx: Context | None = None):
+    def __init__(self, X, ctx: Context | None = None, weights=None):
+        """``weights`` [N] >= 0 (default None): per-point weights of the flat fit (``Context.flat_set_weights``) that travel
+        with the cloud -- every use of it sets them, an explicit ``sample_weight=`` of the call takes precedence."""
         self.ctx = ctx or default_context()
         X = np.asarray(X)
         if X.ndim != 2 or X.shape[1] != 3:
             raise ValueError("points must have shape [N,3], got %s" % (X.shape,))
+        self.weights = _check_weights(weights, X.shape[0])
         self.shape = X.shape
         self.dtype = np.dtype(np.float32)
         self._h = self.ctx.points_create(X)
@@ -42,6 +45,8 @@ class DevicePoints:
         if self._h is None:
             raise RuntimeError("this DevicePoints has been freed")
         self.ctx.points_bind(self._h)
+        # (a handle owns no weights on the device: another cloud may have been bound in between, so they are set again)
+        self.ctx.flat_set_weights(self.weights)
         return self.ctx
 
     def free(self):
@@ -56,17 +61,46 @@ class DevicePoints:
             pass
 
 
-def asarray(X, ctx: Context | None = None):
-    return X if isinstance(X, DevicePoints) else DevicePoints(X, ctx)
-
-
-def _ctx_for(X) -> Context:
-    """Returns the context holding X as its bound cloud: resident clouds are bound (nothing moves), host arrays are
-    uploaded into the context's own cloud (like handing NumPy to the reference: a copy per call)."""
+def asarray(X, ctx: Context | None = None, weights=None):
+    """``weights``: as in :class:`DevicePoints`; a cloud that is resident already keeps the weights it has unless new ones
+    are given."""
     if isinstance(X, DevicePoints):
-        return X.bind()
+        if weights is not None:
+            X.weights = _check_weights(weights, X.shape[0])
+        return X
+    return DevicePoints(X, ctx, weights)
+
+
+def _check_weights(s, n):
+    """``s`` as the float32 [n] array the library takes, or None.  What the library would refuse (hgmm_flat_set_weights) is
+    refused here first, before anything is uploaded: a wrong shape, a NaN, infinite or negative weight, all-zero weights."""
+    if s is None:
+        return None
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    if s.ndim != 1 or s.shape[0] != n:
+        raise ValueError("sample_weight must have shape [%d], got %s" % (n, s.shape))
+    bad = np.flatnonzero(~(np.isfinite(s) & (s >= 0)))
+    if bad.size:
+        raise ValueError("sample_weight[%d] is %g (weights must be finite and >= 0)" % (bad[0], s[bad[0]]))
+    if not (s > 0).any():
+        raise ValueError("sample_weight: all %d weights are zero" % n)
+    return s
+
+
+def _ctx_for(X, sample_weight=None) -> Context:
+    """Returns the context holding X as its bound cloud: resident clouds are bound (nothing moves), host arrays are
+    uploaded into the context's own cloud (like handing NumPy to the reference: a copy per call).  The per-point weights
+    in force afterwards are ``sample_weight``, else the resident cloud's own, else none."""
+    if isinstance(X, DevicePoints):
+        ctx = X.bind()
+        if sample_weight is not None:
+            ctx.flat_set_weights(_check_weights(sample_weight, X.shape[0]))
+        return ctx
     ctx = default_context()
+    sample_weight = _check_weights(sample_weight, np.shape(X)[0])
     ctx.set_points(X)
+    if sample_weight is not None:
+        ctx.flat_set_weights(sample_weight)
     return ctx
 
 
@@ -96,8 +130,9 @@ def estimate_log_prob(X, inv_cov, means, cov_type):
     return ctx.flat_log_prob(_host(inv_cov), _host(means), cov_type)
 
 
-def e_step(X, inv_cov, means, weights, cov_type, variant):
-    ctx = _ctx_for(X)
+def e_step(X, inv_cov, means, weights, cov_type, variant, sample_weight=None):
+    """``sample_weight`` [N] >= 0: the returned mean is ``sum(s * lpn) / sum(s)``; log_resp does not see the weights."""
+    ctx = _ctx_for(X, sample_weight)
     # like the reference under CuPy nothing waits here: the mean is a device scalar, read when it is looked at
     # Parameters handed over as DeviceArrays (an earlier m_step's results, arithmetic on them) are used where they are.
     mean_lpn, log_resp, _, _ = ctx.flat_estep(_param(inv_cov), _param(means), _param(weights), cov_type, variant,
@@ -105,16 +140,19 @@ def e_step(X, inv_cov, means, weights, cov_type, variant):
     return mean_lpn, log_resp
 
 
-def m_step(X, resp, cov_type, variant, centre_hint=None):
-    """Array module in = array module out, like the reference (``xp = cupy.get_array_module(X)``, gmm_impl.py:91):
+def m_step(X, resp, cov_type, variant, centre_hint=None, sample_weight=None):
+    """``sample_weight`` [N] >= 0: row i of ``resp`` counts ``sample_weight[i]`` times, the weights are ``nk / sum(s)``.
+    Array module in = array module out, like the reference (``xp = cupy.get_array_module(X)``, gmm_impl.py:91):
     responsibilities that live in HBM (a DeviceArray, e.g. ``log_resp.exp()`` of this module's e_step) give
     DeviceArrays -- nothing is downloaded, nothing waits; host responsibilities give NumPy arrays."""
-    ctx = _ctx_for(X)
+    ctx = _ctx_for(X, sample_weight)
     return ctx.flat_mstep(resp, cov_type, variant, centre_hint, device_out=isinstance(resp, DeviceArray))
 
 
-def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, variant):
-    ctx = _ctx_for(X)
+def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, variant, sample_weight=None):
+    """``sample_weight`` [N] >= 0 (default: the weights a ``DevicePoints`` brings, else none): point i counts as that many
+    points in the M-step and in the log-likelihood behind the stop rule; a zero removes the row (hgmm_flat_set_weights)."""
+    ctx = _ctx_for(X, sample_weight)
     inv, mu, w, cov, lls, converged = ctx.flat_train(max_iter, tol, _host(means), _host(covariances),
                                                      _host(weights), cov_type, variant)
     if not converged:

@@ -105,6 +105,7 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_flat_train_step", [ctx, C.c_int])
         _sig(lib, "hgmm_flat_train_end", [ctx, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)])
         _sig(lib, "hgmm_flat_stats", [ctx, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _f64p, _f64p])
+        _sig(lib, "hgmm_flat_set_weights", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_build", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int,
                                       _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)])
         _sig(lib, "hgmm_tree_set_nodes", [ctx, C.c_int, _vp, _vp, _vp])
@@ -927,6 +928,24 @@ class Context:
         self._check(self.lib.hgmm_flat_stats(self.h, COV_TYPES[cov_type], VARIANTS[variant], J, _ptr(mu),
                                              _ptr(inv_std), _ptr(w), _ptr(stats), C.byref(s), C.byref(n)))
         return stats, s.value, n.value
+
+    def flat_set_weights(self, s):
+        """Per-point weights ``s`` [n] >= 0 of the resident cloud for the flat fit (hgmm_flat_set_weights): point i counts as
+        ``s[i]`` points -- every M-step sum takes ``s[i] * resp``, the mixing weights are ``nk / sum(s)`` and the
+        log-likelihood behind the stop rule is ``sum(s * lpn) / sum(s)``; flat_stats returns the weighted sums and
+        ``sum(s)`` as its point count.  A zero weight removes the row whatever its coordinates (NaN included).  Honoured by
+        flat_train*, flat_stats, flat_mstep and the mean of flat_estep; log_resp, lpn, arg-max, predict and
+        estimate_log_prob do not see them.  ``None``: no weights.  They belong to the cloud :meth:`set_points` uploaded (or
+        the bound handle): whatever changes the resident cloud drops them.  The library refuses a wrong length, a NaN,
+        infinite or negative weight and all-zero weights (HgmmError, naming the index) and keeps the previous weights."""
+        if s is None:
+            self._check(self.lib.hgmm_flat_set_weights(self.h, None, 0))
+            return self
+        s = np.ascontiguousarray(s, dtype=np.float32)
+        if s.ndim != 1:
+            raise ValueError("weights must be [N], got %s" % (s.shape,))
+        self._check(self.lib.hgmm_flat_set_weights(self.h, _ptr(s), s.shape[0]))
+        return self
 
     # -- HGMM ---------------------------------------------------------------------------
     def tree_build(self, L, ls, ld, init_mu, sig2, max_iters_per_level=1000, q_capacity=None, want_leaf=True):

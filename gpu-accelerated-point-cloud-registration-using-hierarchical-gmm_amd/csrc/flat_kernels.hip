@@ -824,12 +824,22 @@ __global__ __launch_bounds__(BLOCK) void flat_predict_rows_kernel(
 // while M0 <= CS_MAX_SHIFT, and the denominator stays >= eps 2^-M0 >> FLT_MIN.  A model with a
 // larger M0 (sigma < ~1e-7: only the clipped-covariance flavour can get there) is served by the
 // row-maximum loop of the same kernel: every wave derives the same M0 from the table and picks its loop.
+//
+// WEIGHTED (hgmm_flat_set_weights): row i counts as SW[i] >= 0 points.  The weight is wave-uniform like the coordinates --
+// a scalar load, prefetched with the next row's x -- and enters twice: it multiplies inv_den (so every responsibility of
+// the row) once, and the row's log-normaliser on its way into the sum (fmaf(s, log2 den, lacc) in the constant-shift loop,
+// s * lpn in the row-maximum loop; the closing (r1 - r0) m0 term becomes (sum of s) m0, the sum kept in float64).  A row
+// with s == 0 is SKIPPED by a wave-uniform branch, not multiplied by zero: its coordinates are never looked at, so a NaN
+// row with zero weight leaves every sum finite; the 8-row flush of lacc keeps its schedule.  s == 1 everywhere reproduces
+// the unweighted sums bit for bit (every product by 1 is exact), s == 2 doubles them exactly.  The unweighted
+// instantiations read no weight and are the code they were: the launch passes nullptr.
+__device__ __forceinline__ bool weight_is_zero(float s) { return (__float_as_uint(s) & 0x7fffffffu) == 0u; }
 
-template <int NSLOT>
+template <int NSLOT, bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     const float* __restrict__ X, const float* __restrict__ pack, int64_t n, int J, int Jpad,
     float* __restrict__ partials, double* __restrict__ lpn_partials,
-    const int* __restrict__ done_flag, int allow_const_shift, int comp_major) {
+    const int* __restrict__ done_flag, int allow_const_shift, int comp_major, const float* __restrict__ SW) {
     if (done_flag && *done_flag) return;
     constexpr int K = NSLOT;
     constexpr int KP = K / 2;          // full pairs
@@ -918,95 +928,125 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     const float eps_scale = __builtin_amdgcn_exp2f(-m0);
     float lacc = 0.f;                      // sum of log2(den) of the rows since the last flush
     float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    if (r0 < r1) { const float* xp = X + 3 * r0; x0 = xp[0]; x1 = xp[1]; x2 = xp[2]; }
+    float sw = 1.f;                        // (WEIGHTED) this row's weight
+    double swsum = 0.0;                    // (WEIGHTED) sum of the weights of this wave's rows
+    if (r0 < r1) { const float* xp = X + 3 * r0; x0 = xp[0]; x1 = xp[1]; x2 = xp[2]; if (WEIGHTED) sw = SW[r0]; }
     for (int64_t row = r0; row < r1; ++row) {
         const int64_t nrow = (row + 1 < r1) ? row + 1 : row;
         const float* xn = X + 3 * nrow;
         const float nx0 = xn[0], nx1 = xn[1], nx2 = xn[2];
-        const f2 X0 = f2{x0, x0}, X1 = f2{x1, x1}, X2 = f2{x2, x2};
-        const float xo0 = x0 - o0, xo1 = x1 - o1, xo2 = x2 - o2;
-        const f2 XO0 = f2{xo0, xo0}, XO1 = f2{xo1, xo1}, XO2 = f2{xo2, xo2};
+        float nsw = 1.f;
+        if constexpr (WEIGHTED) nsw = SW[nrow];
+        // (WEIGHTED) a row of weight zero is absent, whatever its coordinates: a wave-uniform branch round the row's work
+        if (!WEIGHTED || !weight_is_zero(sw)) {
+            const f2 X0 = f2{x0, x0}, X1 = f2{x1, x1}, X2 = f2{x2, x2};
+            const float xo0 = x0 - o0, xo1 = x1 - o1, xo2 = x2 - o2;
+            const f2 XO0 = f2{xo0, xo0}, XO1 = f2{xo1, xo1}, XO2 = f2{xo2, xo2};
 
-        f2 wl[KP + 1];
-        f2 q0[KP + 1], q1[KP + 1], q2[KP + 1];
-        float q0s = 0.f, q1s = 0.f, q2s = 0.f;
-        float wls = NEG_INF;
-        float m = NEG_INF;
-        f2 sacc = f2{0.f, 0.f};
-#pragma unroll
-        for (int p = 0; p < KP; ++p) {
-            const f2 d0 = X0 - mu0[p], d1 = X1 - mu1[p], d2 = X2 - mu2[p];
-            q0[p] = d0 * d0; q1[p] = d1 * d1; q2[p] = d2 * d2;
-            f2 a = cc[p] - g0[p] * q0[p];
-            a = a - g1[p] * q1[p];
-            a = a - g2[p] * q2[p];
-            if (CS) {
-                wl[p] = f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-                sacc += wl[p];
-            } else {
-                wl[p] = a;
-                m = fmaxf(m, fmaxf(a.x, a.y));
-            }
-        }
-        if (ODD) {
-            const float d0 = x0 - mu0s, d1 = x1 - mu1s, d2 = x2 - mu2s;
-            q0s = d0 * d0; q1s = d1 * d1; q2s = d2 * d2;
-            float a = fmaf(-g0s, q0s, cs);
-            a = fmaf(-g1s, q1s, a);
-            a = fmaf(-g2s, q2s, a);
-            wls = CS ? __builtin_amdgcn_exp2f(a) : a;
-            m = fmaxf(m, a);
-        }
-        if (CS) {
-            m = m0;
-        } else {
-            m = wave_max_dpp(m);
-            if (m == NEG_INF) m = 0.f;
-            const f2 M = f2{m, m};
+            f2 wl[KP + 1];
+            f2 q0[KP + 1], q1[KP + 1], q2[KP + 1];
+            float q0s = 0.f, q1s = 0.f, q2s = 0.f;
+            float wls = NEG_INF;
+            float m = NEG_INF;
+            f2 sacc = f2{0.f, 0.f};
 #pragma unroll
             for (int p = 0; p < KP; ++p) {
-                const f2 t = wl[p] - M;
-                wl[p] = f2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                sacc += wl[p];
+                const f2 d0 = X0 - mu0[p], d1 = X1 - mu1[p], d2 = X2 - mu2[p];
+                q0[p] = d0 * d0; q1[p] = d1 * d1; q2[p] = d2 * d2;
+                f2 a = cc[p] - g0[p] * q0[p];
+                a = a - g1[p] * q1[p];
+                a = a - g2[p] * q2[p];
+                if (CS) {
+                    wl[p] = f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
+                    sacc += wl[p];
+                } else {
+                    wl[p] = a;
+                    m = fmaxf(m, fmaxf(a.x, a.y));
+                }
             }
-            if (ODD) wls = __builtin_amdgcn_exp2f(wls - m);
+            if (ODD) {
+                const float d0 = x0 - mu0s, d1 = x1 - mu1s, d2 = x2 - mu2s;
+                q0s = d0 * d0; q1s = d1 * d1; q2s = d2 * d2;
+                float a = fmaf(-g0s, q0s, cs);
+                a = fmaf(-g1s, q1s, a);
+                a = fmaf(-g2s, q2s, a);
+                wls = CS ? __builtin_amdgcn_exp2f(a) : a;
+                m = fmaxf(m, a);
+            }
+            if (CS) {
+                m = m0;
+            } else {
+                m = wave_max_dpp(m);
+                if (m == NEG_INF) m = 0.f;
+                const f2 M = f2{m, m};
+#pragma unroll
+                for (int p = 0; p < KP; ++p) {
+                    const f2 t = wl[p] - M;
+                    wl[p] = f2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+                    sacc += wl[p];
+                }
+                if (ODD) wls = __builtin_amdgcn_exp2f(wls - m);
+            }
+            float s = sacc.x + sacc.y;
+            if (ODD) s += wls;
+            s = wave_sum_dpp(s);
+            float inv_den;
+            if (CS) {
+                // lpn2_from with m = m0 in [-64, CS_MAX_SHIFT]: no "tiny" case, eps 2^-m0 is loop-invariant;
+                // the log-normalisers are summed in float32 over 8 rows before they join the float64 total
+                const float den = fmaf(FLAT_EPS, eps_scale, s);
+                inv_den = __builtin_amdgcn_rcpf(den);
+                if constexpr (WEIGHTED) lacc = fmaf(sw, __builtin_amdgcn_logf(den), lacc);
+                else lacc += __builtin_amdgcn_logf(den);
+                if constexpr (!WEIGHTED) {
+                    if (((row - r0) & 7) == 7) {
+                        asm volatile("" ::: "memory");          // keeps this a (wave-uniform) branch, not selects
+                        lsum += (double)lacc;
+                        lacc = 0.f;
+                    }
+                }
+            } else {
+                const float lpn2 = lpn2_from(m, s, inv_den);
+                if constexpr (WEIGHTED) lsum += (double)sw * (double)(lpn2 * LN2);
+                else lsum += (double)(lpn2 * LN2);
+            }
+            if constexpr (WEIGHTED) inv_den *= sw;
+            const f2 INV = f2{inv_den, inv_den};
+#pragma unroll
+            for (int p = 0; p < KP; ++p) {
+                const f2 rr = wl[p] * INV;
+                s0[p] += rr;
+                a0[p] += rr * XO0; a1[p] += rr * XO1; a2[p] += rr * XO2;
+                b0[p] += rr * q0[p]; b1[p] += rr * q1[p]; b2[p] += rr * q2[p];
+            }
+            if (ODD) {
+                const float rr = wls * inv_den;
+                s0s += rr;
+                a0s = fmaf(rr, xo0, a0s); a1s = fmaf(rr, xo1, a1s); a2s = fmaf(rr, xo2, a2s);
+                b0s = fmaf(rr, q0s, b0s); b1s = fmaf(rr, q1s, b1s); b2s = fmaf(rr, q2s, b2s);
+            }
         }
-        float s = sacc.x + sacc.y;
-        if (ODD) s += wls;
-        s = wave_sum_dpp(s);
-        float inv_den;
-        if (CS) {
-            // lpn2_from with m = m0 in [-64, CS_MAX_SHIFT]: no "tiny" case, eps 2^-m0 is loop-invariant;
-            // the log-normalisers are summed in float32 over 8 rows before they join the float64 total
-            const float den = fmaf(FLAT_EPS, eps_scale, s);
-            inv_den = __builtin_amdgcn_rcpf(den);
-            lacc += __builtin_amdgcn_logf(den);
-            if (((row - r0) & 7) == 7) {
-                asm volatile("" ::: "memory");          // keeps this a (wave-uniform) branch, not selects
+        if constexpr (WEIGHTED) {
+            // the 8-row flush of lacc, on the rows' schedule whether this one was skipped or not (ONE site for both paths:
+            // a second one in the skipped path cost <13, true> 45 AGPRs and its second wave per SIMD)
+            if (CS && ((row - r0) & 7) == 7) {
+                asm volatile("" ::: "memory");
                 lsum += (double)lacc;
                 lacc = 0.f;
             }
-        } else {
-            const float lpn2 = lpn2_from(m, s, inv_den);
-            lsum += (double)(lpn2 * LN2);
-        }
-        const f2 INV = f2{inv_den, inv_den};
-#pragma unroll
-        for (int p = 0; p < KP; ++p) {
-            const f2 rr = wl[p] * INV;
-            s0[p] += rr;
-            a0[p] += rr * XO0; a1[p] += rr * XO1; a2[p] += rr * XO2;
-            b0[p] += rr * q0[p]; b1[p] += rr * q1[p]; b2[p] += rr * q2[p];
-        }
-        if (ODD) {
-            const float rr = wls * inv_den;
-            s0s += rr;
-            a0s = fmaf(rr, xo0, a0s); a1s = fmaf(rr, xo1, a1s); a2s = fmaf(rr, xo2, a2s);
-            b0s = fmaf(rr, q0s, b0s); b1s = fmaf(rr, q1s, b1s); b2s = fmaf(rr, q2s, b2s);
         }
         x0 = nx0; x1 = nx1; x2 = nx2;
+        if constexpr (WEIGHTED) sw = nsw;
     }
-    if (CS) lsum = (lsum + (double)lacc + (double)(r1 > r0 ? r1 - r0 : 0) * (double)m0) * (double)LN2;
+    if constexpr (WEIGHTED) {
+        // the closing term's sum of the wave's weights, float64, taken here and not in the loop (two registers the loop
+        // does not have); zero weights add nothing
+        if (CS) {
+            for (int64_t i = r0 + lane; i < r1; i += 64) swsum += (double)SW[i];
+            swsum = wave_sum_f64(swsum);
+        }
+    }
+    if (CS) lsum = (lsum + (double)lacc + (WEIGHTED ? swsum : (double)(r1 > r0 ? r1 - r0 : 0)) * (double)m0) * (double)LN2;
     };
     if (small_shift) rows(std::true_type{});
     else rows(std::false_type{});
@@ -1070,11 +1110,15 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
 // ------------------------------------------------------------------------------------------
 // M-step moments from a materialised responsibility matrix (m_step(X, resp))
 // ------------------------------------------------------------------------------------------
-template <int NV4, int NV1, bool ISLOG, bool NTLOAD>
+// WEIGHTED (hgmm_flat_set_weights): the row's responsibilities are scaled by its weight SW[row] (a wave-uniform scalar load
+// that travels with the row's coordinates); a row of weight zero is skipped -- its matrix row is still fetched, so that the
+// loads stay unconditional, but neither it nor the row's coordinates are looked at.  The unweighted instantiations read no
+// weight and are the code they were.
+template <int NV4, int NV1, bool ISLOG, bool NTLOAD, bool WEIGHTED = false>
 __global__ __launch_bounds__(BLOCK) void flat_mstep_kernel(
     const float* __restrict__ X, const float* __restrict__ resp,
     const float* __restrict__ hint /*[3][Jpad]*/, int64_t n, int J, int Jpad,
-    float* __restrict__ partials, int64_t ld, int round_robin) {
+    float* __restrict__ partials, int64_t ld, int round_robin, const float* __restrict__ SW = nullptr) {
     // resp / hint / partials point at this launch's first column; J = valid columns from there,
     // ld = row stride of resp (the full component count).  Components are paired into float2 like
     // in the fused kernel (pairs (4v, 4v+1), (4v+2, 4v+3), pairs of scalar slots, one single).
@@ -1136,8 +1180,12 @@ __global__ __launch_bounds__(BLOCK) void flat_mstep_kernel(
 #pragma unroll
         for (int s = 0; s < NV1; ++s) v[4 * NV4 + s] = NTLOAD ? __builtin_nontemporal_load(in + off1[s]) : in[off1[s]];
     };
-    auto accumulate = [&](const float (&v)[K], float x0, float x1, float x2) {
+    auto accumulate = [&](const float (&v)[K], float x0, float x1, float x2, float sw) {
+        if constexpr (WEIGHTED) {
+            if (weight_is_zero(sw)) return;                  // wave-uniform: the row is absent
+        }
         const f2 X0 = f2{x0, x0}, X1 = f2{x1, x1}, X2 = f2{x2, x2}, L2 = f2{LOG2E, LOG2E};
+        const f2 SWV = f2{sw, sw};
 #pragma unroll
         for (int p = 0; p < KP; ++p) {
             f2 r = f2{v[2 * p], v[2 * p + 1]};
@@ -1145,6 +1193,7 @@ __global__ __launch_bounds__(BLOCK) void flat_mstep_kernel(
                 const f2 t = r * L2;
                 r = f2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
             }
+            if constexpr (WEIGHTED) r = r * SWV;
             const f2 d0 = X0 - c0[p], d1 = X1 - c1[p], d2 = X2 - c2[p];
             const f2 rd0 = r * d0, rd1 = r * d1, rd2 = r * d2;
             s0[p] += r;
@@ -1152,7 +1201,8 @@ __global__ __launch_bounds__(BLOCK) void flat_mstep_kernel(
             b0[p] += rd0 * d0; b1[p] += rd1 * d1; b2[p] += rd2 * d2;
         }
         if (ODD) {
-            const float r = is_log ? __builtin_amdgcn_exp2f(v[K - 1] * LOG2E) : v[K - 1];
+            float r = is_log ? __builtin_amdgcn_exp2f(v[K - 1] * LOG2E) : v[K - 1];
+            if constexpr (WEIGHTED) r *= sw;
             const float d0 = x0 - c0s, d1 = x1 - c1s, d2 = x2 - c2s;
             const float rd0 = r * d0, rd1 = r * d1, rd2 = r * d2;
             s0s += r;
@@ -1168,6 +1218,8 @@ __global__ __launch_bounds__(BLOCK) void flat_mstep_kernel(
         load_row(base, bufa);
         const float* xp = X + 3 * base;
         float xa0 = xp[0], xa1 = xp[1], xa2 = xp[2];
+        float swa = 1.f, swb = 1.f;
+        if constexpr (WEIGHTED) swa = SW[base];
         int64_t it = 0;
         for (; it + 2 <= cnt; it += 2) {
             const int64_t rb = base + (it + 1) * stride;
@@ -1175,18 +1227,20 @@ __global__ __launch_bounds__(BLOCK) void flat_mstep_kernel(
             load_row(rb, bufb);
             const float* xq = X + 3 * rb;
             const float xb0 = xq[0], xb1 = xq[1], xb2 = xq[2];
+            if constexpr (WEIGHTED) swb = SW[rb];
             __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise sinks the loads to just before their use)
-            accumulate(bufa, xa0, xa1, xa2);
+            accumulate(bufa, xa0, xa1, xa2, swa);
             __builtin_amdgcn_sched_barrier(0);
             const int64_t ra = base + ((it + 2 < cnt) ? it + 2 : cnt - 1) * stride;
             load_row(ra, bufa);
             const float* xr = X + 3 * ra;
             xa0 = xr[0]; xa1 = xr[1]; xa2 = xr[2];
+            if constexpr (WEIGHTED) swa = SW[ra];
             __builtin_amdgcn_sched_barrier(0);
-            accumulate(bufb, xb0, xb1, xb2);
+            accumulate(bufb, xb0, xb1, xb2, swb);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (it < cnt) accumulate(bufa, xa0, xa1, xa2);
+        if (it < cnt) accumulate(bufa, xa0, xa1, xa2, swa);
     }
     __shared__ float sh[FLAT_NSTAT * L::CAP];
     const int w = wave_in_block();
@@ -1281,7 +1335,7 @@ __global__ __launch_bounds__(BLOCK) void flat_chunk_lse_kernel(
 __global__ __launch_bounds__(256) void flat_chunk_combine_kernel(
     const float* __restrict__ cm, const float* __restrict__ cs, const int* __restrict__ ca, int nchunks,
     int64_t n, float* __restrict__ lpn2_out, float* __restrict__ lpn_out, int32_t* __restrict__ argmax_out,
-    double* __restrict__ lpn_partials) {
+    double* __restrict__ lpn_partials, const float* __restrict__ SW /*hgmm_flat_set_weights; null: none*/) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double lp = 0.0;
     if (i < n) {
@@ -1305,6 +1359,10 @@ __global__ __launch_bounds__(256) void flat_chunk_combine_kernel(
         if (lpn_out) lpn_out[i] = lpn;
         if (argmax_out) argmax_out[i] = ca ? ca[(size_t)best_c * n + i] : 0;
         lp = (double)lpn;
+        if (SW) {                                       // the partial sums are the weighted ones; a zero-weight row is absent
+            const float sw = SW[i];
+            lp = weight_is_zero(sw) ? 0.0 : (double)sw * (double)lpn;
+        }
     }
     if (lpn_partials) {
         __shared__ double sh[4];
@@ -1315,10 +1373,12 @@ __global__ __launch_bounds__(256) void flat_chunk_combine_kernel(
     }
 }
 
+// (WEIGHTED: the row's responsibilities times its weight SW[row], zero-weight rows skipped -- see flat_fused_pk_kernel)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void flat_chunk_fused_kernel(
     const float* __restrict__ X, const float* __restrict__ pack, int64_t n, int Jpad,
     const float* __restrict__ lpn2, float* __restrict__ partials /*at the chunk's first column*/,
-    const int* __restrict__ done_flag) {
+    const int* __restrict__ done_flag, const float* __restrict__ SW) {
     if (done_flag && *done_flag) return;
     constexpr int K = CH_SLOTS;
     const int lane = lane_id();
@@ -1329,19 +1389,28 @@ __global__ __launch_bounds__(BLOCK) void flat_chunk_fused_kernel(
     for (int k = 0; k < K; ++k) a_s0[k] = a_a0[k] = a_a1[k] = a_a2[k] = a_b0[k] = a_b1[k] = a_b2[k] = 0.f;
     int64_t r0, r1;
     wave_row_range(n, r0, r1);
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f, l2 = 0.f;
-    if (r0 < r1) { const float* xp = X + 3 * r0; x0 = xp[0]; x1 = xp[1]; x2 = xp[2]; l2 = lpn2[r0]; }
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f, l2 = 0.f, sw = 1.f;
+    if (r0 < r1) { const float* xp = X + 3 * r0; x0 = xp[0]; x1 = xp[1]; x2 = xp[2]; l2 = lpn2[r0]; if (WEIGHTED) sw = SW[r0]; }
     for (int64_t row = r0; row < r1; ++row) {
         const int64_t nrow = (row + 1 < r1) ? row + 1 : row;
         const float* xn = X + 3 * nrow;
         const float nx0 = xn[0], nx1 = xn[1], nx2 = xn[2], nl2 = lpn2[nrow];
+        float nsw = 1.f;
+        if constexpr (WEIGHTED) {
+            nsw = SW[nrow];
+            if (weight_is_zero(sw)) {                        // wave-uniform: the row is absent
+                x0 = nx0; x1 = nx1; x2 = nx2; l2 = nl2; sw = nsw;
+                continue;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const float d0 = x0 - P.mu0[k], d1 = x1 - P.mu1[k], d2 = x2 - P.mu2[k];
             float a = fmaf(-(d0 * P.g0[k]), d0, P.c[k] - l2);
             a = fmaf(-(d1 * P.g1[k]), d1, a);
             a = fmaf(-(d2 * P.g2[k]), d2, a);
-            const float rr = __builtin_amdgcn_exp2f(a);      // r = 2^(wl2 - lpn2) = exp(wlp - lpn)
+            float rr = __builtin_amdgcn_exp2f(a);            // r = 2^(wl2 - lpn2) = exp(wlp - lpn)
+            if constexpr (WEIGHTED) rr *= sw;
             const float rd0 = rr * d0, rd1 = rr * d1, rd2 = rr * d2;
             a_s0[k] += rr;
             a_a0[k] += rd0; a_a1[k] += rd1; a_a2[k] += rd2;
@@ -1350,6 +1419,7 @@ __global__ __launch_bounds__(BLOCK) void flat_chunk_fused_kernel(
             a_b2[k] = fmaf(rd2, d2, a_b2[k]);
         }
         x0 = nx0; x1 = nx1; x2 = nx2; l2 = nl2;
+        if constexpr (WEIGHTED) sw = nsw;
     }
     __shared__ float sh[FLAT_NSTAT * CH_J];
     const int w = wave_in_block();
@@ -2221,6 +2291,7 @@ static int launch_estep(hgmm_ctx* c, float* log_resp, float* lpn, int32_t* argma
     // (profiles/r04/estep_nt_by_J.log)
     const bool nt = NORMALISE && f.J % 4 == 0;
     const int rr = 0;
+    c->flat.last_estep_rows4 = false;                  // (set where the four-rows-in-flight kernel is launched)
     if (!NORMALISE && !log_resp && !lpn && argmax && predict_rows_layout(c, nv4, nv1)) {      // predict(): labels only
         ProfScope prof(c, HGMM_K_FLAT_ESTEP);
         (void)launch_predict_rows(c, nv4, nv1, argmax);
@@ -2264,6 +2335,7 @@ static int launch_estep(hgmm_ctx* c, float* log_resp, float* lpn, int32_t* argma
         }
         if (launched) {
             if (observed) pace_observe_end(c);
+            c->flat.last_estep_rows4 = true;
             *grid_out = grid_r;
             HGMM_HIP(c, hipGetLastError());
             return HGMM_OK;
@@ -2308,6 +2380,7 @@ static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* v
     const float* pk = c->f_pack.as<float>();
     float* part = c->f_partials.as<float>();
     double* lp = c->f_lpn_partials.as<double>();
+    const float* sw = c->flat_sw_ptr();             // hgmm_flat_set_weights: the WEIGHTED instantiations
     // Design notes (measured on MI355X at N = 1e6, J = 800; see DESIGN.md section 6 for the list):
     //  * more rows in flight per wave lose: 1 row (249 VGPRs, 2 waves/SIMD) 0.544 ms, 2 rows
     //    (310 regs, 1 wave/SIMD) 0.677 ms, 4 rows (424 regs) 0.772 ms;
@@ -2323,8 +2396,10 @@ static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* v
     //    leaves the safe range takes the kernel's row-maximum loop by itself).
 #define FUSED_CASE(S)                                                                           \
     do {                                                                                        \
-        flat_fused_pk_kernel<S><<<grid, BLOCK, 0, c->stream>>>(X, pk, c->n, f.J, f.Jpad, part,  \
-                                                              lp, done_flag, 1, comp_major ? 1 : 0); \
+        if (sw) flat_fused_pk_kernel<S, true><<<grid, BLOCK, 0, c->stream>>>(                  \
+                    X, pk, c->n, f.J, f.Jpad, part, lp, done_flag, 1, comp_major ? 1 : 0, sw);  \
+        else flat_fused_pk_kernel<S, false><<<grid, BLOCK, 0, c->stream>>>(                    \
+                    X, pk, c->n, f.J, f.Jpad, part, lp, done_flag, 1, comp_major ? 1 : 0, nullptr); \
         *valid_j = S * 64;                                                                      \
     } while (0)
     ProfScope prof(c, HGMM_K_FLAT_FUSED);
@@ -2362,7 +2437,7 @@ static int launch_reduce(hgmm_ctx* c, int nblocks, int valid_j, bool with_lpn, c
     if (c->comm_on() || !done_flag) done_flag = c->f_ctl.as<int>() + 16;        // always 0 (flat_setup)
     flat_reduce_kernel<<<(total + RED_IDX - 1) / RED_IDX + 1, RED_IDX * RED_SLICES, 0, c->stream>>>(
         c->f_partials.as<float>(), with_lpn ? c->f_lpn_partials.as<double>() : nullptr, nblocks,
-        n_lpn_blocks < 0 ? nblocks : n_lpn_blocks, valid_j, f.Jpad, (double)c->n, c->f_stats.as<double>(),
+        n_lpn_blocks < 0 ? nblocks : n_lpn_blocks, valid_j, f.Jpad, c->flat_n(), c->f_stats.as<double>(),
         done_flag);
     HGMM_HIP(c, hipGetLastError());
     if (c->comm_on()) HGMM_TRY(allreduce_f64_dev(c, c->f_stats.as<double>(), (size_t)total + 2));
@@ -2390,7 +2465,8 @@ static int chunk_normalisers(hgmm_ctx* c, bool want_arg, float* lpn_out, int32_t
     const int cblocks = (int)((c->n + 255) / 256);
     flat_chunk_combine_kernel<<<cblocks, 256, 0, c->stream>>>(cm, cs, want_arg ? ca : nullptr, f.nchunks, c->n,
                                                             c->f_lpn2.as<float>(), lpn_out, argmax_out,
-                                                            want_partials ? c->f_lpn_partials.as<double>() : nullptr);
+                                                            want_partials ? c->f_lpn_partials.as<double>() : nullptr,
+                                                            c->flat_sw_ptr());
     HGMM_HIP(c, hipGetLastError());
     if (n_lpn_blocks) *n_lpn_blocks = cblocks;
     return HGMM_OK;
@@ -2402,10 +2478,15 @@ static int chunk_statistics(hgmm_ctx* c, const int* done_flag, int* grid_out) {
     const int grid = grid_for(c, c->n, 2);
     {
         ProfScope prof(c, HGMM_K_FLAT_FUSED);
-        for (int ci = 0; ci < f.nchunks; ++ci)
-            flat_chunk_fused_kernel<<<grid, BLOCK, 0, c->stream>>>(
-                c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, f.Jpad, c->f_lpn2.as<float>(),
-                c->f_partials.as<float>() + ci * CH_J, done_flag);
+        const float* sw = c->flat_sw_ptr();
+        for (int ci = 0; ci < f.nchunks; ++ci) {
+            if (sw) flat_chunk_fused_kernel<true><<<grid, BLOCK, 0, c->stream>>>(
+                        c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, f.Jpad, c->f_lpn2.as<float>(),
+                        c->f_partials.as<float>() + ci * CH_J, done_flag, sw);
+            else flat_chunk_fused_kernel<false><<<grid, BLOCK, 0, c->stream>>>(
+                        c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, f.Jpad, c->f_lpn2.as<float>(),
+                        c->f_partials.as<float>() + ci * CH_J, done_flag, nullptr);
+        }
     }
     HGMM_HIP(c, hipGetLastError());
     *grid_out = grid;
@@ -2460,7 +2541,7 @@ static int enqueue_em_iteration(hgmm_ctx* c) {
         ProfScope prof(c, HGMM_K_FLAT_BOUNDARY);
         flat_boundary_kernel<<<f.Jpad / BND_COMP + 1, BND_COMP * RED_SLICES, 0, c->stream>>>(
             c->f_partials.as<float>(), c->f_lpn_partials.as<double>(), grid, valid_j, f.J, f.Jpad, f.cov_type, f.variant,
-            (double)c->n, c->f_stats.as<double>(), c->f_mu.as<float>(), c->f_cov.as<float>(), c->f_w.as<float>(),
+            c->flat_n(), c->f_stats.as<double>(), c->f_mu.as<float>(), c->f_cov.as<float>(), c->f_w.as<float>(),
             c->f_inv.as<float>(), c->f_pack.as<float>(), c->f_lls.as<float>(), f.lls_cap, f.tol, ctl, ctl_f, stop,
             stop_next);
         HGMM_HIP(c, hipGetLastError());
@@ -2497,11 +2578,59 @@ __global__ __launch_bounds__(256) void flat_mean_lpn_kernel(const double* __rest
     if (threadIdx.x == 0) *out = (sh[0] + sh[1] + sh[2] + sh[3]) / n;
 }
 
+// hgmm_flat_set_weights: the E-step's mean is sum_i s_i lpn_i / S.  The materialising kernels are not touched: the rows'
+// log-normalisers, which they write anyway, are reduced in ONE pass to the per-workgroup partial sums those kernels leave
+// without weights -- the same rows per wave, in the same order, the waves of a workgroup added in the same order -- so that
+// what follows (the host's sum or flat_mean_lpn_kernel, with S for n) is the code it was and s == 1 gives the unweighted
+// mean bit for bit.  A thread plays one wave of the E-step launch: `rows4` = the four-rows-in-flight kernel (groups of 4
+// rows dealt round-robin over the waves), otherwise the single-row kernel (one contiguous range per wave).  float64, a
+// fixed order, no floating-point atomics; rows of weight zero are skipped, not multiplied (their lpn may be NaN).
+__global__ __launch_bounds__(256) void flat_weighted_lpn_partials_kernel(
+    const float* __restrict__ lpn, const float* __restrict__ SW, int64_t n, int grid, int rows4, double* __restrict__ partials) {
+    const int64_t nw = (int64_t)grid * WAVES_PER_BLOCK;
+    const int64_t gw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // the wave this thread plays
+    double acc = 0.0;
+    if (gw < nw) {
+        if (rows4) {
+            const int64_t ngroups = (n + 3) / 4;
+            for (int64_t g = gw; g < ngroups; g += nw)
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t row = g * 4 + r;
+                    if (row < n) {
+                        const float sw = SW[row];
+                        if (!weight_is_zero(sw)) acc += (double)sw * (double)lpn[row];
+                    }
+                }
+        } else {
+            const int64_t per = (n + nw - 1) / nw;
+            const int64_t r0 = gw * per < n ? gw * per : n, r1 = r0 + per < n ? r0 + per : n;
+            for (int64_t row = r0; row < r1; ++row) {
+                const float sw = SW[row];
+                if (!weight_is_zero(sw)) acc += (double)sw * (double)lpn[row];
+            }
+        }
+    }
+    __shared__ double sh[256];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    if (gw < nw && (threadIdx.x % WAVES_PER_BLOCK) == 0) {
+        double t = 0.0;
+        for (int i = 0; i < WAVES_PER_BLOCK; ++i) t += sh[threadIdx.x + i];
+        partials[gw / WAVES_PER_BLOCK] = t;
+    }
+}
+
 static int flat_estep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu, const float* inv_std,
-                              const float* w, float* dev_log_resp, float* dev_lpn, int32_t* dev_argmax, int* grid_out,
-                              bool params_on_device = false) {
+                              const float* w, float* dev_log_resp, float*& dev_lpn, int32_t* dev_argmax, int* grid_out,
+                              bool params_on_device = false, bool want_mean = false) {
     HGMM_TRY(flat_check(c, cov_type, variant, J));
     HGMM_TRY(flat_setup(c, cov_type, variant, J));
+    if (want_mean && c->flat_weighted && !dev_lpn && J <= FLAT_MAX_J) {
+        // weights in force: the mean is formed from the rows' log-normalisers -- the context's scratch when the caller has none
+        // (J > FLAT_MAX_J: the chunked path's combine kernel weights its partial sums itself)
+        HGMM_TRY(ensure(c, c->f_lpn_rows, sizeof(float) * (size_t)c->n));
+        dev_lpn = c->f_lpn_rows.as<float>();
+    }
     if (params_on_device) {
         // the packed table is formed straight from the caller's device arrays: no staging, no copy
         if (!mu || !inv_std || !w) return fail(c, HGMM_ERR_ARG, "device parameter array is NULL");
@@ -2527,6 +2656,11 @@ static int flat_estep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
         }
     } else {
         HGMM_TRY(launch_estep<true>(c, dev_log_resp, dev_lpn, dev_argmax, &grid));
+        if (want_mean && c->flat_weighted) {               // the workgroups' partial sums, weighted (see the kernel)
+            flat_weighted_lpn_partials_kernel<<<(grid * WAVES_PER_BLOCK + 255) / 256, 256, 0, c->stream>>>(
+                dev_lpn, c->flat_sw.as<float>(), c->n, grid, c->flat.last_estep_rows4 ? 1 : 0, c->f_lpn_partials.as<double>());
+            HGMM_HIP(c, hipGetLastError());
+        }
     }
     *grid_out = grid;
     return HGMM_OK;
@@ -2537,7 +2671,8 @@ extern "C" int hgmm_flat_estep(hgmm_ctx* c, int cov_type, int variant, int J, co
                                float* dev_lpn, int32_t* dev_argmax, double* mean_lpn_out) {
     HGMM_ENTER(c);
     int grid = 0;
-    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid));
+    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid, false,
+                                mean_lpn_out != nullptr));
     if (mean_lpn_out) {
         std::vector<double> h(grid);
         HGMM_HIP(c, hipMemcpyAsync(h.data(), c->f_lpn_partials.p, sizeof(double) * grid,
@@ -2545,7 +2680,7 @@ extern "C" int hgmm_flat_estep(hgmm_ctx* c, int cov_type, int variant, int J, co
         HGMM_HIP(c, ctx_stream_sync(c));
         double t = 0.0;
         for (double v : h) t += v;
-        *mean_lpn_out = t / (double)c->n;
+        *mean_lpn_out = t / c->flat_n();
     }
     return HGMM_OK;
 }
@@ -2555,9 +2690,10 @@ extern "C" int hgmm_flat_estep_async(hgmm_ctx* c, int cov_type, int variant, int
                                      float* dev_lpn, int32_t* dev_argmax, double* dev_mean_lpn) {
     HGMM_ENTER(c);
     int grid = 0;
-    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid));
+    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid, false,
+                                dev_mean_lpn != nullptr));
     if (dev_mean_lpn) {
-        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, (double)c->n, dev_mean_lpn);
+        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, c->flat_n(), dev_mean_lpn);
         HGMM_HIP(c, hipGetLastError());
     }
     return HGMM_OK;                                   // nothing waited for: the caller's arrays were copied to the ring
@@ -2569,9 +2705,9 @@ extern "C" int hgmm_flat_estep_dev(hgmm_ctx* c, int cov_type, int variant, int J
     HGMM_ENTER(c);
     int grid = 0;
     HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, dev_mu, dev_inv_std, dev_w, dev_log_resp, dev_lpn, dev_argmax,
-                                &grid, /*params_on_device=*/true));
+                                &grid, /*params_on_device=*/true, dev_mean_lpn != nullptr));
     if (dev_mean_lpn) {
-        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, (double)c->n, dev_mean_lpn);
+        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, c->flat_n(), dev_mean_lpn);
         HGMM_HIP(c, hipGetLastError());
     }
     return HGMM_OK;
@@ -2676,12 +2812,23 @@ static int flat_mstep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
     const float* X = c->x_aos.as<float>();
     float* part = c->f_partials.as<float>();
     const float* hint = c->f_hint.as<float>();
+    const float* sw = c->flat_sw_ptr();
     int valid_j = 0;
     // non-temporal loads: 6.1 -> 6.8 TB/s at J = 800, a gain or a tie for every row length that is a whole number of
     // 16-byte pieces -- and a loss when rows straddle them (J = 513: 0.380 vs 0.351 ms, J = 37: 0.176 vs 0.142: a line shared by
     // two rows is then fetched for each of them; profiles/r04/mstep_nt_by_J.log)
     const bool ntload = J % 4 == 0;
-#define MSTEP_LAUNCH(A, B, RESP, HINT, JV, PART)                                                               \
+#define MSTEP_LAUNCH_W(A, B, RESP, HINT, JV, PART)                                                             \
+    do {                                                                                                       \
+        if (is_log) {                                                                                          \
+            if (ntload) flat_mstep_kernel<A, B, true, true, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw);  \
+            else flat_mstep_kernel<A, B, true, false, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw);       \
+        } else {                                                                                               \
+            if (ntload) flat_mstep_kernel<A, B, false, true, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw); \
+            else flat_mstep_kernel<A, B, false, false, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw);      \
+        }                                                                                                      \
+    } while (0)
+#define MSTEP_LAUNCH_U(A, B, RESP, HINT, JV, PART)                                                             \
     do {                                                                                                       \
         if (is_log) {                                                                                          \
             if (ntload) flat_mstep_kernel<A, B, true, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr);  \
@@ -2690,6 +2837,11 @@ static int flat_mstep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
             if (ntload) flat_mstep_kernel<A, B, false, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr); \
             else flat_mstep_kernel<A, B, false, false><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr);      \
         }                                                                                                      \
+    } while (0)
+    // hgmm_flat_set_weights: the WEIGHTED instantiation set
+#define MSTEP_LAUNCH(A, B, RESP, HINT, JV, PART)                                                               \
+    do {                                                                                                       \
+        if (sw) MSTEP_LAUNCH_W(A, B, RESP, HINT, JV, PART); else MSTEP_LAUNCH_U(A, B, RESP, HINT, JV, PART);    \
     } while (0)
     if (f.chunked) {
         ProfScope prof(c, HGMM_K_FLAT_MSTEP);
@@ -2709,6 +2861,8 @@ static int flat_mstep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
 #undef MSTEP_M
     }
 #undef MSTEP_LAUNCH
+#undef MSTEP_LAUNCH_W
+#undef MSTEP_LAUNCH_U
     HGMM_HIP(c, hipGetLastError());
     c->flat.last_kernel = 2;                               // (the next E-step's grid looks at this, estep_rows_grid)
     c->flat.idle_since_launch = false;
@@ -2921,6 +3075,34 @@ extern "C" int hgmm_flat_train(hgmm_ctx* c, int cov_type, int variant, int J, in
     HGMM_TRY(hgmm_flat_train_begin(c, cov_type, variant, J, tol, mu, cov, w, max_iter));
     HGMM_TRY(hgmm_flat_train_step(c, max_iter));
     return hgmm_flat_train_end(c, mu, cov, w, inv_std_out, lls_out, n_iter_out, converged_out);
+}
+
+// per-point weights of the resident cloud for the flat EM (include/hgmm.h): flat_sw [n] parallel to the rows of x_aos
+extern "C" int hgmm_flat_set_weights(hgmm_ctx* c, const float* s, int64_t n) {
+    HGMM_ENTER(c);
+    const char* what = "hgmm_flat_set_weights";
+    if (!c->have_f32 || c->n <= 0)
+        return fail(c, HGMM_ERR_STATE, "%s: no cloud with float32 rows (hgmm_set_points_f32 / _f64 or hgmm_points_bind first; "
+                    "a forest cloud of hgmm_set_points_batch_* has none)", what);
+    if (!s) { c->flat_weighted = false; return HGMM_OK; }
+    if (n != c->n)
+        return fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident cloud has %lld points", what, (long long)n, (long long)c->n);
+    double sum = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(s[i] >= 0.0f) || !(s[i] < INFINITY))                  // (NaN fails the first comparison)
+            return fail(c, HGMM_ERR_ARG, "%s: weight %lld is %g (weights must be finite and >= 0)", what, (long long)i, (double)s[i]);
+        sum += (double)s[i];
+    }
+    if (!(sum > 0.0)) return fail(c, HGMM_ERR_ARG, "%s: all %lld weights are zero", what, (long long)n);
+    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
+    c->flat_weighted = false;
+    HGMM_HIP(c, hipSetDevice(c->device));
+    HGMM_TRY(ensure(c, c->flat_sw, sizeof(float) * (size_t)n));
+    HGMM_HIP(c, hipMemcpyAsync(c->flat_sw.p, s, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    c->flat_wsum = sum;
+    c->flat_weighted = true;
+    return HGMM_OK;
 }
 
 extern "C" int hgmm_flat_stats(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu,

@@ -40,6 +40,8 @@ struct FlatState {
     bool chunked = false;             // J > FLAT_MAX_J: 832-component chunks
     int nchunks = 1;
     int last_kernel = 0;              // what this context enqueued last: 1 materialising E-step, 2 M-step from resp, 3 fused EM
+    bool last_estep_rows4 = false;    // the last materialising E-step ran the four-rows-in-flight kernel (its waves' row order:
+                                      // flat_weighted_lpn_partials_kernel re-plays it)
     bool idle_since_launch = true;    // the host has drained the stream since the last of these launches (ctx_stream_sync)
 };
 
@@ -191,6 +193,14 @@ struct hgmm_ctx {
     hgmm::DevBuf src_w;               // double [n_pad], parallel to x_soa64 (level-0 order)
     bool src_weighted = false;        // src_w is in force
     double src_wsum = 0.0;            // (src_weighted) sum of the weights, on the host in index order
+    // per-point weights of the resident cloud for the flat (diag / spherical) EM (hgmm_flat_set_weights); dropped with the
+    // cloud like src_w
+    hgmm::DevBuf flat_sw;             // float [n], parallel to the rows of x_aos
+    bool flat_weighted = false;       // flat_sw is in force
+    double flat_wsum = 0.0;           // (flat_weighted) S = sum of the float32 weights, float64 on the host in index order
+    hgmm::DevBuf f_lpn_rows;          // float [n] the rows' log-normalisers when a weighted E-step's caller brings no dev_lpn
+    double flat_n() const { return flat_weighted ? flat_wsum : (double)n; }     // what the flat M-step divides by
+    const float* flat_sw_ptr() const { return flat_weighted ? static_cast<const float*>(flat_sw.p) : nullptr; }
 
     // ---- flat EM ----------------------------------------------------------------
     hgmm::FlatState flat;

@@ -36,6 +36,14 @@ class Feature(abc.ABC):
         return self.compute(data)
 
 
+def _split_weighted(X, sample_weight):
+    """(points, weights) of a fit's input: a ``WeightedPoints(points, weights)`` -- any object with those two fields -- is
+    taken apart, an explicit ``sample_weight`` takes precedence over the weights it brings."""
+    if hasattr(X, "points") and hasattr(X, "weights") and not isinstance(X, DevicePoints):
+        return X.points, (X.weights if sample_weight is None else sample_weight)
+    return X, sample_weight
+
+
 class GMM_GPU_Base:
     """fit/predict (reference gmm.py:65-101).  After ``fit``: ``means_``, ``covariances_``,
     ``weights_``, ``lls``, ``inv_covs``."""
@@ -52,9 +60,13 @@ class GMM_GPU_Base:
     def _init_params(self, X):
         return init_gmm_params(X, self.num_components, cov_type=self.cov_type)
 
-    def fit(self, X, init=None):
+    def fit(self, X, init=None, sample_weight=None):
         """``init`` = optional explicit ``(means, weights, covs)`` (the reference always draws
-        them with the host RNG; tests and benchmarks pass them in)."""
+        them with the host RNG; tests and benchmarks pass them in).
+        ``sample_weight`` [N] >= 0 (default None; a ``WeightedPoints(points, weights)`` brings its own, a
+        ``DevicePoints(X, weights=)`` too): point i counts as that many points -- a voxel centroid with its count.  The
+        initialiser does not see the weights."""
+        X, sample_weight = _split_weighted(X, sample_weight)
         if isinstance(X, DevicePoints):                   # already resident (hgmm_amd.asarray): no upload
             # the reference's initialiser samples from the HOST array (gmm_impl.py:26-41): one download of the
             # float32 rows when the caller brings no initial parameters
@@ -63,11 +75,13 @@ class GMM_GPU_Base:
         else:
             X = np.asarray(X)
             means, weights, covs = init if init is not None else self._init_params(X)
-            dev_X = asarray(X.astype(np.float32))
+            dev_X = asarray(X.astype(np.float32), weights=sample_weight)     # (the weights travel with the resident cloud)
+            sample_weight = None
         with timer(self._label, getattr(dev_X, "ctx", None)):
             inv, mu, w, cov, lls = train_gmm(dev_X, self.max_iter, self.tol,
                                              np.asarray(means, np.float32), np.asarray(covs, np.float32),
-                                             np.asarray(weights, np.float32), cov_type=self.cov_type)
+                                             np.asarray(weights, np.float32), cov_type=self.cov_type,
+                                             sample_weight=sample_weight)
         self.means_, self.covariances_, self.weights_ = mu, cov, w
         self.lls, self.inv_covs = lls, inv
         if self._verbose and len(lls):
@@ -116,8 +130,10 @@ class GMM_GPU(Feature):
         self._clf = self._base(self._n_gmm_components, max_iter=self.max_iter, tol=self.tol,
                                cov_type=self.cov_type)
 
-    def compute(self, data):
-        self._clf.fit(data)
+    def compute(self, data, weights=None):
+        """``weights`` [N] >= 0: per-point weights of the fit (``fit(data, sample_weight=weights)``); a
+        ``WeightedPoints`` brings its own."""
+        self._clf.fit(data, sample_weight=weights)
         return self._clf.means_, self._clf.weights_, self._clf.covariances_, self._clf.inv_covs
 
     def predict(self, data):
@@ -128,8 +144,8 @@ class GMM_CPU(GMM_GPU):
     """reference gmm.py:103-118; ``compute`` -> (means, weights, covariances)."""
     _base = GMM_CPU_Base
 
-    def compute(self, data):
-        self._clf.fit(data)
+    def compute(self, data, weights=None):
+        self._clf.fit(data, sample_weight=weights)
         return self._clf.means_, self._clf.weights_, self._clf.covariances_
 
 

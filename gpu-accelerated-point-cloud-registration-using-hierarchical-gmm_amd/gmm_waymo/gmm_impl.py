@@ -50,21 +50,24 @@ def row_norms(X, squared=False):
     return n if squared else np.sqrt(n)
 
 
-def e_step(X, inv_cov, means, weights, cov_type='diag'):
-    """-> (mean log-normaliser, log_resp[N,J] DeviceArray).  Reference gmm_impl.py:105-116."""
-    return _flat.e_step(X, inv_cov, means, weights, cov_type, VARIANT)
+def e_step(X, inv_cov, means, weights, cov_type='diag', sample_weight=None):
+    """-> (mean log-normaliser, log_resp[N,J] DeviceArray).  Reference gmm_impl.py:105-116.
+    ``sample_weight`` [N] >= 0: the mean is ``sum(s * lpn) / sum(s)``."""
+    return _flat.e_step(X, inv_cov, means, weights, cov_type, VARIANT, sample_weight)
 
 
-def m_step(X, resp, cov_type='diag', centre_hint=None):
+def m_step(X, resp, cov_type='diag', centre_hint=None, sample_weight=None):
     """-> (weights, means, covariances).  Reference gmm_impl.py:90-103.  ``resp`` may be a
     host array, a DeviceArray, or ``log_resp.exp()`` (lazy; the exp is fused)."""
-    return _flat.m_step(X, resp, cov_type, VARIANT, centre_hint)
+    return _flat.m_step(X, resp, cov_type, VARIANT, centre_hint, sample_weight)
 
 
-def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type='diag'):
+def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type='diag', sample_weight=None):
     """-> (inv_cov, means, weights, covariances, log_ll).  Reference gmm_impl.py:118-145.
-    The whole loop is device-resident (fused E+M kernels, one read-back at the end)."""
-    return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, VARIANT)
+    The whole loop is device-resident (fused E+M kernels, one read-back at the end).
+    ``sample_weight`` [N] >= 0: point i counts as that many points (a voxel centroid with its count); default: the weights a
+    ``DevicePoints`` brings, else none."""
+    return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, VARIANT, sample_weight)
 
 
 def predict(X, inv_cov, means, weights, cov_type='diag'):

@@ -3,7 +3,7 @@ returns ``(means, weights)`` only (reference gmm.py:57,70); covariances start at
 (gmm.py:80); host NumPy results (gmm.py:95)."""
 import numpy as np
 
-from ..gmm_waymo.gmm import Feature, GMM_Sklearn, _cpu_name_notice  # noqa: F401
+from ..gmm_waymo.gmm import Feature, GMM_Sklearn, _cpu_name_notice, _split_weighted  # noqa: F401
 from ..gmm_waymo.gmm import OneClassSVM as _SklearnOneClassSVM
 from . import gmm_impl
 from .gmm_impl import train_gmm, init_gmm_params, timer, predict, asarray  # noqa: F401
@@ -17,11 +17,14 @@ class GMM_GPU_Base:
         self.max_iter = max_iter
         self.tol = tol
 
-    def fit(self, X, init=None):
+    def fit(self, X, init=None, sample_weight=None):
+        """``sample_weight`` [N] >= 0 (default None; a ``WeightedPoints(points, weights)`` brings its own): point i counts as
+        that many points.  The KMeans seeding of ``init_gmm_params`` does not see the weights."""
+        X, sample_weight = _split_weighted(X, sample_weight)
         X = np.asarray(X)
+        dev_X = asarray(X.astype(np.float32), weights=sample_weight)         # (the weights travel with the resident cloud)
         means, weights = init if init is not None else init_gmm_params(X, self.num_components)
         covs = 0.1 * np.ones((self.num_components, 3), dtype=np.float32)
-        dev_X = asarray(X.astype(np.float32))
         with timer(self._label):
             inv, mu, w, cov, lls = train_gmm(dev_X, self.max_iter, self.tol, np.asarray(means, np.float32),
                                              covs, np.asarray(weights, np.float32))
@@ -56,8 +59,9 @@ class GMM_GPU(Feature):
     def init(self):
         self._clf = self._base(self._n_gmm_components, max_iter=self.max_iter, tol=self.tol)
 
-    def compute(self, data):
-        self._clf.fit(data)
+    def compute(self, data, weights=None):
+        """``weights`` [N] >= 0: per-point weights of the fit; a ``WeightedPoints`` brings its own."""
+        self._clf.fit(data, sample_weight=weights)
         return self._clf.means_, self._clf.weights_
 
     def predict(self, data):

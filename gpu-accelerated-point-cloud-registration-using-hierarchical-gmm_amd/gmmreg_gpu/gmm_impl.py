@@ -23,18 +23,20 @@ def estimate_log_prob(X, inv_cov, means):
     return _flat.estimate_log_prob(X, inv_cov, means, 'diag')
 
 
-def e_step(X, inv_cov, means, weights):
-    return _flat.e_step(X, inv_cov, means, weights, 'diag', VARIANT)
+def e_step(X, inv_cov, means, weights, sample_weight=None):
+    return _flat.e_step(X, inv_cov, means, weights, 'diag', VARIANT, sample_weight)
 
 
-def m_step(X, resp, centre_hint=None):
-    return _flat.m_step(X, resp, 'diag', VARIANT, centre_hint)
+def m_step(X, resp, centre_hint=None, sample_weight=None):
+    return _flat.m_step(X, resp, 'diag', VARIANT, centre_hint, sample_weight)
 
 
-def train_gmm(X, max_iter, tol, means, covariances, weights=None):
+def train_gmm(X, max_iter, tol, means, covariances, weights=None, sample_weight=None):
+    """``sample_weight`` [N] >= 0: per-point weights of the fit (a ``DevicePoints`` may bring its own).  The KMeans seeding of
+    :func:`init_gmm_params` does not see them."""
     if weights is None:
         weights = np.ones(len(means), dtype=np.float32) / len(means)
-    return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, 'diag', VARIANT)
+    return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, 'diag', VARIANT, sample_weight)
 
 
 def predict(X, inv_cov, means, weights):

@@ -210,6 +210,32 @@ int hgmm_flat_train_end(hgmm_ctx* ctx, float* mu, float* cov, float* w, float* i
 int hgmm_flat_stats(hgmm_ctx* ctx, int cov_type, int variant, int J,
                     const float* mu, const float* inv_std, const float* w,
                     double* stats_out, double* sum_lpn_out, double* n_points_out);
+/* Per-point weights for the flat (diag / spherical) fit.  The reference has no counterpart: its pipeline voxel-down-samples
+ * a scan (run_gmm_static.py:28) and fits the centroids as if each were one point.  Point i with weight s_i >= 0 counts as
+ * s_i points.  Let S = sum_i s_i (a float64 sum on the host, in index order, of the float32 values the device holds).  Three
+ * statements of the reference change and nothing else does:
+ *   M-step          (gmm_waymo gmm_impl.py:90-103, gmmreg_gpu gmm_impl.py:46-52)  resp_ij becomes s_i resp_ij in every sum and
+ *                   nk / n becomes nk / S; the + eps terms of both flavours stay where they are, after the sums;
+ *   log-likelihood  behind the stop rule (gmm_impl.py:113,136)  mean_i lpn_i becomes sum_i s_i lpn_i / S;
+ *   hgmm_flat_stats the statistics and sum_lpn are the s-weighted sums, n_points_out = S.
+ * Unchanged: log_resp, the per-point lpn, arg-max, predict, estimate_log_prob, the initialisers (the KMeans seeding of
+ * flavour G does NOT see the weights) and the full-covariance, KMeans and tree entries.
+ * Integer weights are repetition (up to the order of summation).  A ZERO WEIGHT MAKES THE ROW ABSENT WHATEVER ITS
+ * COORDINATES: the weighted kernels skip such a row instead of multiplying by zero, so a row of NaNs with s = 0 leaves every
+ * result finite (a mask).  s == 1 everywhere gives the unweighted results bit for bit; s == 2 everywhere gives exactly twice
+ * the hgmm_flat_stats outputs.
+ * The weights ATTACH TO THE CLOUD THE CONTEXT IS WORKING ON -- the float32 rows of hgmm_set_points_* or of a bound handle:
+ * HGMM_ERR_STATE without one, and with the forest cloud of hgmm_set_points_batch_* resident (it has no float32 rows).
+ * Whatever changes the resident cloud drops them: hgmm_set_points_f32 / _f64, hgmm_points_bind (of another cloud),
+ * hgmm_set_points_batch_f32 / _f64, hgmm_points_destroy of the bound handle.  A handle does not own weights: they do not
+ * survive binding another cloud and coming back (per-handle ownership is out of scope; set them again after the bind).
+ * s == NULL: no weights (the unweighted kernels run, every result what it was, bit for bit).  n must equal the resident
+ * count; a NaN, infinite or negative weight (hgmm_last_error names its index) and all-zero weights are refused on the host
+ * before anything is touched: HGMM_ERR_ARG, and the previous weights stay in force.
+ * Honoured by hgmm_flat_train, hgmm_flat_train_begin / _step / _end, hgmm_flat_stats, hgmm_flat_mstep, hgmm_flat_mstep_dev
+ * and by the MEAN written by hgmm_flat_estep, _async and _dev -- under a communicator too: each rank holds the weights of its
+ * shard, and the point-count slot that travels with the statistics carries the rank's S.  IGNORED by everything else.       */
+int hgmm_flat_set_weights(hgmm_ctx* ctx, const float* s /* host [n]; NULL = no weights */, int64_t n);
 
 /* All-reduces this context has enqueued on its communicator so far, and the level-iterations hgmm_tree_build has enqueued
  * behind a level's stop (each costs two all-reduces on unchanged operands): under a communicator every rank must issue
@@ -438,7 +464,7 @@ int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, c
  * hgmm_tree_score_multi: summary[0] = sum of w, summary[1..6] = the w-weighted sums of what they are without weights, added in
  * the same fixed order; the per-point arrays node / maha2 / logp are not weighted.  NOT honoured by the build (hgmm_tree_build*:
  * the weights of a SOURCE cloud are hgmm_tree_set_source_weights', below) nor by any flat, full-covariance or KMeans entry:
- * they ignore them.                                                                                                         */
+ * they ignore them (the flat fit has weights of its own: hgmm_flat_set_weights).                                             */
 int hgmm_tree_set_target_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
 int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
                                        const double* const* w /* w == NULL: none; w[b] == NULL: pair b unweighted */,
@@ -469,8 +495,9 @@ int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
  * refused on the host before anything is touched: HGMM_ERR_ARG, and the previous weights stay in force.
  * Honoured by hgmm_tree_build (serial entry) and hgmm_tree_build_batch (batch entry), in both precisions of
  * hgmm_tree_set_precision, and by nothing else.  IGNORED by the stand-alone steps below (hgmm_tree_estep, hgmm_tree_mstep,
- * hgmm_tree_loglik and the generic E-step kernel behind them), by every flat, full-covariance and KMeans entry, and by the
- * registration and score entries (their weights are the TARGET's, above).  Under a communicator hgmm_tree_build with
+ * hgmm_tree_loglik and the generic E-step kernel behind them), by every flat, full-covariance and KMeans entry (the flat fit
+ * has weights of its own: hgmm_flat_set_weights), and by the registration and score entries (their weights are the TARGET's,
+ * above).  Under a communicator hgmm_tree_build with
  * weights resident returns HGMM_ERR_STATE: sharded weighted builds are not supported.                                        */
 int hgmm_tree_set_source_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
 int hgmm_tree_set_source_weights_batch(hgmm_ctx* ctx, int B,
