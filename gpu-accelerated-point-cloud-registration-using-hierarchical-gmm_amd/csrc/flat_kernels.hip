@@ -181,6 +181,20 @@ __device__ __forceinline__ void wave_row_range(int64_t n, int64_t& r0, int64_t& 
     r1 = r0 + per < n ? r0 + per : n;
     if (r0 > n) r0 = n;
 }
+// The same range as wave-uniform SCALARS: first row and row count.  The 64-bit division above goes through v_rcp and
+// leaves r0 / r1 in vector registers although every lane holds the same value; a row loop that compares against them
+// pays a v_cmp_*_i64 per comparison.  Read back through readfirstlane, the loop's counter, its prefetch clamp and its
+// exit test are scalar instructions.  (A wave never owns 2^31 rows: the count is an int.)
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+    const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffLL)), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return ((int64_t)hi << 32) | (int64_t)(unsigned int)lo;
+}
+__device__ __forceinline__ void wave_row_range_uniform(int64_t n, int64_t& r0, int& nrows) {
+    int64_t r1;
+    wave_row_range(n, r0, r1);
+    r0 = uniform_i64(r0);
+    nrows = (int)(uniform_i64(r1) - r0);                 // (r1 >= r0 always)
+}
 
 template <bool NT>
 __device__ __forceinline__ void store_f4(float* p, float a, float b, float c, float d) {
@@ -869,6 +883,11 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     }
 
     // largest constant of the table = upper bound of every wl2 (identical in every wave)
+    // (m0 and the origin below are derived by EVERY wave, from the table it has just loaded, and not once by the kernel
+    //  that writes the table: flat_finalize_kernel, flat_boundary_kernel, flat_finalize_mb_kernel and flat_pack_kernel
+    //  all write it from several workgroups, so one wave could only derive them behind a cross-workgroup hand-off --
+    //  a ticket and agent-scope fences, microseconds on the latency chain between two iterations -- or in one more
+    //  launch, against ~130 vector instructions per wave here, less than one of its ~1000 rows)
     float m0 = cs;
 #pragma unroll
     for (int p = 0; p < KP; ++p) m0 = fmaxf(m0, fmaxf(cc[p].x, cc[p].y));
@@ -876,8 +895,11 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     // (false for NaN as well; below -64 the row-maximum loop's "tiny" rule applies, see lpn2_from)
     const bool small_shift = allow_const_shift && m0 <= CS_MAX_SHIFT && m0 >= -64.0f;
 
-    int64_t r0, r1;
-    wave_row_range(n, r0, r1);
+    // row range and loop control in scalar registers (wave_row_range_uniform)
+    int64_t r0;
+    int nrows;
+    wave_row_range_uniform(n, r0, nrows);
+    const float* const xw = X + 3 * r0;
     double lsum = 0.0;
     // First moments are summed about ONE origin for all components and moved to the component's mean when the wave is
     // done:  sum r (x - mu) = sum r (x - o) - (mu - o) sum r.  The row's x - o is a wave-uniform operand, so the update
@@ -926,17 +948,21 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
         cs -= m0;
     }
     const float eps_scale = __builtin_amdgcn_exp2f(-m0);
+    // FLAT_EPS in a vector register: the denominator's FMA below then reads the row's sum straight from the scalar
+    // register the wave reduction left it in (one v_fma_f32; an inline literal would need the sum copied to a VGPR first)
+    float eps_v = FLAT_EPS;
+    asm volatile("" : "+v"(eps_v));
     float lacc = 0.f;                      // sum of log2(den) of the rows since the last flush
     float x0 = 0.f, x1 = 0.f, x2 = 0.f;
     float sw = 1.f;                        // (WEIGHTED) this row's weight
     double swsum = 0.0;                    // (WEIGHTED) sum of the weights of this wave's rows
-    if (r0 < r1) { const float* xp = X + 3 * r0; x0 = xp[0]; x1 = xp[1]; x2 = xp[2]; if (WEIGHTED) sw = SW[r0]; }
-    for (int64_t row = r0; row < r1; ++row) {
-        const int64_t nrow = (row + 1 < r1) ? row + 1 : row;
-        const float* xn = X + 3 * nrow;
+    if (nrows > 0) { x0 = xw[0]; x1 = xw[1]; x2 = xw[2]; if (WEIGHTED) sw = SW[r0]; }
+    for (int row = 0; row < nrows; ++row) {                 // (row: counted from the wave's first one)
+        const int nrow = (row + 1 < nrows) ? row + 1 : row;
+        const float* xn = xw + 3 * (int64_t)nrow;
         const float nx0 = xn[0], nx1 = xn[1], nx2 = xn[2];
         float nsw = 1.f;
-        if constexpr (WEIGHTED) nsw = SW[nrow];
+        if constexpr (WEIGHTED) nsw = SW[r0 + nrow];
         // (WEIGHTED) a row of weight zero is absent, whatever its coordinates: a wave-uniform branch round the row's work
         if (!WEIGHTED || !weight_is_zero(sw)) {
             const f2 X0 = f2{x0, x0}, X1 = f2{x1, x1}, X2 = f2{x2, x2};
@@ -958,7 +984,9 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
                 a = a - g2[p] * q2[p];
                 if (CS) {
                     wl[p] = f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-                    sacc += wl[p];
+                    // (the first pair starts the sum: 0 + 2^a is 2^a bit for bit -- an exponential is never -0 --
+                    //  and one packed addition fewer)
+                    sacc = p == 0 ? wl[p] : sacc + wl[p];
                 } else {
                     wl[p] = a;
                     m = fmaxf(m, fmaxf(a.x, a.y));
@@ -983,7 +1011,7 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
                 for (int p = 0; p < KP; ++p) {
                     const f2 t = wl[p] - M;
                     wl[p] = f2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                    sacc += wl[p];
+                    sacc = p == 0 ? wl[p] : sacc + wl[p];
                 }
                 if (ODD) wls = __builtin_amdgcn_exp2f(wls - m);
             }
@@ -994,12 +1022,12 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
             if (CS) {
                 // lpn2_from with m = m0 in [-64, CS_MAX_SHIFT]: no "tiny" case, eps 2^-m0 is loop-invariant;
                 // the log-normalisers are summed in float32 over 8 rows before they join the float64 total
-                const float den = fmaf(FLAT_EPS, eps_scale, s);
+                const float den = fmaf(eps_v, eps_scale, s);
                 inv_den = __builtin_amdgcn_rcpf(den);
                 if constexpr (WEIGHTED) lacc = fmaf(sw, __builtin_amdgcn_logf(den), lacc);
                 else lacc += __builtin_amdgcn_logf(den);
                 if constexpr (!WEIGHTED) {
-                    if (((row - r0) & 7) == 7) {
+                    if ((row & 7) == 7) {
                         asm volatile("" ::: "memory");          // keeps this a (wave-uniform) branch, not selects
                         lsum += (double)lacc;
                         lacc = 0.f;
@@ -1029,7 +1057,7 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
         if constexpr (WEIGHTED) {
             // the 8-row flush of lacc, on the rows' schedule whether this one was skipped or not (ONE site for both paths:
             // a second one in the skipped path cost <13, true> 45 AGPRs and its second wave per SIMD)
-            if (CS && ((row - r0) & 7) == 7) {
+            if (CS && (row & 7) == 7) {
                 asm volatile("" ::: "memory");
                 lsum += (double)lacc;
                 lacc = 0.f;
@@ -1042,11 +1070,11 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
         // the closing term's sum of the wave's weights, float64, taken here and not in the loop (two registers the loop
         // does not have); zero weights add nothing
         if (CS) {
-            for (int64_t i = r0 + lane; i < r1; i += 64) swsum += (double)SW[i];
+            for (int64_t i = r0 + lane; i < r0 + nrows; i += 64) swsum += (double)SW[i];
             swsum = wave_sum_f64(swsum);
         }
     }
-    if (CS) lsum = (lsum + (double)lacc + (WEIGHTED ? swsum : (double)(r1 > r0 ? r1 - r0 : 0)) * (double)m0) * (double)LN2;
+    if (CS) lsum = (lsum + (double)lacc + (WEIGHTED ? swsum : (double)nrows) * (double)m0) * (double)LN2;
     };
     if (small_shift) rows(std::true_type{});
     else rows(std::false_type{});
@@ -1064,40 +1092,47 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
 
     // (a statistic's LDS row is padded by 8 words: the component-major copy below has a wave read 8 components x 8
     //  rows at once, and NSLOT * 64 words apart all rows of a component would share one bank)
-    constexpr int ST = NSLOT * 64, STP = ST + 8;
-    __shared__ float sh[FLAT_NSTAT * STP];
+    // The four waves' sums meet in the fixed order ((w0 + w1) + w2) + w3 -- what makes a partial reproducible -- over THREE
+    // LDS copies of the block: waves 0, 2 and 3 store theirs side by side, wave 1 then adds into wave 0's copy, and the
+    // output loop adds the three copies in that order on its way out.  Two barriers where four turns on one copy took
+    // four, and the same bits.  (Four copies and one barrier do not fit: 4 x 23.5 KB at NSLOT = 13, twice per CU, is
+    // more than the 160 KB; three copies leave every NSLOT the workgroups per CU its registers allow.)
+    constexpr int ST = NSLOT * 64, STP = ST + 8, CP = FLAT_NSTAT * STP;
+    __shared__ float sh[3 * CP];
     __shared__ double shl[WAVES_PER_BLOCK];
     const int w = wave_in_block();
     if (lane == 0) shl[w] = lsum;
-    auto put = [&](int k, bool first, float v0, float v1, float v2, float v3, float v4, float v5, float v6) {
-        float* q = sh + k * 64 + lane;
+    auto put = [&](float* base, int k, bool first, float v0, float v1, float v2, float v3, float v4, float v5, float v6) {
+        float* q = base + k * 64 + lane;
         if (first) { q[0 * STP] = v0; q[1 * STP] = v1; q[2 * STP] = v2; q[3 * STP] = v3; q[4 * STP] = v4; q[5 * STP] = v5; q[6 * STP] = v6; }
         else { q[0 * STP] += v0; q[1 * STP] += v1; q[2 * STP] += v2; q[3 * STP] += v3; q[4 * STP] += v4; q[5 * STP] += v5; q[6 * STP] += v6; }
     };
-    for (int turn = 0; turn < WAVES_PER_BLOCK; ++turn) {
-        if (w == turn) {
+    auto put_all = [&](float* base, bool first) {
 #pragma unroll
-            for (int p = 0; p < KP; ++p) {
-                put(2 * p, turn == 0, s0[p].x, a0[p].x, a1[p].x, a2[p].x, b0[p].x, b1[p].x, b2[p].x);
-                put(2 * p + 1, turn == 0, s0[p].y, a0[p].y, a1[p].y, a2[p].y, b0[p].y, b1[p].y, b2[p].y);
-            }
-            if (ODD) put(K - 1, turn == 0, s0s, a0s, a1s, a2s, b0s, b1s, b2s);
+        for (int p = 0; p < KP; ++p) {
+            put(base, 2 * p, first, s0[p].x, a0[p].x, a1[p].x, a2[p].x, b0[p].x, b1[p].x, b2[p].x);
+            put(base, 2 * p + 1, first, s0[p].y, a0[p].y, a1[p].y, a2[p].y, b0[p].y, b1[p].y, b2[p].y);
         }
-        __syncthreads();
-    }
+        if (ODD) put(base, K - 1, first, s0s, a0s, a1s, a2s, b0s, b1s, b2s);
+    };
+    if (w != 1) put_all(sh + (w == 0 ? 0 : w - 1) * CP, true);
+    __syncthreads();
+    if (w == 1) put_all(sh, false);
+    __syncthreads();
+    auto total = [&](int i) { return (sh[i] + sh[CP + i]) + sh[2 * CP + i]; };
     if (comp_major) {
         // [block][Jpad][8]: a component's 7 statistics + one pad word are 32 contiguous bytes, 8 components -- what a
         // workgroup of flat_boundary_kernel owns -- 256 (the train loop without a communicator; kernel-uniform)
         float* outp = partials + (size_t)blockIdx.x * FLAT_CM_STRIDE * Jpad;
         for (int idx = threadIdx.x; idx < FLAT_CM_STRIDE * ST; idx += BLOCK) {
             const int j = idx / FLAT_CM_STRIDE, st = idx % FLAT_CM_STRIDE;
-            outp[idx] = st < FLAT_NSTAT ? sh[st * STP + j] : 0.f;
+            outp[idx] = st < FLAT_NSTAT ? total(st * STP + j) : 0.f;
         }
     } else {
         float* outp = partials + (size_t)blockIdx.x * FLAT_NSTAT * Jpad;
         for (int idx = threadIdx.x; idx < FLAT_NSTAT * ST; idx += BLOCK) {
             const int st = idx / ST, j = idx % ST;
-            outp[st * Jpad + j] = sh[st * STP + j];
+            outp[st * Jpad + j] = total(st * STP + j);
         }
     }
     if (threadIdx.x == 0) {
