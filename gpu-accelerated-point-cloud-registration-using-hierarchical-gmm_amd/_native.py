@@ -21,7 +21,7 @@ VARIANTS = {"W": 0, "G": 1}
 KERNEL_IDS = {"flat_estep": 0, "flat_fused": 1, "flat_mstep": 2, "tree_estep": 3,
               "tree_loglik": 4, "tree_reg": 5, "util_fill": 6, "full_pass": 7, "full_moments": 8,
               "kmeans_assign": 9, "kmeans_accum": 10, "allreduce": 11, "full_fused": 12, "tree_score": 13,
-              "flat_boundary": 14}
+              "flat_boundary": 14, "voxel": 15}
 # default inlier bound of the tree score: the 0.99 quantile of chi-square with three degrees of freedom (the squared
 # Mahalanobis distance of a point drawn from its own Gaussian)
 CHI2_3_99 = 11.344866730144373
@@ -168,6 +168,11 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_register_multi", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
                                                _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_score_multi", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp])
+        _sig(lib, "hgmm_voxel_downsample_f64", [ctx, _vp, C.c_int64, C.c_double, _i64p])
+        _sig(lib, "hgmm_voxel_downsample_f32", [ctx, _vp, C.c_int64, C.c_double, _i64p])
+        _sig(lib, "hgmm_voxel_downsample_batch_f64", [ctx, C.c_int, C.POINTER(_vp), _i64p, C.c_double, _i64p])
+        _sig(lib, "hgmm_voxel_downsample_batch_f32", [ctx, C.c_int, C.POINTER(_vp), _i64p, C.c_double, _i64p])
+        _sig(lib, "hgmm_voxel_downsample_get", [ctx, _vp, _vp])
         _lib = lib
         return lib
 
@@ -1475,6 +1480,44 @@ class Context:
         ms, n = C.c_double(), C.c_int64()
         self._check(self.lib.hgmm_profile_get(self.h, KERNEL_IDS[kernel], C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    # -- voxel-grid down-sample ---------------------------------------------------------------
+    def voxel_down_sample(self, points, voxel_size):
+        """Centroids and counts of the occupied voxels of ``points`` [N,3] on the device (hgmm_voxel_downsample_f64 / _f32):
+        bit for bit ``pointcloud_io.voxel_down_sample(points, voxel_size, return_counts=True)``.  A float32 array is uploaded
+        as it is and widened on the device.  The resident cloud, target and trees of the context are not touched.
+        -> (centroids float64 [M,3], counts int64 [M])."""
+        return self.voxel_down_sample_batch([points], voxel_size, _serial=True)[0]
+
+    def voxel_down_sample_batch(self, clouds, voxel_size, _serial=False):
+        """:meth:`voxel_down_sample` of every cloud of the list by the same launches (hgmm_voxel_downsample_batch_f64 / _f32:
+        float32 when all of them are); each member's result is bitwise the serial call's.  -> list of (centroids, counts)."""
+        arrs, ptrs, counts, all32 = self._cloud_list(clouds, "voxel_down_sample")
+        m = (C.c_int64 * len(arrs))()
+        if _serial:
+            entry = self.lib.hgmm_voxel_downsample_f32 if all32 else self.lib.hgmm_voxel_downsample_f64
+            self._check(entry(self.h, _ptr(arrs[0]), arrs[0].shape[0], float(voxel_size), m))
+        else:
+            entry = self.lib.hgmm_voxel_downsample_batch_f32 if all32 else self.lib.hgmm_voxel_downsample_batch_f64
+            self._check(entry(self.h, len(arrs), ptrs, counts, float(voxel_size), m))
+        self._vx_m = [int(v) for v in m]
+        cent, cnt = self.voxel_down_sample_get()
+        out, at = [], 0
+        for mb in self._vx_m:
+            out.append((cent[at:at + mb], cnt[at:at + mb]))
+            at += mb
+        return out
+
+    def voxel_down_sample_get(self):
+        """The last successful down-sample's result once more (hgmm_voxel_downsample_get): centroids [sum M,3] and counts
+        [sum M], cloud after cloud.  A refused call in between does not change it; without any, HgmmError."""
+        if getattr(self, "_vx_m", None) is None:
+            self._check(self.lib.hgmm_voxel_downsample_get(self.h, None, None))
+            raise HgmmError("voxel_down_sample_get: this Context object has not down-sampled anything")
+        M = sum(self._vx_m)
+        cent, cnt = np.empty((M, 3), np.float64), np.empty(M, np.int64)
+        self._check(self.lib.hgmm_voxel_downsample_get(self.h, _ptr(cent), _ptr(cnt)))
+        return cent, cnt
 
 
 _default_ctx = None

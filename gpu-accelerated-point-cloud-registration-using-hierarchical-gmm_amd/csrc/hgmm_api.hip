@@ -744,7 +744,9 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->km_mind2, &c->km_partial, &c->km_out, &c->gt_buf, &c->t_momq, &c->t_flags, &c->exp_tab2, &c->t_tickets,
                       &c->fr_pi, &c->fr_mu, &c->fr_cov, &c->fr_prep, &c->fr_mom, &c->fr_clouds, &c->fr_q, &c->fr_trace, &c->fr_tg,
                       &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w, &c->fr_tg_w,
-                      &c->src_w, &c->fr_src_w, &c->t_w2, &c->t_w3, &c->flat_sw, &c->f_lpn_rows};
+                      &c->src_w, &c->fr_src_w, &c->t_w2, &c->t_w3, &c->flat_sw, &c->f_lpn_rows,
+                      &c->vx_in, &c->vx_tab, &c->vx_keys, &c->vx_keys2, &c->vx_rows, &c->vx_rows2, &c->vx_heads, &c->vx_tmp,
+                      &c->vx_cent, &c->vx_cnt};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);

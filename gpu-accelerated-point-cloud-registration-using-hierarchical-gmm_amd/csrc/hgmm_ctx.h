@@ -286,6 +286,17 @@ struct hgmm_ctx {
     // ---- L2 GMMReg Gauss transform ---------------------------------------------------
     hgmm::DevBuf gt_buf;                      // double: centres, points, weights, per-split partial sums
 
+    // ---- voxel-grid down-sample (voxel_kernels.hip): buffers of its own, nothing above is touched --------
+    hgmm::DevBuf vx_in;                       // the clouds' rows as uploaded, back to back: float or double [total][3]
+    hgmm::DevBuf vx_tab;                      // int64 first row [B + 1], VoxelBox [B], VoxelGrid [B], uint32 M + first voxel [B]
+    hgmm::DevBuf vx_keys, vx_keys2;           // uint64 [total] voxel keys, unsorted / sorted
+    hgmm::DevBuf vx_rows, vx_rows2;           // uint32 [total] row indices, unsorted / sorted
+    hgmm::DevBuf vx_heads;                    // uint32 [total] first sorted position of every voxel (M of them in use)
+    hgmm::DevBuf vx_tmp;                      // temporary storage of the sort and of the compaction
+    hgmm::DevBuf vx_cent, vx_cnt;             // the last result: double [M][3] centroids, int64 [M] counts, cloud after cloud
+    bool vx_have = false;                     // a down-sample has succeeded on this context
+    int64_t vx_m = 0;                         // its M (all clouds)
+
     // ---- multi-GPU --------------------------------------------------------------
     ncclComm_t comm = nullptr;                // RCCL over xGMI (one GPU per rank)
     hgmm::HostComm* hcomm = nullptr;          // host shared-memory communicator (tests: ranks may share a GPU)

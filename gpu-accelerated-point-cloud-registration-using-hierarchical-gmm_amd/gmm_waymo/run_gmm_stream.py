@@ -17,10 +17,11 @@ from ..pointcloud_io import read_point_cloud, voxel_down_sample
 
 
 def run_stream(frames, n_components=50, max_iter=50, cov_type='spherical', fit_every=10, tol=1e-4,
-               voxel_size=None, seed=0, verbose=False):
+               voxel_size=None, seed=0, verbose=False, ctx=None):
     """frames: iterable of [N,3] arrays.  -> dict(labels=[...], fps=float, fit_s=[...], models=[...]):
     ``models[k]`` = (means, weights, covariances, inv_covs) of the k-th refit, i.e. the parameters frame i was
-    labelled with are ``models[i // fit_every]``."""
+    labelled with are ``models[i // fit_every]``.  ``ctx`` (a Context; default None: on the host): where the frames are
+    voxel-down-sampled when ``voxel_size`` is given (``pointcloud_io.voxel_down_sample(..., ctx=ctx)``, the same values)."""
     gmm = GMM_GPU(n_gmm_components=n_components, max_iter=max_iter, tol=tol, cov_type=cov_type)
     gmm.init()
     gmm._clf._verbose = verbose
@@ -34,7 +35,7 @@ def run_stream(frames, n_components=50, max_iter=50, cov_type='spherical', fit_e
     for i, pts in enumerate(frames):
         pts = np.asarray(pts)
         if voxel_size:
-            pts = voxel_down_sample(pts, voxel_size)
+            pts = voxel_down_sample(pts, voxel_size, ctx=ctx)
         dev = asarray(pts.astype(np.float32))
         resident.append(dev)
         if i % fit_every == 0:

@@ -724,16 +724,17 @@ def euler_matrix_xyz(ai, aj, ak):
 
 def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
                                        orientation=np.deg2rad([0.0, 0.0, 30.0]), translation=np.zeros(3),
-                                       voxel_size=0.005, rng=None):
+                                       voxel_size=0.005, rng=None, ctx=None):
     """Noisy, cluttered, rigidly moved copy of a cloud for registration experiments
     (hgmm_gpu.py:772-795 minus Open3D/normals): voxel down-sample, shuffle, add Gaussian noise and
     ``n_random`` uniform outliers in a 1.5x bounding box, then rotate/translate.
-    ``source``: [N,3] array or a .ply/.pcd path.  -> (source_points, target_points)."""
+    ``source``: [N,3] array or a .ply/.pcd path.  ``ctx`` (default None: on the host): the Context whose device does the
+    down-sample (``pointcloud_io.voxel_down_sample(..., ctx=ctx)``, the same values).  -> (source_points, target_points)."""
     from ..pointcloud_io import read_point_cloud, voxel_down_sample
     rng = rng or np.random
     src = read_point_cloud(source) if isinstance(source, str) else np.asarray(source, dtype=np.float64)
     if voxel_size:
-        src = voxel_down_sample(src, voxel_size)
+        src = voxel_down_sample(src, voxel_size, ctx=ctx)
     tp = src.copy()
     rng.shuffle(tp)
     rg = 1.5 * (tp.max(axis=0) - tp.min(axis=0))
@@ -743,6 +744,18 @@ def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
     return src, tgt @ rot.T + np.asarray(translation)
 
 
+def _voxel_pairs(ctx, pairs, voxel_size, explicit_weights):
+    """``voxel_size=`` of the registration functions: every cloud of ``pairs`` down-sampled on ``ctx``'s device by ONE batch
+    call (``Context.voxel_down_sample_batch``), -> pairs of ``WeightedPoints(centroids, counts)``.  Weights of the caller's
+    own next to a voxel size are refused: they belong to the points that are about to be replaced."""
+    own = any(getattr(c, "weights", None) is not None for p in pairs for c in p)
+    if own or any(w is not None for w in explicit_weights):
+        raise ValueError("voxel_size replaces the clouds by their voxel centroids, weighted by the counts: it cannot be "
+                         "combined with source_weights / target_weights (or WeightedPoints inputs)")
+    ds = ctx.voxel_down_sample_batch([_points(c) for p in pairs for c in p], voxel_size)
+    return [(WeightedPoints(*ds[2 * k]), WeightedPoints(*ds[2 * k + 1])) for k in range(len(pairs))]
+
+
 def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, starts=None, **kargs):
     """hgmm_gpu.py:802-807.  ``return_score=True``: ScoredResult(transformation, q, score) -- see :meth:`GMMTree.registration`.
     ``starts`` (a list of start poses, e.g. :func:`rotation_starts`): :meth:`GMMTree.registration_multistart`'s result.
@@ -750,7 +763,15 @@ def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], r
     ``target_weights=`` [N] >= 0 (a keyword of this function, not of :class:`GMMTree`; default: the target's own if it is a
     :class:`WeightedPoints`): per-point weights of the target, with or without ``starts``.
     ``source_weights=`` [N] >= 0 (default: the source's own if it is a :class:`WeightedPoints`): per-point weights of the
-    source for the tree build, as in :func:`buildGMMTree`."""
+    source for the tree build, as in :func:`buildGMMTree`.
+    ``voxel_size=`` (a keyword of this function like the weights; default None: the clouds as they are): both clouds are
+    voxel-down-sampled on the device first (one ``Context.voxel_down_sample_batch`` call) and the counts travel as source and
+    target weights -- bit for bit this call on ``WeightedPoints(*voxel_down_sample(cloud, voxel_size, True))`` inputs; with
+    explicit weights: ValueError."""
+    voxel_size = kargs.pop("voxel_size", None)
+    if voxel_size is not None:
+        (source, target), = _voxel_pairs(kargs.get("ctx") or default_context(), [(source, target)], voxel_size,
+                                         [kargs.get("source_weights"), kargs.get("target_weights")])
     weights = _target_weights(target, kargs.pop("target_weights", None))
     kargs["source_weights"] = _target_weights(source, kargs.pop("source_weights", None))
     gt = GMMTree(_points(source), **kargs)
@@ -766,7 +787,8 @@ BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this 
 
 def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | None = None, tree_level=5, lambda_c=0.01,
                                ls=20, ld=1.0e-4, sig2=0.004, init_idx=None, return_info=False, pdf_dtype=None,
-                               solve_on_device=False, score=False, maha2_gate=None, target_weights=None, source_weights=None):
+                               solve_on_device=False, score=False, maha2_gate=None, target_weights=None, source_weights=None,
+                               voxel_size=None):
     """``[registration_gmmtree(s, t, maxiter, tol, tree_level=..., ...) for s, t in pairs]`` (hgmm_gpu.py:802-807 per pair)
     with ALL pairs in the same launches: the B source clouds are one resident forest (``hgmm_tree_build_batch``: levels in
     lock-step, one stop rule per cloud), the B targets are registered against their trees together
@@ -796,6 +818,10 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     :class:`WeightedPoints` brings its own); an unweighted pair's tree is bitwise its unweighted tree, and the pairs of
     400 000 points or more that run serially are built under their weights too.
 
+    ``voxel_size`` (default None: the clouds as they are): all 2B clouds are voxel-down-sampled on the device first, by ONE
+    ``Context.voxel_down_sample_batch`` call, and the counts travel as source and target weights -- bit for bit this call
+    on ``WeightedPoints(*voxel_down_sample(cloud, voxel_size, True))`` inputs; with explicit weights: ValueError.
+
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
     gate = _gate_arg(maha2_gate)
@@ -803,6 +829,8 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     pairs = list(pairs)
     if not pairs:
         return ([], {}) if return_info else []
+    if voxel_size is not None:
+        pairs = _voxel_pairs(ctx, pairs, voxel_size, [w for ws in (target_weights, source_weights) if ws is not None for w in ws])
     if target_weights is not None and len(target_weights) != len(pairs):
         raise ValueError("target_weights must have one entry (an array or None) per pair: %d entries for %d pairs"
                          % (len(target_weights), len(pairs)))

@@ -158,13 +158,18 @@ def read_point_cloud(path) -> np.ndarray:
     raise ValueError("unsupported point-cloud format: %s" % path)
 
 
-def voxel_down_sample(points, voxel_size: float, return_counts: bool = False):
+def voxel_down_sample(points, voxel_size: float, return_counts: bool = False, ctx=None):
     """One point per occupied voxel = the mean of the points inside it (what Open3D's
     ``voxel_down_sample`` computes: grid origin at ``min_bound - voxel_size / 2``).  Output order
     is by voxel index (Open3D's order is hash-map dependent; the set of points is what matters).
     ``return_counts=True``: -> (centroids, counts) with the number of points each centroid stands for
     (int64, summing to ``len(points)``) -- the weights that let a registration against the centroids
-    see the scan's density (``GMMTree.registration(centroids, weights=counts)``)."""
+    see the scan's density (``GMMTree.registration(centroids, weights=counts)``).
+    ``ctx`` (a :class:`Context`; default None: this NumPy code): the same values, bit for bit, computed on that context's
+    device (``Context.voxel_down_sample``); the code below is its definition."""
+    if ctx is not None:
+        cent, cnt = ctx.voxel_down_sample(points, voxel_size)
+        return (cent, cnt) if return_counts else cent
     P = np.asarray(points, dtype=np.float64)
     if voxel_size <= 0:
         raise ValueError("voxel_size must be positive")

@@ -64,7 +64,8 @@ enum hgmm_kernel_id {
     HGMM_K_FULL_FUSED = 12,   /* full-cov flat EM, one pass: denominators + arg-max + q + fp64-MFMA statistics */
     HGMM_K_TREE_SCORE = 13,   /* HGMM score of a moved target (tree descent, per-point outputs + summary) */
     HGMM_K_FLAT_BOUNDARY = 14, /* flat EM between two iterations: reduction + M-step + next table + stop rule */
-    HGMM_K_COUNT = 15
+    HGMM_K_VOXEL = 15,        /* voxel-grid down-sample: the whole launch set (box, keys, sort, heads, centroids) */
+    HGMM_K_COUNT = 16
 };
 
 /* ---- lifecycle ------------------------------------------------------------------ */
@@ -589,6 +590,44 @@ int hgmm_kmeans_lloyd(hgmm_ctx* ctx, int k, double* centers_inout, int max_iter,
  * and the gradient of the L2 cost).  Host arrays in and out (mixture sizes).                    */
 int hgmm_gauss_transform(hgmm_ctx* ctx, const double* centres, int n_centres, const double* points,
                          int n_points, const double* weights, int n_weights, double h, double* out);
+
+/* ---- voxel-grid down-sample: centroids + counts, one cloud or B clouds per launch set -----------------------------------
+ * Every pipeline of the reference voxel-down-samples its scans first -- o3.voxel_down_sample at hgmm/hgmm_gpu.py:786 and
+ * 829-830, run_gmm_static.py:28, waymoutils.py:99, gmmreg.py:203-204 -- and the counts are what the weight entries above
+ * (hgmm_tree_set_target_weights, hgmm_tree_set_source_weights, hgmm_flat_set_weights) are fed with.  These entries replace
+ * those calls: one point per occupied voxel, the mean of the points inside it, and the number of points it stands for.
+ * SEMANTICS: pointcloud_io.voxel_down_sample(P, voxel, return_counts=True) on P as float64 is the definition, and the
+ * result has its bits:
+ *   origin    min_i P_i - voxel / 2 per axis
+ *   index     floor((P - origin) / voxel) per axis: one IEEE subtraction, one IEEE division, one floor, in float64 (no
+ *             reciprocal, no fused multiply-add)
+ *   order     voxels in ascending lexicographic (ix, iy, iz) order; with the extents (nx, ny, nz) of the bounding box the
+ *             sort key is (ix ny + iy) nz + iz, in a batch with the cloud number above the largest cloud's key bits
+ *   centroid  per axis the float64 sum of the voxel's points in ASCENDING POINT INDEX, started from +0.0 (a voxel that
+ *             holds only -0.0 comes out as +0.0), divided once by the count converted to float64
+ * float32 rows (_f32) are widened to float64 on the device, exactly: the result is the _f64 entry's on the widened array.
+ * Deterministic: min / max are exact in any order, the sort of (key, row) is stable, one thread adds a voxel's points one
+ * after the other -- no floating-point atomics; two calls return the same bits.  A VOXEL WITH VERY MANY POINTS MAKES THAT
+ * WALK LONG (a cloud that falls into one voxel is added up by one thread): accepted, the order of summation is not traded
+ * for speed.
+ * The batch entries down-sample B clouds by the SAME launches (one launch set whatever B is); every member's result is
+ * bit for bit the serial entry's on it alone.  m_out [B] (serial: [1]) receives the number of voxels per cloud.
+ * The calls come in pairs because M is not known beforehand: hgmm_voxel_downsample_get copies the LAST successful call's
+ * result -- centroids [sum m][3] float64 and counts [sum m] int64, cloud after cloud; either may be NULL -- and returns
+ * HGMM_ERR_STATE when no down-sample has succeeded on the context.
+ * REFUSALS (HGMM_ERR_ARG, hgmm_last_error says why, the previous result stays in place): a voxel size that is NaN, infinite
+ * or <= 0; n < 1 (a batch: any count < 1, B < 1); a non-finite coordinate (found by the bounding-box pass on the device; the
+ * message names the first such row); a voxel grid of nx ny nz >= 2^63 cells; cloud bits + key bits > 64 in a batch; n, or
+ * the batch's total, >= 2^31.
+ * A call works in buffers of its own on the context's stream: the resident cloud, its weights, a forest, a target and a tree
+ * are what they were.  The profiler times the whole launch set as one entry, HGMM_K_VOXEL.                                  */
+int hgmm_voxel_downsample_f64(hgmm_ctx* ctx, const double* xyz /* host [n,3] */, int64_t n, double voxel, int64_t* m_out);
+int hgmm_voxel_downsample_f32(hgmm_ctx* ctx, const float* xyz /* host [n,3] */, int64_t n, double voxel, int64_t* m_out);
+int hgmm_voxel_downsample_batch_f64(hgmm_ctx* ctx, int B, const double* const* xyz, const int64_t* counts, double voxel,
+                                    int64_t* m_out /* [B] */);
+int hgmm_voxel_downsample_batch_f32(hgmm_ctx* ctx, int B, const float* const* xyz, const int64_t* counts, double voxel,
+                                    int64_t* m_out /* [B] */);
+int hgmm_voxel_downsample_get(hgmm_ctx* ctx, double* centroids_out /* [sum m,3] */, int64_t* counts_out /* [sum m] */);
 
 /* ---- multi-GPU: one context per rank, RCCL over xGMI --------------------------------
  * New functionality (the reference is single-GPU).  With a communicator attached,
