@@ -25,6 +25,7 @@
 #include "wave_ops.h"
 
 #include <type_traits>
+#include <utility>
 
 #include <algorithm>
 #include <cmath>
@@ -1933,37 +1934,14 @@ static int flat_setup(hgmm_ctx* c, int cov_type, int variant, int J) {
     return HGMM_OK;
 }
 
-static size_t cov_elems(int cov_type, int J) { return cov_type == HGMM_COV_DIAG ? (size_t)3 * J : (size_t)J; }
+// What opens every entry point: the arguments checked, the context's buffers set up for (cov_type, variant, J).
+// (setup_variant: hgmm_flat_log_prob is checked as the caller's flavour and set up as G)
+static int flat_prepare(hgmm_ctx* c, int cov_type, int variant, int J, int setup_variant = -1) {
+    HGMM_TRY(flat_check(c, cov_type, variant, J));
+    return flat_setup(c, cov_type, setup_variant < 0 ? variant : setup_variant, J);
+}
 
-// ---- pinned staging ring ----------------------------------------------------------------------
-// Small host <-> device transfers of the API-granular calls (parameters in, M-step results out) go through a
-// pinned ring owned by the context: the host side is a memcpy, the device side a genuinely asynchronous DMA
-// that queues behind the kernels already on the stream -- so hgmm_flat_estep_enqueue returns while its kernel
-// runs and the next call's host work overlaps it.  A region is reused only after a stream synchronisation.
-constexpr size_t STAGE_BYTES = 4u << 20;
-int stage_reserve(hgmm_ctx* c, size_t bytes, void** out) {            // (declared in hgmm_ctx.h: the tree build's downloads use it too)
-    if (!c->h_stage) {
-        HGMM_HIP(c, hipHostMalloc(&c->h_stage, STAGE_BYTES, hipHostMallocDefault));
-        c->h_stage_cap = STAGE_BYTES;
-        c->h_stage_off = 0;
-    }
-    bytes = (bytes + 255) & ~(size_t)255;
-    if (bytes > c->h_stage_cap) return fail(c, HGMM_ERR_ARG, "staging request of %zu bytes", bytes);
-    if (c->h_stage_off + bytes > c->h_stage_cap) {
-        HGMM_HIP(c, ctx_stream_sync(c));         // every earlier region has been consumed
-        c->h_stage_off = 0;
-    }
-    *out = static_cast<char*>(c->h_stage) + c->h_stage_off;
-    c->h_stage_off += bytes;
-    return HGMM_OK;
-}
-int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {       // (declared in hgmm_ctx.h)
-    void* st = nullptr;
-    HGMM_TRY(stage_reserve(c, bytes, &st));
-    std::memcpy(st, host, bytes);
-    HGMM_HIP(c, hipMemcpyAsync(dev, st, bytes, hipMemcpyHostToDevice, c->stream));
-    return HGMM_OK;
-}
+static size_t cov_elems(int cov_type, int J) { return cov_type == HGMM_COV_DIAG ? (size_t)3 * J : (size_t)J; }
 
 static int flat_upload(hgmm_ctx* c, const float* mu, const float* inv_or_cov, bool is_cov, const float* w) {
     const int J = c->flat.J, Jpad = c->flat.Jpad;
@@ -1984,11 +1962,23 @@ static int flat_upload(hgmm_ctx* c, const float* mu, const float* inv_or_cov, bo
     return HGMM_OK;
 }
 
-static void launch_pack(hgmm_ctx* c) {
+// the packed table from device arrays: the context's own block or a caller's
+static void launch_pack(hgmm_ctx* c, const float* mu, const float* inv_std, const float* w) {
     const FlatState& f = c->flat;
-    flat_pack_kernel<<<(f.Jpad + 255) / 256, 256, 0, c->stream>>>(
-        f.J, f.Jpad, f.cov_type, f.variant, c->f_mu.as<float>(), c->f_inv.as<float>(), c->f_w.as<float>(),
-        c->f_pack.as<float>());
+    flat_pack_kernel<<<(f.Jpad + 255) / 256, 256, 0, c->stream>>>(f.J, f.Jpad, f.cov_type, f.variant, mu, inv_std, w,
+                                                                c->f_pack.as<float>());
+}
+
+// the parameters of an E-step-like call on their way into the packed table: host arrays through the ring and the
+// context's block; device arrays as they are -- no staging, no copy
+static int flat_load(hgmm_ctx* c, const float* mu, const float* inv_std, const float* w, bool on_device) {
+    if (on_device) {
+        launch_pack(c, mu, inv_std, w);
+        return HGMM_OK;
+    }
+    HGMM_TRY(flat_upload(c, mu, inv_std, false, w));
+    launch_pack(c, c->f_mu.as<float>(), c->f_inv.as<float>(), c->f_w.as<float>());
+    return HGMM_OK;
 }
 
 // layout choice: vector slots for full 256-component groups, scalar slots for a short remainder
@@ -2006,136 +1996,91 @@ static void pick_layout(int J, int* nv4, int* nv1) {
     }
 }
 
-
+// The 18 layouts pick_layout reaches, ONE table.  R4 marks the twelve the four-rows-in-flight kernels (materialising
+// E-step, estimate_log_prob, predict) are instantiated for -- every layout with vector slots, and one or two scalar
+// slots alone; R1 the six that only the single-row kernels know.
+#define FLAT_LAYOUTS(R4, R1, M)                                                                 \
+    R4(M, 0, 1) R4(M, 0, 2) R1(M, 0, 3) R1(M, 0, 4) R1(M, 0, 6) R1(M, 0, 8) R1(M, 0, 12) R1(M, 0, 16)  \
+    R4(M, 1, 0) R4(M, 1, 1) R4(M, 1, 2) R4(M, 2, 0) R4(M, 2, 1) R4(M, 2, 2)                     \
+    R4(M, 3, 0) R4(M, 3, 1) R4(M, 3, 2) R4(M, 4, 0)
+#define LAYOUT_CASE_(M, A, B) case (A) * 100 + (B): M(A, B); break;
+#define LAYOUT_SKIP_(M, A, B)
 // LAYOUT_DISPATCH(nv4, nv1, M): expands M(NV4, NV1) for the supported (NV4, NV1) pairs
 #define LAYOUT_DISPATCH(nv4, nv1, M)                                                           \
     do {                                                                                       \
-        const int key_ = (nv4) * 100 + (nv1);                                                  \
-        switch (key_) {                                                                        \
-            case 1: M(0, 1); break;   case 2: M(0, 2); break;   case 3: M(0, 3); break;        \
-            case 4: M(0, 4); break;   case 6: M(0, 6); break;   case 8: M(0, 8); break;        \
-            case 12: M(0, 12); break; case 16: M(0, 16); break;                                \
-            case 100: M(1, 0); break; case 101: M(1, 1); break; case 102: M(1, 2); break;      \
-            case 200: M(2, 0); break; case 201: M(2, 1); break; case 202: M(2, 2); break;      \
-            case 300: M(3, 0); break; case 301: M(3, 1); break; case 302: M(3, 2); break;      \
-            case 400: M(4, 0); break;                                                          \
+        switch ((nv4) * 100 + (nv1)) {                                                         \
+            FLAT_LAYOUTS(LAYOUT_CASE_, LAYOUT_CASE_, M)                                        \
             default: return fail(c, HGMM_ERR_ARG, "unsupported layout %d/%d", (nv4), (nv1));   \
         }                                                                                      \
     } while (0)
+// ROWS4_DISPATCH(nv4, nv1, M): M(NV4, NV1) for the four-rows-in-flight layouts, nothing for the others
+#define ROWS4_DISPATCH(nv4, nv1, M)                                                            \
+    do {                                                                                       \
+        switch ((nv4) * 100 + (nv1)) {                                                         \
+            FLAT_LAYOUTS(LAYOUT_CASE_, LAYOUT_SKIP_, M)                                        \
+            default: break;                                                                    \
+        }                                                                                      \
+    } while (0)
+static bool rows4_layout(int nv4, int nv1) {
+#define ROWS4_YES(A, B) return true
+    ROWS4_DISPATCH(nv4, nv1, ROWS4_YES);
+#undef ROWS4_YES
+    return false;
+}
 
-// Offered store rate of the paced N x J writers (materialising E-step, estimate_log_prob), GB/s.  The knee of the write
-// path sat at 6.8 - 7.0 TB/s on every box of round 4, but it is a property of the memory system's state (refresh rate
-// with temperature, the stacks of the particular chip), and past it the kernel does not degrade gracefully -- it drops
-// to ~5.3 TB/s; the knee is soft besides: at 6700 one launch in three already ran 3 - 18 % long in bursts, at 6600 the
-// 150 launches of a bench run stayed within 488 - 506 us of their 487 (profiles/r04).  So the rate starts at 6600 and is
-// CONTROLLED: a paced launch that runs more than 6 % longer than its
-// target explains counts as a strike, three strikes in a row lower the target by 2 % (never below PACE_FLOOR_GBS).  The
-// evidence comes from event pairs around the last few launches that are queried -- never waited for -- at the next
-// launch, so the stream is not disturbed.  Launches that are not store-bound by construction (the row-maximum loop,
-// small tables) neither adapt nor are they judged.  HGMM_ESTEP_TARGET_GBS=<n> fixes the rate (0: un-paced), HGMM_ESTEP_ADAPT=0
-// keeps the initial one.
-constexpr int ESTEP_TARGET_GBS = 6600;
-constexpr double PACE_FLOOR_GBS = 5800.0;
-constexpr double PACE_STRIKE_RATIO = 1.06;
-constexpr double PACE_STEP = 0.98;
-constexpr double PACE_MIN_BYTES = 256.0 * 1024 * 1024;
-// ... and upwards, carefully: the knee sat at 7.0 TB/s on one box and at 7.6 on another (profiles/r04/paced_fill_lease*.log).
-// After PACE_PROBE_AFTER clean launches in a row the rate is raised by 2 % on probation: three clean launches keep it, the
-// first long one takes it back, remembers the rate as a ceiling and doubles the wait before the next probe.
-// ... and a ceiling is a statement about the memory system's state WHEN it was learnt (another stream writing at the same
-// time, a hot chip), not for life: after PACE_FORGET_AFTER clean launches below it (HGMM_PACE_FORGET=<n>) it is forgotten and
-// the probes start over with their first waiting time.  hgmm_pace_reset() forgets everything at once.
-constexpr int PACE_FORGET_AFTER = 10000;
-constexpr int PACE_PROBE_AFTER = 24, PACE_PROBE_AFTER_MAX = 4096;
-constexpr double PACE_PROBE_STEP = 1.02;
-constexpr double PACE_CEILING_GBS = 7600.0;
+// what the context enqueued last (the E-step's un-paced grid policy looks at it, estep_rows_grid)
+static void note_launch(hgmm_ctx* c, FlatKernel k) {
+    c->flat.last_kernel = k;
+    c->flat.idle_since_launch = false;
+}
 
+// ---- the kernel families of the flat launches (kernel_for, hgmm_ctx.h; the last flag: WEIGHTED, hgmm_flat_set_weights) ----
+// (non-temporal stores come with the normalising pass only: the raw table's single-row kernel has ONE form)
+template <int NV4, int NV1, bool NORMALISE>
+struct EstepFamily { template <bool NT> static auto kernel() { return flat_estep_kernel<NV4, NV1, NORMALISE, NORMALISE && NT>; } };
+template <int NV4, int NV1>
+struct MstepFamily { template <bool ISLOG, bool NTLOAD, bool W> static auto kernel() { return flat_mstep_kernel<NV4, NV1, ISLOG, NTLOAD, W>; } };
+template <int NSLOT>
+struct FusedFamily { template <bool W> static auto kernel() { return flat_fused_pk_kernel<NSLOT, W>; } };
+struct ChunkFusedFamily { template <bool W> static auto kernel() { return flat_chunk_fused_kernel<W>; } };
+
+// ---- store pacer: the measurement ring around the rate controller of flat_pace.h ---------------------------------
 // the rate the next paced launch of J-float rows offers
 static double pace_target(hgmm_ctx* c, int J) {
     const int fixed = c->cfg[CFG_ESTEP_TARGET_GBS];
     if (fixed >= 0) return (double)fixed;
-    PaceCtl& p = c->pace;
-    if (p.target <= 0.0 || p.J != J) {
-        p.target = (double)c->cfg[CFG_PACE_START];
-        p.strikes = p.clean = p.probe_seen = 0;
-        p.probe_after = PACE_PROBE_AFTER;
-        p.probe_base = 0.0;
-        p.ceiling = 1e30;
-        p.since_ceiling = 0;
-        p.J = J;
-    }
-    return p.target;
+    return pace_rate_for(c->pace, J, (double)c->cfg[CFG_PACE_START]);
 }
-// look at the launches that have finished since the last call (no waiting)
+// a finished slot's duration in ms: first workgroup start to last workgroup end by the stamps, or its event pair
+static bool pace_slot_ms(hgmm_ctx* c, unsigned s, float* ms) {
+    const PaceRing& p = c->pace_ring;
+    if (p.stamps && p.grid_at[s] > 0 && c->wall_khz > 0) {
+        const unsigned long long* st = p.stamps + (size_t)s * 2 * PaceRing::STAMP_WG;
+        unsigned long long t0 = ~0ull, t1 = 0ull;
+        for (int b = 0; b < p.grid_at[s]; ++b) {
+            t0 = st[b] < t0 ? st[b] : t0;
+            t1 = st[p.grid_at[s] + b] > t1 ? st[p.grid_at[s] + b] : t1;
+        }
+        if (t1 <= t0) return false;
+        *ms = (float)((double)(t1 - t0) / (double)c->wall_khz);
+        return true;
+    }
+    return hipEventElapsedTime(ms, p.ev[s][0], p.ev[s][1]) == hipSuccess;
+}
+// look at the launches that have finished since the last call (no waiting): for each, measure and judge
 static void pace_poll(hgmm_ctx* c) {
-    PaceCtl& p = c->pace;
-    while (p.tail != p.head) {
-        const unsigned s = p.tail % PaceCtl::RING;
+    PaceRing& p = c->pace_ring;
+    for (; p.tail != p.head; p.tail++) {
+        const unsigned s = p.tail % PaceRing::RING;
         if (hipEventQuery(p.ev[s][1]) != hipSuccess) { (void)hipGetLastError(); break; }
         float ms = 0.f;
-        bool have_ms = false;
-        if (p.stamps && p.grid_at[s] > 0 && c->wall_khz > 0) {
-            // the launch is complete (its end event has passed): first workgroup start to last workgroup end
-            const unsigned long long* st = p.stamps + (size_t)s * 2 * PaceCtl::STAMP_WG;
-            unsigned long long t0 = ~0ull, t1 = 0ull;
-            for (int b = 0; b < p.grid_at[s]; ++b) {
-                t0 = st[b] < t0 ? st[b] : t0;
-                t1 = st[p.grid_at[s] + b] > t1 ? st[p.grid_at[s] + b] : t1;
-            }
-            if (t1 > t0) { ms = (float)((double)(t1 - t0) / (double)c->wall_khz); have_ms = true; }
-        } else {
-            have_ms = hipEventElapsedTime(&ms, p.ev[s][0], p.ev[s][1]) == hipSuccess;
-        }
-        if (have_ms && p.tgt_at[s] == p.target) {
-            const double ideal_ms = p.bytes_at[s] / (p.tgt_at[s] * 1e9) * 1e3;
-            const bool slow = (double)ms > PACE_STRIKE_RATIO * ideal_ms;
-            if (p.probe_base > 0.0) {
-                // a probe is running: ONE long launch ends it (the memory system has said no), three clean ones accept it
-                if (slow) {
-                    p.ceiling = p.target;
-                    p.since_ceiling = 0;
-                    p.target = p.probe_base;
-                    p.probe_base = 0.0;
-                    p.probe_after = std::min(PACE_PROBE_AFTER_MAX, 2 * p.probe_after);
-                    p.clean = 0;
-                    p.strikes = 0;
-                } else if (++p.probe_seen >= 3) {
-                    p.probe_base = 0.0;
-                    p.steps_up++;
-                    p.clean = 0;
-                }
-            } else if (slow) {
-                p.clean = 0;
-                if (++p.strikes >= 3) {
-                    p.ceiling = std::min(p.ceiling, p.target);
-                    p.since_ceiling = 0;
-                    p.target = std::max(PACE_FLOOR_GBS, p.target * PACE_STEP);
-                    p.strikes = 0;
-                    p.steps_down++;
-                }
-            } else {
-                p.strikes = 0;
-                if (p.ceiling < 1e29 && ++p.since_ceiling >= c->cfg[CFG_PACE_FORGET]) {
-                    p.ceiling = 1e30;                       // what congested then need not congest now: probe afresh
-                    p.since_ceiling = 0;
-                    p.probe_after = PACE_PROBE_AFTER;
-                    p.ceilings_forgotten++;
-                }
-                const double up = p.target * PACE_PROBE_STEP;
-                if (++p.clean >= p.probe_after && up < p.ceiling * 0.995 && up <= PACE_CEILING_GBS) {
-                    p.probe_base = p.target;
-                    p.target = up;
-                    p.probe_seen = 0;
-                }
-            }
-        }
-        p.tail++;
+        if (pace_slot_ms(c, s, &ms)) pace_judge(c->pace, p.tgt_at[s], p.bytes_at[s], (double)ms, c->cfg[CFG_PACE_FORGET]);
     }
 }
 // bracket a paced launch: begin() before the kernel, end() behind it; false: this launch is not observed
 // (*stamp_out: where this launch's workgroups leave their wall-clock stamps, null when the launch is judged by its events)
 static bool pace_observe_begin(hgmm_ctx* c, double target, double bytes, int grid, unsigned long long** stamp_out) {
-    PaceCtl& p = c->pace;
+    PaceRing& p = c->pace_ring;
     *stamp_out = nullptr;
     if (c->cfg[CFG_ESTEP_TARGET_GBS] >= 0) return false;            // a fixed rate: nothing to control
     if (bytes < PACE_MIN_BYTES || target <= 0.0) return false;
@@ -2146,7 +2091,7 @@ static bool pace_observe_begin(hgmm_ctx* c, double target, double bytes, int gri
         {
             void* h = nullptr;
             void* d = nullptr;
-            const size_t bytes_st = sizeof(unsigned long long) * PaceCtl::RING * 2 * PaceCtl::STAMP_WG;
+            const size_t bytes_st = sizeof(unsigned long long) * PaceRing::RING * 2 * PaceRing::STAMP_WG;
             if (hipHostMalloc(&h, bytes_st, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
                 p.stamps = static_cast<unsigned long long*>(h);
                 p.stamps_dev = static_cast<unsigned long long*>(d);
@@ -2157,21 +2102,21 @@ static bool pace_observe_begin(hgmm_ctx* c, double target, double bytes, int gri
         }
     }
     pace_poll(c);
-    if (p.head - p.tail >= (unsigned)PaceCtl::RING) return false;          // every pair is still in flight
-    const unsigned s = p.head % PaceCtl::RING;
+    if (p.head - p.tail >= (unsigned)PaceRing::RING) return false;          // every pair is still in flight
+    const unsigned s = p.head % PaceRing::RING;
     p.tgt_at[s] = target;
     p.bytes_at[s] = bytes;
     p.grid_at[s] = 0;
-    if (p.stamps && grid <= PaceCtl::STAMP_WG) {
+    if (p.stamps && grid <= PaceRing::STAMP_WG) {
         // the kernel writes start[b] at st[b] and end[b] at st[grid + b]: the slot is laid out for THIS grid
         p.grid_at[s] = grid;
-        *stamp_out = p.stamps_dev + (size_t)s * 2 * PaceCtl::STAMP_WG;
+        *stamp_out = p.stamps_dev + (size_t)s * 2 * PaceRing::STAMP_WG;
     }
     return hipEventRecord(p.ev[s][0], c->stream) == hipSuccess;
 }
 static void pace_observe_end(hgmm_ctx* c) {
-    PaceCtl& p = c->pace;
-    if (hipEventRecord(p.ev[p.head % PaceCtl::RING][1], c->stream) == hipSuccess) p.head++;
+    PaceRing& p = c->pace_ring;
+    if (hipEventRecord(p.ev[p.head % PaceRing::RING][1], c->stream) == hipSuccess) p.head++;
 }
 
 // StorePacer period (1/16 ticks of the 100 MHz wall clock) per group of 4 rows: all `grid` x 4 waves together offer
@@ -2199,28 +2144,15 @@ static bool launch_estep_rows(hgmm_ctx* c, int nv4, int nv1, int grid_r, bool cs
 #define ESTEP_R(A, B)                                                                              \
     flat_estep_rows_pk_kernel<A, B, 4, true><<<grid_r, BLOCK, 0, c->stream>>>(                      \
         X, pk, c->n, f.J, f.Jpad, log_resp, lpn, argmax, lp, cshift ? 1 : 0, pace, stamp)
-    if (nv4 == 3 && nv1 == 1) ESTEP_R(3, 1);
-    else if (nv4 == 3 && nv1 == 0) ESTEP_R(3, 0);
-    else if (nv4 == 3 && nv1 == 2) ESTEP_R(3, 2);
-    else if (nv4 == 4 && nv1 == 0) ESTEP_R(4, 0);
-    else if (nv4 == 2 && nv1 == 0) ESTEP_R(2, 0);
-    else if (nv4 == 2 && nv1 == 1) ESTEP_R(2, 1);
-    else if (nv4 == 2 && nv1 == 2) ESTEP_R(2, 2);
-    else if (nv4 == 1 && nv1 == 0) ESTEP_R(1, 0);
-    else if (nv4 == 1 && nv1 == 1) ESTEP_R(1, 1);
-    else if (nv4 == 1 && nv1 == 2) ESTEP_R(1, 2);
-    else if (nv4 == 0 && nv1 == 1) ESTEP_R(0, 1);
-    else if (nv4 == 0 && nv1 == 2) ESTEP_R(0, 2);
-    else return false;
+    ROWS4_DISPATCH(nv4, nv1, ESTEP_R);
 #undef ESTEP_R
-    return true;
+    return rows4_layout(nv4, nv1);
 }
 
-// estimate_log_prob on the four-rows-in-flight kernel (the layouts the materialising E-step is instantiated for); false: not instantiated
+// estimate_log_prob on the four-rows-in-flight kernel; false: layout not instantiated
 static bool launch_logprob_rows(hgmm_ctx* c, int nv4, int nv1, float* log_prob) {
     const FlatState& f = c->flat;
-    const bool have = (nv4 >= 1 && nv4 <= 3 && nv1 <= 2) || (nv4 == 4 && nv1 == 0) || (nv4 == 0 && (nv1 == 1 || nv1 == 2));
-    if (!have) return false;
+    if (!rows4_layout(nv4, nv1)) return false;
     // Grid: with no reduction and no exponential left, the store stream is all this kernel waits for.  Un-paced it ran
     // 0.60 ms at every grid from 128 to 4096 workgroups on the box where the E-step took 0.54 (tools/logprob_sweep.py):
     // the write path was over-subscribed.  Paced like the E-step (StorePacer), two workgroups per CU: 0.506 ms.
@@ -2233,30 +2165,14 @@ static bool launch_logprob_rows(hgmm_ctx* c, int nv4, int nv1, float* log_prob) 
     // (the raw table follows the rate the E-step's controller has settled on for this row length)
     const int pace = store_pace16(c, grid, f.J, pace_target(c, f.J));
 #define LOGP_R(A, B) flat_logprob_rows_pk_kernel<A, B, true><<<grid, BLOCK, 0, c->stream>>>(X, pk, c->n, f.J, f.Jpad, log_prob, pace)
-    if (nv4 == 3 && nv1 == 1) LOGP_R(3, 1);
-    else if (nv4 == 3 && nv1 == 0) LOGP_R(3, 0);
-    else if (nv4 == 3 && nv1 == 2) LOGP_R(3, 2);
-    else if (nv4 == 4 && nv1 == 0) LOGP_R(4, 0);
-    else if (nv4 == 2 && nv1 == 0) LOGP_R(2, 0);
-    else if (nv4 == 2 && nv1 == 1) LOGP_R(2, 1);
-    else if (nv4 == 2 && nv1 == 2) LOGP_R(2, 2);
-    else if (nv4 == 1 && nv1 == 0) LOGP_R(1, 0);
-    else if (nv4 == 1 && nv1 == 1) LOGP_R(1, 1);
-    else if (nv4 == 1 && nv1 == 2) LOGP_R(1, 2);
-    else if (nv4 == 0 && nv1 == 1) LOGP_R(0, 1);
-    else if (nv4 == 0 && nv1 == 2) LOGP_R(0, 2);
-    else return false;
+    ROWS4_DISPATCH(nv4, nv1, LOGP_R);
 #undef LOGP_R
     return true;
 }
 
-// predict(): the four-rows-in-flight arg-max kernel for the layouts it is instantiated for (the others take the general kernel)
-static bool predict_rows_layout(const hgmm_ctx* c, int nv4, int nv1) {
-    if (c->cfg[CFG_PREDICT_SINGLE_ROW]) return false;
-    return (nv4 == 3 && nv1 <= 2) || (nv4 == 4 && nv1 == 0) || (nv4 == 2 && nv1 <= 2) || (nv4 == 1 && nv1 <= 2) ||
-           (nv4 == 0 && (nv1 == 1 || nv1 == 2));
-}
-static bool launch_predict_rows(hgmm_ctx* c, int nv4, int nv1, int32_t* labels) {
+// predict(): the four-rows-in-flight arg-max kernel (a layout it is not instantiated for takes the general kernel:
+// the caller asks rows4_layout first)
+static void launch_predict_rows(hgmm_ctx* c, int nv4, int nv1, int32_t* labels) {
     const FlatState& f = c->flat;
     // (one frame of 10^6 x 800: 0.38 / 0.26 / 0.26 / 0.24 ms with 1 / 2 / 3 / 4 workgroups per CU; the single-row kernel 0.36)
     // (N = 1e6: 8 workgroups per CU beat 4 at every J -- 0.258 -> 0.235 ms at J = 800, 0.080 -> 0.072 at J = 100; profiles/r04/small_j_grids.log)
@@ -2266,35 +2182,21 @@ static bool launch_predict_rows(hgmm_ctx* c, int nv4, int nv1, int32_t* labels) 
     // (the marginal cost per component is the VALU floor of 4.5 packed + 2.5 plain instructions; what remains is ~0.06 ms
     //  that does not depend on J)
 #define PRED_R(A, B) flat_predict_rows_kernel<A, B><<<grid, BLOCK, 0, c->stream>>>(X, pk, c->n, f.J, f.Jpad, labels)
-    if (nv4 == 3 && nv1 == 1) PRED_R(3, 1);
-    else if (nv4 == 3 && nv1 == 0) PRED_R(3, 0);
-    else if (nv4 == 3 && nv1 == 2) PRED_R(3, 2);
-    else if (nv4 == 4 && nv1 == 0) PRED_R(4, 0);
-    else if (nv4 == 2 && nv1 == 0) PRED_R(2, 0);
-    else if (nv4 == 2 && nv1 == 1) PRED_R(2, 1);
-    else if (nv4 == 2 && nv1 == 2) PRED_R(2, 2);
-    else if (nv4 == 1 && nv1 == 0) PRED_R(1, 0);
-    else if (nv4 == 1 && nv1 == 1) PRED_R(1, 1);
-    else if (nv4 == 1 && nv1 == 2) PRED_R(1, 2);
-    else if (nv4 == 0 && nv1 == 1) PRED_R(0, 1);
-    else if (nv4 == 0 && nv1 == 2) PRED_R(0, 2);
-    else return false;
+    ROWS4_DISPATCH(nv4, nv1, PRED_R);
 #undef PRED_R
-    return true;
 }
 
-// Number of workgroups of the materialising E-step.  The kernel sits where two limits meet: with one wave per SIMD
-// its arithmetic is issue-bound, and the HBM write path delivers LESS the more waves write at once (fillbench) --
-// so there is a best grid and it is sharp: constant-shift loop 0.559 / 0.543 / 0.559 / 0.580 / 0.616 ms at 184 / 192 /
-// 200 / 208 / 256 workgroups, row-maximum loop 0.576 / 0.540 / 0.565 / 0.589 at 208 / 224 / 240 / 256 (one box; the
-// generic loop's optimum sat at 256 on the next one, the constant-shift loop's at 192 on all three that were tried:
-// 0.543 / 0.556 / 0.538 ms against 0.589 / 0.564 / 0.551 for the round-1 shape).  Timing the candidates at first
-// use was tried and dropped: two launches after an idle moment run at other clocks than a stream of them, and picked
-// 176.  Per-row results do not depend on the grid; the mean log-normaliser's summation order does (last bits).
-// Grid of the materialising E-step.  The kernel sits where two limits meet (its header): one wave per SIMD issues one
-// VALU instruction per ~5 cycles whatever its ILP, and the HBM write path delivers less the more waves write at once --
-// so in a stream of E-steps 3/4 of the CUs with one workgroup each is the optimum (0.536 ms; 2 per CU: 0.565).  That
-// optimum is FRAGILE: right behind the HBM-read-bound M-step (the `e_step -> m_step` loop of a caller of the module
+// Number of workgroups of the un-paced materialising E-step.  The kernel sits where two limits meet (its header): with
+// one wave per SIMD its arithmetic is issue-bound -- one VALU instruction per ~5 cycles whatever its ILP -- and the HBM
+// write path delivers LESS the more waves write at once (fillbench) -- so there is a best grid and it is sharp:
+// constant-shift loop 0.559 / 0.543 / 0.559 / 0.580 / 0.616 ms at 184 / 192 / 200 / 208 / 256 workgroups, row-maximum
+// loop 0.576 / 0.540 / 0.565 / 0.589 at 208 / 224 / 240 / 256 (one box; the generic loop's optimum sat at 256 on the
+// next one, the constant-shift loop's at 192 on all three that were tried: 0.543 / 0.556 / 0.538 ms against 0.589 /
+// 0.564 / 0.551 for the round-1 shape).  So in a stream of E-steps 3/4 of the CUs with one workgroup each is the optimum
+// (0.536 ms; 2 per CU: 0.565).  Timing the candidates at first use was tried and dropped: two launches after an idle
+// moment run at other clocks than a stream of them, and picked 176.  Per-row results do not depend on the grid; the
+// mean log-normaliser's summation order does (last bits).
+// That optimum is FRAGILE: right behind the HBM-read-bound M-step (the `e_step -> m_step` loop of a caller of the module
 // functions) the same launch takes 0.81 ms -- the chip comes out of a memory-bound kernel at a lower core clock and the
 // issue-bound side of the kernel pays for it -- while two workgroups per CU take 0.60 ms there
 // (tools/em_loop_probe.py, profiles/r03/em_loop_probe.log: 160 / 192 / 224 / 256 / 320 / 384 / 512 workgroups behind an
@@ -2305,7 +2207,8 @@ static bool launch_predict_rows(hgmm_ctx* c, int nv4, int nv1, int32_t* labels) 
 // The grid therefore follows what the context did last: behind an M-step, or behind an E-step the host has not
 // waited for, two workgroups per CU; after an idle moment 3/4 of the CUs.
 static int estep_rows_grid(hgmm_ctx* c, bool cshift) {
-    const bool after_mstep = c->flat.last_kernel == 2 || (c->flat.last_kernel == 1 && !c->flat.idle_since_launch);
+    const bool after_mstep = c->flat.last_kernel == FLAT_K_MSTEP ||
+                             (c->flat.last_kernel == FLAT_K_ESTEP && !c->flat.idle_since_launch);
     const int full = grid_for(c, (c->n + 3) / 4, after_mstep ? 2 : 1);
     if (after_mstep) return full;
     return cshift ? std::min(full, std::max(1, c->cus * 3 / 4)) : full;
@@ -2324,19 +2227,17 @@ static int launch_estep(hgmm_ctx* c, float* log_resp, float* lpn, int32_t* argma
     // (single-row kernel) non-temporal stores only for rows that are whole 16-byte pieces: J = 513 wrote its table in 0.364 ms
     // with them and in 0.251 ms without -- a line two rows share is written twice, each time in part
     // (profiles/r04/estep_nt_by_J.log)
-    const bool nt = NORMALISE && f.J % 4 == 0;
-    const int rr = 0;
+    const bool nt = f.J % 4 == 0;
     c->flat.last_estep_rows4 = false;                  // (set where the four-rows-in-flight kernel is launched)
-    if (!NORMALISE && !log_resp && !lpn && argmax && predict_rows_layout(c, nv4, nv1)) {      // predict(): labels only
-        ProfScope prof(c, HGMM_K_FLAT_ESTEP);
-        (void)launch_predict_rows(c, nv4, nv1, argmax);
+    if (!NORMALISE && !log_resp && !lpn && argmax && !c->cfg[CFG_PREDICT_SINGLE_ROW] && rows4_layout(nv4, nv1)) {
+        ProfScope prof(c, HGMM_K_FLAT_ESTEP);                                                // predict(): labels only
+        launch_predict_rows(c, nv4, nv1, argmax);
         HGMM_HIP(c, hipGetLastError());
         return HGMM_OK;
     }
     if (!NORMALISE && log_resp && !lpn && !argmax) {                                        // estimate_log_prob: the raw table
         if (launch_logprob_rows(c, nv4, nv1, log_resp)) {
-            c->flat.last_kernel = 1;
-            c->flat.idle_since_launch = false;
+            note_launch(c, FLAT_K_ESTEP);
             HGMM_HIP(c, hipGetLastError());
             return HGMM_OK;
         }
@@ -2358,8 +2259,7 @@ static int launch_estep(hgmm_ctx* c, float* log_resp, float* lpn, int32_t* argma
         const int grid_r = target > 0.0 ? grid_for(c, (c->n + 3) / 4, bpc_rows)
                                         : estep_rows_grid(c, cshift);
         const int pace = store_pace16(c, grid_r, f.J, target);
-        c->flat.last_kernel = 1;
-        c->flat.idle_since_launch = false;
+        note_launch(c, FLAT_K_ESTEP);
         // (only the constant-shift loop is store-bound by construction: the row-maximum loop is not judged)
         unsigned long long* stamp = nullptr;
         const bool observed = cshift && pace_observe_begin(c, target, 4.0 * (double)c->n * (double)f.J, grid_r, &stamp);
@@ -2378,21 +2278,25 @@ static int launch_estep(hgmm_ctx* c, float* log_resp, float* lpn, int32_t* argma
     }
     ProfScope prof(c, HGMM_K_FLAT_ESTEP);
 #define ESTEP_M(A, B)                                                                              \
-    do {                                                                                           \
-        if (nt) flat_estep_kernel<A, B, NORMALISE, NORMALISE><<<grid, BLOCK, 0, c->stream>>>(       \
-                    X, pk, c->n, f.J, f.Jpad, log_resp, lpn, argmax, lp, rr);                       \
-        else flat_estep_kernel<A, B, NORMALISE, false><<<grid, BLOCK, 0, c->stream>>>(              \
-                    X, pk, c->n, f.J, f.Jpad, log_resp, lpn, argmax, lp, rr);                       \
-    } while (0)
+    kernel_for<EstepFamily<A, B, NORMALISE>>(nt)<<<grid, BLOCK, 0, c->stream>>>(                    \
+        X, pk, c->n, f.J, f.Jpad, log_resp, lpn, argmax, lp, 0)
     LAYOUT_DISPATCH(nv4, nv1, ESTEP_M);
 #undef ESTEP_M
     HGMM_HIP(c, hipGetLastError());
     return HGMM_OK;
 }
 
+// the fused kernel with `slots` = S + 1 component slots per lane, one of 1 .. 16
+template <int... S>
+static auto fused_kernel_for(int slots, bool weighted, std::integer_sequence<int, S...>) {
+    decltype(kernel_for<FusedFamily<1>>(weighted)) kernel = nullptr;
+    ((slots == S + 1 ? (void)(kernel = kernel_for<FusedFamily<S + 1>>(weighted)) : (void)0), ...);
+    return kernel;
+}
+
 // comp_major: the partials' layout, [block][Jpad][8] for flat_boundary_kernel instead of [block][7][Jpad] for flat_reduce_kernel
 static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* valid_j, bool comp_major) {
-    c->flat.last_kernel = 3;
+    note_launch(c, FLAT_K_FUSED);
     const FlatState& f = c->flat;
     if (!done_flag) done_flag = c->f_ctl.as<int>() + 16;        // always 0 (flat_setup)
     const int ns = (f.J + 63) / 64;
@@ -2429,34 +2333,11 @@ static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* v
     //    spills 372 B per lane, 0.43 ms; one row (248 VGPRs, two waves per SIMD) stays the best, 0.405 ms;
     //  * constant-shift log-sum-exp: see flat_fused_pk_kernel; 0.514 -> 0.440 ms (a table whose largest constant
     //    leaves the safe range takes the kernel's row-maximum loop by itself).
-#define FUSED_CASE(S)                                                                           \
-    do {                                                                                        \
-        if (sw) flat_fused_pk_kernel<S, true><<<grid, BLOCK, 0, c->stream>>>(                  \
-                    X, pk, c->n, f.J, f.Jpad, part, lp, done_flag, 1, comp_major ? 1 : 0, sw);  \
-        else flat_fused_pk_kernel<S, false><<<grid, BLOCK, 0, c->stream>>>(                    \
-                    X, pk, c->n, f.J, f.Jpad, part, lp, done_flag, 1, comp_major ? 1 : 0, nullptr); \
-        *valid_j = S * 64;                                                                      \
-    } while (0)
+    const int slots = std::min(ns, 16);
+    *valid_j = slots * 64;
     ProfScope prof(c, HGMM_K_FLAT_FUSED);
-    switch (ns) {
-        case 1: FUSED_CASE(1); break;
-        case 2: FUSED_CASE(2); break;
-        case 3: FUSED_CASE(3); break;
-        case 4: FUSED_CASE(4); break;
-        case 5: FUSED_CASE(5); break;
-        case 6: FUSED_CASE(6); break;
-        case 7: FUSED_CASE(7); break;
-        case 8: FUSED_CASE(8); break;
-        case 9: FUSED_CASE(9); break;
-        case 10: FUSED_CASE(10); break;
-        case 11: FUSED_CASE(11); break;
-        case 12: FUSED_CASE(12); break;
-        case 13: FUSED_CASE(13); break;
-        case 14: FUSED_CASE(14); break;
-        case 15: FUSED_CASE(15); break;
-        default: FUSED_CASE(16); break;
-    }
-#undef FUSED_CASE
+    fused_kernel_for(slots, sw != nullptr, std::make_integer_sequence<int, 16>())<<<grid, BLOCK, 0, c->stream>>>(
+        X, pk, c->n, f.J, f.Jpad, part, lp, done_flag, 1, comp_major ? 1 : 0, sw);
     HGMM_HIP(c, hipGetLastError());
     return HGMM_OK;
 }
@@ -2507,6 +2388,18 @@ static int chunk_normalisers(hgmm_ctx* c, bool want_arg, float* lpn_out, int32_t
     return HGMM_OK;
 }
 
+// the N x J table chunk by chunk: normalised by the rows' lpn2, or (lpn2 == nullptr) the raw weighted log-probabilities
+static int chunk_write(hgmm_ctx* c, const float* lpn2, float* out) {
+    const FlatState& f = c->flat;
+    const int grid = grid_for(c, c->n, 2);
+    for (int ci = 0; ci < f.nchunks; ++ci)
+        flat_chunk_write_kernel<<<grid, BLOCK, 0, c->stream>>>(
+            c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, chunk_valid(f, ci), f.Jpad, lpn2,
+            out + ci * CH_J, (int64_t)f.J);
+    HGMM_HIP(c, hipGetLastError());
+    return HGMM_OK;
+}
+
 // statistics of all chunks with the rows' final normalisers -> f_partials (grid returned)
 static int chunk_statistics(hgmm_ctx* c, const int* done_flag, int* grid_out) {
     const FlatState& f = c->flat;
@@ -2514,14 +2407,11 @@ static int chunk_statistics(hgmm_ctx* c, const int* done_flag, int* grid_out) {
     {
         ProfScope prof(c, HGMM_K_FLAT_FUSED);
         const float* sw = c->flat_sw_ptr();
-        for (int ci = 0; ci < f.nchunks; ++ci) {
-            if (sw) flat_chunk_fused_kernel<true><<<grid, BLOCK, 0, c->stream>>>(
-                        c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, f.Jpad, c->f_lpn2.as<float>(),
-                        c->f_partials.as<float>() + ci * CH_J, done_flag, sw);
-            else flat_chunk_fused_kernel<false><<<grid, BLOCK, 0, c->stream>>>(
-                        c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, f.Jpad, c->f_lpn2.as<float>(),
-                        c->f_partials.as<float>() + ci * CH_J, done_flag, nullptr);
-        }
+        const auto kernel = kernel_for<ChunkFusedFamily>(sw != nullptr);
+        for (int ci = 0; ci < f.nchunks; ++ci)
+            kernel<<<grid, BLOCK, 0, c->stream>>>(
+                c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, f.Jpad, c->f_lpn2.as<float>(),
+                c->f_partials.as<float>() + ci * CH_J, done_flag, sw);
     }
     HGMM_HIP(c, hipGetLastError());
     *grid_out = grid;
@@ -2658,37 +2548,20 @@ __global__ __launch_bounds__(256) void flat_weighted_lpn_partials_kernel(
 static int flat_estep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu, const float* inv_std,
                               const float* w, float* dev_log_resp, float*& dev_lpn, int32_t* dev_argmax, int* grid_out,
                               bool params_on_device = false, bool want_mean = false) {
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
+    HGMM_TRY(flat_prepare(c, cov_type, variant, J));
     if (want_mean && c->flat_weighted && !dev_lpn && J <= FLAT_MAX_J) {
         // weights in force: the mean is formed from the rows' log-normalisers -- the context's scratch when the caller has none
         // (J > FLAT_MAX_J: the chunked path's combine kernel weights its partial sums itself)
         HGMM_TRY(ensure(c, c->f_lpn_rows, sizeof(float) * (size_t)c->n));
         dev_lpn = c->f_lpn_rows.as<float>();
     }
-    if (params_on_device) {
-        // the packed table is formed straight from the caller's device arrays: no staging, no copy
-        if (!mu || !inv_std || !w) return fail(c, HGMM_ERR_ARG, "device parameter array is NULL");
-        const FlatState& f = c->flat;
-        flat_pack_kernel<<<(f.Jpad + 255) / 256, 256, 0, c->stream>>>(f.J, f.Jpad, f.cov_type, f.variant, mu, inv_std, w,
-                                                                    c->f_pack.as<float>());
-    } else {
-        HGMM_TRY(flat_upload(c, mu, inv_std, false, w));
-        launch_pack(c);
-    }
+    if (params_on_device && (!mu || !inv_std || !w)) return fail(c, HGMM_ERR_ARG, "device parameter array is NULL");
+    HGMM_TRY(flat_load(c, mu, inv_std, w, params_on_device));
     int grid = 0;
     if (c->flat.chunked) {
-        const FlatState& f = c->flat;
         ProfScope prof(c, HGMM_K_FLAT_ESTEP);
         HGMM_TRY(chunk_normalisers(c, dev_argmax != nullptr, dev_lpn, dev_argmax, true, &grid));
-        if (dev_log_resp) {
-            const int g2 = grid_for(c, c->n, 2);
-            for (int ci = 0; ci < f.nchunks; ++ci)
-                flat_chunk_write_kernel<<<g2, BLOCK, 0, c->stream>>>(
-                    c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, chunk_valid(f, ci), f.Jpad,
-                    c->f_lpn2.as<float>(), dev_log_resp + ci * CH_J, (int64_t)J);
-            HGMM_HIP(c, hipGetLastError());
-        }
+        if (dev_log_resp) HGMM_TRY(chunk_write(c, c->f_lpn2.as<float>(), dev_log_resp));
     } else {
         HGMM_TRY(launch_estep<true>(c, dev_log_resp, dev_lpn, dev_argmax, &grid));
         if (want_mean && c->flat_weighted) {               // the workgroups' partial sums, weighted (see the kernel)
@@ -2720,27 +2593,13 @@ extern "C" int hgmm_flat_estep(hgmm_ctx* c, int cov_type, int variant, int J, co
     return HGMM_OK;
 }
 
-extern "C" int hgmm_flat_estep_async(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu,
-                                     const float* inv_std, const float* w, float* dev_log_resp,
-                                     float* dev_lpn, int32_t* dev_argmax, double* dev_mean_lpn) {
-    HGMM_ENTER(c);
+// the E-step nobody waits for: everything stays on the device (host parameters were copied to the ring)
+static int flat_estep_nowait(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu, const float* inv_std,
+                             const float* w, bool params_on_device, float* dev_log_resp, float* dev_lpn, int32_t* dev_argmax,
+                             double* dev_mean_lpn) {
     int grid = 0;
-    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid, false,
-                                dev_mean_lpn != nullptr));
-    if (dev_mean_lpn) {
-        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, c->flat_n(), dev_mean_lpn);
-        HGMM_HIP(c, hipGetLastError());
-    }
-    return HGMM_OK;                                   // nothing waited for: the caller's arrays were copied to the ring
-}
-
-extern "C" int hgmm_flat_estep_dev(hgmm_ctx* c, int cov_type, int variant, int J, const float* dev_mu,
-                                   const float* dev_inv_std, const float* dev_w, float* dev_log_resp,
-                                   float* dev_lpn, int32_t* dev_argmax, double* dev_mean_lpn) {
-    HGMM_ENTER(c);
-    int grid = 0;
-    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, dev_mu, dev_inv_std, dev_w, dev_log_resp, dev_lpn, dev_argmax,
-                                &grid, /*params_on_device=*/true, dev_mean_lpn != nullptr));
+    HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid,
+                                params_on_device, dev_mean_lpn != nullptr));
     if (dev_mean_lpn) {
         flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, c->flat_n(), dev_mean_lpn);
         HGMM_HIP(c, hipGetLastError());
@@ -2748,12 +2607,25 @@ extern "C" int hgmm_flat_estep_dev(hgmm_ctx* c, int cov_type, int variant, int J
     return HGMM_OK;
 }
 
+extern "C" int hgmm_flat_estep_async(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu,
+                                     const float* inv_std, const float* w, float* dev_log_resp,
+                                     float* dev_lpn, int32_t* dev_argmax, double* dev_mean_lpn) {
+    HGMM_ENTER(c);
+    return flat_estep_nowait(c, cov_type, variant, J, mu, inv_std, w, false, dev_log_resp, dev_lpn, dev_argmax, dev_mean_lpn);
+}
+
+extern "C" int hgmm_flat_estep_dev(hgmm_ctx* c, int cov_type, int variant, int J, const float* dev_mu,
+                                   const float* dev_inv_std, const float* dev_w, float* dev_log_resp,
+                                   float* dev_lpn, int32_t* dev_argmax, double* dev_mean_lpn) {
+    HGMM_ENTER(c);
+    return flat_estep_nowait(c, cov_type, variant, J, dev_mu, dev_inv_std, dev_w, true, dev_log_resp, dev_lpn, dev_argmax,
+                             dev_mean_lpn);
+}
+
 extern "C" int hgmm_pace_reset(hgmm_ctx* c) {
     HGMM_ENTER(c);
-    PaceCtl& p = c->pace;
-    p.target = 0.0;                                        // the next paced launch starts over (pace_target)
-    p.steps_down = p.steps_up = p.ceilings_forgotten = 0;
-    p.tail = p.head;                                       // launches still in flight are not judged any more
+    pace_rate_reset(c->pace);
+    c->pace_ring.tail = c->pace_ring.head;                 // launches still in flight are not judged any more
     return HGMM_OK;
 }
 
@@ -2767,60 +2639,56 @@ extern "C" int hgmm_pace_info(hgmm_ctx* c, double* target_gbs_out, int* steps_do
     return HGMM_OK;
 }
 
+static int flat_predict(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu, const float* inv_std,
+                        const float* w, bool params_on_device, int32_t* dev_labels) {
+    if (!dev_labels) return fail(c, HGMM_ERR_ARG, "dev_labels is NULL");
+    if (params_on_device && (!mu || !inv_std || !w)) return fail(c, HGMM_ERR_ARG, "device parameter array is NULL");
+    HGMM_TRY(flat_prepare(c, cov_type, variant, J));
+    HGMM_TRY(flat_load(c, mu, inv_std, w, params_on_device));
+    int grid = 0;
+    if (c->flat.chunked) return chunk_normalisers(c, true, nullptr, dev_labels, false, nullptr);
+    return launch_estep<false>(c, nullptr, nullptr, dev_labels, &grid);
+}
+
 extern "C" int hgmm_flat_predict(hgmm_ctx* c, int cov_type, int variant, int J, const float* mu,
                                  const float* inv_std, const float* w, int32_t* dev_labels) {
     HGMM_ENTER(c);
-    if (!c || !dev_labels) return c ? fail(c, HGMM_ERR_ARG, "dev_labels is NULL") : HGMM_ERR_ARG;
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
-    HGMM_TRY(flat_upload(c, mu, inv_std, false, w));
-    launch_pack(c);
-    int grid = 0;
-    if (c->flat.chunked) return chunk_normalisers(c, true, nullptr, dev_labels, false, nullptr);
-    HGMM_TRY(launch_estep<false>(c, nullptr, nullptr, dev_labels, &grid));
-    return HGMM_OK;
+    return flat_predict(c, cov_type, variant, J, mu, inv_std, w, false, dev_labels);
 }
 
 extern "C" int hgmm_flat_predict_dev(hgmm_ctx* c, int cov_type, int variant, int J, const float* dev_mu,
                                      const float* dev_inv_std, const float* dev_w, int32_t* dev_labels) {
     HGMM_ENTER(c);
-    if (!c || !dev_labels) return c ? fail(c, HGMM_ERR_ARG, "dev_labels is NULL") : HGMM_ERR_ARG;
-    if (!dev_mu || !dev_inv_std || !dev_w) return fail(c, HGMM_ERR_ARG, "device parameter array is NULL");
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
-    const FlatState& f = c->flat;
-    flat_pack_kernel<<<(f.Jpad + 255) / 256, 256, 0, c->stream>>>(f.J, f.Jpad, f.cov_type, f.variant, dev_mu, dev_inv_std,
-                                                                dev_w, c->f_pack.as<float>());
-    int grid = 0;
-    if (c->flat.chunked) return chunk_normalisers(c, true, nullptr, dev_labels, false, nullptr);
-    HGMM_TRY(launch_estep<false>(c, nullptr, nullptr, dev_labels, &grid));
-    return HGMM_OK;
+    return flat_predict(c, cov_type, variant, J, dev_mu, dev_inv_std, dev_w, true, dev_labels);
 }
 
 extern "C" int hgmm_flat_log_prob(hgmm_ctx* c, int cov_type, int J, const float* mu, const float* inv_std,
                                   float* dev_log_prob) {
     HGMM_ENTER(c);
-    if (!c || !dev_log_prob) return c ? fail(c, HGMM_ERR_ARG, "dev_log_prob is NULL") : HGMM_ERR_ARG;
+    if (!dev_log_prob) return fail(c, HGMM_ERR_ARG, "dev_log_prob is NULL");
     // weights = 1 under flavour G (log 1 = 0, no eps) gives the bare log-density
-    HGMM_TRY(flat_check(c, cov_type, cov_type == HGMM_COV_DIAG ? HGMM_VARIANT_G : HGMM_VARIANT_W, J));
-    HGMM_TRY(flat_setup(c, cov_type, HGMM_VARIANT_G, J));
+    HGMM_TRY(flat_prepare(c, cov_type, cov_type == HGMM_COV_DIAG ? HGMM_VARIANT_G : HGMM_VARIANT_W, J, HGMM_VARIANT_G));
     std::vector<float> ones((size_t)J, 1.0f);
     HGMM_TRY(flat_upload(c, mu, inv_std, false, ones.data()));
     HGMM_HIP(c, ctx_stream_sync(c));   // `ones` is pageable host memory
-    launch_pack(c);
+    launch_pack(c, c->f_mu.as<float>(), c->f_inv.as<float>(), c->f_w.as<float>());
     int grid = 0;
-    if (c->flat.chunked) {
-        const FlatState& f = c->flat;
-        const int g2 = grid_for(c, c->n, 2);
-        for (int ci = 0; ci < f.nchunks; ++ci)
-            flat_chunk_write_kernel<<<g2, BLOCK, 0, c->stream>>>(
-                c->x_aos.as<float>(), c->f_pack.as<float>() + ci * CH_J, c->n, chunk_valid(f, ci), f.Jpad, nullptr,
-                dev_log_prob + ci * CH_J, (int64_t)J);
-        HGMM_HIP(c, hipGetLastError());
-        return HGMM_OK;
-    }
-    HGMM_TRY(launch_estep<false>(c, dev_log_prob, nullptr, nullptr, &grid));
-    return HGMM_OK;
+    if (c->flat.chunked) return chunk_write(c, nullptr, dev_log_prob);
+    return launch_estep<false>(c, dev_log_prob, nullptr, nullptr, &grid);
+}
+
+// the M-step's kernel in one layout over `jv` columns from resp / hint / part on (the whole table, or one chunk of it)
+template <int NV4, int NV1>
+static void launch_mstep(hgmm_ctx* c, int grid, int is_log, const float* resp, const float* hint, int jv, float* part) {
+    const FlatState& f = c->flat;
+    const float* sw = c->flat_sw_ptr();             // hgmm_flat_set_weights: the WEIGHTED instantiations
+    // non-temporal loads: 6.1 -> 6.8 TB/s at J = 800, a gain or a tie for every row length that is a whole number of
+    // 16-byte pieces -- and a loss when rows straddle them (J = 513: 0.380 vs 0.351 ms, J = 37: 0.176 vs 0.142: a line shared by
+    // two rows is then fetched for each of them; profiles/r04/mstep_nt_by_J.log)
+    const bool ntload = f.J % 4 == 0;
+    const int rr = 1;                               // rows dealt round-robin: 0.480 against 0.492 ms (profiles/r04/mstep_nt_rr_sweep.log)
+    kernel_for<MstepFamily<NV4, NV1>>(is_log != 0, ntload, sw != nullptr)<<<grid, BLOCK, 0, c->stream>>>(
+        c->x_aos.as<float>(), resp, hint, c->n, jv, f.Jpad, part, (int64_t)f.J, rr, sw);
 }
 
 // The M-step's launches.  centre_hint: host [J,3] (staged), device [J,3] (hint_on_device) or NULL; the new parameters
@@ -2843,64 +2711,30 @@ static int flat_mstep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
     //  with 4, J = 400 0.271 -> 0.257; from J = 512 on two again: profiles/r04/small_j_grids.log)
     const int bpc_m = c->n >= 400000 ? (J <= 128 ? 8 : (J <= 448 ? 4 : 2)) : 2;
     const int grid = grid_for(c, c->n, bpc_m);
-    const int rr = 1;                               // rows dealt round-robin: 0.480 against 0.492 ms (profiles/r04/mstep_nt_rr_sweep.log)
-    const float* X = c->x_aos.as<float>();
     float* part = c->f_partials.as<float>();
     const float* hint = c->f_hint.as<float>();
-    const float* sw = c->flat_sw_ptr();
     int valid_j = 0;
-    // non-temporal loads: 6.1 -> 6.8 TB/s at J = 800, a gain or a tie for every row length that is a whole number of
-    // 16-byte pieces -- and a loss when rows straddle them (J = 513: 0.380 vs 0.351 ms, J = 37: 0.176 vs 0.142: a line shared by
-    // two rows is then fetched for each of them; profiles/r04/mstep_nt_by_J.log)
-    const bool ntload = J % 4 == 0;
-#define MSTEP_LAUNCH_W(A, B, RESP, HINT, JV, PART)                                                             \
-    do {                                                                                                       \
-        if (is_log) {                                                                                          \
-            if (ntload) flat_mstep_kernel<A, B, true, true, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw);  \
-            else flat_mstep_kernel<A, B, true, false, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw);       \
-        } else {                                                                                               \
-            if (ntload) flat_mstep_kernel<A, B, false, true, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw); \
-            else flat_mstep_kernel<A, B, false, false, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr, sw);      \
-        }                                                                                                      \
-    } while (0)
-#define MSTEP_LAUNCH_U(A, B, RESP, HINT, JV, PART)                                                             \
-    do {                                                                                                       \
-        if (is_log) {                                                                                          \
-            if (ntload) flat_mstep_kernel<A, B, true, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr);  \
-            else flat_mstep_kernel<A, B, true, false><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr);       \
-        } else {                                                                                               \
-            if (ntload) flat_mstep_kernel<A, B, false, true><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr); \
-            else flat_mstep_kernel<A, B, false, false><<<grid, BLOCK, 0, c->stream>>>(X, RESP, HINT, c->n, JV, f.Jpad, PART, (int64_t)J, rr);      \
-        }                                                                                                      \
-    } while (0)
-    // hgmm_flat_set_weights: the WEIGHTED instantiation set
-#define MSTEP_LAUNCH(A, B, RESP, HINT, JV, PART)                                                               \
-    do {                                                                                                       \
-        if (sw) MSTEP_LAUNCH_W(A, B, RESP, HINT, JV, PART); else MSTEP_LAUNCH_U(A, B, RESP, HINT, JV, PART);    \
-    } while (0)
-    if (f.chunked) {
+    {
         ProfScope prof(c, HGMM_K_FLAT_MSTEP);
-        for (int ci = 0; ci < f.nchunks; ++ci)
-            MSTEP_LAUNCH(0, CH_SLOTS, dev_resp + ci * CH_J, hint + ci * CH_J, chunk_valid(f, ci), part + ci * CH_J);
-        valid_j = f.nchunks * CH_J;
-    } else {
-        ProfScope prof(c, HGMM_K_FLAT_MSTEP);
-        int nv4, nv1;
-        pick_layout(J, &nv4, &nv1);
+        if (f.chunked) {
+            for (int ci = 0; ci < f.nchunks; ++ci)
+                launch_mstep<0, CH_SLOTS>(c, grid, is_log, dev_resp + ci * CH_J, hint + ci * CH_J, chunk_valid(f, ci),
+                                          part + ci * CH_J);
+            valid_j = f.nchunks * CH_J;
+        } else {
+            int nv4, nv1;
+            pick_layout(J, &nv4, &nv1);
 #define MSTEP_M(A, B)                                                                              \
     do {                                                                                           \
-        MSTEP_LAUNCH(A, B, dev_resp, hint, J, part);                                               \
+        launch_mstep<A, B>(c, grid, is_log, dev_resp, hint, J, part);                              \
         valid_j = 256 * A + 64 * B;                                                                \
     } while (0)
-        LAYOUT_DISPATCH(nv4, nv1, MSTEP_M);
+            LAYOUT_DISPATCH(nv4, nv1, MSTEP_M);
 #undef MSTEP_M
+        }
     }
-#undef MSTEP_LAUNCH
-#undef MSTEP_LAUNCH_W
-#undef MSTEP_LAUNCH_U
     HGMM_HIP(c, hipGetLastError());
-    c->flat.last_kernel = 2;                               // (the next E-step's grid looks at this, estep_rows_grid)
-    c->flat.idle_since_launch = false;
+    note_launch(c, FLAT_K_MSTEP);                          // (the next E-step's grid looks at this, estep_rows_grid)
     HGMM_TRY(launch_reduce(c, grid, valid_j, false, nullptr));
     if (f.chunked)
         flat_finalize_mb_kernel<<<(f.Jpad + 255) / 256, 256, 0, c->stream>>>(
@@ -2918,8 +2752,7 @@ extern "C" int hgmm_flat_mstep_dev(hgmm_ctx* c, int cov_type, int variant, int J
     HGMM_ENTER(c);
     if (!c || !dev_resp) return c ? fail(c, HGMM_ERR_ARG, "dev_resp is NULL") : HGMM_ERR_ARG;
     if (!dev_w || !dev_mu || !dev_cov) return fail(c, HGMM_ERR_ARG, "device output array is NULL");
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
+    HGMM_TRY(flat_prepare(c, cov_type, variant, J));
     return flat_mstep_enqueue(c, cov_type, variant, J, dev_resp, is_log, dev_centre_hint, true, dev_w, dev_mu, dev_cov);
 }
 
@@ -2928,8 +2761,7 @@ extern "C" int hgmm_flat_mstep(hgmm_ctx* c, int cov_type, int variant, int J, co
                                float* cov_out) {
     HGMM_ENTER(c);
     if (!c || !dev_resp) return c ? fail(c, HGMM_ERR_ARG, "dev_resp is NULL") : HGMM_ERR_ARG;
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
+    HGMM_TRY(flat_prepare(c, cov_type, variant, J));
     FlatState& f = c->flat;
     HGMM_TRY(flat_mstep_enqueue(c, cov_type, variant, J, dev_resp, is_log, centre_hint, false, c->f_w.as<float>(),
                                 c->f_mu.as<float>(), c->f_cov.as<float>()));
@@ -3021,8 +2853,7 @@ extern "C" int hgmm_flat_train_begin(hgmm_ctx* c, int cov_type, int variant, int
                                      const float* mu, const float* cov, const float* w,
                                      int lls_capacity) {
     HGMM_ENTER(c);
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
+    HGMM_TRY(flat_prepare(c, cov_type, variant, J));
     if (lls_capacity < 1) lls_capacity = 1;
     HGMM_TRY(ensure(c, c->f_lls, sizeof(float) * lls_capacity));
     FlatState& f = c->flat;
@@ -3144,10 +2975,8 @@ extern "C" int hgmm_flat_stats(hgmm_ctx* c, int cov_type, int variant, int J, co
                                const float* inv_std, const float* w, double* stats_out,
                                double* sum_lpn_out, double* n_points_out) {
     HGMM_ENTER(c);
-    HGMM_TRY(flat_check(c, cov_type, variant, J));
-    HGMM_TRY(flat_setup(c, cov_type, variant, J));
-    HGMM_TRY(flat_upload(c, mu, inv_std, false, w));
-    launch_pack(c);
+    HGMM_TRY(flat_prepare(c, cov_type, variant, J));
+    HGMM_TRY(flat_load(c, mu, inv_std, w, false));
     int grid = 0, valid_j = 0;
     if (c->flat.chunked) {
         int n_lpn = 0;

@@ -39,6 +39,35 @@ int ensure(hgmm_ctx* c, DevBuf& b, size_t bytes) {
     return HGMM_OK;
 }
 
+// ---- pinned staging ring ----------------------------------------------------------------------
+// Small host <-> device transfers of the API-granular calls (parameters in, M-step results out, the tree / forest /
+// voxel / k-means tables) go through a pinned ring owned by the context: the host side is a memcpy, the device side a
+// genuinely asynchronous DMA that queues behind the kernels already on the stream -- so an enqueueing call returns while
+// its kernel runs and the next call's host work overlaps it.  A region is reused only after a stream synchronisation.
+int stage_reserve(hgmm_ctx* c, size_t bytes, void** out) {
+    if (!c->h_stage) {
+        HGMM_HIP(c, hipHostMalloc(&c->h_stage, STAGE_RING_BYTES, hipHostMallocDefault));
+        c->h_stage_cap = STAGE_RING_BYTES;
+        c->h_stage_off = 0;
+    }
+    bytes = (bytes + 255) & ~(size_t)255;
+    if (bytes > c->h_stage_cap) return fail(c, HGMM_ERR_ARG, "staging request of %zu bytes", bytes);
+    if (c->h_stage_off + bytes > c->h_stage_cap) {
+        HGMM_HIP(c, ctx_stream_sync(c));         // every earlier region has been consumed
+        c->h_stage_off = 0;
+    }
+    *out = static_cast<char*>(c->h_stage) + c->h_stage_off;
+    c->h_stage_off += bytes;
+    return HGMM_OK;
+}
+int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {
+    void* st = nullptr;
+    HGMM_TRY(stage_reserve(c, bytes, &st));
+    std::memcpy(st, host, bytes);
+    HGMM_HIP(c, hipMemcpyAsync(dev, st, bytes, hipMemcpyHostToDevice, c->stream));
+    return HGMM_OK;
+}
+
 ProfScope::ProfScope(hgmm_ctx* ctx, int kernel) : c(ctx) {
     if (!c->profiling) return;
     if (c->events_used == c->events.size()) {
@@ -753,9 +782,9 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
     if (c->hand.host) (void)hipHostFree(c->hand.host);
     if (c->h_scalars) (void)hipHostFree(c->h_scalars);
     for (hipEvent_t& e : c->ev_slots) if (e) (void)hipEventDestroy(e);
-    if (c->pace.have_events)
-        for (auto& pr : c->pace.ev) { (void)hipEventDestroy(pr[0]); (void)hipEventDestroy(pr[1]); }
-    if (c->pace.stamps) (void)hipHostFree(c->pace.stamps);
+    if (c->pace_ring.have_events)
+        for (auto& pr : c->pace_ring.ev) { (void)hipEventDestroy(pr[0]); (void)hipEventDestroy(pr[1]); }
+    if (c->pace_ring.stamps) (void)hipHostFree(c->pace_ring.stamps);
     for (hipEvent_t& e : c->tree_ev) if (e) (void)hipEventDestroy(e);
     for (auto& p : c->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     (void)hipStreamDestroy(c->stream);

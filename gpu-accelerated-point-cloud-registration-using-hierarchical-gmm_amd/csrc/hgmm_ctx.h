@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/hgmm.h"
+#include "flat_pace.h"
 
 namespace hgmm {
 
@@ -31,6 +32,8 @@ struct DevBuf {
 
 struct EventPair { hipEvent_t a, b; int kernel; };
 
+enum FlatKernel { FLAT_K_NONE, FLAT_K_ESTEP /* materialising E-step */, FLAT_K_MSTEP /* M-step from resp */, FLAT_K_FUSED /* fused EM */ };
+
 struct FlatState {
     int cov_type = 0, variant = 0, J = 0, Jpad = 0;
     float tol = 0.f;
@@ -39,28 +42,16 @@ struct FlatState {
     bool active = false;
     bool chunked = false;             // J > FLAT_MAX_J: 832-component chunks
     int nchunks = 1;
-    int last_kernel = 0;              // what this context enqueued last: 1 materialising E-step, 2 M-step from resp, 3 fused EM
+    FlatKernel last_kernel = FLAT_K_NONE;   // what this context enqueued last (flat_kernels.hip: note_launch)
     bool last_estep_rows4 = false;    // the last materialising E-step ran the four-rows-in-flight kernel (its waves' row order:
                                       // flat_weighted_lpn_partials_kernel re-plays it)
     bool idle_since_launch = true;    // the host has drained the stream since the last of these launches (ctx_stream_sync)
 };
 
-// Online control of the store pacer's target rate (flat_kernels.hip, pace_target / pace_observe): the last few paced
-// E-step launches are bracketed by event pairs that are looked at -- never waited for -- when the next one is launched.
-struct PaceCtl {
+// The store pacer's measurement ring (its rate controller: flat_pace.h): the last few paced E-step launches are bracketed
+// by event pairs that are looked at -- never waited for -- when the next one is launched (flat_kernels.hip, pace_poll).
+struct PaceRing {
     static constexpr int RING = 4;
-    double target = 0.0;               // GB/s offered by the next paced launch; 0: not initialised
-    int strikes = 0;                   // consecutive launches that ran longer than their target explains
-    int J = 0;                         // the row length the state belongs to (another J starts over)
-    int steps_down = 0;                // how often the target was lowered (reported by hgmm_pace_info)
-    int steps_up = 0;                  // probes upwards that held
-    // probing upwards: after `probe_after` clean launches in a row the next ones are offered 2 % more; three clean ones
-    // make that the new target, a single long one ends the probe, caps the rate below it and doubles `probe_after`
-    double ceiling = 1e30;             // a rate that was seen to congest: not probed again until it is forgotten
-    int since_ceiling = 0;             // clean launches since the ceiling was learnt (forgotten after PACE_FORGET_AFTER)
-    int ceilings_forgotten = 0;
-    double probe_base = 0.0;           // > 0: a probe is running, this is the rate to fall back to
-    int clean = 0, probe_after = 0, probe_seen = 0;
     hipEvent_t ev[RING][2] = {};
     double tgt_at[RING] = {}, bytes_at[RING] = {};
     unsigned head = 0, tail = 0;
@@ -204,7 +195,8 @@ struct hgmm_ctx {
 
     // ---- flat EM ----------------------------------------------------------------
     hgmm::FlatState flat;
-    hgmm::PaceCtl pace;
+    hgmm::PaceRate pace;                      // the store pacer's rate (flat_pace.h) ...
+    hgmm::PaceRing pace_ring;                 // ... and what it is measured with
     hgmm::DevBuf f_block;                     // float [10][Jpad]: the allocation behind the four arrays below
     hgmm::DevBuf f_mu, f_cov, f_w, f_inv;     // float model parameters (reference layout): NON-OWNING slices of f_block
     hgmm::DevBuf f_pack;                      // float [PK_ROWS = 8][Jpad] packed E-step params (flat_kernels.hip: mu, g, c, w)
@@ -219,7 +211,7 @@ struct hgmm_ctx {
     double* h_scalars = nullptr;              // pinned, device-visible scalars (hgmm_host_scalars)
     int h_scalars_n = 0;
     hipEvent_t ev_slots[64] = {};             // hgmm_event_record / hgmm_event_wait
-    // pinned host ring for small parameter uploads / result downloads (flat_kernels.hip: stage_*): a pageable
+    // pinned host ring for small parameter uploads / result downloads (hgmm_api.hip: stage_*): a pageable
     // hipMemcpyAsync is staged by the runtime behind the stream's pending work, a pinned one is a plain DMA packet
     void* h_stage = nullptr;
     size_t h_stage_cap = 0, h_stage_off = 0;
@@ -316,11 +308,11 @@ struct hgmm_ctx {
 };
 
 namespace hgmm {
-// a region of the context's pinned staging ring (flat_kernels.hip); reused only after a stream synchronisation
+// a region of the context's pinned staging ring (hgmm_api.hip); reused only after a stream synchronisation
+constexpr size_t STAGE_RING_BYTES = 4u << 20;
 int stage_reserve(hgmm_ctx* c, size_t bytes, void** out);
 // `bytes` of host memory on their way to `dev`: copied into a region of the ring, one DMA packet behind the stream's work
 int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes);
-constexpr size_t STAGE_RING_BYTES = 4u << 20;
 
 }  // namespace hgmm
 
@@ -428,7 +420,17 @@ struct ProfScope {
 };
 int profile_collect(hgmm_ctx* c);
 
-// sub-system entry points implemented in flat_kernels.hip
+// ---- the instantiation of a kernel family for run-time flags -------------------------------------------------------------
+// kernel_for<FAMILY>(flag, flag, ...) is FAMILY::kernel<flag, flag, ...>(): a family is a struct whose static member
+// template `kernel` names the instantiation for its compile-time flags.  The one place a further flag is added.
+template <class FAMILY, bool... FLAGS>
+inline auto kernel_for() { return FAMILY::template kernel<FLAGS...>(); }
+template <class FAMILY, bool... FLAGS, class... REST>
+inline auto kernel_for(bool flag, REST... rest) {
+    return flag ? kernel_for<FAMILY, FLAGS..., true>(rest...) : kernel_for<FAMILY, FLAGS..., false>(rest...);
+}
+
+// the communicator's all-reduces (hgmm_api.hip)
 int allreduce_f64_dev(hgmm_ctx* c, double* dev, size_t n);
 int allreduce_f64_oop(hgmm_ctx* c, const double* src, double* dst, size_t n);
 int allreduce_i64_dev(hgmm_ctx* c, long long* dev, size_t n);      // exact (integer) sum, in place

@@ -504,7 +504,7 @@ int score_set(hgmm_ctx* c, const RegSet& set, const double* rot, const double* t
     return HGMM_OK;
 }
 
-// ---- the kernel families of the forest build (kernel_for, tree_host.h; the last flag: WEIGHTED) ---------------------------
+// ---- the kernel families of the forest build (kernel_for, hgmm_ctx.h; the last flag: WEIGHTED) ---------------------------
 // (the forest's E-step is always the two-pass form)
 struct ForestEstepFamily { template <bool W> static auto kernel() { return forest_estep_kernel<true, W>; } };
 struct ForestLlEstepFamily { template <bool F32, bool W> static auto kernel() { return forest_ll_estep_kernel<F32, W>; } };

@@ -88,16 +88,6 @@ __attribute__((format(printf, 6, 7))) inline int device_watch(hgmm_ctx* c, unsig
     return fail(c, HGMM_ERR_STATE, "%s: no progress (the stream is idle and the device has not reported)", what);
 }
 
-// ---- the instantiation of a kernel family for run-time flags -------------------------------------------------------------
-// kernel_for<FAMILY>(flag, flag, ...) is FAMILY::kernel<flag, flag, ...>(): a family is a struct whose static member
-// template `kernel` names the instantiation for its compile-time flags.  The one place a further flag is added.
-template <class FAMILY, bool... FLAGS>
-inline auto kernel_for() { return FAMILY::template kernel<FLAGS...>(); }
-template <class FAMILY, bool... FLAGS, class... REST>
-inline auto kernel_for(bool flag, REST... rest) {
-    return flag ? kernel_for<FAMILY, FLAGS..., true>(rest...) : kernel_for<FAMILY, FLAGS..., false>(rest...);
-}
-
 // ---- the two host loops of every device-side stop rule -----------------------------------------------------------------
 // The polled look-ahead loop (hgmm_tree_build: B = 1, ahead = tree_ahead; hgmm_tree_build_batch: 2; forest_register_on_device:
 // 3).  Every member's stop rule stores (stopped << 32 | iterations) into its progress word of pinned HOST memory; the host

@@ -597,7 +597,7 @@ static int tree_prep(hgmm_ctx* c, int64_t jb, int64_t je) {
     return HGMM_OK;
 }
 
-// ---- the kernel families of the build (kernel_for, tree_host.h; the last flag: WEIGHTED, hgmm_tree_set_source_weights) ----
+// ---- the kernel families of the build (kernel_for, hgmm_ctx.h; the last flag: WEIGHTED, hgmm_tree_set_source_weights) ----
 struct EstepFamily { template <bool HALF, bool W> static auto kernel() { return tree_estep_kernel<HALF, W>; } };
 // (two points per thread: `overlap` excludes the four-point form)
 struct LlEstepFamily { template <bool F32, bool W> static auto kernel() { return tree_ll_estep_kernel<2, F32, W>; } };

@@ -30,9 +30,10 @@ def oracle64_estep(X, inv, mu, w, cov_type, variant):
     return flat_em.e_step_full(f(X), f(inv), f(mu), f(w), cov_type, variant)
 
 
-def check_estep(ctx, X, inv, mu, w, cov_type, variant, label=""):
+def check_estep(ctx, X, inv, mu, w, cov_type, variant, label="", oracle=None):
+    """(oracle: oracle64_estep's result on these inputs, where the caller has it already)"""
     ctx.set_points(X)
-    o_mean, o_lr, o_lpn, o_am = oracle64_estep(X, inv, mu, w, cov_type, variant)
+    o_mean, o_lr, o_lpn, o_am = oracle or oracle64_estep(X, inv, mu, w, cov_type, variant)
     # Without the arg-max output the materialising kernel takes its constant-shift loop (no row maximum), with it
     # the row-maximum loop: BOTH are held to the oracle, the first here, the second below.
     mean_cs, lr_cs, lpn_cs, _ = ctx.flat_estep(inv, mu, w, cov_type, variant, want_lpn=True, want_argmax=False)
@@ -501,7 +502,7 @@ def test_c3_training_20_iterations_match_oracle_fixture(ctx):
 
 
 def test_store_pacer_controller_backs_off(monkeypatch):
-    """The materialising E-step offers its rows at a controlled rate (StorePacer / PaceCtl, csrc/flat_kernels.hip): a
+    """The materialising E-step offers its rows at a controlled rate (StorePacer; csrc/flat_pace.h, csrc/flat_kernels.hip): a
     context started far above the write path's knee (HGMM_PACE_START=7800) must walk down -- launches that run > 6 %
     longer than the rate explains are strikes, three in a row lower it by 2 % -- without ever waiting for its evidence,
     and the table it writes is the same whatever the rate; a fixed rate (HGMM_ESTEP_TARGET_GBS) switches the controller
@@ -847,9 +848,11 @@ def test_large_component_counts_chunked_path(ctx, N, J):
         assert len(r[4]) == len(o2[4]) and r[5] == o2[5]
 
 
-@pytest.mark.parametrize("J", [4, 64, 128, 132, 256, 300, 384, 512, 560, 640, 768, 832, 896, 1000, 1024])
+@pytest.mark.parametrize("J", [4, 64, 128, 132, 256, 300, 384, 512, 560, 640, 768, 832, 896, 1000, 1024,
+                               63, 65, 129, 193, 257, 385, 513, 769])
 def test_every_lane_layout(ctx, J):
-    """One J per (vector slots, scalar slots) lane layout of the E-step / M-step kernels."""
+    """One J per (vector slots, scalar slots) lane layout of the E-step / M-step kernels -- the second row: the scalar-slot
+    layouts (0,1) (0,2) (0,3) (0,4) (0,6) (0,8) (0,12) (0,16) of a J that is no multiple of 4 -- all 18 of the layout table."""
     N = 1500 + J
     rs = np.random.RandomState(J)
     X = rs.rand(N, 3).astype(np.float32)
@@ -857,8 +860,18 @@ def test_every_lane_layout(ctx, J):
     inv = (1.0 / np.sqrt(0.005 + 0.05 * rs.rand(J, 3))).astype(np.float32)
     w = rs.rand(J).astype(np.float32) + 0.01
     w /= w.sum()
-    lr = check_estep(ctx, X, inv, mu, w, "diag", "W", "layout J=%d" % J)
+    oracle = oracle64_estep(X, inv, mu, w, "diag", "W")
+    lr = check_estep(ctx, X, inv, mu, w, "diag", "W", "layout J=%d" % J, oracle=oracle)
     f64 = lambda a: np.asarray(a, dtype=np.float64)
+    # predict's own kernel and estimate_log_prob's raw table in this layout (test_random_shapes' tie rule and tolerances)
+    o_r, o_am = np.exp(oracle[1]), oracle[3]
+    flips = ctx.flat_predict(inv, mu, w, "diag", "W").get() != o_am
+    if flips.any():
+        part = np.partition(o_r[flips], -2, axis=1)
+        assert ((part[:, -1] - part[:, -2]) < 1e-5).all()
+    o_lp = flat_em.log_gauss_diag(f64(X), f64(inv), f64(mu))
+    np.testing.assert_allclose(ctx.flat_log_prob(inv, mu, "diag").get(), o_lp, rtol=2e-5,
+                               atol=2e-5 * max(1.0, float(np.abs(o_lp).max()) * 1e-2))
     o_w, o_mu, o_cov = flat_em.m_step(f64(X), np.exp(f64(lr)), "diag", "W")
     ctx.set_points(X)
     w_m, mu_m, cov_m = ctx.flat_mstep(ctx.to_device(lr).exp(), "diag", "W", centre_hint=mu)

@@ -157,6 +157,18 @@ def test_ragged_sizes_against_the_restatement(ctx, N, J):
     np.testing.assert_allclose(mu_t, o[1], rtol=0, atol=2e-5)
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("J", [64, 65])
+def test_mstep_every_instantiation_flag(ctx, J, weighted):
+    """flat_mstep_kernel's three flags in one place: log / plain responsibilities (check_mstep runs both), rows that are whole
+    16-byte pieces or not (J % 4), weights or none (unit weights in the restatement: its sums are then the unweighted ones)"""
+    X, mu, inv, w, s = ragged(300, J)
+    ctx.set_points(X)
+    ctx.flat_set_weights(s if weighted else None)
+    lr = ctx.flat_estep(inv, mu, w, "diag", "W")[1].get()
+    check_mstep(ctx, X, s if weighted else np.ones(len(X), np.float32), lr, mu, "flags %dx%d %s" % (300, J, weighted))
+
+
 @pytest.mark.parametrize("N,J", CHUNKED)
 def test_chunked_path_against_the_restatement(ctx, N, J):
     """J > 1024 (test_large_component_counts_chunked_path's cloud, runs and bounds), the early stop included"""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The store pacer's controller (flat_kernels.hip, PaceCtl): started far ABOVE the write path's knee it must walk down to
+"""The store pacer's controller (csrc/flat_pace.h, PaceRate): started far ABOVE the write path's knee it must walk down to
 a rate the memory system takes (HGMM_PACE_START overrides the initial 6700 GB/s for this probe); started at its default
 it must stay put.  Prints the target and the kernel time per block of 10 launches, in three call patterns."""
 import os, sys
