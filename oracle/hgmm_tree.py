@@ -85,31 +85,46 @@ def pdf_pairs(x, mu, inv, coef):
     return coef * np.exp(-0.5 * t)
 
 
-def e_step(points, pi, mu, cov, parent_idx, lvl_nodes=None):
-    """One tree E-step.  hgmm_cupy_cpu_working.py:162-191 (+accumulate 99-106).
-
-    Returns (m0[T], m1[T,3], m2[T,3,3], current_idx[N], gamma[N,8]).
-    """
-    T = len(pi)
-    n = len(points)
-    j0 = child(np.asarray(parent_idx, dtype=np.int64))
-    kid = j0[:, None] + np.arange(N_NODE)[None, :]                  # [N,8]
-    ok, inv, coef = node_prep(cov)
-    g = pi[kid] * pdf_pairs(points[:, None, :], mu[kid], inv[kid], coef[kid])
+def child_gamma(x, j0, pi, mu, inv, coef):
+    """The eight children j0 .. j0+7 of each point's node: kid [n,8], g = pi N(x) [n,8], den = sum g, good = den > EPS and
+    gamma = g / den (0 where not good).  hgmm_cupy_cpu_working.py:170-183 and 207-217: the build's E-step and the
+    registration descent normalise alike."""
+    kid = j0[:, None] + np.arange(N_NODE)[None, :]
+    g = pi[kid] * pdf_pairs(x[:, None, :], mu[kid], inv[kid], coef[kid])
     den = g.sum(axis=1)
     good = den > EPS
     gamma = np.where(good[:, None], g / np.where(good, den, 1.0)[:, None], 0.0)
+    return kid, g, den, good, gamma
+
+
+def new_moments(T):
+    return np.zeros(T), np.zeros((T, 3)), np.zeros((T, 3, 3))
+
+
+def add_moments(m0, m1, m2, nodes, g, x):
+    """m0[nodes] += g, m1[nodes] += g x, m2[nodes] += g x x^T, pair by pair in index order (accumulate, 99-106).
+    ``nodes`` and ``g`` have one shape, ``x`` [..., 3] broadcasts against it."""
+    flat = nodes.ravel()                                             # (add.at is slower under a 2-d index)
+    np.add.at(m0, flat, g.ravel())
+    np.add.at(m1, flat, (g[..., None] * x).reshape(-1, 3))
+    np.add.at(m2, flat, (g[..., None, None] * (x[..., :, None] * x[..., None, :])).reshape(-1, 3, 3))
+
+
+def e_step(points, pi, mu, cov, parent_idx, lvl_nodes=None, w=None):
+    """One tree E-step.  hgmm_cupy_cpu_working.py:162-191 (+accumulate 99-106).  ``w`` [N] >= 0: point i counts as w_i
+    points (hgmm_tree_set_source_weights); the floor is tested on gamma, the arg-max child does not see the weight.
+
+    Returns (m0[T], m1[T,3], m2[T,3,3], current_idx[N], gamma[N,8]).
+    """
+    j0 = child(np.asarray(parent_idx, dtype=np.int64))
+    kid, _, _, _, gamma = child_gamma(points, j0, pi, mu, *node_prep(cov)[1:])
     cur = j0 + np.argmax(gamma, axis=1)
     use = np.where(gamma < EPS, 0.0, gamma)                          # accumulate() skips gamma < eps
-    m0 = np.zeros(T)
-    m1 = np.zeros((T, 3))
-    m2 = np.zeros((T, 3, 3))
-    flat = kid.ravel()
-    np.add.at(m0, flat, use.ravel())
-    np.add.at(m1, flat, (use[:, :, None] * points[:, None, :]).reshape(-1, 3))
-    xx = points[:, :, None] * points[:, None, :]
-    np.add.at(m2, flat, (use[:, :, None, None] * xx[:, None, :, :]).reshape(-1, 3, 3))
-    return m0, m1, m2, cur, gamma
+    if w is not None:
+        use = use * w[:, None]                                       # (1) of the three statements the weights change
+    m = new_moments(len(pi))
+    add_moments(*m, kid, use, points[:, None, :])
+    return (*m, cur, gamma)
 
 
 def m_step(m0, m1, m2, lvl, pi, mu, cov, n_points, ld):
@@ -127,8 +142,8 @@ def m_step(m0, m1, m2, lvl, pi, mu, cov, n_points, ld):
             cov[j] = m2[j] / m0[j] - np.outer(mu[j], mu[j])
 
 
-def log_likelihood(points, pi, mu, cov, lvl, chunk=4096):
-    """q = sum_i log max(sum_{j in level, pi_j >= eps} pi_j N(x_i; j), eps).
+def log_likelihood(points, pi, mu, cov, lvl, chunk=4096, w=None):
+    """q = sum_i [w_i] log max(sum_{j in level, pi_j >= eps} pi_j N(x_i; j), eps).
     hgmm_cupy_cpu_working.py:72-85."""
     lb, le = level(lvl), level(lvl + 1)
     sel = np.arange(lb, le)
@@ -142,15 +157,24 @@ def log_likelihood(points, pi, mu, cov, lvl, chunk=4096):
             tot = (p * pi[sel][None, :]).sum(axis=1)
         else:
             tot = np.zeros(len(x))
-        q += np.log(np.maximum(tot, EPS)).sum()
+        lg = np.log(np.maximum(tot, EPS))
+        q += lg.sum() if w is None else (w[s:s + chunk] * lg).sum()  # (3)
     return q
 
 
-def init_nodes(points, max_level, init_idx, sig2):
-    """pi = 1/8, mu = points[idx], cov = sig2*I  (hgmm_cupy_cpu_working.py:123-136)."""
+def weight_sum(w):
+    """W = sum of the weights in float64, in index order (what the library takes on the host at upload)."""
+    total = 0.0
+    for v in np.asarray(w, dtype=np.float64):
+        total += float(v)
+    return total
+
+
+def init_nodes(points, max_level, init_idx, sig2, init_mu=None):
+    """pi = 1/8, mu = points[idx] (or ``init_mu`` [T,3]), cov = sig2*I  (hgmm_cupy_cpu_working.py:123-136)."""
     T = n_total(max_level)
     pi = np.full(T, 1.0 / N_NODE)
-    mu = np.array(points[np.asarray(init_idx)], dtype=np.float64)
+    mu = np.array(points[np.asarray(init_idx)] if init_mu is None else np.reshape(init_mu, (T, 3)), dtype=np.float64)
     cov = np.tile(np.identity(3) * sig2, (T, 1, 1))
     return pi, mu, cov
 
@@ -158,14 +182,23 @@ def init_nodes(points, max_level, init_idx, sig2):
 BuildTrace = namedtuple('BuildTrace', ['q', 'iters_per_level', 'current_idx_per_level'])
 
 
-def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_level=10000):
+def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_level=10000, w=None, init_mu=None):
     """hgmm_cupy_cpu_working.py:122-160.  RNG stays outside (``init_idx`` explicit; the
-    reference draws ``randint(nTotal, size=nTotal)`` from CuPy's generator).
+    reference draws ``randint(nTotal, size=nTotal)`` from CuPy's generator).  ``init_mu`` [T,3] gives the initial means
+    as coordinates, as the C entry takes them, in place of ``init_idx``.
+
+    ``w`` [n] >= 0 (hgmm_tree_set_source_weights): point i counts as w_i points.  Three statements change, marked
+    (1)-(3): ``use * w`` in :func:`e_step`, ``pi = m0 / W`` here, ``sum w log`` in :func:`log_likelihood`.  ``w = None``
+    runs the unweighted statements themselves.
 
     Returns (pi, mu, cov, trace)."""
     points = np.asarray(points, dtype=np.float64)
-    pi, mu, cov = init_nodes(points, max_level, init_idx, sig2)
-    n = len(points)
+    pi, mu, cov = init_nodes(points, max_level, init_idx, sig2, init_mu)
+    n = n_points = len(points)
+    if w is not None:
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        assert w.shape == (n,)
+        n_points = weight_sum(w)                                     # (2) pi_j = m0_j / W
     parent = -np.ones(n, dtype=np.int64)
     cur = np.zeros(n, dtype=np.int64)
     q_trace, iters, cur_levels = [], [], []
@@ -173,9 +206,9 @@ def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_
         prev_q = 0.0
         it = 0
         while True:
-            m0, m1, m2, cur, _ = e_step(points, pi, mu, cov, parent)
-            m_step(m0, m1, m2, l, pi, mu, cov, n, ld)
-            q = log_likelihood(points, pi, mu, cov, l)
+            m0, m1, m2, cur, _ = e_step(points, pi, mu, cov, parent, w=w)
+            m_step(m0, m1, m2, l, pi, mu, cov, n_points, ld)
+            q = log_likelihood(points, pi, mu, cov, l, w=w)
             q_trace.append(q)
             it += 1
             if abs(q - prev_q) < ls or it >= max_iters_per_level:
@@ -186,6 +219,18 @@ def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_
         parent = cur.copy()
     return pi, mu, cov, BuildTrace(np.array(q_trace), np.array(iters), cur_levels)
 
+
+def stop_margins(q_trace, iters, ls):
+    """||dq| - ls| / ls of every stop decision of a build (dq against 0 at a level's first iteration): how far each
+    decision was from going the other way."""
+    out, at = [], 0
+    for it in iters:
+        prev = 0.0
+        for k in range(int(it)):
+            out.append(abs(abs(q_trace[at + k] - prev) - ls) / ls)
+            prev = q_trace[at + k]
+        at += int(it)
+    return np.array(out)
 
 
 def build_flat_fullcov(points, J, ls, ld, init_idx, sig2=0.00034, max_iters=10000):
@@ -238,46 +283,83 @@ def complexity(cov):
     return lam[..., 0] / lam.sum(axis=-1)
 
 
-def reg_e_step(points, pi, mu, cov, max_level, lc):
-    """Registration E-step: per point descend the tree; at each level normalise gamma over
-    the 8 children of the current node, move to the arg-max child, stop (BEFORE accumulating)
-    when its covariance is 'flat enough', otherwise add (g, g x, g x x^T) to that node.
-    hgmm_cupy_cpu_working.py:202-228.  Returns (m0[T], m1[T,3], m2[T,3,3])."""
-    points = np.asarray(points, dtype=np.float64)
-    T = n_total(max_level)
+def _descend(points, pi, mu, cov, max_level, lc):
+    """THE tree descent of the registration E-step (hgmm_cupy_cpu_working.py:202-228), one level per step: the points still
+    alive normalise gamma over the 8 children of their current node, move to the arg-max child and stop there when its
+    covariance is 'flat enough'.  :func:`reg_e_step` and :func:`reg_descent` are its two consumers and nothing else
+    restates it.  Yields per level (l, idx, x, g, den, good, s, gs, cs, stop):
+      idx [n_l] the points alive at level l, x their coordinates      g [n_l,8], den [n_l], good = den > EPS
+      s the child each moves to, gs its gamma, cs its complexity      stop = cs <= lc"""
+    n = len(points)
     ok, inv, coef = node_prep(cov)
     cplx = complexity(cov)
-    m0 = np.zeros(T)
-    m1 = np.zeros((T, 3))
-    m2 = np.zeros((T, 3, 3))
-    n = len(points)
     search = -np.ones(n, dtype=np.int64)
     alive = np.ones(n, dtype=bool)
-    for _ in range(max_level):
+    for l in range(max_level):
         idx = np.nonzero(alive)[0]
         if len(idx) == 0:
             break
         x = points[idx]
         j0 = child(search[idx])
-        kid = j0[:, None] + np.arange(N_NODE)[None, :]
-        g = pi[kid] * pdf_pairs(x[:, None, :], mu[kid], inv[kid], coef[kid])
-        den = g.sum(axis=1)
-        good = den > EPS
-        gamma = np.where(good[:, None], g / np.where(good, den, 1.0)[:, None], 0.0)
+        _, g, den, good, gamma = child_gamma(x, j0, pi, mu, inv, coef)
         am = np.argmax(gamma, axis=1)
         s = j0 + am
         search[idx] = s
-        stop = cplx[s] <= lc
+        cs = cplx[s]
+        stop = cs <= lc
         alive[idx[stop]] = False
+        yield l, idx, x, g, den, good, s, gamma[np.arange(len(idx)), am], cs, stop
+
+
+GatedEstep = namedtuple('GatedEstep', ['m0', 'm1', 'm2', 'margin', 'pairs', 'gated'])
+
+
+def reg_e_step(points, pi, mu, cov, max_level, lc, w=None, gate=np.inf, report=False):
+    """Registration E-step: descend the tree (:func:`_descend`) and, where a point does not stop, add (g, g x, g x x^T) to
+    the node it moved to; g is its gamma there, 0 below the 1e-15 floor.  hgmm_cupy_cpu_working.py:202-228.
+    Returns (m0[T], m1[T,3], m2[T,3,3]).
+
+    Two options act on a pair that would contribute, in this order, after the floor; neither is seen by the descent, the
+    stop rule or the floor:
+      gate   squared Mahalanobis gate (hgmm_tree_set_reg_gate): the pair counts only if (y - mu_s)^T Sigma_s^-1 (y - mu_s)
+             <= gate; a NaN form fails the comparison.  ``inf`` is OFF, as in the library: no form is evaluated and no
+             comparison is made, so a pair with a NaN form is kept (the earlier gated restatement compared against inf
+             and dropped it; none of the fixtures has such a pair).
+      w      [n] >= 0 (hgmm_tree_set_target_weights): ``g * w_i`` for g.  ``None`` multiplies nothing.
+
+    ``report=True`` returns GatedEstep(m0, m1, m2, margin, pairs, gated) instead:
+      pairs   the (point, node) pairs that contribute without a gate (not stopped, gamma >= 1e-15)
+      gated   how many of them the gate leaves out
+      margin  min |maha2 - gate| / gate over ``pairs`` (inf without pairs or with the gate off): a pair within rounding of
+              the gate may fall on either side in another arithmetic."""
+    points = np.asarray(points, dtype=np.float64)
+    m = new_moments(n_total(max_level))
+    if w is not None:
+        w = np.asarray(w, dtype=np.float64)
+        assert w.shape == (len(points),)
+    inv = node_prep(cov)[1] if np.isfinite(gate) else None
+    margin, pairs, gated = np.inf, 0, 0
+    for _, idx, x, _, _, _, s, gs, _, stop in _descend(points, pi, mu, cov, max_level, lc):
         keep = ~stop
-        gs = gamma[np.arange(len(idx)), am][keep]
+        gs = gs[keep]
         gs = np.where(gs < EPS, 0.0, gs)
         sk = s[keep]
         xk = x[keep]
-        np.add.at(m0, sk, gs)
-        np.add.at(m1, sk, gs[:, None] * xk)
-        np.add.at(m2, sk, gs[:, None, None] * (xk[:, :, None] * xk[:, None, :]))
-    return m0, m1, m2
+        if report:
+            contributes = gs > 0.0
+            pairs += int(contributes.sum())
+        if inv is not None:
+            d = xk - mu[sk]
+            maha2 = np.einsum('...i,...ij,...j->...', d, inv[sk], d)
+            passes = maha2 <= gate
+            if report and contributes.any():
+                gated += int((contributes & ~passes).sum())
+                margin = min(margin, float(np.nanmin(np.abs(maha2[contributes] - gate))) / gate)
+            gs = np.where(passes, gs, 0.0)
+        if w is not None:
+            gs = gs * w[idx][keep]
+        add_moments(*m, sk, gs, xk)
+    return GatedEstep(*m, margin, pairs, gated) if report else m
 
 
 # ---------------------------------------------------------------------------
@@ -325,9 +407,10 @@ def reg_m_step(m0, m1, m2, mu, cov, rot, t):
     return rot, t, q
 
 
-def register(target, pi, mu, cov, max_level, lc=0.01, maxiter=20, tol=1.0e-4):
-    """hgmm_cupy_cpu_working.py:377-391.  Returns (rot_inv, t_inv, q, trace) where
-    (rot_inv, t_inv) is ``tf.inverse()`` as the reference returns it."""
+def register(target, pi, mu, cov, max_level, lc=0.01, maxiter=20, tol=1.0e-4, w=None, gate=np.inf):
+    """hgmm_cupy_cpu_working.py:377-391, THE registration loop; ``w`` and ``gate`` go to :func:`reg_e_step`.
+    Returns (rot_inv, t_inv, q, trace) where (rot_inv, t_inv) is ``tf.inverse()`` as the reference returns it and
+    trace holds per iteration (rot, t, q, m0, m1, m2) of the loop's own pose y = rot x + t (NOT inverted)."""
     target = np.asarray(target, dtype=np.float64)
     rot, t = np.identity(3), np.zeros(3)
     q_prev = None
@@ -335,7 +418,7 @@ def register(target, pi, mu, cov, max_level, lc=0.01, maxiter=20, tol=1.0e-4):
     q = None
     for _ in range(maxiter):
         tt = target @ rot.T + t
-        m0, m1, m2 = reg_e_step(tt, pi, mu, cov, max_level, lc)
+        m0, m1, m2 = reg_e_step(tt, pi, mu, cov, max_level, lc, w, gate)
         rot, t, q = reg_m_step(m0, m1, m2, mu, cov, rot, t)
         trace.append((rot.copy(), t.copy(), np.array(q, copy=True), m0, m1, m2))
         if q_prev is not None and q.size and q_prev.size and abs(q - q_prev) < tol:
@@ -363,39 +446,18 @@ def reg_descent(points, pi, mu, cov, max_level, lc):
       cplx_margin  |complexity(cov_node) - lc| / lc
     A small margin means that a different but equally valid rounding can take the other branch."""
     points = np.asarray(points, dtype=np.float64)
-    n = len(points)
-    ok, inv, coef = node_prep(cov)
-    cplx = complexity(cov)
-    shape = (n, max_level)
+    shape = (len(points), max_level)
     node = -np.ones(shape, dtype=np.int64)
     contrib = np.zeros(shape, dtype=bool)
     gap, den_m, gam_m, cplx_m = (np.full(shape, np.inf) for _ in range(4))
-    search = -np.ones(n, dtype=np.int64)
-    alive = np.ones(n, dtype=bool)
-    for l in range(max_level):
-        idx = np.nonzero(alive)[0]
-        if len(idx) == 0:
-            break
-        x = points[idx]
-        j0 = child(search[idx])
-        kid = j0[:, None] + np.arange(N_NODE)[None, :]
-        g = pi[kid] * pdf_pairs(x[:, None, :], mu[kid], inv[kid], coef[kid])
-        den = g.sum(axis=1)
-        good = den > EPS
-        gamma = np.where(good[:, None], g / np.where(good, den, 1.0)[:, None], 0.0)
-        am = np.argmax(gamma, axis=1)
-        s = j0 + am
+    for l, idx, _, g, den, good, s, gs, cs, stop in _descend(points, pi, mu, cov, max_level, lc):
         top2 = np.sort(g, axis=1)[:, -2:]
         gap[idx, l] = np.where(good, (top2[:, 1] - top2[:, 0]) / np.where(good, top2[:, 1], 1.0), np.inf)
         den_m[idx, l] = np.abs(den - EPS) / EPS
-        cplx_m[idx, l] = np.abs(cplx[s] - lc) / lc
+        cplx_m[idx, l] = np.abs(cs - lc) / lc
         node[idx, l] = s
-        search[idx] = s
-        stop = cplx[s] <= lc
-        gs = gamma[np.arange(len(idx)), am]
         gam_m[idx, l] = np.where(stop, np.inf, np.abs(gs - EPS) / EPS)
         contrib[idx, l] = ~stop & ~(gs < EPS)
-        alive[idx[stop]] = False
     return RegDescent(node, contrib, gap, den_m, gam_m, cplx_m)
 
 

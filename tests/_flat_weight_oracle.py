@@ -15,6 +15,8 @@ import numpy as np
 
 from oracle import flat_em
 
+from _tree_helpers import weights_for
+
 
 def weight_sum(s):
     """S: a float64 sum, in index order, of the float32 values the device holds."""
@@ -76,9 +78,5 @@ def train(X, s, max_iter, tol, mu, cov, w, cov_type='diag', variant='W'):
 
 
 def standard_weights(n, seed=11):
-    """The suites' standard weights (tests/test_tree_source_weights_gpu.py: weights_for): uniform in [0.25, 4), one in ten
-    exactly zero -- as the float32 values the flat entry takes."""
-    rs = np.random.RandomState(seed)
-    w = rs.uniform(0.25, 4.0, n)
-    w[rs.uniform(size=n) < 0.1] = 0.0
-    return w.astype(np.float32)
+    """The suites' standard weights (tests/_tree_helpers.py: weights_for) as the float32 values the flat entry takes."""
+    return weights_for(n, seed).astype(np.float32)

@@ -2,7 +2,7 @@
 
 With a finite gate a (point, node) pair that would contribute to the node's moments does so only if its squared Mahalanobis
 distance to the node is <= the gate; the descent is untouched.  The checks: the gated E-step and the gated loop against the
-NumPy restatement (tests/_gate_oracle.py) at the bounds of the ungated tests; off is off and the gated kernels add exactly
+float64 oracle (oracle.hgmm_tree.reg_e_step / register with gate=) at the bounds of the ungated tests; off is off and the gated kernels add exactly
 what the ungated ones add (bitwise); the batched and multi-start launches are bitwise the serial gated call; on the
 project's real scan pair with clutter the gate brings the result closer to the ground truth; errors and state.
 
@@ -15,8 +15,6 @@ import pytest
 
 from conftest import GOLDEN, load_golden
 from oracle import hgmm_tree
-
-import _gate_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -74,7 +72,7 @@ def test_gated_estep_matches_the_restatement(ctx, records, L, deg, gate):
     X = g["rot%d_target" % deg]
     _, lc, T = resident(ctx, g, X)
     assert not hgmm_tree.reg_near_ties(hgmm_tree.reg_descent(X, g["pi"], g["mu"], g["cov"], L, lc)).any()
-    o = _gate_oracle.gated_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate)
+    o = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate=gate, report=True)
     print("L=%d rot%d gate %g: %d of %d contributing pairs gated, margin %.3g" % (L, deg, gate, o.gated, o.pairs, o.margin))
     assert o.margin > 1e-9 and 0 < o.gated < o.pairs
     ctx.tree_set_reg_gate(gate)
@@ -105,12 +103,13 @@ def test_gated_loop_matches_the_restatement(ctx, records, L, deg, gate):
     finally:
         ctx.tree_set_reg_gate(np.inf)
     assert done == 5 and status == 0
-    o_rot, o_t, o_tr = _gate_oracle.gated_register(X, g["pi"], g["mu"], g["cov"], L, lc, gate, 5, 0.0)
+    o_tr = hgmm_tree.register(X, g["pi"], g["mu"], g["cov"], L, lc, 5, 0.0, gate=gate)[3]
     assert len(o_tr) == 5
+    o_rot, o_t = o_tr[-1][:2]                    # the loop's own final pose (register returns its inverse)
     r_prev, t_prev = I3, np.zeros(3)
     margins = []
     for k in range(5):
-        e = _gate_oracle.gated_reg_e_step(X @ r_prev.T + t_prev, g["pi"], g["mu"], g["cov"], L, lc, gate)
+        e = hgmm_tree.reg_e_step(X @ r_prev.T + t_prev, g["pi"], g["mu"], g["cov"], L, lc, gate=gate, report=True)
         margins.append(e.margin)
         assert e.margin > 1e-9 and e.gated > 0, k
         r_k, t_k = trace[k, :9].reshape(3, 3), trace[k, 9:12]

@@ -1,7 +1,7 @@
 """Per-point weights of the SOURCE cloud in the tree build (hgmm_tree_set_source_weights), the parts that need no GPU: the
-NumPy restatement the GPU tests compare against (tests/_source_weight_oracle.py) is the pinned oracle's build of the cloud
-with its points repeated when the weights are integers, is the oracle bit for bit without weights, and scales exactly with
-w == 2; the mirrors refuse bad weights before they touch the library, upload the cloud before its weights, and a
+weighted build the GPU tests compare against (oracle.hgmm_tree.build_tree(w=...)) is the pinned unweighted build of the
+cloud with its points repeated when the weights are integers, is the unweighted build bit for bit with unit weights, and
+scales exactly with w == 2; the mirrors refuse bad weights before they touch the library, upload the cloud before its weights, and a
 WeightedPoints source brings its weights; the two C entries are declared, exported and bound."""
 import inspect
 import os
@@ -12,8 +12,6 @@ import pytest
 
 from conftest import ROOT
 from oracle import hgmm_tree
-
-import _source_weight_oracle as swo
 
 LS, LD, SIG2 = 20.0, 1e-4, 0.004
 CASES = {700: 2, 3000: 3}           # points -> tree levels
@@ -35,13 +33,18 @@ def draw(bunny, n, L):
     return draw_cases(bunny)[n]
 
 
+def wbuild(X, L, ls, ld, init_mu, w, **kw):
+    """the oracle's build as the C entry is called: initial means as coordinates, weights ``w`` (None: none)"""
+    return hgmm_tree.build_tree(X, L, ls, ld, None, SIG2, w=w, init_mu=init_mu, **kw)
+
+
 @pytest.fixture(scope="module")
 def builds(bunny):
-    """the restatement's weighted build of every case, computed once"""
+    """the weighted build of every case, computed once"""
     out = {}
     for n, L in CASES.items():
         X, c, idx = draw(bunny, n, L)
-        out[n] = (X, c, idx, swo.weighted_build_tree(X, L, LS, LD, X[idx], SIG2, c.astype(np.float64)))
+        out[n] = (X, c, idx, wbuild(X, L, LS, LD, X[idx], c.astype(np.float64)))
     return out
 
 
@@ -54,7 +57,7 @@ def test_restatement_is_the_pinned_oracle_on_the_repeated_cloud(builds, n):
     X, c, idx, (pi, mu, cov, tr) = builds[n]
     first = np.cumsum(c) - c                                          # the first copy of point i in the repeated cloud
     o_pi, o_mu, o_cov, o_tr = hgmm_tree.build_tree(np.repeat(X, c, axis=0), L, LS, LD, first[idx], SIG2)
-    margin = swo.stop_margins(o_tr.q, o_tr.iters_per_level, LS)
+    margin = hgmm_tree.stop_margins(o_tr.q, o_tr.iters_per_level, LS)
     dead = int((o_pi == 0.0).sum())
     print("n=%d L=%d: iterations %s / %s, smallest stop margin %.3g, %d dead nodes" %
           (n, L, list(tr.iters_per_level), list(o_tr.iters_per_level), margin.min(), dead))
@@ -75,11 +78,15 @@ def test_restatement_is_the_pinned_oracle_on_the_repeated_cloud(builds, n):
 
 @pytest.mark.parametrize("n", sorted(CASES))
 def test_restatement_without_weights_and_with_unit_weights_is_the_oracle_bit_for_bit(bunny, n):
+    """There is one build: ``w = None`` with the means given as indices is the reference.  Against it, bit for bit, the
+    means given as coordinates (the other initialisation) and ``w = ones``, which runs the three weighted statements --
+    the multiply, W as an index-order sum and the weighted log-likelihood sum."""
     L = CASES[n]
     X, _, idx = draw(bunny, n, L)
     ref = hgmm_tree.build_tree(X, L, LS, LD, idx, SIG2)
+    assert hgmm_tree.weight_sum(np.ones(n)) == n
     for w in (None, np.ones(n)):
-        got = swo.weighted_build_tree(X, L, LS, LD, X[idx], SIG2, w)
+        got = wbuild(X, L, LS, LD, X[idx], w)
         for a, b in zip(ref[:3], got[:3]):
             assert np.array_equal(a, b)
         assert np.array_equal(ref[3].q, got[3].q) and list(ref[3].iters_per_level) == list(got[3].iters_per_level)
@@ -92,8 +99,8 @@ def test_restatement_scales_exactly_with_a_weight_of_two(bunny, n):
     a scale by a power of two commutes with every product, sum, comparison and quotient of the build"""
     L = CASES[n]
     X, _, idx = draw(bunny, n, L)
-    ref = swo.weighted_build_tree(X, L, LS, LD, X[idx], SIG2, None)
-    got = swo.weighted_build_tree(X, L, 2 * LS, 2 * LD, X[idx], SIG2, np.full(n, 2.0))
+    ref = wbuild(X, L, LS, LD, X[idx], None)
+    got = wbuild(X, L, 2 * LS, 2 * LD, X[idx], np.full(n, 2.0))
     for a, b in zip(ref[:3], got[:3]):
         assert np.array_equal(a, b)
     assert list(ref[3].iters_per_level) == list(got[3].iters_per_level)
@@ -104,8 +111,8 @@ def test_a_zero_weight_is_an_absent_point_in_the_restatement(bunny):
     X, c, idx = draw(bunny, 700, 2)
     w = c.astype(np.float64)
     extra = np.r_[X[:30] + 1e-3, X[:30] + 10.0]                       # inside the cloud, and where every pdf underflows
-    a = swo.weighted_build_tree(X, 2, 0.0, LD, X[idx], SIG2, w, max_iters_per_level=4)
-    b = swo.weighted_build_tree(np.r_[X, extra], 2, 0.0, LD, X[idx], SIG2, np.r_[w, np.zeros(60)], max_iters_per_level=4)
+    a = wbuild(X, 2, 0.0, LD, X[idx], w, max_iters_per_level=4)
+    b = wbuild(np.r_[X, extra], 2, 0.0, LD, X[idx], np.r_[w, np.zeros(60)], max_iters_per_level=4)
     for u, v in zip(a[:3], b[:3]):
         np.testing.assert_allclose(u, v, rtol=1e-12, atol=1e-15)
     np.testing.assert_allclose(a[3].q, b[3].q, rtol=1e-12)

@@ -2,7 +2,7 @@
 
 A source point i with weight w_i >= 0 counts as w_i points: the moments are sum w gamma (1, x, x x^T), pi = m0 / sum w and a
 level's log-likelihood is sum w log(...); the partition and the 1e-15 floor do not see the weight.  The checks: the weighted
-build against the NumPy restatement (tests/_source_weight_oracle.py) at the bounds the unweighted build is held to against
+build against the float64 oracle (oracle.hgmm_tree.build_tree(w=...)) at the bounds the unweighted build is held to against
 its oracle (tests/test_tree_gpu.py), on every driver path and in both precisions; w == 1 bitwise the unweighted build,
 w == 2 with doubled ls / ld bitwise the unweighted tables with twice the q trace, NULL and a new cloud take the weights off;
 integer weights are repetition; a zero weight is an absent point; a forest's members are bitwise their serial weighted
@@ -20,7 +20,7 @@ import pytest
 from conftest import GOLDEN
 from oracle import hgmm_tree
 
-import _source_weight_oracle as swo
+from _tree_helpers import weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -36,14 +36,6 @@ def ctx():
     c = hgmm_amd.Context(0)
     yield c
     c.close()
-
-
-def weights_for(n, seed=11):
-    """the tests' weights unless stated otherwise: uniform in [0.25, 4), one in ten exactly zero"""
-    rs = np.random.RandomState(seed)
-    w = rs.uniform(0.25, 4.0, n)
-    w[rs.uniform(size=n) < 0.1] = 0.0
-    return w
 
 
 def small_cloud(bunny, n, L, seed=5):
@@ -108,8 +100,8 @@ def restated(bunny):
     for case, (n, L, budget) in RESTATED.items():
         X, init_mu = small_cloud(bunny, n, L)
         w = weights_for(n)
-        pi, mu, cov, tr = swo.weighted_build_tree(X, L, LS, LD, init_mu, SIG2, w, max_iters_per_level=budget)
-        margin = swo.stop_margins(tr.q, tr.iters_per_level, LS)
+        pi, mu, cov, tr = hgmm_tree.build_tree(X, L, LS, LD, None, SIG2, budget, w=w, init_mu=init_mu)
+        margin = hgmm_tree.stop_margins(tr.q, tr.iters_per_level, LS)
         print("%s: iterations %s, smallest stop margin %.3g, %d dead nodes" % (case, list(tr.iters_per_level), margin.min(),
                                                                              int((pi == 0).sum())))
         assert margin.min() > 1e-6, case                              # (no stop decision within reach of rounding: else another seed)

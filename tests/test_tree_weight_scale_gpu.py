@@ -27,9 +27,7 @@ import pytest
 from conftest import load_golden
 from oracle import hgmm_tree
 
-import _gate_oracle
-import _weight_oracle
-from _weight_oracle import I3, loop5, resident, weights_for
+from _tree_helpers import I3, loop5, resident, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -75,7 +73,7 @@ def preconditions(records):
         assert not seen[L]
         if np.isfinite(gate):
             if (L, gate) not in seen:
-                seen[L, gate] = _gate_oracle.gated_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate).margin
+                seen[L, gate] = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate=gate, report=True).margin
             assert seen[L, gate] > 1e-9
     return check
 
@@ -178,7 +176,7 @@ def test_scaled_weights_match_the_restatement(ctx, records, gated, preconditions
     _, lc, T = resident(ctx, g, X, wc)
     gated(gate)
     m = ctx.tree_reg_estep(T, None, None, 1.0, lc)
-    o = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, wc, gate)
+    o = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, wc, gate)
     label = "L=%d gate %g c = %s (sum %.17g, F = %d)" % (L, gate, scale, index_sum(wc), frac_bits(index_sum(wc)))
     assert_moments_at_scale(m, o, c, label)
 
@@ -213,7 +211,7 @@ def test_sum_of_the_weights_on_a_step_of_f(ctx, records, preconditions, L, m, si
     _, lc, T = resident(ctx, g, X, w)
     assert ctx.tree_score(None, None, 1.0, lc, want=())[0][0] == total          # (the library's own sum: slot 0)
     mom = ctx.tree_reg_estep(T, None, None, 1.0, lc)
-    o = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w)
+    o = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w)
     assert_moments_at_scale(mom, o, c, "L=%d sum %s, m = %d (F = %d)" % (L, side, m, frac_bits(total)))
 
 
@@ -316,7 +314,7 @@ def test_loop_under_scaled_weights_matches_the_restatement(ctx, records, L, deg,
     _, lc, T = resident(ctx, g, X, wc)
     rot, t, done, q, status, trace = loop5(ctx, lc)
     assert done == 5 and status == 0
-    o_tr = _weight_oracle.weighted_register(X, g["pi"], g["mu"], g["cov"], L, lc, 5, 0.0, wc)[3]
+    o_tr = hgmm_tree.register(X, g["pi"], g["mu"], g["cov"], L, lc, 5, 0.0, wc)[3]
     assert len(o_tr) == 5
     eps32 = hgmm_tree.F32_EPS
     live = [int((~(it[3] < eps32)).sum()) for it in o_tr]

@@ -1,7 +1,8 @@
-"""Per-point weights of the registration target (hgmm_tree_set_target_weights), the parts that need no GPU: the NumPy
-restatement the GPU tests compare against (tests/_weight_oracle.py) is the oracle's E-step when every weight is 1 and the
-E-step of a cloud with its points repeated when the weights are integers; voxel_down_sample hands out the counts; the
-mirrors refuse bad weights before they touch the library; the two C entries are declared, exported and bound."""
+"""Per-point weights of the registration target (hgmm_tree_set_target_weights), the parts that need no GPU: the
+float64 E-step the GPU tests compare against (oracle.hgmm_tree.reg_e_step(w=...)) is the unweighted E-step bit for bit
+when every weight is 1 and the E-step of a cloud with its points repeated when the weights are integers;
+voxel_down_sample hands out the counts; the mirrors refuse bad weights before they touch the library; the two C entries
+are declared, exported and bound."""
 import inspect
 import os
 import re
@@ -12,8 +13,6 @@ import pytest
 from conftest import ROOT, load_golden
 from oracle import hgmm_tree
 
-import _weight_oracle
-
 
 @pytest.fixture(scope="module")
 def records():
@@ -22,22 +21,23 @@ def records():
 
 @pytest.mark.parametrize("L", [2, 4])
 def test_restatement_with_unit_weights_is_the_oracle_bit_for_bit(records, L):
+    """``w = None`` runs the unweighted statements themselves and is the reference; ``w = ones`` runs the multiply and must
+    change no bit, in the E-step and along the register loop (the build: tests/test_tree_source_weights_cpu.py)."""
     g = records[L]
-    lc = float(g["lambda_c"])
+    tree = (g["pi"], g["mu"], g["cov"], L, float(g["lambda_c"]))
     for deg in (10, 30):
         X = g["rot%d_target" % deg]
-        ref = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc)
-        for w in (None, np.ones(len(X))):
-            got = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w)
-            for a, b in zip(ref, got):
-                assert np.array_equal(a, b)
-    # the loop around it: oracle.hgmm_tree.register's trajectory
+        ref = hgmm_tree.reg_e_step(X, *tree)
+        got = hgmm_tree.reg_e_step(X, *tree, np.ones(len(X)))
+        for a, b in zip(ref, got):
+            assert np.array_equal(a, b)
+    # the loop around it
     X = g["rot10_target"]
-    o_rot, o_t, o_q, o_tr = hgmm_tree.register(X, g["pi"], g["mu"], g["cov"], L, lc, 3, 1e-4)
-    rot, t, q, tr = _weight_oracle.weighted_register(X, g["pi"], g["mu"], g["cov"], L, lc, 3, 1e-4, np.ones(len(X)))
-    assert len(tr) == len(o_tr) and np.array_equal(rot, o_rot) and np.array_equal(t, o_t)
+    o_rot, o_t, o_q, o_tr = hgmm_tree.register(X, *tree, 3, 1e-4)
+    rot, t, q, tr = hgmm_tree.register(X, *tree, 3, 1e-4, np.ones(len(X)))
+    assert len(tr) == len(o_tr) and np.array_equal(rot, o_rot) and np.array_equal(t, o_t) and np.array_equal(q, o_q)
     for a, b in zip(tr, o_tr):
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        assert all(np.array_equal(u, v) for u, v in zip(a, b))
 
 
 @pytest.mark.parametrize("L", [2, 4])
@@ -50,7 +50,7 @@ def test_integer_weights_are_repeated_points(records, L):
     X = g["rot10_target"]
     k = np.random.RandomState(11).randint(0, 4, len(X))
     assert (k == 0).sum() > 400 and (k == 3).sum() > 400
-    got = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, k.astype(np.float64))
+    got = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, k.astype(np.float64))
     ref = hgmm_tree.reg_e_step(np.repeat(X, k, axis=0), g["pi"], g["mu"], g["cov"], L, lc)
     for name, a, b in zip(("m0", "m1", "m2"), got, ref):
         err = np.abs(a - b).max() / np.abs(b).max()
@@ -60,17 +60,16 @@ def test_integer_weights_are_repeated_points(records, L):
 
 def test_gate_and_weights_compose_in_the_restatement(records):
     """the gate decides on the pair, the weight scales what passes: a 0/1 weight is a point left out"""
-    import _gate_oracle
     g = records[2]
     L, lc = 2, float(g["lambda_c"])
     X = g["rot10_target"]
-    e = _gate_oracle.gated_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, 16.0)
-    got = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, np.ones(len(X)), 16.0)
+    e = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate=16.0, report=True)
+    got = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, np.ones(len(X)), 16.0)
     for a, b in zip((e.m0, e.m1, e.m2), got):
         assert np.array_equal(a, b)
     keep = np.random.RandomState(3).uniform(size=len(X)) < 0.7
-    sub = _weight_oracle.weighted_reg_e_step(X[keep], g["pi"], g["mu"], g["cov"], L, lc, None, 16.0)
-    got = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, keep.astype(np.float64), 16.0)
+    sub = hgmm_tree.reg_e_step(X[keep], g["pi"], g["mu"], g["cov"], L, lc, None, 16.0)
+    got = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, keep.astype(np.float64), 16.0)
     for a, b in zip(sub, got):
         np.testing.assert_allclose(a, b, rtol=0, atol=1e-12 * np.abs(b).max())
 

@@ -1,9 +1,9 @@
 """Per-point weights of the registration target (hgmm_tree_set_target_weights[_batch]) on the GPU.
 
 A target point i with weight w_i >= 0 adds w_i * gamma where it added gamma; the descent, the stop rule, the 1e-15 floor
-and the gate do not see the weight.  The checks: the weighted E-step and the weighted loop against the NumPy restatement
-(tests/_weight_oracle.py) at the bounds of the unweighted and gated tests; w == 1 is bitwise the unweighted result on every
-entry, w == 2 exactly twice the moments, NULL and a new target take the weights off; a zero weight is an absent point; the
+and the gate do not see the weight.  The checks: the weighted E-step and the weighted loop against the float64 oracle
+(oracle.hgmm_tree.reg_e_step / register with w=) at the bounds of the unweighted and gated tests; w == 1 is bitwise the
+unweighted result on every entry, w == 2 exactly twice the moments, NULL and a new target take the weights off; a zero weight is an absent point; the
 batched and multi-start launches are bitwise the serial weighted call; the score's sums are the weighted sums of its own
 per-point arrays, and the batched and multi-start scores take each member's chunk count and weight sum from its own table
 entry; on the project's real scan pair the count-weighted voxel centroids reach the full scan's pose; errors and state;
@@ -21,9 +21,7 @@ import pytest
 from conftest import GOLDEN, load_golden
 from oracle import hgmm_tree
 
-import _gate_oracle
-import _weight_oracle
-from _weight_oracle import loop5, resident, same_bits, weights_for
+from _tree_helpers import loop5, resident, same_bits, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -78,8 +76,8 @@ def test_weighted_estep_matches_the_restatement(ctx, records, gated, L, deg, gat
     _, lc, T = resident(ctx, g, X, w)
     assert not hgmm_tree.reg_near_ties(hgmm_tree.reg_descent(X, g["pi"], g["mu"], g["cov"], L, lc)).any()
     if np.isfinite(gate):
-        assert _gate_oracle.gated_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate).margin > 1e-9
-    o = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w, gate)
+        assert hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, gate=gate, report=True).margin > 1e-9
+    o = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w, gate)
     gated(gate)
     m = ctx.tree_reg_estep(T, None, None, 1.0, lc)
     for name, a, b in zip(("m0", "m1", "m2"), m, o):
@@ -106,7 +104,7 @@ def test_weighted_loop_matches_the_restatement(ctx, records, gated, L, deg, gate
     gated(gate)
     rot, t, done, q, status, trace = loop5(ctx, lc)
     assert done == 5 and status == 0
-    o_rot_inv, o_t_inv, o_q, o_tr = _weight_oracle.weighted_register(X, g["pi"], g["mu"], g["cov"], L, lc, 5, 0.0, w, gate)
+    o_rot_inv, o_t_inv, o_q, o_tr = hgmm_tree.register(X, g["pi"], g["mu"], g["cov"], L, lc, 5, 0.0, w, gate)
     assert len(o_tr) == 5
     worst = 0.0
     for k in range(5):
@@ -235,8 +233,8 @@ def test_zero_weight_is_an_absent_point(ctx, records, L):
     full = ctx.tree_reg_estep(T, None, None, 1.0, lc)
     resident(ctx, g, X[pos], w[pos])
     sub = ctx.tree_reg_estep(T, None, None, 1.0, lc)
-    o = _weight_oracle.weighted_reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w)
-    o_sub = _weight_oracle.weighted_reg_e_step(X[pos], g["pi"], g["mu"], g["cov"], L, lc, w[pos])
+    o = hgmm_tree.reg_e_step(X, g["pi"], g["mu"], g["cov"], L, lc, w)
+    o_sub = hgmm_tree.reg_e_step(X[pos], g["pi"], g["mu"], g["cov"], L, lc, w[pos])
     for k in range(3):
         np.testing.assert_allclose(full[k], sub[k], rtol=1e-10, atol=1e-12)
         np.testing.assert_allclose(full[k], o[k], rtol=1e-10, atol=1e-12)
@@ -549,7 +547,7 @@ def test_status_2_host_fallback_follows_the_resident_weights(ctx, records):
     gt._device_mstep = False                                           # every iteration through expectation_step + maximization_step
     res = gt.registration(X, 3, 0.0, weights=w)
     tf = res.transformation.inverse()
-    o_tr = _weight_oracle.weighted_register(X, g["pi"], g["mu"], g["cov"], L, lc, 3, 0.0, w)[3]
+    o_tr = hgmm_tree.register(X, g["pi"], g["mu"], g["cov"], L, lc, 3, 0.0, w)[3]
     np.testing.assert_allclose(np.asarray(tf.rot), o_tr[2][0], rtol=0, atol=1e-8)
     np.testing.assert_allclose(np.asarray(tf.t), o_tr[2][1], rtol=0, atol=1e-8)
     free = hgmm_tree.register(X, g["pi"], g["mu"], g["cov"], L, lc, 3, 0.0)[3]

@@ -6,7 +6,7 @@
 Accuracy: bun000's tree (L = 3, product defaults) <- bun045 placed by bun_conf.npz and moved by 8 deg / 5 mm (the scan pair
 of tests/test_tree_gpu.py), as it is and with 10 % / 30 % uniform clutter in its bounding box; maxiter 30, tol 1e-6; gates
 inf, 25, 16, 9.  The figure is the mean distance of the registered scan (clutter left out) from its ground-truth placement.
-``--oracle`` adds the NumPy column (tests/_gate_oracle.py on oracle.build_tree's tree; minutes of CPU time).
+``--oracle`` adds the NumPy column (oracle.hgmm_tree.register(gate=) on oracle.build_tree's tree; minutes of CPU time).
 Cost: hipEvent time per launch (hgmm_profile_*, kernel id tree_reg) of the E-step kernel through hgmm_tree_reg_normal with the
 gate off and at 16 on the same context, tree, target and pose -- bun045-sized target, L = 3 and L = 5: median of 7 samples
 of 10 launches after a warm-up -- and of the batched E-step of 32 pairs (L = 5, 10 iterations, tol 0)."""
@@ -17,7 +17,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 LC = 0.01
@@ -77,7 +76,6 @@ def accuracy_gpu(ctx):
 
 def accuracy_oracle():
     from oracle import hgmm_tree
-    import _gate_oracle
     a, world, moved = scan_pair()
     T = hgmm_tree.n_total(3)
     idx = np.random.RandomState(72).randint(T, size=T)
@@ -86,8 +84,8 @@ def accuracy_oracle():
     for frac in CLUTTER:
         target = with_clutter(moved, frac)
         for gate in GATES:
-            rot, t, trace = _gate_oracle.gated_register(target, pi, mu, cov, 3, LC, gate, 30, 1e-6)
-            rows[frac, gate] = (error_mm(moved, world, rot, t), len(trace))
+            trace = hgmm_tree.register(target, pi, mu, cov, 3, LC, 30, 1e-6, gate=gate)[3]
+            rows[frac, gate] = (error_mm(moved, world, *trace[-1][:2]), len(trace))
             print("   oracle: clutter %3.0f %%, gate %4g: %.2f mm after %d iterations" % (100 * frac, gate, *rows[frac, gate]),
                   flush=True)
     return rows
@@ -176,7 +174,7 @@ def main():
             cost_batch(ctx)
         ctx.close()
     if "--oracle" in sys.argv:
-        print_table(accuracy_oracle(), "oracle (tests/_gate_oracle.py):")
+        print_table(accuracy_oracle(), "oracle (oracle.hgmm_tree.register(gate=)):")
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ of tools/gate_probe.py); maxiter 30, tol 1e-6.  The target is reduced three ways
 (pointcloud_io.voxel_down_sample), and the half of the scan below its median x thinned to every eighth point -- and
 registered without weights and with them (the voxel counts; 8 for a kept point of the thinned half, 1 elsewhere).  The
 figure is the mean distance (mm) between the full scan at the pose the reduced target gives and at the pose the full
-40 097-point target gives.  ``--oracle`` adds the NumPy column (tests/_weight_oracle.py on oracle.build_tree's tree;
+40 097-point target gives.  ``--oracle`` adds the NumPy column (oracle.hgmm_tree.register(w=) on oracle.build_tree's tree;
 minutes of CPU time).
 Cost: hipEvent time per launch (hgmm_profile_*, kernel id tree_reg) of the E-step kernel through hgmm_tree_reg_normal without
 and with weights (uniform in [0.25, 4): no point is skipped) on the same context, tree, target and pose -- the 40 097-point
@@ -21,7 +21,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from gate_probe import GOLDEN, LC, launch_us, rot_about, scan_pair       # noqa: E402
@@ -69,14 +68,13 @@ def accuracy_gpu(ctx):
 
 def accuracy_oracle():
     from oracle import hgmm_tree
-    import _weight_oracle
     a, world, moved = scan_pair()
     T = hgmm_tree.n_total(3)
     idx = np.random.RandomState(72).randint(T, size=T)
     pi, mu, cov, _ = hgmm_tree.build_tree(a, 3, 20, 1e-4, idx, 0.004)
 
     def run(target, w=None):
-        tr = _weight_oracle.weighted_register(target, pi, mu, cov, 3, LC, 30, 1e-6, w)[3]
+        tr = hgmm_tree.register(target, pi, mu, cov, 3, LC, 30, 1e-6, w)[3]
         return (tr[-1][0], tr[-1][1]), len(tr)
 
     full, it_full = run(moved)
@@ -164,7 +162,7 @@ def main():
             cost_batch(ctx)
         ctx.close()
     if "--oracle" in sys.argv:
-        print_table(*accuracy_oracle(), "oracle (tests/_weight_oracle.py):")
+        print_table(*accuracy_oracle(), "oracle (oracle.hgmm_tree.register(w=)):")
 
 
 if __name__ == "__main__":
