@@ -173,6 +173,16 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_voxel_downsample_batch_f64", [ctx, C.c_int, C.POINTER(_vp), _i64p, C.c_double, _i64p])
         _sig(lib, "hgmm_voxel_downsample_batch_f32", [ctx, C.c_int, C.POINTER(_vp), _i64p, C.c_double, _i64p])
         _sig(lib, "hgmm_voxel_downsample_get", [ctx, _vp, _vp])
+        _sig(lib, "hgmm_voxel_result_info", [ctx, C.POINTER(C.c_int), _i64p, _i64p, C.POINTER(C.c_uint64)])
+        _sig(lib, "hgmm_voxel_to_points", [ctx, C.c_int, C.c_int])
+        _sig(lib, "hgmm_voxel_to_target", [ctx, C.c_int, C.c_int])
+        _sig(lib, "hgmm_voxel_to_points_batch", [ctx, C.c_int, _i32p, C.c_int])
+        _sig(lib, "hgmm_voxel_to_targets_batch", [ctx, C.c_int, _i32p, C.c_int])
+        _sig(lib, "hgmm_points_rows_f64", [ctx, _vp, C.c_int64, _vp])
+        _sig(lib, "hgmm_tree_build_rows", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)])
+        _sig(lib, "hgmm_tree_build_batch_rows", [ctx, C.c_int, _i64p, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int,
+                                                 _vp, _vp, _vp, _vp, _vp, C.c_int, _vp])
         _lib = lib
         return lib
 
@@ -953,14 +963,25 @@ class Context:
         return self
 
     # -- HGMM ---------------------------------------------------------------------------
-    def tree_build(self, L, ls, ld, init_mu, sig2, max_iters_per_level=1000, q_capacity=None, want_leaf=True):
+    def tree_build(self, L, ls, ld, init_mu, sig2, max_iters_per_level=1000, q_capacity=None, want_leaf=True, init_rows=None):
         """``want_leaf=False``: the node tables only, like the reference's buildGMMTree (hgmm_gpu.py:466-548 returns the
         nodes; its currentIdx stays on the device) -- the N-long leaf assignment is neither un-sorted nor downloaded
-        (4 MB per million points through pageable memory: 0.4 ms)."""
+        (4 MB per million points through pageable memory: 0.4 ms).
+        ``init_rows`` [T] (with ``init_mu=None``): the initial means are these rows of the resident cloud's float64 view,
+        gathered on the device (hgmm_tree_build_rows) -- bit for bit ``init_mu=cloud[init_rows]``."""
         T = 8 * (8 ** L - 1) // 7
-        init_mu = np.ascontiguousarray(init_mu, dtype=np.float64)
-        if init_mu.shape != (T, 3):
-            raise ValueError("init_mu must be [%d,3]" % T)
+        if (init_mu is None) == (init_rows is None):
+            raise ValueError("tree_build takes init_mu or init_rows, one of the two")
+        if init_rows is not None:
+            init_mu = np.ascontiguousarray(init_rows, dtype=np.int64)
+            if init_mu.shape != (T,):
+                raise ValueError("init_rows must be [%d]" % T)
+            entry = self.lib.hgmm_tree_build_rows
+        else:
+            init_mu = np.ascontiguousarray(init_mu, dtype=np.float64)
+            if init_mu.shape != (T, 3):
+                raise ValueError("init_mu must be [%d,3]" % T)
+            entry = self.lib.hgmm_tree_build
         n = self.num_points
         pi = np.empty(T)
         mu = np.empty((T, 3))
@@ -970,9 +991,9 @@ class Context:
         qcap = int(q_capacity or L * max_iters_per_level)
         q = np.zeros(qcap)
         qlen = C.c_int()
-        self._check(self.lib.hgmm_tree_build(self.h, int(L), float(ls), float(ld), _ptr(init_mu), float(sig2),
-                                             int(max_iters_per_level), _ptr(pi), _ptr(mu), _ptr(cov), _ptr(leaf),
-                                             _ptr(iters), _ptr(q), qcap, C.byref(qlen)))
+        self._check(entry(self.h, int(L), float(ls), float(ld), _ptr(init_mu), float(sig2),
+                          int(max_iters_per_level), _ptr(pi), _ptr(mu), _ptr(cov), _ptr(leaf),
+                          _ptr(iters), _ptr(q), qcap, C.byref(qlen)))
         return pi, mu, cov, leaf, iters, q[:qlen.value].copy()
 
     def tree_set_precision(self, dtype):
@@ -1140,15 +1161,29 @@ class Context:
         return self._set_weights_batch(self.lib.hgmm_tree_set_source_weights_batch, weights, getattr(self, "_batch_counts", None))
 
     def tree_build_batch(self, counts, L, ls, ld, init_mu, sig2, max_iters_per_level=1000, want_tables=True,
-                         want_trace=False, q_capacity=None):
+                         want_trace=False, q_capacity=None, init_rows=None):
         """``B = len(counts)`` trees on the resident cloud's consecutive pieces in the same launches (hgmm_tree_build_batch);
-        each bitwise what :meth:`tree_build` gives for that piece alone.  ``init_mu`` [B,T,3].
+        each bitwise what :meth:`tree_build` gives for that piece alone.  ``init_mu`` [B,T,3], or ``init_mu=None`` and
+        ``init_rows`` [B,T] (or [T], the same for every cloud): row numbers within each cloud, gathered on the device
+        (hgmm_tree_build_batch_rows).
         -> (pi [B,T], mu [B,T,3], cov [B,T,3,3]) or (None, None, None), iters [B,L], list of q traces or None."""
         B = len(counts)
         T = 8 * (8 ** L - 1) // 7
-        init_mu = np.ascontiguousarray(init_mu, dtype=np.float64)
-        if init_mu.shape != (B, T, 3):
-            raise ValueError("init_mu must be [%d,%d,3]" % (B, T))
+        if (init_mu is None) == (init_rows is None):
+            raise ValueError("tree_build_batch takes init_mu or init_rows, one of the two")
+        if init_rows is not None:
+            init_mu = np.asarray(init_rows, dtype=np.int64)
+            if init_mu.shape == (T,):
+                init_mu = np.broadcast_to(init_mu, (B, T))
+            init_mu = np.ascontiguousarray(init_mu)
+            if init_mu.shape != (B, T):
+                raise ValueError("init_rows must be [%d,%d]" % (B, T))
+            entry = self.lib.hgmm_tree_build_batch_rows
+        else:
+            init_mu = np.ascontiguousarray(init_mu, dtype=np.float64)
+            if init_mu.shape != (B, T, 3):
+                raise ValueError("init_mu must be [%d,%d,3]" % (B, T))
+            entry = self.lib.hgmm_tree_build_batch
         cnt = (C.c_int64 * B)(*[int(v) for v in counts])
         pi = np.empty((B, T)) if want_tables else None
         mu = np.empty((B, T, 3)) if want_tables else None
@@ -1158,9 +1193,9 @@ class Context:
         q = np.zeros((B, qcap)) if want_trace else None
         qlen = np.zeros(B, np.int32) if want_trace else None
         self._forest_LT = None
-        self._check(self.lib.hgmm_tree_build_batch(self.h, B, cnt, int(L), float(ls), float(ld), _ptr(init_mu), float(sig2),
-                                                   int(max_iters_per_level), _ptr(pi), _ptr(mu), _ptr(cov), _ptr(iters),
-                                                   _ptr(q), qcap, _ptr(qlen)))
+        self._check(entry(self.h, B, cnt, int(L), float(ls), float(ld), _ptr(init_mu), float(sig2),
+                          int(max_iters_per_level), _ptr(pi), _ptr(mu), _ptr(cov), _ptr(iters),
+                          _ptr(q), qcap, _ptr(qlen)))
         self._forest_LT = (int(L), T)             # (the node tables hgmm_tree_get_nodes_batch copies out are [T] long)
         traces = [q[b, :qlen[b]].copy() for b in range(B)] if want_trace else None
         return (pi, mu, cov), iters, traces
@@ -1482,16 +1517,21 @@ class Context:
         return ms.value, n.value
 
     # -- voxel-grid down-sample ---------------------------------------------------------------
-    def voxel_down_sample(self, points, voxel_size):
+    def voxel_down_sample(self, points, voxel_size, download=True):
         """Centroids and counts of the occupied voxels of ``points`` [N,3] on the device (hgmm_voxel_downsample_f64 / _f32):
         bit for bit ``pointcloud_io.voxel_down_sample(points, voxel_size, return_counts=True)``.  A float32 array is uploaded
         as it is and widened on the device.  The resident cloud, target and trees of the context are not touched.
-        -> (centroids float64 [M,3], counts int64 [M])."""
-        return self.voxel_down_sample_batch([points], voxel_size, _serial=True)[0]
+        -> (centroids float64 [M,3], counts int64 [M]); ``download=False``: the :class:`VoxelCloud` of the one member, nothing
+        is downloaded (see :meth:`voxel_down_sample_batch`)."""
+        res = self.voxel_down_sample_batch([points], voxel_size, _serial=True, download=download)
+        return res[0] if download else res.member(0)
 
-    def voxel_down_sample_batch(self, clouds, voxel_size, _serial=False):
+    def voxel_down_sample_batch(self, clouds, voxel_size, _serial=False, download=True):
         """:meth:`voxel_down_sample` of every cloud of the list by the same launches (hgmm_voxel_downsample_batch_f64 / _f32:
-        float32 when all of them are); each member's result is bitwise the serial call's.  -> list of (centroids, counts)."""
+        float32 when all of them are); each member's result is bitwise the serial call's.  -> list of (centroids, counts).
+        ``download=False``: nothing comes back to the host -- -> the :class:`VoxelResult` that names the resident result;
+        its members (:class:`VoxelCloud`) go where points go: :meth:`set_points_from_voxels`,
+        :meth:`tree_set_target_from_voxels`, :meth:`set_points_batch_from_voxels`, :meth:`tree_set_targets_batch_from_voxels`."""
         arrs, ptrs, counts, all32 = self._cloud_list(clouds, "voxel_down_sample")
         m = (C.c_int64 * len(arrs))()
         if _serial:
@@ -1501,6 +1541,8 @@ class Context:
             entry = self.lib.hgmm_voxel_downsample_batch_f32 if all32 else self.lib.hgmm_voxel_downsample_batch_f64
             self._check(entry(self.h, len(arrs), ptrs, counts, float(voxel_size), m))
         self._vx_m = [int(v) for v in m]
+        if not download:
+            return VoxelResult(self)
         cent, cnt = self.voxel_down_sample_get()
         out, at = [], 0
         for mb in self._vx_m:
@@ -1518,6 +1560,152 @@ class Context:
         cent, cnt = np.empty((M, 3), np.float64), np.empty(M, np.int64)
         self._check(self.lib.hgmm_voxel_downsample_get(self.h, _ptr(cent), _ptr(cnt)))
         return cent, cnt
+
+    # -- the voxel result handed on without a host round trip (hgmm_voxel_to_*) ----------------------------------
+    def voxel_result_info(self):
+        """The resident voxel result (hgmm_voxel_result_info) -> (m [B] voxels per member, n [B] raw points per member,
+        serial number); HgmmError without one."""
+        B, serial = C.c_int(), C.c_uint64()
+        self._check(self.lib.hgmm_voxel_result_info(self.h, C.byref(B), None, None, C.byref(serial)))
+        m, n = (C.c_int64 * B.value)(), (C.c_int64 * B.value)()
+        self._check(self.lib.hgmm_voxel_result_info(self.h, None, m, n, None))
+        return [int(v) for v in m], [int(v) for v in n], int(serial.value)
+
+    def _voxel_members(self, vcs, what):
+        vcs = list(vcs)
+        if not vcs:
+            raise ValueError("%s: no clouds" % what)
+        for vc in vcs:
+            if not isinstance(vc, VoxelCloud):
+                raise TypeError("%s takes VoxelClouds (voxel_down_sample_batch(..., download=False).member(k)), got %s"
+                                % (what, type(vc).__name__))
+            vc.check(self)
+        return vcs, (C.c_int32 * len(vcs))(*[vc.index for vc in vcs])
+
+    def set_points_from_voxels(self, vc, tree_weights=True, flat_weights=False):
+        """Member ``vc`` (a :class:`VoxelCloud`) becomes the resident cloud without leaving the device (hgmm_voxel_to_points):
+        the state of ``set_points(centroids)`` followed by ``tree_set_source_weights(counts)`` (``tree_weights``) and
+        ``flat_set_weights(counts)`` (``flat_weights``), bit for bit."""
+        self._voxel_members([vc], "set_points_from_voxels")
+        # (a refused call leaves the resident cloud what it was, and so the bookkeeping: it moves after the check)
+        self._check(self.lib.hgmm_voxel_to_points(self.h, vc.index, (1 if tree_weights else 0) | (2 if flat_weights else 0)))
+        self._batch_counts = None
+        self.n = len(vc)
+        return self
+
+    def tree_set_target_from_voxels(self, vc, weighted=True):
+        """Member ``vc`` becomes the resident registration target (hgmm_voxel_to_target): ``tree_set_target(centroids)`` and,
+        ``weighted``, ``tree_set_target_weights(counts)``, bit for bit."""
+        self._voxel_members([vc], "tree_set_target_from_voxels")
+        self._check(self.lib.hgmm_voxel_to_target(self.h, vc.index, 1 if weighted else 0))
+        self._tgt_n = len(vc)
+        return self
+
+    def set_points_batch_from_voxels(self, vcs, weighted=True):
+        """The members ``vcs`` become the resident forest cloud, one launch whatever their number (hgmm_voxel_to_points_batch):
+        ``set_points_batch(centroids of each, weights=counts of each)``, bit for bit.  A member may appear more than once.
+        -> the members' lengths (the forest's counts)."""
+        vcs, members = self._voxel_members(vcs, "set_points_batch_from_voxels")
+        self._check(self.lib.hgmm_voxel_to_points_batch(self.h, len(vcs), members, 1 if weighted else 0))
+        self._batch_counts = [len(vc) for vc in vcs]
+        self.n = int(sum(self._batch_counts))
+        return list(self._batch_counts)
+
+    def tree_set_targets_batch_from_voxels(self, vcs, weighted=True):
+        """The members ``vcs`` become the targets of the resident forest's pairs (hgmm_voxel_to_targets_batch):
+        ``tree_set_targets_batch(centroids of each, weights=counts of each)``, bit for bit."""
+        vcs, members = self._voxel_members(vcs, "tree_set_targets_batch_from_voxels")
+        # (unlike hgmm_tree_set_targets_batch a refused hand-over keeps the resident targets: nothing is cleared beforehand)
+        self._check(self.lib.hgmm_voxel_to_targets_batch(self.h, len(vcs), members, 1 if weighted else 0))
+        self._tgt_B = len(vcs)
+        self._tgt_counts = [len(vc) for vc in vcs]
+        return list(self._tgt_counts)
+
+    def points_rows(self, rows):
+        """Rows of the resident cloud's float64 view (hgmm_points_rows_f64) -> float64 [k,3]; a forest cloud: rows of the
+        concatenated cloud.  What is resident, whichever way it got there."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1:
+            raise ValueError("rows must be [k], got %s" % (rows.shape,))
+        out = np.empty((rows.shape[0], 3), np.float64)
+        self._check(self.lib.hgmm_points_rows_f64(self.h, _ptr(rows), rows.shape[0], _ptr(out)))
+        return out
+
+
+class VoxelResult:
+    """The voxel result resident on a context (``Context.voxel_down_sample_batch(..., download=False)``): ``m[k]`` voxels
+    and ``n[k]`` raw points per member, the context's serial number of the down-sample that made it.  :meth:`member` names
+    one member, :meth:`get` downloads everything as the ``download=True`` call returns it.  It is a NAME for what lies on
+    the device: the context's next successful down-sample replaces the result, and every use of this object or of its
+    members raises HgmmError from then on."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.m, self.n, self.serial = ctx.voxel_result_info()
+
+    def __len__(self):
+        return len(self.m)
+
+    def check(self, ctx=None):
+        if ctx is not None and ctx is not self.ctx:
+            raise HgmmError("this voxel result lies on another context")
+        serial = self.ctx.voxel_result_info()[2]
+        if serial != self.serial:
+            raise HgmmError("stale voxel result: the context has down-sampled something else since (result %d, now %d)"
+                            % (self.serial, serial))
+
+    def member(self, k):
+        k = int(k)
+        if not 0 <= k < len(self.m):
+            raise IndexError("member %d of %d" % (k, len(self.m)))
+        return VoxelCloud(self, k)
+
+    def members(self):
+        return [VoxelCloud(self, k) for k in range(len(self.m))]
+
+    def get(self):
+        """-> list of (centroids float64 [m_k,3], counts int64 [m_k]), member after member."""
+        self.check()
+        cent, cnt = self.ctx.voxel_down_sample_get()
+        out, at = [], 0
+        for mb in self.m:
+            out.append((cent[at:at + mb], cnt[at:at + mb]))
+            at += mb
+        return out
+
+
+class VoxelCloud:
+    """One member of a :class:`VoxelResult`: ``len()`` voxels (float64 centroids) that stand for ``count`` raw points, their
+    counts the weights.  Goes where points go in ``hgmm.hgmm_gpu`` (``buildGMMTree``, ``GMMTree``, ``registration_gmmtree``,
+    ``registration_gmmtree_batch``) and into ``Context.set_points_from_voxels`` and its kin, without a copy on the host."""
+    dtype = np.dtype(np.float64)
+
+    def __init__(self, result, index):
+        self.result, self.index = result, int(index)
+
+    def __len__(self):
+        return self.result.m[self.index]
+
+    @property
+    def count(self):
+        return self.result.n[self.index]
+
+    @property
+    def shape(self):
+        return (len(self), 3)
+
+    @property
+    def ctx(self):
+        return self.result.ctx
+
+    def check(self, ctx=None):
+        self.result.check(ctx)
+
+    def get(self):
+        """-> (centroids float64 [m,3], counts int64 [m]) of this member on the host."""
+        return self.result.get()[self.index]
+
+    to_host = get
 
 
 _default_ctx = None

@@ -67,6 +67,11 @@ int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {
     HGMM_HIP(c, hipMemcpyAsync(dev, st, bytes, hipMemcpyHostToDevice, c->stream));
     return HGMM_OK;
 }
+int upload_table(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {
+    if (bytes <= (256u << 10)) return stage_h2d(c, dev, host, bytes);
+    HGMM_HIP(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    return HGMM_OK;
+}
 
 ProfScope::ProfScope(hgmm_ctx* ctx, int kernel) : c(ctx) {
     if (!c->profiling) return;
@@ -775,7 +780,7 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w, &c->fr_tg_w,
                       &c->src_w, &c->fr_src_w, &c->t_w2, &c->t_w3, &c->flat_sw, &c->f_lpn_rows,
                       &c->vx_in, &c->vx_tab, &c->vx_keys, &c->vx_keys2, &c->vx_rows, &c->vx_rows2, &c->vx_heads, &c->vx_tmp,
-                      &c->vx_cent, &c->vx_cnt};
+                      &c->vx_cent, &c->vx_cnt, &c->vx_hand};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -886,7 +891,7 @@ extern "C" int hgmm_d2d(hgmm_ctx* c, void* dev_dst, const void* dev_src, size_t 
 extern "C" int64_t hgmm_num_points(const hgmm_ctx* c) { return c ? c->n : 0; }
 
 // the cloud `p` becomes the one every kernel of the context works on
-static void bind_points(hgmm_ctx* c, hgmm_points* p) {
+void hgmm::bind_points(hgmm_ctx* c, hgmm_points* p) {
     c->bound = p;
     c->x_aos = p ? p->x_aos : DevBuf();
     c->x_soa64 = p ? p->x_soa64 : DevBuf();
@@ -902,7 +907,7 @@ static void bind_points(hgmm_ctx* c, hgmm_points* p) {
     c->forest.src_counts.clear();
 }
 
-static int points_alloc(hgmm_ctx* c, hgmm_points* p, int64_t n) {
+int hgmm::points_alloc(hgmm_ctx* c, hgmm_points* p, int64_t n) {
     if (n <= 0) return fail(c, HGMM_ERR_ARG, "number of points must be positive");
     HGMM_HIP(c, hipSetDevice(c->device));
     p->ctx = c;

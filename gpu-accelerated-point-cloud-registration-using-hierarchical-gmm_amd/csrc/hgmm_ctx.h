@@ -288,6 +288,11 @@ struct hgmm_ctx {
     hgmm::DevBuf vx_cent, vx_cnt;             // the last result: double [M][3] centroids, int64 [M] counts, cloud after cloud
     bool vx_have = false;                     // a down-sample has succeeded on this context
     int64_t vx_m = 0;                         // its M (all clouds)
+    // the voxel result by member (hgmm_voxel_result_info, the hand-overs of voxel_handover.hip): member k has vx_mb[k] voxels,
+    // rows [vx_first[k], vx_first[k] + vx_mb[k]) of vx_cent / vx_cnt, and stands for vx_nb[k] raw points
+    std::vector<int64_t> vx_mb, vx_nb, vx_first;
+    unsigned long long vx_serial = 0;         // successful down-samples of this context so far
+    hgmm::DevBuf vx_hand;                     // hand-over tables: int64 destination first rows [B + 1], source first rows [B]; 3 words
 
     // ---- multi-GPU --------------------------------------------------------------
     ncclComm_t comm = nullptr;                // RCCL over xGMI (one GPU per rank)
@@ -313,6 +318,18 @@ constexpr size_t STAGE_RING_BYTES = 4u << 20;
 int stage_reserve(hgmm_ctx* c, size_t bytes, void** out);
 // `bytes` of host memory on their way to `dev`: copied into a region of the ring, one DMA packet behind the stream's work
 int stage_h2d(hgmm_ctx* c, void* dev, const void* host, size_t bytes);
+// a small table on its way to the device: through the ring while it fits (<= 256 KB), else copied from `host` directly
+int upload_table(hgmm_ctx* c, void* dev, const void* host, size_t bytes);
+
+// B clouds back to back with a table of first rows: the cloud row i belongs to, the largest b with first[b] <= i
+__device__ inline int find_cloud(const int64_t* __restrict__ first, int B, int64_t i) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
 
 }  // namespace hgmm
 
@@ -410,6 +427,14 @@ inline int fail(hgmm_ctx* c, int code, const char* fmt, ...) {
     } while (0)
 
 int ensure(hgmm_ctx* c, DevBuf& b, size_t bytes);
+// (hgmm_api.hip) the cloud `p` becomes the one every kernel of the context works on; storage for n points in `p`
+void bind_points(hgmm_ctx* c, hgmm_points* p);
+int points_alloc(hgmm_ctx* c, hgmm_points* p, int64_t n);
+// (voxel_handover.hip) rows[k] (device, row numbers of the resident cloud's float64 view) -> out [k][3] (device): one launch
+int gather_rows(hgmm_ctx* c, const int64_t* dev_rows, int64_t k, double* dev_out);
+// (voxel_handover.hip) init_rows [k] of hgmm_tree_build_rows / _batch_rows (host; `first`: what is added to every `per` rows,
+// NULL: nothing) -> scratch [k][3], the place the builds read their initial means from.  The rows have been checked.
+int stage_init_rows(hgmm_ctx* c, const int64_t* rows, int64_t k, const int64_t* first, int64_t per);
 
 // profiling brackets: record an event pair around one kernel launch when enabled
 struct ProfScope {

@@ -583,15 +583,17 @@ struct ForestLevel {
 
 using namespace hgmm;
 
-extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, double ls, double ld,
-                                     const double* init_mu, double sig2, int max_iters_per_level, double* pi_out,
-                                     double* mu_out, double* cov_out, int32_t* iters_out, double* q_trace_out,
-                                     int q_capacity, int32_t* q_len_out) {
+// hgmm_tree_build_batch (init_mu) and hgmm_tree_build_batch_rows (init_rows [B][T]: row numbers within each cloud, gathered
+// on the device into the place init_mu is uploaded to): exactly one of the two is given
+static int tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, double ls, double ld,
+                            const double* init_mu, const int64_t* init_rows, bool by_rows, double sig2, int max_iters_per_level,
+                            double* pi_out, double* mu_out, double* cov_out, int32_t* iters_out, double* q_trace_out,
+                            int q_capacity, int32_t* q_len_out) {
     HGMM_ENTER(c);
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "tree build (batch): set points first");
     if (B < 1 || B > 4096 || !counts) return fail(c, HGMM_ERR_ARG, "tree build (batch): B = %d clouds", B);
     if (L < 1 || L > 6) return fail(c, HGMM_ERR_ARG, "tree levels L = %d outside 1..6", L);
-    if (!init_mu) return fail(c, HGMM_ERR_ARG, "init_mu is NULL");
+    if (by_rows ? !init_rows : !init_mu) return fail(c, HGMM_ERR_ARG, by_rows ? "init_rows is NULL" : "init_mu is NULL");
     if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "tree build (batch): independent clouds take no communicator");
     if (c->n > 0x7fffffff - 1024) return fail(c, HGMM_ERR_ARG, "too many points for 32-bit indices");
     if (max_iters_per_level < 1) max_iters_per_level = 1;
@@ -616,6 +618,11 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
         return fail(c, HGMM_ERR_ARG, "tree build (batch): the resident source weights were set for other cloud sizes");
     const int64_t T = level_first(L);
     const int64_t TT = T * B;
+    if (by_rows)
+        for (int64_t j = 0; j < TT; ++j)
+            if (init_rows[j] < 0 || init_rows[j] >= counts[j / T])
+                return fail(c, HGMM_ERR_ARG, "tree build (batch): init_rows[%lld][%lld] = %lld, but cloud %lld has %lld points",
+                            (long long)(j / T), (long long)(j % T), (long long)init_rows[j], (long long)(j / T), (long long)counts[j / T]);
     int64_t P8 = 1;
     for (int i = 0; i < L - 1; ++i) P8 *= 8;                   // parents of one cloud at the last level
     const int64_t maxP = P8 * B;
@@ -647,7 +654,13 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     double* trace_base = c->fr_trace.as<double>();
 
     // node tables: pi = 1/8, mu = given, cov = sig2 I for every tree; per-cloud form flags start at zero
-    HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * TT, hipMemcpyHostToDevice, c->stream));
+    if (by_rows) {
+        std::vector<int64_t> first_row(B, 0);
+        for (int b = 1; b < B; ++b) first_row[b] = first_row[b - 1] + counts[b - 1];
+        HGMM_TRY(stage_init_rows(c, init_rows, TT, first_row.data(), T));
+    } else {
+        HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * TT, hipMemcpyHostToDevice, c->stream));
+    }
     HGMM_HIP(c, hipMemsetAsync(d_flags, 0, sizeof(int) * (B + 1), c->stream));
     tree_init_nodes_kernel<<<nblk(TT, 256), 256, 0, c->stream>>>(c->scratch.as<double>(), sig2, TT, d_pi, d_mu, d_cov);
     forest_prep_kernel<<<nblk(TT, 256), 256, 0, c->stream>>>(d_pi, d_mu, d_cov, TT, (int)T, d_prep, d_flags);
@@ -748,6 +761,21 @@ extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, 
     }
     F.nodes_ready = true;
     return HGMM_OK;
+}
+
+extern "C" int hgmm_tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, double ls, double ld,
+                                     const double* init_mu, double sig2, int max_iters_per_level, double* pi_out,
+                                     double* mu_out, double* cov_out, int32_t* iters_out, double* q_trace_out,
+                                     int q_capacity, int32_t* q_len_out) {
+    return tree_build_batch(c, B, counts, L, ls, ld, init_mu, nullptr, false, sig2, max_iters_per_level, pi_out, mu_out, cov_out,
+                            iters_out, q_trace_out, q_capacity, q_len_out);
+}
+extern "C" int hgmm_tree_build_batch_rows(hgmm_ctx* c, int B, const int64_t* counts, int L, double ls, double ld,
+                                          const int64_t* init_rows, double sig2, int max_iters_per_level, double* pi_out,
+                                          double* mu_out, double* cov_out, int32_t* iters_out, double* q_trace_out,
+                                          int q_capacity, int32_t* q_len_out) {
+    return tree_build_batch(c, B, counts, L, ls, ld, nullptr, init_rows, true, sig2, max_iters_per_level, pi_out, mu_out, cov_out,
+                            iters_out, q_trace_out, q_capacity, q_len_out);
 }
 
 extern "C" int hgmm_tree_get_nodes_batch(hgmm_ctx* c, int b, double* pi_out, double* mu_out, double* cov_out) {

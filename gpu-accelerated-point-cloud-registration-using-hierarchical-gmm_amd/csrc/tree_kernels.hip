@@ -806,14 +806,21 @@ struct BuildLevel {
 
 using namespace hgmm;
 
-extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const double* init_mu,
-                               double sig2, int max_iters_per_level, double* pi_out, double* mu_out,
-                               double* cov_out, int32_t* leaf_idx_out, int32_t* iters_per_level_out,
-                               double* q_trace_out, int q_capacity, int* q_len_out) {
+// hgmm_tree_build (init_mu) and hgmm_tree_build_rows (init_rows: the initial means are rows of the resident cloud, gathered on
+// the device into the place init_mu is uploaded to): exactly one of the two is given
+static int tree_build(hgmm_ctx* c, int L, double ls, double ld, const double* init_mu, const int64_t* init_rows, bool by_rows,
+                      double sig2, int max_iters_per_level, double* pi_out, double* mu_out,
+                      double* cov_out, int32_t* leaf_idx_out, int32_t* iters_per_level_out,
+                      double* q_trace_out, int q_capacity, int* q_len_out) {
     HGMM_ENTER(c);
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "tree build: set points first");
     if (L < 1 || L > 6) return fail(c, HGMM_ERR_ARG, "tree levels L = %d outside 1..6", L);
-    if (!init_mu) return fail(c, HGMM_ERR_ARG, "init_mu is NULL");
+    if (by_rows ? !init_rows : !init_mu) return fail(c, HGMM_ERR_ARG, by_rows ? "init_rows is NULL" : "init_mu is NULL");
+    if (by_rows)
+        for (int64_t j = 0, T_ = level_first(L); j < T_; ++j)
+            if (init_rows[j] < 0 || init_rows[j] >= c->n)
+                return fail(c, HGMM_ERR_ARG, "tree build: init_rows[%lld] = %lld, but the resident cloud has %lld points",
+                            (long long)j, (long long)init_rows[j], (long long)c->n);
     if (c->n > 0x7fffffff - 1024) return fail(c, HGMM_ERR_ARG, "too many points for 32-bit indices");
     // hgmm_tree_set_source_weights: the WEIGHTED instantiations of the level's kernels, the weights on the coordinates' ping-pong
     const bool weighted = c->src_weighted;
@@ -845,7 +852,8 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     int* perm_next = perm_cur + n_pad;
     double* trace_base = c->t_qtrace.as<double>();
 
-    HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * T, hipMemcpyHostToDevice, c->stream));
+    if (by_rows) HGMM_TRY(stage_init_rows(c, init_rows, T, nullptr, 1));
+    else HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * T, hipMemcpyHostToDevice, c->stream));
     tree_init_nodes_kernel<<<nblk(T, 256), 256, 0, c->stream>>>(c->scratch.as<double>(), sig2, T, d_pi, d_mu, d_cov);
     HGMM_TRY(tree_prep(c, 0, T));
     tree_iota_kernel<<<nblk(n, 256), 256, 0, c->stream>>>(perm_cur, n);
@@ -934,6 +942,21 @@ extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const d
     if (q_len_out) *q_len_out = q_len < q_capacity ? q_len : q_capacity;
     if (rc == HGMM_OK) { c->tree.nodes_ready = true; c->tree.mu_rmax = -1.0; }
     return rc;
+}
+
+extern "C" int hgmm_tree_build(hgmm_ctx* c, int L, double ls, double ld, const double* init_mu,
+                               double sig2, int max_iters_per_level, double* pi_out, double* mu_out,
+                               double* cov_out, int32_t* leaf_idx_out, int32_t* iters_per_level_out,
+                               double* q_trace_out, int q_capacity, int* q_len_out) {
+    return tree_build(c, L, ls, ld, init_mu, nullptr, false, sig2, max_iters_per_level, pi_out, mu_out, cov_out, leaf_idx_out,
+                      iters_per_level_out, q_trace_out, q_capacity, q_len_out);
+}
+extern "C" int hgmm_tree_build_rows(hgmm_ctx* c, int L, double ls, double ld, const int64_t* init_rows,
+                                    double sig2, int max_iters_per_level, double* pi_out, double* mu_out,
+                                    double* cov_out, int32_t* leaf_idx_out, int32_t* iters_per_level_out,
+                                    double* q_trace_out, int q_capacity, int* q_len_out) {
+    return tree_build(c, L, ls, ld, nullptr, init_rows, true, sig2, max_iters_per_level, pi_out, mu_out, cov_out, leaf_idx_out,
+                      iters_per_level_out, q_trace_out, q_capacity, q_len_out);
 }
 
 extern "C" int hgmm_tree_set_precision(hgmm_ctx* c, int precision) {

@@ -51,16 +51,6 @@ inline double ord_dec(unsigned long long e) {
     return x;
 }
 
-// the cloud row i belongs to: the largest b with first[b] <= i  (first[B] = total)
-__device__ inline int find_cloud(const int64_t* __restrict__ first, int B, int64_t i) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (first[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ inline void box_point(VoxelBox* bx, double x, int d) {
     atomicMin(&bx->mn[d], ord_enc(x));
     atomicMax(&bx->mx[d], ord_enc(x));
@@ -150,13 +140,6 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_centroid_kernel(const IN* __re
     const double n = (double)(e - s);
     for (int d = 0; d < 3; ++d) cent[3 * vx + d] = sum[d] / n;
     cnt[vx] = e - s;
-}
-
-// a small table on its way to the device: through the pinned ring (one DMA packet behind the stream's work) while it fits
-static int upload_table(hgmm_ctx* c, void* dev, const void* host, size_t bytes) {
-    if (bytes <= (256u << 10)) return stage_h2d(c, dev, host, bytes);
-    HGMM_HIP(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
-    return HGMM_OK;
 }
 
 static unsigned bits_of(unsigned long long x) {         // bits needed to write x
@@ -283,9 +266,17 @@ static int voxel_downsample(hgmm_ctx* c, int B, const IN* const* xyz, const int6
     dl.add(h_out.data(), d_out, sizeof(uint32_t) * ((size_t)B + 1));
     HGMM_HIP(c, dl.finish());
     c->vx_m = (int64_t)M;
+    c->vx_mb.resize((size_t)B);
+    c->vx_first.resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        c->vx_first[b] = (int64_t)h_out[1 + b];
+        c->vx_mb[b] = (int64_t)(b + 1 < B ? h_out[2 + b] : M) - (int64_t)h_out[1 + b];
+    }
+    c->vx_nb.assign(counts, counts + B);
+    ++c->vx_serial;
     c->vx_have = true;
     if (m_out)
-        for (int b = 0; b < B; ++b) m_out[b] = (int64_t)(b + 1 < B ? h_out[2 + b] : M) - (int64_t)h_out[1 + b];
+        for (int b = 0; b < B; ++b) m_out[b] = c->vx_mb[b];
     return HGMM_OK;
 }
 

@@ -23,7 +23,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .._native import CHI2_3_99, CHI2_3_999, Context, default_context
+from .._native import CHI2_3_99, CHI2_3_999, Context, VoxelCloud, VoxelResult, default_context  # noqa: F401
 
 eps = np.float32(1.0e-15)     # hgmm_gpu.py:29
 n_node = 8                    # hgmm_gpu.py:30
@@ -48,7 +48,17 @@ def complexity(cov):
     return lam[0] / np.sum(lam)
 
 
+def _is_voxels(x):
+    """A :class:`VoxelCloud`: a member of the voxel result resident on a context (``Context.voxel_down_sample_batch(...,
+    download=False)``).  It goes where points go, stays on the device, and its counts are its weights."""
+    return isinstance(x, VoxelCloud)
+
+
 def _points(x):
+    """The [N,3] array behind a cloud argument; a :class:`VoxelCloud` is returned as it is (``len()`` and ``dtype`` answer
+    for it: it counts as float64 wherever the points' type selects arithmetic)."""
+    if _is_voxels(x):
+        return x
     return np.asarray(x.points if hasattr(x, "points") else x)
 
 
@@ -93,7 +103,11 @@ def _weights_arg(weights, n):
 
 def _target_weights(target, weights=None):
     """The weights that go with ``target``: the explicit argument, else the target's own ``.weights`` (WeightedPoints), else
-    None -- checked against the target's length."""
+    None -- checked against the target's length.  A :class:`VoxelCloud` brings its counts and takes no others."""
+    if _is_voxels(target):
+        if weights is not None:
+            raise ValueError("a VoxelCloud is weighted by its counts: it cannot be combined with explicit weights")
+        return None
     if weights is None:
         weights = getattr(target, "weights", None)
     return _weights_arg(weights, len(_points(target)))
@@ -102,7 +116,10 @@ def _target_weights(target, weights=None):
 def _set_source(ctx, points, weights):
     """Upload ``points`` (float64 [N,3]) as the context's resident cloud, then its weights if it has any (already checked by
     :func:`_weights_arg`).  A new cloud drops the previous one's weights in the library, so a cloud is never built under
-    another one's weights."""
+    another one's weights.  A :class:`VoxelCloud` is handed over on the device, its counts as the weights."""
+    if _is_voxels(points):
+        ctx.set_points_from_voxels(points, tree_weights=True)
+        return
     ctx.set_points(points)
     if weights is not None:
         ctx.tree_set_source_weights(weights)
@@ -112,6 +129,9 @@ def _set_target(ctx, target, weights=None):
     """Upload ``target`` as the context's resident registration target, with its weights if it has any.  A new target drops
     the weights of the previous one in the library, so a target is never registered under another one's weights."""
     w = _target_weights(target, weights)
+    if _is_voxels(target):
+        ctx.tree_set_target_from_voxels(target, weighted=True)
+        return
     ctx.tree_set_target(_points(target))
     if w is not None:
         ctx.tree_set_target_weights(w)
@@ -158,17 +178,19 @@ def buildGMMTree(points, maxTreeLevel, ls, ld, sig2=0.004, seed=72, init_idx=Non
     pdt = np.dtype(pdf_dtype) if pdf_dtype is not None else dt
     if dt not in (np.dtype(np.float32), np.dtype(np.float64)) or pdt not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise ValueError("dtype must be float32 or float64")
-    P = np.ascontiguousarray(raw, dtype=np.float64)
+    # (a VoxelCloud stays on the device: its initial means are gathered there, by row number)
+    P = raw if _is_voxels(raw) else np.ascontiguousarray(raw, dtype=np.float64)
     T = n_total_nodes(maxTreeLevel)
     if init_idx is None:
         rs = np.random.RandomState(seed)
         init_idx = rs.randint(T, size=T)
     _set_source(ctx, P, weights)
+    init = dict(init_mu=None, init_rows=np.asarray(init_idx)) if _is_voxels(raw) else dict(init_mu=P[np.asarray(init_idx)])
     prev = getattr(ctx, "tree_dtype", np.dtype(np.float64))     # (a precision the caller set on the context survives this call)
     ctx.tree_set_precision(pdt)
     try:
-        pi, mu, cov, leaf, iters, q = ctx.tree_build(maxTreeLevel, ls, ld, P[np.asarray(init_idx)], sig2,
-                                                     max_iters_per_level, want_leaf=bool(return_trace))
+        pi, mu, cov, leaf, iters, q = ctx.tree_build(maxTreeLevel, ls, ld, sig2=sig2, max_iters_per_level=max_iters_per_level,
+                                                     want_leaf=bool(return_trace), **init)
     finally:
         ctx.tree_set_precision(prev)
     if dt == np.dtype(np.float32):
@@ -745,15 +767,42 @@ def prepare_source_and_target_rigid_3d(source, noise_amp=0.001, n_random=500,
 
 
 def _voxel_pairs(ctx, pairs, voxel_size, explicit_weights):
-    """``voxel_size=`` of the registration functions: every cloud of ``pairs`` down-sampled on ``ctx``'s device by ONE batch
-    call (``Context.voxel_down_sample_batch``), -> pairs of ``WeightedPoints(centroids, counts)``.  Weights of the caller's
-    own next to a voxel size are refused: they belong to the points that are about to be replaced."""
+    """``voxel_size=`` of the registration functions: every DISTINCT cloud of ``pairs`` down-sampled on ``ctx``'s device by
+    ONE batch call (``Context.voxel_down_sample_batch(..., download=False)``), -> pairs of :class:`VoxelCloud`: the result
+    stays on the device and is handed to build and registration there.  Distinct means identity (``is``): a scan that is the
+    target of one pair and the source of the next -- the same object -- is one member, down-sampled once; equal arrays that
+    are different objects are not merged.  Weights of the caller's own next to a voxel size are refused: they belong to the
+    points that are about to be replaced."""
     own = any(getattr(c, "weights", None) is not None for p in pairs for c in p)
     if own or any(w is not None for w in explicit_weights):
         raise ValueError("voxel_size replaces the clouds by their voxel centroids, weighted by the counts: it cannot be "
                          "combined with source_weights / target_weights (or WeightedPoints inputs)")
-    ds = ctx.voxel_down_sample_batch([_points(c) for p in pairs for c in p], voxel_size)
-    return [(WeightedPoints(*ds[2 * k]), WeightedPoints(*ds[2 * k + 1])) for k in range(len(pairs))]
+    if any(_is_voxels(c) for p in pairs for c in p):
+        raise ValueError("voxel_size next to a VoxelCloud: that cloud has been down-sampled already")
+    distinct, member = [], {}                      # (`distinct` keeps every object alive: its id stays its own)
+    for p in pairs:
+        for c in p:
+            if id(c) not in member:
+                member[id(c)] = len(distinct)
+                distinct.append(c)
+    res = ctx.voxel_down_sample_batch([_points(c) for c in distinct], voxel_size, download=False)
+    return [(res.member(member[id(s)]), res.member(member[id(t)])) for s, t in pairs]
+
+
+def _voxels_to_host(clouds, weights):
+    """A list of clouds of which only SOME are :class:`VoxelCloud`s (the batched hand-overs take members only): those come
+    to the host as (centroids, counts) -- ``weights`` (a list, changed in place) receives the counts.  Each distinct voxel
+    result is downloaded once, whatever the number of its members in the list."""
+    if not any(_is_voxels(c) for c in clouds) or all(_is_voxels(c) for c in clouds):
+        return clouds
+    out, host = list(clouds), {}
+    for k, c in enumerate(out):
+        if _is_voxels(c):
+            if id(c.result) not in host:
+                host[id(c.result)] = c.result.get()
+            cent, cnt = host[id(c.result)][c.index]
+            out[k], weights[k] = cent, cnt.astype(np.float64)
+    return out
 
 
 def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], return_score=False, starts=None, **kargs):
@@ -767,14 +816,16 @@ def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], r
     ``voxel_size=`` (a keyword of this function like the weights; default None: the clouds as they are): both clouds are
     voxel-down-sampled on the device first (one ``Context.voxel_down_sample_batch`` call) and the counts travel as source and
     target weights -- bit for bit this call on ``WeightedPoints(*voxel_down_sample(cloud, voxel_size, True))`` inputs; with
-    explicit weights: ValueError."""
+    explicit weights: ValueError.  Centroids and counts do not come to the host in between: the clouds become
+    :class:`VoxelCloud`s, which ``source`` and ``target`` may also be from the start (``Context.voxel_down_sample(...,
+    download=False)``; explicit weights next to one: ValueError)."""
     voxel_size = kargs.pop("voxel_size", None)
     if voxel_size is not None:
         (source, target), = _voxel_pairs(kargs.get("ctx") or default_context(), [(source, target)], voxel_size,
                                          [kargs.get("source_weights"), kargs.get("target_weights")])
     weights = _target_weights(target, kargs.pop("target_weights", None))
     kargs["source_weights"] = _target_weights(source, kargs.pop("source_weights", None))
-    gt = GMMTree(_points(source), **kargs)
+    gt = GMMTree(_points(source), **kargs)           # (a VoxelCloud: handed over on the device, build and target alike)
     if starts is not None:
         tgt = _points(target) if weights is None else WeightedPoints(_points(target), weights)
         return gt.registration_multistart(tgt, starts, maxiter, tol)
@@ -820,7 +871,9 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
 
     ``voxel_size`` (default None: the clouds as they are): all 2B clouds are voxel-down-sampled on the device first, by ONE
     ``Context.voxel_down_sample_batch`` call, and the counts travel as source and target weights -- bit for bit this call
-    on ``WeightedPoints(*voxel_down_sample(cloud, voxel_size, True))`` inputs; with explicit weights: ValueError.
+    on ``WeightedPoints(*voxel_down_sample(cloud, voxel_size, True))`` inputs; with explicit weights: ValueError.  Each
+    DISTINCT array object is down-sampled once (a chain ``[(a, b), (b, c)]`` down-samples three clouds), and nothing but the
+    results comes back to the host: the clouds travel as :class:`VoxelCloud`s, which the pairs may also hold from the start.
 
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
@@ -841,6 +894,8 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     sws = [_target_weights(pairs[k][0], None if source_weights is None else source_weights[k]) for k in range(len(pairs))]
     # (from here on the weights travel as lists: the recursive calls below must not read a WeightedPoints' own a second time)
     pairs = [(_points(s), t) for s, t in pairs]
+    # (VoxelClouds among host arrays: the batched hand-overs take members only, so those come to the host with their counts)
+    pairs = list(zip(_voxels_to_host([s for s, _ in pairs], sws), _voxels_to_host([t for _, t in pairs], ws)))
     big = [k for k, (s, _) in enumerate(pairs) if len(_points(s)) >= BATCH_MAX_POINTS]
     if big:
         # a cloud of >= 400 000 points fills the chip by itself and takes the serial build's four-points-per-thread
@@ -896,9 +951,12 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     B = len(pairs)
     T = n_total_nodes(tree_level)
     idx = np.asarray(init_idx) if init_idx is not None else np.random.RandomState(72).randint(T, size=T)
-    init_mu = np.stack([np.asarray(S[idx], dtype=np.float64) for S in srcs])
+    vox_src, vox_tgt = _is_voxels(srcs[0]), _is_voxels(tgts[0])      # (all of a side or none: _voxels_to_host)
+    init = dict(init_mu=None, init_rows=idx) if vox_src else dict(init_mu=np.stack([np.asarray(S[idx], dtype=np.float64) for S in srcs]))
     clock.append(time.perf_counter())
-    if any(w is not None for w in sws):
+    if vox_src:
+        ctx.set_points_batch_from_voxels(srcs, weighted=True)
+    elif any(w is not None for w in sws):
         ctx.set_points_batch(srcs, weights=sws)
     else:
         ctx.set_points_batch(srcs)
@@ -906,11 +964,13 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     prev = getattr(ctx, "tree_dtype", np.dtype(np.float64))     # (a precision the caller set on the context survives this call)
     ctx.tree_set_precision(pdf_dtype)
     try:
-        _, build_iters, _ = ctx.tree_build_batch([len(S) for S in srcs], tree_level, ls, ld, init_mu, sig2, want_tables=False)
+        _, build_iters, _ = ctx.tree_build_batch([len(S) for S in srcs], tree_level, ls, ld, sig2=sig2, want_tables=False, **init)
     finally:
         ctx.tree_set_precision(prev)
     clock.append(time.perf_counter())
-    if any(w is not None for w in ws):
+    if vox_tgt:
+        ctx.tree_set_targets_batch_from_voxels(tgts, weighted=True)
+    elif any(w is not None for w in ws):
         ctx.tree_set_targets_batch(tgts, weights=ws)
     else:
         ctx.tree_set_targets_batch(tgts)

@@ -629,6 +629,67 @@ int hgmm_voxel_downsample_batch_f32(hgmm_ctx* ctx, int B, const float* const* xy
                                     int64_t* m_out /* [B] */);
 int hgmm_voxel_downsample_get(hgmm_ctx* ctx, double* centroids_out /* [sum m,3] */, int64_t* counts_out /* [sum m] */);
 
+/* ---- the voxel result handed to its consumers on the device: no download, no second upload --------------------------------
+ * The last successful down-sample of a context is its VOXEL RESULT: B member clouds, member k with m[k] voxels that stand
+ * for n[k] raw points.  It stays resident until the next successful down-sample; every successful down-sample increments
+ * the context's serial number, by which a caller can tell whether a member it remembers is still the one resident.
+ * hgmm_voxel_result_info describes it (any pointer may be NULL; m and n are [B]); HGMM_ERR_STATE without one, like _get.
+ *
+ * The four hand-overs copy members to where the existing setters put host arrays.  Each is DEFINED by a sequence of
+ * existing entries and leaves the context in the state of that sequence, bit for bit -- every later result (tree build,
+ * flat statistics and fit, float32 download, registration E-step, registration, score) has that sequence's bits -- without
+ * running it: ONE launch per call whatever B is, no host pass over the points or the weights.  With (cent, cnt) =
+ * hgmm_voxel_downsample_get's arrays, cent_k / cnt_k the rows of member k:
+ *   hgmm_voxel_to_points(k, weights)          hgmm_set_points_f64(cent_k, m[k]);
+ *                                             weights & HGMM_VOXEL_W_TREE: hgmm_tree_set_source_weights((double)cnt_k, m[k]);
+ *                                             weights & HGMM_VOXEL_W_FLAT: hgmm_flat_set_weights((float)cnt_k, m[k])
+ *   hgmm_voxel_to_target(k, weighted)         hgmm_tree_set_target(cent_k, m[k]);
+ *                                             weighted: hgmm_tree_set_target_weights((double)cnt_k, m[k])
+ *   hgmm_voxel_to_points_batch(B, members, weighted)
+ *                                             hgmm_set_points_batch_f64 of the clouds cent_members[b];
+ *                                             weighted: hgmm_tree_set_source_weights_batch of (double)cnt_members[b]
+ *   hgmm_voxel_to_targets_batch(B, members, weighted)
+ *                                             hgmm_tree_set_targets_batch of the clouds cent_members[b];
+ *                                             weighted: hgmm_tree_set_target_weights_batch of (double)cnt_members[b]
+ * That state includes the zero padding of the float64 planes and of the weights, the float32 rows (float)centroid (the forest
+ * cloud has none), everything a new resident cloud / new target resets, and the weight sums: the tree's and the targets' are
+ * (double)n[k] -- counts are integers, their sum is the member's raw point count in any order -- and the flat fit's is the
+ * float64 sum of the float32 values (float)cnt (n[k] again unless a count reaches 2^24; then it is summed on the device, as
+ * integers).  The targets' extent bound is sqrt(max_i ((x x + y y) + z z)) with separately rounded products and sums, the
+ * maximum taken by integer atomics on the bits: hgmm_tree_set_target's and hgmm_tree_set_targets_batch's number.
+ * The result is COPIED, not moved: hgmm_voxel_downsample_get returns what it returned, and a member may be handed over any
+ * number of times, to several slots of one batch too (members = {3, 0, 0, 2} is legal).
+ * The source hand-overs do not wait for the device; the target hand-overs wait once, for the extent bounds.
+ * REFUSALS, each checked before anything resident is touched (the resident cloud, target, weights, forest and the voxel
+ * result stay what they were; hgmm_last_error says why): HGMM_ERR_STATE without a voxel result; HGMM_ERR_ARG for a member
+ * outside [0, B_result), B < 1 (targets: B > 4096), NULL members, bits of `weights` other than the two below, more than
+ * 0x7fffffff - 1024 target points in all.  A runtime failure part-way leaves nothing bound / no target.                       */
+#define HGMM_VOXEL_W_TREE 1   /* the counts as source weights of the tree build (hgmm_tree_set_source_weights) */
+#define HGMM_VOXEL_W_FLAT 2   /* the counts as weights of the flat fit (hgmm_flat_set_weights) */
+int hgmm_voxel_result_info(hgmm_ctx* ctx, int* B_out, int64_t* m_out /* [B] */, int64_t* n_out /* [B] */, uint64_t* serial_out);
+int hgmm_voxel_to_points(hgmm_ctx* ctx, int member, int weights /* HGMM_VOXEL_W_* bits */);
+int hgmm_voxel_to_target(hgmm_ctx* ctx, int member, int weighted);
+int hgmm_voxel_to_points_batch(hgmm_ctx* ctx, int B, const int32_t* members /* [B] */, int weighted);
+int hgmm_voxel_to_targets_batch(hgmm_ctx* ctx, int B, const int32_t* members /* [B] */, int weighted);
+
+/* Rows of the resident cloud's float64 view on the host: out[j] = row rows[j] (a forest cloud: rows of the concatenated
+ * cloud) -- how a caller reads back what is resident, whichever way it got there.  HGMM_ERR_STATE without a float64 view;
+ * HGMM_ERR_ARG for k < 0, NULL pointers or a row outside the cloud (the message names its position and value).
+ * hgmm_tree_build_rows / hgmm_tree_build_batch_rows are hgmm_tree_build / hgmm_tree_build_batch with init_mu[j] = the float64
+ * row init_rows[j] of the resident cloud (batch: init_rows [B][T], row numbers WITHIN each cloud), gathered on the device into
+ * the place init_mu is uploaded to: bit for bit the same build, no host copy of the cloud needed.  They work on any
+ * resident cloud, not only one that came from a voxel result; a row outside its cloud is HGMM_ERR_ARG and nothing is touched. */
+int hgmm_points_rows_f64(hgmm_ctx* ctx, const int64_t* rows /* [k] */, int64_t k, double* out /* [k,3] */);
+int hgmm_tree_build_rows(hgmm_ctx* ctx, int L, double ls, double ld, const int64_t* init_rows /* [T] */,
+                         double sig2, int max_iters_per_level,
+                         double* pi_out, double* mu_out, double* cov_out, int32_t* leaf_idx_out,
+                         int32_t* iters_per_level_out, double* q_trace_out, int q_capacity,
+                         int* q_len_out);
+int hgmm_tree_build_batch_rows(hgmm_ctx* ctx, int B, const int64_t* counts, int L, double ls, double ld,
+                               const int64_t* init_rows /* [B][T] */, double sig2, int max_iters_per_level,
+                               double* pi_out, double* mu_out, double* cov_out, int32_t* iters_out,
+                               double* q_trace_out, int q_capacity, int32_t* q_len_out);
+
 /* ---- multi-GPU: one context per rank, RCCL over xGMI --------------------------------
  * New functionality (the reference is single-GPU).  With a communicator attached,
  * hgmm_flat_train*, hgmm_flat_stats and hgmm_tree_build all-reduce their per-cluster

@@ -12,6 +12,20 @@ Cases: bun000 (40 256 float32 points) at 4 mm and 2 mm; 10^6 uniform float64 poi
 clouds (bun000 and bun045 alternating) at 4 mm, beside 64 host calls.
 --bench-parent / --bench-pr: files of bench.py result lines (one JSON object per line) of the parent commit and of this
 tree, taken in one session; their medians are written below the table.
+
+The voxel result handed to build and registration on the device -> profiles/voxel_handover.md:
+
+    python tools/voxelbench.py --handover [--root TREE] [--reps 10]        one run on one tree: ONE JSON line
+    python tools/voxelbench.py --handover-report --parent-runs FILE --pr-runs FILE [--bench-parent FILE --bench-pr FILE] [--out FILE]
+
+``--handover`` times three calls that both the parent commit and this tree offer (``voxel_size=`` of the registration
+mirrors), bun000 / bun045 at 4 mm, L = 3, 20 iterations, wall clock from host arrays to results, median of --reps calls after
+two warm-up calls: (1) one ``registration_gmmtree``; (2) ``registration_gmmtree_batch`` on 32 pairs, every cloud an array
+object of its own (64 down-samples on either tree); (3) a chain of 33 scans -- bun000 under 33 small rotations -- registered
+as 32 consecutive pairs, the inner scans the same object in two pairs.  ``--root`` names the tree whose package is imported
+(a checkout of the parent commit with its library built); the line carries a digest of every result, which the report
+compares between the trees.  ``--handover-report`` reads the lines of the alternating runs and writes the table: every run,
+the medians, the parent's spread.
 """
 import argparse
 import json
@@ -49,14 +63,104 @@ def bench_lines(path):
     return vals
 
 
+def handover_run(args):
+    """one run on the tree --root names: a JSON line {"rows": {name: median ms}, "digest": {name: sha1 of the results}}"""
+    import hashlib
+    root = os.path.abspath(args.root or ROOT)
+    sys.path.insert(0, root)
+    import hgmm_amd
+    from hgmm_amd.hgmm.hgmm_gpu import registration_gmmtree, registration_gmmtree_batch
+    assert os.path.abspath(hgmm_amd.__file__).startswith(root + os.sep), (hgmm_amd.__file__, root)
+    golden = os.path.join(root, "tests", "golden")
+    bun000 = np.load(os.path.join(golden, "bun000_xyz.npy"))
+    bun045 = np.load(os.path.join(golden, "bun045_xyz.npy"))
+    ctx = hgmm_amd.Context(0)
+    kw = dict(maxiter=20, ctx=ctx, tree_level=3, voxel_size=0.004)
+    pairs32 = [(bun000.copy(), bun045.copy()) for _ in range(32)]
+    scans = []
+    for k in range(33):
+        th = 0.01 * k
+        rz = np.array([[np.cos(th), -np.sin(th), 0.0], [np.sin(th), np.cos(th), 0.0], [0.0, 0.0, 1.0]])
+        scans.append(np.ascontiguousarray((bun000.astype(np.float64) @ rz.T).astype(np.float32)))
+    chain = [(scans[k], scans[k + 1]) for k in range(32)]
+    cases = [("one registration_gmmtree", lambda: [registration_gmmtree(bun000, bun045, **kw)]),
+             ("registration_gmmtree_batch, 32 pairs", lambda: registration_gmmtree_batch(pairs32, **kw)),
+             ("chain of 33 scans, 32 consecutive pairs", lambda: registration_gmmtree_batch(chain, **kw))]
+    rows, digest = {}, {}
+    for name, run in cases:
+        res = run()
+        h = hashlib.sha1()
+        for r in res:
+            tf = r.transformation
+            for a in (tf.rot, tf.t, r.q):
+                h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        digest[name] = h.hexdigest()
+        run()
+        rows[name] = 1e3 * median_s(run, args.reps)
+    ctx.close()
+    print(json.dumps({"root": root, "reps": args.reps, "rows": rows, "digest": digest}), flush=True)
+    return 0
+
+
+def handover_report(args):
+    def lines(path):
+        return [json.loads(l) for l in open(path) if l.strip().startswith("{")]
+    par, pr = lines(args.parent_runs), lines(args.pr_runs)
+    names = list(par[0]["rows"])
+    out = ["# Voxel centroids straight to build and registration: this tree beside the parent commit", "",
+           "`python tools/voxelbench.py --handover --reps %d`, %d runs on a checkout of the parent commit and %d on this tree in one "
+           "session, alternating (parent first).  bun000 / bun045 at 4 mm, L = 3, 20 iterations; wall clock of the call from host "
+           "arrays to results, per run the median of its calls after two warm-up calls.  Rows 2 and 3: 32 pairs in one "
+           "`registration_gmmtree_batch(..., voxel_size=0.004)`; in row 2 every cloud is an array object of its own (64 "
+           "down-samples on either tree), in row 3 the 33 scans of a chain are shared between consecutive pairs (64 "
+           "down-samples on the parent, 33 here)." % (par[0]["reps"], len(par), len(pr)), "",
+           "| call | parent runs, ms | parent median | parent spread | this tree runs, ms | this tree median | this tree / parent | same results |",
+           "|---|---|---|---|---|---|---|---|"]
+    slower = []
+    for name in names:
+        a, b = [r["rows"][name] for r in par], [r["rows"][name] for r in pr]
+        ma, mb = float(np.median(a)), float(np.median(b))
+        same_bits = len({r["digest"][name] for r in par + pr}) == 1
+        if mb > max(a):
+            slower.append(name)
+        out.append("| %s | %s | %.3f | %.3f .. %.3f | %s | %.3f | %.2f | %s |"
+                   % (name, ", ".join("%.3f" % x for x in a), ma, min(a), max(a), ", ".join("%.3f" % x for x in b), mb, mb / ma,
+                      "yes" if same_bits else "NO"))
+    out += ["", "No row's median is above the parent's slowest run." if not slower else
+            "SLOWER THAN EVERY RUN OF THE PARENT on: %s." % "; ".join(slower)]
+    if args.bench_parent and args.bench_pr:
+        bp, bq = bench_lines(args.bench_parent), bench_lines(args.bench_pr)
+        out += ["", "## `bench.py --gpus 1 --steps 20 --warmup 5`, parent and this tree in the same session, alternating", "",
+                "| tree | runs (`value`, EM it/s) | median |", "|---|---|---|",
+                "| parent | %s | %.1f |" % (", ".join("%.1f" % x for x in bp), np.median(bp)),
+                "| this tree | %s | %.1f |" % (", ".join("%.1f" % x for x in bq), np.median(bq)), "",
+                "This tree's median is %+.2f %% of the parent's." % (100.0 * (np.median(bq) / np.median(bp) - 1.0))]
+    text = "\n".join(out) + "\n"
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    print(text)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--handover", action="store_true")
+    ap.add_argument("--handover-report", action="store_true")
+    ap.add_argument("--root", default=None)
+    ap.add_argument("--parent-runs", default=None)
+    ap.add_argument("--pr-runs", default=None)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--bench-parent", default=None)
     ap.add_argument("--bench-pr", default=None)
     args = ap.parse_args()
+    args.reps = args.reps or (10 if args.handover else 20)
+    if args.handover:
+        return handover_run(args)
+    if args.handover_report:
+        return handover_report(args)
 
     import hgmm_amd
     from hgmm_amd.pointcloud_io import voxel_down_sample
