@@ -160,6 +160,71 @@ def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, variant, 
     return inv, mu, w, cov, [np.float32(v) for v in lls]
 
 
+BATCH_MAX_J = 1024        # hgmm_flat_train_batch: only the one-pass fused path is batched
+
+
+def _batch_member_points(X, b):
+    """Member b's cloud without its weights -- or the refusal: the batched fit takes no per-point weights (a handle owns
+    none), and weights were silently dropped once in this project."""
+    weights = getattr(X, "weights", None)
+    if weights is not None:
+        raise ValueError("train_gmm_batch: member %d brings per-point weights, which the batched fit does not take: fit it "
+                         "with train_gmm(..., sample_weight=)" % b)
+    if hasattr(X, "points") and hasattr(X, "weights") and not isinstance(X, DevicePoints):
+        return X.points                                          # (a WeightedPoints whose weights are None)
+    return X
+
+
+def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, variant):
+    """B independent ``train_gmm`` calls through one launch set (``Context.flat_train_batch``) -> a list of ``train_gmm``'s
+    tuples, member b's bit for bit what ``train_gmm(Xs[b], ...)`` returns.  ``Xs``: host arrays [N,3] (each uploaded into a
+    temporary ``DevicePoints`` and freed afterwards) and / or ``DevicePoints`` of one context (used where they are; one may
+    occur several times: restarts of one resident cloud).  ``means``, ``covariances``, ``weights``: one per member, all of
+    the same J.  A member that brings per-point weights is refused (ValueError naming it).  J > 1024, which the batched
+    entry does not take, falls back to a loop of ``train_gmm``."""
+    Xs = [_batch_member_points(X, b) for b, X in enumerate(Xs)]
+    B = len(Xs)
+    for name, seq in (("means", means), ("covariances", covariances), ("weights", weights)):
+        if len(seq) != B:
+            raise ValueError("train_gmm_batch: %d clouds, but %d arrays in %s" % (B, len(seq), name))
+    if B == 0:
+        return []
+    means, covariances, weights = [_host(m) for m in means], [_host(c) for c in covariances], [_host(w) for w in weights]
+    Js = [np.shape(m)[0] if np.ndim(m) == 2 else -1 for m in means]
+    for b, m in enumerate(means):
+        if np.ndim(m) != 2 or np.shape(m)[1] != 3:
+            raise ValueError("train_gmm_batch: member %d: means must be [J,3], got %s" % (b, np.shape(m)))
+        if Js[b] != Js[0]:
+            raise ValueError("train_gmm_batch: member %d has J = %d, member 0 has J = %d (the members share J)" % (b, Js[b], Js[0]))
+    ctxs = [X.ctx for X in Xs if isinstance(X, DevicePoints)]
+    ctx = ctxs[0] if ctxs else default_context()
+    for b, X in enumerate(Xs):
+        if isinstance(X, DevicePoints) and X.ctx is not ctx:
+            raise ValueError("train_gmm_batch: member %d is a cloud of another context" % b)
+        if not isinstance(X, DevicePoints) and (np.ndim(X) != 2 or np.shape(X)[1] != 3):
+            raise ValueError("train_gmm_batch: member %d: points must have shape [N,3], got %s" % (b, np.shape(X)))
+    if Js[0] > BATCH_MAX_J:
+        return [train_gmm(Xs[b], max_iter, tol, means[b], covariances[b], weights[b], cov_type, variant) for b in range(B)]
+    temporary = []
+    try:
+        clouds = []
+        for X in Xs:
+            if not isinstance(X, DevicePoints):
+                X = DevicePoints(np.asarray(X), ctx)
+                temporary.append(X)
+            clouds.append(X)
+        fits = ctx.flat_train_batch(clouds, max_iter, tol, means, covariances, weights, cov_type, variant)
+    finally:
+        for X in temporary:
+            X.free()
+    out = []
+    for inv, mu, w, cov, lls, converged in fits:
+        if not converged:
+            print('Failed to converge. Increase max-iter or tol.')
+        out.append((inv, mu, w, cov, [np.float32(v) for v in lls]))
+    return out
+
+
 def predict(X, inv_cov, means, weights, cov_type, variant):
     """Array module in = array module out (``xp.argmax``, gmm_impl.py:147-155): a resident cloud gives the labels as a
     DeviceArray (int32 in HBM; nothing is downloaded, nothing waits -- the reference's caller does the

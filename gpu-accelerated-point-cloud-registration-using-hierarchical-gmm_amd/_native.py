@@ -104,6 +104,8 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_flat_train_begin", [ctx, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int])
         _sig(lib, "hgmm_flat_train_step", [ctx, C.c_int])
         _sig(lib, "hgmm_flat_train_end", [ctx, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)])
+        _sig(lib, "hgmm_flat_train_batch", [ctx, C.c_int, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                            _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)])
         _sig(lib, "hgmm_flat_stats", [ctx, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _f64p, _f64p])
         _sig(lib, "hgmm_flat_set_weights", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_build", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int,
@@ -914,6 +916,72 @@ class Context:
                                              float(tol), _ptr(mu), _ptr(cov), _ptr(w), _ptr(inv), _ptr(lls),
                                              C.byref(n_it), C.byref(conv)))
         return inv, mu, w, cov, lls[:n_it.value].copy(), bool(conv.value)
+
+    def _flat_batch_args(self, clouds, mu, cov, w, cov_type):
+        """What flat_train_batch checks on the host, before the library is reached: -> (handles, J, mu [B,J,3], cov, w)."""
+        if cov_type not in COV_TYPES:
+            raise ValueError("cov_type must be one of %s, not %r" % (sorted(COV_TYPES), cov_type))
+        clouds = list(clouds)
+        B = len(clouds)
+        if B < 1:
+            raise ValueError("flat_train_batch: no clouds")
+        handles = []
+        for b, cl in enumerate(clouds):
+            if hasattr(cl, "_h") and hasattr(cl, "ctx"):                # a DevicePoints (hgmm_amd._flat)
+                if cl.ctx is not self:
+                    raise ValueError("flat_train_batch: member %d is a cloud of another context" % b)
+                if getattr(cl, "weights", None) is not None:
+                    raise ValueError("flat_train_batch: member %d brings per-point weights, which the batched fit does not "
+                                     "take (a handle owns none): fit it with flat_train" % b)
+                if cl._h is None:
+                    raise ValueError("flat_train_batch: member %d has been freed" % b)
+                cl = cl._h
+            if not isinstance(cl, _vp) or not cl.value:
+                raise ValueError("flat_train_batch: member %d is neither a DevicePoints nor a points_create handle" % b)
+            handles.append(cl)
+        for name, seq in (("mu", mu), ("cov", cov), ("w", w)):
+            if len(seq) != B:
+                raise ValueError("flat_train_batch: %d clouds, but %d arrays in %s" % (B, len(seq), name))
+        J = None
+        out = ([], [], [])
+        for b in range(B):
+            m = np.ascontiguousarray(mu[b], dtype=np.float32)
+            if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
+                raise ValueError("flat_train_batch: member %d: means must be [J,3], got %s" % (b, m.shape))
+            if J is None:
+                J = m.shape[0]
+            if m.shape[0] != J:
+                raise ValueError("flat_train_batch: member %d has J = %d, member 0 has J = %d (the members share J)"
+                                 % (b, m.shape[0], J))
+            try:
+                out[0].append(m)
+                out[1].append(_f32(cov[b], (J, 3) if cov_type == "diag" else (J,)))
+                out[2].append(_f32(w[b], (J,)))
+            except ValueError as e:
+                raise ValueError("flat_train_batch: member %d: %s" % (b, e)) from None
+        return handles, J, np.stack(out[0]), np.stack(out[1]), np.stack(out[2])
+
+    def flat_train_batch(self, clouds, max_iter, tol, mu, cov, w, cov_type="diag", variant="W"):
+        """B independent fits in one launch set (hgmm_flat_train_batch).  ``clouds``: a sequence of ``DevicePoints`` of this
+        context or of ``points_create`` handles (one may occur several times: restarts); ``mu``, ``cov``, ``w``: sequences or
+        stacked arrays, one initialisation per member, all of the same J <= 1024.  -> a list of
+        ``(inv, mu, w, cov, lls, converged)``, member b's bit for bit what ``flat_train`` returns with that cloud bound and no
+        weights in force.  The bound cloud, its weights and a ``flat_train_begin`` in progress are left alone.  Per-point
+        weights do not enter: a ``DevicePoints`` that brings some is refused (ValueError naming the member)."""
+        handles, J, mu, cov, w = self._flat_batch_args(clouds, mu, cov, w, cov_type)
+        if variant not in VARIANTS:
+            raise ValueError("variant must be one of %s, not %r" % (sorted(VARIANTS), variant))
+        B = len(handles)
+        cap = max(int(max_iter), 1)
+        inv = np.empty_like(cov)
+        lls = np.zeros((B, cap), np.float32)
+        n_it, conv = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._check(self.lib.hgmm_flat_train_batch(
+            self.h, B, (_vp * B)(*[h.value for h in handles]), COV_TYPES[cov_type], VARIANTS[variant], J, int(max_iter),
+            float(tol), _ptr(mu), _ptr(cov), _ptr(w), _ptr(inv), _ptr(lls), n_it.ctypes.data_as(_i32p),
+            conv.ctypes.data_as(_i32p)))
+        return [(inv[b].copy(), mu[b].copy(), w[b].copy(), cov[b].copy(), lls[b, :min(int(n_it[b]), cap)].copy(),
+                 bool(conv[b])) for b in range(B)]
 
     def flat_train_begin(self, tol, mu, cov, w, cov_type="diag", variant="W", lls_capacity=1024):
         J, mu, cov, w = self._flat_args(mu, cov, w, cov_type)

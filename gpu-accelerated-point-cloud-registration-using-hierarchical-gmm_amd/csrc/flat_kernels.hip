@@ -21,6 +21,8 @@
 //                       is the buffer the RCCL all-reduce works on.
 //   flat_finalize_kernel  fp64 M-step (both reference flavours), next E-step's packed
 //                       parameters, log-likelihood trace and the device-side stop rule.
+//   flat_*_batch_kernel   the train loop's four kernels for B clouds per launch (hgmm_flat_train_batch, end of this file):
+//                       the same bodies, each member's arguments read from a table on the device.
 #include "hgmm_ctx.h"
 #include "wave_ops.h"
 
@@ -195,6 +197,18 @@ __device__ __forceinline__ void wave_row_range_uniform(int64_t n, int64_t& r0, i
     wave_row_range(n, r0, r1);
     r0 = uniform_i64(r0);
     nrows = (int)(uniform_i64(r1) - r0);                 // (r1 >= r0 always)
+}
+
+// (the same for workgroup `block` of the `nblocks` that share a cloud in a batched launch, flat_fused_pk_batch_kernel)
+__device__ __forceinline__ void wave_row_range_uniform(int64_t n, unsigned block, unsigned nblocks, int64_t& r0, int& nrows) {
+    const int64_t nw = (int64_t)nblocks * WAVES_PER_BLOCK;
+    const int64_t gw = (int64_t)block * WAVES_PER_BLOCK + wave_in_block();
+    const int64_t per = (n + nw - 1) / nw;
+    int64_t a = gw * per;
+    const int64_t b = a + per < n ? a + per : n;
+    if (a > n) a = n;
+    r0 = uniform_i64(a);
+    nrows = (int)(uniform_i64(b) - r0);
 }
 
 template <bool NT>
@@ -856,291 +870,11 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     float* __restrict__ partials, double* __restrict__ lpn_partials,
     const int* __restrict__ done_flag, int allow_const_shift, int comp_major, const float* __restrict__ SW) {
     if (done_flag && *done_flag) return;
-    constexpr int K = NSLOT;
-    constexpr int KP = K / 2;          // full pairs
-    constexpr bool ODD = (K & 1) != 0; // one trailing single component
-    const int lane = lane_id();
-    f2 mu0[KP + 1], mu1[KP + 1], mu2[KP + 1], g0[KP + 1], g1[KP + 1], g2[KP + 1], cc[KP + 1];
-    f2 s0[KP + 1], a0[KP + 1], a1[KP + 1], a2[KP + 1], b0[KP + 1], b1[KP + 1], b2[KP + 1];
-    float mu0s = 0.f, mu1s = 0.f, mu2s = 0.f, g0s = 0.f, g1s = 0.f, g2s = 0.f, cs = NEG_INF;
-    float s0s = 0.f, a0s = 0.f, a1s = 0.f, a2s = 0.f, b0s = 0.f, b1s = 0.f, b2s = 0.f;
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-        const int ja = (2 * p) * 64 + lane, jb = (2 * p + 1) * 64 + lane;
-        mu0[p] = f2{pack[(PK_MU + 0) * Jpad + ja], pack[(PK_MU + 0) * Jpad + jb]};
-        mu1[p] = f2{pack[(PK_MU + 1) * Jpad + ja], pack[(PK_MU + 1) * Jpad + jb]};
-        mu2[p] = f2{pack[(PK_MU + 2) * Jpad + ja], pack[(PK_MU + 2) * Jpad + jb]};
-        g0[p] = f2{pack[(PK_G + 0) * Jpad + ja], pack[(PK_G + 0) * Jpad + jb]};
-        g1[p] = f2{pack[(PK_G + 1) * Jpad + ja], pack[(PK_G + 1) * Jpad + jb]};
-        g2[p] = f2{pack[(PK_G + 2) * Jpad + ja], pack[(PK_G + 2) * Jpad + jb]};
-        cc[p] = f2{pack[PK_C * Jpad + ja], pack[PK_C * Jpad + jb]};
-        s0[p] = a0[p] = a1[p] = a2[p] = b0[p] = b1[p] = b2[p] = f2{0.f, 0.f};
-    }
-    if (ODD) {
-        const int j = (K - 1) * 64 + lane;
-        mu0s = pack[(PK_MU + 0) * Jpad + j]; mu1s = pack[(PK_MU + 1) * Jpad + j]; mu2s = pack[(PK_MU + 2) * Jpad + j];
-        g0s = pack[(PK_G + 0) * Jpad + j]; g1s = pack[(PK_G + 1) * Jpad + j]; g2s = pack[(PK_G + 2) * Jpad + j];
-        cs = pack[PK_C * Jpad + j];
-    }
-
-    // largest constant of the table = upper bound of every wl2 (identical in every wave)
-    // (m0 and the origin below are derived by EVERY wave, from the table it has just loaded, and not once by the kernel
-    //  that writes the table: flat_finalize_kernel, flat_boundary_kernel, flat_finalize_mb_kernel and flat_pack_kernel
-    //  all write it from several workgroups, so one wave could only derive them behind a cross-workgroup hand-off --
-    //  a ticket and agent-scope fences, microseconds on the latency chain between two iterations -- or in one more
-    //  launch, against ~130 vector instructions per wave here, less than one of its ~1000 rows)
-    float m0 = cs;
-#pragma unroll
-    for (int p = 0; p < KP; ++p) m0 = fmaxf(m0, fmaxf(cc[p].x, cc[p].y));
-    m0 = wave_max_dpp(m0);
-    // (false for NaN as well; below -64 the row-maximum loop's "tiny" rule applies, see lpn2_from)
-    const bool small_shift = allow_const_shift && m0 <= CS_MAX_SHIFT && m0 >= -64.0f;
-
-    // row range and loop control in scalar registers (wave_row_range_uniform)
-    int64_t r0;
-    int nrows;
-    wave_row_range_uniform(n, r0, nrows);
-    const float* const xw = X + 3 * r0;
-    double lsum = 0.0;
-    // First moments are summed about ONE origin for all components and moved to the component's mean when the wave is
-    // done:  sum r (x - mu) = sum r (x - o) - (mu - o) sum r.  The row's x - o is a wave-uniform operand, so the update
-    // is one packed FMA per axis -- and the squares (x - mu)^2 the quadratic form needs anyway are what the second
-    // moments need: the per-component differences themselves do not have to survive the row's reduction.  18 instead of
-    // 21 packed instructions per pair of components (round 4: 0.374 -> 0.33 ms at C3).  The origin is the weighted mean
-    // of the component means (every wave derives the same one from the table) -- inside the model whatever the
-    // coordinates' offset and whatever outliers the cloud has.  The price: a first moment's
-    // rounding error is relative to the MODEL's extent instead of the component's, 2^-24 |x - o| per addition -- the
-    // reference's own float32 resp.T @ X has it relative to |x| (tests: test_fit_far_from_the_origin,
-    // test_train_far_points_and_mixed_scales).
-    // ... WEIGHTED by the mixing weights (table row PK_W; 0 for padding, dead and non-finite components): a component
-    // that has lost its points sits wherever its last M-step left it -- at the coordinate origin, which for a cloud in
-    // map coordinates is kilometres outside the model -- and must not pull the common origin (and with it every
-    // component's rounding error) towards itself.
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f, ow = 0.f;
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-        const float wa = pack[PK_W * Jpad + (2 * p) * 64 + lane], wb = pack[PK_W * Jpad + (2 * p + 1) * 64 + lane];
-        o0 = fmaf(wa, mu0[p].x, fmaf(wb, mu0[p].y, o0));
-        o1 = fmaf(wa, mu1[p].x, fmaf(wb, mu1[p].y, o1));
-        o2 = fmaf(wa, mu2[p].x, fmaf(wb, mu2[p].y, o2));
-        ow += wa + wb;
-    }
-    if (ODD) {
-        const float ws = pack[PK_W * Jpad + (K - 1) * 64 + lane];
-        o0 = fmaf(ws, mu0s, o0); o1 = fmaf(ws, mu1s, o1); o2 = fmaf(ws, mu2s, o2);
-        ow += ws;
-    }
-    {
-        ow = wave_sum_dpp(ow);
-        const float inv_w = ow > 0.f ? 1.0f / ow : 0.f;      // (no usable component at all: the coordinate origin)
-        o0 = wave_sum_dpp(o0) * inv_w; o1 = wave_sum_dpp(o1) * inv_w; o2 = wave_sum_dpp(o2) * inv_w;
-        if (!(fabsf(o0) < 3.0e38f)) o0 = 0.f;
-        if (!(fabsf(o1) < 3.0e38f)) o1 = 0.f;
-        if (!(fabsf(o2) < 3.0e38f)) o2 = 0.f;
-    }
-    // the row loop exists twice in this kernel, once per log-sum-exp variant; the choice is uniform
-    // over the whole grid (every wave derives the same m0 from the table)
-    auto rows = [&](auto cs_tag) {
-    constexpr bool CS = decltype(cs_tag)::value;
-    if (CS) {
-        const f2 M0 = f2{m0, m0};
-#pragma unroll
-        for (int p = 0; p < KP; ++p) cc[p] = cc[p] - M0;
-        cs -= m0;
-    }
-    const float eps_scale = __builtin_amdgcn_exp2f(-m0);
-    // FLAT_EPS in a vector register: the denominator's FMA below then reads the row's sum straight from the scalar
-    // register the wave reduction left it in (one v_fma_f32; an inline literal would need the sum copied to a VGPR first)
-    float eps_v = FLAT_EPS;
-    asm volatile("" : "+v"(eps_v));
-    float lacc = 0.f;                      // sum of log2(den) of the rows since the last flush
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    float sw = 1.f;                        // (WEIGHTED) this row's weight
-    double swsum = 0.0;                    // (WEIGHTED) sum of the weights of this wave's rows
-    if (nrows > 0) { x0 = xw[0]; x1 = xw[1]; x2 = xw[2]; if (WEIGHTED) sw = SW[r0]; }
-    for (int row = 0; row < nrows; ++row) {                 // (row: counted from the wave's first one)
-        const int nrow = (row + 1 < nrows) ? row + 1 : row;
-        const float* xn = xw + 3 * (int64_t)nrow;
-        const float nx0 = xn[0], nx1 = xn[1], nx2 = xn[2];
-        float nsw = 1.f;
-        if constexpr (WEIGHTED) nsw = SW[r0 + nrow];
-        // (WEIGHTED) a row of weight zero is absent, whatever its coordinates: a wave-uniform branch round the row's work
-        if (!WEIGHTED || !weight_is_zero(sw)) {
-            const f2 X0 = f2{x0, x0}, X1 = f2{x1, x1}, X2 = f2{x2, x2};
-            const float xo0 = x0 - o0, xo1 = x1 - o1, xo2 = x2 - o2;
-            const f2 XO0 = f2{xo0, xo0}, XO1 = f2{xo1, xo1}, XO2 = f2{xo2, xo2};
-
-            f2 wl[KP + 1];
-            f2 q0[KP + 1], q1[KP + 1], q2[KP + 1];
-            float q0s = 0.f, q1s = 0.f, q2s = 0.f;
-            float wls = NEG_INF;
-            float m = NEG_INF;
-            f2 sacc = f2{0.f, 0.f};
-#pragma unroll
-            for (int p = 0; p < KP; ++p) {
-                const f2 d0 = X0 - mu0[p], d1 = X1 - mu1[p], d2 = X2 - mu2[p];
-                q0[p] = d0 * d0; q1[p] = d1 * d1; q2[p] = d2 * d2;
-                f2 a = cc[p] - g0[p] * q0[p];
-                a = a - g1[p] * q1[p];
-                a = a - g2[p] * q2[p];
-                if (CS) {
-                    wl[p] = f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-                    // (the first pair starts the sum: 0 + 2^a is 2^a bit for bit -- an exponential is never -0 --
-                    //  and one packed addition fewer)
-                    sacc = p == 0 ? wl[p] : sacc + wl[p];
-                } else {
-                    wl[p] = a;
-                    m = fmaxf(m, fmaxf(a.x, a.y));
-                }
-            }
-            if (ODD) {
-                const float d0 = x0 - mu0s, d1 = x1 - mu1s, d2 = x2 - mu2s;
-                q0s = d0 * d0; q1s = d1 * d1; q2s = d2 * d2;
-                float a = fmaf(-g0s, q0s, cs);
-                a = fmaf(-g1s, q1s, a);
-                a = fmaf(-g2s, q2s, a);
-                wls = CS ? __builtin_amdgcn_exp2f(a) : a;
-                m = fmaxf(m, a);
-            }
-            if (CS) {
-                m = m0;
-            } else {
-                m = wave_max_dpp(m);
-                if (m == NEG_INF) m = 0.f;
-                const f2 M = f2{m, m};
-#pragma unroll
-                for (int p = 0; p < KP; ++p) {
-                    const f2 t = wl[p] - M;
-                    wl[p] = f2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                    sacc = p == 0 ? wl[p] : sacc + wl[p];
-                }
-                if (ODD) wls = __builtin_amdgcn_exp2f(wls - m);
-            }
-            float s = sacc.x + sacc.y;
-            if (ODD) s += wls;
-            s = wave_sum_dpp(s);
-            float inv_den;
-            if (CS) {
-                // lpn2_from with m = m0 in [-64, CS_MAX_SHIFT]: no "tiny" case, eps 2^-m0 is loop-invariant;
-                // the log-normalisers are summed in float32 over 8 rows before they join the float64 total
-                const float den = fmaf(eps_v, eps_scale, s);
-                inv_den = __builtin_amdgcn_rcpf(den);
-                if constexpr (WEIGHTED) lacc = fmaf(sw, __builtin_amdgcn_logf(den), lacc);
-                else lacc += __builtin_amdgcn_logf(den);
-                if constexpr (!WEIGHTED) {
-                    if ((row & 7) == 7) {
-                        asm volatile("" ::: "memory");          // keeps this a (wave-uniform) branch, not selects
-                        lsum += (double)lacc;
-                        lacc = 0.f;
-                    }
-                }
-            } else {
-                const float lpn2 = lpn2_from(m, s, inv_den);
-                if constexpr (WEIGHTED) lsum += (double)sw * (double)(lpn2 * LN2);
-                else lsum += (double)(lpn2 * LN2);
-            }
-            if constexpr (WEIGHTED) inv_den *= sw;
-            const f2 INV = f2{inv_den, inv_den};
-#pragma unroll
-            for (int p = 0; p < KP; ++p) {
-                const f2 rr = wl[p] * INV;
-                s0[p] += rr;
-                a0[p] += rr * XO0; a1[p] += rr * XO1; a2[p] += rr * XO2;
-                b0[p] += rr * q0[p]; b1[p] += rr * q1[p]; b2[p] += rr * q2[p];
-            }
-            if (ODD) {
-                const float rr = wls * inv_den;
-                s0s += rr;
-                a0s = fmaf(rr, xo0, a0s); a1s = fmaf(rr, xo1, a1s); a2s = fmaf(rr, xo2, a2s);
-                b0s = fmaf(rr, q0s, b0s); b1s = fmaf(rr, q1s, b1s); b2s = fmaf(rr, q2s, b2s);
-            }
-        }
-        if constexpr (WEIGHTED) {
-            // the 8-row flush of lacc, on the rows' schedule whether this one was skipped or not (ONE site for both paths:
-            // a second one in the skipped path cost <13, true> 45 AGPRs and its second wave per SIMD)
-            if (CS && (row & 7) == 7) {
-                asm volatile("" ::: "memory");
-                lsum += (double)lacc;
-                lacc = 0.f;
-            }
-        }
-        x0 = nx0; x1 = nx1; x2 = nx2;
-        if constexpr (WEIGHTED) sw = nsw;
-    }
-    if constexpr (WEIGHTED) {
-        // the closing term's sum of the wave's weights, float64, taken here and not in the loop (two registers the loop
-        // does not have); zero weights add nothing
-        if (CS) {
-            for (int64_t i = r0 + lane; i < r0 + nrows; i += 64) swsum += (double)SW[i];
-            swsum = wave_sum_f64(swsum);
-        }
-    }
-    if (CS) lsum = (lsum + (double)lacc + (WEIGHTED ? swsum : (double)nrows) * (double)m0) * (double)LN2;
-    };
-    if (small_shift) rows(std::true_type{});
-    else rows(std::false_type{});
-    // first moments: from the common origin to the component's mean
-    {
-        const f2 O0 = f2{o0, o0}, O1 = f2{o1, o1}, O2 = f2{o2, o2};
-#pragma unroll
-        for (int p = 0; p < KP; ++p) {
-            a0[p] -= (mu0[p] - O0) * s0[p]; a1[p] -= (mu1[p] - O1) * s0[p]; a2[p] -= (mu2[p] - O2) * s0[p];
-        }
-        if (ODD) {
-            a0s = fmaf(-(mu0s - o0), s0s, a0s); a1s = fmaf(-(mu1s - o1), s0s, a1s); a2s = fmaf(-(mu2s - o2), s0s, a2s);
-        }
-    }
-
-    // (a statistic's LDS row is padded by 8 words: the component-major copy below has a wave read 8 components x 8
-    //  rows at once, and NSLOT * 64 words apart all rows of a component would share one bank)
-    // The four waves' sums meet in the fixed order ((w0 + w1) + w2) + w3 -- what makes a partial reproducible -- over THREE
-    // LDS copies of the block: waves 0, 2 and 3 store theirs side by side, wave 1 then adds into wave 0's copy, and the
-    // output loop adds the three copies in that order on its way out.  Two barriers where four turns on one copy took
-    // four, and the same bits.  (Four copies and one barrier do not fit: 4 x 23.5 KB at NSLOT = 13, twice per CU, is
-    // more than the 160 KB; three copies leave every NSLOT the workgroups per CU its registers allow.)
-    constexpr int ST = NSLOT * 64, STP = ST + 8, CP = FLAT_NSTAT * STP;
-    __shared__ float sh[3 * CP];
-    __shared__ double shl[WAVES_PER_BLOCK];
-    const int w = wave_in_block();
-    if (lane == 0) shl[w] = lsum;
-    auto put = [&](float* base, int k, bool first, float v0, float v1, float v2, float v3, float v4, float v5, float v6) {
-        float* q = base + k * 64 + lane;
-        if (first) { q[0 * STP] = v0; q[1 * STP] = v1; q[2 * STP] = v2; q[3 * STP] = v3; q[4 * STP] = v4; q[5 * STP] = v5; q[6 * STP] = v6; }
-        else { q[0 * STP] += v0; q[1 * STP] += v1; q[2 * STP] += v2; q[3 * STP] += v3; q[4 * STP] += v4; q[5 * STP] += v5; q[6 * STP] += v6; }
-    };
-    auto put_all = [&](float* base, bool first) {
-#pragma unroll
-        for (int p = 0; p < KP; ++p) {
-            put(base, 2 * p, first, s0[p].x, a0[p].x, a1[p].x, a2[p].x, b0[p].x, b1[p].x, b2[p].x);
-            put(base, 2 * p + 1, first, s0[p].y, a0[p].y, a1[p].y, a2[p].y, b0[p].y, b1[p].y, b2[p].y);
-        }
-        if (ODD) put(base, K - 1, first, s0s, a0s, a1s, a2s, b0s, b1s, b2s);
-    };
-    if (w != 1) put_all(sh + (w == 0 ? 0 : w - 1) * CP, true);
-    __syncthreads();
-    if (w == 1) put_all(sh, false);
-    __syncthreads();
-    auto total = [&](int i) { return (sh[i] + sh[CP + i]) + sh[2 * CP + i]; };
-    if (comp_major) {
-        // [block][Jpad][8]: a component's 7 statistics + one pad word are 32 contiguous bytes, 8 components -- what a
-        // workgroup of flat_boundary_kernel owns -- 256 (the train loop without a communicator; kernel-uniform)
-        float* outp = partials + (size_t)blockIdx.x * FLAT_CM_STRIDE * Jpad;
-        for (int idx = threadIdx.x; idx < FLAT_CM_STRIDE * ST; idx += BLOCK) {
-            const int j = idx / FLAT_CM_STRIDE, st = idx % FLAT_CM_STRIDE;
-            outp[idx] = st < FLAT_NSTAT ? total(st * STP + j) : 0.f;
-        }
-    } else {
-        float* outp = partials + (size_t)blockIdx.x * FLAT_NSTAT * Jpad;
-        for (int idx = threadIdx.x; idx < FLAT_NSTAT * ST; idx += BLOCK) {
-            const int st = idx / ST, j = idx % ST;
-            outp[st * Jpad + j] = total(st * STP + j);
-        }
-    }
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < WAVES_PER_BLOCK; ++i) t += shl[i];
-        lpn_partials[blockIdx.x] = t;
-    }
+#define FLAT_FUSED_BLOCK blockIdx.x
+#define FLAT_FUSED_ROW_RANGE(n, r0, nrows) wave_row_range_uniform(n, r0, nrows)
+#include "flat_fused_body.h"
+#undef FLAT_FUSED_BLOCK
+#undef FLAT_FUSED_ROW_RANGE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1521,10 +1255,10 @@ constexpr int RED_BATCH = 16;    // loads a thread has in flight: 512 workgroups
 // This kernel sits between two EM iterations and is nothing but latency: every load is issued before the first
 // add (index clamped, value masked -- no branch between the loads), the stop flag is fetched alongside and only
 // gates the store.
-__global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_kernel(
-    const float* __restrict__ partials, const double* __restrict__ lpn_partials, int nblocks,
-    int n_lpn_blocks, int valid_j, int Jpad, double n_local, double* __restrict__ stats,
-    const int* __restrict__ done_flag) {
+// (the body, stated once for flat_reduce_kernel and flat_reduce_batch_kernel)
+__device__ __forceinline__ void flat_reduce_body(
+    const float* partials, const double* lpn_partials, int nblocks, int n_lpn_blocks, int valid_j, int Jpad,
+    double n_local, double* stats, const int* done_flag) {
     // (an atomic load is a VECTOR load: it is waited for where `done` is used, a scalar load would be waited for
     //  at the next kernel-argument fetch, i.e. before the partials' loads are even issued)
     // (fetched through a per-lane address the compiler cannot prove uniform: a uniform value would be moved to an
@@ -1576,6 +1310,12 @@ __global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_kernel(
             stats[total + 1] = n_local;
         }
     }
+}
+__global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_kernel(
+    const float* __restrict__ partials, const double* __restrict__ lpn_partials, int nblocks,
+    int n_lpn_blocks, int valid_j, int Jpad, double n_local, double* __restrict__ stats,
+    const int* __restrict__ done_flag) {
+    flat_reduce_body(partials, lpn_partials, nblocks, n_lpn_blocks, valid_j, Jpad, n_local, stats, done_flag);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1682,8 +1422,9 @@ __device__ inline void ctl_update(const double* __restrict__ stats, int Jpad, fl
 // nothing in this launch writes -- and thread 0 records its verdict in `stop_next` = flag[(k + 1) & 1], the word
 // the kernels of iteration k + 1 look at.  (With ONE flag a workgroup that starts late could see the verdict of its
 // own launch and skip its share of the update.)
-__global__ __launch_bounds__(256) void flat_finalize_kernel(const double* __restrict__ stats,
-                                     const float* __restrict__ centre /*[3][Jpad] or pack mu rows*/,
+// (the body, stated once for flat_finalize_kernel and flat_finalize_batch_kernel)
+__device__ __forceinline__ void flat_finalize_body(const double* stats,
+                                     const float* centre /*[3][Jpad] or pack mu rows*/,
                                      int J, int Jpad, int cov_type, int variant,
                                      float* mu, float* cov, float* w, float* inv, float* pack,
                                      float* lls, int lls_cap, float tol, int* ctl, float* ctl_f,
@@ -1699,6 +1440,15 @@ __global__ __launch_bounds__(256) void flat_finalize_kernel(const double* __rest
     if (j < J) store_component(j, r, cov_type, mu, cov, w, inv);
     if (pack && j < Jpad) pack_values(j, j < J, Jpad, variant, r.mu, r.inv, r.w, pack);
     if (j == 0 && ctl) ctl_update(stats, Jpad, lls, lls_cap, tol, ctl, ctl_f, stop_next);
+}
+__global__ __launch_bounds__(256) void flat_finalize_kernel(const double* __restrict__ stats,
+                                     const float* __restrict__ centre /*[3][Jpad] or pack mu rows*/,
+                                     int J, int Jpad, int cov_type, int variant,
+                                     float* mu, float* cov, float* w, float* inv, float* pack,
+                                     float* lls, int lls_cap, float tol, int* ctl, float* ctl_f,
+                                     const int* stop /*never null*/, int* stop_next /*null: no device loop*/) {
+    flat_finalize_body(stats, centre, J, Jpad, cov_type, variant, mu, cov, w, inv, pack, lls, lls_cap, tol, ctl, ctl_f, stop,
+                       stop_next);
 }
 
 // Everything between two iterations of the train loop in ONE launch: flat_reduce_kernel's sums, flat_finalize_kernel's
@@ -1872,15 +1622,16 @@ __global__ void flat_hint_const_kernel(float c0, float c1, float c2, int Jpad, f
 // ------------------------------------------------------------------------------------------
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-static int grid_for(hgmm_ctx* c, int64_t n, int blocks_per_cu) {
+static int grid_for_cus(int cus, int64_t n, int blocks_per_cu) {
     int64_t want = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;     // one row per wave at least
     if (blocks_per_cu < 1) blocks_per_cu = 1;
     if (blocks_per_cu > 8) blocks_per_cu = 8;
-    int64_t cap = (int64_t)c->cus * blocks_per_cu;
+    int64_t cap = (int64_t)cus * blocks_per_cu;
     if (cap > FLAT_MAX_BLOCKS) cap = FLAT_MAX_BLOCKS;
     int64_t g = want < cap ? want : cap;
     return (int)(g < 1 ? 1 : g);
 }
+static int grid_for(hgmm_ctx* c, int64_t n, int blocks_per_cu) { return grid_for_cus(c->cus, n, blocks_per_cu); }
 
 static int flat_check(hgmm_ctx* c, int cov_type, int variant, int J) {
     if (!c->have_f32 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "flat EM: call hgmm_set_points_f32 first");
@@ -2294,26 +2045,30 @@ static auto fused_kernel_for(int slots, bool weighted, std::integer_sequence<int
     return kernel;
 }
 
+// The fused kernel's grid for a cloud of n points and ns = ceil(J / 64) component slots on a chip of `cus` CUs: ONE rule for
+// the launch of one cloud (launch_fused) and for every member of a batched launch (hgmm_flat_train_batch), whose partials
+// must be the serial launch's partials.
+static int fused_grid(int cus, int64_t n, int ns) {
+    // Two workgroups per CU are the floor (a small cloud wants every CU busy: bun000 is fastest at 512 workgroups of
+    // 20 rows per wave, tools/bunny_grid.py); a large cloud takes more, as long as a wave keeps ~100 rows: J = 800 (254
+    // registers, two waves per SIMD resident either way) gains 1.6 % from 4 per CU -- a finer tail -- and small J, whose
+    // lanes hold few components and leave the register file empty, gain 10 - 28 % from 6 - 8 per CU: more resident waves
+    // hide the row's reduction chain (N = 1e6: J = 64 0.105 -> 0.075 ms per iteration, J = 100 0.117 -> 0.098, J = 400
+    // 0.227 -> 0.202; profiles/r04/fused_bpc_by_J.log).  More workgroups are more partials for the reduction to read:
+    // the iteration times above include it.
+    const int bpc_max = ns <= 4 ? 8 : (ns <= 8 ? 6 : 4);
+    const int64_t by_rows = n / (WAVES_PER_BLOCK * 100);
+    const int64_t big = std::min<int64_t>(by_rows, std::min<int64_t>((int64_t)cus * bpc_max, FLAT_MAX_BLOCKS));
+    return (int)std::max<int64_t>(grid_for_cus(cus, n, 2), big);
+}
+
 // comp_major: the partials' layout, [block][Jpad][8] for flat_boundary_kernel instead of [block][7][Jpad] for flat_reduce_kernel
 static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* valid_j, bool comp_major) {
     note_launch(c, FLAT_K_FUSED);
     const FlatState& f = c->flat;
     if (!done_flag) done_flag = c->f_ctl.as<int>() + 16;        // always 0 (flat_setup)
     const int ns = (f.J + 63) / 64;
-    // Grid.  Two workgroups per CU are the floor (a small cloud wants every CU busy: bun000 is fastest at 512 workgroups of
-    // 20 rows per wave, tools/bunny_grid.py); a large cloud takes more, as long as a wave keeps ~100 rows: J = 800 (254
-    // registers, two waves per SIMD resident either way) gains 1.6 % from 4 per CU -- a finer tail -- and small J, whose
-    // lanes hold few components and leave the register file empty, gain 10 - 28 % from 6 - 8 per CU: more resident waves
-    // hide the row's reduction chain (N = 1e6: J = 64 0.105 -> 0.075 ms per iteration, J = 100 0.117 -> 0.098, J = 400
-    // 0.227 -> 0.202; profiles/r04/fused_bpc_by_J.log).  More workgroups are more partials for the reduction to read:
-    // the iteration times above include it.  
-    int grid;
-    {
-        const int bpc_max = ns <= 4 ? 8 : (ns <= 8 ? 6 : 4);
-        const int64_t by_rows = c->n / (WAVES_PER_BLOCK * 100);
-        const int64_t big = std::min<int64_t>(by_rows, std::min<int64_t>((int64_t)c->cus * bpc_max, FLAT_MAX_BLOCKS));
-        grid = (int)std::max<int64_t>(grid_for(c, c->n, 2), big);
-    }
+    const int grid = fused_grid(c->cus, c->n, ns);
     *grid_out = grid;
     const float* X = c->x_aos.as<float>();
     const float* pk = c->f_pack.as<float>();
@@ -2824,9 +2579,9 @@ extern "C" int hgmm_elementwise_f32(hgmm_ctx* c, int op, int64_t n, const float*
 // Everything a fit needs before its first iteration, in ONE launch: initial inv_std from the covariances, the packed
 // table from them, the loop's control words.  (Three launches before round 4; at the start of a call -- the stream has
 // been idle -- each of them came with ~13 us of launch latency: 40 us of a 620 us bun000 fit.)
-__global__ void flat_begin_kernel(int J, int Jpad, int cov_type, int variant, const float* __restrict__ mu,
-                                  const float* __restrict__ cov, const float* __restrict__ w, float* __restrict__ inv,
-                                  float* __restrict__ pack, int* __restrict__ ctl, float* __restrict__ ctl_f) {
+// (the body, stated once for flat_begin_kernel and flat_begin_batch_kernel)
+__device__ __forceinline__ void flat_begin_body(int J, int Jpad, int cov_type, int variant, const float* mu,
+                                  const float* cov, const float* w, float* inv, float* pack, int* ctl, float* ctl_f) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j == 0) {
         ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
@@ -2847,6 +2602,11 @@ __global__ void flat_begin_kernel(int J, int Jpad, int cov_type, int variant, co
         wj = w[j];
     }
     pack_values(j, j < J, Jpad, variant, m, i, wj, pack);
+}
+__global__ void flat_begin_kernel(int J, int Jpad, int cov_type, int variant, const float* __restrict__ mu,
+                                  const float* __restrict__ cov, const float* __restrict__ w, float* __restrict__ inv,
+                                  float* __restrict__ pack, int* __restrict__ ctl, float* __restrict__ ctl_f) {
+    flat_begin_body(J, Jpad, cov_type, variant, mu, cov, w, inv, pack, ctl, ctl_f);
 }
 
 extern "C" int hgmm_flat_train_begin(hgmm_ctx* c, int cov_type, int variant, int J, float tol,
@@ -2996,5 +2756,253 @@ extern "C" int hgmm_flat_stats(hgmm_ctx* c, int cov_type, int variant, int J, co
             for (int s = 0; s < FLAT_NSTAT; ++s) stats_out[(size_t)j * FLAT_NSTAT + s] = h[(size_t)s * f.Jpad + j];
     if (sum_lpn_out) *sum_lpn_out = h[(size_t)FLAT_NSTAT * f.Jpad];
     if (n_points_out) *n_points_out = h[(size_t)FLAT_NSTAT * f.Jpad + 1];
+    return HGMM_OK;
+}
+
+// ==========================================================================================
+// Batched fit: B independent clouds, one launch set (include/hgmm.h: hgmm_flat_train_batch)
+// ==========================================================================================
+// Member b is the serial loop above on clouds[b] -- the same grid (fused_grid), the same bodies (flat_begin_body,
+// flat_fused_body.h, flat_reduce_body, flat_finalize_body), the same partials, slices and orders of summation, the same
+// control words -- so its results are the serial entry's bit for bit, whatever B is and whoever its neighbours are.  What the
+// serial kernels take as arguments the batched ones read from the member's row of a table (FlatBatchMember, hgmm_ctx.h):
+// wave-uniform scalar loads at the head of the kernel.  A member that has stopped returns from every later launch at the
+// stop word, as the serial kernels do.
+//
+// A pointer read from memory is a generic pointer to the compiler, and a generic pointer is dereferenced by flat_load: no
+// scalar loads for the row's coordinates, no global_load for the table.  The table holds device allocations only, so the
+// pointer is rebuilt from its bits as a pointer into the global address space -- what a kernel argument is by itself.  (Through
+// the integer: a cast to the global address space and back is folded away before the address spaces are inferred.)
+template <class T>
+__device__ __forceinline__ T* global_ptr(T* p) {
+    typedef __attribute__((address_space(1))) T* gptr;
+    return (T*)(gptr)(uintptr_t)p;
+}
+// ... and the cloud, which nothing writes while a fit runs, as a pointer into the CONSTANT address space: a wave-uniform load
+// from it is a scalar load whatever else the kernel does (the serial kernel's `const float* __restrict__ X` argument says as
+// much; behind a plain global pointer the row loop's compiler barrier counts as a possible store, and the row's coordinates
+// arrive by vector loads into six more registers)
+template <class T>
+__device__ __forceinline__ const T* constant_ptr(const T* p) {
+    typedef __attribute__((address_space(4))) const T* cptr;
+    return (const T*)(cptr)(uintptr_t)p;
+}
+
+// One workgroup of member `me.x`, the member's workgroup number `me.y`: ONE 8-byte load, then the member's row.  (A search
+// over the members' first blocks would be a dozen dependent loads at the head of a kernel whose waves have 20 rows of work.)
+// Unweighted: a handle owns no weights.  The partials are stat-major (comp_major = 0: the boundary kernel is not batched); the
+// choice between the constant-shift and the row-maximum loop is each wave's, from its member's table.
+template <int NSLOT>
+__global__ __launch_bounds__(BLOCK) void flat_fused_pk_batch_kernel(
+    const FlatBatchMember* __restrict__ members, const int2* __restrict__ wg_table, int J, int Jpad, int parity) {
+    const int2 me = wg_table[blockIdx.x];
+    const FlatBatchMember& m = members[me.x];
+    if (global_ptr(m.ctl)[parity ? 3 : 0]) return;
+    constexpr bool WEIGHTED = false;
+    const float* const X = constant_ptr(m.X);
+    const float* const pack = global_ptr(m.pack);
+    float* const partials = global_ptr(m.partials);
+    double* const lpn_partials = global_ptr(m.lpn_partials);
+    const float* const SW = nullptr;
+    const int64_t n = m.n;
+    const unsigned block = (unsigned)me.y, nblocks = (unsigned)m.nblocks;
+    constexpr int allow_const_shift = 1, comp_major = 0;
+#define FLAT_FUSED_BLOCK block
+#define FLAT_FUSED_ROW_RANGE(n, r0, nrows) wave_row_range_uniform(n, block, nblocks, r0, nrows)
+#include "flat_fused_body.h"
+#undef FLAT_FUSED_BLOCK
+#undef FLAT_FUSED_ROW_RANGE
+}
+
+// blockIdx.y = member in the three small kernels; blockIdx.x is what it is in the serial launch
+__global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_batch_kernel(
+    const FlatBatchMember* __restrict__ members, int valid_j, int Jpad, int parity) {
+    const FlatBatchMember& m = members[blockIdx.y];
+    flat_reduce_body(global_ptr(m.partials), global_ptr(m.lpn_partials), m.nblocks, m.nblocks, valid_j, Jpad, (double)m.n,
+                     global_ptr(m.stats), global_ptr(m.ctl) + (parity ? 3 : 0));
+}
+
+// (the stop flag: double-buffered by iteration parity per member, see flat_finalize_kernel)
+__global__ __launch_bounds__(256) void flat_finalize_batch_kernel(
+    const FlatBatchMember* __restrict__ members, int J, int Jpad, int cov_type, int variant, int lls_cap, float tol,
+    int parity) {
+    const FlatBatchMember& m = members[blockIdx.y];
+    float* blk = global_ptr(m.params);
+    float* pack = global_ptr(m.pack);
+    int* ctl = global_ptr(m.ctl);
+    flat_finalize_body(global_ptr(m.stats), pack + PK_MU * Jpad, J, Jpad, cov_type, variant, blk + 3 * (size_t)Jpad, blk,
+                       blk + 6 * (size_t)Jpad, blk + 7 * (size_t)Jpad, pack, global_ptr(m.lls), lls_cap, tol, ctl,
+                       reinterpret_cast<float*>(ctl + 8), ctl + (parity ? 3 : 0), ctl + (parity ? 0 : 3));
+}
+
+__global__ void flat_begin_batch_kernel(const FlatBatchMember* __restrict__ members, int J, int Jpad, int cov_type,
+                                        int variant) {
+    const FlatBatchMember& m = members[blockIdx.y];
+    float* blk = global_ptr(m.params);
+    int* ctl = global_ptr(m.ctl);
+    flat_begin_body(J, Jpad, cov_type, variant, blk + 3 * (size_t)Jpad, blk, blk + 6 * (size_t)Jpad, blk + 7 * (size_t)Jpad,
+                    global_ptr(m.pack), ctl, reinterpret_cast<float*>(ctl + 8));
+}
+
+template <int... S>
+static auto fused_batch_kernel_for(int slots, std::integer_sequence<int, S...>) {
+    decltype(&flat_fused_pk_batch_kernel<1>) kernel = nullptr;
+    ((slots == S + 1 ? (void)(kernel = flat_fused_pk_batch_kernel<S + 1>) : (void)0), ...);
+    return kernel;
+}
+
+extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clouds, int cov_type, int variant, int J,
+                                     int max_iter, float tol, float* mu, float* cov, float* w, float* inv_std_out,
+                                     float* lls_out, int32_t* n_iter_out, int32_t* converged_out) {
+    HGMM_ENTER(c);
+    const char* what = "hgmm_flat_train_batch";
+    // ---- refusals: all of them before anything resident is touched ----
+    if (B < 1 || B > FLAT_BATCH_MAX) return fail(c, HGMM_ERR_ARG, "%s: B = %d outside 1..%d", what, B, FLAT_BATCH_MAX);
+    if (!clouds) return fail(c, HGMM_ERR_ARG, "%s: clouds is NULL", what);
+    for (int b = 0; b < B; ++b) {
+        const hgmm_points* p = clouds[b];
+        if (!p) return fail(c, HGMM_ERR_ARG, "%s: member %d is NULL", what, b);
+        if (p->ctx != c && p != &c->own_points)
+            return fail(c, HGMM_ERR_ARG, "%s: member %d belongs to another context", what, b);
+        if (p->n < 1 || !p->x_aos.p) return fail(c, HGMM_ERR_ARG, "%s: member %d holds no points", what, b);
+    }
+    if (!mu || !cov || !w || !n_iter_out || !converged_out)
+        return fail(c, HGMM_ERR_ARG, "%s: mu, cov, w, n_iter_out and converged_out must not be NULL", what);
+    if (max_iter < 0) return fail(c, HGMM_ERR_ARG, "max_iter < 0");
+    if (cov_type != HGMM_COV_DIAG && cov_type != HGMM_COV_SPHERICAL)
+        return fail(c, HGMM_ERR_ARG, "cov_type must be 0 (diag) or 1 (spherical)");
+    if (variant != HGMM_VARIANT_W && variant != HGMM_VARIANT_G)
+        return fail(c, HGMM_ERR_ARG, "variant must be 0 (W) or 1 (G)");
+    if (variant == HGMM_VARIANT_G && cov_type != HGMM_COV_DIAG)
+        return fail(c, HGMM_ERR_ARG, "variant G (gmmreg_gpu) is diag-only");
+    if (J < 1 || J > FLAT_MAX_J)
+        return fail(c, HGMM_ERR_ARG, "%s: J = %d outside 1..%d: only the one-pass fused path is batched, the chunked path of "
+                    "larger J stays serial (hgmm_flat_train, cloud by cloud)", what, J, FLAT_MAX_J);
+    if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "%s: not under a communicator (the batch all-reduces nothing)", what);
+
+    const int Jpad = round_up(J, 256);
+    const int slots = (J + 63) / 64, valid_j = slots * 64;
+    const int lls_cap = max_iter < 1 ? 1 : max_iter;
+    const size_t ce = cov_elems(cov_type, J);
+    const size_t blk_elems = 10 * (size_t)Jpad, pack_elems = (size_t)PK_ROWS * Jpad, part_elems = (size_t)FLAT_NSTAT * Jpad;
+    const size_t stat_elems = part_elems + 2;
+    // the members' grids: the serial launch's grid for n_b, back to back in the fused launch
+    std::vector<FlatBatchMember> tab((size_t)B);
+    size_t total_grid = 0;
+    for (int b = 0; b < B; ++b) {
+        tab[b].n = clouds[b]->n;
+        tab[b].block0 = (int)total_grid;
+        tab[b].nblocks = fused_grid(c->cus, clouds[b]->n, slots);
+        total_grid += (size_t)tab[b].nblocks;
+    }
+    const unsigned long long part_bytes = (unsigned long long)total_grid * part_elems * sizeof(float);
+    if (part_bytes > FLAT_BATCH_MAX_PARTIALS)
+        return fail(c, HGMM_ERR_ARG, "%s: the members' partial buffers need %llu bytes together (%zu workgroups x 7 x %d x 4), "
+                    "more than the %llu of one call: fit fewer clouds per call", what, part_bytes, total_grid, Jpad,
+                    FLAT_BATCH_MAX_PARTIALS);
+
+    // ---- buffers of the batch's own ----
+    const size_t tab_bytes = (sizeof(FlatBatchMember) * (size_t)B + 255) & ~(size_t)255;
+    HGMM_TRY(ensure(c, c->fb_tab, tab_bytes + sizeof(int2) * total_grid));
+    HGMM_TRY(ensure(c, c->fb_params, sizeof(float) * blk_elems * B));
+    HGMM_TRY(ensure(c, c->fb_pack, sizeof(float) * pack_elems * B));
+    HGMM_TRY(ensure(c, c->fb_partials, (size_t)part_bytes));
+    HGMM_TRY(ensure(c, c->fb_lpn_partials, sizeof(double) * total_grid));
+    HGMM_TRY(ensure(c, c->fb_stats, sizeof(double) * stat_elems * B));
+    HGMM_TRY(ensure(c, c->fb_lls, sizeof(float) * (size_t)lls_cap * B));
+    HGMM_TRY(ensure(c, c->fb_ctl, sizeof(int) * FLAT_BATCH_CTL_WORDS * (size_t)B));
+    std::vector<int2> wg(total_grid);
+    for (int b = 0; b < B; ++b) {
+        FlatBatchMember& m = tab[b];
+        m.X = clouds[b]->x_aos.as<float>();
+        m.params = c->fb_params.as<float>() + blk_elems * b;
+        m.pack = c->fb_pack.as<float>() + pack_elems * b;
+        m.partials = c->fb_partials.as<float>() + part_elems * (size_t)m.block0;
+        m.lpn_partials = c->fb_lpn_partials.as<double>() + m.block0;
+        m.stats = c->fb_stats.as<double>() + stat_elems * b;
+        m.lls = c->fb_lls.as<float>() + (size_t)lls_cap * b;
+        m.ctl = c->fb_ctl.as<int>() + FLAT_BATCH_CTL_WORDS * (size_t)b;
+        for (int k = 0; k < m.nblocks; ++k) wg[(size_t)m.block0 + k] = make_int2(b, k);
+    }
+    const FlatBatchMember* d_tab = c->fb_tab.as<FlatBatchMember>();
+    const int2* d_wg = reinterpret_cast<const int2*>(c->fb_tab.as<char>() + tab_bytes);
+    bool host_in_flight = false;                 // an upload that reads pageable memory of this call directly
+    HGMM_TRY(upload_table(c, c->fb_tab.p, tab.data(), sizeof(FlatBatchMember) * (size_t)B));
+    HGMM_TRY(upload_table(c, const_cast<int2*>(d_wg), wg.data(), sizeof(int2) * total_grid));
+    host_in_flight = sizeof(FlatBatchMember) * (size_t)B > (256u << 10) || sizeof(int2) * total_grid > (256u << 10);
+    // the initial parameters: ONE block [B][10][Jpad], rows cov | mu | w of every member filled in (flat_begin_body writes inv)
+    const size_t img_bytes = sizeof(float) * blk_elems * B;
+    std::vector<float> img_own;
+    float* img = nullptr;
+    if (img_bytes <= STAGE_RING_BYTES / 2) {
+        void* st = nullptr;
+        HGMM_TRY(stage_reserve(c, img_bytes, &st));
+        img = static_cast<float*>(st);
+    } else {
+        img_own.resize(blk_elems * B);
+        img = img_own.data();
+        host_in_flight = true;
+    }
+    std::memset(img, 0, img_bytes);
+    for (int b = 0; b < B; ++b) {
+        float* blk = img + blk_elems * b;
+        std::memcpy(blk, cov + ce * b, sizeof(float) * ce);
+        std::memcpy(blk + 3 * (size_t)Jpad, mu + 3 * (size_t)J * b, sizeof(float) * 3 * J);
+        std::memcpy(blk + 6 * (size_t)Jpad, w + (size_t)J * b, sizeof(float) * J);
+    }
+    HGMM_HIP(c, hipMemcpyAsync(c->fb_params.p, img, img_bytes, hipMemcpyHostToDevice, c->stream));
+    if (host_in_flight) HGMM_HIP(c, ctx_stream_sync(c));      // (the runtime may still be reading tab / wg / img_own)
+
+    // ---- the launch set: begin, then max_iter x (fused, reduce, finalize), enqueued blind ----
+    flat_begin_batch_kernel<<<dim3((Jpad + 255) / 256, B), 256, 0, c->stream>>>(d_tab, J, Jpad, cov_type, variant);
+    HGMM_HIP(c, hipGetLastError());
+    const auto fused = fused_batch_kernel_for(slots, std::make_integer_sequence<int, 16>());
+    const int stat_blocks = ((int)part_elems + RED_IDX - 1) / RED_IDX;
+    for (int it = 0; it < max_iter; ++it) {
+        const int parity = it & 1;
+        {
+            ProfScope prof(c, HGMM_K_FLAT_FUSED);
+            fused<<<(unsigned)total_grid, BLOCK, 0, c->stream>>>(d_tab, d_wg, J, Jpad, parity);
+        }
+        flat_reduce_batch_kernel<<<dim3(stat_blocks + 1, B), RED_IDX * RED_SLICES, 0, c->stream>>>(d_tab, valid_j, Jpad, parity);
+        flat_finalize_batch_kernel<<<dim3(Jpad / 256, B), 256, 0, c->stream>>>(d_tab, J, Jpad, cov_type, variant, lls_cap, tol,
+                                                                             parity);
+        HGMM_HIP(c, hipGetLastError());
+    }
+
+    // ---- results: queued packets, ONE synchronisation, plain memcpys (hgmm_flat_train_end) ----
+    const size_t ctl_bytes = sizeof(int) * FLAT_BATCH_CTL_WORDS * (size_t)B, lls_bytes = sizeof(float) * (size_t)lls_cap * B;
+    std::vector<char> own[3];
+    size_t staged = 0;
+    hipError_t copy_err = hipSuccess;
+    auto fetch = [&](int slot, const void* dev, size_t bytes) -> const void* {
+        void* dst = nullptr;
+        const size_t padded = (bytes + 255) & ~(size_t)255;
+        if (staged + padded <= STAGE_RING_BYTES / 2 && stage_reserve(c, bytes, &dst) == HGMM_OK) staged += padded;
+        else { own[slot].resize(bytes); dst = own[slot].data(); }
+        const hipError_t e = hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (copy_err == hipSuccess) copy_err = e;
+        return dst;
+    };
+    const int* h_ctl = static_cast<const int*>(fetch(0, c->fb_ctl.p, ctl_bytes));
+    const float* h_lls = static_cast<const float*>(fetch(1, c->fb_lls.p, lls_bytes));
+    const float* h_blk = static_cast<const float*>(fetch(2, c->fb_params.p, img_bytes));
+    const hipError_t sync_err = ctx_stream_sync(c);      // (always: copies may be in flight into this call's memory)
+    HGMM_HIP(c, copy_err);
+    HGMM_HIP(c, sync_err);
+    c->h_stage_off = 0;                                  // the stream is idle: every region of the ring is free
+    for (int b = 0; b < B; ++b) {
+        const float* blk = h_blk + blk_elems * b;
+        std::memcpy(cov + ce * b, blk, sizeof(float) * ce);
+        std::memcpy(mu + 3 * (size_t)J * b, blk + 3 * (size_t)Jpad, sizeof(float) * 3 * J);
+        std::memcpy(w + (size_t)J * b, blk + 6 * (size_t)Jpad, sizeof(float) * J);
+        if (inv_std_out) std::memcpy(inv_std_out + ce * b, blk + 7 * (size_t)Jpad, sizeof(float) * ce);
+        const int n_it = h_ctl[FLAT_BATCH_CTL_WORDS * (size_t)b + 1];
+        if (lls_out && n_it > 0)
+            std::memcpy(lls_out + (size_t)lls_cap * b, h_lls + (size_t)lls_cap * b,
+                        sizeof(float) * (size_t)(n_it < lls_cap ? n_it : lls_cap));
+        n_iter_out[b] = n_it;
+        converged_out[b] = h_ctl[FLAT_BATCH_CTL_WORDS * (size_t)b + 2];
+    }
     return HGMM_OK;
 }

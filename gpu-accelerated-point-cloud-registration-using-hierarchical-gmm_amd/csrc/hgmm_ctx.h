@@ -48,6 +48,26 @@ struct FlatState {
     bool idle_since_launch = true;    // the host has drained the stream since the last of these launches (ctx_stream_sync)
 };
 
+// One member of a batched flat fit (hgmm_flat_train_batch, flat_kernels.hip): what the serial loop keeps in the context --
+// the cloud, its grid, the parameter block, the packed table, the partials, the statistics, the trace and the control words --
+// as one row of a table on the device.  The batched kernels find their member by workgroup (the fused launch: a table of
+// (member, local block) per workgroup; the others: blockIdx.y) and read everything else from here.
+struct FlatBatchMember {
+    const float* X;                   // float [n,3]: the handle's x_aos
+    int64_t n;
+    int block0, nblocks;              // the member's workgroups in the fused launch: [block0, block0 + nblocks)
+    float* params;                    // float [10][Jpad]  cov | mu | w | inv, the layout of f_block
+    float* pack;                      // float [PK_ROWS][Jpad]
+    float* partials;                  // float [nblocks][7][Jpad]
+    double* lpn_partials;             // double [nblocks]
+    double* stats;                    // double [7 * Jpad + 2]
+    float* lls;                       // float [lls_cap]
+    int* ctl;                         // int [16], the layout of f_ctl: stop (even), n_iter, converged, stop (odd); float prev at [8]
+};
+constexpr int FLAT_BATCH_MAX = 4096;                              // members per call
+constexpr unsigned long long FLAT_BATCH_MAX_PARTIALS = 8ull << 30;   // bytes of all members' partial buffers together
+constexpr int FLAT_BATCH_CTL_WORDS = 16;
+
 // The store pacer's measurement ring (its rate controller: flat_pace.h): the last few paced E-step launches are bracketed
 // by event pairs that are looked at -- never waited for -- when the next one is launched (flat_kernels.hip, pace_poll).
 struct PaceRing {
@@ -207,6 +227,15 @@ struct hgmm_ctx {
     hgmm::DevBuf f_ctl;                       // int  [4]: done, n_iter, converged, pad ; float prev
     hgmm::DevBuf f_hint;                      // float [3][Jpad] centre hint for m-step
     hgmm::DevBuf f_cm, f_cs, f_ca, f_lpn2;    // chunked path: per-chunk (max, sum, arg-max) [C][n], lpn2 [n]
+    // batched fit (hgmm_flat_train_batch): buffers of its own, nothing above is touched
+    hgmm::DevBuf fb_tab;                      // FlatBatchMember [B], then int2 (member, local block) per workgroup of the fused launch
+    hgmm::DevBuf fb_params;                   // float [B][10][Jpad]
+    hgmm::DevBuf fb_pack;                     // float [B][PK_ROWS][Jpad]
+    hgmm::DevBuf fb_partials;                 // float [sum of the members' grids][7][Jpad]
+    hgmm::DevBuf fb_lpn_partials;             // double [sum of the members' grids]
+    hgmm::DevBuf fb_stats;                    // double [B][7 * Jpad + 2]
+    hgmm::DevBuf fb_lls;                      // float [B][cap]
+    hgmm::DevBuf fb_ctl;                      // int [B][16]
     hgmm::DevBuf scratch;
     double* h_scalars = nullptr;              // pinned, device-visible scalars (hgmm_host_scalars)
     int h_scalars_n = 0;

@@ -15,7 +15,7 @@ import warnings
 import numpy as np
 
 from . import gmm_impl
-from .gmm_impl import train_gmm, init_gmm_params, timer, predict, asarray, DevicePoints  # noqa: F401
+from .gmm_impl import train_gmm, train_gmm_batch, init_gmm_params, timer, predict, asarray, DevicePoints  # noqa: F401
 
 
 class Feature(abc.ABC):
@@ -87,6 +87,41 @@ class GMM_GPU_Base:
         if self._verbose and len(lls):
             print("\nLog Likelihood Min-Max:\n\n", np.min(lls), np.max(lls))
         return self
+
+    def fit_batch(self, frames, inits=None):
+        """One fit per frame through ONE launch set (``train_gmm_batch``) -> a list of fitted estimators of this one's
+        settings, each in the state ``.fit(frame)`` leaves one in (this estimator itself stays as it is).  ``inits``: one
+        ``(means, weights, covs)`` per frame; without it they are drawn by the initialiser FRAME BY FRAME IN FRAME ORDER before
+        the fit -- a loop of ``.fit`` consumes exactly that sequence of the host RNG, since the fit draws nothing -- so under
+        the same seed the models are bit for bit those of the loop.  Frames that bring per-point weights are refused."""
+        frames = list(frames)
+        if inits is not None and len(inits) != len(frames):
+            raise ValueError("fit_batch: %d frames, but %d initialisations" % (len(frames), len(inits)))
+        clouds, params = [], []
+        for b, X in enumerate(frames):
+            if getattr(X, "weights", None) is not None:
+                raise ValueError("fit_batch: frame %d brings per-point weights, which the batched fit does not take: fit it "
+                                 "with fit(frame)" % b)
+            X, _ = _split_weighted(X, None)
+            host = X.get() if isinstance(X, DevicePoints) else np.asarray(X)
+            params.append(inits[b] if inits is not None else self._init_params(host))
+            clouds.append(X if isinstance(X, DevicePoints) else host.astype(np.float32))
+        if not frames:
+            return []
+        ctx = next((X.ctx for X in clouds if isinstance(X, DevicePoints)), None)
+        with timer(self._label, ctx):
+            fits = train_gmm_batch(clouds, self.max_iter, self.tol, [np.asarray(p[0], np.float32) for p in params],
+                                   [np.asarray(p[2], np.float32) for p in params],
+                                   [np.asarray(p[1], np.float32) for p in params], cov_type=self.cov_type)
+        models = []
+        for inv, mu, w, cov, lls in fits:
+            m = type(self)(self.num_components, self.max_iter, self.tol, self.cov_type)
+            m.means_, m.covariances_, m.weights_ = mu, cov, w
+            m.lls, m.inv_covs = lls, inv
+            if self._verbose and len(lls):
+                print("\nLog Likelihood Min-Max:\n\n", np.min(lls), np.max(lls))
+            models.append(m)
+        return models
 
     def predict(self, X):
         """Host array in -> NumPy int64 labels; a resident cloud (DevicePoints) in -> the labels as a DeviceArray,

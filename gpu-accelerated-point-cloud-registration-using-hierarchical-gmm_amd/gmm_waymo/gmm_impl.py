@@ -70,6 +70,13 @@ def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type='diag', sa
     return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, VARIANT, sample_weight)
 
 
+def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type='diag'):
+    """B x :func:`train_gmm` in one launch set -> a list of its tuples, member b's bit for bit the serial call's.  ``Xs``:
+    host arrays and / or ``DevicePoints`` of one context; ``means``, ``covariances``, ``weights``: one per member, same J.
+    No per-point weights (a member that brings some is refused); J > 1024 runs as a loop of :func:`train_gmm`."""
+    return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, VARIANT)
+
+
 def predict(X, inv_cov, means, weights, cov_type='diag'):
     """-> labels[N] int64.  Reference gmm_impl.py:147-155."""
     return _flat.predict(X, inv_cov, means, weights, cov_type, VARIANT)

@@ -39,5 +39,13 @@ def train_gmm(X, max_iter, tol, means, covariances, weights=None, sample_weight=
     return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, 'diag', VARIANT, sample_weight)
 
 
+def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights=None):
+    """B x :func:`train_gmm` in one launch set -> a list of its tuples, member b's bit for bit the serial call's
+    (``weights=None``: uniform, as there).  No per-point weights; J > 1024 runs as a loop of :func:`train_gmm`."""
+    if weights is None:
+        weights = [np.ones(len(m), dtype=np.float32) / len(m) for m in means]
+    return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, 'diag', VARIANT)
+
+
 def predict(X, inv_cov, means, weights):
     return _flat.predict(X, inv_cov, means, weights, 'diag', VARIANT)

@@ -167,17 +167,34 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
 
 
 def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag", devices=None,
-               contexts_per_device: int = 1, pool: ReplicaPool | None = None):
+               contexts_per_device: int = 1, pool: ReplicaPool | None = None, batch: int = 1):
     """One flat GMM per frame (``GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit(frame)``,
-    gmm_waymo/src/gmm.py:65-84), the frames fanned out over the pool's contexts.  -> the fitted models in frame order."""
+    gmm_waymo/src/gmm.py:65-84), the frames fanned out over the pool's contexts.  -> the fitted models in frame order.
+
+    ``batch`` > 1: every context takes ``batch`` frames at a time through the SAME launches (``GMM_GPU_Base.fit_batch``: one
+    fused launch per iteration for all of them) -- a scan-sized frame alone is a chain of small launches that leaves the
+    chip idle.  The last chunk may be short.  With one context and a seeded RNG the models are bitwise those of
+    ``batch=1``: the initial parameters are drawn frame by frame in frame order either way.  (With several contexts the
+    worker threads share the host RNG, with or without ``batch``.)"""
     from .gmm_waymo.gmm import GMM_GPU_Base
+
+    frames = list(frames)
+    B = int(batch)
+    if B < 1:
+        raise ValueError("batch must be >= 1, not %r" % (batch,))
 
     def one(ctx, frame):                                     # (the worker thread runs under use_context(ctx))
         return GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit(frame)
 
+    def chunk(ctx, part):
+        return GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit_batch(part)
+
     own = pool is None
     pool = pool or ReplicaPool(devices, contexts_per_device)
     try:
+        if B > 1:
+            chunks = [frames[i:i + B] for i in range(0, len(frames), B)]
+            return [m for ms in pool.map(chunk, chunks) for m in ms]
         return pool.map(one, frames)
     finally:
         if own:

@@ -204,6 +204,41 @@ int hgmm_flat_train_begin(hgmm_ctx* ctx, int cov_type, int variant, int J, float
 int hgmm_flat_train_step(hgmm_ctx* ctx, int iters);
 int hgmm_flat_train_end(hgmm_ctx* ctx, float* mu, float* cov, float* w, float* inv_std_out,
                         float* lls_out, int* n_iter_out, int* converged_out);
+/* B independent fits in ONE launch set -- B x train_gmm() of either flavour (gmm_waymo gmm_impl.py:118-145, gmmreg_gpu
+ * gmm_impl.py:63-85): the reference's streaming driver fits frame after frame, and a fit of a scan-sized cloud is a chain of
+ * launches that leaves most of the chip idle.  clouds [B] are handles of this context (hgmm_points_create_*).
+ * SEMANTICS.  Member b is hgmm_flat_train on a context whose cloud is clouds[b], with no weights in force: its mu, cov, w,
+ * inv_std, lls, n_iter and converged come out BIT FOR BIT as the serial entry returns them, whatever B is and whoever the
+ * neighbours are.  The members differ in their cloud and its size, in their initial parameters and in the iteration at which
+ * the device-side stop rule fires; they share cov_type, variant, J, max_iter and tol.  A handle may occur several times
+ * (K restarts of one resident cloud: K slots, K initialisations, the caller keeps the best log-likelihood); two slots with
+ * the same handle and the same initialisation return the same bits.  The arrays are member-major: mu [B][J][3], cov and
+ * inv_std_out [B][J][3] (diag) or [B][J] (spherical), w [B][J], lls_out [B][max(max_iter, 1)] (member b's first n_iter[b]
+ * entries are written), n_iter_out and converged_out [B].
+ * LAUNCHES.  One `begin` launch per call; per iteration one fused E+M launch over the workgroups of all members (each member
+ * has the grid the serial launch gives a cloud of its size), one reduce and one finalize launch; one group of download
+ * packets and one synchronisation at the end.  max_iter iterations are enqueued blind, like hgmm_flat_train: a member that has
+ * stopped costs every later launch a workgroup that returns at its stop word.
+ * LIMITS.  J <= 1024: only the one-pass fused path is batched, the chunked path of larger J stays serial.  1 <= B <= 4096.
+ * The members' partial buffers together -- sum_b grid_b x 7 x Jpad x 4 bytes, Jpad = J rounded up to 256 -- are at most
+ * 8 GiB.  No communicator.
+ * REFUSALS, each before anything resident is touched (hgmm_last_error says why).  HGMM_ERR_ARG: B out of range; clouds NULL
+ * or a NULL member; a handle of another context; NULL mu, cov, w, n_iter_out or converged_out; max_iter < 0; a bad cov_type or
+ * variant and flavour G with spherical covariances (hgmm_flat_train's own texts); J outside 1..1024; partial buffers above
+ * the limit (the message names the figure).  HGMM_ERR_STATE under a communicator.
+ * LEFT ALONE.  The batch works in buffers of its own and reads the handles' float32 rows and nothing else of the context: the
+ * bound cloud, its flat weights, the serial train loop (a hgmm_flat_train_begin ... _end in progress included) with its
+ * parameter block, table, partials, control words and trace, the store pacer, the resident tree, forest, target and voxel
+ * result are what they were.  PER-POINT WEIGHTS ARE IGNORED: a handle owns none (hgmm_flat_set_weights), so the weights in
+ * force on the context -- also when the bound handle is a member -- do not enter; fit a weighted cloud with hgmm_flat_train. */
+int hgmm_flat_train_batch(hgmm_ctx* ctx, int B, hgmm_points* const* clouds /* [B] */,
+                          int cov_type, int variant, int J, int max_iter, float tol,
+                          float* mu      /* [B][J][3]          in = initial, out = final */,
+                          float* cov     /* [B][J][3] | [B][J] in / out */,
+                          float* w       /* [B][J]             in / out */,
+                          float* inv_std_out /* as cov, may be NULL */,
+                          float* lls_out /* [B][max(max_iter,1)], may be NULL */,
+                          int32_t* n_iter_out /* [B] */, int32_t* converged_out /* [B] */);
 /* Sufficient statistics of ONE fused E+M pass on this context's points (after the
  * all-reduce when a communicator is attached): stats [J,7] doubles laid out
  * (s0, a_x, a_y, a_z, b_x, b_y, b_z) with a = sum r (x - mu_old), b = sum r (x - mu_old)^2,
