@@ -175,15 +175,109 @@ def _batch_member_points(X, b):
     return X
 
 
-def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, variant):
+def _is_voxel_cloud(X):
+    from ._native import VoxelCloud
+    return isinstance(X, VoxelCloud)
+
+
+def _batch_member_weighted(X):
+    """(points, own weights or None) of a member of a weighted batch: a ``DevicePoints`` stays what it is, a
+    ``WeightedPoints(points, weights)`` -- any object with those two fields -- is taken apart."""
+    if isinstance(X, DevicePoints):
+        return X, X.weights
+    if hasattr(X, "points") and hasattr(X, "weights"):
+        return X.points, X.weights
+    return X, None
+
+
+def _batch_sample_weights(Xs, sample_weight):
+    """``sample_weight`` of train_gmm_batch resolved per member -> (clouds without their weights, [B] arrays or None).
+    ``"own"``: each member's own weights, none where it brings none; a sequence: per member, None means its own."""
+    B = len(Xs)
+    if isinstance(sample_weight, str):
+        if sample_weight != "own":
+            raise ValueError("train_gmm_batch: sample_weight must be None, 'own' or a sequence, not %r" % (sample_weight,))
+        sample_weight = [None] * B
+    else:
+        sample_weight = list(sample_weight)
+        if len(sample_weight) != B:
+            raise ValueError("train_gmm_batch: %d clouds, but %d entries in sample_weight" % (B, len(sample_weight)))
+    clouds, out = [], []
+    for b, X in enumerate(Xs):
+        X, own = _batch_member_weighted(X)
+        s = own if sample_weight[b] is None else sample_weight[b]
+        try:
+            n = X.shape[0] if isinstance(X, DevicePoints) else np.shape(X)[0]
+            out.append(_check_weights(s, n))
+        except (ValueError, IndexError) as e:
+            raise ValueError("train_gmm_batch: member %d: %s" % (b, e)) from None
+        clouds.append(X)
+    return clouds, out
+
+
+def _report(fits):
+    out = []
+    for inv, mu, w, cov, lls, converged in fits:
+        if not converged:
+            print('Failed to converge. Increase max-iter or tol.')
+        out.append((inv, mu, w, cov, [np.float32(v) for v in lls]))
+    return out
+
+
+def _train_gmm_batch_voxels(vcs, max_iter, tol, means, covariances, weights, cov_type, variant, sample_weight):
+    """train_gmm_batch over ``VoxelCloud`` s: count-weighted, as they are wherever they go, and without a host trip."""
+    B = len(vcs)
+    if sample_weight is not None and not isinstance(sample_weight, str):
+        sample_weight = list(sample_weight)
+        if len(sample_weight) != B:
+            raise ValueError("train_gmm_batch: %d clouds, but %d entries in sample_weight" % (B, len(sample_weight)))
+        for b, s in enumerate(sample_weight):
+            if s is not None:
+                raise ValueError("train_gmm_batch: member %d is a VoxelCloud, whose weights are its counts: it takes no "
+                                 "explicit sample_weight" % b)
+    elif isinstance(sample_weight, str) and sample_weight != "own":
+        raise ValueError("train_gmm_batch: sample_weight must be None, 'own' or a sequence, not %r" % (sample_weight,))
+    ctx = vcs[0].ctx
+    for b, vc in enumerate(vcs):
+        if vc.ctx is not ctx:
+            raise ValueError("train_gmm_batch: member %d is a cloud of another context" % b)
+    if np.shape(means[0])[0] > BATCH_MAX_J:
+        fits = []
+        for b, vc in enumerate(vcs):
+            ctx.set_points_from_voxels(vc, tree_weights=False, flat_weights=True)
+            fits.append(ctx.flat_train(max_iter, tol, means[b], covariances[b], weights[b], cov_type, variant))
+        return _report(fits)
+    return _report(ctx.flat_train_batch_voxels(vcs, max_iter, tol, means, covariances, weights, cov_type, variant,
+                                               weighted=True))
+
+
+def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, variant, sample_weight=None):
     """B independent ``train_gmm`` calls through one launch set (``Context.flat_train_batch``) -> a list of ``train_gmm``'s
     tuples, member b's bit for bit what ``train_gmm(Xs[b], ...)`` returns.  ``Xs``: host arrays [N,3] (each uploaded into a
     temporary ``DevicePoints`` and freed afterwards) and / or ``DevicePoints`` of one context (used where they are; one may
     occur several times: restarts of one resident cloud).  ``means``, ``covariances``, ``weights``: one per member, all of
-    the same J.  A member that brings per-point weights is refused (ValueError naming it).  J > 1024, which the batched
-    entry does not take, falls back to a loop of ``train_gmm``."""
-    Xs = [_batch_member_points(X, b) for b, X in enumerate(Xs)]
+    the same J.  J > 1024, which the batched entry does not take, falls back to a loop of ``train_gmm``.
+
+    ``sample_weight``: None -- no per-point weights, and a member that brings some is refused (ValueError naming it);
+    ``"own"`` -- each member's own (``DevicePoints.weights``, ``WeightedPoints.weights``), none where it brings none; a
+    sequence of B entries -- an array [n_b] per member, None meaning the member's own.  Member b is then bit for bit
+    ``train_gmm(Xs[b], ..., sample_weight=)`` with those weights.
+
+    A list made only of ``VoxelCloud`` s (one live voxel result) is fitted count-weighted without leaving the device
+    (``Context.flat_train_batch_voxels``), whatever ``sample_weight`` says short of an explicit array, which is a
+    ValueError; so is a list that mixes ``VoxelCloud`` s with other members."""
+    Xs = list(Xs)
     B = len(Xs)
+    n_vox = sum(1 for X in Xs if _is_voxel_cloud(X))
+    if 0 < n_vox < B:
+        raise ValueError("train_gmm_batch: VoxelClouds and other members in one batch (%d of %d are VoxelClouds): fit them "
+                         "in two calls" % (n_vox, B))
+    slot_weights = None
+    if n_vox == 0:
+        if sample_weight is None:
+            Xs = [_batch_member_points(X, b) for b, X in enumerate(Xs)]
+        else:
+            Xs, slot_weights = _batch_sample_weights(Xs, sample_weight)
     for name, seq in (("means", means), ("covariances", covariances), ("weights", weights)):
         if len(seq) != B:
             raise ValueError("train_gmm_batch: %d clouds, but %d arrays in %s" % (B, len(seq), name))
@@ -196,6 +290,8 @@ def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, va
             raise ValueError("train_gmm_batch: member %d: means must be [J,3], got %s" % (b, np.shape(m)))
         if Js[b] != Js[0]:
             raise ValueError("train_gmm_batch: member %d has J = %d, member 0 has J = %d (the members share J)" % (b, Js[b], Js[0]))
+    if n_vox:
+        return _train_gmm_batch_voxels(Xs, max_iter, tol, means, covariances, weights, cov_type, variant, sample_weight)
     ctxs = [X.ctx for X in Xs if isinstance(X, DevicePoints)]
     ctx = ctxs[0] if ctxs else default_context()
     for b, X in enumerate(Xs):
@@ -204,7 +300,11 @@ def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, va
         if not isinstance(X, DevicePoints) and (np.ndim(X) != 2 or np.shape(X)[1] != 3):
             raise ValueError("train_gmm_batch: member %d: points must have shape [N,3], got %s" % (b, np.shape(X)))
     if Js[0] > BATCH_MAX_J:
-        return [train_gmm(Xs[b], max_iter, tol, means[b], covariances[b], weights[b], cov_type, variant) for b in range(B)]
+        if slot_weights is None:
+            return [train_gmm(Xs[b], max_iter, tol, means[b], covariances[b], weights[b], cov_type, variant) for b in range(B)]
+        # (a slot without weights is a member that brings none: train_gmm's None finds none either)
+        return [train_gmm(Xs[b], max_iter, tol, means[b], covariances[b], weights[b], cov_type, variant,
+                          sample_weight=slot_weights[b]) for b in range(B)]
     temporary = []
     try:
         clouds = []
@@ -213,16 +313,15 @@ def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, va
                 X = DevicePoints(np.asarray(X), ctx)
                 temporary.append(X)
             clouds.append(X)
-        fits = ctx.flat_train_batch(clouds, max_iter, tol, means, covariances, weights, cov_type, variant)
+        if slot_weights is None:
+            fits = ctx.flat_train_batch(clouds, max_iter, tol, means, covariances, weights, cov_type, variant)
+        else:
+            fits = ctx.flat_train_batch(clouds, max_iter, tol, means, covariances, weights, cov_type, variant,
+                                        weights=slot_weights)
     finally:
         for X in temporary:
             X.free()
-    out = []
-    for inv, mu, w, cov, lls, converged in fits:
-        if not converged:
-            print('Failed to converge. Increase max-iter or tol.')
-        out.append((inv, mu, w, cov, [np.float32(v) for v in lls]))
-    return out
+    return _report(fits)
 
 
 def predict(X, inv_cov, means, weights, cov_type, variant):

@@ -106,6 +106,12 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_flat_train_end", [ctx, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)])
         _sig(lib, "hgmm_flat_train_batch", [ctx, C.c_int, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                             _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)])
+        _sig(lib, "hgmm_flat_train_batch_weighted", [ctx, C.c_int, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32),
+                                                     C.POINTER(C.c_int32)])
+        _sig(lib, "hgmm_flat_train_batch_voxels", [ctx, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32)])
         _sig(lib, "hgmm_flat_stats", [ctx, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _f64p, _f64p])
         _sig(lib, "hgmm_flat_set_weights", [ctx, _vp, C.c_int64])
         _sig(lib, "hgmm_tree_build", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int,
@@ -917,28 +923,39 @@ class Context:
                                              C.byref(n_it), C.byref(conv)))
         return inv, mu, w, cov, lls[:n_it.value].copy(), bool(conv.value)
 
-    def _flat_batch_args(self, clouds, mu, cov, w, cov_type):
-        """What flat_train_batch checks on the host, before the library is reached: -> (handles, J, mu [B,J,3], cov, w)."""
+    def _flat_batch_args(self, clouds, mu, cov, w, cov_type, weights=None):
+        """What flat_train_batch checks on the host, before the library is reached: -> (handles, J, mu [B,J,3], cov, w), and
+        with ``weights`` (a sequence of B entries) a sixth item: the slots' weights, float32 [n_b] or None each."""
         if cov_type not in COV_TYPES:
             raise ValueError("cov_type must be one of %s, not %r" % (sorted(COV_TYPES), cov_type))
         clouds = list(clouds)
         B = len(clouds)
         if B < 1:
             raise ValueError("flat_train_batch: no clouds")
-        handles = []
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != B:
+                raise ValueError("flat_train_batch: %d clouds, but %d entries in weights" % (B, len(weights)))
+        handles, slot_weights = [], []
         for b, cl in enumerate(clouds):
+            own, n = None, None
             if hasattr(cl, "_h") and hasattr(cl, "ctx"):                # a DevicePoints (hgmm_amd._flat)
                 if cl.ctx is not self:
                     raise ValueError("flat_train_batch: member %d is a cloud of another context" % b)
-                if getattr(cl, "weights", None) is not None:
+                own, n = getattr(cl, "weights", None), cl.shape[0]
+                if own is not None and weights is None:
                     raise ValueError("flat_train_batch: member %d brings per-point weights, which the batched fit does not "
-                                     "take (a handle owns none): fit it with flat_train" % b)
+                                     "take unless the call says so (a handle owns none): pass weights=[...] (a None entry: "
+                                     "the member's own) or fit it with flat_train" % b)
                 if cl._h is None:
                     raise ValueError("flat_train_batch: member %d has been freed" % b)
                 cl = cl._h
             if not isinstance(cl, _vp) or not cl.value:
                 raise ValueError("flat_train_batch: member %d is neither a DevicePoints nor a points_create handle" % b)
             handles.append(cl)
+            if weights is not None:
+                # (an explicit array takes precedence over the weights the member brings, as in hgmm_amd._flat._ctx_for)
+                slot_weights.append(self._flat_batch_slot_weights(own if weights[b] is None else weights[b], n, b))
         for name, seq in (("mu", mu), ("cov", cov), ("w", w)):
             if len(seq) != B:
                 raise ValueError("flat_train_batch: %d clouds, but %d arrays in %s" % (B, len(seq), name))
@@ -959,29 +976,92 @@ class Context:
                 out[2].append(_f32(w[b], (J,)))
             except ValueError as e:
                 raise ValueError("flat_train_batch: member %d: %s" % (b, e)) from None
+        if weights is not None:
+            return handles, J, np.stack(out[0]), np.stack(out[1]), np.stack(out[2]), slot_weights
         return handles, J, np.stack(out[0]), np.stack(out[1]), np.stack(out[2])
 
-    def flat_train_batch(self, clouds, max_iter, tol, mu, cov, w, cov_type="diag", variant="W"):
+    @staticmethod
+    def _flat_batch_slot_weights(s, n, b):
+        """Slot b's weights as the float32 [n] array the library reads (it trusts the length), or None.  What the library
+        would refuse is refused here first; ``n``: the member's rows where they are known (a DevicePoints)."""
+        if s is None:
+            return None
+        s = np.ascontiguousarray(s, dtype=np.float32)
+        if s.ndim != 1 or (n is not None and s.shape[0] != n):
+            raise ValueError("flat_train_batch: member %d: weights must have shape [%s], got %s"
+                             % (b, "N" if n is None else n, s.shape))
+        bad = np.flatnonzero(~(np.isfinite(s) & (s >= 0)))
+        if bad.size:
+            raise ValueError("flat_train_batch: member %d: weight %d is %g (weights must be finite and >= 0)"
+                             % (b, bad[0], s[bad[0]]))
+        if not (s > 0).any():
+            raise ValueError("flat_train_batch: member %d: all %d weights are zero" % (b, s.shape[0]))
+        return s
+
+    def flat_train_batch(self, clouds, max_iter, tol, mu, cov, w, cov_type="diag", variant="W", weights=None):
         """B independent fits in one launch set (hgmm_flat_train_batch).  ``clouds``: a sequence of ``DevicePoints`` of this
         context or of ``points_create`` handles (one may occur several times: restarts); ``mu``, ``cov``, ``w``: sequences or
         stacked arrays, one initialisation per member, all of the same J <= 1024.  -> a list of
         ``(inv, mu, w, cov, lls, converged)``, member b's bit for bit what ``flat_train`` returns with that cloud bound and no
         weights in force.  The bound cloud, its weights and a ``flat_train_begin`` in progress are left alone.  Per-point
-        weights do not enter: a ``DevicePoints`` that brings some is refused (ValueError naming the member)."""
-        handles, J, mu, cov, w = self._flat_batch_args(clouds, mu, cov, w, cov_type)
+        weights do not enter: a ``DevicePoints`` that brings some is refused (ValueError naming the member).
+
+        ``weights``: a sequence of B entries, each None or an array [n_b] >= 0 -- per-point weights of that SLOT
+        (hgmm_flat_train_batch_weighted): member b is then bit for bit ``flat_train`` with that cloud bound and
+        ``flat_set_weights(weights[b])`` in force.  Where the entry is None a ``DevicePoints`` that brings ``.weights`` uses
+        them (an explicit array takes precedence), any other member is unweighted.  One cloud may fill several slots with
+        different weights.  The library trusts an array's length: it is checked here against a ``DevicePoints``' rows; behind
+        a bare ``points_create`` handle it is the caller's to get right."""
+        if weights is None:
+            handles, J, mu, cov, w = self._flat_batch_args(clouds, mu, cov, w, cov_type)
+            slot_weights = None
+        else:
+            handles, J, mu, cov, w, slot_weights = self._flat_batch_args(clouds, mu, cov, w, cov_type, weights)
         if variant not in VARIANTS:
             raise ValueError("variant must be one of %s, not %r" % (sorted(VARIANTS), variant))
         B = len(handles)
+        out = self._flat_batch_outputs(B, max_iter, cov)
+        head = (self.h, B, (_vp * B)(*[h.value for h in handles]))
+        tail = (COV_TYPES[cov_type], VARIANTS[variant], J, int(max_iter), float(tol), _ptr(mu), _ptr(cov), _ptr(w)) + out[1]
+        if slot_weights is None:
+            self._check(self.lib.hgmm_flat_train_batch(*(head + tail)))
+        else:
+            s = (_vp * B)(*[None if a is None else a.ctypes.data for a in slot_weights])
+            self._check(self.lib.hgmm_flat_train_batch_weighted(*(head + (s,) + tail)))
+        return self._flat_batch_results(mu, cov, w, out[0])
+
+    @staticmethod
+    def _flat_batch_outputs(B, max_iter, cov):
         cap = max(int(max_iter), 1)
         inv = np.empty_like(cov)
         lls = np.zeros((B, cap), np.float32)
         n_it, conv = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        self._check(self.lib.hgmm_flat_train_batch(
-            self.h, B, (_vp * B)(*[h.value for h in handles]), COV_TYPES[cov_type], VARIANTS[variant], J, int(max_iter),
-            float(tol), _ptr(mu), _ptr(cov), _ptr(w), _ptr(inv), _ptr(lls), n_it.ctypes.data_as(_i32p),
-            conv.ctypes.data_as(_i32p)))
+        return (inv, lls, n_it, conv), (_ptr(inv), _ptr(lls), n_it.ctypes.data_as(_i32p), conv.ctypes.data_as(_i32p))
+
+    @staticmethod
+    def _flat_batch_results(mu, cov, w, out):
+        inv, lls, n_it, conv = out
+        cap = lls.shape[1]
         return [(inv[b].copy(), mu[b].copy(), w[b].copy(), cov[b].copy(), lls[b, :min(int(n_it[b]), cap)].copy(),
-                 bool(conv[b])) for b in range(B)]
+                 bool(conv[b])) for b in range(len(n_it))]
+
+    def flat_train_batch_voxels(self, vcs, max_iter, tol, mu, cov, w, cov_type="diag", variant="W", weighted=True):
+        """:meth:`flat_train_batch` over members of the resident voxel result, without a host trip
+        (hgmm_flat_train_batch_voxels).  ``vcs``: :class:`VoxelCloud` s of ONE live result (one may occur several times).
+        Slot b is bit for bit ``set_points_from_voxels(vcs[b], tree_weights=False, flat_weights=weighted)`` followed by
+        ``flat_train`` -- the centroids as float32 rows, ``weighted``: their counts as weights -- but the resident cloud, its
+        weights and the voxel result stay what they were."""
+        vcs, members = self._voxel_members(vcs, "flat_train_batch_voxels")
+        B = len(vcs)
+        # (the checks of the parameters are those of flat_train_batch; the handles play no part)
+        _, J, mu, cov, w = self._flat_batch_args([_vp(1)] * B, mu, cov, w, cov_type)
+        if variant not in VARIANTS:
+            raise ValueError("variant must be one of %s, not %r" % (sorted(VARIANTS), variant))
+        out = self._flat_batch_outputs(B, max_iter, cov)
+        self._check(self.lib.hgmm_flat_train_batch_voxels(
+            self.h, B, members, 1 if weighted else 0, COV_TYPES[cov_type], VARIANTS[variant], J, int(max_iter), float(tol),
+            _ptr(mu), _ptr(cov), _ptr(w), *out[1]))
+        return self._flat_batch_results(mu, cov, w, out[0])
 
     def flat_train_begin(self, tol, mu, cov, w, cov_type="diag", variant="W", lls_capacity=1024):
         J, mu, cov, w = self._flat_args(mu, cov, w, cov_type)

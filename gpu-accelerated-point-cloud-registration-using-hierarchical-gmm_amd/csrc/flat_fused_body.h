@@ -1,6 +1,7 @@
 // The body of the fused E+M kernel (flat_kernels.hip), stated ONCE and included TEXTUALLY by the kernel of one cloud
-// (flat_fused_pk_kernel) and by the batched kernel (flat_fused_pk_batch_kernel).  Not a header: no include guard, included
-// inside a kernel's braces.  The including kernel provides
+// (flat_fused_pk_kernel) and by the batched kernels (flat_fused_pk_batch_kernel<NSLOT> there, <NSLOT, true> in
+// flat_batch_weighted.hip; what the text names beyond the kernel's own: flat_fused_device.h).  Not a header: no include
+// guard, included inside a kernel's braces.  The including kernel provides
 //   NSLOT, WEIGHTED                 compile-time constants
 //   X, pack, n, J, Jpad, partials, lpn_partials, allow_const_shift, comp_major, SW     what the serial kernel's arguments are
 //   FLAT_FUSED_BLOCK                the workgroup's number among those that share the cloud X [n]

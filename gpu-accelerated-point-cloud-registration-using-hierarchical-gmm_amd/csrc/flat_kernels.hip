@@ -25,6 +25,7 @@
 //                       the same bodies, each member's arguments read from a table on the device.
 #include "hgmm_ctx.h"
 #include "wave_ops.h"
+#include "flat_fused_device.h"
 
 #include <type_traits>
 #include <utility>
@@ -35,15 +36,6 @@
 #include <cstring>
 
 namespace hgmm {
-
-constexpr float NEG_INF = -__builtin_huge_valf();
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-constexpr int PK_MU = 0, PK_G = 3, PK_C = 6, PK_W = 7;   // rows of the packed parameter table (PK_W: the raw weight, for the fused kernel's origin)
-constexpr int PK_ROWS = 8;
-typedef float f2 __attribute__((ext_vector_type(2)));
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr int BLOCK = WAVES_PER_BLOCK * 64;
 
 // ------------------------------------------------------------------------------------------
 // parameter packing (log2 domain):  wl2_ij = c2_j - sum_d g_jd (x_id - mu_jd)^2 = log2e * wlp_ij
@@ -160,55 +152,6 @@ __device__ __forceinline__ float row_wl2(const LaneParams<NV4, NV1>& P, float x0
         m = fmaxf(m, a);
     }
     return m;
-}
-
-// The reference's normaliser  log( sum_j exp(wlp_j) + eps )  (gmm_waymo gmm_impl.py:113, no
-// max-shift there) from the wave maximum m2 and S = sum_j 2^(wl2_j - m2), all in log2 units:
-//   lpn2 = mc + log2( S' + eps 2^-mc ),  mc = max(m2, -64),  S' = S (or 0 when m2 < -64: then
-//   sum_j exp(wlp_j) < 1e-19 J is below float32 resolution of eps = 1e-8).
-// inv_den satisfies  r_j = 2^(wl2_j - m2) * inv_den.
-constexpr float CS_MAX_SHIFT = 60.0f;      // constant-shift log-sum-exp is used while max_j c2_j <= this (flat_fused_pk_kernel)
-__device__ __forceinline__ float lpn2_from(float m2, float s, float& inv_den) {
-    const bool tiny = m2 < -64.0f;
-    const float mc = tiny ? -64.0f : m2;
-    const float den = fmaf(FLAT_EPS, __builtin_amdgcn_exp2f(-mc), tiny ? 0.0f : s);
-    inv_den = tiny ? 0.0f : __builtin_amdgcn_rcpf(den);
-    return mc + __builtin_amdgcn_logf(den);
-}
-
-__device__ __forceinline__ void wave_row_range(int64_t n, int64_t& r0, int64_t& r1) {
-    const int64_t nw = (int64_t)gridDim.x * WAVES_PER_BLOCK;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
-    const int64_t per = (n + nw - 1) / nw;
-    r0 = gw * per;
-    r1 = r0 + per < n ? r0 + per : n;
-    if (r0 > n) r0 = n;
-}
-// The same range as wave-uniform SCALARS: first row and row count.  The 64-bit division above goes through v_rcp and
-// leaves r0 / r1 in vector registers although every lane holds the same value; a row loop that compares against them
-// pays a v_cmp_*_i64 per comparison.  Read back through readfirstlane, the loop's counter, its prefetch clamp and its
-// exit test are scalar instructions.  (A wave never owns 2^31 rows: the count is an int.)
-__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
-    const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffLL)), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return ((int64_t)hi << 32) | (int64_t)(unsigned int)lo;
-}
-__device__ __forceinline__ void wave_row_range_uniform(int64_t n, int64_t& r0, int& nrows) {
-    int64_t r1;
-    wave_row_range(n, r0, r1);
-    r0 = uniform_i64(r0);
-    nrows = (int)(uniform_i64(r1) - r0);                 // (r1 >= r0 always)
-}
-
-// (the same for workgroup `block` of the `nblocks` that share a cloud in a batched launch, flat_fused_pk_batch_kernel)
-__device__ __forceinline__ void wave_row_range_uniform(int64_t n, unsigned block, unsigned nblocks, int64_t& r0, int& nrows) {
-    const int64_t nw = (int64_t)nblocks * WAVES_PER_BLOCK;
-    const int64_t gw = (int64_t)block * WAVES_PER_BLOCK + wave_in_block();
-    const int64_t per = (n + nw - 1) / nw;
-    int64_t a = gw * per;
-    const int64_t b = a + per < n ? a + per : n;
-    if (a > n) a = n;
-    r0 = uniform_i64(a);
-    nrows = (int)(uniform_i64(b) - r0);
 }
 
 template <bool NT>
@@ -862,8 +805,6 @@ __global__ __launch_bounds__(BLOCK) void flat_predict_rows_kernel(
 // row with zero weight leaves every sum finite; the 8-row flush of lacc keeps its schedule.  s == 1 everywhere reproduces
 // the unweighted sums bit for bit (every product by 1 is exact), s == 2 doubles them exactly.  The unweighted
 // instantiations read no weight and are the code they were: the launch passes nullptr.
-__device__ __forceinline__ bool weight_is_zero(float s) { return (__float_as_uint(s) & 0x7fffffffu) == 0u; }
-
 template <int NSLOT, bool WEIGHTED>
 __global__ __launch_bounds__(BLOCK) void flat_fused_pk_kernel(
     const float* __restrict__ X, const float* __restrict__ pack, int64_t n, int J, int Jpad,
@@ -2767,27 +2708,8 @@ extern "C" int hgmm_flat_stats(hgmm_ctx* c, int cov_type, int variant, int J, co
 // control words -- so its results are the serial entry's bit for bit, whatever B is and whoever its neighbours are.  What the
 // serial kernels take as arguments the batched ones read from the member's row of a table (FlatBatchMember, hgmm_ctx.h):
 // wave-uniform scalar loads at the head of the kernel.  A member that has stopped returns from every later launch at the
-// stop word, as the serial kernels do.
-//
-// A pointer read from memory is a generic pointer to the compiler, and a generic pointer is dereferenced by flat_load: no
-// scalar loads for the row's coordinates, no global_load for the table.  The table holds device allocations only, so the
-// pointer is rebuilt from its bits as a pointer into the global address space -- what a kernel argument is by itself.  (Through
-// the integer: a cast to the global address space and back is folded away before the address spaces are inferred.)
-template <class T>
-__device__ __forceinline__ T* global_ptr(T* p) {
-    typedef __attribute__((address_space(1))) T* gptr;
-    return (T*)(gptr)(uintptr_t)p;
-}
-// ... and the cloud, which nothing writes while a fit runs, as a pointer into the CONSTANT address space: a wave-uniform load
-// from it is a scalar load whatever else the kernel does (the serial kernel's `const float* __restrict__ X` argument says as
-// much; behind a plain global pointer the row loop's compiler barrier counts as a possible store, and the row's coordinates
-// arrive by vector loads into six more registers)
-template <class T>
-__device__ __forceinline__ const T* constant_ptr(const T* p) {
-    typedef __attribute__((address_space(4))) const T* cptr;
-    return (const T*)(cptr)(uintptr_t)p;
-}
-
+// stop word, as the serial kernels do.  (global_ptr, constant_ptr: flat_fused_device.h -- a pointer read from the table is
+// rebuilt as a pointer into the global resp. constant address space.)
 // One workgroup of member `me.x`, the member's workgroup number `me.y`: ONE 8-byte load, then the member's row.  (A search
 // over the members' first blocks would be a dozen dependent loads at the head of a kernel whose waves have 20 rows of work.)
 // Unweighted: a handle owns no weights.  The partials are stat-major (comp_major = 0: the boundary kernel is not batched); the
@@ -2815,10 +2737,11 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_batch_kernel(
 }
 
 // blockIdx.y = member in the three small kernels; blockIdx.x is what it is in the serial launch
+// (m.wn: what flat_n() is to the serial launch -- the slot's weight sum, or (double)n)
 __global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_batch_kernel(
     const FlatBatchMember* __restrict__ members, int valid_j, int Jpad, int parity) {
     const FlatBatchMember& m = members[blockIdx.y];
-    flat_reduce_body(global_ptr(m.partials), global_ptr(m.lpn_partials), m.nblocks, m.nblocks, valid_j, Jpad, (double)m.n,
+    flat_reduce_body(global_ptr(m.partials), global_ptr(m.lpn_partials), m.nblocks, m.nblocks, valid_j, Jpad, m.wn,
                      global_ptr(m.stats), global_ptr(m.ctl) + (parity ? 3 : 0));
 }
 
@@ -2851,21 +2774,10 @@ static auto fused_batch_kernel_for(int slots, std::integer_sequence<int, S...>) 
     return kernel;
 }
 
-extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clouds, int cov_type, int variant, int J,
-                                     int max_iter, float tol, float* mu, float* cov, float* w, float* inv_std_out,
-                                     float* lls_out, int32_t* n_iter_out, int32_t* converged_out) {
-    HGMM_ENTER(c);
-    const char* what = "hgmm_flat_train_batch";
-    // ---- refusals: all of them before anything resident is touched ----
+// every refusal the batched entries share, before anything is touched (the texts name the entry that was called)
+int hgmm::flat_batch_check(hgmm_ctx* c, const char* what, int B, int cov_type, int variant, int J, int max_iter, const float* mu,
+                           const float* cov, const float* w, const int32_t* n_iter_out, const int32_t* converged_out) {
     if (B < 1 || B > FLAT_BATCH_MAX) return fail(c, HGMM_ERR_ARG, "%s: B = %d outside 1..%d", what, B, FLAT_BATCH_MAX);
-    if (!clouds) return fail(c, HGMM_ERR_ARG, "%s: clouds is NULL", what);
-    for (int b = 0; b < B; ++b) {
-        const hgmm_points* p = clouds[b];
-        if (!p) return fail(c, HGMM_ERR_ARG, "%s: member %d is NULL", what, b);
-        if (p->ctx != c && p != &c->own_points)
-            return fail(c, HGMM_ERR_ARG, "%s: member %d belongs to another context", what, b);
-        if (p->n < 1 || !p->x_aos.p) return fail(c, HGMM_ERR_ARG, "%s: member %d holds no points", what, b);
-    }
     if (!mu || !cov || !w || !n_iter_out || !converged_out)
         return fail(c, HGMM_ERR_ARG, "%s: mu, cov, w, n_iter_out and converged_out must not be NULL", what);
     if (max_iter < 0) return fail(c, HGMM_ERR_ARG, "max_iter < 0");
@@ -2879,22 +2791,35 @@ extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clo
         return fail(c, HGMM_ERR_ARG, "%s: J = %d outside 1..%d: only the one-pass fused path is batched, the chunked path of "
                     "larger J stays serial (hgmm_flat_train, cloud by cloud)", what, J, FLAT_MAX_J);
     if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "%s: not under a communicator (the batch all-reduces nothing)", what);
+    return HGMM_OK;
+}
 
+// The launch set over B slots whose rows (and weights, where a slot has some) lie on the device.  flat_batch_check has passed.
+int hgmm::flat_batch_run(hgmm_ctx* c, const char* what, int B, const FlatBatchSlot* in, int cov_type, int variant, int J,
+                         int max_iter, float tol, float* mu, float* cov, float* w, float* inv_std_out, float* lls_out,
+                         int32_t* n_iter_out, int32_t* converged_out) {
     const int Jpad = round_up(J, 256);
     const int slots = (J + 63) / 64, valid_j = slots * 64;
     const int lls_cap = max_iter < 1 ? 1 : max_iter;
     const size_t ce = cov_elems(cov_type, J);
     const size_t blk_elems = 10 * (size_t)Jpad, pack_elems = (size_t)PK_ROWS * Jpad, part_elems = (size_t)FLAT_NSTAT * Jpad;
     const size_t stat_elems = part_elems + 2;
-    // the members' grids: the serial launch's grid for n_b, back to back in the fused launch
+    // the members' grids: the serial launch's grid for n_b, back to back in the fused launch -- in TWO segments, the
+    // unweighted slots' workgroups first (flat_fused_pk_batch_kernel<NSLOT>), then the weighted slots' (<NSLOT, true>); a
+    // segment is launched when it is not empty, so a batch of one kind costs one fused launch per iteration
     std::vector<FlatBatchMember> tab((size_t)B);
-    size_t total_grid = 0;
-    for (int b = 0; b < B; ++b) {
-        tab[b].n = clouds[b]->n;
-        tab[b].block0 = (int)total_grid;
-        tab[b].nblocks = fused_grid(c->cus, clouds[b]->n, slots);
-        total_grid += (size_t)tab[b].nblocks;
+    size_t total_grid = 0, grid_unweighted = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int b = 0; b < B; ++b) {
+            if ((in[b].SW != nullptr) != (pass == 1)) continue;
+            tab[b].n = in[b].n;
+            tab[b].block0 = (int)total_grid;
+            tab[b].nblocks = fused_grid(c->cus, in[b].n, slots);
+            total_grid += (size_t)tab[b].nblocks;
+        }
+        if (pass == 0) grid_unweighted = total_grid;
     }
+    const size_t grid_weighted = total_grid - grid_unweighted;
     const unsigned long long part_bytes = (unsigned long long)total_grid * part_elems * sizeof(float);
     if (part_bytes > FLAT_BATCH_MAX_PARTIALS)
         return fail(c, HGMM_ERR_ARG, "%s: the members' partial buffers need %llu bytes together (%zu workgroups x 7 x %d x 4), "
@@ -2914,7 +2839,9 @@ extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clo
     std::vector<int2> wg(total_grid);
     for (int b = 0; b < B; ++b) {
         FlatBatchMember& m = tab[b];
-        m.X = clouds[b]->x_aos.as<float>();
+        m.X = in[b].X;
+        m.SW = in[b].SW;
+        m.wn = in[b].wn;
         m.params = c->fb_params.as<float>() + blk_elems * b;
         m.pack = c->fb_pack.as<float>() + pack_elems * b;
         m.partials = c->fb_partials.as<float>() + part_elems * (size_t)m.block0;
@@ -2962,7 +2889,9 @@ extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clo
         const int parity = it & 1;
         {
             ProfScope prof(c, HGMM_K_FLAT_FUSED);
-            fused<<<(unsigned)total_grid, BLOCK, 0, c->stream>>>(d_tab, d_wg, J, Jpad, parity);
+            if (grid_unweighted) fused<<<(unsigned)grid_unweighted, BLOCK, 0, c->stream>>>(d_tab, d_wg, J, Jpad, parity);
+            if (grid_weighted)            // (<NSLOT, true>: flat_batch_weighted.hip)
+                launch_fused_batch_weighted(slots, (unsigned)grid_weighted, c->stream, d_tab, d_wg + grid_unweighted, J, Jpad, parity);
         }
         flat_reduce_batch_kernel<<<dim3(stat_blocks + 1, B), RED_IDX * RED_SLICES, 0, c->stream>>>(d_tab, valid_j, Jpad, parity);
         flat_finalize_batch_kernel<<<dim3(Jpad / 256, B), 256, 0, c->stream>>>(d_tab, J, Jpad, cov_type, variant, lls_cap, tol,
@@ -3005,4 +2934,79 @@ extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clo
         converged_out[b] = h_ctl[FLAT_BATCH_CTL_WORDS * (size_t)b + 2];
     }
     return HGMM_OK;
+}
+
+// what hgmm_flat_train_batch and hgmm_flat_train_batch_weighted check of their handles
+static int flat_batch_check_clouds(hgmm_ctx* c, const char* what, int B, hgmm_points* const* clouds) {
+    if (B < 1 || B > FLAT_BATCH_MAX) return fail(c, HGMM_ERR_ARG, "%s: B = %d outside 1..%d", what, B, FLAT_BATCH_MAX);
+    if (!clouds) return fail(c, HGMM_ERR_ARG, "%s: clouds is NULL", what);
+    for (int b = 0; b < B; ++b) {
+        const hgmm_points* p = clouds[b];
+        if (!p) return fail(c, HGMM_ERR_ARG, "%s: member %d is NULL", what, b);
+        if (p->ctx != c && p != &c->own_points)
+            return fail(c, HGMM_ERR_ARG, "%s: member %d belongs to another context", what, b);
+        if (p->n < 1 || !p->x_aos.p) return fail(c, HGMM_ERR_ARG, "%s: member %d holds no points", what, b);
+    }
+    return HGMM_OK;
+}
+
+static int flat_train_batch_handles(hgmm_ctx* c, const char* what, int B, hgmm_points* const* clouds, const float* const* s,
+                                    int cov_type, int variant, int J, int max_iter, float tol, float* mu, float* cov, float* w,
+                                    float* inv_std_out, float* lls_out, int32_t* n_iter_out, int32_t* converged_out) {
+    // ---- refusals: all of them before anything is touched ----
+    HGMM_TRY(flat_batch_check_clouds(c, what, B, clouds));
+    HGMM_TRY(flat_batch_check(c, what, B, cov_type, variant, J, max_iter, mu, cov, w, n_iter_out, converged_out));
+    // the value checks of hgmm_flat_set_weights, slot by slot, and its sum: float64, on the host, in index order
+    std::vector<FlatBatchSlot> slots((size_t)B);
+    std::vector<size_t> sw_at((size_t)B, 0);
+    size_t sw_total = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = clouds[b]->n;
+        slots[b] = FlatBatchSlot{clouds[b]->x_aos.as<float>(), n, nullptr, (double)n};
+        const float* sb = s ? s[b] : nullptr;
+        if (!sb) continue;
+        double sum = 0.0;
+        for (int64_t i = 0; i < n; ++i) {
+            if (!(sb[i] >= 0.0f) || !(sb[i] < INFINITY))                // (NaN fails the first comparison)
+                return fail(c, HGMM_ERR_ARG, "%s: slot %d: weight %lld is %g (weights must be finite and >= 0)", what, b,
+                            (long long)i, (double)sb[i]);
+            sum += (double)sb[i];
+        }
+        if (!(sum > 0.0)) return fail(c, HGMM_ERR_ARG, "%s: slot %d: all %lld weights are zero", what, b, (long long)n);
+        slots[b].wn = sum;
+        sw_at[b] = sw_total;
+        sw_total += (size_t)n;
+    }
+    if (sw_total) {
+        // ONE buffer of the batch's own and one copy into it, before the begin launch: nothing is uploaded between iterations,
+        // and the context's own flat weights (flat_sw, flat_wsum) are neither read nor written
+        HGMM_TRY(ensure(c, c->fb_sw,sizeof(float) * sw_total + 64));
+        std::vector<float> packed(sw_total);
+        for (int b = 0; b < B; ++b)
+            if (s[b]) {
+                std::memcpy(packed.data() + sw_at[b], s[b], sizeof(float) * (size_t)slots[b].n);
+                slots[b].SW = c->fb_sw.as<float>() + sw_at[b];
+            }
+        HGMM_HIP(c, hipMemcpyAsync(c->fb_sw.p, packed.data(), sizeof(float) * sw_total, hipMemcpyHostToDevice, c->stream));
+        HGMM_HIP(c, ctx_stream_sync(c));                    // (packed leaves scope)
+    }
+    return flat_batch_run(c, what, B, slots.data(), cov_type, variant, J, max_iter, tol, mu, cov, w, inv_std_out, lls_out,
+                          n_iter_out, converged_out);
+}
+
+extern "C" int hgmm_flat_train_batch(hgmm_ctx* c, int B, hgmm_points* const* clouds, int cov_type, int variant, int J,
+                                     int max_iter, float tol, float* mu, float* cov, float* w, float* inv_std_out,
+                                     float* lls_out, int32_t* n_iter_out, int32_t* converged_out) {
+    HGMM_ENTER(c);
+    return flat_train_batch_handles(c, "hgmm_flat_train_batch", B, clouds, nullptr, cov_type, variant, J, max_iter, tol, mu, cov,
+                                    w, inv_std_out, lls_out, n_iter_out, converged_out);
+}
+
+extern "C" int hgmm_flat_train_batch_weighted(hgmm_ctx* c, int B, hgmm_points* const* clouds, const float* const* s,
+                                              int cov_type, int variant, int J, int max_iter, float tol, float* mu, float* cov,
+                                              float* w, float* inv_std_out, float* lls_out, int32_t* n_iter_out,
+                                              int32_t* converged_out) {
+    HGMM_ENTER(c);
+    return flat_train_batch_handles(c, "hgmm_flat_train_batch_weighted", B, clouds, s, cov_type, variant, J, max_iter, tol, mu,
+                                    cov, w, inv_std_out, lls_out, n_iter_out, converged_out);
 }

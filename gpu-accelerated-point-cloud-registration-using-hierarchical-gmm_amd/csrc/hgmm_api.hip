@@ -781,7 +781,8 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->src_w, &c->fr_src_w, &c->t_w2, &c->t_w3, &c->flat_sw, &c->f_lpn_rows,
                       &c->vx_in, &c->vx_tab, &c->vx_keys, &c->vx_keys2, &c->vx_rows, &c->vx_rows2, &c->vx_heads, &c->vx_tmp,
                       &c->vx_cent, &c->vx_cnt, &c->vx_hand,
-                      &c->fb_tab, &c->fb_params, &c->fb_pack, &c->fb_partials, &c->fb_lpn_partials, &c->fb_stats, &c->fb_lls, &c->fb_ctl};
+                      &c->fb_tab, &c->fb_params, &c->fb_pack, &c->fb_partials, &c->fb_lpn_partials, &c->fb_stats, &c->fb_lls, &c->fb_ctl,
+                      &c->fb_sw, &c->fb_x};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);

@@ -63,6 +63,15 @@ struct FlatBatchMember {
     double* stats;                    // double [7 * Jpad + 2]
     float* lls;                       // float [lls_cap]
     int* ctl;                         // int [16], the layout of f_ctl: stop (even), n_iter, converged, stop (odd); float prev at [8]
+    const float* SW;                  // float [n] per-point weights of this SLOT (a handle owns none), or NULL: unweighted
+    double wn;                        // what flat_n() is to the serial launchers: the slot's weight sum S_b, or (double)n
+};
+// One slot of a batched fit as its entries hand it to the launch set (flat_batch_run, flat_kernels.hip): device pointers only.
+struct FlatBatchSlot {
+    const float* X;                   // float [n,3]
+    int64_t n;
+    const float* SW;                  // float [n] on the device, or NULL
+    double wn;                        // S_b, or (double)n
 };
 constexpr int FLAT_BATCH_MAX = 4096;                              // members per call
 constexpr unsigned long long FLAT_BATCH_MAX_PARTIALS = 8ull << 30;   // bytes of all members' partial buffers together
@@ -236,6 +245,8 @@ struct hgmm_ctx {
     hgmm::DevBuf fb_stats;                    // double [B][7 * Jpad + 2]
     hgmm::DevBuf fb_lls;                      // float [B][cap]
     hgmm::DevBuf fb_ctl;                      // int [B][16]
+    hgmm::DevBuf fb_sw;                       // float: the weights of the weighted slots of one call, slot after slot
+    hgmm::DevBuf fb_x;                        // float [sum m][3]: the rows of hgmm_flat_train_batch_voxels, slot after slot
     hgmm::DevBuf scratch;
     double* h_scalars = nullptr;              // pinned, device-visible scalars (hgmm_host_scalars)
     int h_scalars_n = 0;
@@ -464,6 +475,14 @@ int gather_rows(hgmm_ctx* c, const int64_t* dev_rows, int64_t k, double* dev_out
 // (voxel_handover.hip) init_rows [k] of hgmm_tree_build_rows / _batch_rows (host; `first`: what is added to every `per` rows,
 // NULL: nothing) -> scratch [k][3], the place the builds read their initial means from.  The rows have been checked.
 int stage_init_rows(hgmm_ctx* c, const int64_t* rows, int64_t k, const int64_t* first, int64_t per);
+// (flat_kernels.hip) the batched flat fit behind hgmm_flat_train_batch, _weighted and _voxels: flat_batch_check is every
+// refusal the three share (nothing is touched), flat_batch_run the launch set over slots whose rows and weights are on the
+// device already.  `what` names the entry in the messages.
+int flat_batch_check(hgmm_ctx* c, const char* what, int B, int cov_type, int variant, int J, int max_iter, const float* mu,
+                     const float* cov, const float* w, const int32_t* n_iter_out, const int32_t* converged_out);
+int flat_batch_run(hgmm_ctx* c, const char* what, int B, const FlatBatchSlot* slots, int cov_type, int variant, int J,
+                   int max_iter, float tol, float* mu, float* cov, float* w, float* inv_std_out, float* lls_out,
+                   int32_t* n_iter_out, int32_t* converged_out);
 
 // profiling brackets: record an event pair around one kernel launch when enabled
 struct ProfScope {

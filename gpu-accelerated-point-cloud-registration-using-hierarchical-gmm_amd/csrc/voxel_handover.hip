@@ -102,6 +102,23 @@ __global__ __launch_bounds__(HO_BLOCK) void handover_kernel(HandoverArgs a) {
     }
 }
 
+// The hand-over to the batched flat fit (hgmm_flat_train_batch_voxels): what handover_kernel writes for the flat fit and
+// nothing else -- the float32 row (float)centroid and the weight (float)count, by the same conversions -- slot after slot into
+// buffers of the batch's own.  One thread per destination row; no float64 planes, no pad, no sums.
+__global__ __launch_bounds__(HO_BLOCK) void handover_flat_kernel(const double* __restrict__ cent, const int64_t* __restrict__ cnt,
+                                                                  const int64_t* __restrict__ dst_first,
+                                                                  const int64_t* __restrict__ src_first, int B, int64_t total,
+                                                                  float* __restrict__ aos, float* __restrict__ wf) {
+    const int64_t i = (int64_t)blockIdx.x * HO_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    const int b = find_cloud(dst_first, B, i);
+    const int64_t src = src_first[b] + (i - dst_first[b]);
+    aos[3 * i] = (float)cent[3 * src];
+    aos[3 * i + 1] = (float)cent[3 * src + 1];
+    aos[3 * i + 2] = (float)cent[3 * src + 2];
+    if (wf) wf[i] = (float)cnt[src];
+}
+
 __global__ __launch_bounds__(HO_BLOCK) void gather_rows_kernel(const double* __restrict__ soa, int64_t n_pad,
                                                                 const int64_t* __restrict__ rows, int64_t k,
                                                                 double* __restrict__ out) {
@@ -363,6 +380,57 @@ extern "C" int hgmm_voxel_to_targets_batch(hgmm_ctx* c, int B, const int32_t* me
         F.tg_weighted = true;
     }
     return HGMM_OK;
+}
+
+extern "C" int hgmm_flat_train_batch_voxels(hgmm_ctx* c, int B, const int32_t* members, int weighted, int cov_type, int variant,
+                                            int J, int max_iter, float tol, float* mu, float* cov, float* w,
+                                            float* inv_std_out, float* lls_out, int32_t* n_iter_out, int32_t* converged_out) {
+    HGMM_ENTER(c);
+    const char* what = "hgmm_flat_train_batch_voxels";
+    // ---- refusals: all of them before anything is touched ----
+    HGMM_TRY(check_result(c, what));
+    HGMM_TRY(check_members(c, what, B, members, FLAT_BATCH_MAX));
+    HGMM_TRY(flat_batch_check(c, what, B, cov_type, variant, J, max_iter, mu, cov, w, n_iter_out, converged_out));
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t m = c->vx_mb[members[b]];
+        if (m < 1) return fail(c, HGMM_ERR_ARG, "%s: members[%d] = %d holds no points", what, b, members[b]);
+        // S_b is the member's raw point count (hgmm_voxel_to_points' rule), which is the sum of the float32 weights only
+        // while no count rounds
+        if (weighted && c->vx_nb[members[b]] >= ((int64_t)1 << 24))
+            return fail(c, HGMM_ERR_ARG, "%s: members[%d] = %d stands for %lld raw points, 2^24 or more: a count may round as "
+                        "a float32 weight; hand it over with hgmm_voxel_to_points(member, HGMM_VOXEL_W_FLAT), which sums such "
+                        "counts on the device, and fit it with hgmm_flat_train", what, b, members[b],
+                        (long long)c->vx_nb[members[b]]);
+        total += m;
+    }
+    // ---- ONE hand-over launch, whatever B is: rows and weights of every slot into fb_x / fb_sw ----
+    HGMM_TRY(ensure(c, c->fb_x, sizeof(float) * 3 * (size_t)total + 64));
+    if (weighted) HGMM_TRY(ensure(c, c->fb_sw, sizeof(float) * (size_t)total + 64));
+    std::vector<int64_t> tab((size_t)2 * B + 1);
+    std::vector<FlatBatchSlot> slots((size_t)B);
+    int64_t at = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t m = c->vx_mb[members[b]];
+        tab[b] = at;
+        tab[(size_t)B + 1 + b] = c->vx_first[members[b]];
+        slots[b].X = c->fb_x.as<float>() + 3 * at;
+        slots[b].n = m;
+        slots[b].SW = weighted ? c->fb_sw.as<float>() + at : nullptr;
+        slots[b].wn = weighted ? (double)c->vx_nb[members[b]] : (double)m;
+        at += m;
+    }
+    tab[B] = at;
+    HGMM_TRY(ensure(c, c->vx_hand, sizeof(int64_t) * tab.size() + 64));
+    HGMM_TRY(upload_table(c, c->vx_hand.p, tab.data(), sizeof(int64_t) * tab.size()));
+    if (sizeof(int64_t) * tab.size() > (256u << 10)) HGMM_HIP(c, ctx_stream_sync(c));    // (tab leaves scope)
+    const int64_t* d_first = c->vx_hand.as<int64_t>();
+    handover_flat_kernel<<<(unsigned)((total + HO_BLOCK - 1) / HO_BLOCK), HO_BLOCK, 0, c->stream>>>(
+        c->vx_cent.as<double>(), c->vx_cnt.as<int64_t>(), d_first, d_first + B + 1, B, total, c->fb_x.as<float>(),
+        weighted ? c->fb_sw.as<float>() : nullptr);
+    HGMM_HIP(c, hipGetLastError());
+    return flat_batch_run(c, what, B, slots.data(), cov_type, variant, J, max_iter, tol, mu, cov, w, inv_std_out, lls_out,
+                          n_iter_out, converged_out);
 }
 
 extern "C" int hgmm_points_rows_f64(hgmm_ctx* c, const int64_t* rows, int64_t k, double* out) {

@@ -10,12 +10,14 @@ caller timing "CPU vs GPU" is not comparing the engine with itself unknowingly. 
 imported when ``init()`` is called.
 """
 import abc
+import collections
 import warnings
 
 import numpy as np
 
 from . import gmm_impl
 from .gmm_impl import train_gmm, train_gmm_batch, init_gmm_params, timer, predict, asarray, DevicePoints  # noqa: F401
+from .._native import VoxelCloud
 
 
 class Feature(abc.ABC):
@@ -34,6 +36,9 @@ class Feature(abc.ABC):
 
     def __call__(self, data):
         return self.compute(data)
+
+
+_Weighted = collections.namedtuple("_Weighted", ["points", "weights"])      # (what _split_weighted takes apart)
 
 
 def _split_weighted(X, sample_weight):
@@ -88,31 +93,62 @@ class GMM_GPU_Base:
             print("\nLog Likelihood Min-Max:\n\n", np.min(lls), np.max(lls))
         return self
 
-    def fit_batch(self, frames, inits=None):
+    def fit_batch(self, frames, inits=None, sample_weight=None):
         """One fit per frame through ONE launch set (``train_gmm_batch``) -> a list of fitted estimators of this one's
         settings, each in the state ``.fit(frame)`` leaves one in (this estimator itself stays as it is).  ``inits``: one
         ``(means, weights, covs)`` per frame; without it they are drawn by the initialiser FRAME BY FRAME IN FRAME ORDER before
         the fit -- a loop of ``.fit`` consumes exactly that sequence of the host RNG, since the fit draws nothing -- so under
-        the same seed the models are bit for bit those of the loop.  Frames that bring per-point weights are refused."""
+        the same seed the models are bit for bit those of the loop.
+
+        ``sample_weight``: the convention of ``train_gmm_batch`` -- None: frames that bring per-point weights are refused;
+        ``"own"``: each frame's own (``DevicePoints.weights``, ``WeightedPoints.weights``); a sequence: one array or None (its
+        own) per frame.  The initialiser does not see the weights.
+
+        Frames that are all ``VoxelCloud`` s of one voxel result are fitted count-weighted where they lie: bit for bit the
+        loop of ``fit(centroids, sample_weight=counts)``.  Without ``inits`` the centroids are downloaded once, for the
+        initialiser, which samples the host array by the reference's definition; with ``inits`` nothing is downloaded."""
         frames = list(frames)
         if inits is not None and len(inits) != len(frames):
             raise ValueError("fit_batch: %d frames, but %d initialisations" % (len(frames), len(inits)))
+        n_vox = sum(1 for X in frames if isinstance(X, VoxelCloud))
+        if 0 < n_vox < len(frames):
+            raise ValueError("fit_batch: VoxelClouds and other frames in one batch (%d of %d are VoxelClouds): fit them in "
+                             "two calls" % (n_vox, len(frames)))
+        if n_vox and sample_weight is not None and not isinstance(sample_weight, str):
+            for b, s in enumerate(sample_weight):
+                if s is not None:
+                    raise ValueError("fit_batch: frame %d is a VoxelCloud, whose weights are its counts: it takes no explicit "
+                                     "sample_weight" % b)
         clouds, params = [], []
-        for b, X in enumerate(frames):
-            if getattr(X, "weights", None) is not None:
-                raise ValueError("fit_batch: frame %d brings per-point weights, which the batched fit does not take: fit it "
-                                 "with fit(frame)" % b)
-            X, _ = _split_weighted(X, None)
-            host = X.get() if isinstance(X, DevicePoints) else np.asarray(X)
+        if n_vox:
+            host = None
+            if inits is None:
+                frames[0].check()
+                host = frames[0].result.get()                    # (ONE download of the whole result, whatever B is)
+            for b, X in enumerate(frames):
+                params.append(inits[b] if inits is not None else self._init_params(host[X.index][0]))
+                clouds.append(X)
+        for b, X in enumerate(frames if not n_vox else ()):
+            if sample_weight is None and getattr(X, "weights", None) is not None:
+                raise ValueError("fit_batch: frame %d brings per-point weights, which the batched fit does not take unless the "
+                                 "call says so: pass sample_weight='own', or fit it with fit(frame)" % b)
+            P, _ = _split_weighted(X, None)
+            host = P.get() if isinstance(P, DevicePoints) else np.asarray(P)
             params.append(inits[b] if inits is not None else self._init_params(host))
-            clouds.append(X if isinstance(X, DevicePoints) else host.astype(np.float32))
+            if sample_weight is None:
+                clouds.append(P if isinstance(P, DevicePoints) else host.astype(np.float32))
+            elif isinstance(P, DevicePoints):
+                clouds.append(P)
+            else:                                                # (a WeightedPoints keeps its weights on the way down)
+                clouds.append(_Weighted(host.astype(np.float32), getattr(X, "weights", None)))
         if not frames:
             return []
         ctx = next((X.ctx for X in clouds if isinstance(X, DevicePoints)), None)
         with timer(self._label, ctx):
+            extra = {} if sample_weight is None else {"sample_weight": sample_weight}
             fits = train_gmm_batch(clouds, self.max_iter, self.tol, [np.asarray(p[0], np.float32) for p in params],
                                    [np.asarray(p[2], np.float32) for p in params],
-                                   [np.asarray(p[1], np.float32) for p in params], cov_type=self.cov_type)
+                                   [np.asarray(p[1], np.float32) for p in params], cov_type=self.cov_type, **extra)
         models = []
         for inv, mu, w, cov, lls in fits:
             m = type(self)(self.num_components, self.max_iter, self.tol, self.cov_type)

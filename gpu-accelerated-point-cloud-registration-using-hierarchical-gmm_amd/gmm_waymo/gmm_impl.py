@@ -70,11 +70,15 @@ def train_gmm(X, max_iter, tol, means, covariances, weights, cov_type='diag', sa
     return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, cov_type, VARIANT, sample_weight)
 
 
-def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type='diag'):
+def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type='diag', sample_weight=None):
     """B x :func:`train_gmm` in one launch set -> a list of its tuples, member b's bit for bit the serial call's.  ``Xs``:
-    host arrays and / or ``DevicePoints`` of one context; ``means``, ``covariances``, ``weights``: one per member, same J.
-    No per-point weights (a member that brings some is refused); J > 1024 runs as a loop of :func:`train_gmm`."""
-    return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, VARIANT)
+    host arrays and / or ``DevicePoints`` of one context, or ``VoxelCloud`` s of one voxel result (count-weighted, no host
+    trip); ``means``, ``covariances``, ``weights``: one per member, same J.  ``sample_weight``: None -- no per-point weights (a
+    member that brings some is refused); ``"own"`` -- each member's own; a sequence -- one array or None (its own) per member.
+    J > 1024 runs as a loop of :func:`train_gmm`."""
+    if sample_weight is None:
+        return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, VARIANT)
+    return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, cov_type, VARIANT, sample_weight=sample_weight)
 
 
 def predict(X, inv_cov, means, weights, cov_type='diag'):

@@ -39,12 +39,16 @@ def train_gmm(X, max_iter, tol, means, covariances, weights=None, sample_weight=
     return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, 'diag', VARIANT, sample_weight)
 
 
-def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights=None):
+def train_gmm_batch(Xs, max_iter, tol, means, covariances, weights=None, sample_weight=None):
     """B x :func:`train_gmm` in one launch set -> a list of its tuples, member b's bit for bit the serial call's
-    (``weights=None``: uniform, as there).  No per-point weights; J > 1024 runs as a loop of :func:`train_gmm`."""
+    (``weights=None``: uniform, as there).  ``sample_weight``: None -- no per-point weights (a member that brings some is
+    refused); ``"own"`` -- each member's own; a sequence -- one array or None (its own) per member; ``VoxelCloud`` s of one
+    voxel result are fitted count-weighted without a host trip.  J > 1024 runs as a loop of :func:`train_gmm`."""
     if weights is None:
         weights = [np.ones(len(m), dtype=np.float32) / len(m) for m in means]
-    return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, 'diag', VARIANT)
+    if sample_weight is None:
+        return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, 'diag', VARIANT)
+    return _flat.train_gmm_batch(Xs, max_iter, tol, means, covariances, weights, 'diag', VARIANT, sample_weight=sample_weight)
 
 
 def predict(X, inv_cov, means, weights):

@@ -167,7 +167,7 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
 
 
 def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag", devices=None,
-               contexts_per_device: int = 1, pool: ReplicaPool | None = None, batch: int = 1):
+               contexts_per_device: int = 1, pool: ReplicaPool | None = None, batch: int = 1, voxel_size=None):
     """One flat GMM per frame (``GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit(frame)``,
     gmm_waymo/src/gmm.py:65-84), the frames fanned out over the pool's contexts.  -> the fitted models in frame order.
 
@@ -175,7 +175,13 @@ def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag
     fused launch per iteration for all of them) -- a scan-sized frame alone is a chain of small launches that leaves the
     chip idle.  The last chunk may be short.  With one context and a seeded RNG the models are bitwise those of
     ``batch=1``: the initial parameters are drawn frame by frame in frame order either way.  (With several contexts the
-    worker threads share the host RNG, with or without ``batch``.)"""
+    worker threads share the host RNG, with or without ``batch``.)
+
+    ``voxel_size``: the reference's pipeline -- every frame is voxel-down-sampled before it is fitted
+    (run_gmm_static.py:28).  Each chunk of ``batch`` frames (``batch=1``: a chunk of one) is down-sampled on its context by
+    one launch set (``voxel_down_sample_batch(chunk, voxel_size, download=False)``) and fitted COUNT-WEIGHTED through
+    ``fit_batch`` where the centroids lie: a voxel counts as the raw points it stands for.  Only the initialiser's copy of
+    the centroids comes back to the host."""
     from .gmm_waymo.gmm import GMM_GPU_Base
 
     frames = list(frames)
@@ -189,12 +195,16 @@ def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag
     def chunk(ctx, part):
         return GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit_batch(part)
 
+    def voxel_chunk(ctx, part):
+        result = ctx.voxel_down_sample_batch(part, voxel_size, download=False)
+        return GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit_batch(result.members())
+
     own = pool is None
     pool = pool or ReplicaPool(devices, contexts_per_device)
     try:
-        if B > 1:
+        if B > 1 or voxel_size is not None:
             chunks = [frames[i:i + B] for i in range(0, len(frames), B)]
-            return [m for ms in pool.map(chunk, chunks) for m in ms]
+            return [m for ms in pool.map(chunk if voxel_size is None else voxel_chunk, chunks) for m in ms]
         return pool.map(one, frames)
     finally:
         if own:

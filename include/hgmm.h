@@ -239,6 +239,49 @@ int hgmm_flat_train_batch(hgmm_ctx* ctx, int B, hgmm_points* const* clouds /* [B
                           float* inv_std_out /* as cov, may be NULL */,
                           float* lls_out /* [B][max(max_iter,1)], may be NULL */,
                           int32_t* n_iter_out /* [B] */, int32_t* converged_out /* [B] */);
+/* hgmm_flat_train_batch with per-point weights that belong to a SLOT OF THIS CALL, not to a handle: s [B] host pointers, s[b]
+ * the n_b float32 weights of slot b or NULL (the slot is unweighted); s == NULL is hgmm_flat_train_batch.  Handles still own
+ * no weights, and hgmm_points_bind / hgmm_flat_set_weights keep their semantics.
+ * SEMANTICS.  Slot b is the sequence hgmm_points_bind(clouds[b]); hgmm_flat_set_weights(s[b], n_b); hgmm_flat_train(...): all
+ * seven outputs come out BIT FOR BIT as that sequence returns them, whatever B is and whoever the neighbours are.  S_b, what
+ * the M-step divides by, is the float64 host sum of s[b] in index order, as hgmm_flat_set_weights forms it.  A zero weight
+ * makes the row absent, NaN coordinates included.  A slot with s[b] == NULL has the unweighted serial fit's bits (so has a
+ * slot whose weights are all 1).  One handle may fill several slots with different weights: bootstrap restarts, a caller's
+ * own reweighting.
+ * LAUNCHES.  The weights of all weighted slots are packed into ONE buffer of the batch's own and uploaded once, before the
+ * begin launch; nothing is uploaded between iterations.  The fused launch's workgroups form two segments, the unweighted
+ * slots' (the kernels of hgmm_flat_train_batch) and the weighted slots' (the same body with the serial kernels' weight
+ * switch); a segment is launched when it is not empty: a mixed batch costs one more fused launch per iteration, a batch of one
+ * kind what hgmm_flat_train_batch costs.  Reduce and finalize stay one launch each.
+ * LIMITS.  Those of hgmm_flat_train_batch.  The call packs the weights on the host (one pass over them, with the checks).
+ * REFUSALS, each before anything resident is touched.  Every refusal of hgmm_flat_train_batch; and, per slot, the value checks of
+ * hgmm_flat_set_weights -- a NaN, infinite or negative weight, all-zero weights -- as HGMM_ERR_ARG with a message that names
+ * the slot and the index.  (The length of s[b] cannot be checked: it is n_b by contract.)
+ * LEFT ALONE.  Everything hgmm_flat_train_batch leaves alone; the context's own flat weights are neither read nor written. */
+int hgmm_flat_train_batch_weighted(hgmm_ctx* ctx, int B, hgmm_points* const* clouds /* [B] */,
+                                   const float* const* s /* NULL: none; s[b] NULL: slot b unweighted; else host [n_b] */,
+                                   int cov_type, int variant, int J, int max_iter, float tol,
+                                   float* mu, float* cov, float* w, float* inv_std_out, float* lls_out,
+                                   int32_t* n_iter_out /* [B] */, int32_t* converged_out /* [B] */);
+/* The batched fit fed from the resident voxel result (hgmm_voxel_downsample_*): slot b is member members[b] of it.
+ * SEMANTICS.  Slot b is the sequence hgmm_voxel_to_points(members[b], weighted ? HGMM_VOXEL_W_FLAT : 0); hgmm_flat_train(...),
+ * bit for bit: the rows are (float)centroid, the weights (float)count, and S_b is the member's raw point count as a double
+ * (hgmm_voxel_to_points' rule).  Unlike that sequence the call does not touch the resident cloud or its weights.  A member
+ * may fill several slots.  Outputs as hgmm_flat_train_batch.
+ * LAUNCHES.  ONE hand-over launch, whatever B is, writes every slot's rows and weights into buffers of the batch's own; then
+ * the launch set of hgmm_flat_train_batch_weighted (weighted: the weighted segment only; else the unweighted one).  No launch
+ * per member, no host pass over points or counts, no allocation once the buffers have their size.
+ * LIMITS.  Those of hgmm_flat_train_batch.  weighted: a member that stands for 2^24 raw points or more is refused (a count
+ * could round as a float32 weight, and S_b would no longer be the weights' sum): hand such a member over with
+ * hgmm_voxel_to_points, which sums the counts on the device, and fit it with hgmm_flat_train.
+ * REFUSALS.  HGMM_ERR_STATE without a voxel result; HGMM_ERR_ARG for a member outside the result, B < 1, NULL members, a
+ * member of 2^24 raw points (weighted); every refusal of hgmm_flat_train_batch that does not concern handles.
+ * LEFT ALONE.  Everything hgmm_flat_train_batch leaves alone.  The voxel result is read, not consumed:
+ * hgmm_voxel_downsample_get returns the same bytes afterwards. */
+int hgmm_flat_train_batch_voxels(hgmm_ctx* ctx, int B, const int32_t* members /* [B] of the voxel result */, int weighted,
+                                 int cov_type, int variant, int J, int max_iter, float tol,
+                                 float* mu, float* cov, float* w, float* inv_std_out, float* lls_out,
+                                 int32_t* n_iter_out /* [B] */, int32_t* converged_out /* [B] */);
 /* Sufficient statistics of ONE fused E+M pass on this context's points (after the
  * all-reduce when a communicator is attached): stats [J,7] doubles laid out
  * (s0, a_x, a_y, a_z, b_x, b_y, b_z) with a = sum r (x - mu_old), b = sum r (x - mu_old)^2,
