@@ -134,6 +134,9 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_fullcov_fit", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp,
                                        _vp, _vp, C.c_int, C.POINTER(C.c_int)])
         _sig(lib, "hgmm_fullcov_estep", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64p])
+        _sig(lib, "hgmm_fullcov_fit_weighted", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp,
+                                                _vp, _vp, C.c_int, C.POINTER(C.c_int)])
+        _sig(lib, "hgmm_fullcov_estep_weighted", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64p])
         _sig(lib, "hgmm_kmeans_plusplus", [ctx, C.c_int, C.c_int64, _vp, C.c_int, _vp, _vp])
         _sig(lib, "hgmm_kmeans_step", [ctx, C.c_int, _vp, C.c_int, _vp, _f64p, C.POINTER(C.c_int64)])
         _sig(lib, "hgmm_kmeans_labels", [ctx, _vp, _vp])
@@ -1507,7 +1510,9 @@ class Context:
         return out
 
     # -- flat full-covariance EM -----------------------------------------------------------
-    def fullcov_fit(self, J, ls, ld, init_mu, sig2, max_iters=1000):
+    def fullcov_fit(self, J, ls, ld, init_mu, sig2, max_iters=1000, weighted=False):
+        """``weighted``: the fit under the resident SOURCE weights (hgmm_fullcov_fit_weighted; ``tree_set_source_weights`` or
+        ``set_points_from_voxels(vc, tree_weights=True)``) -- HgmmError without them.  False: they are ignored."""
         init_mu = np.ascontiguousarray(init_mu, dtype=np.float64)
         if init_mu.shape != (J, 3):
             raise ValueError("init_mu must be [%d,3]" % J)
@@ -1515,12 +1520,13 @@ class Context:
         labels = np.empty(self.num_points, np.int32)
         q = np.zeros(int(max_iters))
         qlen = C.c_int()
-        self._check(self.lib.hgmm_fullcov_fit(self.h, int(J), float(ls), float(ld), _ptr(init_mu), float(sig2),
-                                              int(max_iters), _ptr(pi), _ptr(mu), _ptr(cov), _ptr(labels), _ptr(q),
-                                              int(max_iters), C.byref(qlen)))
+        fit = self.lib.hgmm_fullcov_fit_weighted if weighted else self.lib.hgmm_fullcov_fit
+        self._check(fit(self.h, int(J), float(ls), float(ld), _ptr(init_mu), float(sig2), int(max_iters), _ptr(pi), _ptr(mu),
+                        _ptr(cov), _ptr(labels), _ptr(q), int(max_iters), C.byref(qlen)))
         return pi, mu, cov, labels, q[:qlen.value].copy()
 
-    def fullcov_estep(self, pi, mu, cov):
+    def fullcov_estep(self, pi, mu, cov, weighted=False):
+        """``weighted``: the moments and q under the resident SOURCE weights (hgmm_fullcov_estep_weighted)."""
         pi = np.ascontiguousarray(pi, dtype=np.float64)
         J = len(pi)
         mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(J, 3)
@@ -1528,8 +1534,8 @@ class Context:
         m0, m1, m2 = np.empty(J), np.empty((J, 3)), np.empty((J, 3, 3))
         labels = np.empty(self.num_points, np.int32)
         q = C.c_double()
-        self._check(self.lib.hgmm_fullcov_estep(self.h, J, _ptr(pi), _ptr(mu), _ptr(cov), _ptr(m0), _ptr(m1), _ptr(m2),
-                                                _ptr(labels), C.byref(q)))
+        estep = self.lib.hgmm_fullcov_estep_weighted if weighted else self.lib.hgmm_fullcov_estep
+        self._check(estep(self.h, J, _ptr(pi), _ptr(mu), _ptr(cov), _ptr(m0), _ptr(m1), _ptr(m2), _ptr(labels), C.byref(q)))
         return m0, m1, m2, labels, q.value
 
     # -- KMeans initialiser (float64 points) -------------------------------------------------

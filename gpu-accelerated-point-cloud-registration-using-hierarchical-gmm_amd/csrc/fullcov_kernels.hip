@@ -30,52 +30,28 @@ constexpr int FULL_WAVES = 2;        // waves per workgroup of the moments kerne
 constexpr int FULL_BLOCK = FULL_WAVES * 64;
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
+// The bodies of full_pass_kernel, full_moments_kernel and full_fused_f32_kernel are in fullcov_body.h, included once per kernel
+// under `constexpr bool WEIGHTED` and `wsrc` (hgmm_fullcov_*_weighted: the points' weights [n], parallel to xs): the unweighted
+// kernels are compiled from the text they always had.  The weight multiplies the point's log-likelihood term in the pass and
+// its feature row in the moments; gamma, its floor and the arg-max never see it.
 __global__ __launch_bounds__(CH) void full_pass_kernel(const double* __restrict__ xs, int64_t n, int64_t n_pad,
                                                        const double* __restrict__ prep, int J,
                                                        double* __restrict__ den_out, int* __restrict__ label_out,
                                                        double* __restrict__ block_q) {
-    __shared__ double tile[LL_TILE][11];
-    __shared__ double shq[CH / 64];
-    const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
-    const bool active = i < n;
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
-    if (active) { x0 = xs[i]; x1 = xs[n_pad + i]; x2 = xs[2 * n_pad + i]; }
-    double den = 0.0, tot = 0.0, best = -1.0;
-    int am = 0;
-    for (int base = 0; base < J; base += LL_TILE) {
-        const int cnt = (J - base < LL_TILE) ? J - base : LL_TILE;
-        __syncthreads();
-        for (int t = threadIdx.x; t < cnt * 11; t += CH) {
-            const int node = t / 11, fidx = t % 11;
-            tile[node][fidx] = prep[PREP_N * (base + node) + fidx];
-        }
-        __syncthreads();
-        for (int node = 0; node < cnt; ++node) {
-            const double wE = tile[node][9];
-            if (wE == 0.0) continue;                                    // workgroup-uniform
-            const double d0 = x0 - tile[node][6], d1 = x1 - tile[node][7], d2 = x2 - tile[node][8];
-            const double q = sym3_quad(tile[node][0], tile[node][1], tile[node][2], tile[node][3], tile[node][4],
-                                       tile[node][5], d0, d1, d2);
-            double g = 0.0;
-            if (__any(q < 1500.0)) g = wE * exp(-0.5 * q);
-            den += g;
-            if (tile[node][10] != 0.0) tot += g;      // pi >= eps: counts towards the log-likelihood
-            if (g > best) { best = g; am = base + node; }
-        }
-    }
-    if (active) {
-        den_out[i] = den;
-        label_out[i] = (den > TREE_EPS) ? am : 0;   // all gammas zero -> argmax = 0 (C:178,184)
-    }
-    double lq = active ? log(fmax(tot, TREE_EPS)) : 0.0;
-    lq = wave_sum_f64(lq);
-    if (lane_id() == 0) shq[wave_in_block()] = lq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < CH / 64; ++w) t += shq[w];
-        block_q[blockIdx.x] = t;
-    }
+    constexpr bool WEIGHTED = false;
+    const double* const wsrc = nullptr;
+#define FULLCOV_BODY 1
+#include "fullcov_body.h"
+#undef FULLCOV_BODY
+}
+__global__ __launch_bounds__(CH) void full_pass_w_kernel(const double* __restrict__ xs, int64_t n, int64_t n_pad,
+                                                         const double* __restrict__ prep, int J,
+                                                         double* __restrict__ den_out, int* __restrict__ label_out,
+                                                         double* __restrict__ block_q, const double* __restrict__ wsrc) {
+    constexpr bool WEIGHTED = true;
+#define FULLCOV_BODY 1
+#include "fullcov_body.h"
+#undef FULLCOV_BODY
 }
 
 // grid = persistent workgroups, each owning a contiguous range of 64-point groups
@@ -83,73 +59,21 @@ __global__ __launch_bounds__(FULL_BLOCK) void full_moments_kernel(const double* 
                                                           const double* __restrict__ prep, int J16,
                                                           const double* __restrict__ den_in,
                                                           double* __restrict__ partials /*[grid][J16][NMOM]*/) {
-    __shared__ double G[FULL_WAVES][16][FULL_LD];    // gamma, component-major, per wave
-    __shared__ double F[FULL_WAVES][16][FULL_LD];    // features, feature-major, per wave
-    __shared__ double red[FULL_WAVES][16][16];
-    const int w = wave_in_block(), lane = lane_id();
-    const int64_t groups = (n + 63) / 64;
-    const int64_t nw = (int64_t)gridDim.x * FULL_WAVES;
-    const int64_t per = (groups + nw - 1) / nw;
-    const int64_t gw = (int64_t)blockIdx.x * FULL_WAVES + w;
-    const int64_t g0 = gw * per, g1 = (g0 + per < groups) ? g0 + per : groups;
-    const int a_idx = lane & 15, b_idx = lane >> 4;
-
-    for (int tile = 0; tile < J16; tile += 16) {
-        double4_t acc = {0.0, 0.0, 0.0, 0.0};
-        for (int64_t grp = g0; grp < g1; ++grp) {
-            const int64_t i = grp * 64 + lane;
-            const bool active = i < n;
-            double x0 = 0.0, x1 = 0.0, x2 = 0.0, inv_den = 0.0;
-            if (active) {
-                x0 = xs[i]; x1 = xs[n_pad + i]; x2 = xs[2 * n_pad + i];
-                const double den = den_in[i];
-                inv_den = (den > TREE_EPS) ? 1.0 / den : 0.0;
-            }
-            // features of this lane's point, feature-major
-            F[w][0][lane] = 1.0; F[w][1][lane] = x0; F[w][2][lane] = x1; F[w][3][lane] = x2;
-            F[w][4][lane] = x0 * x0; F[w][5][lane] = x0 * x1; F[w][6][lane] = x0 * x2;
-            F[w][7][lane] = x1 * x1; F[w][8][lane] = x1 * x2; F[w][9][lane] = x2 * x2;
-#pragma unroll
-            for (int f = 10; f < 16; ++f) F[w][f][lane] = 0.0;
-#pragma unroll
-            for (int cc = 0; cc < 16; ++cc) {
-                const double* pr = prep + PREP_N * (tile + cc);     // wave-uniform
-                const double wE = pr[9];
-                double gam = 0.0;
-                if (wE != 0.0) {
-                    const double d0 = x0 - pr[6], d1 = x1 - pr[7], d2 = x2 - pr[8];
-                    const double q = sym3_quad(pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], d0, d1, d2);
-                    if (__any(q < 1500.0)) gam = wE * exp(-0.5 * q) * inv_den;
-                    // reference: gamma = g / den (C:176); accumulate() drops gamma < eps (C:100)
-                    if (gam < TREE_EPS || !active) gam = 0.0;
-                }
-                G[w][cc][lane] = gam;
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): this wave's LDS writes landed
-            __builtin_amdgcn_wave_barrier();
-            // 16 MFMAs: D[comp][feat] += sum over the 4 points of sub-group s
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const double a = G[w][a_idx][4 * s + b_idx];
-                const double b = F[w][a_idx][4 * s + b_idx];
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        // D layout (f64 16x16x4): row (component) = (lane >> 4) + 4 r, col (feature) = lane & 15
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[w][b_idx + 4 * r][a_idx] = acc[r];
-        __syncthreads();
-        // fixed-order combination of the workgroup's waves, one partial per workgroup
-        for (int e = threadIdx.x; e < 16 * NMOM; e += FULL_BLOCK) {
-            const int comp = e / NMOM, feat = e % NMOM;
-            double t = 0.0;
-#pragma unroll
-            for (int ww = 0; ww < FULL_WAVES; ++ww) t += red[ww][comp][feat];
-            partials[((size_t)blockIdx.x * J16 + tile + comp) * NMOM + feat] = t;
-        }
-        __syncthreads();
-    }
+    constexpr bool WEIGHTED = false;
+    const double* const wsrc = nullptr;
+#define FULLCOV_BODY 2
+#include "fullcov_body.h"
+#undef FULLCOV_BODY
+}
+__global__ __launch_bounds__(FULL_BLOCK) void full_moments_w_kernel(const double* __restrict__ xs, int64_t n, int64_t n_pad,
+                                                            const double* __restrict__ prep, int J16,
+                                                            const double* __restrict__ den_in,
+                                                            double* __restrict__ partials /*[grid][J16][NMOM]*/,
+                                                            const double* __restrict__ wsrc) {
+    constexpr bool WEIGHTED = true;
+#define FULLCOV_BODY 2
+#include "fullcov_body.h"
+#undef FULLCOV_BODY
 }
 
 // ------------------------------------------------------------------------------------------
@@ -179,8 +103,9 @@ constexpr int FT_MAX_J16 = 1024;
 __host__ __device__ inline int ft_ldg(int J16) {        // doubles per point row of g: == 16 (mod 32), and room
     return (J16 + 127) / 128 * 128 + 16;                // for whole 128-column steps (tail columns stay 0)
 }
-inline size_t ft_lds_bytes(int J16) {
-    return sizeof(double) * ((size_t)FT_P * ft_ldg(J16) + 16 * FT_LDF + 3 * FT_P + J16 + 4 * 3 * FT_P + EXP_TAB2_N);
+inline size_t ft_lds_bytes(int J16, bool weighted = false) {      // (weighted: + the tiles' weights, see WX / WT)
+    return sizeof(double) * ((size_t)FT_P * ft_ldg(J16) + 16 * FT_LDF + 3 * FT_P + J16 + 4 * 3 * FT_P + EXP_TAB2_N +
+                             (weighted ? 4 * FT_P : 0));
 }
 
 // The kernel's body, specialised at compile time on the form of the exponent:
@@ -190,11 +115,16 @@ inline size_t ft_lds_bytes(int J16) {
 //          form carries a relative error of ~ eps |x - o| / sigma in the exponent: 1e-13 for millimetre clusters in a
 //          metre-sized cloud, far inside the parity tolerances.)
 //   !CHOL  the symmetric form, for node tables with a Sigma^-1 that failed the Cholesky test (flags bit 0).
-template <int CPL, bool CHOL>
+// ... and on WEIGHTED (hgmm_fullcov_*_weighted; `wsrc` [n] parallel to xs): the tile's weights are staged next to its
+// coordinates (0 for the rows past the cloud's end), phase B writes the feature row of point p as w_p f -- the weight rides in
+// the B operand of the matrix product, the A operand (gamma and its floor) and the arg-max are what they are without it --
+// and the point's log-likelihood term is multiplied by w_p.
+template <int CPL, bool CHOL, bool WEIGHTED>
 __device__ __forceinline__ void full_fused_body(
     const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ prep, int J16,
     int* __restrict__ label_out, double* __restrict__ block_q, double* __restrict__ partials /*[grid][J16][NMOM]*/,
-    int want_stats, long long* __restrict__ dbg, double* lds, const double* __restrict__ exp2_tab) {
+    int want_stats, long long* __restrict__ dbg, double* lds, const double* __restrict__ exp2_tab,
+    const double* __restrict__ wsrc) {
     long long tA = 0, tB = 0, tC = 0, tW = 0, tm = 0;
 #define FT_TICK(acc) do { if (dbg) { const long long now_ = clock64(); acc += now_ - tm; tm = now_; } } while (0)
     const int LDG = ft_ldg(J16);
@@ -206,6 +136,8 @@ __device__ __forceinline__ void full_fused_body(
     double* XS = WL + J16;                        // [2][3][FT_P] the tile's coordinates relative to the origin, double-buffered
     double* XA = XS + 2 * 3 * FT_P;               // [2][3][FT_P] ... and as given (the statistics' features)
     double* EXPT = XA + 2 * 3 * FT_P;             // [2048] 2^(j/2048) for exp_t11_4
+    double* WX = EXPT + EXP_TAB2_N;               // (WEIGHTED) [2][FT_P] the tile's weights, double-buffered like XA
+    double* WT = WX + 2 * FT_P;                   // (WEIGHTED) [2][FT_P] ... by tile parity like TOT, for its log terms
     const int w = wave_in_block(), lane = lane_id();
     const int tid = (int)threadIdx.x;
     exp_tab2_load(EXPT, exp2_tab);                // (the barrier behind the WL / G initialisation covers it)
@@ -284,7 +216,22 @@ __device__ __forceinline__ void full_fused_body(
     const int st_d = tid / FT_P, st_p = tid % FT_P;                      // the staging threads' (coordinate, point)
     const double st_o = (tid < 3 * FT_P) ? xs[(size_t)st_d * n_pad] : 0.0;    // ... and their coordinate of the origin
     auto stage = [&](int64_t tile, int buf) {
-        if (tid < 3 * FT_P) {
+        if (WEIGHTED) {
+            // threads 48..63 bring the points' weights (past the end: 0) by the SAME load instruction as the coordinates: a
+            // branch of their own put a second memory round trip behind the first one at the end of wave 0's phase A
+            if (tid < 4 * FT_P) {
+                const int64_t i = tile * FT_P + st_p;
+                const int64_t ic = i < n ? i : n - 1;
+                const bool is_w = st_d == 3;
+                const double v = *(is_w ? wsrc + ic : xs + (size_t)st_d * n_pad + ic);
+                if (is_w) {
+                    WX[buf * FT_P + st_p] = i < n ? v : 0.0;
+                } else {
+                    XA[(buf * 3 + st_d) * FT_P + st_p] = v;
+                    XS[(buf * 3 + st_d) * FT_P + st_p] = v - st_o;
+                }
+            }
+        } else if (tid < 3 * FT_P) {
             int64_t i = tile * FT_P + st_p;
             i = i < n ? i : n - 1;
             const double v = xs[(size_t)st_d * n_pad + i];
@@ -297,6 +244,7 @@ __device__ __forceinline__ void full_fused_body(
     auto tile_loglik = [&](int par) {
         const double tv = (lane < FT_P) ? TOT[par * FT_P + lane] : -1.0;
         double term = (tv >= 0.0) ? log(fmax(tv, TREE_EPS)) : 0.0;
+        if (WEIGHTED) term *= (lane < FT_P) ? WT[par * FT_P + lane] : 0.0;
         term = wave_sum_f64(term);
         lq += term;
     };
@@ -473,6 +421,7 @@ __device__ __forceinline__ void full_fused_body(
                 INV[p] = (live && good) ? inv : 0.0;
                 TOT[buf * FT_P + p] = live ? tot_h : -1.0;             // its log is taken during the next tile's phase A
                 if (live) label_out[base + p] = good ? (h ? c1 : c0) : 0;   // all gammas zero -> argmax = 0 (C:178,184)
+                if (WEIGHTED) WT[buf * FT_P + p] = WX[buf * FT_P + p];
             }
             if (sub < 16) {
                 const double* A = XA + buf * 3 * FT_P;                 // cloud coordinates
@@ -491,6 +440,7 @@ __device__ __forceinline__ void full_fused_body(
                     case 9: f = x2 * x2; break;
                     default: f = 0.0;
                 }
+                if (WEIGHTED) f *= WX[buf * FT_P + p];
                 F[sub * FT_LDF + p] = f;
             }
         }
@@ -572,9 +522,23 @@ __global__ __launch_bounds__(FT_BLOCK) void full_fused_kernel(
     extern __shared__ double lds[];
     if (done && *done) return;                     // the loop stopped in an earlier iteration of this batch
     if (flags && (*flags & 1))                     // kernel-uniform: some Sigma^-1 failed the Cholesky test
-        full_fused_body<CPL, false>(xs, n, n_pad, prep, J16, label_out, block_q, partials, want_stats, dbg, lds, exp2_tab);
+        full_fused_body<CPL, false, false>(xs, n, n_pad, prep, J16, label_out, block_q, partials, want_stats, dbg, lds, exp2_tab, nullptr);
     else
-        full_fused_body<CPL, true>(xs, n, n_pad, prep, J16, label_out, block_q, partials, want_stats, dbg, lds, exp2_tab);
+        full_fused_body<CPL, true, false>(xs, n, n_pad, prep, J16, label_out, block_q, partials, want_stats, dbg, lds, exp2_tab, nullptr);
+}
+// ... under the weights `wsrc` (hgmm_fullcov_fit_weighted / hgmm_fullcov_estep_weighted)
+template <int CPL>
+__global__ __launch_bounds__(FT_BLOCK) void full_fused_w_kernel(
+    const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ prep, int J16,
+    int* __restrict__ label_out, double* __restrict__ block_q, double* __restrict__ partials /*[grid][J16][NMOM]*/,
+    int want_stats, const int* __restrict__ flags, const double* __restrict__ exp2_tab,
+    long long* __restrict__ dbg, const int* __restrict__ done, const double* __restrict__ wsrc) {
+    extern __shared__ double lds[];
+    if (done && *done) return;
+    if (flags && (*flags & 1))
+        full_fused_body<CPL, false, true>(xs, n, n_pad, prep, J16, label_out, block_q, partials, want_stats, dbg, lds, exp2_tab, wsrc);
+    else
+        full_fused_body<CPL, true, true>(xs, n, n_pad, prep, J16, label_out, block_q, partials, want_stats, dbg, lds, exp2_tab, wsrc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -627,281 +591,35 @@ __host__ __device__ inline int ff_ld(int J16) {            // floats per point r
     while ((ld & 63) != 16 && (ld & 63) != 48) ld += 16;
     return ld;
 }
-inline size_t ff_lds_bytes(int J16) {
-    return sizeof(float) * ((size_t)FF_P * ff_ld(J16) + 16 * FF_P + FF_P + J16 + 2 * 2 * 3 * FF_P * 2) + sizeof(double) * (2 * FF_P + 2);
+inline size_t ff_lds_bytes(int J16, bool weighted = false) {       // (weighted: + the tiles' weights, see WX / WT)
+    return sizeof(float) * ((size_t)FF_P * ff_ld(J16) + 16 * FF_P + FF_P + J16 + 2 * 2 * 3 * FF_P * 2) +
+           sizeof(double) * (2 * FF_P + 2 + (weighted ? 4 * FF_P : 0));
 }
 
+// WEIGHTED (hgmm_fullcov_*_weighted; `wsrc` [n] parallel to xs): the tile's weights are staged with its coordinates (0 past the
+// cloud's end); phase B converts w_p to float32 once and writes the feature row about the centroid as w_p f, and the point's
+// log term is multiplied by w_p in float64.  The origin stays the UNWEIGHTED centroid: it is a reference point only, and the
+// move back in full_reduce_f32_kernel holds for any o because it uses the (weighted) m0.
 __global__ __launch_bounds__(FF_BLOCK, 4) void full_fused_f32_kernel(
     const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ prep, int J16,
     int* __restrict__ label_out, double* __restrict__ block_q, float* __restrict__ partials /*[segments][J16][NMOM]*/,
     int segs_per_wg, int want_stats, const int* __restrict__ flags, const int* __restrict__ done,
     const double* __restrict__ origin_parts, long long* __restrict__ dbg) {
-    extern __shared__ double lds_raw[];
-    if (done && *done) return;
-    const bool use_chol = !(flags && (*flags & 1));        // kernel-uniform: some Sigma^-1 failed its factorisation -> symmetric form
-    long long tA = 0, tB = 0, tC = 0, tW = 0, tm = 0;
-#define FF_TICK(acc) do { if (dbg) { const long long now_ = clock64(); acc += now_ - tm; tm = now_; } } while (0)
-    const int LD = ff_ld(J16);
-    double* TOT = lds_raw;                                  // [2][FF_P] row sums over the components with pi >= eps (-1: dead point)
-    float* G = reinterpret_cast<float*>(TOT + 2 * FF_P + 2);      // [FF_P][LD]
-    float* F = G + (size_t)FF_P * LD;                       // [FF_P points][16 features]
-    float* INV = F + 16 * FF_P;                             // [FF_P] 1 / denominator (0: dead point)
-    float* WL = INV + FF_P;                                 // [J16] 1 where pi_j >= eps
-    f2t* XH = reinterpret_cast<f2t*>(WL + J16);             // [2][3][FF_P] {v, v}: head of x - o, double-buffered
-    f2t* XT = XH + 2 * 3 * FF_P;                            // ... and its tail
-    const int w = wave_in_block(), lane = lane_id();
-    const int tid = (int)threadIdx.x;
-    const int npair = J16 / 2;
-    const bool mine = tid < npair;
-    // the origin: wave 0 adds the partial sums up, everybody reads the three numbers from LDS (TOT's row 0 is not used
-    // before the first tile's phase B, two barriers from here)
-    if (tid < 64) {
-        const double inv_n = 1.0 / (double)n;
-        const double c0 = ff_origin(origin_parts, 0, inv_n), c1 = ff_origin(origin_parts, 1, inv_n), c2 = ff_origin(origin_parts, 2, inv_n);
-        if (tid == 0) { TOT[0] = c0; TOT[1] = c1; TOT[2] = c2; }
-    }
-    __syncthreads();
-    const double o0 = TOT[0], o1 = TOT[1], o2 = TOT[2];
-    __syncthreads();
-    // this lane's two components 2 tid, 2 tid + 1
-    f2t r00 = {0.f, 0.f}, r01 = r00, r02 = r00, r11 = r00, r12 = r00, r22 = r00, nh0 = r00, nh1 = r00, nh2 = r00, nt0 = r00,
-        nt1 = r00, nt2 = r00, we = r00;
-    if (mine) {
-        float v[2][13];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const double* pr = prep + PREP_N * (2 * tid + c);
-            // triangular form: sqrt(log2 e) R;  symmetric form: (log2 e / 2) Sigma^-1
-            const double S = use_chol ? LLF_SQRT_LOG2E : 0.5 * LLF_LOG2E;
-            const int fo = use_chol ? PREP_R : 0;
-            const double u0 = pr[6] - o0, u1 = pr[7] - o1, u2 = pr[8] - o2;
-            v[c][0] = llf_f32(S * pr[fo]); v[c][1] = llf_f32(S * pr[fo + 1]); v[c][2] = llf_f32(S * pr[fo + 2]);
-            v[c][3] = llf_f32(S * pr[fo + 3]); v[c][4] = llf_f32(S * pr[fo + 4]); v[c][5] = llf_f32(S * pr[fo + 5]);
-            const float h0 = (float)u0, h1 = (float)u1, h2 = (float)u2;
-            v[c][6] = -h0; v[c][7] = -h1; v[c][8] = -h2;
-            v[c][9] = -(float)(u0 - (double)h0); v[c][10] = -(float)(u1 - (double)h1); v[c][11] = -(float)(u2 - (double)h2);
-            v[c][12] = (float)pr[9];
-        }
-        r00 = f2t{v[0][0], v[1][0]}; r01 = f2t{v[0][1], v[1][1]}; r02 = f2t{v[0][2], v[1][2]};
-        r11 = f2t{v[0][3], v[1][3]}; r12 = f2t{v[0][4], v[1][4]}; r22 = f2t{v[0][5], v[1][5]};
-        nh0 = f2t{v[0][6], v[1][6]}; nh1 = f2t{v[0][7], v[1][7]}; nh2 = f2t{v[0][8], v[1][8]};
-        nt0 = f2t{v[0][9], v[1][9]}; nt1 = f2t{v[0][10], v[1][10]}; nt2 = f2t{v[0][11], v[1][11]};
-        we = f2t{v[0][12], v[1][12]};
-    }
-    int my_small = 0;
-    for (int j = tid; j < J16; j += FF_BLOCK) {
-        const double wl = prep[PREP_N * j + 10], wev = prep[PREP_N * j + 9];
-        WL[j] = (wl != 0.0) ? 1.f : 0.f;
-        if (wl == 0.0 && wev != 0.0) my_small = 1;
-    }
-    for (int e = tid; e < FF_P * LD; e += FF_BLOCK) G[e] = 0.f;
-    const bool any_small = __syncthreads_or(my_small) != 0;
-    const int ntiles = J16 / 16;
-    constexpr int MAXT = (FT_MAX_J16 / 16 + FF_WAVES - 1) / FF_WAVES;      // 8
-    f4t acc[MAXT];
-#pragma unroll
-    for (int t = 0; t < MAXT; ++t) acc[t] = f4t{0.f, 0.f, 0.f, 0.f};
-    const int a_idx = lane & 15, b_idx = lane >> 4;
-
-    const int64_t tiles = (n + FF_P - 1) / FF_P;
-    const int64_t per = (int64_t)segs_per_wg * FF_SEG;
-    const int64_t t0 = (int64_t)blockIdx.x * per;
-    const int64_t t1 = (t0 + per < tiles) ? t0 + per : tiles;
-    constexpr int LQ_WAVE = 7;                             // (the wave with the fewest components at J = 800)
-    double lq = 0.0;
-    const int st_d = tid / FF_P, st_p = tid % FF_P;
-    const double st_o = st_d == 0 ? o0 : (st_d == 1 ? o1 : o2);
-    auto stage = [&](int64_t tile, int buf) {
-        if (tid < 3 * FF_P) {
-            int64_t i = tile * FF_P + st_p;
-            i = i < n ? i : n - 1;
-            const double dv = xs[(size_t)st_d * n_pad + i] - st_o;
-            const float h = (float)dv, tl = (float)(dv - (double)h);
-            XH[(buf * 3 + st_d) * FF_P + st_p] = f2t{h, h};
-            XT[(buf * 3 + st_d) * FF_P + st_p] = f2t{tl, tl};
-        }
-    };
-    auto tile_loglik = [&](int par) {
-        const double tv = (lane < FF_P) ? TOT[par * FF_P + lane] : -1.0;
-        double term = (tv >= 0.0) ? log_pos_f64(fmax(tv, TREE_EPS)) : 0.0;
-        term = wave_sum_f64(term);
-        lq += term;
-    };
-    auto flush = [&](int64_t seg) {                        // the wave's accumulator tiles -> the segment's float partial
-        // (the segment index is made opaque: otherwise the eight tiles' addresses are formed ahead of the tile loop and kept
-        //  in registers through it -- 199 registers instead of 86)
-        int seg_lo = (int)seg;
-        asm volatile("" : "+s"(seg_lo));
-        seg = seg_lo;
-#pragma unroll
-        for (int t = 0; t < MAXT; ++t) {
-            const int ct = w + t * FF_WAVES;
-            if (ct < ntiles) {
-                if (a_idx < NMOM) {
-                    // D layout (f32 16x16x4): row (component) = 4 (lane >> 4) + r, column (feature) = lane & 15
-                    float* dst = partials + ((size_t)seg * J16 + 16 * ct + 4 * b_idx) * NMOM + a_idx;
-                    dst[0] = acc[t].x; dst[NMOM] = acc[t].y; dst[2 * NMOM] = acc[t].z; dst[3 * NMOM] = acc[t].w;
-                }
-                acc[t] = f4t{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    };
-    if (t0 < t1) stage(t0, 0);
-    __syncthreads();
-    for (int64_t seg0 = t0; seg0 < t1; seg0 += FF_SEG) {
-    const int64_t seg1 = (seg0 + FF_SEG < t1) ? seg0 + FF_SEG : t1;
-    for (int64_t tile = seg0; tile < seg1; ++tile) {
-        const int64_t base = tile * FF_P;
-        const int buf = (int)((tile - t0) & 1);
-        if (dbg) tm = clock64();
-        if (w == LQ_WAVE && tile > t0) tile_loglik(buf ^ 1);
-        // ---- phase A ----------------------------------------------------------------------------------------------
-        if (mine) {
-            const f2t* xh = XH + buf * 3 * FF_P;
-            const f2t* xt = XT + buf * 3 * FF_P;
-#pragma unroll 4
-            for (int p = 0; p < FF_P; ++p) {
-                const f2t d0 = (xh[p] + nh0) + (xt[p] + nt0);
-                const f2t d1 = (xh[FF_P + p] + nh1) + (xt[FF_P + p] + nt1);
-                const f2t d2 = (xh[2 * FF_P + p] + nh2) + (xt[2 * FF_P + p] + nt2);
-                f2t q;
-                if (use_chol) {
-                    const f2t z0 = llf_fma(r02, d2, llf_fma(r01, d1, r00 * d0));
-                    const f2t z1 = llf_fma(r12, d2, r11 * d1);
-                    const f2t z2 = r22 * d2;
-                    q = llf_fma(z2, z2, llf_fma(z1, z1, z0 * z0));
-                } else {
-                    const f2t t0 = llf_fma(llf_bc(2.f), llf_fma(r02, d2, r01 * d1), r00 * d0);
-                    const f2t t1 = llf_fma(llf_bc(2.f), r12 * d2, r11 * d1);
-                    q = llf_fma(d2, r22 * d2, llf_fma(d1, t1, d0 * t0));
-                }
-                const f2t e = f2t{__builtin_amdgcn_exp2f(-q.x), __builtin_amdgcn_exp2f(-q.y)};
-                *reinterpret_cast<f2t*>(G + (size_t)p * LD + 2 * tid) = we * e;
-            }
-        }
-        if (tile + 1 < t1) stage(tile + 1, buf ^ 1);
-        FF_TICK(tA);
-        __syncthreads();
-        FF_TICK(tW);
-        // ---- phase B: wave w owns points 2 w, 2 w + 1 (one per half-wave) ---------------------------------------------
-        {
-            const int h = lane >> 5, sub = lane & 31;
-            const int p = w * 2 + h;
-            const float* Gp = G + (size_t)p * LD;
-            const int J128 = (J16 + 127) & ~127;                       // (the row is zero beyond J16: LD >= J16 + 16 ... see below)
-            double den = 0.0, tot = 0.0;
-            float best = -1.f;
-            int jbest = 0;
-            for (int jb = 0; jb < J128; jb += 128) {
-                const int j = jb + 4 * sub;
-                f4t gv = f4t{0.f, 0.f, 0.f, 0.f};
-                if (j < J16) gv = *reinterpret_cast<const f4t*>(Gp + j);
-                const float m4 = fmaxf(fmaxf(gv.x, gv.y), fmaxf(gv.z, gv.w));
-                den += (double)((gv.x + gv.y) + (gv.z + gv.w));
-                jbest = (m4 > best) ? j : jbest;
-                best = fmaxf(best, m4);
-                if (any_small && j < J16) {
-                    const f4t wl = *reinterpret_cast<const f4t*>(WL + j);
-                    tot += (double)((gv.x * wl.x + gv.y * wl.y) + (gv.z * wl.z + gv.w * wl.w));
-                }
-            }
-            int am;
-            {
-                const f4t gv = *reinterpret_cast<const f4t*>(Gp + jbest);
-                am = jbest + ((gv.x == best) ? 0 : ((gv.y == best) ? 1 : ((gv.z == best) ? 2 : 3)));
-            }
-            double den0, den1, bm0, bm1;
-            halfwave_sum_f64(den, den0, den1);
-            halfwave_max_f64((double)best, bm0, bm1);
-            const double den_h = h ? den1 : den0;
-            const float bm_h = (float)(h ? bm1 : bm0);
-            int c0, c1;
-            halfwave_min_i32((best == bm_h) ? am : 0x7fffffff, c0, c1);
-            double tot_h = den_h;
-            if (any_small) {
-                double t0s, t1s;
-                halfwave_sum_f64(tot, t0s, t1s);
-                tot_h = h ? t1s : t0s;
-            }
-            const double inv = 1.0 / den_h;
-            if (sub == 0) {
-                const bool live = base + p < n;
-                const bool good = den_h > TREE_EPS;
-                INV[p] = (live && good) ? (float)inv : 0.f;
-                TOT[buf * FF_P + p] = live ? tot_h : -1.0;
-                if (live) label_out[base + p] = good ? (h ? c1 : c0) : 0;
-            }
-            if (sub < 16) {
-                const f2t* xh = XH + buf * 3 * FF_P;
-                const float x0 = xh[p].x, x1 = xh[FF_P + p].x, x2 = xh[2 * FF_P + p].x;
-                float f = 0.f;
-                switch (sub) {
-                    case 0: f = 1.f; break;
-                    case 1: f = x0; break;
-                    case 2: f = x1; break;
-                    case 3: f = x2; break;
-                    case 4: f = x0 * x0; break;
-                    case 5: f = x0 * x1; break;
-                    case 6: f = x0 * x2; break;
-                    case 7: f = x1 * x1; break;
-                    case 8: f = x1 * x2; break;
-                    case 9: f = x2 * x2; break;
-                    default: f = 0.f;
-                }
-                F[p * 16 + sub] = f;
-            }
-        }
-        FF_TICK(tB);
-        __syncthreads();
-        FF_TICK(tW);
-        // ---- phase C: v_mfma_f32_16x16x4_f32, A[i][k] in lane i + 16 k, B[k][j] in lane j + 16 k ----------------------
-        if (want_stats) {
-            float bfrag[4], ifrag[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                ifrag[s] = INV[4 * s + b_idx];
-                bfrag[s] = F[(4 * s + b_idx) * 16 + a_idx];
-            }
-            // (the next tile's four A values are requested before the current tile's are consumed; the fences keep the
-            //  compiler from requesting ALL tiles' values at once -- 168 registers instead of 84 for the rest of the kernel)
-            float araw[2][4];
-            const int row_off = b_idx * LD + a_idx, srow = 4 * LD;
-            auto load_a = [&](int ct, float (&dst)[4]) {
-                // (the tile's offset is made opaque: left alone the compiler forms all 28 addresses ahead of the loop, spills
-                //  them and reloads four per tile from scratch)
-                int off = row_off + 16 * ct;
-                asm volatile("" : "+v"(off));
-#pragma unroll
-                for (int s = 0; s < 4; ++s) dst[s] = G[off + s * srow];
-            };
-            if (w < ntiles) load_a(w, araw[0]);
-#pragma unroll
-            for (int t = 0; t < MAXT; ++t) {
-                const int ct = w + t * FF_WAVES;                       // wave-uniform
-                if (ct < ntiles) {
-                    if (t + 1 < MAXT && ct + FF_WAVES < ntiles) load_a(ct + FF_WAVES, araw[(t + 1) & 1]);
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        float a = araw[t & 1][s] * ifrag[s];
-                        if (a < 1.0e-15f) a = 0.f;                     // accumulate() drops gamma < eps (C:100)
-                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bfrag[s], acc[t], 0, 0, 0);
-                    }
-                    asm volatile("" ::: "memory");
-                }
-            }
-        }
-        FF_TICK(tC);
-        __syncthreads();                                               // G is overwritten by the next tile
-        FF_TICK(tW);
-    }
-    if (want_stats) flush((int64_t)blockIdx.x * segs_per_wg + (seg0 - t0) / FF_SEG);
-    }
-    if (w == LQ_WAVE && t0 < t1) tile_loglik((int)((t1 - 1 - t0) & 1));
-    if (dbg && lane == 0 && blockIdx.x == 7) {
-        dbg[w * 4 + 0] = tA; dbg[w * 4 + 1] = tB; dbg[w * 4 + 2] = tC; dbg[w * 4 + 3] = tW;
-    }
-    if (w == LQ_WAVE && lane == 0) block_q[blockIdx.x] = lq;
-#undef FF_TICK
+    constexpr bool WEIGHTED = false;
+    const double* const wsrc = nullptr;
+#define FULLCOV_BODY 3
+#include "fullcov_body.h"
+#undef FULLCOV_BODY
+}
+__global__ __launch_bounds__(FF_BLOCK, 4) void full_fused_f32_w_kernel(
+    const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ prep, int J16,
+    int* __restrict__ label_out, double* __restrict__ block_q, float* __restrict__ partials /*[segments][J16][NMOM]*/,
+    int segs_per_wg, int want_stats, const int* __restrict__ flags, const int* __restrict__ done,
+    const double* __restrict__ origin_parts, long long* __restrict__ dbg, const double* __restrict__ wsrc) {
+    constexpr bool WEIGHTED = true;
+#define FULLCOV_BODY 3
+#include "fullcov_body.h"
+#undef FULLCOV_BODY
 }
 
 // The segments' float partials -> float64 moments, in two fixed-order stages (one wave per component walking all ~4000
@@ -1024,9 +742,16 @@ static int fullcov_alloc(hgmm_ctx* c, int J, int* J16_out, int* grid_out) {
     return HGMM_OK;
 }
 
-static int fullcov_moments(hgmm_ctx* c, int J, int J16, int grid) {
+// `wsrc` (here and below): the resident source weights for the _weighted entries -- the WEIGHTED instantiation of the launch's
+// E-step kernel --, NULL for the unweighted ones, whose launches are what they were
+static int fullcov_moments(hgmm_ctx* c, int J, int J16, int grid, const double* wsrc) {
     {
         ProfScope prof(c, HGMM_K_FULL_MOMENTS);
+        if (wsrc)
+            full_moments_w_kernel<<<grid, FULL_BLOCK, 0, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,
+                                                                       c->t_prep.as<double>(), J16, c->t_parent.as<double>(),
+                                                                       c->t_partials.as<double>(), wsrc);
+        else
         full_moments_kernel<<<grid, FULL_BLOCK, 0, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad, c->t_prep.as<double>(),
                                                        J16, c->t_parent.as<double>(), c->t_partials.as<double>());
     }
@@ -1043,7 +768,7 @@ static bool fullcov_one_pass(const hgmm_ctx* c, int J16) {
 }
 // `ctl` (device): the launches look at ctl->done first and the sum of q applies the stop rule `stop` -- for a loop whose
 // iterations are enqueued ahead of the host's knowledge (hgmm_fullcov_fit); then nothing is copied to the host here.
-static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_host, bool want_stats = true,
+static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_host, const double* wsrc, bool want_stats = true,
                          const int* done = nullptr, TreeStop stop = NO_STOP) {
     const int64_t tiles = (c->n + FT_P - 1) / FT_P;
     const int grid = (int)std::min<int64_t>(tiles, c->cus);             // 100+ KB of LDS: one workgroup per CU
@@ -1059,12 +784,20 @@ static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_hos
         // [segments][J16][NMOM] floats, then stage 1's [FF_RB][J16][NMOM] doubles (8-byte aligned: an even number of floats)
         HGMM_TRY(ensure(c, c->t_partials, sizeof(float) * (size_t)nseg * J16 * NMOM + sizeof(double) * (size_t)FF_RB * J16 * NMOM + 8));
         // (grid32 <= 2 CUs: the workgroups' shares of q fit in front of q_dev, where hgmm_fullcov_fit's loop expects it)
-        const size_t lds32 = ff_lds_bytes(J16);
+        const size_t lds32 = ff_lds_bytes(J16, wsrc != nullptr);
         HGMM_TRY(ensure(c, c->ff_origin, sizeof(double) * 3 * FF_OPARTS));
         double* oparts = c->ff_origin.as<double>();
         full_origin_parts_kernel<<<FF_OPARTS, 256, 0, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad, oparts);
         {
             ProfScope prof(c, HGMM_K_FULL_FUSED);
+            if (wsrc) {
+                HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&full_fused_f32_w_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
+                full_fused_f32_w_kernel<<<grid32, FF_BLOCK, lds32, c->stream>>>(
+                    c->x_soa64.as<double>(), c->n, c->n_pad, c->t_prep.as<double>(), J16, labels, block_q, c->t_partials.as<float>(),
+                    segs_per_wg, want_stats ? 1 : 0, flags_ptr(c), done, oparts,
+                    c->ff_clocks_on ? c->ff_clocks.as<long long>() : nullptr, wsrc);
+            } else {
             HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&full_fused_f32_kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
             full_fused_f32_kernel<<<grid32, FF_BLOCK, lds32, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,
@@ -1072,6 +805,7 @@ static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_hos
                                                                          c->t_partials.as<float>(), segs_per_wg,
                                                                          want_stats ? 1 : 0, flags_ptr(c), done, oparts,
                                                                          c->ff_clocks_on ? c->ff_clocks.as<long long>() : nullptr);
+            }
         }
         HGMM_HIP(c, hipGetLastError());
         if (want_stats) {
@@ -1092,7 +826,7 @@ static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_hos
         }
         return HGMM_OK;
     }
-    const size_t lds = ft_lds_bytes(J16);
+    const size_t lds = ft_lds_bytes(J16, wsrc != nullptr);
     HGMM_TRY(ensure_exp_tab2(c));
     // (a 16-wave form of this kernel -- 1024 threads, one component per lane, 128 registers -- was built and measured in
     //  round 3: 1.83 vs 1.76 ms, phase A no shorter with four waves per SIMD than with two; removed again, commit b7f6218,
@@ -1103,7 +837,20 @@ static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_hos
     //  8 points against 4.5 k per 16; removed again, commit 875bec9, profiles/r04/fullcov_accounting_r04.md)
     {
         ProfScope prof(c, HGMM_K_FULL_FUSED);
-        if (J16 <= FT_BLOCK) {
+        long long* clocks = c->ff_clocks_on ? c->ff_clocks.as<long long>() : nullptr;
+        if (wsrc && J16 <= FT_BLOCK) {
+            HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&full_fused_w_kernel<1>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            full_fused_w_kernel<1><<<grid, FT_BLOCK, lds, c->stream>>>(
+                c->x_soa64.as<double>(), c->n, c->n_pad, c->t_prep.as<double>(), J16, labels, block_q, c->t_partials.as<double>(),
+                want_stats ? 1 : 0, flags_ptr(c), c->exp_tab2.as<double>(), nullptr, done, wsrc);
+        } else if (wsrc) {
+            HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&full_fused_w_kernel<2>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            full_fused_w_kernel<2><<<grid, FT_BLOCK, lds, c->stream>>>(
+                c->x_soa64.as<double>(), c->n, c->n_pad, c->t_prep.as<double>(), J16, labels, block_q, c->t_partials.as<double>(),
+                want_stats ? 1 : 0, flags_ptr(c), c->exp_tab2.as<double>(), clocks, done, wsrc);
+        } else if (J16 <= FT_BLOCK) {
             HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&full_fused_kernel<1>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             full_fused_kernel<1><<<grid, FT_BLOCK, lds, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,
@@ -1117,8 +864,7 @@ static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_hos
             full_fused_kernel<2><<<grid, FT_BLOCK, lds, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,
                                                                    c->t_prep.as<double>(), J16, labels, block_q,
                                                                    c->t_partials.as<double>(), want_stats ? 1 : 0,
-                                                                   flags_ptr(c), c->exp_tab2.as<double>(),
-                                                                   c->ff_clocks_on ? c->ff_clocks.as<long long>() : nullptr, done);
+                                                                   flags_ptr(c), c->exp_tab2.as<double>(), clocks, done);
         }
     }
     HGMM_HIP(c, hipGetLastError());
@@ -1139,11 +885,16 @@ static int fullcov_fused(hgmm_ctx* c, int J, int J16, int* labels, double* q_hos
     return HGMM_OK;
 }
 
-static int fullcov_pass(hgmm_ctx* c, int J, int* labels, double* q_host) {
+static int fullcov_pass(hgmm_ctx* c, int J, int* labels, double* q_host, const double* wsrc) {
     double* block_q = c->t_q.as<double>();
     double* q_dev = block_q + nblk(c->n, CH);
     {
         ProfScope prof(c, HGMM_K_FULL_PASS);
+        if (wsrc)
+            full_pass_w_kernel<<<nblk(c->n, CH), CH, 0, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,
+                                                                     c->t_prep.as<double>(), J, c->t_parent.as<double>(),
+                                                                     labels, block_q, wsrc);
+        else
         full_pass_kernel<<<nblk(c->n, CH), CH, 0, c->stream>>>(c->x_soa64.as<double>(), c->n, c->n_pad,
                                                              c->t_prep.as<double>(), J, c->t_parent.as<double>(),
                                                              labels, block_q);
@@ -1158,11 +909,24 @@ static int fullcov_pass(hgmm_ctx* c, int J, int* labels, double* q_host) {
     return HGMM_OK;
 }
 
-extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const double* init_mu, double sig2,
-                                int max_iters, double* pi_out, double* mu_out, double* cov_out,
-                                int32_t* labels_out, double* q_trace_out, int q_capacity, int* q_len_out) {
+// The _weighted entries' own refusals (include/hgmm.h), made before anything resident is touched
+static int fullcov_weights_ready(hgmm_ctx* c, const char* what) {
+    if (!c->src_weighted)
+        return fail(c, HGMM_ERR_STATE, "%s: no source weights are resident (set them with hgmm_tree_set_source_weights or "
+                    "hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE), or call the unweighted entry)", what);
+    if (c->comm_on())
+        return fail(c, HGMM_ERR_STATE, "%s: the context has a communicator; sharded weighted fits are not supported", what);
+    return HGMM_OK;
+}
+
+// hgmm_fullcov_fit (weighted = false) and hgmm_fullcov_fit_weighted: the weighted level's three statements -- the E-step
+// kernels' WEIGHTED instantiations (moments and log-likelihood) and pi = m0 / W with W = src_wsum
+static int fullcov_fit(hgmm_ctx* c, bool weighted, int J, double ls, double ld, const double* init_mu, double sig2,
+                       int max_iters, double* pi_out, double* mu_out, double* cov_out,
+                       int32_t* labels_out, double* q_trace_out, int q_capacity, int* q_len_out) {
     HGMM_ENTER(c);
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "full-covariance fit: set points first");
+    if (weighted) HGMM_TRY(fullcov_weights_ready(c, "hgmm_fullcov_fit_weighted"));
     if (J < 1 || J > 4096) return fail(c, HGMM_ERR_ARG, "J = %d outside 1..4096", J);
     if (!init_mu) return fail(c, HGMM_ERR_ARG, "init_mu is NULL");
     if (max_iters < 1) max_iters = 1;
@@ -1179,12 +943,14 @@ extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const 
     HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * J, hipMemcpyHostToDevice, c->stream));
     full_init_nodes_kernel<<<nblk(J16, 256), 256, 0, c->stream>>>(c->scratch.as<double>(), sig2, J, J16, d_pi, d_mu, d_cov);
     tree_prep_kernel<<<nblk(J16, 256), 256, 0, c->stream>>>(d_pi, d_mu, d_cov, 0, J16, d_prep, flags_ptr(c));
-    double n_total = (double)c->n;
+    // (src_w is never written by a tree build: the level-0 order of x_soa64, BuildWorkspace in tree_host.h)
+    const double* wsrc = weighted ? c->src_w.as<double>() : nullptr;
+    double n_total = weighted ? c->src_wsum : (double)c->n;          // pi = m0 / N; with weights their sum
     if (c->comm_on()) HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_total, 1, 0));
     // E-step quantities of the initial parameters
     const bool one_pass = fullcov_one_pass(c, J16);
-    if (one_pass) HGMM_TRY(fullcov_fused(c, J, J16, lab_a, nullptr));
-    else HGMM_TRY(fullcov_pass(c, J, lab_a, nullptr));
+    if (one_pass) HGMM_TRY(fullcov_fused(c, J, J16, lab_a, nullptr, wsrc));
+    else HGMM_TRY(fullcov_pass(c, J, lab_a, nullptr, wsrc));
     int* lab_cur = lab_a;      // arg-max of the most recent E-step
     int* lab_nxt = lab_b;
     double prev_q = 0.0;
@@ -1206,7 +972,7 @@ extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const 
         const auto enqueue_one = [&](int k) -> int {               // iteration k: labels into buffer (k + 1) & 1
             tree_mstep_kernel<<<nblk(J, 256), 256, 0, c->stream>>>(c->t_mom.as<double>(), 0, J, n_total, ld, d_pi, d_mu,
                                                                    d_cov, d_prep, flags_ptr(c), &ctl->done, 1);
-            return fullcov_fused(c, J, J16, ((k + 1) & 1) ? lab_b : lab_a, nullptr, k + 1 < max_iters, &ctl->done, stop);
+            return fullcov_fused(c, J, J16, ((k + 1) & 1) ? lab_b : lab_a, nullptr, wsrc, k + 1 < max_iters, &ctl->done, stop);
         };
         HGMM_TRY(run_batches(c, ctl, hand, max_iters, batch, enqueue_one, &it, "full-covariance fit"));
         q_len = it;
@@ -1216,14 +982,14 @@ extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const 
                                        hipMemcpyDeviceToHost, c->stream));
     } else
     while (true) {
-        if (!one_pass) HGMM_TRY(fullcov_moments(c, J, J16, grid));                    // E (moments)
+        if (!one_pass) HGMM_TRY(fullcov_moments(c, J, J16, grid, wsrc));              // E (moments)
         tree_mstep_kernel<<<nblk(J, 256), 256, 0, c->stream>>>(c->t_mom.as<double>(), 0, J, n_total, ld, d_pi, d_mu,
                                                                d_cov, d_prep, flags_ptr(c), nullptr, 1);    // M (+ prep)
         double q = 0.0;
         // q of the new parameters; one pass: the same launch already holds the next iteration's statistics
         // (the statistics of a call that is known to be the last one -- iteration budget reached -- are not formed)
-        if (one_pass) HGMM_TRY(fullcov_fused(c, J, J16, lab_nxt, &q, it + 1 < max_iters));
-        else HGMM_TRY(fullcov_pass(c, J, lab_nxt, &q));                               // q (+ next E-step's den)
+        if (one_pass) HGMM_TRY(fullcov_fused(c, J, J16, lab_nxt, &q, wsrc, it + 1 < max_iters));
+        else HGMM_TRY(fullcov_pass(c, J, lab_nxt, &q, wsrc));                         // q (+ next E-step's den)
         ++it;
         if (q_trace_out && q_len < q_capacity) q_trace_out[q_len] = q;
         ++q_len;
@@ -1241,6 +1007,20 @@ extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const 
     }
     if (q_len_out) *q_len_out = q_len < q_capacity ? q_len : q_capacity;
     return HGMM_OK;
+}
+
+extern "C" int hgmm_fullcov_fit(hgmm_ctx* c, int J, double ls, double ld, const double* init_mu, double sig2,
+                                int max_iters, double* pi_out, double* mu_out, double* cov_out,
+                                int32_t* labels_out, double* q_trace_out, int q_capacity, int* q_len_out) {
+    return fullcov_fit(c, false, J, ls, ld, init_mu, sig2, max_iters, pi_out, mu_out, cov_out, labels_out, q_trace_out,
+                       q_capacity, q_len_out);
+}
+
+extern "C" int hgmm_fullcov_fit_weighted(hgmm_ctx* c, int J, double ls, double ld, const double* init_mu, double sig2,
+                                         int max_iters, double* pi_out, double* mu_out, double* cov_out,
+                                         int32_t* labels_out, double* q_trace_out, int q_capacity, int* q_len_out) {
+    return fullcov_fit(c, true, J, ls, ld, init_mu, sig2, max_iters, pi_out, mu_out, cov_out, labels_out, q_trace_out,
+                       q_capacity, q_len_out);
 }
 
 extern "C" int hgmm_fullcov_phase_clocks(hgmm_ctx* c, int enable, int64_t* clocks_out) {
@@ -1261,12 +1041,12 @@ extern "C" int hgmm_fullcov_phase_clocks(hgmm_ctx* c, int enable, int64_t* clock
     return HGMM_OK;
 }
 
-extern "C" int hgmm_fullcov_estep(hgmm_ctx* c, int J, const double* pi, const double* mu, const double* cov,
-                                  double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out,
-                                  double* q_out) {
+static int fullcov_estep(hgmm_ctx* c, bool weighted, int J, const double* pi, const double* mu, const double* cov,
+                         double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out, double* q_out) {
     HGMM_ENTER(c);
     if (!c || !pi || !mu || !cov) return c ? fail(c, HGMM_ERR_ARG, "NULL parameter table") : HGMM_ERR_ARG;
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "full-covariance E-step: set points first");
+    if (weighted) HGMM_TRY(fullcov_weights_ready(c, "hgmm_fullcov_estep_weighted"));
     if (J < 1 || J > 4096) return fail(c, HGMM_ERR_ARG, "J = %d outside 1..4096", J);
     HGMM_HIP(c, hipSetDevice(c->device));
     int J16 = 0, grid = 0;
@@ -1281,11 +1061,12 @@ extern "C" int hgmm_fullcov_estep(hgmm_ctx* c, int J, const double* pi, const do
                                                            c->t_cov.as<double>(), 0, J16, c->t_prep.as<double>(), flags_ptr(c));
     int* lab = c->t_current.as<int>();
     double q = 0.0;
+    const double* wsrc = weighted ? c->src_w.as<double>() : nullptr;
     if (fullcov_one_pass(c, J16)) {
-        HGMM_TRY(fullcov_fused(c, J, J16, lab, &q));
+        HGMM_TRY(fullcov_fused(c, J, J16, lab, &q, wsrc));
     } else {
-        HGMM_TRY(fullcov_pass(c, J, lab, &q));
-        HGMM_TRY(fullcov_moments(c, J, J16, grid));
+        HGMM_TRY(fullcov_pass(c, J, lab, &q, wsrc));
+        HGMM_TRY(fullcov_moments(c, J, J16, grid, wsrc));
     }
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * 13 * J16));
     double* e0 = c->scratch.as<double>();
@@ -1303,4 +1084,16 @@ extern "C" int hgmm_fullcov_estep(hgmm_ctx* c, int J, const double* pi, const do
     }
     if (q_out) *q_out = q;
     return HGMM_OK;
+}
+
+extern "C" int hgmm_fullcov_estep(hgmm_ctx* c, int J, const double* pi, const double* mu, const double* cov,
+                                  double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out,
+                                  double* q_out) {
+    return fullcov_estep(c, false, J, pi, mu, cov, m0_out, m1_out, m2_out, labels_out, q_out);
+}
+
+extern "C" int hgmm_fullcov_estep_weighted(hgmm_ctx* c, int J, const double* pi, const double* mu, const double* cov,
+                                           double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out,
+                                           double* q_out) {
+    return fullcov_estep(c, true, J, pi, mu, cov, m0_out, m1_out, m2_out, labels_out, q_out);
 }

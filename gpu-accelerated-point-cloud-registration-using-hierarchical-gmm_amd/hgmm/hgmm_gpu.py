@@ -82,7 +82,11 @@ ones; an explicit ``weights=`` / ``target_weights=`` argument, where there is on
 As a SOURCE (``buildGMMTree``, ``GMMTree(source)``, ``set_source``, ``registration_gmmtree`` and the sources of
 ``registration_gmmtree_batch``) it brings its weights to the tree build: point i counts as ``weights[i]`` points
 (``Context.tree_set_source_weights``).  Earlier versions accepted a WeightedPoints source and silently dropped its weights;
-pass ``source.points`` to build the unweighted tree.  An explicit ``weights=`` / ``source_weights=`` takes precedence."""
+pass ``source.points`` to build the unweighted tree.  An explicit ``weights=`` / ``source_weights=`` takes precedence.
+
+:func:`fitFullCovGMM` takes it the same way: the flat full-covariance fit under its weights
+(``Context.fullcov_fit(..., weighted=True)``).  Earlier versions unwrapped a WeightedPoints there and silently dropped its
+weights; pass ``.points`` for the unweighted fit."""
 
 
 def _weights_arg(weights, n):
@@ -226,7 +230,7 @@ def logLikelihoodValue(mixingCoeff, mean, covar, data, j0, j1, ctx: Context | No
 
 
 def fitFullCovGMM(points, n_components, ls=80.0, ld=1.0e-4, sig2=0.00034, init_idx=None, seed=None,
-                  max_iters=1000, ctx: Context | None = None, return_trace=False, dtype=None):
+                  max_iters=1000, ctx: Context | None = None, return_trace=False, dtype=None, weights=None):
     """Flat full-covariance GMM = ONE tree level with branching ``n_components`` (the reference's
     CPU twin run with its module global ``n_node = J`` and ``buildGMMTree(P, 1, ls, ld)``,
     hgmm_cupy_cpu_working.py:30,122-160).  -> (mixingCoeff[J], mean[J,3], covar[J,3,3]).
@@ -237,18 +241,32 @@ def fitFullCovGMM(points, n_components, ls=80.0, ld=1.0e-4, sig2=0.00034, init_i
     ``dtype=np.float32`` (explicit only; the points' own type does NOT switch it): the float32-tile kernel for this fit
     (``Context.tree_set_precision``; J <= 1024) -- float32 pdfs, tile and matrix-core statistics about the centroid, float64
     row sums / log / M-step; ~25 % faster per iteration at 10^6 x 800, Sigma to ~1e-5 of a variance.  The context's own
-    setting is restored afterwards."""
+    setting is restored afterwards.
+
+    ``weights`` [N] >= 0 (no counterpart in the reference; default None: the points' own if they are a
+    :class:`WeightedPoints`, else none): point i counts as ``weights[i]`` points, as in :func:`buildGMMTree` -- the moments,
+    ``pi = m0 / sum(weights)`` and the log-likelihood behind the stop rule ``ls`` are weighted; the labels and the 1e-15 floor
+    are not (``Context.fullcov_fit(..., weighted=True)``).  A :class:`VoxelCloud` is handed over on the device and fitted
+    under its counts; it takes no explicit weights.  A plain array fits as it always did.  Earlier versions accepted a
+    WeightedPoints here and silently dropped its weights: pass its ``.points`` for the unweighted fit."""
     ctx = ctx or default_context()
-    P = np.ascontiguousarray(_points(points), dtype=np.float64)
+    raw = _points(points)
+    weights = _target_weights(points, weights)       # (refused before anything is uploaded)
+    # (a VoxelCloud stays on the device: its initial means are read back by row number)
+    P = raw if _is_voxels(raw) else np.ascontiguousarray(raw, dtype=np.float64)
     J = int(n_components)
     if init_idx is None:
         init_idx = np.random.RandomState(J if seed is None else seed).randint(J, size=J)
-    ctx.set_points(P)
+    _set_source(ctx, P, weights)
+    weighted = _is_voxels(raw) or weights is not None
+    init_mu = ctx.points_rows(np.asarray(init_idx)) if _is_voxels(raw) else P[np.asarray(init_idx)]
     prev = getattr(ctx, "tree_dtype", np.dtype(np.float64))
     if dtype is not None:
         ctx.tree_set_precision(dtype)
     try:
-        pi, mu, cov, labels, q = ctx.fullcov_fit(J, ls, ld, P[np.asarray(init_idx)], sig2, max_iters)
+        # (the unweighted call is the one every earlier version made: no weight call, no keyword)
+        pi, mu, cov, labels, q = (ctx.fullcov_fit(J, ls, ld, init_mu, sig2, max_iters, weighted=True) if weighted
+                                  else ctx.fullcov_fit(J, ls, ld, init_mu, sig2, max_iters))
     finally:
         if dtype is not None:
             ctx.tree_set_precision(prev)

@@ -298,7 +298,9 @@ int hgmm_flat_stats(hgmm_ctx* ctx, int cov_type, int variant, int J,
  *   log-likelihood  behind the stop rule (gmm_impl.py:113,136)  mean_i lpn_i becomes sum_i s_i lpn_i / S;
  *   hgmm_flat_stats the statistics and sum_lpn are the s-weighted sums, n_points_out = S.
  * Unchanged: log_resp, the per-point lpn, arg-max, predict, estimate_log_prob, the initialisers (the KMeans seeding of
- * flavour G does NOT see the weights) and the full-covariance, KMeans and tree entries.
+ * flavour G does NOT see the weights) and the full-covariance, KMeans and tree entries (the full-covariance fit's weights are
+ * the SOURCE weights of the tree build: the unweighted entries ignore them; hgmm_fullcov_fit_weighted /
+ * hgmm_fullcov_estep_weighted honour them, and never these).
  * Integer weights are repetition (up to the order of summation).  A ZERO WEIGHT MAKES THE ROW ABSENT WHATEVER ITS
  * COORDINATES: the weighted kernels skip such a row instead of multiplying by zero, so a row of NaNs with s = 0 leaves every
  * result finite (a mask).  s == 1 everywhere gives the unweighted results bit for bit; s == 2 everywhere gives exactly twice
@@ -543,7 +545,8 @@ int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, c
  * hgmm_tree_score_multi: summary[0] = sum of w, summary[1..6] = the w-weighted sums of what they are without weights, added in
  * the same fixed order; the per-point arrays node / maha2 / logp are not weighted.  NOT honoured by the build (hgmm_tree_build*:
  * the weights of a SOURCE cloud are hgmm_tree_set_source_weights', below) nor by any flat, full-covariance or KMeans entry:
- * they ignore them (the flat fit has weights of its own: hgmm_flat_set_weights).                                             */
+ * they ignore them (the flat fit has weights of its own: hgmm_flat_set_weights; the full-covariance fit takes the SOURCE
+ * weights: the unweighted entries ignore them; hgmm_fullcov_fit_weighted / hgmm_fullcov_estep_weighted honour them).         */
 int hgmm_tree_set_target_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
 int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
                                        const double* const* w /* w == NULL: none; w[b] == NULL: pair b unweighted */,
@@ -573,9 +576,11 @@ int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
  * counts; a NaN, infinite or negative weight (hgmm_last_error names its index) and a cloud whose weights are all zero are
  * refused on the host before anything is touched: HGMM_ERR_ARG, and the previous weights stay in force.
  * Honoured by hgmm_tree_build (serial entry) and hgmm_tree_build_batch (batch entry), in both precisions of
- * hgmm_tree_set_precision, and by nothing else.  IGNORED by the stand-alone steps below (hgmm_tree_estep, hgmm_tree_mstep,
- * hgmm_tree_loglik and the generic E-step kernel behind them), by every flat, full-covariance and KMeans entry (the flat fit
- * has weights of its own: hgmm_flat_set_weights), and by the registration and score entries (their weights are the TARGET's,
+ * hgmm_tree_set_precision, by the flat full-covariance entries that ask for them (serial weights: hgmm_fullcov_fit_weighted,
+ * hgmm_fullcov_estep_weighted, below), and by nothing else.  IGNORED by the stand-alone steps below (hgmm_tree_estep,
+ * hgmm_tree_mstep, hgmm_tree_loglik and the generic E-step kernel behind them), by every flat and KMeans entry (the flat fit
+ * has weights of its own: hgmm_flat_set_weights), by hgmm_fullcov_fit / hgmm_fullcov_estep (full-covariance: the unweighted
+ * entries ignore them; `_weighted` honours them), and by the registration and score entries (their weights are the TARGET's,
  * above).  Under a communicator hgmm_tree_build with
  * weights resident returns HGMM_ERR_STATE: sharded weighted builds are not supported.                                        */
 int hgmm_tree_set_source_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
@@ -622,6 +627,32 @@ int hgmm_fullcov_fit(hgmm_ctx* ctx, int J, double ls, double ld, const double* i
 int hgmm_fullcov_estep(hgmm_ctx* ctx, int J, const double* pi, const double* mu, const double* cov,
                        double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out,
                        double* q_out);
+/* The same fit and E-step under the SOURCE weights resident on the context (hgmm_tree_set_source_weights, or
+ * hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE): the counts, with no host trip).  Same argument lists.  The call says what it
+ * wants: there is no weight storage, setter, drop rule or switch of its own, and hgmm_fullcov_fit / hgmm_fullcov_estep keep
+ * ignoring the weights -- their results are bit for bit what they are, with weights resident or not.
+ * The fit is ONE weighted tree level with branching J, i.e. the three statements of hgmm_tree_set_source_weights, with
+ * W = the weights' float64 host sum in index order (a voxel member: its raw count):
+ *   moments         m = sum_i w_i gamma_ij (1, x_i, x_i x_i^T); the 1e-15 floor is tested on gamma, not on w gamma, and the
+ *                   arg-max label does not see the weight;
+ *   M-step          pi_j = m0_j / W; the m0 < ld rule, mu and cov are unchanged and see the weighted moments;
+ *   log-likelihood  q = sum_i w_i log max(sum_{pi_j >= eps} pi_j N(x_i; j), eps); the stop rule |q - q_prev| < ls is unchanged.
+ * A zero weight makes a point add nothing; it is still labelled.  Non-finite coordinates are not covered, as in the tree
+ * build.  w == 1 everywhere gives the unweighted entry's outputs bit for bit, in both precisions; w == 2 everywhere with ls
+ * and ld doubled gives the unweighted tables, labels and iteration count bit for bit and exactly twice the q trace; integer
+ * weights are repetition, up to the order of summation.
+ * All three kernel paths take the weights (one-pass float64, the float32 tile of hgmm_tree_set_precision, two-pass): the
+ * weight multiplies the point's feature row -- the B operand of the matrix product -- and its log term.  In the float32 tile
+ * it is converted to float32 once; the statistics' origin stays the unweighted centroid (a reference point only).
+ * Refused before anything resident is touched: HGMM_ERR_STATE without a float64 view, without resident source weights (set
+ * them, or call the unweighted entry; a forest cloud's weights are not these) and under a communicator (sharded weighted
+ * fits are not supported, as for the weighted tree build); every HGMM_ERR_ARG of the unweighted entries.                    */
+int hgmm_fullcov_fit_weighted(hgmm_ctx* ctx, int J, double ls, double ld, const double* init_mu, double sig2,
+                              int max_iters, double* pi_out, double* mu_out, double* cov_out,
+                              int32_t* labels_out, double* q_trace_out, int q_capacity, int* q_len_out);
+int hgmm_fullcov_estep_weighted(hgmm_ctx* ctx, int J, const double* pi, const double* mu, const double* cov,
+                                double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out,
+                                double* q_out);
 
 /* ---- KMeans initialiser (float64, on the resident cloud) -------------------------------
  * Replaces the scikit-learn call the GMMReg flavour seeds its EM with
