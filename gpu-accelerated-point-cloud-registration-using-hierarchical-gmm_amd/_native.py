@@ -142,6 +142,10 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_kmeans_labels", [ctx, _vp, _vp])
         _sig(lib, "hgmm_kmeans_lloyd", [ctx, C.c_int, _vp, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, C.POINTER(C.c_int64)])
+        _sig(lib, "hgmm_kmeans_plusplus_weighted", [ctx, C.c_int, C.c_int64, _vp, C.c_int, _vp, _vp])
+        _sig(lib, "hgmm_kmeans_step_weighted", [ctx, C.c_int, _vp, C.c_int, _vp, _f64p, C.POINTER(C.c_int64)])
+        _sig(lib, "hgmm_kmeans_lloyd_weighted", [ctx, C.c_int, _vp, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, C.POINTER(C.c_int64)])
         _sig(lib, "hgmm_gauss_transform", [ctx, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp])
         _sig(lib, "hgmm_comm_unique_id", [_vp])
         _sig(lib, "hgmm_comm_init_rank", [ctx, C.c_int, C.c_int, _vp])
@@ -1208,7 +1212,8 @@ class Context:
         i counts as ``w[i]`` points -- the moments are ``sum w gamma (1, x, x x^T)``, ``pi = m0 / sum(w)`` and a level's
         log-likelihood is ``sum w log(...)``; the partition (arg-max) and the 1e-15 floor do not see them.  ``None``: no
         weights.  They belong to the cloud :meth:`set_points` uploaded (or the bound handle): whatever changes the resident
-        cloud drops them.  Nothing but the build reads them.  The library refuses a wrong length, a NaN, infinite or negative
+        cloud drops them.  The build reads them, and the entries that ask for them by name (``fullcov_fit(..., weighted=True)``,
+        ``kmeans_plusplus / kmeans_step / kmeans_lloyd(..., weighted=True)``); nothing else does.  The library refuses a wrong length, a NaN, infinite or negative
         weight and all-zero weights (HgmmError, naming the index) and keeps the previous weights."""
         if w is None:
             self._check(self.lib.hgmm_tree_set_source_weights(self.h, None, 0))
@@ -1539,41 +1544,46 @@ class Context:
         return m0, m1, m2, labels, q.value
 
     # -- KMeans initialiser (float64 points) -------------------------------------------------
-    def kmeans_plusplus(self, k, first_id, rand_vals):
+    def kmeans_plusplus(self, k, first_id, rand_vals, weighted=False):
         """Greedy k-means++ seeding on the resident cloud.  rand_vals[(k-1), n_trials] are the
-        host-drawn uniforms of steps 1..k-1 in draw order.  Returns (ids[k] int64, centres[k,3])."""
+        host-drawn uniforms of steps 1..k-1 in draw order.  Returns (ids[k] int64, centres[k,3]).
+        ``weighted``: under the resident source weights (``tree_set_source_weights``): hgmm_kmeans_plusplus_weighted."""
         k = int(k)
         if k > 1:
             rand_vals = np.ascontiguousarray(rand_vals, dtype=np.float64).reshape(k - 1, -1)
         n_trials = rand_vals.shape[1] if k > 1 else 1
         ids = np.empty(k, np.int64)
         centres = np.empty((k, 3))
-        self._check(self.lib.hgmm_kmeans_plusplus(self.h, k, int(first_id), _ptr(rand_vals) if k > 1 else None,
-                                                  int(n_trials), _ptr(ids), _ptr(centres)))
+        entry = self.lib.hgmm_kmeans_plusplus_weighted if weighted else self.lib.hgmm_kmeans_plusplus
+        self._check(entry(self.h, k, int(first_id), _ptr(rand_vals) if k > 1 else None, int(n_trials), _ptr(ids),
+                          _ptr(centres)))
         return ids, centres
 
-    def kmeans_step(self, centres, reset_labels=False):
-        """One Lloyd assignment: returns (sums[k,3], counts[k], inertia, n_changed)."""
+    def kmeans_step(self, centres, reset_labels=False, weighted=False):
+        """One Lloyd assignment: returns (sums[k,3], counts[k], inertia, n_changed).  ``weighted``: the sums are
+        sum w x, ``counts`` the weight per cluster and the inertia sum w d2 (hgmm_kmeans_step_weighted)."""
         centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
         k = len(centres)
         sums = np.empty((k, 4))
         inertia = C.c_double()
         changed = C.c_int64()
-        self._check(self.lib.hgmm_kmeans_step(self.h, k, _ptr(centres), int(bool(reset_labels)), _ptr(sums),
-                                              C.byref(inertia), C.byref(changed)))
+        entry = self.lib.hgmm_kmeans_step_weighted if weighted else self.lib.hgmm_kmeans_step
+        self._check(entry(self.h, k, _ptr(centres), int(bool(reset_labels)), _ptr(sums), C.byref(inertia),
+                          C.byref(changed)))
         return sums[:, :3].copy(), sums[:, 3].copy(), inertia.value, changed.value
 
-    def kmeans_lloyd(self, centres, max_iter, tol_abs, reset_labels=True):
+    def kmeans_lloyd(self, centres, max_iter, tol_abs, reset_labels=True, weighted=False):
         """Device-resident Lloyd loop.  Returns (centres, n_iter, strict, pending) where ``pending`` is None
-        or, when an iteration met an empty cluster, that iteration's (sums[k,3], counts[k], n_changed)."""
+        or, when an iteration met an empty cluster, that iteration's (sums[k,3], counts[k], n_changed).
+        ``weighted``: hgmm_kmeans_lloyd_weighted; a cluster is empty when its weight is 0."""
         centres = np.array(centres, dtype=np.float64).reshape(-1, 3)
         k = len(centres)
         n_iter, strict, needs = C.c_int(), C.c_int(), C.c_int()
         sums = np.empty((k, 4))
         changed = C.c_int64()
-        self._check(self.lib.hgmm_kmeans_lloyd(self.h, k, _ptr(centres), int(max_iter), float(tol_abs),
-                                               int(bool(reset_labels)), C.byref(n_iter), C.byref(strict),
-                                               C.byref(needs), _ptr(sums), C.byref(changed)))
+        entry = self.lib.hgmm_kmeans_lloyd_weighted if weighted else self.lib.hgmm_kmeans_lloyd
+        self._check(entry(self.h, k, _ptr(centres), int(max_iter), float(tol_abs), int(bool(reset_labels)),
+                          C.byref(n_iter), C.byref(strict), C.byref(needs), _ptr(sums), C.byref(changed)))
         pending = (sums[:, :3].copy(), sums[:, 3].copy(), changed.value) if needs.value else None
         return centres, n_iter.value, bool(strict.value), pending
 

@@ -82,26 +82,37 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh /* [4] */) 
 // ------------------------------------------------------------------------------------------
 // k-means++ seeding
 // ------------------------------------------------------------------------------------------
+// WEIGHTED (the `_w` kernels behind hgmm_kmeans_*_weighted; the kernels' bodies are in kmeans_body.h, included once per
+// kernel, plain and _w; the tail below takes the flag as a template argument): point i counts as wts[i] >= 0 points --
+// wts [n_pad] is the context's source-weight array, on the row index of xs.  Whatever is SUMMED
+// over points carries the weight (block / group sums, the running sum inside the block a threshold lands in, part and
+// part16, the inertia partials, the per-cluster sums and their fourth column); closest[], the labels and the per-point
+// distance do not.  A weighted body keeps the traversal and the summation order of its unweighted twin: with w = 1
+// every product is its operand and the results are the unweighted bits, with w = 2 every sum is exactly doubled.  The
+// unweighted kernels never read `wts` and compile to the code they were (tools/isa_diff.py).
 __global__ __launch_bounds__(KM_BLOCK) void kmpp_first_kernel(const double* __restrict__ xs, int64_t n,
                                                               int64_t n_pad, int64_t first,
                                                               double* __restrict__ closest,
                                                               double* __restrict__ bsum,
                                                               double* __restrict__ centres,
                                                               int64_t* __restrict__ ids) {
-    __shared__ double sh[4];
-    const int64_t i = (int64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
-    const double cx = xs[first], cy = xs[n_pad + first], cz = xs[2 * n_pad + first];
-    double d = 0.0;
-    if (i < n) d = dist2(xs[i], xs[n_pad + i], xs[2 * n_pad + i], cx, cy, cz);
-    closest[i] = d;
-    const double t = block_sum_256(d, sh);
-    if (threadIdx.x == 0) {
-        bsum[blockIdx.x] = t;
-        if (blockIdx.x == 0) {
-            centres[0] = cx; centres[1] = cy; centres[2] = cz;
-            ids[0] = first;
-        }
-    }
+    constexpr bool WEIGHTED = false;
+    const double* wts = nullptr;
+#define KMEANS_BODY 1
+#include "kmeans_body.h"
+#undef KMEANS_BODY
+}
+__global__ __launch_bounds__(KM_BLOCK) void kmpp_first_w_kernel(const double* __restrict__ xs, int64_t n,
+                                                                int64_t n_pad, int64_t first,
+                                                                const double* __restrict__ wts,
+                                                                double* __restrict__ closest,
+                                                                double* __restrict__ bsum,
+                                                                double* __restrict__ centres,
+                                                                int64_t* __restrict__ ids) {
+    constexpr bool WEIGHTED = true;
+#define KMEANS_BODY 1
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 // ------------------------------------------------------------------------------------------
@@ -152,56 +163,24 @@ __global__ __launch_bounds__(KM_STEP_BLOCK) void kmpp_step_kernel(const double* 
                                                                   const double* __restrict__ cand_xyz, int T,
                                                                   double* __restrict__ part, int B,
                                                                   double* __restrict__ part16) {
-    __shared__ double shg[KM_MAX_TRIALS][KM_GROUP];
-    const int lane = lane_id();
-    const int64_t blk = (int64_t)blockIdx.x * KM_GROUP + wave_in_block();     // 256-point block of this wave
-    const bool have = blk < B;
-    const int64_t i0 = (have ? blk : 0) * KM_BLOCK + 4 * lane;                 // n_pad is a multiple of 256
-    // every candidate's coordinates through ONE batch of scalar loads (index clamped, not branched on, so that the
-    // loads can leave the per-candidate blocks): the tail's CU wrote them a moment ago and each cache line of them
-    // is a trip through the fabric -- a load per loop iteration would chain those trips
-    // (issued before the points' loads so that the two kinds of trip overlap)
-    double cc[TMAX][3];
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-        const int tt = t < T ? t : T - 1;
-        cc[t][0] = cand_xyz[3 * tt]; cc[t][1] = cand_xyz[3 * tt + 1]; cc[t][2] = cand_xyz[3 * tt + 2];
-    }
-    double x[4], y[4], z[4], cl[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { x[q] = xs[i0 + q]; y[q] = xs[n_pad + i0 + q]; z[q] = xs[2 * n_pad + i0 + q]; cl[q] = closest[i0 + q]; }
-    if (fold >= 0 && have) {
-        const double fx = centres[3 * fold], fy = centres[3 * fold + 1], fz = centres[3 * fold + 2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double d = dist2(x[q], y[q], z[q], fx, fy, fz);
-            if (i0 + q < n && d < cl[q]) { cl[q] = d; closest[i0 + q] = d; }   // few points move once j is large
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) if (!have || !(i0 + q < n)) cl[q] = 0.0;      // padding contributes min(0, d) = 0
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-        if (t < T) {
-            const double cx = cc[t][0], cy = cc[t][1], cz = cc[t][2];
-            double sacc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sacc += fmin(cl[q], dist2(x[q], y[q], z[q], cx, cy, cz));
-            const double w = wave_sum_f64(sacc);
-            if (lane == 0) {
-                if (have) part[(size_t)t * B + blk] = w;
-                shg[t][wave_in_block()] = have ? w : 0.0;
-            }
-        }
-    }
-    __syncthreads();
-    // the workgroup's 16 block sums, added in block order: what the tail's winner selection and group search read
-    if ((int)threadIdx.x < T) {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < KM_GROUP; ++q) s += shg[threadIdx.x][q];
-        part16[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-    }
+    constexpr bool WEIGHTED = false;
+    const double* wts = nullptr;
+#define KMEANS_BODY 2
+#include "kmeans_body.h"
+#undef KMEANS_BODY
+}
+template <int TMAX>
+__global__ __launch_bounds__(KM_STEP_BLOCK) void kmpp_step_w_kernel(const double* __restrict__ xs, int64_t n, int64_t n_pad,
+                                                                    const double* __restrict__ wts,
+                                                                    double* __restrict__ closest,
+                                                                    const double* __restrict__ centres, int fold,
+                                                                    const double* __restrict__ cand_xyz, int T,
+                                                                    double* __restrict__ part, int B,
+                                                                    double* __restrict__ part16) {
+    constexpr bool WEIGHTED = true;
+#define KMEANS_BODY 2
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 // One workgroup of 1024 threads.  `select`: pick the winner among the T candidates of centre j from `part16`.
@@ -228,8 +207,13 @@ struct KmTailShared {                                    // the tail's LDS (decl
 // the next potentials.  `writer`: this workgroup stores the results to memory (always, in the one-workgroup kernel);
 // `sh_cand` (LDS [T][3], may be null) receives the drawn candidates' coordinates for the code that follows in the
 // same workgroup; (pcx, pcy, pcz) = the accepted centre's coordinates in every thread (select).
-template <int TMAX>
+// (W: `wts` as in the pass; the group and block sums the tail searches are weighted sums already, so the weight enters
+//  in ONE place, the running sum inside the block a threshold lands in -- its four loads per lane ride in the round of
+//  loads that fetches the block, one multiply per visited point, no further trip.  pre_pts then holds 20 values: the
+//  caller's weights behind its 16 point values.)
+template <int TMAX, bool W = false>
 __device__ __forceinline__ void kmpp_tail_body(const double* __restrict__ xs, int64_t n, int64_t n_pad,
+                                               const double* __restrict__ wts,
                                                const double* closest,
                                                const double* __restrict__ part,
                                                const double* __restrict__ part16, int G,
@@ -290,6 +274,10 @@ __device__ __forceinline__ void kmpp_tail_body(const double* __restrict__ xs, in
             for (int q = 0; q < 4; ++q) {
                 pre_pts[q] = xs[pre_i0 + q]; pre_pts[4 + q] = xs[n_pad + pre_i0 + q];
                 pre_pts[8 + q] = xs[2 * n_pad + pre_i0 + q]; pre_pts[12 + q] = closest[pre_i0 + q];
+            }
+            if constexpr (W) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pre_pts[16 + q] = wts[pre_i0 + q];
             }
         }
         // (a wave none of whose threads owns a group -- 12 of the 16 at N = 1M -- has nothing to add up: eight fp64
@@ -408,11 +396,17 @@ __device__ __forceinline__ void kmpp_tail_body(const double* __restrict__ xs, in
             for (int q = 0; q < 4; ++q) {
                 cv[q] = closest[e0 + q]; xv[q] = xs[e0 + q]; yv[q] = xs[n_pad + e0 + q]; zv[q] = xs[2 * n_pad + e0 + q];
             }
+            double wv[4] = {1.0, 1.0, 1.0, 1.0};
+            if constexpr (W) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wv[q] = wts[e0 + q];
+            }
             double s = 0.0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 double val = cv[q];
                 if (pend >= 0) val = fmin(val, dist2(xv[q], yv[q], zv[q], pcx, pcy, pcz));
+                if constexpr (W) val = wv[q] * val;
                 if (!(e0 + q < n)) val = 0.0;
                 s += val;
                 c[q] = s;
@@ -463,8 +457,27 @@ __global__ __launch_bounds__(1024) void kmpp_tail_kernel(const double* __restric
                                                          int64_t* __restrict__ ids, double* __restrict__ gprefix) {
     __shared__ KmTailShared ts;
     double pcx, pcy, pcz;
-    kmpp_tail_body<TMAX>(xs, n, n_pad, closest, part, part16, G, bsum0, g0, B, T, j, select, draw, rand_c, cand_in,
+    kmpp_tail_body<TMAX>(xs, n, n_pad, nullptr, closest, part, part16, G, bsum0, g0, B, T, j, select, draw, rand_c, cand_in,
                          cand_xyz_in, cand_out, cand_xyz_out, centres, ids, gprefix, true, nullptr, pcx, pcy, pcz, ts);
+}
+template <int TMAX>
+__global__ __launch_bounds__(1024) void kmpp_tail_w_kernel(const double* __restrict__ xs, int64_t n, int64_t n_pad,
+                                                           const double* __restrict__ wts,
+                                                           const double* __restrict__ closest,
+                                                           const double* __restrict__ part,
+                                                           const double* __restrict__ part16, int G,
+                                                           const double* __restrict__ bsum0,
+                                                           const double* __restrict__ g0, int B, int T, int j,
+                                                           int select, int draw, const double* __restrict__ rand_c,
+                                                           const int64_t* cand_in, const double* cand_xyz_in,
+                                                           int64_t* cand_out, double* cand_xyz_out,
+                                                           double* __restrict__ centres,
+                                                           int64_t* __restrict__ ids, double* __restrict__ gprefix) {
+    __shared__ KmTailShared ts;
+    double pcx, pcy, pcz;
+    kmpp_tail_body<TMAX, true>(xs, n, n_pad, wts, closest, part, part16, G, bsum0, g0, B, T, j, select, draw, rand_c,
+                               cand_in, cand_xyz_in, cand_out, cand_xyz_out, centres, ids, gprefix, true, nullptr, pcx, pcy,
+                               pcz, ts);
 }
 
 // ONE launch per centre: every workgroup of the pass over the points first runs the tail of the PREVIOUS centre for
@@ -490,58 +503,30 @@ __global__ __launch_bounds__(KM_STEP_BLOCK) void kmpp_fused_kernel(const double*
                                                                    double* __restrict__ centres,
                                                                    int64_t* __restrict__ ids,
                                                                    unsigned long long* dbg) {
-    const unsigned long long t_start = dbg ? (unsigned long long)wall_clock64() : 0ull;
-    static_assert(KM_STEP_BLOCK == 1024, "the tail body is written for 1024 threads");
-    __shared__ double shg[KM_MAX_TRIALS][KM_GROUP];
-    __shared__ double sh_cand[3 * KM_MAX_TRIALS];
-    __shared__ KmTailShared ts;
-    const int lane = lane_id();
-    const int64_t blk = (int64_t)blockIdx.x * KM_GROUP + wave_in_block();     // 256-point block of this wave
-    const bool have = blk < B;
-    const int64_t i0 = (have ? blk : 0) * KM_BLOCK + 4 * lane;                 // n_pad is a multiple of 256
-    // the pass's operands do not depend on the tail: requested inside its first round of loads (see there)
-    double pts[16];
-    double fx, fy, fz;
-    kmpp_tail_body<TMAX>(xs, n, n_pad, closest, part_prev, part16_prev, G, nullptr, nullptr, B, T, j - 1, 1, 1, rand_c,
-                         cand_prev, cand_xyz_prev, cand_next, cand_xyz_next, centres, ids, nullptr, blockIdx.x == 0,
-                         sh_cand, fx, fy, fz, ts, dbg, t_start, pts, i0);
-    __syncthreads();                                         // sh_cand
-    km_stamp(dbg, 7, t_start);
-    double x[4], y[4], z[4], cl[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { x[q] = pts[q]; y[q] = pts[4 + q]; z[q] = pts[8 + q]; cl[q] = pts[12 + q]; }
-    if (have) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double d = dist2(x[q], y[q], z[q], fx, fy, fz);
-            if (i0 + q < n && d < cl[q]) { cl[q] = d; closest[i0 + q] = d; }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) if (!have || !(i0 + q < n)) cl[q] = 0.0;      // padding contributes min(0, d) = 0
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-        if (t < T) {
-            const double cx = sh_cand[3 * t], cy = sh_cand[3 * t + 1], cz = sh_cand[3 * t + 2];
-            double sacc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sacc += fmin(cl[q], dist2(x[q], y[q], z[q], cx, cy, cz));
-            const double w = wave_sum_f64(sacc);
-            if (lane == 0) {
-                if (have) part_next[(size_t)t * B + blk] = w;
-                shg[t][wave_in_block()] = have ? w : 0.0;
-            }
-        }
-    }
-    km_stamp(dbg, 9, t_start);
-    __syncthreads();
-    if ((int)threadIdx.x < T) {
-        double s2 = 0.0;
-#pragma unroll
-        for (int q = 0; q < KM_GROUP; ++q) s2 += shg[threadIdx.x][q];
-        part16_next[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s2;
-    }
-    km_stamp(dbg, 8, t_start);
+    constexpr bool WEIGHTED = false;
+    const double* wts = nullptr;
+#define KMEANS_BODY 3
+#include "kmeans_body.h"
+#undef KMEANS_BODY
+}
+template <int TMAX>
+__global__ __launch_bounds__(KM_STEP_BLOCK) void kmpp_fused_w_kernel(const double* __restrict__ xs, int64_t n, int64_t n_pad,
+                                                                   const double* __restrict__ wts,
+                                                                   double* closest,
+                                                                   const double* __restrict__ part_prev,
+                                                                   const double* __restrict__ part16_prev,
+                                                                   double* __restrict__ part_next,
+                                                                   double* __restrict__ part16_next, int G, int B, int T,
+                                                                   int j, const double* __restrict__ rand_c,
+                                                                   const int64_t* cand_prev, const double* cand_xyz_prev,
+                                                                   int64_t* cand_next, double* cand_xyz_next,
+                                                                   double* __restrict__ centres,
+                                                                   int64_t* __restrict__ ids,
+                                                                   unsigned long long* dbg) {
+    constexpr bool WEIGHTED = true;
+#define KMEANS_BODY 3
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 // ------------------------------------------------------------------------------------------
@@ -549,86 +534,33 @@ __global__ __launch_bounds__(KM_STEP_BLOCK) void kmpp_fused_kernel(const double*
 // ------------------------------------------------------------------------------------------
 // Two points per thread (512 per workgroup); the centre table [k][4] (x y z pad) is read with a
 // wave-uniform index, i.e. through the scalar cache.  ~10 fp64 lane-ops per (point, centre).
+// (W: the inertia partial is sum w_i d2_i; labels, mind2 and the changed-label count do not see the weights)
 __global__ __launch_bounds__(KM_BLOCK) void kmeans_assign_kernel(
     const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ c4, int k,
     int32_t* __restrict__ labels, double* __restrict__ mind2, double* __restrict__ inertia_part,
     unsigned long long* __restrict__ n_changed, const int* __restrict__ done) {
-    if (done && *done) return;
-    __shared__ double sh[4];
-    __shared__ int shc[4];
-    const int64_t i0 = (int64_t)blockIdx.x * (2 * KM_BLOCK) + threadIdx.x;
-    const int64_t i1 = i0 + KM_BLOCK;
-    const bool l0 = i0 < n, l1 = i1 < n;
-    const int64_t j0 = l0 ? i0 : 0, j1 = l1 ? i1 : 0;
-    const double x0 = xs[j0], y0 = xs[n_pad + j0], z0 = xs[2 * n_pad + j0];
-    const double x1 = xs[j1], y1 = xs[n_pad + j1], z1 = xs[2 * n_pad + j1];
-    // Four centres at a time: their minimum (3 v_min_f64) is compared with the running best once, and only the
-    // group's first index is recorded (1 compare + 3 selects per FOUR pairs instead of per pair: 7.75 instead of 10
-    // lane-operations per pair); which of the four it was is settled afterwards by evaluating the winning group
-    // again -- same arithmetic, so the same values, and the first index that attains the minimum wins as before.
-    double b0 = INFINITY, b1 = INFINITY;
-    int a0 = 0, a1 = 0;
-    const int k4 = k & ~3;
-    for (int j = 0; j < k4; j += 4) {
-        double e0[4], e1[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double cx = c4[4 * (j + u)], cy = c4[4 * (j + u) + 1], cz = c4[4 * (j + u) + 2];
-            e0[u] = dist2(x0, y0, z0, cx, cy, cz);
-            e1[u] = dist2(x1, y1, z1, cx, cy, cz);
-        }
-        const double m0 = fmin(fmin(e0[0], e0[1]), fmin(e0[2], e0[3]));
-        const double m1 = fmin(fmin(e1[0], e1[1]), fmin(e1[2], e1[3]));
-        if (m0 < b0) { b0 = m0; a0 = j; }
-        if (m1 < b1) { b1 = m1; a1 = j; }
-    }
-    if (k4 > 0) {
-        // the member of the winning group (divergent group index: vector loads, once per point)
-        int w0 = a0, w1 = a1;
-#pragma unroll
-        for (int u = 3; u >= 0; --u) {
-            const double* p0 = c4 + 4 * (a0 + u);
-            const double* p1 = c4 + 4 * (a1 + u);
-            if (dist2(x0, y0, z0, p0[0], p0[1], p0[2]) == b0) w0 = a0 + u;
-            if (dist2(x1, y1, z1, p1[0], p1[1], p1[2]) == b1) w1 = a1 + u;
-        }
-        a0 = w0; a1 = w1;
-    }
-    for (int j = k4; j < k; ++j) {
-        const double cx = c4[4 * j], cy = c4[4 * j + 1], cz = c4[4 * j + 2];
-        const double d0 = dist2(x0, y0, z0, cx, cy, cz);
-        const double d1 = dist2(x1, y1, z1, cx, cy, cz);
-        if (d0 < b0) { b0 = d0; a0 = j; }
-        if (d1 < b1) { b1 = d1; a1 = j; }
-    }
-    int changed = 0;
-    double in = 0.0;
-    if (l0) {
-        changed += labels[i0] != a0;
-        labels[i0] = a0;
-        mind2[i0] = b0;
-        in += b0;
-    }
-    if (l1) {
-        changed += labels[i1] != a1;
-        labels[i1] = a1;
-        mind2[i1] = b1;
-        in += b1;
-    }
-    const int wc = wave_reduce_i(changed, OpAddI());
-    if (lane_id() == 0) shc[wave_in_block()] = wc;
-    const double t = block_sum_256(in, sh);
-    if (threadIdx.x == 0) {
-        inertia_part[blockIdx.x] = t;
-        const int tc = shc[0] + shc[1] + shc[2] + shc[3];
-        if (tc) atomicAdd(n_changed, (unsigned long long)tc);
-    }
+    constexpr bool WEIGHTED = false;
+    const double* wts = nullptr;
+#define KMEANS_BODY 4
+#include "kmeans_body.h"
+#undef KMEANS_BODY
+}
+__global__ __launch_bounds__(KM_BLOCK) void kmeans_assign_w_kernel(
+    const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ wts,
+    const double* __restrict__ c4, int k, int32_t* __restrict__ labels, double* __restrict__ mind2,
+    double* __restrict__ inertia_part, unsigned long long* __restrict__ n_changed, const int* __restrict__ done) {
+    constexpr bool WEIGHTED = true;
+#define KMEANS_BODY 4
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 // One wave owns a contiguous run of points and NSLOT * 64 centres starting at slot0 * 64; lane l
 // holds the sums of centres slot * 64 + l.  The 64 points of a step are loaded coalesced and then
 // visited one by one (label and coordinates broadcast with v_readlane): the label is wave-uniform,
 // so 'which register' is a scalar branch and 'which lane' an exec mask -- no atomics.
+// (W: the lane multiplies its point's coordinates by its weight once, where it loads them, and the weight is broadcast
+//  with them: the cluster's registers take (w x, w y, w z, w) where they took (x, y, z, 1), in the same order)
 template <int NSLOT>
 __global__ __launch_bounds__(KM_BLOCK) void kmeans_accum_kernel(const double* __restrict__ xs, int64_t n,
                                                                 int64_t n_pad,
@@ -636,48 +568,23 @@ __global__ __launch_bounds__(KM_BLOCK) void kmeans_accum_kernel(const double* __
                                                                 int slot0, int k_alloc,
                                                                 double* __restrict__ partial,
                                                                 const int* __restrict__ done) {
-    if (done && *done) return;
-    __shared__ double sh[4][64][4];
-    const int lane = lane_id(), wave = wave_in_block();
-    double ax[NSLOT], ay[NSLOT], az[NSLOT], ac[NSLOT];
-#pragma unroll
-    for (int s = 0; s < NSLOT; ++s) ax[s] = ay[s] = az[s] = ac[s] = 0.0;
-    const int64_t waves = (int64_t)gridDim.x * 4;
-    const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t begin = gw * per;
-    const int64_t end = begin + per < n ? begin + per : n;
-    for (int64_t base = begin; base < end; base += 64) {
-        const int64_t i = base + lane;
-        const bool ok = i < end;
-        const int64_t ii = ok ? i : 0;
-        const int rel = ok ? labels[ii] - slot0 * 64 : -1;
-        const double x = xs[ii], y = xs[n_pad + ii], z = xs[2 * n_pad + ii];
-        const int cnt = (int)(end - base < 64 ? end - base : 64);
-        for (int t = 0; t < cnt; ++t) {
-            const int r = __builtin_amdgcn_readlane(rel, t);
-            if (r < 0 || r >= NSLOT * 64) continue;
-            const double px = readlane_f64(x, t), py = readlane_f64(y, t), pz = readlane_f64(z, t);
-            const int s = r >> 6;
-            if (lane == (r & 63)) {
-#pragma unroll
-                for (int u = 0; u < NSLOT; ++u)
-                    if (u == s) { ax[u] += px; ay[u] += py; az[u] += pz; ac[u] += 1.0; }
-            }
-        }
-    }
-    double* out = partial + (size_t)blockIdx.x * k_alloc * 4;
-#pragma unroll
-    for (int s = 0; s < NSLOT; ++s) {
-        sh[wave][lane][0] = ax[s];
-        sh[wave][lane][1] = ay[s];
-        sh[wave][lane][2] = az[s];
-        sh[wave][lane][3] = ac[s];
-        __syncthreads();
-        const int l = threadIdx.x >> 2, f = threadIdx.x & 3;
-        out[((size_t)(slot0 + s) * 64 + l) * 4 + f] = (sh[0][l][f] + sh[1][l][f]) + (sh[2][l][f] + sh[3][l][f]);
-        __syncthreads();
-    }
+    constexpr bool WEIGHTED = false;
+    const double* wts = nullptr;
+#define KMEANS_BODY 5
+#include "kmeans_body.h"
+#undef KMEANS_BODY
+}
+template <int NSLOT>
+__global__ __launch_bounds__(KM_BLOCK) void kmeans_accum_w_kernel(const double* __restrict__ xs, int64_t n,
+                                                                  int64_t n_pad, const double* __restrict__ wts,
+                                                                  const int32_t* __restrict__ labels,
+                                                                  int slot0, int k_alloc,
+                                                                  double* __restrict__ partial,
+                                                                  const int* __restrict__ done) {
+    constexpr bool WEIGHTED = true;
+#define KMEANS_BODY 5
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 // k <= 1024: the sums live in LDS instead of registers.  Every wave owns a private table [k][4] (x, y, z, count)
@@ -686,66 +593,27 @@ __global__ __launch_bounds__(KM_BLOCK) void kmeans_accum_kernel(const double* __
 // point instead of ~80.  The table is private to the wave and LDS executes a wave's operations in order, so the
 // additions happen in point order: deterministic, like the register form.  The four tables of a workgroup are added
 // in fixed order on the way out.  One workgroup per CU (4 x 32 KB at k = 1024).
+// (W: the staging tile holds (w x, w y, w z, w) where it held (x, y, z, 1))
 __global__ __launch_bounds__(KM_BLOCK) void kmeans_accum_lds_kernel(const double* __restrict__ xs, int64_t n,
                                                                     int64_t n_pad,
                                                                     const int32_t* __restrict__ labels, int k_alloc,
                                                                     double* __restrict__ partial,
                                                                     const int* __restrict__ done) {
-    if (done && *done) return;
-    extern __shared__ double km_lds[];
-    const int lane = lane_id(), wave = wave_in_block();
-    const int tsz = k_alloc * 4;
-    double* T = km_lds + (size_t)wave * tsz;              // this wave's sums
-    double* S = km_lds + (size_t)4 * tsz + wave * 256;    // [64 points][4] staging of the current batch
-    for (int e = lane; e < tsz; e += 64) T[e] = 0.0;
-    // Wave-level ordering contract, stated instead of assumed: lanes 0..3 read what OTHER lanes of this wave stored
-    // (the staging tile, the cleared table).  The hardware executes one wave's LDS operations in order, but the
-    // compiler may reorder accesses it cannot prove to alias; a wavefront-scope release / acquire fence pair plus the
-    // (free) wave barrier pins the order in the generated code.
-    auto wave_lds_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    wave_lds_sync();                                      // table cleared before the first ds_add
-    const int64_t waves = (int64_t)gridDim.x * 4;
-    const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t begin = gw * per;
-    const int64_t end = begin + per < n ? begin + per : n;
-    const int f = lane & 3;
-    for (int64_t base = begin; base < end; base += 64) {
-        const int64_t i = base + lane;
-        const bool ok = i < end;
-        const int64_t ii = ok ? i : 0;
-        const int lab = ok ? labels[ii] : 0;
-        const double x = xs[ii], y = xs[n_pad + ii], z = xs[2 * n_pad + ii];
-        wave_lds_sync();                                  // the previous batch has been consumed
-        S[lane * 4 + 0] = x; S[lane * 4 + 1] = y; S[lane * 4 + 2] = z; S[lane * 4 + 3] = 1.0;
-        wave_lds_sync();                                  // all 64 lanes' stores before lanes 0..3 read them
-        const int cnt = (int)(end - base < 64 ? end - base : 64);
-        if (lane < 4) {
-            int t = 0;
-            for (; t + 8 <= cnt; t += 8) {
-                double v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = S[(t + u) * 4 + f];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int r = __builtin_amdgcn_readlane(lab, t + u);
-                    (void)__hip_atomic_fetch_add(&T[r * 4 + f], v[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            }
-            for (; t < cnt; ++t) {
-                const int r = __builtin_amdgcn_readlane(lab, t);
-                (void)__hip_atomic_fetch_add(&T[r * 4 + f], S[t * 4 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-    }
-    __syncthreads();
-    double* out = partial + (size_t)blockIdx.x * tsz;
-    for (int e = threadIdx.x; e < tsz; e += KM_BLOCK)
-        out[e] = (km_lds[e] + km_lds[tsz + e]) + (km_lds[2 * tsz + e] + km_lds[3 * tsz + e]);
+    constexpr bool WEIGHTED = false;
+    const double* wts = nullptr;
+#define KMEANS_BODY 6
+#include "kmeans_body.h"
+#undef KMEANS_BODY
+}
+__global__ __launch_bounds__(KM_BLOCK) void kmeans_accum_lds_w_kernel(const double* __restrict__ xs, int64_t n,
+                                                                      int64_t n_pad, const double* __restrict__ wts,
+                                                                      const int32_t* __restrict__ labels, int k_alloc,
+                                                                      double* __restrict__ partial,
+                                                                      const int* __restrict__ done) {
+    constexpr bool WEIGHTED = true;
+#define KMEANS_BODY 6
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 // out[e] = sum over workgroups of partial[b][e], e < 4 k: 32 entries x 8 block slices per
@@ -852,6 +720,19 @@ static int km_check(hgmm_ctx* c, int k) {
     return HGMM_OK;
 }
 
+// The _weighted entries' own refusals (include/hgmm.h), made before anything resident is touched; on success *wts is the
+// context's source-weight array [n_pad], on the row index of x_soa64
+static int km_weights_ready(hgmm_ctx* c, const char* what, const double** wts) {
+    if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "%s: set points first", what);
+    if (!c->src_weighted || !c->src_w.p || c->src_w.cap < sizeof(double) * (size_t)c->n_pad)
+        return fail(c, HGMM_ERR_STATE, "%s: no source weights are resident (set them with hgmm_tree_set_source_weights or "
+                    "hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE), or call the unweighted entry)", what);
+    if (c->comm_on())
+        return fail(c, HGMM_ERR_STATE, "%s: the context has a communicator; sharded weighted fits are not supported", what);
+    *wts = c->src_w.as<double>();
+    return HGMM_OK;
+}
+
 }  // namespace hgmm
 
 using namespace hgmm;
@@ -883,10 +764,18 @@ extern "C" int hgmm_kmeans_center_f64(const double* x, int64_t n, double* mean3,
 }
 #pragma clang fp contract(fast)
 
-extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const double* rand_vals,
-                                    int n_trials, int64_t* ids_out, double* centers_out) {
+// hgmm_kmeans_plusplus (weighted = false) and hgmm_kmeans_plusplus_weighted: the same launch sequence, the `_w` kernels
+// under the resident source weights
+static int km_plusplus(hgmm_ctx* c, bool weighted, int k, int64_t first_id, const double* rand_vals, int n_trials,
+                       int64_t* ids_out, double* centers_out) {
     HGMM_ENTER(c);
+    const double* wts = nullptr;
+    if (weighted) HGMM_TRY(km_weights_ready(c, "hgmm_kmeans_plusplus_weighted", &wts));
     HGMM_TRY(km_check(c, k));
+    if (weighted && (km_nblk(c->n, KM_BLOCK) + KM_GROUP - 1) / KM_GROUP > (unsigned)KM_TAIL_LDS_GROUPS)
+        return fail(c, HGMM_ERR_ARG, "hgmm_kmeans_plusplus_weighted: %lld points exceed the one-launch-per-centre seeding form "
+                    "(%lld points); the two-launch form of larger clouds is unweighted only", (long long)c->n,
+                    (long long)KM_TAIL_LDS_GROUPS * KM_GROUP * KM_BLOCK);
     if (k > c->n) return fail(c, HGMM_ERR_ARG, "kmeans++: k = %d exceeds the %lld points", k, (long long)c->n);
     if (n_trials < 1 || n_trials > KM_MAX_TRIALS)
         return fail(c, HGMM_ERR_ARG, "kmeans++: n_trials = %d outside 1..%d", n_trials, KM_MAX_TRIALS);
@@ -918,6 +807,8 @@ extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const 
     if (k > 1)
         HGMM_HIP(c, hipMemcpyAsync(rand_dev, rand_vals, sizeof(double) * (size_t)(k - 1) * n_trials,
                                    hipMemcpyHostToDevice, c->stream));
+    if (weighted) kmpp_first_w_kernel<<<B, KM_BLOCK, 0, c->stream>>>(xs, n, n_pad, first_id, wts, closest, bsum, centres, ids);
+    else
     kmpp_first_kernel<<<B, KM_BLOCK, 0, c->stream>>>(xs, n, n_pad, first_id, closest, bsum, centres, ids);
     if (k > 1) {
         // The candidates of centre j, their coordinates and their potentials live in buffer j & 1.
@@ -929,6 +820,17 @@ extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const 
         auto part16_b = [&](int j) { return part16 + (size_t)(j & 1) * G * KM_MAX_TRIALS; };
         // tail(jj): accept centre jj among its candidates (select) and / or draw the candidates of centre jj + 1 (draw)
         auto tail = [&](int jj, int select, int draw, const double* rnd) {
+            if (weighted) {
+                if (t8)
+                    kmpp_tail_w_kernel<8><<<1, 1024, 0, c->stream>>>(xs, n, n_pad, wts, closest, part_b(jj), part16_b(jj), G, bsum,
+                                                                     g0, B, n_trials, jj, select, draw, rnd, cand_b(jj), xyz_b(jj),
+                                                                     cand_b(jj + 1), xyz_b(jj + 1), centres, ids, gprefix);
+                else
+                    kmpp_tail_w_kernel<KM_MAX_TRIALS><<<1, 1024, 0, c->stream>>>(xs, n, n_pad, wts, closest, part_b(jj),
+                                                                                 part16_b(jj), G, bsum, g0, B, n_trials, jj, select,
+                                                                                 draw, rnd, cand_b(jj), xyz_b(jj), cand_b(jj + 1),
+                                                                                 xyz_b(jj + 1), centres, ids, gprefix);
+            } else
             if (t8)
                 kmpp_tail_kernel<8><<<1, 1024, 0, c->stream>>>(xs, n, n_pad, closest, part_b(jj), part16_b(jj), G, bsum, g0, B,
                                                                n_trials, jj, select, draw, rnd, cand_b(jj), xyz_b(jj),
@@ -940,6 +842,15 @@ extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const 
                                                                            ids, gprefix);
         };
         auto step = [&](int j, int fold) {
+            if (weighted) {
+                if (t8)
+                    kmpp_step_w_kernel<8><<<G, KM_STEP_BLOCK, 0, c->stream>>>(xs, n, n_pad, wts, closest, centres, fold, xyz_b(j),
+                                                                              n_trials, part_b(j), B, part16_b(j));
+                else
+                    kmpp_step_w_kernel<KM_MAX_TRIALS><<<G, KM_STEP_BLOCK, 0, c->stream>>>(xs, n, n_pad, wts, closest, centres, fold,
+                                                                                          xyz_b(j), n_trials, part_b(j), B,
+                                                                                          part16_b(j));
+            } else
             if (t8)
                 kmpp_step_kernel<8><<<G, KM_STEP_BLOCK, 0, c->stream>>>(xs, n, n_pad, closest, centres, fold, xyz_b(j), n_trials,
                                                                         part_b(j), B, part16_b(j));
@@ -956,6 +867,16 @@ extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const 
             unsigned long long* dbg = nullptr;               // (phase clocks of thread 0: a debugging aid, off)
             for (int j = 2; j < k; ++j) {
                 const double* rnd = rand_dev + (size_t)(j - 1) * n_trials;
+                if (weighted) {
+                    if (t8)
+                        kmpp_fused_w_kernel<8><<<G, KM_STEP_BLOCK, 0, c->stream>>>(
+                            xs, n, n_pad, wts, closest, part_b(j - 1), part16_b(j - 1), part_b(j), part16_b(j), G, B, n_trials, j,
+                            rnd, cand_b(j - 1), xyz_b(j - 1), cand_b(j), xyz_b(j), centres, ids, dbg);
+                    else
+                        kmpp_fused_w_kernel<KM_MAX_TRIALS><<<G, KM_STEP_BLOCK, 0, c->stream>>>(
+                            xs, n, n_pad, wts, closest, part_b(j - 1), part16_b(j - 1), part_b(j), part16_b(j), G, B, n_trials, j,
+                            rnd, cand_b(j - 1), xyz_b(j - 1), cand_b(j), xyz_b(j), centres, ids, dbg);
+                } else
                 if (t8)
                     kmpp_fused_kernel<8><<<G, KM_STEP_BLOCK, 0, c->stream>>>(
                         xs, n, n_pad, closest, part_b(j - 1), part16_b(j - 1), part_b(j), part16_b(j), G, B, n_trials, j, rnd,
@@ -984,10 +905,20 @@ extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const 
     return HGMM_OK;
 }
 
+extern "C" int hgmm_kmeans_plusplus(hgmm_ctx* c, int k, int64_t first_id, const double* rand_vals,
+                                    int n_trials, int64_t* ids_out, double* centers_out) {
+    return km_plusplus(c, false, k, first_id, rand_vals, n_trials, ids_out, centers_out);
+}
+extern "C" int hgmm_kmeans_plusplus_weighted(hgmm_ctx* c, int k, int64_t first_id, const double* rand_vals,
+                                             int n_trials, int64_t* ids_out, double* centers_out) {
+    return km_plusplus(c, true, k, first_id, rand_vals, n_trials, ids_out, centers_out);
+}
+
 namespace {
 struct KmLaunch {
     int nslot, k_alloc, nb_assign, nb_acc;
     bool acc_lds;                                   // per-wave LDS tables (k <= 1024) instead of register slots
+    const double* wts = nullptr;                    // the `_w` kernels under these weights (the _weighted entries)
     double *c3, *c4, *out, *inertia_part;
     unsigned long long* changed;
     KmCtl* ctl;
@@ -1027,13 +958,24 @@ int km_enqueue(hgmm_ctx* c, int k, const KmLaunch& L, const int* done) {
     kmeans_pad_centres_kernel<<<km_nblk(k, 256), 256, 0, c->stream>>>(L.c3, k, L.c4, done);
     {
         ProfScope prof(c, HGMM_K_KMEANS_ASSIGN);
+        if (L.wts)
+            kmeans_assign_w_kernel<<<L.nb_assign, KM_BLOCK, 0, c->stream>>>(xs, n, n_pad, L.wts, L.c4, k, labels,
+                                                                            c->km_mind2.as<double>(), L.inertia_part,
+                                                                            L.changed, done);
+        else
         kmeans_assign_kernel<<<L.nb_assign, KM_BLOCK, 0, c->stream>>>(xs, n, n_pad, L.c4, k, labels,
                                                                       c->km_mind2.as<double>(), L.inertia_part,
                                                                       L.changed, done);
     }
     {
         ProfScope prof(c, HGMM_K_KMEANS_ACCUM);
-        if (L.acc_lds) {
+        if (L.acc_lds && L.wts) {
+            const size_t lds = sizeof(double) * ((size_t)4 * 4 * L.k_alloc + 4 * 256);
+            HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_accum_lds_w_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            kmeans_accum_lds_w_kernel<<<L.nb_acc, KM_BLOCK, lds, c->stream>>>(xs, n, n_pad, L.wts, labels, L.k_alloc,
+                                                                             c->km_partial.as<double>(), done);
+        } else if (L.acc_lds) {
             const size_t lds = sizeof(double) * ((size_t)4 * 4 * L.k_alloc + 4 * 256);
             HGMM_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_accum_lds_kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1041,6 +983,14 @@ int km_enqueue(hgmm_ctx* c, int k, const KmLaunch& L, const int* done) {
                                                                            c->km_partial.as<double>(), done);
         } else
         for (int slot0 = 0; slot0 * 64 < k; slot0 += L.nslot) {
+            if (L.wts) {
+                if (L.nslot == 4)
+                    kmeans_accum_w_kernel<4><<<L.nb_acc, KM_BLOCK, 0, c->stream>>>(xs, n, n_pad, L.wts, labels, slot0, L.k_alloc,
+                                                                                    c->km_partial.as<double>(), done);
+                else
+                    kmeans_accum_w_kernel<KM_ACC_SLOTS><<<L.nb_acc, KM_BLOCK, 0, c->stream>>>(
+                        xs, n, n_pad, L.wts, labels, slot0, L.k_alloc, c->km_partial.as<double>(), done);
+            } else
             if (L.nslot == 4)
                 kmeans_accum_kernel<4><<<L.nb_acc, KM_BLOCK, 0, c->stream>>>(xs, n, n_pad, labels, slot0, L.k_alloc,
                                                                               c->km_partial.as<double>(), done);
@@ -1056,13 +1006,16 @@ int km_enqueue(hgmm_ctx* c, int k, const KmLaunch& L, const int* done) {
 }
 }  // namespace
 
-extern "C" int hgmm_kmeans_step(hgmm_ctx* c, int k, const double* centers, int reset_labels,
-                                double* sums_out, double* inertia_out, int64_t* n_changed_out) {
+static int km_step(hgmm_ctx* c, bool weighted, int k, const double* centers, int reset_labels,
+                   double* sums_out, double* inertia_out, int64_t* n_changed_out) {
     HGMM_ENTER(c);
+    const double* wts = nullptr;
+    if (weighted) HGMM_TRY(km_weights_ready(c, "hgmm_kmeans_step_weighted", &wts));
     HGMM_TRY(km_check(c, k));
     if (!centers) return fail(c, HGMM_ERR_ARG, "kmeans: centers is NULL");
     KmLaunch L;
     HGMM_TRY(km_prepare(c, k, reset_labels, L));
+    L.wts = wts;
     HGMM_HIP(c, hipMemcpyAsync(L.c3, centers, sizeof(double) * 3 * k, hipMemcpyHostToDevice, c->stream));
     HGMM_HIP(c, hipMemsetAsync(L.changed, 0, sizeof(unsigned long long), c->stream));
     HGMM_TRY(km_enqueue(c, k, L, nullptr));
@@ -1077,10 +1030,23 @@ extern "C" int hgmm_kmeans_step(hgmm_ctx* c, int k, const double* centers, int r
     return HGMM_OK;
 }
 
-extern "C" int hgmm_kmeans_lloyd(hgmm_ctx* c, int k, double* centers_inout, int max_iter, double tol_abs,
-                                 int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
-                                 double* sums_out, int64_t* n_changed_out) {
+extern "C" int hgmm_kmeans_step(hgmm_ctx* c, int k, const double* centers, int reset_labels,
+                                double* sums_out, double* inertia_out, int64_t* n_changed_out) {
+    return km_step(c, false, k, centers, reset_labels, sums_out, inertia_out, n_changed_out);
+}
+extern "C" int hgmm_kmeans_step_weighted(hgmm_ctx* c, int k, const double* centers, int reset_labels,
+                                         double* sums_out, double* inertia_out, int64_t* n_changed_out) {
+    return km_step(c, true, k, centers, reset_labels, sums_out, inertia_out, n_changed_out);
+}
+
+// (weighted: column 3 of the sums is the weight in the cluster, and kmeans_update_kernel's `== 0.0` hands the iteration to
+//  the host when a cluster's WEIGHT is zero -- a cluster of zero-weight points included)
+static int km_lloyd(hgmm_ctx* c, bool weighted, int k, double* centers_inout, int max_iter, double tol_abs,
+                    int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
+                    double* sums_out, int64_t* n_changed_out) {
     HGMM_ENTER(c);
+    const double* wts = nullptr;
+    if (weighted) HGMM_TRY(km_weights_ready(c, "hgmm_kmeans_lloyd_weighted", &wts));
     HGMM_TRY(km_check(c, k));
     if (!centers_inout) return fail(c, HGMM_ERR_ARG, "kmeans: centers is NULL");
     if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "kmeans: the device-resident Lloyd loop is single-rank; "
@@ -1091,6 +1057,7 @@ extern "C" int hgmm_kmeans_lloyd(hgmm_ctx* c, int k, double* centers_inout, int 
     if (max_iter < 1) return HGMM_OK;
     KmLaunch L;
     HGMM_TRY(km_prepare(c, k, reset_labels, L));
+    L.wts = wts;
     HGMM_HIP(c, hipMemcpyAsync(L.c3, centers_inout, sizeof(double) * 3 * k, hipMemcpyHostToDevice, c->stream));
     HGMM_HIP(c, hipMemsetAsync(L.changed, 0, sizeof(unsigned long long) + sizeof(KmCtl), c->stream));
     // the stop rule runs on the device; `batch` iterations are enqueued per host synchronisation and the
@@ -1122,6 +1089,19 @@ extern "C" int hgmm_kmeans_lloyd(hgmm_ctx* c, int k, double* centers_inout, int 
     if (strict_out) *strict_out = h.strict;
     if (needs_host_out) *needs_host_out = h.needs_host;
     return HGMM_OK;
+}
+
+extern "C" int hgmm_kmeans_lloyd(hgmm_ctx* c, int k, double* centers_inout, int max_iter, double tol_abs,
+                                 int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
+                                 double* sums_out, int64_t* n_changed_out) {
+    return km_lloyd(c, false, k, centers_inout, max_iter, tol_abs, reset_labels, n_iter_out, strict_out, needs_host_out,
+                    sums_out, n_changed_out);
+}
+extern "C" int hgmm_kmeans_lloyd_weighted(hgmm_ctx* c, int k, double* centers_inout, int max_iter, double tol_abs,
+                                          int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
+                                          double* sums_out, int64_t* n_changed_out) {
+    return km_lloyd(c, true, k, centers_inout, max_iter, tol_abs, reset_labels, n_iter_out, strict_out, needs_host_out,
+                    sums_out, n_changed_out);
 }
 
 extern "C" int hgmm_kmeans_labels(hgmm_ctx* c, int32_t* labels_out, double* min_dist2_out) {

@@ -12,18 +12,29 @@ from .gmm_impl import train_gmm, init_gmm_params, timer, predict, asarray  # noq
 class GMM_GPU_Base:
     _label = 'GPU GMM TRAIN'
 
-    def __init__(self, num_components, max_iter=30, tol=1e-4):
+    def __init__(self, num_components, max_iter=30, tol=1e-4, weighted_init=False):
+        """``weighted_init=True`` (an option of the estimator, so that ``fit`` keeps its argument list): the KMeans seeding
+        gets the same per-point weights as the EM; a fit without weights is then refused."""
         self.num_components = num_components
         self.max_iter = max_iter
         self.tol = tol
+        self.weighted_init = bool(weighted_init)
 
     def fit(self, X, init=None, sample_weight=None):
         """``sample_weight`` [N] >= 0 (default None; a ``WeightedPoints(points, weights)`` brings its own): point i counts as
-        that many points.  The KMeans seeding of ``init_gmm_params`` does not see the weights."""
+        that many points.  The KMeans seeding of ``init_gmm_params`` does not see the weights -- unless the estimator was
+        built with ``weighted_init=True``: the seeding then gets the same weights as the EM (refused without weights)."""
         X, sample_weight = _split_weighted(X, sample_weight)
+        if self.weighted_init and sample_weight is None:
+            raise ValueError("weighted_init=True needs per-point weights (sample_weight=, or a WeightedPoints input)")
         X = np.asarray(X)
         dev_X = asarray(X.astype(np.float32), weights=sample_weight)         # (the weights travel with the resident cloud)
-        means, weights = init if init is not None else init_gmm_params(X, self.num_components)
+        if init is not None:
+            means, weights = init
+        elif self.weighted_init:
+            means, weights = init_gmm_params(X, self.num_components, sample_weight=sample_weight)
+        else:
+            means, weights = init_gmm_params(X, self.num_components)
         covs = 0.1 * np.ones((self.num_components, 3), dtype=np.float32)
         with timer(self._label):
             inv, mu, w, cov, lls = train_gmm(dev_X, self.max_iter, self.tol, np.asarray(means, np.float32),
@@ -51,16 +62,21 @@ class GMM_CPU_Base(GMM_GPU_Base):
 class GMM_GPU(Feature):
     _base = GMM_GPU_Base
 
-    def __init__(self, n_gmm_components=100, max_iter=30, tol=1e-4):
+    def __init__(self, n_gmm_components=100, max_iter=30, tol=1e-4, weighted_init=False):
         self._n_gmm_components = n_gmm_components
         self.max_iter = max_iter
         self.tol = tol
+        self.weighted_init = bool(weighted_init)
 
     def init(self):
-        self._clf = self._base(self._n_gmm_components, max_iter=self.max_iter, tol=self.tol)
+        if self.weighted_init:
+            self._clf = self._base(self._n_gmm_components, max_iter=self.max_iter, tol=self.tol, weighted_init=True)
+        else:
+            self._clf = self._base(self._n_gmm_components, max_iter=self.max_iter, tol=self.tol)
 
     def compute(self, data, weights=None):
-        """``weights`` [N] >= 0: per-point weights of the fit; a ``WeightedPoints`` brings its own."""
+        """``weights`` [N] >= 0: per-point weights of the fit; a ``WeightedPoints`` brings its own.  The KMeans seeding does
+        not see the weights unless the feature was built with ``weighted_init=True`` (then refused without weights)."""
         self._clf.fit(data, sample_weight=weights)
         return self._clf.means_, self._clf.weights_
 

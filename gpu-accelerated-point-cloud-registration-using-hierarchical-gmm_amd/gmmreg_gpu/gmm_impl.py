@@ -9,13 +9,14 @@ eps = 1e-8
 VARIANT = "G"
 
 
-def init_gmm_params(X, k):
+def init_gmm_params(X, k, sample_weight=None):
     """KMeans(k, random_state=1, max_iter=50, n_init=1) centres + uniform weights
     (reference gmm_impl.py:18-24).  The reference calls scikit-learn on the host; here the same
     algorithm (same random stream, same seeds, same stop rule) runs on the device
-    (``hgmm_amd.kmeans``, ``csrc/kmeans_kernels.hip``)."""
+    (``hgmm_amd.kmeans``, ``csrc/kmeans_kernels.hip``).  ``sample_weight`` (default None: the reference's unweighted
+    clustering): ``.fit(X, sample_weight=...)`` as in :meth:`hgmm_amd.kmeans.KMeans.fit`."""
     from ..kmeans import kmeans_centres
-    return kmeans_centres(X, k, random_state=1, max_iter=50), np.ones((k)) / k
+    return kmeans_centres(X, k, random_state=1, max_iter=50, sample_weight=sample_weight), np.ones((k)) / k
 
 
 def estimate_log_prob(X, inv_cov, means):
@@ -33,7 +34,7 @@ def m_step(X, resp, centre_hint=None, sample_weight=None):
 
 def train_gmm(X, max_iter, tol, means, covariances, weights=None, sample_weight=None):
     """``sample_weight`` [N] >= 0: per-point weights of the fit (a ``DevicePoints`` may bring its own).  The KMeans seeding of
-    :func:`init_gmm_params` does not see them."""
+    :func:`init_gmm_params` does not see them (unless it is handed them: ``init_gmm_params(X, k, sample_weight=)``)."""
     if weights is None:
         weights = np.ones(len(means), dtype=np.float32) / len(means)
     return _flat.train_gmm(X, max_iter, tol, means, covariances, weights, 'diag', VARIANT, sample_weight)

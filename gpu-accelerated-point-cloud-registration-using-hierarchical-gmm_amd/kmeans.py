@@ -18,6 +18,18 @@ seeding and the Lloyd assignment / per-cluster sums -- run in HIP kernels
   farthest from their centre (``np.argpartition`` order, like scikit-learn), stop on unchanged
   labels or summed squared centre shift <= tol, one more assignment if the stop was not strict.
 
+Per-point weights (``fit(X, sample_weight=w)``, scikit-learn 1.7.2's semantics): point i counts as ``w[i] >= 0`` points.  Four
+statements change and nothing else does -- the first seed is drawn from ``w / w.sum()``; k-means++ sums ``w * closest`` (the
+potential, the running sum the thresholds search, a candidate's potential) while ``closest`` itself stays the unweighted
+distance; the Lloyd sums are ``sum w x`` over ``sum w``, the inertia is ``sum w d^2`` and a cluster is empty when its weight
+is 0 (assignment, labels and the changed-label count do not see the weights); an empty cluster takes the point farthest from
+its own centre by the UNWEIGHTED distance, and that point carries ``w x`` and ``w`` along.  The mean that centres X and the
+variance that scales ``tol`` stay unweighted, and the weights are not rescaled.  The weighted seeding and Lloyd loop run in the
+``_w`` kernels of ``csrc/kmeans_kernels.hip`` under the context's source weights.  Zero weights together with an empty cluster reach two more
+statements of scikit-learn's, followed here too: a cluster whose weight is still 0 after relocation (it was given a point of
+weight 0) takes the row of the heaviest cluster as the in-order sweep of ``_average_centers`` finds it (averaged if that
+cluster comes earlier in the table, the raw sum if later), and nothing is relocated when the largest distance is 0.  Sharded (communicator) weighted fits are not supported.
+
 Arithmetic is float64 whatever the input dtype (scikit-learn keeps float32 input in float32).
 With an RCCL communicator attached to the context, X is this rank's shard of one joint clustering:
 mean, variance, per-cluster sums, inertia and the changed-label count are all-reduced, the seeds
@@ -82,6 +94,41 @@ def _uniform_cdf(n):
     return _cdf_cache[n]
 
 
+def _weight_cdf(w):
+    """The normalised running sum ``RandomState.choice(n, p=w / w.sum())`` searches."""
+    cdf = (w / w.sum()).cumsum()
+    cdf /= cdf[-1]
+    return cdf
+
+
+def _resolve_weights(X, sample_weight):
+    """(points float64 [N,3], weights float64 [N] or None) of ``fit``'s arguments; every refusal that needs no device."""
+    if sample_weight is None:
+        return np.asarray(X.points if hasattr(X, "points") else X, dtype=np.float64), None
+    if isinstance(sample_weight, str):
+        if sample_weight != "own":
+            raise ValueError("sample_weight must be None, an array [N] or 'own', got %r" % (sample_weight,))
+        if hasattr(X, "points") and getattr(X, "weights", None) is not None:
+            X, w = X.points, X.weights
+        elif hasattr(X, "result") and hasattr(X, "get"):          # a VoxelCloud: centroids and counts, downloaded here
+            X, w = X.get()
+        else:
+            raise ValueError("sample_weight='own' needs an X that brings weights (a WeightedPoints with weights or a "
+                             "VoxelCloud), got %s" % type(X).__name__)
+    else:
+        X, w = (X.points if hasattr(X, "points") else X), sample_weight
+    X = np.asarray(X, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.ndim != 1 or len(w) != len(X):
+        raise ValueError("sample_weight must be [N] = [%d], got %s" % (len(X), w.shape))
+    bad = np.flatnonzero(~(np.isfinite(w) & (w >= 0)))
+    if len(bad):
+        raise ValueError("sample_weight[%d] = %r: the weights must be finite and >= 0" % (bad[0], float(w[bad[0]])))
+    if not w.sum() > 0:
+        raise ValueError("sample_weight: all %d weights are zero" % len(w))
+    return X, w
+
+
 def column_mean_var(X):
     """``X.mean(axis=0)``, ``np.var(X, axis=0)`` and ``X - mean`` of an [N,3] float64 array, bit for bit, at memory
     speed: NumPy reduces a C-ordered [N,3] array over axis 0 row by row (a plain running sum per column, 3 elements
@@ -115,26 +162,39 @@ class KMeans:
         self._ctx = ctx
 
     # -- seeding -------------------------------------------------------------------------
-    def _seed(self, ctx, n, rs):
+    def _seed(self, ctx, n, rs, w=None):
         k = self.n_clusters
         trials = 2 + int(np.log(k))
         # == rs.choice(n, p=w / w.sum()) with w = 1 (the draw scikit-learn makes), without choice()'s
         # validation passes over p: one uniform against the normalised running sum of p
-        first = int(_uniform_cdf(n).searchsorted(rs.random_sample(), side='right'))
+        cdf = _uniform_cdf(n) if w is None else _weight_cdf(w)
+        first = int(cdf.searchsorted(rs.random_sample(), side='right'))
         rand = rs.uniform(size=(max(k - 1, 0), trials))       # == k-1 successive draws of `trials`
         import time
         t0 = time.perf_counter()
-        ids, centres = ctx.kmeans_plusplus(k, first, rand)
+        ids, centres = ctx.kmeans_plusplus(k, first, rand) if w is None else ctx.kmeans_plusplus(k, first, rand, weighted=True)
         self.seeding_ms_ = (time.perf_counter() - t0) * 1e3     # device k-means++ incl. the transfer of the draws
         return ids, centres
 
     # -- scikit-learn's _relocate_empty_clusters_dense ---------------------------------------
     @staticmethod
-    def _relocate_empty(ctx, Xc, sums, counts):
+    def _relocate_empty(ctx, Xc, sums, counts, w=None):
         empty = np.where(counts == 0)[0]
         if len(empty) == 0:
             return
         labels, dist = ctx.kmeans_labels(with_distances=True)
+        if w is not None:
+            # weighted: the farthest points by the UNWEIGHTED distance, in the same order; the point carries w x and w
+            far = np.argpartition(dist, -len(empty))[:-len(empty) - 1:-1]
+            if dist.max() == 0:
+                return
+            for new_id, far_idx in zip(empty, far):
+                old_id = labels[far_idx]
+                sums[old_id] -= Xc[far_idx] * w[far_idx]
+                sums[new_id] = Xc[far_idx] * w[far_idx]
+                counts[new_id] = w[far_idx]
+                counts[old_id] -= w[far_idx]
+            return
         if getattr(ctx, "nranks", 1) > 1:
             relocate_empty_sharded(lambda v, op: ctx.allreduce(v, op=op), ctx.rank, labels, dist, Xc, sums, counts)
             return
@@ -146,8 +206,11 @@ class KMeans:
             counts[new_id] = 1.0
             counts[old_id] -= 1.0
 
-    def fit(self, X):
-        X = np.asarray(X.points if hasattr(X, "points") else X, dtype=np.float64)
+    def fit(self, X, sample_weight=None):
+        """``sample_weight``: None -- the unweighted fit (a ``WeightedPoints`` is read for its points only); an array [N] >= 0
+        -- point i counts as that many points (module docstring); ``"own"`` -- the weights X brings (a ``WeightedPoints``, or
+        a ``VoxelCloud``, whose centroids and counts are downloaded here)."""
+        X, w = _resolve_weights(X, sample_weight)
         if X.ndim != 2 or X.shape[1] != 3:
             raise ValueError("expected an [N,3] array, got %s" % (X.shape,))
         n, k = len(X), self.n_clusters
@@ -155,6 +218,8 @@ class KMeans:
             raise ValueError("n_samples=%d should be >= n_clusters=%d." % (n, k))
         ctx = self._ctx or default_context()
         ranks = getattr(ctx, "nranks", 1)
+        if w is not None:
+            return self._fit_weighted(ctx, X, w)
         if ranks > 1:
             # X is this rank's shard of one joint clustering: global mean / variance / count
             tot = ctx.allreduce(np.concatenate([[float(n)], X.sum(axis=0), (X * X).sum(axis=0)]))
@@ -219,11 +284,72 @@ class KMeans:
         self.cluster_centers_ = centres + mean
         return self
 
-    def fit_predict(self, X):
-        return self.fit(X).labels_
+    def _fit_weighted(self, ctx, X, w):
+        """``fit`` under per-point weights: the loop of the unweighted fit on the weighted entries (single context)."""
+        from ._native import HgmmError
+        n, k = len(X), self.n_clusters
+        if getattr(ctx, "nranks", 1) > 1 or getattr(ctx, "comm_attached", False):
+            raise ValueError("KMeans.fit(sample_weight=): the context has a communicator; sharded weighted fits are not "
+                             "supported")
+        mean, var, Xc = column_mean_var(X)                    # (unweighted, as scikit-learn's X.mean / np.var are)
+        tol_abs = 0.0 if self.tol == 0 else float(np.mean(var) * self.tol)
+        ctx.set_points(Xc)
+        try:
+            ctx.tree_set_source_weights(w)
+        except HgmmError as e:                                # (a refusal _resolve_weights did not foresee)
+            raise ValueError(str(e)) from None
+        if isinstance(self.init, str):
+            self.init_indices_, centres = self._seed(ctx, n, _random_state(self.random_state), w)
+        else:
+            centres = np.array(self.init, dtype=np.float64).reshape(k, 3) - mean
+            self.init_indices_ = None
+        strict = False
+        n_iter = 0
+        inertia = 0.0
+        first = True
+        while n_iter < self.max_iter:
+            centres, done_it, strict, pending = ctx.kmeans_lloyd(centres, self.max_iter - n_iter, tol_abs,
+                                                                 reset_labels=first, weighted=True)
+            n_iter += done_it
+            first = False
+            if pending is None:
+                break
+            # the iteration that met a cluster of weight 0, finished on the host
+            sums, wsum, changed = pending
+            self._relocate_empty(ctx, Xc, sums, wsum, w)
+            # scikit-learn's _average_centers, in table order: a cluster still of weight 0 copies the heaviest cluster's
+            # row as it stands (averaged if that cluster comes earlier, the raw sum if later)
+            new = sums
+            heaviest = int(np.argmax(wsum))
+            for j in range(k):
+                if wsum[j] > 0:
+                    new[j] *= 1.0 / wsum[j]
+                else:
+                    new[j] = new[heaviest]
+            shift_tot = float((np.sqrt(((new - centres) ** 2).sum(axis=1)) ** 2).sum())
+            centres = new
+            n_iter += 1
+            if changed == 0:
+                strict = True
+                break
+            if shift_tot <= tol_abs:
+                break
+        if not strict:
+            _, _, inertia, _ = ctx.kmeans_step(centres, weighted=True)
+        self.labels_ = ctx.kmeans_labels()
+        if strict:
+            inertia = float((w * ((Xc - centres[self.labels_]) ** 2).sum(axis=1)).sum())
+        self.inertia_ = float(inertia)
+        self.n_iter_ = n_iter
+        self.cluster_centers_ = centres + mean
+        return self
+
+    def fit_predict(self, X, sample_weight=None):
+        return self.fit(X, sample_weight=sample_weight).labels_
 
 
-def kmeans_centres(X, k, random_state=1, max_iter=50, ctx: Context | None = None):
+def kmeans_centres(X, k, random_state=1, max_iter=50, ctx: Context | None = None, sample_weight=None):
     """``KMeans(n_clusters=k, random_state=1, max_iter=50, n_init=1).fit(X).cluster_centers_``
-    (gmmreg_gpu/gmm_impl.py:20-21) on the device."""
-    return KMeans(n_clusters=k, random_state=random_state, max_iter=max_iter, n_init=1, ctx=ctx).fit(X).cluster_centers_
+    (gmmreg_gpu/gmm_impl.py:20-21) on the device; ``sample_weight`` as in :meth:`KMeans.fit`."""
+    return KMeans(n_clusters=k, random_state=random_state, max_iter=max_iter, n_init=1,
+                  ctx=ctx).fit(X, sample_weight=sample_weight).cluster_centers_

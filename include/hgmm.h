@@ -545,8 +545,9 @@ int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, c
  * hgmm_tree_score_multi: summary[0] = sum of w, summary[1..6] = the w-weighted sums of what they are without weights, added in
  * the same fixed order; the per-point arrays node / maha2 / logp are not weighted.  NOT honoured by the build (hgmm_tree_build*:
  * the weights of a SOURCE cloud are hgmm_tree_set_source_weights', below) nor by any flat, full-covariance or KMeans entry:
- * they ignore them (the flat fit has weights of its own: hgmm_flat_set_weights; the full-covariance fit takes the SOURCE
- * weights: the unweighted entries ignore them; hgmm_fullcov_fit_weighted / hgmm_fullcov_estep_weighted honour them).         */
+ * they ignore them (the flat fit has weights of its own: hgmm_flat_set_weights; the full-covariance fit and the KMeans
+ * initialiser take the SOURCE weights: the unweighted entries ignore them; hgmm_fullcov_fit_weighted /
+ * hgmm_fullcov_estep_weighted and hgmm_kmeans_plusplus_weighted / _step_weighted / _lloyd_weighted honour them).             */
 int hgmm_tree_set_target_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
 int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
                                        const double* const* w /* w == NULL: none; w[b] == NULL: pair b unweighted */,
@@ -577,11 +578,12 @@ int hgmm_tree_set_target_weights_batch(hgmm_ctx* ctx, int B,
  * refused on the host before anything is touched: HGMM_ERR_ARG, and the previous weights stay in force.
  * Honoured by hgmm_tree_build (serial entry) and hgmm_tree_build_batch (batch entry), in both precisions of
  * hgmm_tree_set_precision, by the flat full-covariance entries that ask for them (serial weights: hgmm_fullcov_fit_weighted,
- * hgmm_fullcov_estep_weighted, below), and by nothing else.  IGNORED by the stand-alone steps below (hgmm_tree_estep,
- * hgmm_tree_mstep, hgmm_tree_loglik and the generic E-step kernel behind them), by every flat and KMeans entry (the flat fit
- * has weights of its own: hgmm_flat_set_weights), by hgmm_fullcov_fit / hgmm_fullcov_estep (full-covariance: the unweighted
- * entries ignore them; `_weighted` honours them), and by the registration and score entries (their weights are the TARGET's,
- * above).  Under a communicator hgmm_tree_build with
+ * hgmm_fullcov_estep_weighted, below), by the KMeans entries that ask for them (serial weights: hgmm_kmeans_plusplus_weighted,
+ * hgmm_kmeans_step_weighted, hgmm_kmeans_lloyd_weighted, below), and by nothing else.  IGNORED by the stand-alone steps below
+ * (hgmm_tree_estep, hgmm_tree_mstep, hgmm_tree_loglik and the generic E-step kernel behind them), by every flat entry (the
+ * flat fit has weights of its own: hgmm_flat_set_weights), by hgmm_fullcov_fit / hgmm_fullcov_estep and hgmm_kmeans_plusplus /
+ * _step / _lloyd / _labels (the unweighted entries ignore them; `_weighted` honours them), and by the registration and score
+ * entries (their weights are the TARGET's, above).  Under a communicator hgmm_tree_build with
  * weights resident returns HGMM_ERR_STATE: sharded weighted builds are not supported.                                        */
 int hgmm_tree_set_source_weights(hgmm_ctx* ctx, const double* w /* host [n]; NULL = no weights */, int64_t n);
 int hgmm_tree_set_source_weights_batch(hgmm_ctx* ctx, int B,
@@ -690,6 +692,37 @@ int hgmm_kmeans_labels(hgmm_ctx* ctx, int32_t* labels_out, double* min_dist2_out
 int hgmm_kmeans_lloyd(hgmm_ctx* ctx, int k, double* centers_inout, int max_iter, double tol_abs,
                       int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
                       double* sums_out, int64_t* n_changed_out);
+/* The same three entries under the SOURCE weights resident on the context (hgmm_tree_set_source_weights, or
+ * hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE): the counts, with no host trip) = the semantics of scikit-learn 1.7.2's
+ * KMeans(...).fit(X, sample_weight=w).  Same argument lists.  The call says what it wants: there is no weight storage, setter,
+ * drop rule or switch of its own, and hgmm_kmeans_plusplus / _step / _lloyd keep ignoring the weights -- their results are bit
+ * for bit what they are, with weights resident or not; hgmm_kmeans_labels is unchanged and serves both.  Point i counts as
+ * w_i >= 0 points; whatever is summed over points carries the weight, nothing else does:
+ *   seeding   closest_i stays the unweighted squared distance; the potential is sum w_i closest_i, the candidates are
+ *             searchsorted(cumsum(w closest), rand * pot) clipped to n - 1, a candidate's potential is
+ *             sum w_i min(closest_i, d2(x_i, cand)), first minimum wins.  (The first seed is the host's draw: first_id.)
+ *   Lloyd     assignment, labels, per-point distance and changed-label count do not see the weights; sums_out[k,4] =
+ *             (sum w x, sum w y, sum w z, sum w) per cluster, centres = sums * (1 / weight), inertia = sum w_i d2_i; a cluster
+ *             is EMPTY when its weight is 0 (a cluster that holds only zero-weight points included): hgmm_kmeans_lloyd_weighted
+ *             then hands the iteration to the host (needs_host = 1) as the unweighted loop does for a count of 0.  Centre
+ *             shift and the three stop rules are unchanged, in their order.
+ * A zero weight leaves the point labelled; it adds nothing to sums, weight or inertia, and the threshold search never lands
+ * on it.  The weighted kernels keep the traversal and summation order of their unweighted twins: w == 1 everywhere gives the
+ * unweighted entries' outputs bit for bit (seeds, labels, sums, centres, inertia, n_iter); w == 2 everywhere gives the
+ * unweighted seeds, labels, centres and n_iter bit for bit and exactly twice the sums, weights and inertia; integer weights
+ * are repetition, up to the order of summation.  Non-finite coordinates are not covered, as in the tree build.
+ * Refused before anything resident is touched: HGMM_ERR_STATE without a float64 view, without resident source weights (set
+ * them, or call the unweighted entry; a forest cloud's weights are not these) and under a communicator (sharded weighted
+ * fits are not supported, as for the weighted tree build and the weighted full-covariance fit); HGMM_ERR_ARG from
+ * hgmm_kmeans_plusplus_weighted for a cloud beyond the one-launch-per-centre seeding form (16.7 M points: the two-launch form
+ * of larger clouds is unweighted only); every HGMM_ERR_ARG of the unweighted entries.                                        */
+int hgmm_kmeans_plusplus_weighted(hgmm_ctx* ctx, int k, int64_t first_id, const double* rand_vals, int n_trials,
+                                  int64_t* ids_out, double* centers_out);
+int hgmm_kmeans_step_weighted(hgmm_ctx* ctx, int k, const double* centers, int reset_labels,
+                              double* sums_out /* [k,4]: w-sums + weight */, double* inertia_out, int64_t* n_changed_out);
+int hgmm_kmeans_lloyd_weighted(hgmm_ctx* ctx, int k, double* centers_inout, int max_iter, double tol_abs,
+                               int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
+                               double* sums_out, int64_t* n_changed_out);
 
 /* ---- L2 GMMReg: Gauss transform (float64) ---------------------------------------------
  * out[k, i] = sum_j weights[k, j] exp(-|points_i - centres_j|^2 / h^2),  k < n_weights <= 8
