@@ -109,16 +109,9 @@
     float eps_v = FLAT_EPS;
     asm volatile("" : "+v"(eps_v));
     float lacc = 0.f;                      // sum of log2(den) of the rows since the last flush
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    float sw = 1.f;                        // (WEIGHTED) this row's weight
     double swsum = 0.0;                    // (WEIGHTED) sum of the weights of this wave's rows
-    if (nrows > 0) { x0 = xw[0]; x1 = xw[1]; x2 = xw[2]; if (WEIGHTED) sw = SW[r0]; }
-    for (int row = 0; row < nrows; ++row) {                 // (row: counted from the wave's first one)
-        const int nrow = (row + 1 < nrows) ? row + 1 : row;
-        const float* xn = xw + 3 * (int64_t)nrow;
-        const float nx0 = xn[0], nx1 = xn[1], nx2 = xn[2];
-        float nsw = 1.f;
-        if constexpr (WEIGHTED) nsw = SW[r0 + nrow];
+    // One row's E and M phase: everything a row does but fetch its coordinates and flush lacc, which belong to the loops below.
+    auto row_em = [&](const float x0, const float x1, const float x2, const float sw) __attribute__((always_inline)) {
         // (WEIGHTED) a row of weight zero is absent, whatever its coordinates: a wave-uniform branch round the row's work
         if (!WEIGHTED || !weight_is_zero(sw)) {
             const f2 X0 = f2{x0, x0}, X1 = f2{x1, x1}, X2 = f2{x2, x2};
@@ -182,13 +175,6 @@
                 inv_den = __builtin_amdgcn_rcpf(den);
                 if constexpr (WEIGHTED) lacc = fmaf(sw, __builtin_amdgcn_logf(den), lacc);
                 else lacc += __builtin_amdgcn_logf(den);
-                if constexpr (!WEIGHTED) {
-                    if ((row & 7) == 7) {
-                        asm volatile("" ::: "memory");          // keeps this a (wave-uniform) branch, not selects
-                        lsum += (double)lacc;
-                        lacc = 0.f;
-                    }
-                }
             } else {
                 const float lpn2 = lpn2_from(m, s, inv_den);
                 if constexpr (WEIGHTED) lsum += (double)sw * (double)(lpn2 * LN2);
@@ -205,19 +191,104 @@
             }
             if (ODD) {
                 const float rr = wls * inv_den;
-                s0s += rr;
+                // (unweighted: spelt as the fused multiply-add the compiler makes of s0 += rr everywhere else in this loop --
+                //  left to it, this one addition can be paired with lacc's instead, and the sum is then rounded twice.
+                //  Weighted, lacc's update is a fused multiply-add itself: spelt alike the two are paired into one packed
+                //  instruction whose operands cost <13, true> its 256th register and its second wave per SIMD.)
+                if constexpr (WEIGHTED) s0s += rr;
+                else s0s = fmaf(wls, inv_den, s0s);
                 a0s = fmaf(rr, xo0, a0s); a1s = fmaf(rr, xo1, a1s); a2s = fmaf(rr, xo2, a2s);
                 b0s = fmaf(rr, q0s, b0s); b1s = fmaf(rr, q1s, b1s); b2s = fmaf(rr, q2s, b2s);
             }
         }
-        if constexpr (WEIGHTED) {
-            // the 8-row flush of lacc, on the rows' schedule whether this one was skipped or not (ONE site for both paths:
-            // a second one in the skipped path cost <13, true> 45 AGPRs and its second wave per SIMD)
-            if (CS && (row & 7) == 7) {
-                asm volatile("" ::: "memory");
-                lsum += (double)lacc;
-                lacc = 0.f;
+    };
+    // The constant-shift loop runs FUSED_TRIP rows per trip, straight-line: a full trip has no prefetch clamp, no exit test
+    // and no flush test per row -- one compare and one branch per trip, and the float64 flush of lacc at its end.  The wave
+    // counts its rows from zero and a trip starts at a multiple of FUSED_TRIP, so the flush falls after the rows with
+    // (row & 7) == 7, the same eight rows per float32 sum as when every row tested for it; rows, operations and operands are
+    // in the order they were.
+    // The coordinates (and weights) arrive by wide scalar loads, half a trip at a time, into the registers of the half
+    // consumed before: the second half of this trip is fetched behind the first row of the first half, the first half of
+    // the next trip behind the first row of the second (this trip's again when no full trip follows: the address stays
+    // inside the wave's rows).  Scalar loads return out of order, so a wait is a wait for all of them: a fetch issued before
+    // the half in flight is first read would be waited for at once.  The three rows between a fetch and its first use are
+    // what the trip is for: with the same trip fetching one row ahead, as the one-row loop does, the kernel is as fast as
+    // it was without trips (N = 1e6, J = 800: 3137 against 3129 it/s), with them 3274 (profiles/fused_row_trip.md).
+    // What keeps a row's instructions between its neighbours': the empty asm statements -- a row's coordinates exist from
+    // its first statement on, the odd slot's sums are complete at its last -- and the scheduling barrier.  Without them the
+    // vectoriser pairs the odd slot's scalar operations of one row with the next row's and the scheduler interleaves rows,
+    // and both keep the values in between in registers the kernel does not have (<13, false>: 256 + 85 and scratch).
+    // (NSLOT > 13 keeps one row per trip: those kernels run one wave per SIMD with part of their sums in AGPRs, and the
+    //  straight-line trip's allocation spilt to scratch at NSLOT = 15 and 16)
+    constexpr int TRIP = NSLOT <= 13 ? FUSED_TRIP : 1;
+    int row = 0;                                            // (row: counted from the wave's first one)
+    if constexpr (CS && TRIP > 1) {
+        constexpr int HALF = TRIP > 1 ? TRIP / 2 : 1;       // (TRIP == 1: this block is discarded, but it is still parsed)
+        static_assert(8 % TRIP == 0, "a flush every eight rows falls at the end of a trip");
+        if (nrows >= TRIP) {
+            float xa[3 * HALF], xb[3 * HALF], wa[HALF], wb[HALF];
+            // HALF rows from `have`; behind the first of them, the fetch of the HALF rows from row `next` into `into`
+            auto half_trip = [&](const float (&have)[3 * HALF], const float (&whave)[HALF], float (&into)[3 * HALF],
+                                 float (&winto)[HALF], const int next) __attribute__((always_inline)) {
+#pragma unroll
+                for (int t = 0; t < HALF; ++t) {
+                    float c0 = have[3 * t], c1 = have[3 * t + 1], c2 = have[3 * t + 2];
+                    asm volatile("" : "+s"(c0), "+s"(c1), "+s"(c2));
+                    row_em(c0, c1, c2, whave[t]);
+                    if (ODD) asm volatile("" : : "v"(s0s), "v"(a0s), "v"(a1s), "v"(a2s), "v"(b0s), "v"(b1s), "v"(b2s));
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t == 0) {
+                        const float* xn = xw + 3 * (int64_t)next;
+#pragma unroll
+                        for (int i = 0; i < 3 * HALF; ++i) into[i] = xn[i];
+                        if constexpr (WEIGHTED) {
+#pragma unroll
+                            for (int i = 0; i < HALF; ++i) winto[i] = SW[r0 + next + i];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            };
+#pragma unroll
+            for (int i = 0; i < 3 * HALF; ++i) xa[i] = xw[i];
+#pragma unroll
+            for (int i = 0; i < HALF; ++i) wa[i] = wb[i] = 1.f;
+            if constexpr (WEIGHTED) {
+#pragma unroll
+                for (int i = 0; i < HALF; ++i) wa[i] = SW[r0 + i];
             }
+            for (; nrows - row >= TRIP; row += TRIP) {
+                half_trip(xa, wa, xb, wb, row + HALF);
+                half_trip(xb, wb, xa, wa, nrows - row >= 2 * TRIP ? row + TRIP : row);
+                if (TRIP == 8 || ((row + TRIP) & 7) == 0) {
+                    lsum += (double)lacc;
+                    lacc = 0.f;
+                }
+            }
+        }
+    }
+    // the last nrows % TRIP rows, and every row of the row-maximum variant: one row per trip, the next row's
+    // coordinates prefetched behind a clamp
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
+    float sw = 1.f;                        // (WEIGHTED) this row's weight
+    if (row < nrows) {
+        const float* xr = xw + 3 * (int64_t)row;
+        x0 = xr[0]; x1 = xr[1]; x2 = xr[2];
+        if (WEIGHTED) sw = SW[r0 + row];
+    }
+    for (; row < nrows; ++row) {
+        const int nrow = (row + 1 < nrows) ? row + 1 : row;
+        const float* xn = xw + 3 * (int64_t)nrow;
+        const float nx0 = xn[0], nx1 = xn[1], nx2 = xn[2];
+        float nsw = 1.f;
+        if constexpr (WEIGHTED) nsw = SW[r0 + nrow];
+        row_em(x0, x1, x2, sw);
+        // the 8-row flush of lacc, on the rows' schedule whether this one was skipped or not; with eight rows per trip the
+        // rows left over start at a multiple of eight and are fewer than eight: none of them is a row 7
+        if (CS && TRIP != 8 && (row & 7) == 7) {
+            asm volatile("" ::: "memory");                  // keeps this a (wave-uniform) branch, not selects
+            lsum += (double)lacc;
+            lacc = 0.f;
         }
         x0 = nx0; x1 = nx1; x2 = nx2;
         if constexpr (WEIGHTED) sw = nsw;

@@ -17,6 +17,7 @@ constexpr int PK_ROWS = 8;
 typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr int BLOCK = WAVES_PER_BLOCK * 64;
+constexpr int FUSED_TRIP = 8;              // rows per straight-line trip of the fused kernels' constant-shift loop (8, 4 or 2)
 
 // The reference's normaliser  log( sum_j exp(wlp_j) + eps )  (gmm_waymo gmm_impl.py:113, no
 // max-shift there) from the wave maximum m2 and S = sum_j 2^(wl2_j - m2), all in log2 units:

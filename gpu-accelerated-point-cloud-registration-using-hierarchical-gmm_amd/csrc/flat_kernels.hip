@@ -2029,6 +2029,11 @@ static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* v
     //    spills 372 B per lane, 0.43 ms; one row (248 VGPRs, two waves per SIMD) stays the best, 0.405 ms;
     //  * constant-shift log-sum-exp: see flat_fused_pk_kernel; 0.514 -> 0.440 ms (a table whose largest constant
     //    leaves the safe range takes the kernel's row-maximum loop by itself).
+    //  * eight rows per straight-line trip, their coordinates fetched by wide scalar loads three rows before their first
+    //    use (flat_fused_body.h): the kernel 310.4 -> 296.6 us, the step 0.3196 -> 0.3054 ms, the same bits.  The fetch
+    //    distance is the gain: the same trip fetching one row ahead is no faster than one row per trip (0.3188 ms); the
+    //    trip itself takes the loop's scalar instructions from 18 to 5 per row and its branches from 3 to 1/8
+    //    (profiles/fused_row_trip.md).
     const int slots = std::min(ns, 16);
     *valid_j = slots * 64;
     ProfScope prof(c, HGMM_K_FLAT_FUSED);
