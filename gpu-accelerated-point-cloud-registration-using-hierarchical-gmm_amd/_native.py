@@ -1108,13 +1108,18 @@ class Context:
         estimate_log_prob do not see them.  ``None``: no weights.  They belong to the cloud :meth:`set_points` uploaded (or
         the bound handle): whatever changes the resident cloud drops them.  The library refuses a wrong length, a NaN,
         infinite or negative weight and all-zero weights (HgmmError, naming the index) and keeps the previous weights."""
-        if s is None:
-            self._check(self.lib.hgmm_flat_set_weights(self.h, None, 0))
+        return self._set_weights(self.lib.hgmm_flat_set_weights, s, np.float32, "N")
+
+    def _set_weights(self, entry, w, dtype, length):
+        """flat_set_weights, tree_set_target_weights, tree_set_source_weights: ``None`` takes the weights off, anything else
+        goes to the library as a contiguous 1-D array of ``dtype``"""
+        if w is None:
+            self._check(entry(self.h, None, 0))
             return self
-        s = np.ascontiguousarray(s, dtype=np.float32)
-        if s.ndim != 1:
-            raise ValueError("weights must be [N], got %s" % (s.shape,))
-        self._check(self.lib.hgmm_flat_set_weights(self.h, _ptr(s), s.shape[0]))
+        w = np.ascontiguousarray(w, dtype=dtype)
+        if w.ndim != 1:
+            raise ValueError("weights must be [%s], got %s" % (length, w.shape))
+        self._check(entry(self.h, _ptr(w), w.shape[0]))
         return self
 
     # -- HGMM ---------------------------------------------------------------------------
@@ -1198,14 +1203,7 @@ class Context:
         see them.  ``None``: no weights.  They belong to the target :meth:`tree_set_target` uploaded -- a new target drops
         them.  The library refuses a wrong length, a NaN, infinite or negative weight and all-zero weights (HgmmError, naming
         the index) and keeps the previous weights."""
-        if w is None:
-            self._check(self.lib.hgmm_tree_set_target_weights(self.h, None, 0))
-            return self
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if w.ndim != 1:
-            raise ValueError("weights must be [M], got %s" % (w.shape,))
-        self._check(self.lib.hgmm_tree_set_target_weights(self.h, _ptr(w), w.shape[0]))
-        return self
+        return self._set_weights(self.lib.hgmm_tree_set_target_weights, w, np.float64, "M")
 
     def tree_set_source_weights(self, w):
         """Per-point weights ``w`` [n] >= 0 of the resident cloud for :meth:`tree_build` (hgmm_tree_set_source_weights): point
@@ -1215,14 +1213,7 @@ class Context:
         cloud drops them.  The build reads them, and the entries that ask for them by name (``fullcov_fit(..., weighted=True)``,
         ``kmeans_plusplus / kmeans_step / kmeans_lloyd(..., weighted=True)``); nothing else does.  The library refuses a wrong length, a NaN, infinite or negative
         weight and all-zero weights (HgmmError, naming the index) and keeps the previous weights."""
-        if w is None:
-            self._check(self.lib.hgmm_tree_set_source_weights(self.h, None, 0))
-            return self
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if w.ndim != 1:
-            raise ValueError("weights must be [N], got %s" % (w.shape,))
-        self._check(self.lib.hgmm_tree_set_source_weights(self.h, _ptr(w), w.shape[0]))
-        return self
+        return self._set_weights(self.lib.hgmm_tree_set_source_weights, w, np.float64, "N")
 
     def tree_reg_estep(self, T, rot=None, t=None, scale=1.0, lambda_c=0.01):
         rot = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3, 3)

@@ -2015,7 +2015,7 @@ static int launch_fused(hgmm_ctx* c, const int* done_flag, int* grid_out, int* v
     const float* pk = c->f_pack.as<float>();
     float* part = c->f_partials.as<float>();
     double* lp = c->f_lpn_partials.as<double>();
-    const float* sw = c->flat_sw_ptr();             // hgmm_flat_set_weights: the WEIGHTED instantiations
+    const float* sw = c->flat_w.ptr();             // hgmm_flat_set_weights: the WEIGHTED instantiations
     // Design notes (measured on MI355X at N = 1e6, J = 800; see DESIGN.md section 6 for the list):
     //  * more rows in flight per wave lose: 1 row (249 VGPRs, 2 waves/SIMD) 0.544 ms, 2 rows
     //    (310 regs, 1 wave/SIMD) 0.677 ms, 4 rows (424 regs) 0.772 ms;
@@ -2054,7 +2054,7 @@ static int launch_reduce(hgmm_ctx* c, int nblocks, int valid_j, bool with_lpn, c
     if (c->comm_on() || !done_flag) done_flag = c->f_ctl.as<int>() + 16;        // always 0 (flat_setup)
     flat_reduce_kernel<<<(total + RED_IDX - 1) / RED_IDX + 1, RED_IDX * RED_SLICES, 0, c->stream>>>(
         c->f_partials.as<float>(), with_lpn ? c->f_lpn_partials.as<double>() : nullptr, nblocks,
-        n_lpn_blocks < 0 ? nblocks : n_lpn_blocks, valid_j, f.Jpad, c->flat_n(), c->f_stats.as<double>(),
+        n_lpn_blocks < 0 ? nblocks : n_lpn_blocks, valid_j, f.Jpad, c->flat_w.total(c->n), c->f_stats.as<double>(),
         done_flag);
     HGMM_HIP(c, hipGetLastError());
     if (c->comm_on()) HGMM_TRY(allreduce_f64_dev(c, c->f_stats.as<double>(), (size_t)total + 2));
@@ -2083,7 +2083,7 @@ static int chunk_normalisers(hgmm_ctx* c, bool want_arg, float* lpn_out, int32_t
     flat_chunk_combine_kernel<<<cblocks, 256, 0, c->stream>>>(cm, cs, want_arg ? ca : nullptr, f.nchunks, c->n,
                                                             c->f_lpn2.as<float>(), lpn_out, argmax_out,
                                                             want_partials ? c->f_lpn_partials.as<double>() : nullptr,
-                                                            c->flat_sw_ptr());
+                                                            c->flat_w.ptr());
     HGMM_HIP(c, hipGetLastError());
     if (n_lpn_blocks) *n_lpn_blocks = cblocks;
     return HGMM_OK;
@@ -2107,7 +2107,7 @@ static int chunk_statistics(hgmm_ctx* c, const int* done_flag, int* grid_out) {
     const int grid = grid_for(c, c->n, 2);
     {
         ProfScope prof(c, HGMM_K_FLAT_FUSED);
-        const float* sw = c->flat_sw_ptr();
+        const float* sw = c->flat_w.ptr();
         const auto kernel = kernel_for<ChunkFusedFamily>(sw != nullptr);
         for (int ci = 0; ci < f.nchunks; ++ci)
             kernel<<<grid, BLOCK, 0, c->stream>>>(
@@ -2167,7 +2167,7 @@ static int enqueue_em_iteration(hgmm_ctx* c) {
         ProfScope prof(c, HGMM_K_FLAT_BOUNDARY);
         flat_boundary_kernel<<<f.Jpad / BND_COMP + 1, BND_COMP * RED_SLICES, 0, c->stream>>>(
             c->f_partials.as<float>(), c->f_lpn_partials.as<double>(), grid, valid_j, f.J, f.Jpad, f.cov_type, f.variant,
-            c->flat_n(), c->f_stats.as<double>(), c->f_mu.as<float>(), c->f_cov.as<float>(), c->f_w.as<float>(),
+            c->flat_w.total(c->n), c->f_stats.as<double>(), c->f_mu.as<float>(), c->f_cov.as<float>(), c->f_w.as<float>(),
             c->f_inv.as<float>(), c->f_pack.as<float>(), c->f_lls.as<float>(), f.lls_cap, f.tol, ctl, ctl_f, stop,
             stop_next);
         HGMM_HIP(c, hipGetLastError());
@@ -2250,7 +2250,7 @@ static int flat_estep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
                               const float* w, float* dev_log_resp, float*& dev_lpn, int32_t* dev_argmax, int* grid_out,
                               bool params_on_device = false, bool want_mean = false) {
     HGMM_TRY(flat_prepare(c, cov_type, variant, J));
-    if (want_mean && c->flat_weighted && !dev_lpn && J <= FLAT_MAX_J) {
+    if (want_mean && c->flat_w.ptr() && !dev_lpn && J <= FLAT_MAX_J) {
         // weights in force: the mean is formed from the rows' log-normalisers -- the context's scratch when the caller has none
         // (J > FLAT_MAX_J: the chunked path's combine kernel weights its partial sums itself)
         HGMM_TRY(ensure(c, c->f_lpn_rows, sizeof(float) * (size_t)c->n));
@@ -2265,9 +2265,9 @@ static int flat_estep_enqueue(hgmm_ctx* c, int cov_type, int variant, int J, con
         if (dev_log_resp) HGMM_TRY(chunk_write(c, c->f_lpn2.as<float>(), dev_log_resp));
     } else {
         HGMM_TRY(launch_estep<true>(c, dev_log_resp, dev_lpn, dev_argmax, &grid));
-        if (want_mean && c->flat_weighted) {               // the workgroups' partial sums, weighted (see the kernel)
+        if (want_mean && c->flat_w.ptr()) {                // the workgroups' partial sums, weighted (see the kernel)
             flat_weighted_lpn_partials_kernel<<<(grid * WAVES_PER_BLOCK + 255) / 256, 256, 0, c->stream>>>(
-                dev_lpn, c->flat_sw.as<float>(), c->n, grid, c->flat.last_estep_rows4 ? 1 : 0, c->f_lpn_partials.as<double>());
+                dev_lpn, c->flat_w.ptr(), c->n, grid, c->flat.last_estep_rows4 ? 1 : 0, c->f_lpn_partials.as<double>());
             HGMM_HIP(c, hipGetLastError());
         }
     }
@@ -2289,7 +2289,7 @@ extern "C" int hgmm_flat_estep(hgmm_ctx* c, int cov_type, int variant, int J, co
         HGMM_HIP(c, ctx_stream_sync(c));
         double t = 0.0;
         for (double v : h) t += v;
-        *mean_lpn_out = t / c->flat_n();
+        *mean_lpn_out = t / c->flat_w.total(c->n);
     }
     return HGMM_OK;
 }
@@ -2302,7 +2302,7 @@ static int flat_estep_nowait(hgmm_ctx* c, int cov_type, int variant, int J, cons
     HGMM_TRY(flat_estep_enqueue(c, cov_type, variant, J, mu, inv_std, w, dev_log_resp, dev_lpn, dev_argmax, &grid,
                                 params_on_device, dev_mean_lpn != nullptr));
     if (dev_mean_lpn) {
-        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, c->flat_n(), dev_mean_lpn);
+        flat_mean_lpn_kernel<<<1, 256, 0, c->stream>>>(c->f_lpn_partials.as<double>(), grid, c->flat_w.total(c->n), dev_mean_lpn);
         HGMM_HIP(c, hipGetLastError());
     }
     return HGMM_OK;
@@ -2382,7 +2382,7 @@ extern "C" int hgmm_flat_log_prob(hgmm_ctx* c, int cov_type, int J, const float*
 template <int NV4, int NV1>
 static void launch_mstep(hgmm_ctx* c, int grid, int is_log, const float* resp, const float* hint, int jv, float* part) {
     const FlatState& f = c->flat;
-    const float* sw = c->flat_sw_ptr();             // hgmm_flat_set_weights: the WEIGHTED instantiations
+    const float* sw = c->flat_w.ptr();             // hgmm_flat_set_weights: the WEIGHTED instantiations
     // non-temporal loads: 6.1 -> 6.8 TB/s at J = 800, a gain or a tie for every row length that is a whole number of
     // 16-byte pieces -- and a loss when rows straddle them (J = 513: 0.380 vs 0.351 ms, J = 37: 0.176 vs 0.142: a line shared by
     // two rows is then fetched for each of them; profiles/r04/mstep_nt_by_J.log)
@@ -2649,31 +2649,25 @@ extern "C" int hgmm_flat_train(hgmm_ctx* c, int cov_type, int variant, int J, in
     return hgmm_flat_train_end(c, mu, cov, w, inv_std_out, lls_out, n_iter_out, converged_out);
 }
 
-// per-point weights of the resident cloud for the flat EM (include/hgmm.h): flat_sw [n] parallel to the rows of x_aos
+// per-point weights of the resident cloud for the flat EM (include/hgmm.h): flat_w [n] parallel to the rows of x_aos
 extern "C" int hgmm_flat_set_weights(hgmm_ctx* c, const float* s, int64_t n) {
     HGMM_ENTER(c);
     const char* what = "hgmm_flat_set_weights";
     if (!c->have_f32 || c->n <= 0)
         return fail(c, HGMM_ERR_STATE, "%s: no cloud with float32 rows (hgmm_set_points_f32 / _f64 or hgmm_points_bind first; "
                     "a forest cloud of hgmm_set_points_batch_* has none)", what);
-    if (!s) { c->flat_weighted = false; return HGMM_OK; }
+    if (!s) { c->flat_w.drop(); return HGMM_OK; }
     if (n != c->n)
         return fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident cloud has %lld points", what, (long long)n, (long long)c->n);
-    double sum = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (!(s[i] >= 0.0f) || !(s[i] < INFINITY))                  // (NaN fails the first comparison)
-            return fail(c, HGMM_ERR_ARG, "%s: weight %lld is %g (weights must be finite and >= 0)", what, (long long)i, (double)s[i]);
-        sum += (double)s[i];
-    }
-    if (!(sum > 0.0)) return fail(c, HGMM_ERR_ARG, "%s: all %lld weights are zero", what, (long long)n);
+    double sum = 0.0;                                   // float64, on the host, in index order
+    HGMM_TRY(check_point_weights(c, what, s, n, &sum));
     // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
-    c->flat_weighted = false;
+    c->flat_w.drop();
     HGMM_HIP(c, hipSetDevice(c->device));
-    HGMM_TRY(ensure(c, c->flat_sw, sizeof(float) * (size_t)n));
-    HGMM_HIP(c, hipMemcpyAsync(c->flat_sw.p, s, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HGMM_TRY(ensure(c, c->flat_w.buf, sizeof(float) * (size_t)n));
+    HGMM_HIP(c, hipMemcpyAsync(c->flat_w.buf.p, s, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HGMM_HIP(c, ctx_stream_sync(c));
-    c->flat_wsum = sum;
-    c->flat_weighted = true;
+    c->flat_w.publish({sum});
     return HGMM_OK;
 }
 
@@ -2742,7 +2736,7 @@ __global__ __launch_bounds__(BLOCK) void flat_fused_pk_batch_kernel(
 }
 
 // blockIdx.y = member in the three small kernels; blockIdx.x is what it is in the serial launch
-// (m.wn: what flat_n() is to the serial launch -- the slot's weight sum, or (double)n)
+// (m.wn: what flat_w.total(n) is to the serial launch -- the slot's weight sum, or (double)n)
 __global__ __launch_bounds__(RED_IDX * RED_SLICES) void flat_reduce_batch_kernel(
     const FlatBatchMember* __restrict__ members, int valid_j, int Jpad, int parity) {
     const FlatBatchMember& m = members[blockIdx.y];
@@ -2970,21 +2964,15 @@ static int flat_train_batch_handles(hgmm_ctx* c, const char* what, int B, hgmm_p
         slots[b] = FlatBatchSlot{clouds[b]->x_aos.as<float>(), n, nullptr, (double)n};
         const float* sb = s ? s[b] : nullptr;
         if (!sb) continue;
-        double sum = 0.0;
-        for (int64_t i = 0; i < n; ++i) {
-            if (!(sb[i] >= 0.0f) || !(sb[i] < INFINITY))                // (NaN fails the first comparison)
-                return fail(c, HGMM_ERR_ARG, "%s: slot %d: weight %lld is %g (weights must be finite and >= 0)", what, b,
-                            (long long)i, (double)sb[i]);
-            sum += (double)sb[i];
-        }
-        if (!(sum > 0.0)) return fail(c, HGMM_ERR_ARG, "%s: slot %d: all %lld weights are zero", what, b, (long long)n);
-        slots[b].wn = sum;
+        char label[96];
+        snprintf(label, sizeof label, "%s: slot %d", what, b);
+        HGMM_TRY(check_point_weights(c, label, sb, n, &slots[b].wn));
         sw_at[b] = sw_total;
         sw_total += (size_t)n;
     }
     if (sw_total) {
         // ONE buffer of the batch's own and one copy into it, before the begin launch: nothing is uploaded between iterations,
-        // and the context's own flat weights (flat_sw, flat_wsum) are neither read nor written
+        // and the context's own flat weights (flat_w) are neither read nor written
         HGMM_TRY(ensure(c, c->fb_sw,sizeof(float) * sw_total + 64));
         std::vector<float> packed(sw_total);
         for (int b = 0; b < B; ++b)

@@ -909,24 +909,16 @@ static int fullcov_pass(hgmm_ctx* c, int J, int* labels, double* q_host, const d
     return HGMM_OK;
 }
 
-// The _weighted entries' own refusals (include/hgmm.h), made before anything resident is touched
-static int fullcov_weights_ready(hgmm_ctx* c, const char* what) {
-    if (!c->src_weighted)
-        return fail(c, HGMM_ERR_STATE, "%s: no source weights are resident (set them with hgmm_tree_set_source_weights or "
-                    "hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE), or call the unweighted entry)", what);
-    if (c->comm_on())
-        return fail(c, HGMM_ERR_STATE, "%s: the context has a communicator; sharded weighted fits are not supported", what);
-    return HGMM_OK;
-}
-
 // hgmm_fullcov_fit (weighted = false) and hgmm_fullcov_fit_weighted: the weighted level's three statements -- the E-step
-// kernels' WEIGHTED instantiations (moments and log-likelihood) and pi = m0 / W with W = src_wsum
+// kernels' WEIGHTED instantiations (moments and log-likelihood) and pi = m0 / W with W = the source weights' sum
 static int fullcov_fit(hgmm_ctx* c, bool weighted, int J, double ls, double ld, const double* init_mu, double sig2,
                        int max_iters, double* pi_out, double* mu_out, double* cov_out,
                        int32_t* labels_out, double* q_trace_out, int q_capacity, int* q_len_out) {
     HGMM_ENTER(c);
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "full-covariance fit: set points first");
-    if (weighted) HGMM_TRY(fullcov_weights_ready(c, "hgmm_fullcov_fit_weighted"));
+    // (the source weights are never written by a tree build: the level-0 order of x_soa64, BuildWorkspace in tree_host.h)
+    const double* wsrc = nullptr;
+    if (weighted) HGMM_TRY(source_weights_ready(c, "hgmm_fullcov_fit_weighted", &wsrc));
     if (J < 1 || J > 4096) return fail(c, HGMM_ERR_ARG, "J = %d outside 1..4096", J);
     if (!init_mu) return fail(c, HGMM_ERR_ARG, "init_mu is NULL");
     if (max_iters < 1) max_iters = 1;
@@ -943,9 +935,7 @@ static int fullcov_fit(hgmm_ctx* c, bool weighted, int J, double ls, double ld, 
     HGMM_HIP(c, hipMemcpyAsync(c->scratch.p, init_mu, sizeof(double) * 3 * J, hipMemcpyHostToDevice, c->stream));
     full_init_nodes_kernel<<<nblk(J16, 256), 256, 0, c->stream>>>(c->scratch.as<double>(), sig2, J, J16, d_pi, d_mu, d_cov);
     tree_prep_kernel<<<nblk(J16, 256), 256, 0, c->stream>>>(d_pi, d_mu, d_cov, 0, J16, d_prep, flags_ptr(c));
-    // (src_w is never written by a tree build: the level-0 order of x_soa64, BuildWorkspace in tree_host.h)
-    const double* wsrc = weighted ? c->src_w.as<double>() : nullptr;
-    double n_total = weighted ? c->src_wsum : (double)c->n;          // pi = m0 / N; with weights their sum
+    double n_total = weighted ? c->src.total(c->n) : (double)c->n;   // pi = m0 / N; with weights their sum
     if (c->comm_on()) HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_total, 1, 0));
     // E-step quantities of the initial parameters
     const bool one_pass = fullcov_one_pass(c, J16);
@@ -1046,7 +1036,8 @@ static int fullcov_estep(hgmm_ctx* c, bool weighted, int J, const double* pi, co
     HGMM_ENTER(c);
     if (!c || !pi || !mu || !cov) return c ? fail(c, HGMM_ERR_ARG, "NULL parameter table") : HGMM_ERR_ARG;
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "full-covariance E-step: set points first");
-    if (weighted) HGMM_TRY(fullcov_weights_ready(c, "hgmm_fullcov_estep_weighted"));
+    const double* wsrc = nullptr;
+    if (weighted) HGMM_TRY(source_weights_ready(c, "hgmm_fullcov_estep_weighted", &wsrc));
     if (J < 1 || J > 4096) return fail(c, HGMM_ERR_ARG, "J = %d outside 1..4096", J);
     HGMM_HIP(c, hipSetDevice(c->device));
     int J16 = 0, grid = 0;
@@ -1061,7 +1052,6 @@ static int fullcov_estep(hgmm_ctx* c, bool weighted, int J, const double* pi, co
                                                            c->t_cov.as<double>(), 0, J16, c->t_prep.as<double>(), flags_ptr(c));
     int* lab = c->t_current.as<int>();
     double q = 0.0;
-    const double* wsrc = weighted ? c->src_w.as<double>() : nullptr;
     if (fullcov_one_pass(c, J16)) {
         HGMM_TRY(fullcov_fused(c, J, J16, lab, &q, wsrc));
     } else {

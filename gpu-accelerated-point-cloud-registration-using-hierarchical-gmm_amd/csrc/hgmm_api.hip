@@ -777,8 +777,8 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->km_closest, &c->km_block, &c->km_centres, &c->km_ids, &c->km_rand, &c->km_labels,
                       &c->km_mind2, &c->km_partial, &c->km_out, &c->gt_buf, &c->t_momq, &c->t_flags, &c->exp_tab2, &c->t_tickets,
                       &c->fr_pi, &c->fr_mu, &c->fr_cov, &c->fr_prep, &c->fr_mom, &c->fr_clouds, &c->fr_q, &c->fr_trace, &c->fr_tg,
-                      &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w, &c->fr_tg_w,
-                      &c->src_w, &c->fr_src_w, &c->t_w2, &c->t_w3, &c->flat_sw, &c->f_lpn_rows,
+                      &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w.buf, &c->forest.tg_w.buf,
+                      &c->src.buf, &c->forest.src_w.buf, &c->t_w2, &c->t_w3, &c->flat_w.buf, &c->f_lpn_rows,
                       &c->vx_in, &c->vx_tab, &c->vx_keys, &c->vx_keys2, &c->vx_rows, &c->vx_rows2, &c->vx_heads, &c->vx_tmp,
                       &c->vx_cent, &c->vx_cnt, &c->vx_hand,
                       &c->fb_tab, &c->fb_params, &c->fb_pack, &c->fb_partials, &c->fb_lpn_partials, &c->fb_stats, &c->fb_lls, &c->fb_ctl,
@@ -903,9 +903,9 @@ void hgmm::bind_points(hgmm_ctx* c, hgmm_points* p) {
     c->flat.active = false;
     c->tree.nodes_ready = false;
     c->km_labels_n = -1;              // labels / distances of the previous cloud are void
-    c->src_weighted = false;          // hgmm_tree_set_source_weights[_batch]: the weights belonged to the previous cloud
-    c->forest.src_weighted = false;
-    c->flat_weighted = false;         // hgmm_flat_set_weights: likewise
+    c->src.drop();                    // the weights belonged to the previous cloud: hgmm_tree_set_source_weights ...
+    c->forest.src_w.drop();           // ... _batch ...
+    c->flat_w.drop();                 // ... and hgmm_flat_set_weights
     c->forest.src_counts.clear();
 }
 

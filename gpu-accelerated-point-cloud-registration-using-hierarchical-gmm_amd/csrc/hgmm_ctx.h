@@ -9,10 +9,12 @@
 #include <cstdio>
 #include <string>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/hgmm.h"
 #include "flat_pace.h"
+#include "point_weights.h"
 
 namespace hgmm {
 
@@ -29,6 +31,21 @@ struct DevBuf {
     size_t cap = 0;
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+
+// Per-point weights of a resident cloud or target -- or of the forest's B clouds / targets, back to back -- : the buffer,
+// whether it is in force, and the weights' sums (on the host in index order).  Consumers read ptr() and total() and nothing
+// else; the writers are upload_weights (tree_host.h), hgmm_flat_set_weights, the hand-overs of voxel_handover.hip and
+// whatever replaces the cloud or the target (drop).
+template <class T> struct WeightSet {
+    DevBuf buf;                       // T [n] or [n_pad], parallel to the points (a forest's unweighted member: 1.0 per point)
+    bool on = false;
+    std::vector<double> sums;         // (on) one per member, a serial set: one; an unweighted member: its count
+    const T* ptr() const { return on ? buf.as<T>() : nullptr; }                           // NULL: no weights in force
+    double total(int64_t n, int b = 0) const { return on ? sums[b] : (double)n; }          // what pi = m0 / W divides by
+    void drop() { on = false; }                                                            // (the buffer stays allocated)
+    void publish(std::vector<double> s) { sums = std::move(s); on = true; }
+};
+using MemberWeights = WeightSet<double>;     // (the forest's: B members)
 
 struct EventPair { hipEvent_t a, b; int kernel; };
 
@@ -64,7 +81,7 @@ struct FlatBatchMember {
     float* lls;                       // float [lls_cap]
     int* ctl;                         // int [16], the layout of f_ctl: stop (even), n_iter, converged, stop (odd); float prev at [8]
     const float* SW;                  // float [n] per-point weights of this SLOT (a handle owns none), or NULL: unweighted
-    double wn;                        // what flat_n() is to the serial launchers: the slot's weight sum S_b, or (double)n
+    double wn;                        // what flat_w.total(n) is to the serial launchers: the slot's weight sum S_b, or (double)n
 };
 // One slot of a batched fit as its entries hand it to the launch set (flat_batch_run, flat_kernels.hip): device pointers only.
 struct FlatBatchSlot {
@@ -171,11 +188,9 @@ struct ForestState {
     std::vector<double> tg_rmax;          // largest |x| per target
     int64_t tg_pad = 0;
     bool momq_clean = false;              // every word of fr_momq is zero (tree_host.h: MomqScope)
-    bool tg_weighted = false;             // hgmm_tree_set_target_weights_batch: fr_tg_w holds a weight per target point
-    std::vector<double> tg_wsum;          // (tg_weighted) sum of the weights per target; an unweighted pair: its count
+    MemberWeights tg_w;                   // hgmm_tree_set_target_weights_batch: [tg_pad] parallel to fr_tg; new targets drop them
     std::vector<int64_t> src_counts;      // hgmm_set_points_batch_*: the resident cloud's members (empty: not a batch cloud)
-    bool src_weighted = false;            // hgmm_tree_set_source_weights_batch: fr_src_w holds a weight per source point
-    std::vector<double> src_wsum;         // (src_weighted) sum of the weights per cloud; an unweighted cloud: its count
+    MemberWeights src_w;                  // hgmm_tree_set_source_weights_batch: [n_pad] parallel to x_soa64; a new cloud drops them
 };
 
 }  // namespace hgmm
@@ -208,19 +223,11 @@ struct hgmm_ctx {
     hgmm_points* bound = nullptr;     // nullptr: nothing resident yet
     bool have_f32 = false, have_f64 = false;
     int64_t n_pad = 0;
-    // per-point weights of the resident cloud (hgmm_tree_set_source_weights: the tree build alone reads them); whatever
-    // changes the resident cloud drops them (hgmm_api.hip: bind_points)
-    hgmm::DevBuf src_w;               // double [n_pad], parallel to x_soa64 (level-0 order)
-    bool src_weighted = false;        // src_w is in force
-    double src_wsum = 0.0;            // (src_weighted) sum of the weights, on the host in index order
-    // per-point weights of the resident cloud for the flat (diag / spherical) EM (hgmm_flat_set_weights); dropped with the
-    // cloud like src_w
-    hgmm::DevBuf flat_sw;             // float [n], parallel to the rows of x_aos
-    bool flat_weighted = false;       // flat_sw is in force
-    double flat_wsum = 0.0;           // (flat_weighted) S = sum of the float32 weights, float64 on the host in index order
+    // per-point weights of the resident cloud; whatever changes the resident cloud drops them (hgmm_api.hip: bind_points)
+    hgmm::WeightSet<double> src;      // [n_pad], parallel to x_soa64 (level-0 order): hgmm_tree_set_source_weights, read by the
+                                      // tree build, the weighted full-covariance fit and the weighted KMeans entries
+    hgmm::WeightSet<float> flat_w;    // [n], parallel to the rows of x_aos: hgmm_flat_set_weights, the flat (diag / spherical) EM
     hgmm::DevBuf f_lpn_rows;          // float [n] the rows' log-normalisers when a weighted E-step's caller brings no dev_lpn
-    double flat_n() const { return flat_weighted ? flat_wsum : (double)n; }     // what the flat M-step divides by
-    const float* flat_sw_ptr() const { return flat_weighted ? static_cast<const float*>(flat_sw.p) : nullptr; }
 
     // ---- flat EM ----------------------------------------------------------------
     hgmm::FlatState flat;
@@ -281,9 +288,8 @@ struct hgmm_ctx {
     hgmm::DevBuf tgt_soa64;                   // double [3][m_pad] registration target
     int64_t tgt_n = 0, tgt_pad = 0;
     double tgt_rmax = 0.0;                    // largest |x| of the target (extent bound of the fixed-point moments)
-    hgmm::DevBuf tgt_w;                       // double [m_pad] per-point weights of the target (hgmm_tree_set_target_weights)
-    bool tgt_weighted = false;                // tgt_w is in force (a new target drops it)
-    double tgt_wsum = 0.0;                    // (tgt_weighted) sum of the weights, on the host in index order
+    hgmm::WeightSet<double> tgt_w;            // [m_pad] per-point weights of the target (hgmm_tree_set_target_weights); a new
+                                              // target drops them
 
     // ---- forest (batched trees: tree_batch.hip) ------------------------------------
     hgmm::ForestState forest;
@@ -292,8 +298,6 @@ struct hgmm_ctx {
     hgmm::DevBuf fr_q;                        // double: the clouds' shares of q
     hgmm::DevBuf fr_trace;                    // double [B][L][trace_cap]
     hgmm::DevBuf fr_tg;                       // double [3][tg_pad] the targets, back to back
-    hgmm::DevBuf fr_tg_w;                     // double [tg_pad] their weights (forest.tg_weighted; 1.0 for an unweighted pair)
-    hgmm::DevBuf fr_src_w;                    // double [n_pad] the source clouds' weights (forest.src_weighted; 1.0 for an unweighted cloud)
     hgmm::DevBuf fr_momq;                     // uint64 [B T][4] registration sums
     hgmm::DevBuf ff_clocks;                   // int64 [8][4] phase clocks of the one-pass full-covariance kernels (armed: ff_clocks_on)
     bool ff_clocks_on = false;
@@ -432,6 +436,31 @@ inline int fail(hgmm_ctx* c, int code, const char* fmt, ...) {
     va_end(ap);
     if (c) c->err = buf;
     return code;
+}
+
+// scan_weights (point_weights.h) of the n weights at w; a refusal in the weight entries' words, under the caller's `label`
+template <class T>
+inline int check_point_weights(hgmm_ctx* c, const char* label, const T* w, int64_t n, double* sum_out) {
+    const WeightScan s = scan_weights(w, n);
+    if (s.verdict == WEIGHTS_BAD_VALUE)
+        return fail(c, HGMM_ERR_ARG, "%s: weight %lld is %g (weights must be finite and >= 0)", label, (long long)s.index, s.value);
+    if (s.verdict == WEIGHTS_ALL_ZERO) return fail(c, HGMM_ERR_ARG, "%s: all %lld weights are zero", label, (long long)n);
+    if (s.verdict == WEIGHTS_SUM_NOT_FINITE) return fail(c, HGMM_ERR_ARG, "%s: the weights' sum is not finite", label);
+    *sum_out = s.sum;
+    return HGMM_OK;
+}
+
+// The _weighted entries of the full-covariance fit and of KMeans: their own refusals (include/hgmm.h), made before anything
+// resident is touched; on success *wts is the resident source-weight array [n_pad], on the row index of x_soa64
+inline int source_weights_ready(hgmm_ctx* c, const char* what, const double** wts) {
+    if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "%s: set points first", what);
+    if (!c->src.ptr() || c->src.buf.cap < sizeof(double) * (size_t)c->n_pad)
+        return fail(c, HGMM_ERR_STATE, "%s: no source weights are resident (set them with hgmm_tree_set_source_weights or "
+                    "hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE), or call the unweighted entry)", what);
+    if (c->comm_on())
+        return fail(c, HGMM_ERR_STATE, "%s: the context has a communicator; sharded weighted fits are not supported", what);
+    *wts = c->src.ptr();
+    return HGMM_OK;
 }
 
 #define HGMM_HIP(ctx, call)                                                              \

@@ -720,19 +720,6 @@ static int km_check(hgmm_ctx* c, int k) {
     return HGMM_OK;
 }
 
-// The _weighted entries' own refusals (include/hgmm.h), made before anything resident is touched; on success *wts is the
-// context's source-weight array [n_pad], on the row index of x_soa64
-static int km_weights_ready(hgmm_ctx* c, const char* what, const double** wts) {
-    if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "%s: set points first", what);
-    if (!c->src_weighted || !c->src_w.p || c->src_w.cap < sizeof(double) * (size_t)c->n_pad)
-        return fail(c, HGMM_ERR_STATE, "%s: no source weights are resident (set them with hgmm_tree_set_source_weights or "
-                    "hgmm_voxel_to_points(..., HGMM_VOXEL_W_TREE), or call the unweighted entry)", what);
-    if (c->comm_on())
-        return fail(c, HGMM_ERR_STATE, "%s: the context has a communicator; sharded weighted fits are not supported", what);
-    *wts = c->src_w.as<double>();
-    return HGMM_OK;
-}
-
 }  // namespace hgmm
 
 using namespace hgmm;
@@ -770,7 +757,7 @@ static int km_plusplus(hgmm_ctx* c, bool weighted, int k, int64_t first_id, cons
                        int64_t* ids_out, double* centers_out) {
     HGMM_ENTER(c);
     const double* wts = nullptr;
-    if (weighted) HGMM_TRY(km_weights_ready(c, "hgmm_kmeans_plusplus_weighted", &wts));
+    if (weighted) HGMM_TRY(source_weights_ready(c, "hgmm_kmeans_plusplus_weighted", &wts));
     HGMM_TRY(km_check(c, k));
     if (weighted && (km_nblk(c->n, KM_BLOCK) + KM_GROUP - 1) / KM_GROUP > (unsigned)KM_TAIL_LDS_GROUPS)
         return fail(c, HGMM_ERR_ARG, "hgmm_kmeans_plusplus_weighted: %lld points exceed the one-launch-per-centre seeding form "
@@ -1010,7 +997,7 @@ static int km_step(hgmm_ctx* c, bool weighted, int k, const double* centers, int
                    double* sums_out, double* inertia_out, int64_t* n_changed_out) {
     HGMM_ENTER(c);
     const double* wts = nullptr;
-    if (weighted) HGMM_TRY(km_weights_ready(c, "hgmm_kmeans_step_weighted", &wts));
+    if (weighted) HGMM_TRY(source_weights_ready(c, "hgmm_kmeans_step_weighted", &wts));
     HGMM_TRY(km_check(c, k));
     if (!centers) return fail(c, HGMM_ERR_ARG, "kmeans: centers is NULL");
     KmLaunch L;
@@ -1046,7 +1033,7 @@ static int km_lloyd(hgmm_ctx* c, bool weighted, int k, double* centers_inout, in
                     double* sums_out, int64_t* n_changed_out) {
     HGMM_ENTER(c);
     const double* wts = nullptr;
-    if (weighted) HGMM_TRY(km_weights_ready(c, "hgmm_kmeans_lloyd_weighted", &wts));
+    if (weighted) HGMM_TRY(source_weights_ready(c, "hgmm_kmeans_lloyd_weighted", &wts));
     HGMM_TRY(km_check(c, k));
     if (!centers_inout) return fail(c, HGMM_ERR_ARG, "kmeans: centers is NULL");
     if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "kmeans: the device-resident Lloyd loop is single-rank; "

@@ -282,8 +282,8 @@ __global__ __launch_bounds__(CH) void forest_score_finish_kernel(const double* _
                                                                  double* __restrict__ summary) {
     const int b = blockIdx.x;
     const int count = tab[b].tg_count;
-    // (tg_wsum: the target's weight sum, (double)count without weights -- reg_pair)
-    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * b, (count + CH - 1) / CH, tab[b].tg_wsum, summary + 8 * b);
+    // (tg_wtotal: the target's weight sum, (double)count without weights -- reg_pair)
+    tree_score_finish_body(partial + (size_t)SCORE_NSUM * gx * b, (count + CH - 1) / CH, tab[b].tg_wtotal, summary + 8 * b);
 }
 
 template <bool SHARED>
@@ -613,8 +613,8 @@ static int tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, do
                                   (long long)sum, (long long)n);
     }
     // hgmm_tree_set_source_weights_batch: the WEIGHTED instantiations, the weights on the coordinates' ping-pong
-    const bool weighted = c->forest.src_weighted;
-    if (weighted && (c->forest.src_counts.size() != (size_t)B || !std::equal(counts, counts + B, c->forest.src_counts.begin())))
+    const double* wsrc = c->forest.src_w.ptr();
+    if (wsrc && (c->forest.src_counts.size() != (size_t)B || !std::equal(counts, counts + B, c->forest.src_counts.begin())))
         return fail(c, HGMM_ERR_ARG, "tree build (batch): the resident source weights were set for other cloud sizes");
     const int64_t T = level_first(L);
     const int64_t TT = T * B;
@@ -642,7 +642,7 @@ static int tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, do
     HGMM_TRY(ensure(c, c->fr_trace, sizeof(double) * (size_t)trace_cap * L * B));
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * 3 * TT));
     BuildWorkspace ws;
-    HGMM_TRY(ws.take(c, n, n_pad, maxP, L, c->x_soa64.as<double>(), weighted ? c->fr_src_w.as<double>() : nullptr));
+    HGMM_TRY(ws.take(c, n, n_pad, maxP, L, c->x_soa64.as<double>(), wsrc));
     HandOver* hand = nullptr;
     HGMM_TRY(hand_over(c, B, &hand));
     const HostDev<unsigned long long> words = hand->progress(0);
@@ -692,7 +692,7 @@ static int tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, do
             // (level 0: the E-step stores the shares, one per chunk -- a cloud's chunks are consecutive, TreeEstepArgs::q_shares)
             fc.q_count = (l == 0 || chunks > 1) ? (int)nblk(counts[b], CH) : llblocks;
             q_at += fc.q_count;
-            fc.n_total = weighted ? c->forest.src_wsum[b] : (double)counts[b];     // (an unweighted member: its count)
+            fc.n_total = c->forest.src_w.total(counts[b], b);                      // (an unweighted member: its count)
             ll_stride = std::max(ll_stride, llblocks);
         }
         if (l == 0) ll_stride = 0;                              // no log-likelihood workgroups at level 0
@@ -714,7 +714,7 @@ static int tree_build_batch(hgmm_ctx* c, int B, const int64_t* counts, int L, do
             // partition for the next level
             forest_hist_kernel<<<lv.grid_chunks, CH, 0, c->stream>>>(ws.cur[0], ws.cur[1], ws.chunk_desc, ws.n_chunks_dev, ws.hist, lv.fa);
             tree_offsets_kernel<<<P, OFF_BLOCK, 0, c->stream>>>(ws.hist, ws.chunk_first, ws.seg, P, ws.chunk_off, ws.seg_next);
-            const auto scatter = kernel_for<ForestScatterFamily>(weighted);
+            const auto scatter = kernel_for<ForestScatterFamily>(wsrc != nullptr);
             scatter<<<lv.grid_chunks, CH, 0, c->stream>>>(ws.xs, n_pad, ws.cur[0], ws.cur[1], ws.chunk_desc, ws.n_chunks_dev,
                                                           ws.chunk_off, ws.xs_next, lv.fa, ws.w, ws.w_next);
             if (hipGetLastError() != hipSuccess) { rc = fail(c, HGMM_ERR_HIP, "tree build (batch): partition launch failed"); break; }
@@ -796,9 +796,7 @@ template <class IN>
 static int set_targets_batch(hgmm_ctx* c, int B, const IN* const* xyz, const int64_t* counts) {
     HGMM_ENTER(c);
     if (B < 1 || B > 4096 || !xyz || !counts) return fail(c, HGMM_ERR_ARG, "targets (batch): B = %d", B);
-    ForestState& F = c->forest;
-    F.tg_B = 0;
-    F.tg_weighted = false;                                 // (hgmm_tree_set_target_weights_batch: new targets drop the weights)
+    forest_targets_begin(c);
     int64_t total = 0, longest = 0;
     for (int b = 0; b < B; ++b) {
         if (!xyz[b] || counts[b] < 1) return fail(c, HGMM_ERR_ARG, "targets (batch): target %d is empty", b);
@@ -813,12 +811,9 @@ static int set_targets_batch(hgmm_ctx* c, int B, const IN* const* xyz, const int
     HGMM_TRY(reg_table(c, c->fr_reg, B, &tb));
     unsigned long long* r2bits = tb.r2max;
     HGMM_HIP(c, hipMemsetAsync(r2bits, 0, sizeof(unsigned long long) * B, c->stream));
-    F.tg_counts.assign(counts, counts + B);
-    F.tg_first.assign(B, 0);
     int64_t at = 0;
     IN* stage = c->scratch.as<IN>();
     for (int b = 0; b < B; ++b) {
-        F.tg_first[b] = at;
         HGMM_HIP(c, hipMemcpyAsync(stage + 3 * at, xyz[b], sizeof(IN) * 3 * (size_t)counts[b], hipMemcpyHostToDevice, c->stream));
         forest_target_kernel<IN><<<nblk(counts[b], 256), 256, 0, c->stream>>>(stage + 3 * at, counts[b], at, pad, c->fr_tg.as<double>(),
                                                                              r2bits + b);
@@ -831,14 +826,7 @@ static int set_targets_batch(hgmm_ctx* c, int B, const IN* const* xyz, const int
         dl.add(bits.data(), r2bits, sizeof(unsigned long long) * B);
         HGMM_HIP(c, dl.finish());
     }
-    F.tg_rmax.resize(B);
-    for (int b = 0; b < B; ++b) {
-        double r2;
-        std::memcpy(&r2, &bits[b], sizeof r2);
-        F.tg_rmax[b] = std::sqrt(r2);
-    }
-    F.tg_pad = pad;
-    F.tg_B = B;
+    forest_targets_publish(c, B, counts, bits.data(), pad, nullptr);
     return HGMM_OK;
 }
 
@@ -849,34 +837,30 @@ extern "C" int hgmm_tree_set_targets_batch_f32(hgmm_ctx* c, int B, const float* 
     return set_targets_batch<float>(c, B, xyz, counts);
 }
 
-// per-point weights of the resident targets (include/hgmm.h): fr_tg_w [tg_pad] parallel to fr_tg (upload_weights)
+// per-point weights of the resident targets (include/hgmm.h): forest.tg_w [tg_pad] parallel to fr_tg (upload_weights)
 extern "C" int hgmm_tree_set_target_weights_batch(hgmm_ctx* c, int B, const double* const* w, const int64_t* counts) {
     HGMM_ENTER(c);
     const char* what = "hgmm_tree_set_target_weights_batch";
     ForestState& F = c->forest;
     if (F.tg_B < 1) return fail(c, HGMM_ERR_STATE, "%s: no targets (call hgmm_tree_set_targets_batch first)", what);
-    if (!w) { F.tg_weighted = false; return HGMM_OK; }
+    if (!w) { F.tg_w.drop(); return HGMM_OK; }
     if (B != F.tg_B) return fail(c, HGMM_ERR_ARG, "%s: B = %d, but %d targets are resident", what, B, F.tg_B);
     if (!counts) return fail(c, HGMM_ERR_ARG, "%s: counts is NULL", what);
-    F.tg_wsum.resize(B);                               // (sums in force have this length already: they keep their values)
-    return upload_weights(c, what, "target", true, B, w, counts, F.tg_counts.data(), F.tg_pad, c->fr_tg_w, F.tg_wsum.data(),
-                          &F.tg_weighted);
+    return upload_weights(c, what, "target", true, B, w, counts, F.tg_counts.data(), F.tg_pad, F.tg_w);
 }
 
-// per-point weights of the resident forest cloud (include/hgmm.h): fr_src_w [n_pad] parallel to x_soa64 (upload_weights)
+// per-point weights of the resident forest cloud (include/hgmm.h): forest.src_w [n_pad] parallel to x_soa64 (upload_weights)
 extern "C" int hgmm_tree_set_source_weights_batch(hgmm_ctx* c, int B, const double* const* w, const int64_t* counts) {
     HGMM_ENTER(c);
     const char* what = "hgmm_tree_set_source_weights_batch";
     ForestState& F = c->forest;
     if (!c->have_f64 || c->n <= 0 || F.src_counts.empty())
         return fail(c, HGMM_ERR_STATE, "%s: no forest cloud (call hgmm_set_points_batch_f64 / _f32 first)", what);
-    if (!w) { F.src_weighted = false; return HGMM_OK; }
+    if (!w) { F.src_w.drop(); return HGMM_OK; }
     if (B != (int)F.src_counts.size())
         return fail(c, HGMM_ERR_ARG, "%s: B = %d, but %d clouds are resident", what, B, (int)F.src_counts.size());
     if (!counts) return fail(c, HGMM_ERR_ARG, "%s: counts is NULL", what);
-    F.src_wsum.resize(B);                              // (sums in force have this length already: they keep their values)
-    return upload_weights(c, what, "cloud", true, B, w, counts, F.src_counts.data(), c->n_pad, c->fr_src_w, F.src_wsum.data(),
-                          &F.src_weighted);
+    return upload_weights(c, what, "cloud", true, B, w, counts, F.src_counts.data(), c->n_pad, F.src_w);
 }
 
 extern "C" int hgmm_tree_register_batch(hgmm_ctx* c, int B, double* rot, double* t, double scale, double lambda_c,

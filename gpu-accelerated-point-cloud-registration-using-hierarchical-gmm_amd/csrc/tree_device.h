@@ -2161,7 +2161,7 @@ struct ForestRegPair {
     int active, pad;
     double q_prev, tg_rmax, mu_rmax;     // q of the previous iteration (valid with has_q), extent bounds of the encoding
     int has_q, it, status, pad2;         // iterations done; 0: running / budget used up, 1: |dq| < tol, 2: ill-conditioned
-    double tg_wsum;                      // n_all of reg_encoding: the sum of the target's weights, (double)tg_count without weights
+    double tg_wtotal;                    // n_all of reg_encoding: the sum of the target's weights, (double)tg_count without weights
 };
 
 // The host side of a registration iteration (reg_host_step) done by ONE device thread (per-context option
@@ -2259,7 +2259,7 @@ __device__ inline void reg_device_step(const double* __restrict__ o, ForestRegPa
     if (stop || it + 1 >= max_iter) { pr->active = 0; return; }
     double D = 1.0;
     int F = 0;
-    reg_encoding(reg_extent(tf, pr->tg_rmax, pr->mu_rmax), pr->tg_wsum, &D, &F);
+    reg_encoding(reg_extent(tf, pr->tg_rmax, pr->mu_rmax), pr->tg_wtotal, &D, &F);
     pr->inv_d = 1.0 / D;
     pr->fix_scale = ldexp(1.0, F);
     pr->d_ext = D;

@@ -305,11 +305,10 @@ inline RegSet reg_set_forest(hgmm_ctx* c) {
     const ForestState& F = c->forest;
     RegSet s;
     for (int b = 0; b < F.B; ++b)
-        s.regs.push_back({F.tg_first[b], F.tg_counts[b], F.tg_rmax[b], F.mu_rmax[b],
-                          F.tg_weighted ? F.tg_wsum[b] : (double)F.tg_counts[b]});
+        s.regs.push_back({F.tg_first[b], F.tg_counts[b], F.tg_rmax[b], F.mu_rmax[b], F.tg_w.total(F.tg_counts[b], b)});
     s.tg = c->fr_tg.as<double>();
     s.tg_pad = F.tg_pad;
-    s.w = F.tg_weighted ? c->fr_tg_w.as<double>() : nullptr;
+    s.w = F.tg_w.ptr();
     s.prep = c->fr_prep.as<double>();
     s.T = F.T;
     s.L = F.L;
@@ -325,10 +324,10 @@ inline RegSet reg_set_forest(hgmm_ctx* c) {
 inline RegSet reg_set_pair(hgmm_ctx* c, int K, bool multi) {
     RegSet s;
     s.shared_tree = true;
-    s.regs.assign(K, {0, c->tgt_n, c->tgt_rmax, c->tree.mu_rmax, c->tgt_weighted ? c->tgt_wsum : (double)c->tgt_n});
+    s.regs.assign(K, {0, c->tgt_n, c->tgt_rmax, c->tree.mu_rmax, c->tgt_w.total(c->tgt_n)});
     s.tg = c->tgt_soa64.as<double>();
     s.tg_pad = c->tgt_pad;
-    s.w = c->tgt_weighted ? c->tgt_w.as<double>() : nullptr;
+    s.w = c->tgt_w.ptr();
     s.prep = c->t_prep.as<double>();
     s.T = c->tree.T;
     s.L = c->tree.L;
@@ -365,7 +364,7 @@ inline ForestRegPair reg_pair(const RegSet::One& r) {
     std::memset(&pr, 0, sizeof pr);
     pr.tg_first = (int)r.first;
     pr.tg_count = (int)r.count;
-    pr.tg_wsum = r.wsum;
+    pr.tg_wtotal = r.wsum;
     return pr;
 }
 // ... of one that takes part: its transform and the fixed-point encoding of its next E-step
@@ -374,7 +373,7 @@ inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, const RegSet::One&
     pr.tf = tf;
     double D = 1.0;
     int F = 0;
-    reg_encoding(reg_extent(tf, r.rmax, r.mu_rmax), pr.tg_wsum, &D, &F);
+    reg_encoding(reg_extent(tf, r.rmax, r.mu_rmax), pr.tg_wtotal, &D, &F);
     pr.inv_d = 1.0 / D;
     pr.fix_scale = std::ldexp(1.0, F);
     pr.d_ext = D;
@@ -382,14 +381,78 @@ inline void reg_pair_fill(ForestRegPair& pr, const Rigid& tf, const RegSet::One&
     pr.tg_rmax = r.rmax;
     pr.mu_rmax = r.mu_rmax;
 }
-// (tree_kernels.hip) what the four weight entries (hgmm_tree_set_target_weights[_batch], hgmm_tree_set_source_weights[_batch])
-// do once their own state checks have passed and w is not NULL.  `what`: the entry's name; `noun`: "target" / "cloud";
-// batch: the messages name the member (the serial entries: B = 1, no index).  The B members lie back to back in an array of
-// `pad` doubles, resident[b] points each.  In this order: counts[b] against resident[b]; every w[b] finite, >= 0 and not
-// all zero (a NULL member: 1.0 per point, its count as the sum -- gamma * 1.0 is gamma, so it keeps its unweighted bits);
-// a refusal up to here leaves the previous weights in force.  Then *in_force = false: what is left to fail is the device,
-// and then no weights are in force.  Upload into `dst`; sums[B] and *in_force = true (all members NULL: stays false).
-int upload_weights(hgmm_ctx* c, const char* what, const char* noun, bool batch, int B, const double* const* w,
-                   const int64_t* counts, const int64_t* resident, int64_t pad, DevBuf& dst, double* sums, bool* in_force);
+// What the four weight entries (hgmm_tree_set_target_weights[_batch], hgmm_tree_set_source_weights[_batch]) do once their own
+// state checks have passed and w is not NULL.  `what`: the entry's name; `noun`: "target" / "cloud"; batch: the messages name
+// the member (the serial entries: B = 1, no index).  The B members lie back to back in an array of `pad` doubles, resident[b]
+// points each.  In this order: counts[b] against resident[b]; every w[b] finite, >= 0 and not all zero (a NULL member: 1.0
+// per point, its count as the sum -- gamma * 1.0 is gamma, so it keeps its unweighted bits); a refusal up to here leaves the
+// previous weights in force.  Then set.drop(): what is left to fail is the device, and then no weights are in force.  Upload
+// into set.buf and publish the sums (all members NULL: the set stays off).
+inline int upload_weights(hgmm_ctx* c, const char* what, const char* noun, bool batch, int B, const double* const* w,
+                   const int64_t* counts, const int64_t* resident, int64_t pad, WeightSet<double>& set) {
+    std::vector<double> sum(B), padded((size_t)pad, 0.0);
+    bool any = false;
+    int64_t at = 0;
+    for (int b = 0; b < B; at += counts[b], ++b) {
+        if (counts[b] != resident[b])
+            return batch ? fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident %s %d has %lld points", what, b,
+                                (long long)counts[b], noun, b, (long long)resident[b])
+                         : fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident %s has %lld points", what,
+                                (long long)counts[b], noun, (long long)resident[b]);
+        double* slot = padded.data() + at;
+        if (!w[b]) {
+            std::fill(slot, slot + counts[b], 1.0);
+            sum[b] = (double)counts[b];
+            continue;
+        }
+        char label[96];
+        if (batch) snprintf(label, sizeof label, "%s (%s %d)", what, noun, b);
+        HGMM_TRY(check_point_weights(c, batch ? label : what, w[b], counts[b], &sum[b]));
+        std::copy(w[b], w[b] + counts[b], slot);
+        any = true;
+    }
+    set.drop();
+    if (!any) return HGMM_OK;
+    HGMM_TRY(ensure(c, set.buf, sizeof(double) * padded.size()));
+    HGMM_HIP(c, hipMemcpyAsync(set.buf.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, ctx_stream_sync(c));
+    set.publish(sum);
+    return HGMM_OK;
+}
+
+// ---- a new target: begin, the upload or hand-over launches of the caller, publish -----------------------------------------
+// the serial target (hgmm_tree_set_target, hgmm_voxel_to_target).  From begin on a failure leaves no target, and the previous
+// target's weights are gone whatever happens.  publish: n points in tgt_soa64 [3][pad], r2max their largest |x|^2; wsum: the
+// sum of the weights the caller has put into tgt_w.buf, NULL: none
+inline void target_begin(hgmm_ctx* c) { c->tgt_n = 0; c->tgt_w.drop(); }
+inline void target_publish(hgmm_ctx* c, int64_t n, int64_t pad, double r2max, const double* wsum) {
+    c->tgt_rmax = std::sqrt(r2max);
+    c->tgt_n = n;
+    c->tgt_pad = pad;
+    if (wsum) c->tgt_w.publish({*wsum});
+}
+inline double r2_of_bits(unsigned long long bits) {        // (forest_target_kernel / handover_kernel: bits of a double >= 0)
+    double r2;
+    std::memcpy(&r2, &bits, sizeof r2);
+    return r2;
+}
+// the forest's targets (hgmm_tree_set_targets_batch[_f32], hgmm_voxel_to_targets_batch), likewise: B targets of counts[b]
+// points back to back in fr_tg [3][pad], r2bits[b] the bits of their largest |x|^2, wsums [B] or NULL
+inline void forest_targets_begin(hgmm_ctx* c) { c->forest.tg_B = 0; c->forest.tg_w.drop(); }
+inline void forest_targets_publish(hgmm_ctx* c, int B, const int64_t* counts, const unsigned long long* r2bits, int64_t pad,
+                                   const double* wsums) {
+    ForestState& F = c->forest;
+    F.tg_counts.assign(counts, counts + B);
+    F.tg_first.resize((size_t)B);
+    F.tg_rmax.resize((size_t)B);
+    int64_t at = 0;
+    for (int b = 0; b < B; at += counts[b], ++b) {
+        F.tg_first[b] = at;
+        F.tg_rmax[b] = std::sqrt(r2_of_bits(r2bits[b]));
+    }
+    F.tg_pad = pad;
+    F.tg_B = B;
+    if (wsums) F.tg_w.publish(std::vector<double>(wsums, wsums + B));
+}
 
 }  // namespace hgmm

@@ -823,7 +823,8 @@ static int tree_build(hgmm_ctx* c, int L, double ls, double ld, const double* in
                             (long long)j, (long long)init_rows[j], (long long)c->n);
     if (c->n > 0x7fffffff - 1024) return fail(c, HGMM_ERR_ARG, "too many points for 32-bit indices");
     // hgmm_tree_set_source_weights: the WEIGHTED instantiations of the level's kernels, the weights on the coordinates' ping-pong
-    const bool weighted = c->src_weighted;
+    const double* wsrc = c->src.ptr();
+    const bool weighted = wsrc != nullptr;
     if (weighted && c->comm_on())
         return fail(c, HGMM_ERR_STATE, "tree build: source weights are resident and the context has a communicator; sharded "
                     "weighted builds are not supported (hgmm_tree_set_source_weights(ctx, NULL, 0) takes the weights off)");
@@ -838,7 +839,7 @@ static int tree_build(hgmm_ctx* c, int L, double ls, double ld, const double* in
     int64_t maxP = 1;
     for (int i = 0; i < L - 1; ++i) maxP *= 8;                 // parents at the last level
     BuildWorkspace ws;
-    HGMM_TRY(ws.take(c, n, n_pad, maxP, L, c->x_soa64.as<double>(), weighted ? c->src_w.as<double>() : nullptr));
+    HGMM_TRY(ws.take(c, n, n_pad, maxP, L, c->x_soa64.as<double>(), wsrc));
     HGMM_TRY(ensure(c, c->scratch, sizeof(double) * 3 * T));
     HGMM_TRY(ensure(c, c->t_perm, sizeof(int) * 2 * n_pad));                 // ping-pong
     HGMM_TRY(ensure(c, c->t_q, sizeof(double) * (nblk(n, CH) + 8)));
@@ -862,7 +863,7 @@ static int tree_build(hgmm_ctx* c, int L, double ls, double ld, const double* in
     HGMM_HIP(c, hipGetLastError());
 
     // global point count (pi = m0 / N_total); with weights their sum: point i counts as w_i points
-    double n_total = weighted ? c->src_wsum : (double)n;
+    double n_total = c->src.total(n);
     if (c->comm_on()) HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_total, 1, 0));
 
     std::vector<int> level_iters(L, 0);
@@ -1004,6 +1005,7 @@ extern "C" int hgmm_tree_set_target(hgmm_ctx* c, const double* xyz, int64_t n) {
     if (n <= 0) return fail(c, HGMM_ERR_ARG, "target must have at least one point");
     HGMM_HIP(c, hipSetDevice(c->device));
     const int64_t n_pad = (n + 255) / 256 * 256;
+    target_begin(c);
     HGMM_TRY(ensure(c, c->tgt_soa64, sizeof(double) * 3 * n_pad));
     std::vector<double> soa((size_t)3 * n_pad, 0.0);
     double r2max = 0.0;                                         // largest |x|^2: bounds the extent of the moved cloud
@@ -1012,61 +1014,9 @@ extern "C" int hgmm_tree_set_target(hgmm_ctx* c, const double* xyz, int64_t n) {
         for (int d = 0; d < 3; ++d) { soa[(size_t)d * n_pad + i] = xyz[3 * i + d]; r2 += xyz[3 * i + d] * xyz[3 * i + d]; }
         if (r2 > r2max) r2max = r2;
     }
-    c->tgt_rmax = std::sqrt(r2max);
     HGMM_HIP(c, hipMemcpyAsync(c->tgt_soa64.p, soa.data(), sizeof(double) * soa.size(), hipMemcpyHostToDevice, c->stream));
     HGMM_HIP(c, ctx_stream_sync(c));
-    c->tgt_n = n;
-    c->tgt_pad = n_pad;
-    c->tgt_weighted = false;                                    // (hgmm_tree_set_target_weights: a new target drops them)
-    return HGMM_OK;
-}
-
-// what the weight entries ask of one cloud's weights: finite, >= 0, not all zero; *sum_out: their sum in index order
-static int check_weights(hgmm_ctx* c, const char* what, const double* w, int64_t n, double* sum_out) {
-    double sum = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (!(w[i] >= 0.0) || !(w[i] < INFINITY))                 // (NaN fails the first comparison)
-            return fail(c, HGMM_ERR_ARG, "%s: weight %lld is %g (weights must be finite and >= 0)", what, (long long)i, w[i]);
-        sum += w[i];
-    }
-    if (!(sum > 0.0)) return fail(c, HGMM_ERR_ARG, "%s: all %lld weights are zero", what, (long long)n);
-    if (!(sum < INFINITY)) return fail(c, HGMM_ERR_ARG, "%s: the weights' sum is not finite", what);
-    *sum_out = sum;
-    return HGMM_OK;
-}
-
-// tree_host.h
-int hgmm::upload_weights(hgmm_ctx* c, const char* what, const char* noun, bool batch, int B, const double* const* w,
-                         const int64_t* counts, const int64_t* resident, int64_t pad, DevBuf& dst, double* sums, bool* in_force) {
-    std::vector<double> sum(B), padded((size_t)pad, 0.0);
-    bool any = false;
-    int64_t at = 0;
-    for (int b = 0; b < B; at += counts[b], ++b) {
-        if (counts[b] != resident[b])
-            return batch ? fail(c, HGMM_ERR_ARG, "%s: counts[%d] = %lld, but the resident %s %d has %lld points", what, b,
-                                (long long)counts[b], noun, b, (long long)resident[b])
-                         : fail(c, HGMM_ERR_ARG, "%s: %lld weights, but the resident %s has %lld points", what,
-                                (long long)counts[b], noun, (long long)resident[b]);
-        double* slot = padded.data() + at;
-        if (!w[b]) {
-            std::fill(slot, slot + counts[b], 1.0);
-            sum[b] = (double)counts[b];
-            continue;
-        }
-        char label[96];
-        if (batch) snprintf(label, sizeof label, "%s (%s %d)", what, noun, b);
-        HGMM_TRY(check_weights(c, batch ? label : what, w[b], counts[b], &sum[b]));
-        std::copy(w[b], w[b] + counts[b], slot);
-        any = true;
-    }
-    // (the arguments are good from here on: what is left to fail is the device, and then no weights are in force)
-    *in_force = false;
-    if (!any) return HGMM_OK;
-    HGMM_TRY(ensure(c, dst, sizeof(double) * padded.size()));
-    HGMM_HIP(c, hipMemcpyAsync(dst.p, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice, c->stream));
-    HGMM_HIP(c, ctx_stream_sync(c));
-    std::copy(sum.begin(), sum.end(), sums);
-    *in_force = true;
+    target_publish(c, n, n_pad, r2max, nullptr);
     return HGMM_OK;
 }
 
@@ -1075,17 +1025,17 @@ extern "C" int hgmm_tree_set_target_weights(hgmm_ctx* c, const double* w, int64_
     HGMM_ENTER(c);
     const char* what = "hgmm_tree_set_target_weights";
     if (c->tgt_n <= 0) return fail(c, HGMM_ERR_STATE, "%s: no target (call hgmm_tree_set_target first)", what);
-    if (!w) { c->tgt_weighted = false; return HGMM_OK; }
-    return upload_weights(c, what, "target", false, 1, &w, &n, &c->tgt_n, c->tgt_pad, c->tgt_w, &c->tgt_wsum, &c->tgt_weighted);
+    if (!w) { c->tgt_w.drop(); return HGMM_OK; }
+    return upload_weights(c, what, "target", false, 1, &w, &n, &c->tgt_n, c->tgt_pad, c->tgt_w);
 }
 
-// per-point weights of the resident cloud (include/hgmm.h): src_w [n_pad] parallel to x_soa64; hgmm_tree_build alone reads them
+// per-point weights of the resident cloud (include/hgmm.h): src [n_pad] parallel to x_soa64; hgmm_tree_build alone reads them
 extern "C" int hgmm_tree_set_source_weights(hgmm_ctx* c, const double* w, int64_t n) {
     HGMM_ENTER(c);
     const char* what = "hgmm_tree_set_source_weights";
     if (!c->have_f64 || c->n <= 0) return fail(c, HGMM_ERR_STATE, "%s: no cloud (set or bind points first)", what);
-    if (!w) { c->src_weighted = false; return HGMM_OK; }
-    return upload_weights(c, what, "cloud", false, 1, &w, &n, &c->n, c->n_pad, c->src_w, &c->src_wsum, &c->src_weighted);
+    if (!w) { c->src.drop(); return HGMM_OK; }
+    return upload_weights(c, what, "cloud", false, 1, &w, &n, &c->n, c->n_pad, c->src);
 }
 
 // fixed-point moments of the resident target under (rot, t, scale) -> c->t_momq [T][NMQ] (all-reduced over the
@@ -1106,7 +1056,7 @@ static int reg_estep_fixed(hgmm_ctx* c, MomqScope& sums, const double* rot, cons
         HGMM_TRY(hgmm_comm_allreduce_f64(c, &e, 1, 1));
         ext = e;
     }
-    double n_all = c->tgt_weighted ? c->tgt_wsum : (double)c->tgt_n;     // (weights: this rank's shard's, like its points)
+    double n_all = c->tgt_w.total(c->tgt_n);                             // (weights: this rank's shard's, like its points)
     if (c->comm_on()) HGMM_TRY(hgmm_comm_allreduce_f64(c, &n_all, 1, 0));
     double D = 1.0;
     int F = 0;
@@ -1116,11 +1066,11 @@ static int reg_estep_fixed(hgmm_ctx* c, MomqScope& sums, const double* rot, cons
     {
         ProfScope prof(c, HGMM_K_TREE_REG);
         const double gate = c->tree.reg_gate;
-        const auto kernel = tree_reg_estep_kernel_for<NMQ>(std::isfinite(gate), c->tgt_weighted);
+        const double* w = c->tgt_w.ptr();
+        const auto kernel = tree_reg_estep_kernel_for<NMQ>(std::isfinite(gate), w != nullptr);
         kernel<<<nblk(c->tgt_n, CH), CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), c->tgt_n, c->tgt_pad, tf,
                                                          c->t_prep.as<double>(), c->tree.L, lambda_c, 1.0 / D,
-                                                         std::ldexp(1.0, F), mq, gate,
-                                                         c->tgt_weighted ? c->tgt_w.as<double>() : nullptr);
+                                                         std::ldexp(1.0, F), mq, gate, w);
     }
     HGMM_HIP(c, hipGetLastError());
     if (c->comm_on()) HGMM_TRY(allreduce_i64_dev(c, reinterpret_cast<long long*>(mq), (size_t)NMQ * T));
@@ -1249,12 +1199,12 @@ extern "C" int hgmm_tree_score(hgmm_ctx* c, const double* rot, const double* t, 
     int32_t* d_node = node_out ? reinterpret_cast<int32_t*>(at) : nullptr;
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
-        const auto kernel = c->tgt_weighted ? tree_score_kernel<true> : tree_score_kernel<false>;
+        const double* w = c->tgt_w.ptr();
+        const auto kernel = w ? tree_score_kernel<true> : tree_score_kernel<false>;
         kernel<<<nb, CH, 0, c->stream>>>(c->tgt_soa64.as<double>(), n, n_pad, tf, c->t_prep.as<double>(), c->tree.L, lambda_c,
-                                         maha2_max, d_node, d_maha, d_logp, partial,
-                                         c->tgt_weighted ? c->tgt_w.as<double>() : nullptr);
+                                         maha2_max, d_node, d_maha, d_logp, partial, w);
     }
-    tree_score_finish_kernel<<<1, CH, 0, c->stream>>>(partial, (int)nb, c->tgt_weighted ? c->tgt_wsum : (double)n, d_sum);
+    tree_score_finish_kernel<<<1, CH, 0, c->stream>>>(partial, (int)nb, c->tgt_w.total(n), d_sum);
     HGMM_HIP(c, hipGetLastError());
     StagedDownloads dl(c);
     dl.add(summary_out, d_sum, sizeof(double) * 8);

@@ -174,6 +174,13 @@ static int check_members(hgmm_ctx* c, const char* what, int B, const int32_t* me
     return HGMM_OK;
 }
 
+// the weight sums of B slots filled from `members`: counts are integers that add up to the member's raw point count
+static std::vector<double> raw_counts(const hgmm_ctx* c, int B, const int32_t* members) {
+    std::vector<double> sums((size_t)B);
+    for (int b = 0; b < B; ++b) sums[b] = (double)c->vx_nb[members[b]];
+    return sums;
+}
+
 // the launch: B slots filled from `members` (B == 1: no table), the words of `zeroed` cleared in front of it
 template <bool TARGET>
 static int launch_handover(hgmm_ctx* c, HandoverArgs a, int B, const int32_t* members, unsigned long long* zeroed, int n_zeroed) {
@@ -232,8 +239,8 @@ extern "C" int hgmm_voxel_to_points(hgmm_ctx* c, int member, int weights) {
     bind_points(c, nullptr);
     hgmm_points* p = &c->own_points;
     HGMM_TRY(points_alloc(c, p, m));
-    if (w_tree) HGMM_TRY(ensure(c, c->src_w, sizeof(double) * (size_t)p->n_pad));
-    if (w_flat) HGMM_TRY(ensure(c, c->flat_sw, sizeof(float) * (size_t)m));
+    if (w_tree) HGMM_TRY(ensure(c, c->src.buf, sizeof(double) * (size_t)p->n_pad));
+    if (w_flat) HGMM_TRY(ensure(c, c->flat_w.buf, sizeof(float) * (size_t)m));
     // (float)count == count while count < 2^24, and no count exceeds the member's raw points: only a member of 2^24 raw
     // points or more can hold a count that rounds, and only then is the sum of the float32 weights taken on the device
     const bool sum_on_device = w_flat && n_raw >= ((int64_t)1 << 24);
@@ -243,8 +250,8 @@ extern "C" int hgmm_voxel_to_points(hgmm_ctx* c, int member, int weights) {
     a.pad = p->n_pad;
     a.soa = p->x_soa64.as<double>();
     a.aos = p->x_aos.as<float>();
-    a.wd = w_tree ? c->src_w.as<double>() : nullptr;
-    a.wf = w_flat ? c->flat_sw.as<float>() : nullptr;
+    a.wd = w_tree ? c->src.buf.as<double>() : nullptr;
+    a.wf = w_flat ? c->flat_w.buf.as<float>() : nullptr;
     // (B == 1 launches use no table: the first word of vx_hand is free for the sum)
     a.wf_sum = sum_on_device ? c->vx_hand.as<unsigned long long>() : nullptr;
     const int32_t mem = member;
@@ -258,8 +265,8 @@ extern "C" int hgmm_voxel_to_points(hgmm_ctx* c, int member, int weights) {
         flat_sum = (double)s;
     }
     bind_points(c, p);
-    if (w_tree) { c->src_wsum = (double)n_raw; c->src_weighted = true; }
-    if (w_flat) { c->flat_wsum = flat_sum; c->flat_weighted = true; }
+    if (w_tree) c->src.publish({(double)n_raw});
+    if (w_flat) c->flat_w.publish({flat_sum});
     return HGMM_OK;
 }
 
@@ -271,16 +278,15 @@ extern "C" int hgmm_voxel_to_target(hgmm_ctx* c, int member, int weighted) {
     const int64_t m = c->vx_mb[member];
     const int64_t pad = (m + 255) / 256 * 256;
     // ---- the arguments are good: from here on a failure is the runtime's and leaves no target ----
-    c->tgt_n = 0;
-    c->tgt_weighted = false;
+    target_begin(c);
     HGMM_TRY(ensure(c, c->tgt_soa64, sizeof(double) * 3 * (size_t)pad));
-    if (weighted) HGMM_TRY(ensure(c, c->tgt_w, sizeof(double) * (size_t)pad));
+    if (weighted) HGMM_TRY(ensure(c, c->tgt_w.buf, sizeof(double) * (size_t)pad));
     HGMM_TRY(ensure(c, c->vx_hand, 64));
     HandoverArgs a{};
     a.total = m;
     a.pad = pad;
     a.soa = c->tgt_soa64.as<double>();
-    a.wd = weighted ? c->tgt_w.as<double>() : nullptr;
+    a.wd = weighted ? c->tgt_w.buf.as<double>() : nullptr;
     a.r2bits = c->vx_hand.as<unsigned long long>();          // (B == 1 launches use no table)
     const int32_t mem = member;
     HGMM_TRY(launch_handover<true>(c, a, 1, &mem, a.r2bits, 1));
@@ -290,12 +296,8 @@ extern "C" int hgmm_voxel_to_target(hgmm_ctx* c, int member, int weighted) {
         dl.add(&bits, a.r2bits, sizeof bits);
         HGMM_HIP(c, dl.finish());
     }
-    double r2;
-    std::memcpy(&r2, &bits, sizeof r2);
-    c->tgt_rmax = std::sqrt(r2);
-    c->tgt_n = m;
-    c->tgt_pad = pad;
-    if (weighted) { c->tgt_wsum = (double)c->vx_nb[member]; c->tgt_weighted = true; }
+    const double wsum = (double)c->vx_nb[member];
+    target_publish(c, m, pad, r2_of_bits(bits), weighted ? &wsum : nullptr);
     return HGMM_OK;
 }
 
@@ -310,23 +312,19 @@ extern "C" int hgmm_voxel_to_points_batch(hgmm_ctx* c, int B, const int32_t* mem
     bind_points(c, nullptr);
     hgmm_points* p = &c->own_points;
     HGMM_TRY(points_alloc(c, p, total));
-    if (weighted) HGMM_TRY(ensure(c, c->fr_src_w, sizeof(double) * (size_t)p->n_pad));
+    ForestState& F = c->forest;
+    if (weighted) HGMM_TRY(ensure(c, F.src_w.buf, sizeof(double) * (size_t)p->n_pad));
     HandoverArgs a{};
     a.total = total;
     a.pad = p->n_pad;
     a.soa = p->x_soa64.as<double>();
-    a.wd = weighted ? c->fr_src_w.as<double>() : nullptr;
+    a.wd = weighted ? F.src_w.buf.as<double>() : nullptr;
     HGMM_TRY(launch_handover<false>(c, a, B, members, nullptr, 0));
     bind_points(c, p);
     c->have_f32 = false;                                    // (a forest cloud has no float32 rows: hgmm_set_points_batch_*)
-    ForestState& F = c->forest;
     F.src_counts.resize((size_t)B);
     for (int b = 0; b < B; ++b) F.src_counts[b] = c->vx_mb[members[b]];
-    if (weighted) {
-        F.src_wsum.resize((size_t)B);
-        for (int b = 0; b < B; ++b) F.src_wsum[b] = (double)c->vx_nb[members[b]];
-        F.src_weighted = true;
-    }
+    if (weighted) F.src_w.publish(raw_counts(c, B, members));
     return HGMM_OK;
 }
 
@@ -335,23 +333,22 @@ extern "C" int hgmm_voxel_to_targets_batch(hgmm_ctx* c, int B, const int32_t* me
     const char* what = "hgmm_voxel_to_targets_batch";
     HGMM_TRY(check_result(c, what));
     HGMM_TRY(check_members(c, what, B, members, 4096));
+    std::vector<int64_t> counts((size_t)B);
     int64_t total = 0;
-    for (int b = 0; b < B; ++b) total += c->vx_mb[members[b]];
+    for (int b = 0; b < B; ++b) { counts[b] = c->vx_mb[members[b]]; total += counts[b]; }
     if (total > 0x7fffffff - 1024) return fail(c, HGMM_ERR_ARG, "%s: too many target points for 32-bit indices", what);
     // ---- the arguments are good: from here on a failure is the runtime's and leaves no targets ----
-    ForestState& F = c->forest;
-    F.tg_B = 0;
-    F.tg_weighted = false;
+    forest_targets_begin(c);
     const int64_t pad = (total + 255) / 256 * 256;
     HGMM_TRY(ensure(c, c->fr_tg, sizeof(double) * 3 * (size_t)pad));
-    if (weighted) HGMM_TRY(ensure(c, c->fr_tg_w, sizeof(double) * (size_t)pad));
+    if (weighted) HGMM_TRY(ensure(c, c->forest.tg_w.buf, sizeof(double) * (size_t)pad));
     RegTable tb;
     HGMM_TRY(reg_table(c, c->fr_reg, B, &tb));
     HandoverArgs a{};
     a.total = total;
     a.pad = pad;
     a.soa = c->fr_tg.as<double>();
-    a.wd = weighted ? c->fr_tg_w.as<double>() : nullptr;
+    a.wd = weighted ? c->forest.tg_w.buf.as<double>() : nullptr;
     a.r2bits = tb.r2max;
     HGMM_TRY(launch_handover<true>(c, a, B, members, tb.r2max, B));
     std::vector<unsigned long long> bits((size_t)B);
@@ -360,25 +357,8 @@ extern "C" int hgmm_voxel_to_targets_batch(hgmm_ctx* c, int B, const int32_t* me
         dl.add(bits.data(), tb.r2max, sizeof(unsigned long long) * (size_t)B);
         HGMM_HIP(c, dl.finish());
     }
-    F.tg_counts.resize((size_t)B);
-    F.tg_first.resize((size_t)B);
-    F.tg_rmax.resize((size_t)B);
-    int64_t at = 0;
-    for (int b = 0; b < B; ++b) {
-        F.tg_first[b] = at;
-        F.tg_counts[b] = c->vx_mb[members[b]];
-        at += F.tg_counts[b];
-        double r2;
-        std::memcpy(&r2, &bits[b], sizeof r2);
-        F.tg_rmax[b] = std::sqrt(r2);
-    }
-    F.tg_pad = pad;
-    F.tg_B = B;
-    if (weighted) {
-        F.tg_wsum.resize((size_t)B);
-        for (int b = 0; b < B; ++b) F.tg_wsum[b] = (double)c->vx_nb[members[b]];
-        F.tg_weighted = true;
-    }
+    const std::vector<double> wsums = raw_counts(c, B, members);
+    forest_targets_publish(c, B, counts.data(), bits.data(), pad, weighted ? wsums.data() : nullptr);
     return HGMM_OK;
 }
 
