@@ -159,6 +159,8 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_fullcov_phase_clocks", [ctx, C.c_int, C.POINTER(C.c_int64)])
         _sig(lib, "hgmm_util_fill_f32", [ctx, _vp, C.c_int64, C.c_float, C.c_int])
         _sig(lib, "hgmm_kmeans_center_f64", [_vp, C.c_int64, _vp, _vp, _vp])
+        _sig(lib, "hgmm_kmeans_fit_batch", [ctx, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_register", [ctx, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
                                          C.POINTER(C.c_int), C.POINTER(C.c_int), _vp])
         _sig(lib, "hgmm_comm_stats", [ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
@@ -1583,6 +1585,55 @@ class Context:
         d2 = np.empty(self.num_points) if with_distances else None
         self._check(self.lib.hgmm_kmeans_labels(self.h, _ptr(labels), _ptr(d2) if with_distances else None))
         return (labels, d2) if with_distances else labels
+
+    def kmeans_fit_batch(self, counts, k, max_iter, tol_abs, first_ids=None, rand_vals=None, init_centres=None,
+                         want_labels=True):
+        """B clouds seeded and clustered by the same launches (hgmm_kmeans_fit_batch) on the resident batch cloud of
+        :meth:`set_points_batch`, whose members the caller has centred.  Either ``first_ids`` [B] with ``rand_vals``
+        [B, k-1, n_trials] (the host-drawn first seeds and uniforms) or ``init_centres`` [B, k, 3] (no seeding).
+        -> dict: ``ids`` [B,k] (None with ``init_centres``), ``seeds`` [B,k,3] (the seeds, or the given start), ``centres`` [B,k,3], ``n_iter``, ``strict``,
+        ``status`` [B] (1: the member met an empty cluster and left the batch -- only its seeds are valid), ``inertia`` [B]
+        (of the last assignment of a member that did not stop strictly, else 0), ``labels``: a list of B arrays (or None).
+        Member b's numbers are bit for bit those of kmeans_plusplus + kmeans_lloyd (+ kmeans_step) on that cloud alone."""
+        counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        B, k = len(counts), int(k)
+        tol_abs = np.ascontiguousarray(np.broadcast_to(np.asarray(tol_abs, dtype=np.float64), (B,)))
+        seeded = init_centres is None
+        n_trials = 1
+        if seeded:
+            if first_ids is None:
+                raise ValueError("kmeans_fit_batch takes first_ids (+ rand_vals) or init_centres, one of the two")
+            first_ids = np.ascontiguousarray(first_ids, dtype=np.int64).reshape(-1)
+            if len(first_ids) != B:
+                raise ValueError("first_ids must be [%d], got %s" % (B, first_ids.shape))
+            if k > 1:
+                rand_vals = np.ascontiguousarray(rand_vals, dtype=np.float64)
+                if rand_vals.ndim != 3 or rand_vals.shape[:2] != (B, k - 1):
+                    raise ValueError("rand_vals must be [%d,%d,n_trials], got %s" % (B, k - 1, rand_vals.shape))
+                n_trials = rand_vals.shape[2]
+            else:
+                rand_vals = None
+        else:
+            if first_ids is not None or rand_vals is not None:
+                raise ValueError("kmeans_fit_batch takes first_ids (+ rand_vals) or init_centres, one of the two")
+            init_centres = np.ascontiguousarray(init_centres, dtype=np.float64)
+            if init_centres.shape != (B, k, 3):
+                raise ValueError("init_centres must be [%d,%d,3], got %s" % (B, k, init_centres.shape))
+        ids = np.empty((B, k), np.int64) if seeded else None
+        seeds = np.empty((B, k, 3))
+        centres = np.empty((B, k, 3))
+        n_iter, strict, status = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        inertia = np.zeros(B)
+        labels = np.empty(int(counts.sum()), np.int32) if want_labels else None
+        opt = lambda a: _ptr(a) if a is not None else None
+        self._check(self.lib.hgmm_kmeans_fit_batch(self.h, B, _ptr(counts), k, opt(first_ids), opt(rand_vals), int(n_trials),
+                                                   opt(init_centres), int(max_iter), _ptr(tol_abs), opt(ids), opt(seeds),
+                                                   _ptr(centres), _ptr(n_iter), _ptr(strict), _ptr(status), _ptr(inertia),
+                                                   opt(labels)))
+        if labels is not None:
+            labels = np.split(labels, np.cumsum(counts)[:-1])
+        return {"ids": ids, "seeds": seeds, "centres": centres, "n_iter": n_iter, "strict": strict, "status": status,
+                "inertia": inertia, "labels": labels}
 
     # -- L2 GMMReg ---------------------------------------------------------------------------
     def gauss_transform(self, centres, points, weights, h):

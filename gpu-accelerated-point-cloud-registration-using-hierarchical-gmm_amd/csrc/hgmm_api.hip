@@ -782,7 +782,8 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->vx_in, &c->vx_tab, &c->vx_keys, &c->vx_keys2, &c->vx_rows, &c->vx_rows2, &c->vx_heads, &c->vx_tmp,
                       &c->vx_cent, &c->vx_cnt, &c->vx_hand,
                       &c->fb_tab, &c->fb_params, &c->fb_pack, &c->fb_partials, &c->fb_lpn_partials, &c->fb_stats, &c->fb_lls, &c->fb_ctl,
-                      &c->fb_sw, &c->fb_x};
+                      &c->fb_sw, &c->fb_x,
+                      &c->kb_tab, &c->kb_x, &c->kb_points, &c->kb_blocks, &c->kb_partial, &c->kb_small};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);

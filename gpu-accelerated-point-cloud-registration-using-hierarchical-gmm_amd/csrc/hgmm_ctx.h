@@ -93,6 +93,8 @@ struct FlatBatchSlot {
 constexpr int FLAT_BATCH_MAX = 4096;                              // members per call
 constexpr unsigned long long FLAT_BATCH_MAX_PARTIALS = 8ull << 30;   // bytes of all members' partial buffers together
 constexpr int FLAT_BATCH_CTL_WORDS = 16;
+constexpr int KM_BATCH_MAX = 4096;                                // members per hgmm_kmeans_fit_batch
+constexpr unsigned long long KM_BATCH_MAX_PARTIALS = 8ull << 30;  // bytes of all members' per-cluster partial sums together
 
 // The store pacer's measurement ring (its rate controller: flat_pace.h): the last few paced E-step launches are bracketed
 // by event pairs that are looked at -- never waited for -- when the next one is launched (flat_kernels.hip, pace_poll).
@@ -318,6 +320,13 @@ struct hgmm_ctx {
     hgmm::DevBuf km_partial;                  // double [blocks][k_alloc][4]
     hgmm::DevBuf km_out;                      // double [4k + 2] sums, inertia, changed (+ scratch)
     int64_t km_labels_n = -1;
+    // batched initialiser (hgmm_kmeans_fit_batch, kmeans_batch.h): buffers of its own, nothing above is touched
+    hgmm::DevBuf kb_tab;                      // KmBatchMember [B], then (member, local index) per workgroup of the four sized launches
+    hgmm::DevBuf kb_x;                        // double: the members' copies of their clouds, [3][n_pad_b] each, n_pad_b a multiple of 4096
+    hgmm::DevBuf kb_points;                   // double closest | double mind2 | int32 labels, [sum n_pad_b] each; int32 [n_pad] packed labels
+    hgmm::DevBuf kb_blocks;                   // double: the members' block / group / candidate tables, then their inertia partials
+    hgmm::DevBuf kb_partial;                  // double: the members' [nb_acc_b][k_alloc][4]
+    hgmm::DevBuf kb_small;                    // per member: seeds, centres, padded centres, candidates, sums, uniforms, ids, control words
 
     // ---- L2 GMMReg Gauss transform ---------------------------------------------------
     hgmm::DevBuf gt_buf;                      // double: centres, points, weights, per-split partial sums

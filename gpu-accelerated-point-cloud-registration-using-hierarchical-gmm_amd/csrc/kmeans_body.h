@@ -1,15 +1,22 @@
-// The bodies of six kernels of the KMeans initialiser (kmeans_kernels.hip), included once per kernel -- plain and _w --
+// The bodies of eight kernels of the KMeans initialiser (kmeans_kernels.hip), included once per kernel -- plain and _w --
 // inside the kernel's braces, as fullcov_body.h and flat_fused_body.h are: KMEANS_BODY selects the body (1 kmpp_first_kernel,
-// 2 kmpp_step_kernel, 3 kmpp_fused_kernel, 4 kmeans_assign_kernel, 5 kmeans_accum_kernel, 6 kmeans_accum_lds_kernel).  The
-// including kernel defines
+// 2 kmpp_step_kernel, 3 kmpp_fused_kernel, 4 kmeans_assign_kernel, 5 kmeans_accum_kernel, 6 kmeans_accum_lds_kernel, and the
+// two that have no _w form: 7 kmeans_reduce_kernel, 8 kmeans_update_kernel).  The including kernel defines
 //   constexpr bool WEIGHTED       the points carry weights (hgmm_kmeans_plusplus_weighted / _step_weighted / _lloyd_weighted)
 //   const double* wts             ... [n_pad], on the row index of xs (NULL without)
 // next to its own arguments.  An include and not a template: the unweighted kernels are then compiled from the very text they
 // had before the weights, and their code objects stay what they were, instruction for instruction (tools/isa_diff.py).
+// The BATCHED kernels (kmeans_batch.h: many clouds through one launch) include the same bodies once more: they declare the
+// kernel's arguments as locals read from their member's row of a table, and the two names a body knows its place in the
+// launch by,
+//   KM_WG                         the workgroup's index within ITS CLOUD's launch   (serial kernels: blockIdx.x)
+//   KM_NWG                        the workgroups that launch has for the cloud      (serial kernels: gridDim.x)
+// as what the serial launch of that cloud alone would have given this workgroup.  Same text, same operations in the same
+// order: a member's numbers are the serial kernels' bit for bit.
 // No include guard: the file is meant to be included more than once.
 #if KMEANS_BODY == 1    // kmpp_first_kernel
     __shared__ double sh[4];
-    const int64_t i = (int64_t)blockIdx.x * KM_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)KM_WG * KM_BLOCK + threadIdx.x;
     const double cx = xs[first], cy = xs[n_pad + first], cz = xs[2 * n_pad + first];
     double d = 0.0;
     if (i < n) d = dist2(xs[i], xs[n_pad + i], xs[2 * n_pad + i], cx, cy, cz);
@@ -18,8 +25,8 @@
     if constexpr (WEIGHTED) term = i < n ? wts[i] * d : 0.0;
     const double t = block_sum_256(term, sh);
     if (threadIdx.x == 0) {
-        bsum[blockIdx.x] = t;
-        if (blockIdx.x == 0) {
+        bsum[KM_WG] = t;
+        if (KM_WG == 0) {
             centres[0] = cx; centres[1] = cy; centres[2] = cz;
             ids[0] = first;
         }
@@ -27,7 +34,7 @@
 #elif KMEANS_BODY == 2    // kmpp_step_kernel
     __shared__ double shg[KM_MAX_TRIALS][KM_GROUP];
     const int lane = lane_id();
-    const int64_t blk = (int64_t)blockIdx.x * KM_GROUP + wave_in_block();     // 256-point block of this wave
+    const int64_t blk = (int64_t)KM_WG * KM_GROUP + wave_in_block();     // 256-point block of this wave
     const bool have = blk < B;
     const int64_t i0 = (have ? blk : 0) * KM_BLOCK + 4 * lane;                 // n_pad is a multiple of 256
     // every candidate's coordinates through ONE batch of scalar loads (index clamped, not branched on, so that the
@@ -85,7 +92,7 @@
         double s = 0.0;
 #pragma unroll
         for (int q = 0; q < KM_GROUP; ++q) s += shg[threadIdx.x][q];
-        part16[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
+        part16[(size_t)threadIdx.x * KM_NWG + KM_WG] = s;
     }
 #elif KMEANS_BODY == 3    // kmpp_fused_kernel
     const unsigned long long t_start = dbg ? (unsigned long long)wall_clock64() : 0ull;
@@ -94,7 +101,7 @@
     __shared__ double sh_cand[3 * KM_MAX_TRIALS];
     __shared__ KmTailShared ts;
     const int lane = lane_id();
-    const int64_t blk = (int64_t)blockIdx.x * KM_GROUP + wave_in_block();     // 256-point block of this wave
+    const int64_t blk = (int64_t)KM_WG * KM_GROUP + wave_in_block();     // 256-point block of this wave
     const bool have = blk < B;
     const int64_t i0 = (have ? blk : 0) * KM_BLOCK + 4 * lane;                 // n_pad is a multiple of 256
     // the pass's operands do not depend on the tail: requested inside its first round of loads (see there)
@@ -102,7 +109,7 @@
     double fx, fy, fz;
     kmpp_tail_body<TMAX, WEIGHTED>(xs, n, n_pad, wts, closest, part_prev, part16_prev, G, nullptr, nullptr, B, T, j - 1, 1, 1,
                             rand_c, cand_prev, cand_xyz_prev, cand_next, cand_xyz_next, centres, ids, nullptr,
-                            blockIdx.x == 0, sh_cand, fx, fy, fz, ts, dbg, t_start, pts, i0);
+                            KM_WG == 0, sh_cand, fx, fy, fz, ts, dbg, t_start, pts, i0);
     __syncthreads();                                         // sh_cand
     km_stamp(dbg, 7, t_start);
     double x[4], y[4], z[4], cl[4];
@@ -145,14 +152,14 @@
         double s2 = 0.0;
 #pragma unroll
         for (int q = 0; q < KM_GROUP; ++q) s2 += shg[threadIdx.x][q];
-        part16_next[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s2;
+        part16_next[(size_t)threadIdx.x * KM_NWG + KM_WG] = s2;
     }
     km_stamp(dbg, 8, t_start);
 #elif KMEANS_BODY == 4    // kmeans_assign_kernel
     if (done && *done) return;
     __shared__ double sh[4];
     __shared__ int shc[4];
-    const int64_t i0 = (int64_t)blockIdx.x * (2 * KM_BLOCK) + threadIdx.x;
+    const int64_t i0 = (int64_t)KM_WG * (2 * KM_BLOCK) + threadIdx.x;
     const int64_t i1 = i0 + KM_BLOCK;
     const bool l0 = i0 < n, l1 = i1 < n;
     const int64_t j0 = l0 ? i0 : 0, j1 = l1 ? i1 : 0;
@@ -217,7 +224,7 @@
     if (lane_id() == 0) shc[wave_in_block()] = wc;
     const double t = block_sum_256(in, sh);
     if (threadIdx.x == 0) {
-        inertia_part[blockIdx.x] = t;
+        inertia_part[KM_WG] = t;
         const int tc = shc[0] + shc[1] + shc[2] + shc[3];
         if (tc) atomicAdd(n_changed, (unsigned long long)tc);
     }
@@ -228,9 +235,9 @@
     double ax[NSLOT], ay[NSLOT], az[NSLOT], ac[NSLOT];
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) ax[s] = ay[s] = az[s] = ac[s] = 0.0;
-    const int64_t waves = (int64_t)gridDim.x * 4;
+    const int64_t waves = (int64_t)KM_NWG * 4;
     const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t gw = (int64_t)KM_WG * 4 + wave;
     const int64_t begin = gw * per;
     const int64_t end = begin + per < n ? begin + per : n;
     for (int64_t base = begin; base < end; base += 64) {
@@ -256,7 +263,7 @@
             }
         }
     }
-    double* out = partial + (size_t)blockIdx.x * k_alloc * 4;
+    double* out = partial + (size_t)KM_WG * k_alloc * 4;
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
         sh[wave][lane][0] = ax[s];
@@ -286,9 +293,9 @@
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
     wave_lds_sync();                                      // table cleared before the first ds_add
-    const int64_t waves = (int64_t)gridDim.x * 4;
+    const int64_t waves = (int64_t)KM_NWG * 4;
     const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t gw = (int64_t)KM_WG * 4 + wave;
     const int64_t begin = gw * per;
     const int64_t end = begin + per < n ? begin + per : n;
     const int f = lane & 3;
@@ -326,7 +333,67 @@
         }
     }
     __syncthreads();
-    double* out = partial + (size_t)blockIdx.x * tsz;
+    double* out = partial + (size_t)KM_WG * tsz;
     for (int e = threadIdx.x; e < tsz; e += KM_BLOCK)
         out[e] = (km_lds[e] + km_lds[tsz + e]) + (km_lds[2 * tsz + e] + km_lds[3 * tsz + e]);
+#elif KMEANS_BODY == 7    // kmeans_reduce_kernel
+    if (done && *done) return;
+    __shared__ double sh[8][32];
+    __shared__ double shi[4];
+    const int e_loc = threadIdx.x & 31, slice = threadIdx.x >> 5;
+    const int e = KM_WG * 32 + e_loc;
+    double s = 0.0;
+    if (e < 4 * k) {
+        const int per = (nb + 7) / 8;
+        const int b0 = slice * per, b1 = min(nb, b0 + per);
+        for (int b = b0; b < b1; ++b) s += partial[(size_t)b * k_alloc * 4 + e];
+    }
+    sh[slice][e_loc] = s;
+    __syncthreads();
+    if (slice == 0 && e < 4 * k) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t += sh[q][e_loc];
+        out[e] = t;
+    }
+    if (KM_WG == 0) {
+        double v = 0.0;
+        for (int b = threadIdx.x; b < nib; b += KM_BLOCK) v += inertia_part[b];
+        const double t = block_sum_256(v, shi);
+        if (threadIdx.x == 0) {
+            out[4 * k] = t;
+            out[4 * k + 1] = (double)n_changed[0];
+        }
+    }
+#elif KMEANS_BODY == 8    // kmeans_update_kernel
+    if (ctl->done) return;
+    __shared__ double sh[4];
+    __shared__ int sh_empty;
+    if (threadIdx.x == 0) sh_empty = 0;
+    __syncthreads();
+    int empty = 0;
+    for (int j = threadIdx.x; j < k; j += 256) empty |= out[4 * j + 3] == 0.0;
+    if (empty) sh_empty = 1;
+    __syncthreads();
+    if (sh_empty) {
+        if (threadIdx.x == 0) { ctl->needs_host = 1; ctl->done = 1; }
+        return;
+    }
+    double shift = 0.0;
+    for (int j = threadIdx.x; j < k; j += 256) {
+        const double alpha = 1.0 / out[4 * j + 3];
+        const double n0 = out[4 * j] * alpha, n1 = out[4 * j + 1] * alpha, n2 = out[4 * j + 2] * alpha;
+        const double d0 = n0 - c3[3 * j], d1 = n1 - c3[3 * j + 1], d2 = n2 - c3[3 * j + 2];
+        const double nrm = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        shift += nrm * nrm;
+        c3[3 * j] = n0; c3[3 * j + 1] = n1; c3[3 * j + 2] = n2;
+    }
+    const double tot = block_sum_256(shift, sh);
+    if (threadIdx.x == 0) {
+        const int it = ctl->it + 1;
+        ctl->it = it;
+        if (out[4 * k + 1] == 0.0) { ctl->strict = 1; ctl->done = 1; }
+        else if (tot <= tol_abs || it >= max_iter) ctl->done = 1;
+        *changed = 0ull;                                   // next iteration's counter
+    }
 #endif

@@ -34,6 +34,9 @@ constexpr int KM_BLOCK = 256;
 constexpr int KM_MAX_TRIALS = 16;
 constexpr int KM_ACC_SLOTS = 16;                   // 64-centre slots per accumulate pass
 constexpr int KM_MAX_K = 16384;
+// a kernel body's place in its cloud's launch (kmeans_body.h); kmeans_batch.h redefines the two for its kernels
+#define KM_WG blockIdx.x
+#define KM_NWG gridDim.x
 
 struct OpAddI { __device__ __forceinline__ int operator()(int a, int b) const { return a + b; } };
 
@@ -626,34 +629,9 @@ __global__ __launch_bounds__(KM_BLOCK) void kmeans_reduce_kernel(const double* _
                                                                  const unsigned long long* __restrict__ n_changed,
                                                                  double* __restrict__ out,
                                                                  const int* __restrict__ done) {
-    if (done && *done) return;
-    __shared__ double sh[8][32];
-    __shared__ double shi[4];
-    const int e_loc = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int e = blockIdx.x * 32 + e_loc;
-    double s = 0.0;
-    if (e < 4 * k) {
-        const int per = (nb + 7) / 8;
-        const int b0 = slice * per, b1 = min(nb, b0 + per);
-        for (int b = b0; b < b1; ++b) s += partial[(size_t)b * k_alloc * 4 + e];
-    }
-    sh[slice][e_loc] = s;
-    __syncthreads();
-    if (slice == 0 && e < 4 * k) {
-        double t = 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t += sh[q][e_loc];
-        out[e] = t;
-    }
-    if (blockIdx.x == 0) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nib; b += KM_BLOCK) v += inertia_part[b];
-        const double t = block_sum_256(v, shi);
-        if (threadIdx.x == 0) {
-            out[4 * k] = t;
-            out[4 * k + 1] = (double)n_changed[0];
-        }
-    }
+#define KMEANS_BODY 7
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 __global__ void kmeans_pad_centres_kernel(const double* __restrict__ c3, int k, double* __restrict__ c4,
@@ -681,36 +659,9 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const double* __rest
                                                             int max_iter, double* __restrict__ c3,
                                                             unsigned long long* __restrict__ changed,
                                                             KmCtl* __restrict__ ctl) {
-    if (ctl->done) return;
-    __shared__ double sh[4];
-    __shared__ int sh_empty;
-    if (threadIdx.x == 0) sh_empty = 0;
-    __syncthreads();
-    int empty = 0;
-    for (int j = threadIdx.x; j < k; j += 256) empty |= out[4 * j + 3] == 0.0;
-    if (empty) sh_empty = 1;
-    __syncthreads();
-    if (sh_empty) {
-        if (threadIdx.x == 0) { ctl->needs_host = 1; ctl->done = 1; }
-        return;
-    }
-    double shift = 0.0;
-    for (int j = threadIdx.x; j < k; j += 256) {
-        const double alpha = 1.0 / out[4 * j + 3];
-        const double n0 = out[4 * j] * alpha, n1 = out[4 * j + 1] * alpha, n2 = out[4 * j + 2] * alpha;
-        const double d0 = n0 - c3[3 * j], d1 = n1 - c3[3 * j + 1], d2 = n2 - c3[3 * j + 2];
-        const double nrm = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
-        shift += nrm * nrm;
-        c3[3 * j] = n0; c3[3 * j + 1] = n1; c3[3 * j + 2] = n2;
-    }
-    const double tot = block_sum_256(shift, sh);
-    if (threadIdx.x == 0) {
-        const int it = ctl->it + 1;
-        ctl->it = it;
-        if (out[4 * k + 1] == 0.0) { ctl->strict = 1; ctl->done = 1; }
-        else if (tot <= tol_abs || it >= max_iter) ctl->done = 1;
-        *changed = 0ull;                                   // next iteration's counter
-    }
+#define KMEANS_BODY 8
+#include "kmeans_body.h"
+#undef KMEANS_BODY
 }
 
 static int km_check(hgmm_ctx* c, int k) {
@@ -1102,3 +1053,5 @@ extern "C" int hgmm_kmeans_labels(hgmm_ctx* c, int32_t* labels_out, double* min_
     HGMM_HIP(c, ctx_stream_sync(c));
     return HGMM_OK;
 }
+
+#include "kmeans_batch.h"

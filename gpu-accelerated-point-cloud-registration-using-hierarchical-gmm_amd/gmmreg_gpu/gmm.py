@@ -3,10 +3,11 @@ returns ``(means, weights)`` only (reference gmm.py:57,70); covariances start at
 (gmm.py:80); host NumPy results (gmm.py:95)."""
 import numpy as np
 
-from ..gmm_waymo.gmm import Feature, GMM_Sklearn, _cpu_name_notice, _split_weighted  # noqa: F401
+from ..gmm_waymo.gmm import Feature, GMM_Sklearn, _cpu_name_notice, _split_weighted, _Weighted  # noqa: F401
 from ..gmm_waymo.gmm import OneClassSVM as _SklearnOneClassSVM
 from . import gmm_impl
-from .gmm_impl import train_gmm, init_gmm_params, timer, predict, asarray  # noqa: F401
+from .gmm_impl import train_gmm, train_gmm_batch, init_gmm_params, init_gmm_params_batch, timer, predict, asarray  # noqa: F401
+from .gmm_impl import DevicePoints
 
 
 class GMM_GPU_Base:
@@ -44,6 +45,53 @@ class GMM_GPU_Base:
         if len(lls):
             print("\nLog Likelihood Min-Max:\n\n", np.min(lls), np.max(lls))
         return self
+
+    def fit_batch(self, frames, inits=None, sample_weight=None):
+        """One fit per frame through ONE launch set each for the initialiser (``init_gmm_params_batch``: the batched KMeans)
+        and for the EM (``train_gmm_batch``) -> a list of fitted estimators of this one's settings, each bit for bit in the
+        state ``.fit(frame)`` leaves one in (this estimator itself stays as it is).  ``inits``: one ``(means, weights)`` per
+        frame instead of the initialiser.
+
+        ``sample_weight``: the convention of ``gmm_waymo``'s ``fit_batch`` -- None: frames that bring per-point weights are
+        refused; ``"own"``: each frame's own; a sequence: one array or None (its own) per frame.  The initialiser does not see
+        the weights, and an estimator built with ``weighted_init=True`` is refused: the batched initialiser is unweighted."""
+        if self.weighted_init:
+            raise ValueError("fit_batch: weighted_init=True is not supported -- the batched KMeans initialiser is unweighted; "
+                             "fit the frames one by one with fit(frame)")
+        frames = list(frames)
+        if inits is not None and len(inits) != len(frames):
+            raise ValueError("fit_batch: %d frames, but %d initialisations" % (len(frames), len(inits)))
+        if sample_weight is not None and not isinstance(sample_weight, str) and len(sample_weight) != len(frames):
+            raise ValueError("fit_batch: %d frames, but %d sample_weight entries" % (len(frames), len(sample_weight)))
+        clouds, hosts = [], []
+        for b, X in enumerate(frames):
+            if sample_weight is None and getattr(X, "weights", None) is not None:
+                raise ValueError("fit_batch: frame %d brings per-point weights, which the batched fit does not take unless the "
+                                 "call says so: pass sample_weight='own', or fit it with fit(frame)" % b)
+            P, _ = _split_weighted(X, None)
+            host = P.get() if isinstance(P, DevicePoints) else np.asarray(P)
+            hosts.append(host)
+            if sample_weight is None or isinstance(P, DevicePoints):
+                clouds.append(P if isinstance(P, DevicePoints) else host.astype(np.float32))
+            else:                                                # (a WeightedPoints keeps its weights on the way down)
+                clouds.append(_Weighted(host.astype(np.float32), getattr(X, "weights", None)))
+        if not frames:
+            return []
+        params = list(inits) if inits is not None else init_gmm_params_batch(hosts, self.num_components)
+        covs = [0.1 * np.ones((self.num_components, 3), dtype=np.float32) for _ in frames]
+        with timer(self._label):
+            extra = {} if sample_weight is None else {"sample_weight": sample_weight}
+            fits = train_gmm_batch(clouds, self.max_iter, self.tol, [np.asarray(p[0], np.float32) for p in params], covs,
+                                   [np.asarray(p[1], np.float32) for p in params], **extra)
+        models = []
+        for inv, mu, w, cov, lls in fits:
+            m = type(self)(self.num_components, self.max_iter, self.tol)
+            m.means_, m.covariances_, m.weights_ = mu, cov, w
+            m.lls, m.inv_covs = lls, inv
+            if len(lls):
+                print("\nLog Likelihood Min-Max:\n\n", np.min(lls), np.max(lls))
+            models.append(m)
+        return models
 
     def predict(self, X):
         return predict(np.asarray(X).astype(np.float32), self.inv_covs, self.means_, self.weights_)

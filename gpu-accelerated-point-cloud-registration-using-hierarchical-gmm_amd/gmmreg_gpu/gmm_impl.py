@@ -19,6 +19,14 @@ def init_gmm_params(X, k, sample_weight=None):
     return kmeans_centres(X, k, random_state=1, max_iter=50, sample_weight=sample_weight), np.ones((k)) / k
 
 
+def init_gmm_params_batch(Xs, k):
+    """:func:`init_gmm_params` of every cloud of ``Xs`` through one launch set (``hgmm_amd.kmeans.KMeans.fit_batch``) -> a
+    list of its ``(centres, weights)``, member b's bit for bit the serial call's.  Unweighted: the batched initialiser takes no
+    ``sample_weight``."""
+    from ..kmeans import kmeans_centres_batch
+    return [(c, np.ones((k)) / k) for c in kmeans_centres_batch(Xs, k, random_state=1, max_iter=50)]
+
+
 def estimate_log_prob(X, inv_cov, means):
     """Reference gmmreg_gpu/gmm_impl.py:36-43."""
     return _flat.estimate_log_prob(X, inv_cov, means, 'diag')

@@ -239,6 +239,11 @@ class KMeans:
             centres = np.array(self.init, dtype=np.float64).reshape(k, 3) - mean
             self.init_indices_ = None
 
+        return self._lloyd_from(ctx, Xc, mean, tol_abs, centres, ranks)
+
+    def _lloyd_from(self, ctx, Xc, mean, tol_abs, centres, ranks=1):
+        """The rest of :meth:`fit` from the (centred) start ``centres`` on the resident cloud ``Xc``: Lloyd loop, the last
+        assignment, the attributes.  (:meth:`fit_batch` hands a member that met an empty cluster over to it, from its seeds.)"""
         strict = False
         n_iter = 0
         inertia = 0.0
@@ -283,6 +288,75 @@ class KMeans:
         self.n_iter_ = n_iter
         self.cluster_centers_ = centres + mean
         return self
+
+    def fit_batch(self, Xs, sample_weight=None):
+        """One fit per cloud of ``Xs`` through ONE launch set (``Context.kmeans_fit_batch``: every seeding and Lloyd launch
+        serves all clouds) -> a list of fitted estimators of this one's settings, each in the state ``.fit(X_b)`` leaves one
+        in, bit for bit: ``cluster_centers_``, ``labels_``, ``inertia_``, ``n_iter_``, ``init_indices_`` (this estimator itself
+        stays as it is).  The random stream is consumed cloud by cloud in order, as a loop of ``fit`` consumes it: an int seed
+        gives every cloud a fresh ``RandomState(seed)``, a shared ``RandomState`` is drawn from in the loop's order.  ``init``
+        may be a list of one array of centres per cloud.  A cloud whose iteration meets an empty cluster leaves the batch and
+        is finished by the serial path from its seeds (the relocation stays on the host).  Unweighted only: ``sample_weight``
+        is refused, and so is a context with a communicator."""
+        if sample_weight is not None:
+            raise ValueError("KMeans.fit_batch: the batched initialiser is unweighted (sample_weight / weighted_init are not "
+                             "supported); fit weighted clouds one by one with fit(X, sample_weight=)")
+        Xs = [np.asarray(X.points if hasattr(X, "points") else X, dtype=np.float64) for X in Xs]
+        k, B = self.n_clusters, len(Xs)
+        inits = None
+        if not isinstance(self.init, str):
+            inits = list(self.init)
+            if len(inits) != B:
+                raise ValueError("KMeans.fit_batch: %d clouds, but init has %d entries (one array of centres per cloud)"
+                                 % (B, len(inits)))
+        for b, X in enumerate(Xs):
+            if X.ndim != 2 or X.shape[1] != 3:
+                raise ValueError("KMeans.fit_batch: cloud %d: expected an [N,3] array, got %s" % (b, X.shape))
+            if len(X) < k:
+                raise ValueError("KMeans.fit_batch: cloud %d: n_samples=%d should be >= n_clusters=%d." % (b, len(X), k))
+        if B == 0:
+            return []
+        ctx = self._ctx or default_context()
+        if getattr(ctx, "nranks", 1) > 1 or getattr(ctx, "comm_attached", False):
+            raise ValueError("KMeans.fit_batch: the context has a communicator; the batched initialiser is single-rank")
+        means, tols, Xcs = [], [], []
+        for X in Xs:
+            mean, var, Xc = column_mean_var(X)
+            means.append(mean)
+            tols.append(0.0 if self.tol == 0 else float(np.mean(var) * self.tol))
+            Xcs.append(Xc)
+        first_ids = rand = start = None
+        if inits is None:
+            trials = 2 + int(np.log(k))
+            first_ids, rand = np.empty(B, np.int64), np.empty((B, max(k - 1, 0), trials))
+            for b, Xc in enumerate(Xcs):                        # (the draws of a loop of fit, in its order)
+                rs = _random_state(self.random_state)
+                first_ids[b] = int(_uniform_cdf(len(Xc)).searchsorted(rs.random_sample(), side='right'))
+                rand[b] = rs.uniform(size=(max(k - 1, 0), trials))
+        else:
+            start = np.stack([np.array(c, dtype=np.float64).reshape(k, 3) - m for c, m in zip(inits, means)])
+        ctx.set_points_batch(Xcs)
+        res = ctx.kmeans_fit_batch([len(X) for X in Xcs], k, self.max_iter, tols, first_ids=first_ids, rand_vals=rand,
+                                   init_centres=start)
+        fitted = []
+        for b, Xc in enumerate(Xcs):
+            est = KMeans(k, self.random_state, self.max_iter, 1, self.tol, self.init if inits is None else inits[b], self._ctx)
+            est.init_indices_ = res["ids"][b].copy() if inits is None else None
+            if res["status"][b]:
+                # an empty cluster: the serial path from the member's own start (its seeds, as the device chose them)
+                ctx.set_points(Xc)
+                est._lloyd_from(ctx, Xc, means[b], tols[b], res["seeds"][b].copy())
+            else:
+                centres = res["centres"][b].copy()
+                est.labels_ = res["labels"][b].copy()
+                if res["strict"][b]:
+                    est.inertia_ = float(((Xc - centres[est.labels_]) ** 2).sum())
+                else:
+                    est.inertia_ = float(res["inertia"][b])
+                est.n_iter_ = int(res["n_iter"][b])
+                est.cluster_centers_ = centres + means[b]
+            fitted.append(est)
+        return fitted
 
     def _fit_weighted(self, ctx, X, w):
         """``fit`` under per-point weights: the loop of the unweighted fit on the weighted entries (single context)."""
@@ -353,3 +427,10 @@ def kmeans_centres(X, k, random_state=1, max_iter=50, ctx: Context | None = None
     (gmmreg_gpu/gmm_impl.py:20-21) on the device; ``sample_weight`` as in :meth:`KMeans.fit`."""
     return KMeans(n_clusters=k, random_state=random_state, max_iter=max_iter, n_init=1,
                   ctx=ctx).fit(X, sample_weight=sample_weight).cluster_centers_
+
+
+def kmeans_centres_batch(Xs, k, random_state=1, max_iter=50, ctx: Context | None = None):
+    """:func:`kmeans_centres` of every cloud of ``Xs`` through one launch set (:meth:`KMeans.fit_batch`) -> a list of
+    ``cluster_centers_``, member b's bit for bit what ``kmeans_centres(Xs[b], k, ...)`` returns."""
+    fits = KMeans(n_clusters=k, random_state=random_state, max_iter=max_iter, n_init=1, ctx=ctx).fit_batch(Xs)
+    return [f.cluster_centers_ for f in fits]

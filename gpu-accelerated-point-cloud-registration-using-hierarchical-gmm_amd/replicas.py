@@ -167,7 +167,8 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
 
 
 def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag", devices=None,
-               contexts_per_device: int = 1, pool: ReplicaPool | None = None, batch: int = 1, voxel_size=None):
+               contexts_per_device: int = 1, pool: ReplicaPool | None = None, batch: int = 1, voxel_size=None,
+               flavour: str = "W"):
     """One flat GMM per frame (``GMM_GPU_Base(n_components, max_iter, tol, cov_type).fit(frame)``,
     gmm_waymo/src/gmm.py:65-84), the frames fanned out over the pool's contexts.  -> the fitted models in frame order.
 
@@ -181,8 +182,24 @@ def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag
     (run_gmm_static.py:28).  Each chunk of ``batch`` frames (``batch=1``: a chunk of one) is down-sampled on its context by
     one launch set (``voxel_down_sample_batch(chunk, voxel_size, download=False)``) and fitted COUNT-WEIGHTED through
     ``fit_batch`` where the centroids lie: a voxel counts as the raw points it stands for.  Only the initialiser's copy of
-    the centroids comes back to the host."""
-    from .gmm_waymo.gmm import GMM_GPU_Base
+    the centroids comes back to the host.
+
+    ``flavour="G"``: the GMMReg flavour's model instead (``gmmreg_gpu.gmm.GMM_GPU_Base(n_components, max_iter, tol)``: diag,
+    KMeans initialisation); with ``batch`` > 1 its ``fit_batch`` runs the KMeans initialiser of the chunk's frames through
+    one launch set as well, and the models are bitwise those of ``batch=1``.  It takes neither ``cov_type`` other than
+    ``"diag"`` nor ``voxel_size``."""
+    if flavour == "G":
+        from .gmmreg_gpu.gmm import GMM_GPU_Base as _G
+
+        if cov_type != "diag" or voxel_size is not None:
+            raise ValueError("fit_frames(flavour='G') takes cov_type='diag' and no voxel_size")
+
+        def GMM_GPU_Base(n_components, max_iter, tol, cov_type):
+            return _G(n_components, max_iter, tol)
+    elif flavour == "W":
+        from .gmm_waymo.gmm import GMM_GPU_Base
+    else:
+        raise ValueError("flavour must be 'W' or 'G', not %r" % (flavour,))
 
     frames = list(frames)
     B = int(batch)

@@ -723,6 +723,54 @@ int hgmm_kmeans_step_weighted(hgmm_ctx* ctx, int k, const double* centers, int r
 int hgmm_kmeans_lloyd_weighted(hgmm_ctx* ctx, int k, double* centers_inout, int max_iter, double tol_abs,
                                int reset_labels, int* n_iter_out, int* strict_out, int* needs_host_out,
                                double* sums_out, int64_t* n_changed_out);
+/* B clouds seeded and clustered by the same launches -- B x KMeans(k, ...).fit(X_b) of the GMMReg flavour's initialiser
+ * (gmmreg_gpu/gmm_impl.py:18-24): a scan-sized cloud fills a small part of the chip, and the serial chain is one launch per
+ * centre and five per Lloyd iteration.  Works on the resident batch cloud of hgmm_set_points_batch_f64 / _f32, whose B
+ * consecutive pieces the caller has centred already; counts [B] must equal the resident members.
+ * SEMANTICS.  Member b is the sequence hgmm_set_points_f64(member b); hgmm_kmeans_plusplus(k, first_ids[b], rand_vals[b], ...);
+ * hgmm_kmeans_lloyd(..., max_iter, tol_abs[b], reset_labels = 1, ...) and, when the loop did not stop strictly, one more
+ * hgmm_kmeans_step against the final centres -- what KMeans.fit drives.  Its seed ids, seed coordinates, final centres, n_iter,
+ * strict, the labels of the last assignment and the non-strict inertia come out BIT FOR BIT as that sequence returns them,
+ * whatever B is, wherever b sits and whoever its neighbours are: every member gets the serial geometry of a cloud of its size
+ * (256-point blocks, 16-block seeding workgroups, 512-point assignment workgroups, the accumulator's workgroup count and
+ * contiguous runs, the slot / LDS-or-register choice by k and kmeans_acc_regs, the reduce order, the update rule) and runs the
+ * serial kernels' bodies on tables of its own.  The members share k, n_trials and max_iter; each has its size, first seed,
+ * uniforms rand_vals [B][k-1][n_trials], start and tol_abs [B].  Either the seeding inputs (first_ids, and rand_vals when
+ * k > 1) or init_centres [B][k][3] are given: an explicit start skips the seeding, leaves ids_out unwritten and reports itself
+ * in seeds_out (which may then be NULL).
+ * Outputs are member-major: ids_out [B][k], seeds_out and centres_out [B][k][3], n_iter_out, strict_out, status_out and
+ * inertia_out [B] (0 for a member that stopped strictly: the host forms that inertia, as KMeans.fit does), labels_out [total]
+ * (may be NULL) member after member as the clouds lie in the resident cloud.
+ * EMPTY CLUSTERS.  A member whose iteration meets an empty cluster leaves the batch at that iteration: status_out[b] = 1, its
+ * seeds are valid, its other outputs are unspecified, its neighbours are unaffected.  The caller runs it through the serial
+ * entries from its seeds (kmeans.py does); there is no batched relocation.
+ * THE CLOUD COPY.  The serial kernels rely on a cloud whose row 0 is buffer-aligned and whose padding rows read as the
+ * origin; in the packed batch cloud a member starts at any row and is followed by its neighbour.  One launch therefore copies
+ * the members into a buffer of the batch's own, each at a multiple of 4096 rows with zero rows behind it (at most 4095 rows
+ * per member): every member sees what the serial cloud shows.
+ * LAUNCHES.  One copy launch; per centre one fused seeding launch over the workgroups of all members (the one-launch-per-centre
+ * form, whatever kmpp_two_launches says); per Lloyd iteration the five launches of the serial loop plus the update, each over
+ * all members, eight iterations per synchronisation, until every member is done (a stopped member's workgroups return at its
+ * `done` word); one more assignment for the members that did not stop strictly; one group of download packets.  Nothing is
+ * launched per member.
+ * LIMITS.  1 <= B <= 4096.  A member has at most 16 777 216 points (4096 seeding workgroups, the one-launch form), the
+ * batch cloud fewer than 2^31 - 1024 in all.  The
+ * members' per-cluster partial sums together are at most 8 GiB.  No communicator.  Unweighted: resident source weights are
+ * ignored, as hgmm_kmeans_plusplus / _lloyd ignore them.
+ * REFUSALS, each before anything resident is touched (hgmm_last_error names the member where there is one).  HGMM_ERR_ARG: B
+ * out of range; k outside 1..16384; k > counts[b]; n_trials outside 1..16; first_ids[b] out of range; a NULL required
+ * argument; both or neither of the seeding inputs and init_centres; max_iter < 0; a member or the partial sums above the
+ * limits.  HGMM_ERR_STATE: no resident batch cloud, B or counts that differ from it, a communicator.
+ * LEFT ALONE.  The batch works in buffers of its own and reads the resident cloud's float64 view and nothing else: the serial
+ * KMeans entries' buffers (labels, distances -- a later hgmm_kmeans_step(reset_labels = 0) counts its changes against what it
+ * counted them against before), the resident weights, the tree, the forest, the targets, the voxel result and the flat state
+ * are what they were. */
+int hgmm_kmeans_fit_batch(hgmm_ctx* ctx, int B, const int64_t* counts /* [B] */, int k,
+                          const int64_t* first_ids /* [B] | NULL */, const double* rand_vals /* [B][k-1][n_trials] | NULL */,
+                          int n_trials, const double* init_centres /* [B][k][3] | NULL */, int max_iter,
+                          const double* tol_abs /* [B] */, int64_t* ids_out /* [B][k] */, double* seeds_out /* [B][k][3] */,
+                          double* centres_out /* [B][k][3] */, int32_t* n_iter_out /* [B] */, int32_t* strict_out /* [B] */,
+                          int32_t* status_out /* [B] */, double* inertia_out /* [B] */, int32_t* labels_out /* [total] | NULL */);
 
 /* ---- L2 GMMReg: Gauss transform (float64) ---------------------------------------------
  * out[k, i] = sum_j weights[k, j] exp(-|points_i - centres_j|^2 / h^2),  k < n_weights <= 8
