@@ -182,14 +182,16 @@ def init_nodes(points, max_level, init_idx, sig2, init_mu=None):
 BuildTrace = namedtuple('BuildTrace', ['q', 'iters_per_level', 'current_idx_per_level'])
 
 
-def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_level=10000, w=None, init_mu=None):
+def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_level=10000, w=None, init_mu=None,
+               ll_chunk=4096):
     """hgmm_cupy_cpu_working.py:122-160.  RNG stays outside (``init_idx`` explicit; the
     reference draws ``randint(nTotal, size=nTotal)`` from CuPy's generator).  ``init_mu`` [T,3] gives the initial means
     as coordinates, as the C entry takes them, in place of ``init_idx``.
 
     ``w`` [n] >= 0 (hgmm_tree_set_source_weights): point i counts as w_i points.  Three statements change, marked
     (1)-(3): ``use * w`` in :func:`e_step`, ``pi = m0 / W`` here, ``sum w log`` in :func:`log_likelihood`.  ``w = None``
-    runs the unweighted statements themselves.
+    runs the unweighted statements themselves.  ``ll_chunk``: the points :func:`log_likelihood` takes at a time (its
+    ``chunk``; the default is that function's own, so nothing changes) -- deep levels of a small cloud bound memory with it.
 
     Returns (pi, mu, cov, trace)."""
     points = np.asarray(points, dtype=np.float64)
@@ -208,7 +210,7 @@ def build_tree(points, max_level, ls, ld, init_idx, sig2=0.00034, max_iters_per_
         while True:
             m0, m1, m2, cur, _ = e_step(points, pi, mu, cov, parent, w=w)
             m_step(m0, m1, m2, l, pi, mu, cov, n_points, ld)
-            q = log_likelihood(points, pi, mu, cov, l, w=w)
+            q = log_likelihood(points, pi, mu, cov, l, chunk=ll_chunk, w=w)
             q_trace.append(q)
             it += 1
             if abs(q - prev_q) < ls or it >= max_iters_per_level:

@@ -47,13 +47,13 @@ def ragged_clouds(bunny):
 
 
 @pytest.mark.parametrize("L,ls,sig2", [(1, 20.0, 0.004), (2, 20.0, 0.004), (3, 20.0, 0.004), (3, 80.0, 0.00034), (4, 20.0, 0.004),
-                                     (5, 20.0, 0.004)])
+                                     (5, 20.0, 0.004), (6, 20.0, 0.004)])
 def test_build_batch_is_bitwise_the_serial_build(ctx, bunny, L, ls, sig2):
     clouds = ragged_clouds(bunny)
     T = hgmm_tree.n_total(L)
     idx = np.random.RandomState(72).randint(T, size=T)
     idx = np.minimum(idx, min(len(c) for c in clouds) - 1)            # (the smallest cloud has 200 points)
-    if L >= 5:    # (37 448 draws: clamped, nearly all of them would be the same point -- wrapped, they stay spread)
+    if L >= 5:    # (37 448 / 299 592 draws: clamped, nearly all of them would be the same point -- wrapped, they stay spread)
         idx = np.random.RandomState(72).randint(T, size=T) % min(len(c) for c in clouds)
     (pi, mu, cov), iters, traces = batch_build(ctx, clouds, L, ls, 1e-4, idx, sig2)
     for b, P in enumerate(clouds):
@@ -65,7 +65,8 @@ def test_build_batch_is_bitwise_the_serial_build(ctx, bunny, L, ls, sig2):
     assert len({tuple(r) for r in iters.tolist()}) > 1                 # the clouds do stop at different iterations
 
 
-@pytest.mark.parametrize("L,ls,sig2", [(1, 20.0, 0.004), (2, 20.0, 0.004), (3, 20.0, 0.004), (3, 80.0, 0.00034), (4, 20.0, 0.004)])
+@pytest.mark.parametrize("L,ls,sig2", [(1, 20.0, 0.004), (2, 20.0, 0.004), (3, 20.0, 0.004), (3, 80.0, 0.00034), (4, 20.0, 0.004),
+                                     (5, 20.0, 0.004), (6, 20.0, 0.004)])
 def test_build_batch_float32_pdfs_is_bitwise_the_serial_build_and_keeps_the_float64_trees(ctx, bunny, L, ls, sig2):
     """hgmm_tree_set_precision(F32_PDF) on small clouds and forests (round 6): the stop rule's log-likelihood in float32.
     (i) batch == serial bit for bit in that mode too (trees, iteration counts, q traces); (ii) against the float64 mode:
@@ -75,6 +76,8 @@ def test_build_batch_float32_pdfs_is_bitwise_the_serial_build_and_keeps_the_floa
     T = hgmm_tree.n_total(L)
     idx = np.random.RandomState(72).randint(T, size=T)
     idx = np.minimum(idx, min(len(c) for c in clouds) - 1)
+    if L >= 5:    # (wrapped, not clamped: as in test_build_batch_is_bitwise_the_serial_build)
+        idx = np.random.RandomState(72).randint(T, size=T) % min(len(c) for c in clouds)
     (pi64, mu64, cov64), iters64, traces64 = batch_build(ctx, clouds, L, ls, 1e-4, idx, sig2)
     ctx.tree_set_precision(np.float32)
     try:

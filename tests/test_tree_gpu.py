@@ -225,7 +225,9 @@ def test_standalone_tree_steps_match_oracle(ctx):
 def test_deep_trees_properties(ctx, L, n, max_iters):
     """Deep trees (37448 / 299592 nodes, most of them dead): the partition tables, chunk lists and
     the 2-D log-likelihood grid at their largest, checked through oracle-free properties and one
-    oracle log-likelihood of the last level (L = 5 only; the oracle is O(N 8^L))."""
+    oracle log-likelihood of the last level (L = 5 only here: on these 20 000 / 30 000 points the oracle's
+    log-likelihood is O(N x live nodes)).  The oracle is not too expensive at L = 6 as such -- with few live nodes and a
+    small cloud it runs in seconds: tests/test_tree_build_depth_gpu.py holds whole L = 5 and L = 6 builds to it."""
     rs = np.random.RandomState(L)
     centres = rs.rand(64, 3)
     P = centres[rs.randint(64, size=n)] + 0.02 * rs.randn(n, 3)
