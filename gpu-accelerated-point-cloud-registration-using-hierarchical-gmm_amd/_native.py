@@ -27,6 +27,23 @@ KERNEL_IDS = {"flat_estep": 0, "flat_fused": 1, "flat_mstep": 2, "tree_estep": 3
 CHI2_3_99 = 11.344866730144373
 # the 0.999 quantile: a suggested ``maha2_gate`` of the registration E-step (Context.tree_set_reg_gate), not a default
 CHI2_3_999 = 16.27
+# include/hgmm.h: HGMM_TREE_BATCH_MULTI_MAX_BYTES, the cap on the sums of one hgmm_tree_register_batch_multi call
+BATCH_MULTI_MAX_BYTES = 4 << 30
+
+
+def plan_batch_multi_rounds(T, owners, cap=None):
+    """Split the hypotheses ``owners`` (the pair each one names) of a forest whose trees have ``T`` nodes into consecutive
+    rounds whose fixed-point sums -- 32 T bytes per hypothesis -- each fit ``cap`` bytes (default: the library's cap of one
+    hgmm_tree_register_batch_multi call).  -> [(begin, end), ...] covering range(len(owners)) in order; the ``pair[]``
+    indirection makes every such slice a valid call of its own.  One hypothesis above the cap: ValueError naming it."""
+    cap = BATCH_MULTI_MAX_BYTES if cap is None else int(cap)
+    per = 32 * int(T)
+    n = len(owners)
+    if n and per > cap:
+        raise ValueError("hypothesis 0 (pair %d) alone takes %d bytes of sums at T = %d nodes, more than the cap of %d"
+                         % (int(owners[0]), per, int(T), cap))
+    fit = max(cap // per, 1)
+    return [(a, min(a + fit, n)) for a in range(0, n, fit)]
 
 
 class HgmmError(RuntimeError):
@@ -185,6 +202,9 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_tree_register_multi", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double, _vp,
                                                _vp, _vp, _vp])
         _sig(lib, "hgmm_tree_score_multi", [ctx, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp])
+        _sig(lib, "hgmm_tree_register_batch_multi", [ctx, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_double,
+                                                     _vp, _vp, _vp, _vp])
+        _sig(lib, "hgmm_tree_score_batch_multi", [ctx, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp])
         _sig(lib, "hgmm_voxel_downsample_f64", [ctx, _vp, C.c_int64, C.c_double, _i64p])
         _sig(lib, "hgmm_voxel_downsample_f32", [ctx, _vp, C.c_int64, C.c_double, _i64p])
         _sig(lib, "hgmm_voxel_downsample_batch_f64", [ctx, C.c_int, C.POINTER(_vp), _i64p, C.c_double, _i64p])
@@ -1172,7 +1192,7 @@ class Context:
         """Mahalanobis gate of the registration E-step (hgmm_tree_set_reg_gate): a (point, node) pair whose squared
         Mahalanobis distance exceeds ``maha2_gate`` adds nothing to that node's moments; the descent is unchanged.
         ``np.inf`` (the default of a context): off.  Honoured by tree_reg_estep, tree_reg_normal, tree_register,
-        tree_register_multi and tree_register_batch, not by the scores; in force until set again.  The library refuses
+        tree_register_multi, tree_register_batch and tree_register_batch_multi, not by the scores; in force until set again.  The library refuses
         NaN and values <= 0 (HgmmError) and keeps the previous gate.  ``CHI2_3_999`` is a reasonable value."""
         self._check(self.lib.hgmm_tree_set_reg_gate(self.h, float(maha2_gate)))
         return self
@@ -1459,6 +1479,44 @@ class Context:
         K = rot.shape[0]
         t = np.ascontiguousarray(t, dtype=np.float64).reshape(K, 3)
         return self._score_poses(self.lib.hgmm_tree_score_multi, K, rot, t, scale, lambda_c, maha2_max)
+
+    # -- batched multi-start: R hypotheses over the resident forest, hypothesis r on pair[r] -------------------------------------
+    @staticmethod
+    def _pair_rows(pair, what):
+        pair = np.ascontiguousarray(pair)
+        if pair.ndim != 1 or (pair.size and not np.issubdtype(pair.dtype, np.integer)):
+            raise ValueError("%s: pair must be a list of integers, one per hypothesis" % what)
+        return np.ascontiguousarray(pair, dtype=np.int32)
+
+    def tree_register_batch_multi(self, pair, rot, t, scale=1.0, lambda_c=0.01, max_iter=20, tol=1.0e-4, q_prev=None,
+                                  want_trace=False):
+        """:meth:`tree_register` from R start poses over the resident forest in the same launches
+        (hgmm_tree_register_batch_multi): hypothesis r runs on (tree ``pair[r]``, target ``pair[r]``), any number per pair in
+        any order, each bitwise the serial call on that pair from that start.  ``pair`` [R], ``rot`` [R,3,3], ``t`` [R,3].
+        -> (rot [R,3,3], t [R,3], iterations [R], q [R] (NaN: none), status [R], traces or None)."""
+        pair = self._pair_rows(pair, "tree_register_batch_multi")
+        if len(pair) != np.asarray(rot).size // 9:
+            raise ValueError("tree_register_batch_multi: %d pairs named for %d poses" % (len(pair), np.asarray(rot).size // 9))
+        lib = self.lib
+
+        def entry(h, n, *rest):
+            return lib.hgmm_tree_register_batch_multi(h, n, _ptr(pair), *rest)
+        return self._register_poses(entry, rot, t, scale, lambda_c, max_iter, tol, q_prev, want_trace)
+
+    def tree_score_batch_multi(self, pair, rot, t, scale=1.0, lambda_c=0.01, maha2_max=CHI2_3_99):
+        """:meth:`tree_score`'s summary of target ``pair[r]`` against tree ``pair[r]`` of the resident forest at R poses in one
+        launch (hgmm_tree_score_batch_multi), each bitwise the serial call's.  -> summaries [R,8]."""
+        pair = self._pair_rows(pair, "tree_score_batch_multi")
+        rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 3, 3)
+        R = rot.shape[0]
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(R, 3)
+        if len(pair) != R:
+            raise ValueError("tree_score_batch_multi: %d pairs named for %d poses" % (len(pair), R))
+        lib = self.lib
+
+        def entry(h, n, *rest):
+            return lib.hgmm_tree_score_batch_multi(h, n, _ptr(pair), *rest)
+        return self._score_poses(entry, R, rot, t, scale, lambda_c, maha2_max)
 
     @staticmethod
     def _node_tables(pi, mu, cov):

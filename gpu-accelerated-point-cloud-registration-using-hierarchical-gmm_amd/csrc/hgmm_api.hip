@@ -777,7 +777,7 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->km_closest, &c->km_block, &c->km_centres, &c->km_ids, &c->km_rand, &c->km_labels,
                       &c->km_mind2, &c->km_partial, &c->km_out, &c->gt_buf, &c->t_momq, &c->t_flags, &c->exp_tab2, &c->t_tickets,
                       &c->fr_pi, &c->fr_mu, &c->fr_cov, &c->fr_prep, &c->fr_mom, &c->fr_clouds, &c->fr_q, &c->fr_trace, &c->fr_tg,
-                      &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w.buf, &c->forest.tg_w.buf,
+                      &c->fr_momq, &c->fr_reg, &c->tm_momq, &c->tm_reg, &c->fm_momq, &c->fm_reg, &c->ff_origin, &c->ff_clocks, &c->tgt_w.buf, &c->forest.tg_w.buf,
                       &c->src.buf, &c->forest.src_w.buf, &c->t_w2, &c->t_w3, &c->flat_w.buf, &c->f_lpn_rows,
                       &c->vx_in, &c->vx_tab, &c->vx_keys, &c->vx_keys2, &c->vx_rows, &c->vx_rows2, &c->vx_heads, &c->vx_tmp,
                       &c->vx_cent, &c->vx_cnt, &c->vx_hand,

@@ -190,6 +190,7 @@ struct ForestState {
     std::vector<double> tg_rmax;          // largest |x| per target
     int64_t tg_pad = 0;
     bool momq_clean = false;              // every word of fr_momq is zero (tree_host.h: MomqScope)
+    bool multi_momq_clean = false;        // ... of fm_momq, the sums of hgmm_tree_register_batch_multi's R hypotheses
     MemberWeights tg_w;                   // hgmm_tree_set_target_weights_batch: [tg_pad] parallel to fr_tg; new targets drop them
     std::vector<int64_t> src_counts;      // hgmm_set_points_batch_*: the resident cloud's members (empty: not a batch cloud)
     MemberWeights src_w;                  // hgmm_tree_set_source_weights_batch: [n_pad] parallel to x_soa64; a new cloud drops them
@@ -308,6 +309,9 @@ struct hgmm_ctx {
     // multi-start (hgmm_tree_register_multi / _score_multi): K start poses on the SERIAL tree and target, buffers of their own
     hgmm::DevBuf tm_momq;                     // uint64 [K][T][4] registration sums, one slice per hypothesis
     hgmm::DevBuf tm_reg;                      // per-hypothesis registration table + the 28 numbers per hypothesis
+    // batched multi-start (hgmm_tree_register_batch_multi / _score_batch_multi): R hypotheses over the forest, likewise
+    hgmm::DevBuf fm_momq;                     // uint64 [R][T][4]
+    hgmm::DevBuf fm_reg;                      // per-hypothesis registration table + the 28 numbers per hypothesis
 
     // ---- KMeans initialiser (float64, on x_soa64) -----------------------------------
     hgmm::DevBuf km_closest;                  // double [n_pad] k-means++: min squared distance so far

@@ -320,6 +320,79 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
     }
 }
 
+// ---- a third kind of set: R registrations OVER the resident forest (hgmm_tree_register_batch_multi / _score_batch_multi) --------
+// Registration r reads the tree and the target of pair owner[r] -- `prep + PREP_N T owner`, and the table entry's tg_first /
+// tg_count / tg_wtotal are that pair's -- and owns slice r of everything that is written: the sums, the table, the 28 numbers,
+// the score's shares, its progress / sequence word.  The owner travels in the entry's spare word (ForestRegPair::owner).  These
+// are kernels of their own over the same bodies, so that the forest's and the shared set's kernels above stay the code they
+// were; a workgroup still serves one registration, and the grid is the one-dimensional gx x R.
+template <bool GATED, bool WEIGHTED>
+__global__ __launch_bounds__(CH) void forest_owned_reg_estep_kernel(const double* __restrict__ tg, int64_t tg_pad,
+                                                                    const ForestRegPair* __restrict__ tab,
+                                                                    const double* __restrict__ prep, int T, int L,
+                                                                    double lambda_c, unsigned long long* __restrict__ momq,
+                                                                    int gx, double maha2_gate, const double* __restrict__ w) {
+    __shared__ unsigned long long lds[REG_LDS_NODES * 4];
+    const int item = (int)blockIdx.x;                  // (gx x R items: registration r, chunk bx)
+    const int r = item / gx, bx = item - r * gx;
+    const ForestRegPair* pr = tab + r;
+    const int first = pr->tg_first, active = pr->active, count = pr->tg_count, owner = pr->owner;
+    if (!active || (int64_t)bx * CH >= count) return;
+    const Rigid tf = pr->tf;
+    const double inv_d = pr->inv_d, fix_scale = pr->fix_scale;
+    const int64_t li = (int64_t)bx * CH + threadIdx.x;
+    tree_reg_estep_body<4, GATED, WEIGHTED>(first + li, li < count, tg, tg_pad, tf, reg_prep_of<false>(prep, T, owner), L, lambda_c,
+                                            inv_d, fix_scale, momq + (size_t)4 * T * r, lds, maha2_gate, w);
+}
+
+// partial: [R][gx][6]; forest_score_finish_kernel adds the shares of every entry as it does for the other sets
+template <bool WEIGHTED>
+__global__ __launch_bounds__(CH) void forest_owned_score_kernel(const double* __restrict__ tg, int64_t tg_pad,
+                                                                const ForestRegPair* __restrict__ tab,
+                                                                const double* __restrict__ prep, int T, int L, double lambda_c,
+                                                                double maha2_max, double* __restrict__ partial, int gx,
+                                                                const double* __restrict__ w) {
+    const int item = (int)blockIdx.x;
+    const int r = item / gx, bx = item - r * gx;
+    const ForestRegPair* pr = tab + r;
+    const int first = pr->tg_first, count = pr->tg_count, owner = pr->owner;
+    if ((int64_t)bx * CH >= count) return;
+    const Rigid tf = pr->tf;
+    const int64_t li = (int64_t)bx * CH + threadIdx.x;
+    tree_score_body<WEIGHTED>(first + li, li, li < count, tg, tg_pad, tf, reg_prep_of<false>(prep, T, owner), L, lambda_c, maha2_max,
+                              nullptr, nullptr, nullptr, partial + (size_t)SCORE_NSUM * item, w);
+}
+
+__global__ __launch_bounds__(256) void forest_owned_reg_normal_kernel(unsigned long long* __restrict__ momq,
+                                                                      const ForestRegPair* __restrict__ tab,
+                                                                      const double* __restrict__ prep, int T,
+                                                                      double* __restrict__ out, double* host_out,
+                                                                      unsigned long long* host_seq, unsigned long long seq) {
+    const int r = blockIdx.x;
+    const ForestRegPair* pr = tab + r;
+    if (!pr->active) return;
+    tree_reg_normal_body(momq + (size_t)4 * T * r, pr->d_ext, pr->inv_scale, reg_prep_of<false>(prep, T, pr->owner), T, out + 28 * r,
+                         host_out + 28 * r, host_seq + r, seq);
+}
+
+__global__ __launch_bounds__(256) void forest_owned_reg_solve_kernel(unsigned long long* __restrict__ momq, ForestRegPair* tab,
+                                                                     const double* __restrict__ prep, int T,
+                                                                     double* __restrict__ out, double tol, int max_iter,
+                                                                     double* __restrict__ trace, unsigned long long* host_words) {
+    const int r = blockIdx.x;
+    ForestRegPair* pr = tab + r;
+    if (!pr->active) return;
+    tree_reg_normal_body(momq + (size_t)4 * T * r, pr->d_ext, pr->inv_scale, reg_prep_of<false>(prep, T, pr->owner), T, out + 28 * r,
+                         nullptr, nullptr, 0ull);
+    __syncthreads();                                         // (the 28 sums are in `out`, written by this workgroup)
+    if (threadIdx.x == 0) {
+        const int it = pr->it;
+        reg_device_step(out + 28 * r, pr, tol, max_iter, trace ? trace + ((size_t)r * max_iter + it) * 13 : nullptr);
+        __hip_atomic_store(host_words + r, ((unsigned long long)(pr->active ? 0 : 1) << 32) | (unsigned long long)(unsigned)pr->it,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -328,8 +401,23 @@ __global__ __launch_bounds__(256) void forest_reg_solve_kernel(unsigned long lon
 struct RegEstepFamily { template <bool... FLAGS> static auto kernel() { return forest_reg_estep_kernel<4, FLAGS...>; } };
 struct RegSolveFamily { template <bool SHARED> static auto kernel() { return forest_reg_solve_kernel<SHARED>; } };
 struct ScoreFamily { template <bool SHARED, bool W> static auto kernel() { return forest_score_kernel<SHARED, W>; } };
+// ... and of a set over the forest (RegSet::owned), whose kernels take the arguments of the others
+struct OwnedRegEstepFamily { template <bool G, bool W> static auto kernel() { return forest_owned_reg_estep_kernel<G, W>; } };
+struct OwnedScoreFamily { template <bool W> static auto kernel() { return forest_owned_score_kernel<W>; } };
 static auto reg_estep_kernel_for(const hgmm_ctx* c, const RegSet& set) {
-    return kernel_for<RegEstepFamily>(set.shared_tree, std::isfinite(c->tree.reg_gate), set.w != nullptr);
+    const bool gated = std::isfinite(c->tree.reg_gate), weighted = set.w != nullptr;
+    if (set.owned) return kernel_for<OwnedRegEstepFamily>(gated, weighted);
+    return kernel_for<RegEstepFamily>(set.shared_tree, gated, weighted);
+}
+static auto reg_solve_kernel_for(const RegSet& set) {
+    return set.owned ? forest_owned_reg_solve_kernel : kernel_for<RegSolveFamily>(set.shared_tree);
+}
+static auto reg_normal_kernel_for(const RegSet& set) {
+    if (set.owned) return forest_owned_reg_normal_kernel;
+    return set.shared_tree ? forest_reg_normal_kernel<true> : forest_reg_normal_kernel<false>;
+}
+static auto score_kernel_for(const RegSet& set) {
+    return set.owned ? kernel_for<OwnedScoreFamily>(set.w != nullptr) : kernel_for<ScoreFamily>(set.shared_tree, set.w != nullptr);
 }
 
 // The registration loop of a set with the device on its own (reg_device_solve): every iteration is two launches -- the
@@ -347,7 +435,7 @@ static int forest_register_on_device(hgmm_ctx* c, const RegSet& set, double* rot
     const size_t trace_bytes = trace ? sizeof(double) * 13 * (size_t)max_iter * B : 0;
     if (trace) HGMM_TRY(ensure(c, c->fr_trace, trace_bytes));
     const auto estep_kernel = reg_estep_kernel_for(c, set);
-    const auto solve_kernel = kernel_for<RegSolveFamily>(set.shared_tree);
+    const auto solve_kernel = reg_solve_kernel_for(set);
     unsigned long long* momq = set.momq->as<unsigned long long>();
     double* d_trace = trace ? c->fr_trace.as<double>() : nullptr;
     HandOver* hand = nullptr;
@@ -408,7 +496,7 @@ static int forest_register_on_host(hgmm_ctx* c, const RegSet& set, double* rot, 
     RegTable tb;
     HGMM_TRY(reg_table(c, *set.table, B, &tb));
     const auto estep_kernel = reg_estep_kernel_for(c, set);
-    const auto normal_kernel = set.shared_tree ? forest_reg_normal_kernel<true> : forest_reg_normal_kernel<false>;
+    const auto normal_kernel = reg_normal_kernel_for(set);
     unsigned long long* momq = set.momq->as<unsigned long long>();
     std::vector<ForestRegPair> tab(B);
     std::vector<char> active(B, 1);
@@ -492,7 +580,7 @@ int score_set(hgmm_ctx* c, const RegSet& set, const double* rot, const double* t
     HGMM_TRY(stage_h2d(c, tb.pairs, tab.data(), sizeof(ForestRegPair) * B));
     {
         ProfScope prof(c, HGMM_K_TREE_SCORE);
-        const auto kernel = kernel_for<ScoreFamily>(set.shared_tree, set.w != nullptr);
+        const auto kernel = score_kernel_for(set);
         kernel<<<gx * (unsigned)B, CH, 0, c->stream>>>(set.tg, set.tg_pad, tb.pairs, set.prep, set.T, set.L, lambda_c, maha2_max,
                                                       partial, (int)gx, set.w);
     }
@@ -921,4 +1009,56 @@ extern "C" int hgmm_tree_score_multi(hgmm_ctx* c, int K, const double* rot, cons
     if (!summary_out) return fail(c, HGMM_ERR_ARG, "tree_score (multi): summary_out is NULL");
     if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "tree_score (multi): maha2_max is NaN");
     return score_set(c, reg_set_pair(c, K, true), rot, t, scale, lambda_c, maha2_max, summary_out);
+}
+
+// ---- batched multi-start: R hypotheses over the resident FOREST, hypothesis r on pair[r] (include/hgmm.h) ---------------------
+// what both entries ask of the context and of `pair`; nothing resident has been touched when this refuses
+static int batch_multi_state(hgmm_ctx* c, const char* what, int R, const int32_t* pair) {
+    const ForestState& F = c->forest;
+    if (c->comm_on()) return fail(c, HGMM_ERR_STATE, "%s: hypotheses over a forest take no communicator", what);
+    if (!F.nodes_ready) return fail(c, HGMM_ERR_STATE, "%s: no forest (hgmm_tree_build_batch first)", what);
+    if (F.tg_B < 1) return fail(c, HGMM_ERR_STATE, "%s: no targets (hgmm_tree_set_targets_batch first)", what);
+    if (F.B != F.tg_B) return fail(c, HGMM_ERR_STATE, "%s: %d trees, but %d targets are resident", what, F.B, F.tg_B);
+    if (R < 1) return fail(c, HGMM_ERR_ARG, "%s: R = %d hypotheses (at least one)", what, R);
+    if (!pair) return fail(c, HGMM_ERR_ARG, "%s: pair is NULL", what);
+    int64_t longest = 0;
+    for (int r = 0; r < R; ++r) {
+        if (pair[r] < 0 || pair[r] >= F.B)
+            return fail(c, HGMM_ERR_ARG, "%s: pair[%d] = %d, but the forest has the pairs 0..%d", what, r, (int)pair[r], F.B - 1);
+        longest = std::max(longest, F.tg_counts[pair[r]]);
+    }
+    if ((uint64_t)nblk(longest, CH) * (uint64_t)R > 0x7fffffffull)                 // (the grid: one workgroup per hypothesis and chunk)
+        return fail(c, HGMM_ERR_ARG, "%s: %d hypotheses x %lld target points is more than 2^31 - 1 workgroups", what, R,
+                    (long long)longest);
+    // the sums: 32 T bytes per hypothesis (1.2 MB at L = 5, 9.6 MB at L = 6), capped so that a long list of hypotheses of a
+    // deep forest is a refusal the caller can act on (split it: any subset is a valid call), not a failed allocation
+    const uint64_t per = (uint64_t)sizeof(unsigned long long) * 4 * (uint64_t)F.T;
+    if (per * (uint64_t)R > HGMM_TREE_BATCH_MULTI_MAX_BYTES)
+        return fail(c, HGMM_ERR_ARG, "%s: the sums of R = %d hypotheses at L = %d take %llu bytes, more than the cap of %llu; "
+                    "at most R = %llu hypotheses fit into one call", what, R, F.L, (unsigned long long)(per * (uint64_t)R),
+                    (unsigned long long)HGMM_TREE_BATCH_MULTI_MAX_BYTES, (unsigned long long)(HGMM_TREE_BATCH_MULTI_MAX_BYTES / per));
+    return HGMM_OK;
+}
+
+extern "C" int hgmm_tree_register_batch_multi(hgmm_ctx* c, int R, const int32_t* pair, double* rot, double* t, double scale,
+                                              double lambda_c, int max_iter, double tol, double* q_prev_inout,
+                                              int32_t* iters_out, int32_t* status_out, double* trace) {
+    HGMM_ENTER(c);
+    const char* what = "tree_register (batch multi)";
+    HGMM_TRY(batch_multi_state(c, what, R, pair));
+    if (!rot || !t) return fail(c, HGMM_ERR_ARG, "%s: rot / t is NULL (R start poses are the call's input)", what);
+    if (!q_prev_inout || !iters_out || !status_out) return fail(c, HGMM_ERR_ARG, "%s: NULL output argument", what);
+    return register_set(c, reg_set_forest_multi(c, R, pair), rot, t, scale, lambda_c, max_iter, tol, q_prev_inout, iters_out,
+                        status_out, trace);
+}
+
+extern "C" int hgmm_tree_score_batch_multi(hgmm_ctx* c, int R, const int32_t* pair, const double* rot, const double* t,
+                                           double scale, double lambda_c, double maha2_max, double* summary_out) {
+    HGMM_ENTER(c);
+    const char* what = "tree_score (batch multi)";
+    HGMM_TRY(batch_multi_state(c, what, R, pair));
+    if (!rot || !t) return fail(c, HGMM_ERR_ARG, "%s: rot / t is NULL (R poses are the call's input)", what);
+    if (!summary_out) return fail(c, HGMM_ERR_ARG, "%s: summary_out is NULL", what);
+    if (maha2_max != maha2_max) return fail(c, HGMM_ERR_ARG, "%s: maha2_max is NaN", what);
+    return score_set(c, reg_set_forest_multi(c, R, pair), rot, t, scale, lambda_c, maha2_max, summary_out);
 }

@@ -2158,7 +2158,7 @@ struct ForestRegPair {
     Rigid tf;
     double inv_d, fix_scale, d_ext, inv_scale;
     int tg_first, tg_count;
-    int active, pad;
+    int active, owner;                   // owner: the forest pair whose tree it reads (sets over the forest only, else 0)
     double q_prev, tg_rmax, mu_rmax;     // q of the previous iteration (valid with has_q), extent bounds of the encoding
     int has_q, it, status, pad2;         // iterations done; 0: running / budget used up, 1: |dq| < tol, 2: ill-conditioned
     double tg_wtotal;                    // n_all of reg_encoding: the sum of the target's weights, (double)tg_count without weights

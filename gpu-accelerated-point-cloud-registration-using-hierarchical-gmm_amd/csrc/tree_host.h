@@ -275,13 +275,16 @@ inline int tree_mu_rmax_resident(hgmm_ctx* c) {
 
 // ---- a set of B registrations: what the E-step, normal-equation, solve and score launches of tree_batch.hip work on ------
 // Either the pairs of the resident forest (hgmm_tree_register_batch / _score_batch) or B start poses of the serial pair
-// (hgmm_tree_register_multi / _score_multi; hgmm_tree_register's device loop with B = 1).
+// (hgmm_tree_register_multi / _score_multi; hgmm_tree_register's device loop with B = 1), or R hypotheses over the forest,
+// each naming its pair (hgmm_tree_register_batch_multi / _score_batch_multi).
 struct RegSet {
     struct One {
         int64_t first, count;                  // its target's slice of `tg`
         double rmax, mu_rmax;                  // largest |x| of the target, largest |mu_j| of the tree: reg_extent
         double wsum;                           // sum of the target's weights; (double)count without
+        int owner = 0;                         // (owned sets) the forest pair whose tree and target these are
     };
+    bool owned = false;                        // hypotheses over the forest: prep is [F.B][T], member r reads tree regs[r].owner
     bool shared_tree = false;                  // one tree and one target for all (the SHARED kernels): prep is [T], not [B][T]
     std::vector<One> regs;                     // [B]
     const double* tg = nullptr;                // device: the targets' structure of arrays [3][tg_pad]
@@ -316,6 +319,24 @@ inline RegSet reg_set_forest(hgmm_ctx* c) {
     s.momq_clean = &c->forest.momq_clean;
     s.momq_bytes = sizeof(unsigned long long) * 4 * (size_t)F.T * F.B;
     s.table = &c->fr_reg;
+    return s;
+}
+// R hypotheses over the resident forest, hypothesis r on (tree pair[r], target pair[r]) (the caller has checked the state and
+// every pair[r]): on fm_momq / fm_reg, which leaves the sums and the table of hgmm_tree_register_batch alone
+inline RegSet reg_set_forest_multi(hgmm_ctx* c, int R, const int32_t* pair) {
+    const ForestState& F = c->forest;
+    RegSet s = reg_set_forest(c);
+    const std::vector<RegSet::One> pairs = std::move(s.regs);
+    s.regs.clear();
+    for (int r = 0; r < R; ++r) {
+        s.regs.push_back(pairs[pair[r]]);
+        s.regs.back().owner = pair[r];
+    }
+    s.owned = true;
+    s.momq = &c->fm_momq;
+    s.momq_clean = &c->forest.multi_momq_clean;
+    s.momq_bytes = sizeof(unsigned long long) * 4 * (size_t)F.T * R;
+    s.table = &c->fm_reg;
     return s;
 }
 // K start poses of the serial pair (the caller has checked the tree and the target; tree.mu_rmax: tree_mu_rmax_resident,
@@ -365,6 +386,7 @@ inline ForestRegPair reg_pair(const RegSet::One& r) {
     pr.tg_first = (int)r.first;
     pr.tg_count = (int)r.count;
     pr.tg_wtotal = r.wsum;
+    pr.owner = r.owner;
     return pr;
 }
 // ... of one that takes part: its transform and the fixed-point encoding of its next E-step

@@ -23,6 +23,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from .. import _native
 from .._native import CHI2_3_99, CHI2_3_999, Context, VoxelCloud, VoxelResult, default_context  # noqa: F401
 
 eps = np.float32(1.0e-15)     # hgmm_gpu.py:29
@@ -854,10 +855,95 @@ def registration_gmmtree(source, target, maxiter=20, tol=1.0e-4, callbacks=[], r
 BATCH_MAX_POINTS = 400000       # hgmm_tree_build_batch takes clouds below this size (csrc/tree_batch.hip)
 
 
+def _batch_starts(starts, B):
+    """``starts=`` of :func:`registration_gmmtree_batch` -> (B lists of start poses, their common scale).  One list of
+    :class:`RigidTransformation`s serves every pair; a list of lists is one list per pair (they may differ in length)."""
+    starts = list(starts)
+    if starts and all(isinstance(s, (list, tuple)) for s in starts):
+        if len(starts) != B:
+            raise ValueError("starts must be one list of start poses, or one such list per pair: %d lists for %d pairs"
+                             % (len(starts), B))
+        per_pair = [list(s) for s in starts]
+    else:
+        per_pair = [starts] * B
+    for b, s in enumerate(per_pair):
+        if not s:
+            raise ValueError("starts: pair %d has no start pose" % b)
+    scale = float(per_pair[0][0].scale)
+    for b, ss in enumerate(per_pair):
+        if any(float(s.scale) != scale for s in ss):
+            raise ValueError("starts: the start poses of a call must share one scale (pair %d differs)" % b)
+    return per_pair, scale
+
+
+def _multistart_info(B):
+    return {"build_iters": [None] * B, "registration_iters": [None] * B, "status": [None] * B, "score": [None] * B,
+            "hypothesis_iters": [None] * B, "hypothesis_status": [None] * B, "hypothesis_scores": [None] * B}
+
+
+def _register_batch_multistart(ctx, starts, scale, tgts, ws, tree_level, lambda_c, ls, ld, sig2, maxiter, tol, solve_on_device,
+                               gate, maha2_max, clock):
+    """The registration half of :func:`registration_gmmtree_batch` with ``starts``: the forest and its targets are resident on
+    ``ctx``.  All hypotheses of all pairs in the launches of one (``hgmm_tree_register_batch_multi``, in consecutive rounds
+    where the sums' cap demands), those that left at status 2 finished through the serial entries, one
+    ``hgmm_tree_score_batch_multi`` at the final poses, the winner per pair by :func:`best_hypothesis`.
+    -> (one :class:`MultiStartResult` per pair, per-pair lists of every hypothesis's iterations, status and TreeScore)."""
+    B = len(tgts)
+    owners = np.repeat(np.arange(B, dtype=np.int32), [len(s) for s in starts])
+    flat = [s for ss in starts for s in ss]
+    rot = np.stack([np.asarray(s.rot, dtype=np.float64).reshape(3, 3) for s in flat])
+    t = np.stack([np.asarray(s.t, dtype=np.float64).reshape(3) for s in flat])
+    R = len(flat)
+    iters, q, status = np.zeros(R, np.int32), np.full(R, np.nan), np.zeros(R, np.int32)
+    rounds = _native.plan_batch_multi_rounds(n_total_nodes(tree_level), owners)
+    with _reg_gate(ctx, gate):                                   # (the rounds AND the hypotheses finished serially below)
+        with (ctx.config(reg_device_solve=1) if solve_on_device else contextlib.nullcontext()):
+            for a, e in rounds:
+                rot[a:e], t[a:e], iters[a:e], q[a:e], status[a:e], _ = ctx.tree_register_batch_multi(
+                    owners[a:e], rot[a:e], t[a:e], scale, lambda_c, maxiter, tol)
+        clock.append(time.perf_counter())
+        iters = [int(v) for v in iters]
+        serial = {}                                              # hypothesis -> its summary from the serial entry
+        for r in np.nonzero(status == 2)[0]:                     # finish this hypothesis through the serial entries
+            b = int(owners[r])
+            gt = GMMTree(tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, ctx=ctx,
+                         solve_on_device=solve_on_device, maha2_gate=gate)
+            gt.set_nodes(*ctx.tree_get_nodes_batch(b, tree_level))
+            gt._tf_result = RigidTransformation(rot[r].copy(), t[r].copy(), scale)
+            ctx.tree_set_nodes(tree_level, gt._mixingCoeff, gt._mean, gt._covar)
+            _set_target(ctx, tgts[b], ws[b])
+            res = gt._registration_in_library(maxiter, tol, _resume=(iters[r], None if np.isnan(q[r]) else float(q[r]), True))
+            rot[r], t[r] = gt._tf_result.rot, gt._tf_result.t
+            q[r] = float(res.q[0]) if np.size(res.q) else np.nan
+            iters[r] = int(gt.n_iter_)
+            serial[int(r)] = ctx.tree_score(rot[r], t[r], scale, lambda_c, maha2_max, ())[0]
+    sums = np.concatenate([ctx.tree_score_batch_multi(owners[a:e], rot[a:e], t[a:e], scale, lambda_c, maha2_max)
+                           for a, e in rounds])
+    for r, summary in serial.items():                            # (its pose moved on: the serial entry, at the final pose)
+        sums[r] = summary
+    clock.append(time.perf_counter())
+    out, every = [], ([], [], [])
+    at = 0
+    for b in range(B):
+        rows = slice(at, at + len(starts[b]))
+        at += len(starts[b])
+        best = best_hypothesis(sums[rows], rot[rows], t[rows])
+        r = rows.start + best
+        tf = RigidTransformation(rot[r].copy(), t[r].copy(), scale)
+        scores = [tree_score_from_summary(v) for v in sums[rows]]
+        win = MultiStartResult(tf.inverse(), np.array([q[r]]) if not np.isnan(q[r]) else np.array([]), scores[best])
+        win.best_index_, win.n_iter_ = int(best), iters[r]
+        out.append(win)
+        every[0].append(iters[rows])
+        every[1].append([int(v) for v in status[rows]])
+        every[2].append(scores)
+    return out, every
+
+
 def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | None = None, tree_level=5, lambda_c=0.01,
                                ls=20, ld=1.0e-4, sig2=0.004, init_idx=None, return_info=False, pdf_dtype=None,
                                solve_on_device=False, score=False, maha2_gate=None, target_weights=None, source_weights=None,
-                               voxel_size=None):
+                               voxel_size=None, starts=None, maha2_max=CHI2_3_99):
     """``[registration_gmmtree(s, t, maxiter, tol, tree_level=..., ...) for s, t in pairs]`` (hgmm_gpu.py:802-807 per pair)
     with ALL pairs in the same launches: the B source clouds are one resident forest (``hgmm_tree_build_batch``: levels in
     lock-step, one stop rule per cloud), the B targets are registered against their trees together
@@ -893,6 +979,19 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     DISTINCT array object is down-sampled once (a chain ``[(a, b), (b, c)]`` down-samples three clouds), and nothing but the
     results comes back to the host: the clouds travel as :class:`VoxelCloud`s, which the pairs may also hold from the start.
 
+    ``starts`` (default None: every pair from the identity, the call as it was): multi-start for every pair of the batch --
+    one list of start poses (e.g. :func:`rotation_starts`) used for every pair, or a list with one such list per pair, which
+    may differ in length; all starts of the call share one scale.  The forest is built and uploaded as without; then ALL
+    hypotheses of ALL pairs run through the launches of one (``hgmm_tree_register_batch_multi``: hypothesis r names its pair
+    and owns its slice of the sums; in consecutive rounds where the sums' cap demands), are scored together
+    (``hgmm_tree_score_batch_multi``, inlier bound ``maha2_max``) and the best one per pair wins (:func:`best_hypothesis`).
+    The result is one :class:`MultiStartResult` per pair -- ``best_index_``, ``n_iter_`` and a summary-only
+    :class:`TreeScore` -- whose ``transformation``, ``q``, ``best_index_``, ``n_iter_`` and score scalars are bitwise those
+    of ``registration_gmmtree(s, t, maxiter, tol, starts=..., same keywords)``.  With ``return_info`` the dict's
+    ``"score"``, ``"registration_iters"`` and ``"status"`` are the winners', and ``"hypothesis_iters"`` /
+    ``"hypothesis_status"`` / ``"hypothesis_scores"`` hold per pair the list over its hypotheses (iterations and status are
+    None for a pair of 400 000 points or more, which runs :meth:`GMMTree.registration_multistart` serially).
+
     -> list of ``MstepResult(transformation, q)`` in the order of ``pairs`` (+ a dict with the per-pair build / registration
     iteration counts with ``return_info``)."""
     gate = _gate_arg(maha2_gate)
@@ -900,6 +999,8 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     pairs = list(pairs)
     if not pairs:
         return ([], {}) if return_info else []
+    if starts is not None:                          # (refused before the device is reached)
+        starts, starts_scale = _batch_starts(starts, len(pairs))
     if voxel_size is not None:
         pairs = _voxel_pairs(ctx, pairs, voxel_size, [w for ws in (target_weights, source_weights) if ws is not None for w in ws])
     if target_weights is not None and len(target_weights) != len(pairs):
@@ -923,9 +1024,17 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
                 "status": [None] * len(pairs)}
         if score:
             info["score"] = [None] * len(pairs)
+        if starts is not None:
+            info.update({k: v for k, v in _multistart_info(len(pairs)).items() if k != "build_iters"})
         for k in big:
             gt = GMMTree(pairs[k][0], tree_level=tree_level, lambda_c=lambda_c, ls=ls, ld=ld, sig2=sig2, init_idx=init_idx, ctx=ctx,
                          solve_on_device=solve_on_device, maha2_gate=gate, source_weights=sws[k])
+            if starts is not None:
+                tgt = _points(pairs[k][1]) if ws[k] is None else WeightedPoints(_points(pairs[k][1]), ws[k])
+                out[k], every = gt.registration_multistart(tgt, starts[k], maxiter, tol, maha2_max, return_all=True)
+                info["registration_iters"][k], info["status"][k], info["score"][k] = int(gt.n_iter_), 0, out[k].score
+                info["hypothesis_scores"][k] = [e.score for e in every]
+                continue
             out[k] = gt.registration(_points(pairs[k][1]), maxiter, tol, weights=ws[k])
             info["registration_iters"][k], info["status"][k] = int(gt.n_iter_), 0
             if score:
@@ -934,13 +1043,14 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
         if rest:
             r, inf = registration_gmmtree_batch([pairs[k] for k in rest], maxiter, tol, ctx, tree_level, lambda_c, ls, ld, sig2,
                                                 init_idx, True, pdf_dtype, solve_on_device, score, gate, [ws[k] for k in rest],
-                                                source_weights=[sws[k] for k in rest])
+                                                source_weights=[sws[k] for k in rest],
+                                                starts=None if starts is None else [starts[k] for k in rest], maha2_max=maha2_max)
             for j, k in enumerate(rest):
                 out[k] = r[j]
                 info["build_iters"][k] = inf["build_iters"][j]
-                info["registration_iters"][k], info["status"][k] = inf["registration_iters"][j], inf["status"][j]
-                if score:
-                    info["score"][k] = inf["score"][j]
+                for key in info:
+                    if key != "build_iters":
+                        info[key][k] = inf[key][j]
         return (out, info) if return_info else out
     if pdf_dtype is None:
         kinds = [np.dtype(np.float32) if _points(s).dtype == np.float32 else np.dtype(np.float64) for s, _ in pairs]
@@ -949,11 +1059,15 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
                                               "status": [None] * len(pairs)}
             if score:
                 info["score"] = [None] * len(pairs)
+            if starts is not None:
+                info.update(_multistart_info(len(pairs)))
             for kind in sorted(set(kinds), key=str):
                 sel = [k for k, v in enumerate(kinds) if v == kind]
                 r, inf = registration_gmmtree_batch([pairs[k] for k in sel], maxiter, tol, ctx, tree_level, lambda_c, ls, ld,
                                                     sig2, init_idx, True, kind, solve_on_device, score, gate,
-                                                    [ws[k] for k in sel], source_weights=[sws[k] for k in sel])
+                                                    [ws[k] for k in sel], source_weights=[sws[k] for k in sel],
+                                                    starts=None if starts is None else [starts[k] for k in sel],
+                                                    maha2_max=maha2_max)
                 for j, k in enumerate(sel):
                     out[k] = r[j]
                     for key in info:
@@ -993,6 +1107,19 @@ def registration_gmmtree_batch(pairs, maxiter=20, tol=1.0e-4, ctx: Context | Non
     else:
         ctx.tree_set_targets_batch(tgts)
     clock.append(time.perf_counter())
+    if starts is not None:
+        out, (hyp_iters, hyp_status, hyp_scores) = _register_batch_multistart(
+            ctx, starts, starts_scale, tgts, ws, tree_level, lambda_c, ls, ld, sig2, maxiter, tol, solve_on_device, gate,
+            maha2_max, clock)
+        if not return_info:
+            return out
+        clock.append(time.perf_counter())
+        phases = dict(zip(("prepare", "sources_up", "build", "targets_up", "register", "score", "results"),
+                          (1e3 * np.diff(clock)).tolist()))
+        return out, {"build_iters": build_iters, "registration_iters": [w.n_iter_ for w in out],
+                     "status": [hyp_status[b][w.best_index_] for b, w in enumerate(out)], "phases_ms": phases,
+                     "score": [w.score for w in out], "hypothesis_iters": hyp_iters, "hypothesis_status": hyp_status,
+                     "hypothesis_scores": hyp_scores}
     rot0 = np.tile(np.identity(3), (B, 1, 1))
     with _reg_gate(ctx, gate):                                   # (the batch AND the pairs finished serially below)
         if solve_on_device:                                          # (per-context option reg_device_solve for this call)

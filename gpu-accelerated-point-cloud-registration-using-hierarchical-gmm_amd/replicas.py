@@ -122,13 +122,29 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
 
     ``score=True`` (gmmtree only): every result is a ``ScoredResult(transformation, q, score)`` with the ``TreeScore`` of the
     target at the pose the loop ended at (``registration_gmmtree(..., return_score=True)``; with ``batch`` > 1
-    ``registration_gmmtree_batch(..., score=True)``: the same numbers without the per-point arrays)."""
+    ``registration_gmmtree_batch(..., score=True)``: the same numbers without the per-point arrays).
+
+    ``starts=`` (gmmtree only, among ``kargs``): multi-start for every pair -- one list of start poses for all pairs, or with
+    ``batch`` > 1 also one list per pair of ``pairs``.  With ``batch`` > 1 every chunk runs
+    ``registration_gmmtree_batch(..., starts=...)`` and every result is its ``MultiStartResult``, which carries the winner's
+    score whether ``score`` is set or not."""
     pairs = list(pairs)
     if method == "gmmtree":
         from .hgmm.hgmm_gpu import ScoredResult, registration_gmmtree, registration_gmmtree_batch
 
         if int(batch) > 1:
-            def one(ctx, chunk):
+            # (starts=: one list for every pair, or one list per pair of ``pairs`` -- those travel with their chunk)
+            starts = kargs.pop("starts", None)
+            starts_per_pair = starts is not None and len(starts) > 0 and all(isinstance(s, (list, tuple)) for s in starts)
+            if starts_per_pair and len(starts) != len(pairs):
+                raise ValueError("starts must be one list of start poses, or one such list per pair: %d lists for %d pairs"
+                                 % (len(starts), len(pairs)))
+
+            def one(ctx, job):
+                first, chunk = job
+                if starts is not None:               # every result is a MultiStartResult, which carries its score
+                    st = starts[first:first + len(chunk)] if starts_per_pair else starts
+                    return registration_gmmtree_batch(chunk, maxiter=maxiter, tol=tol, ctx=ctx, starts=st, **kargs)
                 if not score:
                     return registration_gmmtree_batch(chunk, maxiter=maxiter, tol=tol, ctx=ctx, **kargs)
                 res, info = registration_gmmtree_batch(chunk, maxiter=maxiter, tol=tol, ctx=ctx, return_info=True, score=True, **kargs)
@@ -158,7 +174,7 @@ def register_pairs(pairs, devices=None, contexts_per_device: int = 1, maxiter: i
     try:
         if method == "gmmtree" and int(batch) > 1:
             B = int(batch)
-            chunks = [pairs[i:i + B] for i in range(0, len(pairs), B)]
+            chunks = [(i, pairs[i:i + B]) for i in range(0, len(pairs), B)]
             return [r for rs in pool.map(one, chunks) for r in rs]
         return pool.map(one, pairs)
     finally:

@@ -518,6 +518,38 @@ int hgmm_tree_register_multi(hgmm_ctx* ctx, int K, double* rot /* [K,9] */, doub
                              double* trace /* optional [K,max_iter,13] */);
 int hgmm_tree_score_multi(hgmm_ctx* ctx, int K, const double* rot /* [K,9] */, const double* t /* [K,3] */, double scale,
                           double lambda_c, double maha2_max, double* summary_out /* [K,8] */);
+/* ---- batched multi-start: R hypotheses over the resident FOREST, each naming its pair --------------------------------------
+ * The two remedies combined: the pairs of hgmm_tree_build_batch[_rows] + hgmm_tree_set_targets_batch[_f32] /
+ * hgmm_voxel_to_targets_batch stay resident once, and R start poses -- any number per pair, in any order; a pair without one
+ * takes no part -- run through the launches of one.  Hypothesis r reads tree pair[r] and target pair[r] (and that pair's
+ * weights and weight sum: the hypotheses of a pair share them) and owns slice r of everything that is written.
+ * hgmm_tree_register_batch_multi <- R x hgmm_tree_register, replacing a loop of hgmm_tree_register_multi over pairs set
+ *                            up serially: rot [R][9], t [R][3], q_prev [R] (NaN: none) updated in place; iters [R]; status [R]
+ *                            with hgmm_tree_register's codes (a hypothesis that stops costs the remaining launches one load;
+ *                            one that meets status 2 leaves at that iteration, its neighbours -- the other hypotheses of its
+ *                            own pair included -- unaffected, and the caller finishes it through the serial entries); trace
+ *                            (optional) [R][max_iter][13].  Per iteration one E-step launch of R x ceil(longest target / 256)
+ *                            workgroups and one normal-equations launch of R; the 6 x 6 solves on the host unless
+ *                            reg_device_solve is set.  The Mahalanobis gate and the targets' weights are honoured.
+ * hgmm_tree_score_batch_multi <- R x hgmm_tree_score (replacing hgmm_tree_score_multi per pair) at the poses rot [R][9],
+ *                            t [R][3], summaries [R][8] only.
+ * Hypothesis r comes out bit for bit as hgmm_tree_set_nodes(hgmm_tree_get_nodes_batch(pair[r])) + hgmm_tree_set_target (+ its
+ * weights) + hgmm_tree_register / hgmm_tree_score from / at its pose, whatever R is, wherever r sits and whoever its neighbours
+ * are; with pair = 0..B-1 the entries return what hgmm_tree_register_batch / hgmm_tree_score_batch return.  They work in sums
+ * and a table of their own (32 T bytes of sums per hypothesis: 1.2 MB at L = 5, 9.6 MB at L = 6) and leave the state of
+ * hgmm_tree_register_batch / _score_batch, of the serial entries and of the serial multi-start alone.
+ * Errors, each before anything resident is touched: HGMM_ERR_STATE without a forest or targets, with B trees but another number
+ * of targets, or under a communicator; HGMM_ERR_ARG for R < 1, NULL pair / rot / t (the poses are the input: no identity
+ * default) or NULL outputs, pair[r] outside 0..B-1 (the message names r), a NaN maha2_max, more than 2^31 - 1 workgroups, and
+ * sums above HGMM_TREE_BATCH_MULTI_MAX_BYTES (the message names the largest R that fits: split the list, any subset is a call). */
+#define HGMM_TREE_BATCH_MULTI_MAX_BYTES 4294967296ull /* 4 GiB: 3584 hypotheses at L = 5, 448 at L = 6 */
+int hgmm_tree_register_batch_multi(hgmm_ctx* ctx, int R, const int32_t* pair /* [R], each in 0..B-1 */, double* rot /* [R,9] */,
+                                   double* t /* [R,3] */, double scale, double lambda_c, int max_iter, double tol,
+                                   double* q_prev_inout /* [R], NaN = none */, int32_t* iters_out /* [R] */,
+                                   int32_t* status_out /* [R] */, double* trace /* optional [R,max_iter,13] */);
+int hgmm_tree_score_batch_multi(hgmm_ctx* ctx, int R, const int32_t* pair /* [R] */, const double* rot /* [R,9] */,
+                                const double* t /* [R,3] */, double scale, double lambda_c, double maha2_max,
+                                double* summary_out /* [R,8] */);
 /* Per-point WEIGHTS of the registration target.  The reference has no counterpart: gmmTreeRegESTep
  * (hgmm_cupy_cpu_working.py:202-228 == hgmm_gpu.py:550-577) counts every target point as one unit of evidence, although its
  * own pipeline voxel-downsamples the scans first (run_gmm_static.py:28).  A target point i with weight w_i >= 0 adds
