@@ -154,6 +154,9 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_fullcov_fit_weighted", [ctx, C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp,
                                                 _vp, _vp, C.c_int, C.POINTER(C.c_int)])
         _sig(lib, "hgmm_fullcov_estep_weighted", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64p])
+        for name in ("hgmm_fullcov_fit_batch", "hgmm_fullcov_fit_batch_rows"):
+            _sig(lib, name, [ctx, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_double, C.c_double, _vp, C.c_double, C.c_int, C.c_int, _vp, _vp,
+                             _vp, _vp, _vp, C.c_int, _vp])
         _sig(lib, "hgmm_kmeans_plusplus", [ctx, C.c_int, C.c_int64, _vp, C.c_int, _vp, _vp])
         _sig(lib, "hgmm_kmeans_step", [ctx, C.c_int, _vp, C.c_int, _vp, _f64p, C.POINTER(C.c_int64)])
         _sig(lib, "hgmm_kmeans_labels", [ctx, _vp, _vp])
@@ -1580,6 +1583,46 @@ class Context:
         self._check(fit(self.h, int(J), float(ls), float(ld), _ptr(init_mu), float(sig2), int(max_iters), _ptr(pi), _ptr(mu),
                         _ptr(cov), _ptr(labels), _ptr(q), int(max_iters), C.byref(qlen)))
         return pi, mu, cov, labels, q[:qlen.value].copy()
+
+    def fullcov_fit_batch(self, counts, J, ls, ld, init_mu=None, sig2=0.00034, max_iters=1000, weighted=False, init_rows=None,
+                          want_labels=True):
+        """``B = len(counts)`` flat full-covariance fits on the resident forest cloud's members in the same launches
+        (hgmm_fullcov_fit_batch), each bitwise what :meth:`fullcov_fit` gives for that member alone (``weighted``: under the
+        member's weights of :meth:`tree_set_source_weights_batch` / :meth:`set_points_batch_from_voxels`; a member whose
+        weights were None gives its unweighted fit).  One ``J``, ``ls``, ``ld``, ``sig2`` and budget for all members.
+        ``init_mu`` [B,J,3], or ``init_mu=None`` and ``init_rows`` [B,J] (or [J], the same for every member): row numbers
+        within each member, gathered on the device (hgmm_fullcov_fit_batch_rows).
+        -> (pi [B,J], mu [B,J,3], cov [B,J,3,3], list of labels [N_b] or None, list of q traces)."""
+        B, J = len(counts), int(J)
+        if (init_mu is None) == (init_rows is None):
+            raise ValueError("fullcov_fit_batch takes init_mu or init_rows, one of the two")
+        if int(max_iters) < 1:
+            raise ValueError("max_iters must be >= 1, not %r" % (max_iters,))
+        if init_rows is not None:
+            init = np.asarray(init_rows, dtype=np.int64)
+            if init.shape == (J,):
+                init = np.broadcast_to(init, (B, J))
+            init = np.ascontiguousarray(init)
+            if init.shape != (B, J):
+                raise ValueError("init_rows must be [%d,%d]" % (B, J))
+            entry = self.lib.hgmm_fullcov_fit_batch_rows
+        else:
+            init = np.ascontiguousarray(init_mu, dtype=np.float64)
+            if init.shape != (B, J, 3):
+                raise ValueError("init_mu must be [%d,%d,3]" % (B, J))
+            entry = self.lib.hgmm_fullcov_fit_batch
+        cnt = (C.c_int64 * max(B, 1))(*[int(v) for v in counts])
+        total = int(sum(int(v) for v in counts))
+        pi, mu, cov = np.empty((B, J)), np.empty((B, J, 3)), np.empty((B, J, 3, 3))
+        labels = np.empty(total, np.int32) if want_labels else None
+        qcap = int(max_iters)
+        q = np.zeros((B, qcap))
+        qlen = np.zeros(max(B, 1), np.int32)
+        self._check(entry(self.h, B, cnt, J, float(ls), float(ld), _ptr(init), float(sig2), int(max_iters), 1 if weighted else 0,
+                          _ptr(pi), _ptr(mu), _ptr(cov), _ptr(labels), _ptr(q), qcap, _ptr(qlen)))
+        first = np.concatenate(([0], np.cumsum([int(v) for v in counts]))).astype(np.int64)
+        labs = [labels[first[b]:first[b + 1]].copy() for b in range(B)] if want_labels else None
+        return pi, mu, cov, labs, [q[b, :qlen[b]].copy() for b in range(B)]
 
     def fullcov_estep(self, pi, mu, cov, weighted=False):
         """``weighted``: the moments and q under the resident SOURCE weights (hgmm_fullcov_estep_weighted)."""

@@ -1,6 +1,7 @@
 // Flat full-covariance EM (hgmm_fullcov_fit / hgmm_fullcov_estep / hgmm_fullcov_phase_clocks) for gfx950.  One tree level
 // with branching J: it shares the node preparation, the M-step and the node tables (t_*) with the tree build
-// (tree_kernels.hip, declared in tree_host.h) and nothing else.
+// (tree_kernels.hip, declared in tree_host.h) and nothing else.  The batched fit (hgmm_fullcov_fit_batch: B clouds per launch
+// set, on the one-pass kernel's body) is fullcov_batch.h, included at the end of this file.
 #include "tree_host.h"
 
 #include <algorithm>
@@ -119,12 +120,17 @@ inline size_t ft_lds_bytes(int J16, bool weighted = false) {      // (weighted: 
 // coordinates (0 for the rows past the cloud's end), phase B writes the feature row of point p as w_p f -- the weight rides in
 // the B operand of the matrix product, the A operand (gamma and its floor) and the arg-max are what they are without it --
 // and the point's log-likelihood term is multiplied by w_p.
-template <int CPL, bool CHOL, bool WEIGHTED>
+// FT_WG of FT_NWG: the workgroup's place in the launch of THIS cloud -- blockIdx.x of gridDim.x for the serial kernels (the
+// text they always had); BATCH: the local block and the serial grid of the member, handed in by hgmm_fullcov_fit_batch's
+// kernel (fullcov_batch.h), whose launch holds many clouds.
+template <int CPL, bool CHOL, bool WEIGHTED, bool BATCH = false>
 __device__ __forceinline__ void full_fused_body(
     const double* __restrict__ xs, int64_t n, int64_t n_pad, const double* __restrict__ prep, int J16,
     int* __restrict__ label_out, double* __restrict__ block_q, double* __restrict__ partials /*[grid][J16][NMOM]*/,
     int want_stats, long long* __restrict__ dbg, double* lds, const double* __restrict__ exp2_tab,
-    const double* __restrict__ wsrc) {
+    const double* __restrict__ wsrc, const unsigned wg_arg = 0, const unsigned nwg_arg = 0) {
+#define FT_WG (BATCH ? wg_arg : blockIdx.x)
+#define FT_NWG (BATCH ? nwg_arg : gridDim.x)
     long long tA = 0, tB = 0, tC = 0, tW = 0, tm = 0;
 #define FT_TICK(acc) do { if (dbg) { const long long now_ = clock64(); acc += now_ - tm; tm = now_; } } while (0)
     const int LDG = ft_ldg(J16);
@@ -203,8 +209,8 @@ __device__ __forceinline__ void full_fused_body(
     const int a_idx = lane & 15, b_idx = lane >> 4;
 
     const int64_t tiles = (n + FT_P - 1) / FT_P;
-    const int64_t per = (tiles + gridDim.x - 1) / gridDim.x;
-    const int64_t t0 = (int64_t)blockIdx.x * per;
+    const int64_t per = (tiles + FT_NWG - 1) / FT_NWG;
+    const int64_t t0 = (int64_t)FT_WG * per;
     const int64_t t1 = (t0 + per < tiles) ? t0 + per : tiles;
     // the wave that takes the tiles' log-likelihood terms: with the tail block dealt out, the waves behind the full second
     // blocks carry 16 + 2 evaluations per lane against 32 of the first ones -- but those share their SIMDs; measured,
@@ -493,7 +499,7 @@ __device__ __forceinline__ void full_fused_body(
         FT_TICK(tW);
     }
     if (w == LQ_WAVE && t0 < t1) tile_loglik((int)((t1 - 1 - t0) & 1));      // the last tile's terms
-    if (dbg && lane == 0 && blockIdx.x == 7) {
+    if (dbg && lane == 0 && FT_WG == 7) {
         dbg[w * 4 + 0] = tA; dbg[w * 4 + 1] = tB; dbg[w * 4 + 2] = tC; dbg[w * 4 + 3] = tW;
     }
     // D layout (f64 4x4x4, 4 blocks): lane = j + 4 b + 16 i  ->  component 16 ct + 4 b + i, feature 4 fb + j
@@ -505,12 +511,14 @@ __device__ __forceinline__ void full_fused_body(
 #pragma unroll
             for (int fb = 0; fb < 3; ++fb) {
                 const int feat = 4 * fb + (lane & 3);
-                if (feat < NMOM) partials[((size_t)blockIdx.x * J16 + comp) * NMOM + feat] = acc[t][fb];
+                if (feat < NMOM) partials[((size_t)FT_WG * J16 + comp) * NMOM + feat] = acc[t][fb];
             }
         }
     }
-    if (w == LQ_WAVE && lane == 0) block_q[blockIdx.x] = lq;
+    if (w == LQ_WAVE && lane == 0) block_q[FT_WG] = lq;
 #undef FT_TICK
+#undef FT_WG
+#undef FT_NWG
 }
 
 template <int CPL>
@@ -1087,3 +1095,5 @@ extern "C" int hgmm_fullcov_estep_weighted(hgmm_ctx* c, int J, const double* pi,
                                            double* q_out) {
     return fullcov_estep(c, true, J, pi, mu, cov, m0_out, m1_out, m2_out, labels_out, q_out);
 }
+
+#include "fullcov_batch.h"

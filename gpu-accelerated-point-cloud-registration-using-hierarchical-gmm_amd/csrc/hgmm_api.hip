@@ -783,7 +783,8 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->vx_cent, &c->vx_cnt, &c->vx_hand,
                       &c->fb_tab, &c->fb_params, &c->fb_pack, &c->fb_partials, &c->fb_lpn_partials, &c->fb_stats, &c->fb_lls, &c->fb_ctl,
                       &c->fb_sw, &c->fb_x,
-                      &c->kb_tab, &c->kb_x, &c->kb_points, &c->kb_blocks, &c->kb_partial, &c->kb_small};
+                      &c->kb_tab, &c->kb_x, &c->kb_points, &c->kb_blocks, &c->kb_partial, &c->kb_small,
+                      &c->fc_tab, &c->fc_tables, &c->fc_partials, &c->fc_small, &c->fc_labels};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);

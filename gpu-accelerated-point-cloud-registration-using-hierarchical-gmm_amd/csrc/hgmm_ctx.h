@@ -332,6 +332,13 @@ struct hgmm_ctx {
     hgmm::DevBuf kb_partial;                  // double: the members' [nb_acc_b][k_alloc][4]
     hgmm::DevBuf kb_small;                    // per member: seeds, centres, padded centres, candidates, sums, uniforms, ids, control words
 
+    // batched full-covariance fit (hgmm_fullcov_fit_batch, fullcov_batch.h): buffers of its own, nothing above is touched
+    hgmm::DevBuf fc_tab;                      // FcBatchMember [B], then (member, local block) per workgroup of the fused launch
+    hgmm::DevBuf fc_tables;                   // double [B][J16] x (pi 1 | mu 3 | cov 9 | prep PREP_N | mom NMOM)
+    hgmm::DevBuf fc_partials;                 // double [sum of the members' grids][J16][NMOM]
+    hgmm::DevBuf fc_small;                    // double shares of q [sum of the grids] | q [B] | traces [B][cap]; TreeCtl [B]; int flags [B]
+    hgmm::DevBuf fc_labels;                   // int32 [2][n_pad] the two arg-max buffers on the forest cloud's rows, then [n_pad] the result
+
     // ---- L2 GMMReg Gauss transform ---------------------------------------------------
     hgmm::DevBuf gt_buf;                      // double: centres, points, weights, per-split partial sums
 

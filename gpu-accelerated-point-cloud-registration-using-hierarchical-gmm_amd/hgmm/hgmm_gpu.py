@@ -276,6 +276,60 @@ def fitFullCovGMM(points, n_components, ls=80.0, ld=1.0e-4, sig2=0.00034, init_i
     return pi, mu, cov
 
 
+def fitFullCovGMM_batch(clouds, n_components, ls=80.0, ld=1.0e-4, sig2=0.00034, init_idx=None, seed=None, max_iters=1000,
+                        ctx: Context | None = None, return_trace=False, weights=None):
+    """:func:`fitFullCovGMM` of every cloud of ``clouds`` through ONE launch set (``Context.fullcov_fit_batch``): four
+    launches per iteration for all of them, every member with its own stop rule.  -> a list of what :func:`fitFullCovGMM`
+    returns, member b bit for bit what ``fitFullCovGMM(clouds[b], ...)`` gives.
+
+    ``clouds``: a list of [N_b,3] arrays, :class:`WeightedPoints` (a member brings its own weights) or :class:`VoxelCloud`
+    members of one resident voxel result.  A list of VoxelClouds is handed over on the device and fitted count-weighted,
+    its initial means gathered there by row number; it takes no explicit weights and cannot be mixed with host arrays.
+    ``weights``: a list with one entry per cloud, ``None`` entries allowed (that member is fitted unweighted, bit for bit);
+    an entry takes precedence over the member's own.  ``init_idx``: [J] (the same rows for every member) or one [J] per
+    member; default: the serial function's draw, per member.  One ``n_components``, ``ls``, ``ld``, ``sig2`` and budget for
+    all members; the float32 tile (``dtype=``) has no batched form.
+
+    More than 1024 components (rounded up to a multiple of 16) are beyond the batched kernel: the members are then fitted
+    one by one by :func:`fitFullCovGMM` -- the only case that falls back.  Everything else the library refuses is an error."""
+    ctx = ctx or default_context()
+    clouds = list(clouds)
+    B, J = len(clouds), int(n_components)
+    if B == 0:
+        return []
+    if weights is not None and len(weights) != B:
+        raise ValueError("%d clouds, but %d weights entries" % (B, len(weights)))
+    raws = [_points(x) for x in clouds]
+    voxels = [_is_voxels(r) for r in raws]
+    if any(voxels) and not all(voxels):
+        raise ValueError("VoxelCloud members cannot be mixed with host arrays in one batch")
+    ws = [_target_weights(x, None if weights is None else weights[b]) for b, x in enumerate(clouds)]   # (refused before any upload)
+    if init_idx is None:
+        idx = [np.random.RandomState(J if seed is None else seed).randint(J, size=J) for _ in range(B)]
+    else:
+        idx = np.asarray(init_idx)
+        idx = [idx] * B if idx.ndim == 1 else list(idx)
+        if len(idx) != B or any(np.shape(i) != (J,) for i in idx):
+            raise ValueError("init_idx must be [%d] or [%d,%d]" % (J, B, J))
+    if (J + 15) // 16 * 16 > 1024:
+        return [fitFullCovGMM(x, J, ls, ld, sig2, idx[b], None, max_iters, ctx, return_trace, weights=ws[b])
+                for b, x in enumerate(clouds)]
+    if all(voxels):
+        counts = ctx.set_points_batch_from_voxels(raws, weighted=True)
+        init, weighted = dict(init_rows=np.stack([np.asarray(i, dtype=np.int64) for i in idx])), True
+    else:
+        Ps = [np.ascontiguousarray(r, dtype=np.float64) for r in raws]
+        weighted = any(w is not None for w in ws)
+        Ps = ctx.set_points_batch(Ps, weights=ws if weighted else None)
+        counts = [len(P) for P in Ps]
+        init = dict(init_mu=np.stack([P[np.asarray(i)] for P, i in zip(Ps, idx)]))
+    pi, mu, cov, labels, q = ctx.fullcov_fit_batch(counts, J, ls, ld, sig2=sig2, max_iters=max_iters, weighted=weighted,
+                                                   want_labels=bool(return_trace), **init)
+    if return_trace:
+        return [(pi[b], mu[b], cov[b], {"labels": labels[b], "q_trace": q[b]}) for b in range(B)]
+    return [(pi[b], mu[b], cov[b]) for b in range(B)]
+
+
 def gmmTreeRegESTep(points, mixingCoeff, mean, covar, maxTreeLevel, lc, ctx: Context | None = None):
     """-> (momentsZero[T], momentsOne[T,3], momentsTwo[T,3,3])   (hgmm_gpu.py:550-577)."""
     ctx = ctx or default_context()

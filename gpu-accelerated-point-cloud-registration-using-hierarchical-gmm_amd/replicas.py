@@ -203,7 +203,16 @@ def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag
     ``flavour="G"``: the GMMReg flavour's model instead (``gmmreg_gpu.gmm.GMM_GPU_Base(n_components, max_iter, tol)``: diag,
     KMeans initialisation); with ``batch`` > 1 its ``fit_batch`` runs the KMeans initialiser of the chunk's frames through
     one launch set as well, and the models are bitwise those of ``batch=1``.  It takes neither ``cov_type`` other than
-    ``"diag"`` nor ``voxel_size``."""
+    ``"diag"`` nor ``voxel_size``.
+
+    ``flavour="full"``: the flat FULL-covariance fit (``hgmm.hgmm_gpu.fitFullCovGMM(frame, n_components, ls=tol,
+    max_iters=max_iter)``; ``tol`` is its stop rule's ``ls`` on |q - q_prev|, the other parameters its defaults) -> one
+    ``(pi, mu, cov)`` per frame.  ``batch`` > 1: ``fitFullCovGMM_batch`` of every chunk, four launches per iteration for
+    all its frames, bitwise ``batch=1``.  ``voxel_size``: every chunk is down-sampled on its context and fitted
+    count-weighted where the centroids lie (``batch=1``: chunks of one through the same route).  ``cov_type`` is not looked
+    at."""
+    if flavour == "full":
+        return _fit_frames_full(list(frames), n_components, max_iter, tol, devices, contexts_per_device, pool, batch, voxel_size)
     if flavour == "G":
         from .gmmreg_gpu.gmm import GMM_GPU_Base as _G
 
@@ -215,7 +224,7 @@ def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag
     elif flavour == "W":
         from .gmm_waymo.gmm import GMM_GPU_Base
     else:
-        raise ValueError("flavour must be 'W' or 'G', not %r" % (flavour,))
+        raise ValueError("flavour must be 'W' or 'G' (or 'full'), not %r" % (flavour,))
 
     frames = list(frames)
     B = int(batch)
@@ -238,6 +247,37 @@ def fit_frames(frames, n_components=100, max_iter=30, tol=1.0e-4, cov_type="diag
         if B > 1 or voxel_size is not None:
             chunks = [frames[i:i + B] for i in range(0, len(frames), B)]
             return [m for ms in pool.map(chunk if voxel_size is None else voxel_chunk, chunks) for m in ms]
+        return pool.map(one, frames)
+    finally:
+        if own:
+            pool.close()
+
+
+def _fit_frames_full(frames, n_components, max_iter, tol, devices, contexts_per_device, pool, batch, voxel_size):
+    """fit_frames(flavour="full"): fitFullCovGMM per frame, or fitFullCovGMM_batch per chunk of ``batch`` frames"""
+    from .hgmm.hgmm_gpu import fitFullCovGMM, fitFullCovGMM_batch
+    B = int(batch)
+    if B < 1:
+        raise ValueError("batch must be >= 1, not %r" % (batch,))
+    kw = dict(ls=tol, max_iters=max_iter)
+
+    def one(ctx, frame):                                     # (the worker thread runs under use_context(ctx))
+        if voxel_size is None:
+            return fitFullCovGMM(frame, n_components, ctx=ctx, **kw)
+        vc = ctx.voxel_down_sample_batch([frame], voxel_size, download=False).members()[0]
+        return fitFullCovGMM(vc, n_components, ctx=ctx, **kw)
+
+    def chunk(ctx, part):
+        if voxel_size is not None:
+            part = ctx.voxel_down_sample_batch(part, voxel_size, download=False).members()
+        return fitFullCovGMM_batch(part, n_components, ctx=ctx, **kw)
+
+    own = pool is None
+    pool = pool or ReplicaPool(devices, contexts_per_device)
+    try:
+        if B > 1:
+            chunks = [frames[i:i + B] for i in range(0, len(frames), B)]
+            return [m for ms in pool.map(chunk, chunks) for m in ms]
         return pool.map(one, frames)
     finally:
         if own:

@@ -687,6 +687,38 @@ int hgmm_fullcov_fit_weighted(hgmm_ctx* ctx, int J, double ls, double ld, const 
 int hgmm_fullcov_estep_weighted(hgmm_ctx* ctx, int J, const double* pi, const double* mu, const double* cov,
                                 double* m0_out, double* m1_out, double* m2_out, int32_t* labels_out,
                                 double* q_out);
+/* B clouds fitted by the same launches: the members of the resident FOREST cloud (hgmm_set_points_batch_f64 / _f32,
+ * hgmm_voxel_to_points_batch; counts [B] must equal its member counts), one J, ls, ld, sig2 and budget for all of them.
+ * init_mu [B][J][3]; the _rows entry takes init_rows [B][J] instead, row numbers WITHIN each member, and gathers the initial
+ * means on the device (as hgmm_tree_build_batch_rows does: a voxel batch needs no host trip).
+ * THE CONTRACT.  Member b comes out bit for bit as the serial call on that cloud alone -- hgmm_set_points_f64 plus
+ * hgmm_fullcov_fit, or hgmm_fullcov_fit_weighted under that member's weights --, whatever B is and whoever its neighbours
+ * are: pi_out [B][J], mu_out [B][J][3], cov_out [B][J][3][3], labels_out [sum counts] (member after member; may be NULL),
+ * q_trace_out [B][q_capacity] (may be NULL) and q_len_out [B].  Every member has the serial launch's grid (min(tiles, CUs)
+ * workgroups and the serial tile-to-workgroup map inside them), its own first point as the origin, its own partials, shares
+ * of q, tables, control word, stop rule, q trace and its own Cholesky flag: a member whose Sigma^-1 fails the factorisation
+ * takes the symmetric form alone.  An iteration of all members is four launches (M-step over B J components, the one-pass
+ * kernel over the sum of the members' grids, the reduction over B J workgroups, B sums of q each applying its member's stop
+ * rule); the workgroups of a stopped member return at once and the call ends when every member has stopped.
+ * weighted != 0: under the forest cloud's SOURCE weights (hgmm_tree_set_source_weights_batch, or the counts of
+ * hgmm_voxel_to_points_batch(..., HGMM_VOXEL_W_TREE)); W_b = the member's float64 host sum in index order (a voxel member:
+ * its raw count); a member whose w[b] was NULL carries 1.0 and gives its UNWEIGHTED serial fit bit for bit.  weighted == 0
+ * ignores resident weights, like hgmm_fullcov_fit.
+ * Refused by name before anything resident is touched: HGMM_ERR_STATE without a resident forest cloud, B other than its
+ * member count, under a communicator, with hgmm_tree_set_precision(HGMM_PRECISION_F32_PDF) in force (the batch is the one-pass
+ * float64 kernel only and never runs float64 where the serial call would not), with the fullcov_two_pass option set, or with
+ * weighted != 0 and no resident forest weights; HGMM_ERR_ARG for B outside 1..4096, counts[b] differing from the resident
+ * member, J < 1 or J16 = 16 ceil(J / 16) > 1024 (the two-pass path of the serial entry), NULL init_mu / init_rows / pi_out /
+ * mu_out / cov_out / q_len_out, a row number outside its member, and partials of all members above 8 GiB together.        */
+int hgmm_fullcov_fit_batch(hgmm_ctx* ctx, int B, const int64_t* counts /* [B] */, int J, double ls, double ld,
+                           const double* init_mu /* [B][J][3] */, double sig2, int max_iters, int weighted,
+                           double* pi_out /* [B][J] */, double* mu_out /* [B][J][3] */, double* cov_out /* [B][J][3][3] */,
+                           int32_t* labels_out /* [sum counts] or NULL */, double* q_trace_out /* [B][q_capacity] or NULL */,
+                           int q_capacity, int32_t* q_len_out /* [B] */);
+int hgmm_fullcov_fit_batch_rows(hgmm_ctx* ctx, int B, const int64_t* counts /* [B] */, int J, double ls, double ld,
+                                const int64_t* init_rows /* [B][J] */, double sig2, int max_iters, int weighted,
+                                double* pi_out, double* mu_out, double* cov_out, int32_t* labels_out, double* q_trace_out,
+                                int q_capacity, int32_t* q_len_out);
 
 /* ---- KMeans initialiser (float64, on the resident cloud) -------------------------------
  * Replaces the scikit-learn call the GMMReg flavour seeds its EM with
