@@ -167,6 +167,8 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_kmeans_lloyd_weighted", [ctx, C.c_int, _vp, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int),
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, C.POINTER(C.c_int64)])
         _sig(lib, "hgmm_gauss_transform", [ctx, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp])
+        _sig(lib, "hgmm_l2_set_pairs", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
+        _sig(lib, "hgmm_l2_cost", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp])
         _sig(lib, "hgmm_comm_unique_id", [_vp])
         _sig(lib, "hgmm_comm_init_rank", [ctx, C.c_int, C.c_int, _vp])
         _sig(lib, "hgmm_comm_destroy", [ctx])
@@ -588,6 +590,7 @@ class Context:
         self._tgt_n = None                    # points of the resident registration target (tree_set_target)
         self._tgt_B = None                    # targets of the resident batch (tree_set_targets_batch)
         self._forest_LT = None                # (L, T) of the resident forest (tree_build_batch); tree_get_nodes_batch checks it
+        self.l2_owner = None                  # token of whoever made the resident L2 pairs its own (l2_set_pairs clears it)
 
     # -- plumbing ---------------------------------------------------------------------
     def _check(self, rc):
@@ -1750,6 +1753,45 @@ class Context:
         self._check(self.lib.hgmm_gauss_transform(self.h, _ptr(centres), len(centres), _ptr(points), len(points),
                                                   _ptr(w2), w2.shape[0], float(h), _ptr(out)))
         return out[0] if one else out
+
+    def l2_set_pairs(self, pairs):
+        """Make the mixtures of B (source, target) pairs resident for :meth:`l2_cost` (hgmm_l2_set_pairs): ``pairs`` is a
+        sequence of ``(mu_source [Js,3], phi_source [Js], mu_target [Jt,3], phi_target [Jt])``, ragged.  A later call
+        replaces the set.  -> B."""
+        pairs = list(pairs)
+        self.l2_owner = None            # whoever keeps track of WHOSE set is resident puts a token here after the call
+        cols = [[], [], [], []]
+        for b, pair in enumerate(pairs):
+            if len(pair) != 4:
+                raise ValueError("pair %d: expected (mu_source, phi_source, mu_target, phi_target)" % b)
+            mu_s, mu_t = (np.ascontiguousarray(pair[k], dtype=np.float64).reshape(-1, 3) for k in (0, 2))
+            phi_s, phi_t = (np.ascontiguousarray(pair[k], dtype=np.float64).reshape(-1) for k in (1, 3))
+            if len(phi_s) != len(mu_s) or len(phi_t) != len(mu_t):
+                raise ValueError("pair %d: one weight per centre" % b)
+            for col, a in zip(cols, (mu_s, phi_s, mu_t, phi_t)):
+                col.append(a)
+        cat = lambda col, tail: np.ascontiguousarray(np.concatenate(col)) if col else np.zeros((0,) + tail)
+        mu_s, phi_s, mu_t, phi_t = cat(cols[0], (3,)), cat(cols[1], ()), cat(cols[2], (3,)), cat(cols[3], ())
+        js = np.array([len(a) for a in cols[1]], np.int32)
+        jt = np.array([len(a) for a in cols[3]], np.int32)
+        self._check(self.lib.hgmm_l2_set_pairs(self.h, len(pairs), _ptr(js), _ptr(mu_s), _ptr(phi_s), _ptr(jt), _ptr(mu_t),
+                                               _ptr(phi_t)))
+        return len(pairs)
+
+    def l2_cost(self, pair_ids, rots, ts, sigmas):
+        """R hypotheses on the resident pairs in one launch set (hgmm_l2_cost): ``pair_ids`` [R], ``rots`` [R,3,3], ``ts``
+        [R,3], ``sigmas`` [R] (or one for all) -> [R,13]: f, the gradient's column sums (3), g.T @ mu_source (9, row-major).
+        Row r does not depend on R or on the other rows."""
+        pair_ids = np.ascontiguousarray(pair_ids, dtype=np.int32).reshape(-1)
+        R = len(pair_ids)
+        rots = np.ascontiguousarray(rots, dtype=np.float64).reshape(-1, 9)
+        ts = np.ascontiguousarray(ts, dtype=np.float64).reshape(-1, 3)
+        sigmas = np.ascontiguousarray(np.broadcast_to(np.asarray(sigmas, dtype=np.float64), (R,)))
+        if len(rots) != R or len(ts) != R:
+            raise ValueError("l2_cost: %d pair ids, %d rotations, %d translations" % (R, len(rots), len(ts)))
+        out = np.empty((R, 13))
+        self._check(self.lib.hgmm_l2_cost(self.h, R, _ptr(pair_ids), _ptr(rots), _ptr(ts), _ptr(sigmas), _ptr(out)))
+        return out
 
     # -- multi-GPU ------------------------------------------------------------------------
     @staticmethod

@@ -784,9 +784,11 @@ extern "C" int hgmm_destroy(hgmm_ctx* c) {
                       &c->fb_tab, &c->fb_params, &c->fb_pack, &c->fb_partials, &c->fb_lpn_partials, &c->fb_stats, &c->fb_lls, &c->fb_ctl,
                       &c->fb_sw, &c->fb_x,
                       &c->kb_tab, &c->kb_x, &c->kb_points, &c->kb_blocks, &c->kb_partial, &c->kb_small,
-                      &c->fc_tab, &c->fc_tables, &c->fc_partials, &c->fc_small, &c->fc_labels};
+                      &c->fc_tab, &c->fc_tables, &c->fc_partials, &c->fc_small, &c->fc_labels,
+                      &c->l2.mix, &c->l2.work};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
+    if (c->l2.pin) (void)hipHostFree(c->l2.pin);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->hand.host) (void)hipHostFree(c->hand.host);
     if (c->h_scalars) (void)hipHostFree(c->h_scalars);

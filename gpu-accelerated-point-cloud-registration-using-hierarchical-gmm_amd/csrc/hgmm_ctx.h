@@ -196,6 +196,19 @@ struct ForestState {
     MemberWeights src_w;                  // hgmm_tree_set_source_weights_batch: [n_pad] parallel to x_soa64; a new cloud drops them
 };
 
+// The resident pairs of the fused L2 GMMReg cost (gmmreg_kernels.hip).  One pair on the device: where its centres lie in
+// the concatenated arrays.  Its launch shape -- source blocks x target splits -- follows from (Js, Jt) alone.
+struct L2Pair { int s_first, Js, t_first, Jt; };
+struct L2Set {
+    int B = 0;                        // 0: nothing resident
+    int wg_max = 0;                   // the largest workgroup count of one hypothesis among the resident pairs (grid.x)
+    std::vector<L2Pair> pairs;        // host copy of the device table (hgmm_l2_cost's checks and launch shape)
+    DevBuf mix;                       // double mu_s [sum Js][3] | phi_s [sum Js] | mu_t [sum Jt][3] | phi_t [sum Jt], then L2Pair [B]
+    DevBuf work;                      // per call: L2Hyp [R], then double records [R][wg_max][13]
+    char* pin = nullptr;              // pinned, device-visible: L2Hyp [HGMM_L2_MAX_HYP] on their way in, then double
+    char* pin_dev = nullptr;          // [HGMM_L2_MAX_HYP][13] the finish kernel writes (hipHostFree: hgmm_destroy)
+};
+
 }  // namespace hgmm
 
 // A point cloud resident in HBM that outlives the calls made on it (hgmm_points_create_*): the float32 row-major copy the
@@ -341,6 +354,10 @@ struct hgmm_ctx {
 
     // ---- L2 GMMReg Gauss transform ---------------------------------------------------
     hgmm::DevBuf gt_buf;                      // double: centres, points, weights, per-split partial sums
+    // resident mixtures of the fused rigid cost (hgmm_l2_set_pairs / hgmm_l2_cost, gmmreg_kernels.hip): buffers of their own.
+    // LIFETIME: l2 is replaced as a whole by a successful hgmm_l2_set_pairs (a refused one leaves it alone), read by
+    // hgmm_l2_cost and freed by hgmm_destroy; nothing else of the context reads or writes it
+    hgmm::L2Set l2;
 
     // ---- voxel-grid down-sample (voxel_kernels.hip): buffers of its own, nothing above is touched --------
     hgmm::DevBuf vx_in;                       // the clouds' rows as uploaded, back to back: float or double [total][3]

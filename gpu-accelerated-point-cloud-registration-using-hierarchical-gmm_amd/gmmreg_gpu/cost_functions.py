@@ -6,6 +6,9 @@ sqrt(2) sigma: f = -sum_s phi_s G(mu_s), G(x) = sum_t (phi_t / z) exp(-|x - mu_t
 with respect to the source centres needs the same kernel against the weight rows phi_t mu_t / z.  Both come out
 of ONE kernel matrix here (the reference evaluates it 1 + 3 times, cost_functions.py:29-40); with a device
 context it is `hgmm_gauss_transform`.  The 7-parameter chain rule stays in NumPy.
+``RigidCostFunction.evaluate_many`` evaluates R hypotheses at once over mixtures that stay resident on the device
+(`hgmm_l2_set_pairs` / `hgmm_l2_cost`: the fused kernel returns f, the column sums of the gradient and g.T @ mu_source);
+``__call__`` is the path it always was.
 """
 import numpy as np
 
@@ -22,6 +25,33 @@ def compute_l2_dist(mu_source, phi_source, mu_target, phi_target, sigma, ctx=Non
     g0, g1 = sums[0], sums[1:]                                             # sum_t w e  and  sum_t w mu_t e
     grad = (phi_source * (g0 * mu_source.T - g1)).T / (2.0 * sigma ** 2)
     return -(phi_source @ g0), grad
+
+
+def theta_from_transformation(tf_obj):
+    """RigidTransformation -> theta = (qw, qx, qy, qz, tx, ty, tz), the inverse of ``RigidCostFunction.to_transformation``
+    for a proper rotation.  The quaternion comes from Shepperd's method -- the largest of (trace, R00, R11, R22) decides
+    which component is taken from a square root, so nothing is divided by a small number, also at a turn of 180 degrees --
+    is of unit length and has w >= 0."""
+    r = np.asarray(tf_obj.rot, dtype=np.float64)
+    tr = np.trace(r)
+    k = int(np.argmax([tr, r[0, 0], r[1, 1], r[2, 2]]))
+    if k == 0:                         # s = 4 q_k in every branch; the other three components are off-diagonal sums / s
+        s = 2.0 * np.sqrt(1.0 + tr)
+        q = [0.25 * s, (r[2, 1] - r[1, 2]) / s, (r[0, 2] - r[2, 0]) / s, (r[1, 0] - r[0, 1]) / s]
+    elif k == 1:
+        s = 2.0 * np.sqrt(1.0 + r[0, 0] - r[1, 1] - r[2, 2])
+        q = [(r[2, 1] - r[1, 2]) / s, 0.25 * s, (r[0, 1] + r[1, 0]) / s, (r[0, 2] + r[2, 0]) / s]
+    elif k == 2:
+        s = 2.0 * np.sqrt(1.0 + r[1, 1] - r[0, 0] - r[2, 2])
+        q = [(r[0, 2] - r[2, 0]) / s, (r[0, 1] + r[1, 0]) / s, 0.25 * s, (r[1, 2] + r[2, 1]) / s]
+    else:
+        s = 2.0 * np.sqrt(1.0 + r[2, 2] - r[0, 0] - r[1, 1])
+        q = [(r[1, 0] - r[0, 1]) / s, (r[0, 2] + r[2, 0]) / s, (r[1, 2] + r[2, 1]) / s, 0.25 * s]
+    q = np.array(q, dtype=np.float64)
+    if q[0] < 0.0:
+        q = -q
+    q[0] = abs(q[0])                   # (-0.0 at a half turn)
+    return np.concatenate([q, np.asarray(tf_obj.t, dtype=np.float64).reshape(3)])
 
 
 class CostFunction(object):
@@ -47,6 +77,8 @@ class RigidCostFunction(CostFunction):
     def __init__(self, ctx=None):
         super().__init__(tf.RigidTransformation)
         self._ctx = ctx                     # device context for the Gauss transform (None: host NumPy)
+        self._pairs = None                  # set_pairs: the mixtures evaluate_many works on
+        self._resident = None               # ... and the token the context carries while THEY are its resident set
 
     def to_transformation(self, theta):
         return self._tf_type(so.quaternion_matrix(theta[:4])[:3, :3], theta[4:7])
@@ -61,3 +93,44 @@ class RigidCostFunction(CostFunction):
         # d f / d q_k = sum_{a,b} (g^T mu_source)[a, b] dR[a, b] / d q_k ;  d f / d t = column sums of g
         d_quat = np.einsum('ab,kab->k', g.T @ mu_source, so.diff_rot_from_quaternion(theta[:4]))
         return f, np.concatenate([d_quat, g.sum(axis=0)])
+
+    # ---- many hypotheses over resident mixtures -------------------------------------------------------------------
+    def set_pairs(self, pairs):
+        """The mixtures :meth:`evaluate_many` works on: a sequence of ``(mu_source, phi_source, mu_target, phi_target)``.
+        With a context they become resident on the device (``Context.l2_set_pairs``); a later call replaces them."""
+        self._pairs = [tuple(np.asarray(a, dtype=np.float64) for a in p) for p in pairs]
+        self._make_resident()
+
+    def _make_resident(self):
+        # a context holds ONE resident set: a cost function that finds another's there (two registrations sharing the
+        # default context) puts its own back instead of evaluating on the wrong mixtures
+        if self._ctx is not None:
+            self._ctx.l2_set_pairs(self._pairs)          # (clears the context's token)
+            self._resident = self._ctx.l2_owner = object()
+
+    def evaluate_many(self, thetas, pair_ids, sigmas):
+        """R hypotheses at once -> (f [R], grad [R, 7]): hypothesis r is theta ``thetas[r]`` on pair ``pair_ids[r]`` of
+        :meth:`set_pairs` at kernel width ``sigmas[r]``.  With a context one ``l2_cost`` call evaluates them all (the fused
+        kernel returns f, the column sums of g and g.T @ mu_source; the chain rule below is that of ``__call__``); without,
+        a loop of ``__call__``.  Row r does not depend on R or on the other rows."""
+        thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, 7)
+        R = len(thetas)
+        pair_ids = np.broadcast_to(np.asarray(pair_ids, dtype=np.int64), (R,))
+        sigmas = np.broadcast_to(np.asarray(sigmas, dtype=np.float64), (R,))
+        pairs = self._pairs
+        if not pairs:
+            raise ValueError("evaluate_many: no mixtures (call set_pairs first)")
+        f, grad = np.empty(R), np.empty((R, 7))
+        if self._ctx is None:
+            for r in range(R):
+                f[r], grad[r] = self(thetas[r], *pairs[int(pair_ids[r])], float(sigmas[r]))
+            return f, grad
+        if self._ctx.l2_owner is not self._resident:
+            self._make_resident()
+        poses = [self.to_transformation(th) for th in thetas]
+        out = self._ctx.l2_cost(pair_ids, [p.rot for p in poses], [p.t for p in poses], sigmas)
+        f[:] = out[:, 0]
+        grad[:, 4:] = out[:, 1:4]
+        for r in range(R):
+            grad[r, :4] = np.einsum('ab,kab->k', out[r, 4:].reshape(3, 3), so.diff_rot_from_quaternion(thetas[r, :4]))
+        return f, grad

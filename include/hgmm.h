@@ -845,6 +845,38 @@ int hgmm_kmeans_fit_batch(hgmm_ctx* ctx, int B, const int64_t* counts /* [B] */,
 int hgmm_gauss_transform(hgmm_ctx* ctx, const double* centres, int n_centres, const double* points,
                          int n_points, const double* weights, int n_weights, double h, double* out);
 
+/* ---- L2 GMMReg: resident mixtures, fused rigid cost + gradient sums for R poses per launch set (float64) ----------------
+ * The BFGS solve of the L2 registration (gmmreg.py:62-121) evaluates RigidCostFunction.__call__ (cost_functions.py:29-68)
+ * on mixtures that never change while it runs; only the seven parameters do.  hgmm_l2_set_pairs makes the mixtures of B
+ * (source, target) pairs resident; hgmm_l2_cost evaluates R hypotheses on them in two launches and one download.
+ * Hypothesis r names a pair p = pair[r], a pose (rot[r] row-major, t[r]) and a kernel width sigma[r].  With x_i, phis_i the
+ * pair's source centres and weights, mut_j, phit_j its target's, y_i = rot x_i + t, z = (2 pi sigma^2)^(3/2):
+ *     e_ij = exp(-|y_i - mut_j|^2 / 2 sigma^2)      g0_i = sum_j (phit_j / z) e_ij      g1_i = sum_j (phit_j mut_j / z) e_ij
+ *     grad_i = phis_i (g0_i y_i - g1_i) / 2 sigma^2                                  (compute_l2_dist, cost_functions.py:29-40)
+ *     out[r] = { f = -sum_i phis_i g0_i ;  sum_i grad_i (3) ;  M = sum_i grad_i (x) x_i  (3 x 3 row-major: g.T @ mu_source,
+ *                cost_functions.py:62-68) }
+ * The quaternion chain rule (so.diff_rot_from_quaternion, with the reference's quirks) stays with the caller.
+ * DETERMINISTIC AND INDEPENDENT: a workgroup handles 64 source centres against at most 256 target centres, reduces its 13
+ * sums across the wave in a fixed order and writes one record; a second kernel adds a hypothesis' records in (source
+ * block, target split) order.  That map is a function of (J_s, J_t) alone -- not of R, of the hypothesis' or the pair's
+ * position, or of the device -- and there are no floating-point atomics: out[r] is bit for bit what the R = 1 call returns.
+ * hgmm_l2_set_pairs: Js [B], Jt [B] component counts; mu_s [sum Js][3], phi_s [sum Js], mu_t [sum Jt][3], phi_t [sum Jt] are
+ * host float64 arrays, the pairs' rows back to back.  LIFETIME: the set belongs to the context; a later successful call
+ * replaces it, a refused call leaves it as it was, hgmm_destroy frees it.  Nothing else of the context is touched.
+ * REFUSALS (hgmm_last_error names each).  hgmm_l2_set_pairs, HGMM_ERR_ARG: a NULL argument; B outside 1..HGMM_L2_MAX_PAIRS;
+ * a pair with Js < 1 or Jt < 1 ("J < 1"); more than 2^31 - 1 centres in all.  hgmm_l2_cost, HGMM_ERR_ARG: a NULL argument;
+ * R outside 1..HGMM_L2_MAX_HYP; pair[r] out of range; sigma[r] not positive (NaN included); the records of one call above
+ * 1 GiB.  HGMM_ERR_STATE: no resident pairs.  A NON-FINITE POSE IS NOT REFUSED: a NaN in it makes its 13 outputs NaN, the other
+ * hypotheses' are what they would have been, and the optimiser deals with it. */
+#define HGMM_L2_MAX_PAIRS 65536
+#define HGMM_L2_MAX_HYP 4096
+#define HGMM_L2_NOUT 13
+int hgmm_l2_set_pairs(hgmm_ctx* ctx, int B, const int32_t* Js /* [B] */, const double* mu_s /* [sum Js][3] */,
+                      const double* phi_s /* [sum Js] */, const int32_t* Jt /* [B] */, const double* mu_t /* [sum Jt][3] */,
+                      const double* phi_t /* [sum Jt] */);
+int hgmm_l2_cost(hgmm_ctx* ctx, int R, const int32_t* pair /* [R] */, const double* rot /* [R][9] */,
+                 const double* t /* [R][3] */, const double* sigma /* [R] */, double* out /* [R][13] */);
+
 /* ---- voxel-grid down-sample: centroids + counts, one cloud or B clouds per launch set -----------------------------------
  * Every pipeline of the reference voxel-down-samples its scans first -- o3.voxel_down_sample at hgmm/hgmm_gpu.py:786 and
  * 829-830, run_gmm_static.py:28, waymoutils.py:99, gmmreg.py:203-204 -- and the counts are what the weight entries above
