@@ -1846,8 +1846,9 @@ __device__ __forceinline__ void tree_reg_normal_body(unsigned long long* __restr
 
 
 // ---- the registration loop (hgmm_gpu.py:754-768) with its 6 x 6 M-step on the host side of this library ----------
-// eigenvalue range of a symmetric 6 x 6 matrix by cyclic Jacobi sweeps (for the conditioning test only)
-inline void sym6_eig_range(const double (&A)[6][6], double* lo, double* hi) {
+// eigenvalue range of a symmetric 6 x 6 matrix by cyclic Jacobi sweeps (for the conditioning test only; on the device it is
+// a call of its own, so that the one thread that gets here does not carry its registers through the rest of its kernel)
+__host__ __device__ __attribute__((noinline)) inline void sym6_eig_range(const double (&A)[6][6], double* lo, double* hi) {
     double a[6][6];
     for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) a[i][j] = A[i][j];
     for (int sweep = 0; sweep < 30; ++sweep) {
@@ -1864,8 +1865,8 @@ inline void sym6_eig_range(const double (&A)[6][6], double* lo, double* hi) {
             for (int q = p + 1; q < 6; ++q) {
                 if (a[p][q] == 0.0) continue;
                 const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-                const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / std::sqrt(tt * tt + 1.0), sn = tt * cs;
+                const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
                 for (int k = 0; k < 6; ++k) {
                     const double akp = a[k][p], akq = a[k][q];
                     a[k][p] = cs * akp - sn * akq;
@@ -1879,7 +1880,7 @@ inline void sym6_eig_range(const double (&A)[6][6], double* lo, double* hi) {
             }
     }
     *lo = *hi = a[0][0];
-    for (int i = 1; i < 6; ++i) { *lo = std::min(*lo, a[i][i]); *hi = std::max(*hi, a[i][i]); }
+    for (int i = 1; i < 6; ++i) { *lo = a[i][i] < *lo ? a[i][i] : *lo; *hi = *hi < a[i][i] ? a[i][i] : *hi; }
 }
 // A x = b by Gaussian elimination with partial pivoting (what LAPACK's gesv does); false: singular
 inline bool solve6(const double (&A)[6][6], const double (&b)[6], double (&x)[6]) {
@@ -1933,61 +1934,77 @@ inline void twist_compose(const double (&x)[6], double* rot, double* t) {
     for (int i = 0; i < 3; ++i) t[i] = t2[i];
 }
 
-// The host side of ONE registration iteration, shared by hgmm_tree_register and hgmm_tree_register_batch: o[28] = the
-// normal equations the device produced (tree_reg_normal_kernel).  -> 0: (rot, t) updated, go on; 1: updated and stopped by
-// |q - q_prev| < tol; 2: too ill-conditioned for normal equations (nothing updated): the caller takes the reference's
-// stacked least-squares M-step.  *q_out = this iteration's q (status 0 / 1).
-inline int reg_host_step(const double* o, double* rot, double* t, double* q_prev_inout, double tol, double* q_out) {
-    double A[6][6], b[6], x[6];
+// THE conditioning rule of a registration iteration, for the host step and the device step alike (reg_host_step,
+// reg_device_step): may the normal equations A x = b be solved as they are?  false: not finite, or lambda_min(A) <= 1e-11
+// lambda_max(A) -- the caller leaves with status 2 and the iteration goes to the reference's stacked least squares.
+// A cheap certificate of the opposite first: with A = L L^T, lambda_min >= 1 / ||A^-1||_inf and lambda_max <= ||A||_inf, so
+// 1 / ||A^-1||_inf > 1e-10 ||A||_inf (a decade of margin for its own rounding) settles it without the eigenvalues (~0.2 us
+// instead of the Jacobi sweeps' ~2 us per pair and iteration on the host); only a system that fails the certificate gets the
+// exact test.  The Cholesky factorisation alone decides nothing: a pivot is >= lambda_min and a diagonal entry <= lambda_max,
+// so smallest pivot / largest diagonal entry >= lambda_min / lambda_max -- a small pivot ratio implies a small eigenvalue
+// ratio and NOT the other way round (unpivoted Cholesky is not rank-revealing: centroids within 1e-6 of a line give a pivot
+// ratio of 9e-7 under an eigenvalue ratio of 8e-13).  Lm: the factor L (lower triangle), valid where *factored.
+__host__ __device__ inline bool reg_well_conditioned(const double (&A)[6][6], const double (&b)[6], double (&Lm)[6][6],
+                                                     bool* factored) {
+    *factored = false;
     bool finite = true;
-    for (int i = 0, k = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j, ++k) { A[i][j] = A[j][i] = o[k]; finite = finite && std::isfinite(o[k]); }
-    for (int i = 0; i < 6; ++i) { b[i] = o[21 + i]; finite = finite && std::isfinite(b[i]); }
-    // The conditioning rule is lambda_min <= 1e-11 lambda_max.  A cheap certificate of the opposite first: with A = L L^T,
-    // lambda_min >= 1 / ||A^-1||_inf and lambda_max <= ||A||_inf, so 1 / ||A^-1||_inf > 1e-11 ||A||_inf settles it without
-    // the eigenvalues (~0.2 us instead of the Jacobi sweeps' ~2 us per pair and iteration -- the host's share of a batched
-    // registration); only a system that fails the certificate gets the exact test.  Same verdicts, same solve.
-    bool well = false;
-    if (finite) {
-        double Lm[6][6], Li[6][6];
-        bool spd = true;
-        for (int j = 0; j < 6 && spd; ++j) {
-            double sdiag = A[j][j];
-            for (int k = 0; k < j; ++k) sdiag -= Lm[j][k] * Lm[j][k];
-            if (!(sdiag > 0.0)) { spd = false; break; }
-            Lm[j][j] = std::sqrt(sdiag);
-            for (int i = j + 1; i < 6; ++i) {
-                double v = A[i][j];
-                for (int k = 0; k < j; ++k) v -= Lm[i][k] * Lm[j][k];
-                Lm[i][j] = v / Lm[j][j];
-            }
-        }
-        if (spd) {
-            for (int c2 = 0; c2 < 6; ++c2)                         // Li = L^-1 (lower triangular), column by column
-                for (int i = 0; i < 6; ++i) {
-                    if (i < c2) { Li[i][c2] = 0.0; continue; }
-                    double v = (i == c2) ? 1.0 : 0.0;
-                    for (int k = c2; k < i; ++k) v -= Lm[i][k] * Li[k][c2];
-                    Li[i][c2] = v / Lm[i][i];
-                }
-            double ninv = 0.0, na = 0.0;
-            for (int i = 0; i < 6; ++i) {
-                double ri = 0.0, ra = 0.0;
-                for (int j = 0; j < 6; ++j) {
-                    double aij = 0.0;                              // (A^-1)_ij = sum_k Li[k][i] Li[k][j]
-                    for (int k = (i > j ? i : j); k < 6; ++k) aij += Li[k][i] * Li[k][j];
-                    ri += std::fabs(aij);
-                    ra += std::fabs(A[i][j]);
-                }
-                ninv = std::max(ninv, ri);
-                na = std::max(na, ra);
-            }
-            well = std::isfinite(ninv) && ninv > 0.0 && 1.0 / ninv > 1.0e-10 * na;      // (a decade of margin for its own rounding)
+    for (int i = 0; i < 6; ++i) {
+        for (int j = i; j < 6; ++j) finite = finite && std::isfinite(A[i][j]);
+        finite = finite && std::isfinite(b[i]);
+    }
+    if (!finite) return false;
+    bool spd = true;
+    for (int j = 0; j < 6 && spd; ++j) {
+        double sdiag = A[j][j];
+        for (int k = 0; k < j; ++k) sdiag -= Lm[j][k] * Lm[j][k];
+        if (!(sdiag > 0.0)) { spd = false; break; }
+        Lm[j][j] = sqrt(sdiag);
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[i][j];
+            for (int k = 0; k < j; ++k) v -= Lm[i][k] * Lm[j][k];
+            Lm[i][j] = v / Lm[j][j];
         }
     }
+    *factored = spd;
+    if (spd) {
+        double Li[6][6];
+        for (int c2 = 0; c2 < 6; ++c2)                         // Li = L^-1 (lower triangular), column by column
+            for (int i = 0; i < 6; ++i) {
+                if (i < c2) { Li[i][c2] = 0.0; continue; }
+                double v = (i == c2) ? 1.0 : 0.0;
+                for (int k = c2; k < i; ++k) v -= Lm[i][k] * Li[k][c2];
+                Li[i][c2] = v / Lm[i][i];
+            }
+        double ninv = 0.0, na = 0.0;
+        for (int i = 0; i < 6; ++i) {
+            double ri = 0.0, ra = 0.0;
+            for (int j = 0; j < 6; ++j) {
+                double aij = 0.0;                              // (A^-1)_ij = sum_k Li[k][i] Li[k][j]
+                for (int k = (i > j ? i : j); k < 6; ++k) aij += Li[k][i] * Li[k][j];
+                ri += fabs(aij);
+                ra += fabs(A[i][j]);
+            }
+            ninv = ninv < ri ? ri : ninv;
+            na = na < ra ? ra : na;
+        }
+        if (std::isfinite(ninv) && ninv > 0.0 && 1.0 / ninv > 1.0e-10 * na) return true;
+    }
     double lo = 0.0, hi = 0.0;
-    if (finite && !well) sym6_eig_range(A, &lo, &hi);
-    if (!finite || (!well && (!(hi > 0.0) || lo <= 1e-11 * hi)) || !solve6(A, b, x)) return 2;
+    sym6_eig_range(A, &lo, &hi);
+    return hi > 0.0 && !(lo <= 1e-11 * hi);
+}
+
+// The host side of ONE registration iteration, shared by hgmm_tree_register and hgmm_tree_register_batch: o[28] = the
+// normal equations the device produced (tree_reg_normal_kernel).  -> 0: (rot, t) updated, go on; 1: updated and stopped by
+// |q - q_prev| < tol; 2: too ill-conditioned for normal equations (reg_well_conditioned; nothing updated): the caller takes
+// the reference's stacked least-squares M-step.  *q_out = this iteration's q (status 0 / 1).
+inline int reg_host_step(const double* o, double* rot, double* t, double* q_prev_inout, double tol, double* q_out) {
+    double A[6][6], b[6], x[6], Lm[6][6];
+    for (int i = 0, k = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j, ++k) A[i][j] = A[j][i] = o[k];
+    for (int i = 0; i < 6; ++i) b[i] = o[21 + i];
+    bool factored = false;
+    if (!reg_well_conditioned(A, b, Lm, &factored) || !solve6(A, b, x)) return 2;
     double xb = 0.0;
     for (int i = 0; i < 6; ++i) xb += x[i] * b[i];
     const double q = std::max(o[27] - xb, 0.0);
@@ -2168,34 +2185,20 @@ struct ForestRegPair {
 // reg_device_solve, off by default: north_star keeps the rigid solve on the host, and the host path is the parity
 // reference): o[28] = the normal equations; solves the 6 x 6 system, composes the twist, applies the stop rule and
 // prepares the fixed-point encoding of the next E-step, all in the pair's table entry -- the next launch reads (R, t)
-// from device memory and the host only follows a progress word.  Differences to the host path, both inside the 1e-8 the
-// per-iteration trace is held to: Cholesky instead of elimination with pivoting, the device's sin / cos, fused
-// multiply-adds; the conditioning test is on the Cholesky pivots (smallest pivot <= 1e-11 largest diagonal entry --
-// implied by the host's eigenvalue test failing, not equivalent to it): such a pair stops with status 2 and the caller
-// finishes it on the host path, as in the host loop.
+// from device memory and the host only follows a progress word.  The conditioning verdict is the host's, by the host's
+// function (reg_well_conditioned): a system the host step hands over leaves here with status 2 as well, and the caller
+// finishes the pair on the host path, as in the host loop.  Differences to the host path, both inside the 1e-8 the
+// per-iteration trace is held to: the Cholesky factor of the verdict solves the system instead of elimination with
+// pivoting (a system that passed the exact test without a factor -- none is known -- leaves with status 2 too: the device
+// never goes on where the host does not), the device's sin / cos, fused multiply-adds.
 __device__ inline void reg_device_step(const double* __restrict__ o, ForestRegPair* pr, double tol, int max_iter,
                                        double* __restrict__ trace_row) {
-    double A[6][6], b[6], x[6], y[6];
-    bool ok = true;
-    double dmax = 0.0;
+    double S[6][6], A[6][6], b[6], x[6], y[6];
     for (int i = 0, k = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j, ++k) { A[i][j] = A[j][i] = o[k]; ok = ok && (fabs(o[k]) < 1.0e300); }
-    for (int i = 0; i < 6; ++i) { b[i] = o[21 + i]; ok = ok && (fabs(b[i]) < 1.0e300); dmax = fmax(dmax, A[i][i]); }
-    double pmin = 1.0e300;
-    for (int j = 0; j < 6 && ok; ++j) {                       // A = L L^T, L in the lower triangle of A
-        double s = A[j][j];
-        for (int k = 0; k < j; ++k) s -= A[j][k] * A[j][k];
-        pmin = fmin(pmin, s);
-        if (!(s > 0.0)) { ok = false; break; }
-        const double d = sqrt(s);
-        A[j][j] = d;
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[i][j];
-            for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
-            A[i][j] = v / d;
-        }
-    }
-    if (!ok || !(dmax > 0.0) || pmin <= 1.0e-11 * dmax) {
+        for (int j = i; j < 6; ++j, ++k) S[i][j] = S[j][i] = o[k];
+    for (int i = 0; i < 6; ++i) b[i] = o[21 + i];
+    bool factored = false;                                    // A: the verdict's factor L of S, in its lower triangle
+    if (!reg_well_conditioned(S, b, A, &factored) || !factored) {
         pr->status = 2;
         pr->active = 0;
         return;

@@ -403,9 +403,13 @@ int hgmm_tree_reg_normal(hgmm_ctx* ctx, const double* rot, const double* t, doub
  * (eigh + QR on the host) and may call again.  trace (optional): per iteration rot, t, q.
  * Per-context option reg_device_solve = 1 (hgmm_config_set; off by default -- the host solve is the parity reference):
  * the whole loop runs on the device -- Cholesky solve of the 6 x 6 system, twist, stop rule and the fixed-point encoding
- * of the next E-step in one device thread behind the normal equations, the host only follows a progress word.  Same
- * trajectory to ~1e-12 (device sin / cos, fused multiply-adds, Cholesky instead of pivoted elimination); status 2 is
- * decided on the Cholesky pivots (smallest pivot <= 1e-11 largest diagonal entry).  Not under a communicator.      */
+ * of the next E-step in one device thread behind the normal equations, the host only follows a progress word.  Status 2
+ * is decided by the host path's own rule, in the same function (lambda_min <= 1e-11 lambda_max, behind a Cholesky
+ * certificate of the opposite): the device never goes on where the host hands over.  The Cholesky pivots alone do not
+ * decide it -- smallest pivot / largest diagonal entry >= lambda_min / lambda_max, so small pivots imply the rule and the
+ * rule does not imply small pivots.  Where both go on: the same trajectory to ~1e-12 on well-conditioned pairs, in general
+ * to the order of cond(A^T A) 2^-52 |twist| per iteration (device sin / cos, fused multiply-adds, Cholesky instead of
+ * pivoted elimination).  Not under a communicator.      */
 int hgmm_tree_register(hgmm_ctx* ctx, double* rot, double* t, double scale, double lambda_c, int max_iter, double tol,
                        double* q_prev_inout, int* iters_out, int* status_out, double* trace);
 /* Mahalanobis GATE of the registration E-step (robustness to clutter and partial overlap).  The reference has no counterpart:

@@ -182,6 +182,16 @@ def solution_tolerance(m0, m1, mu, cov, k, D, F, x):
     return 1e-9 + lam[-1] / lam[0] * U * np.abs(x).max()
 
 
+def cholesky_gap(ata, x):
+    """What the device's solve (reg_device_solve: Cholesky on the normal equations, reg_device_step) may add to
+    solution_tolerance: c cond(A^T A) 2^-52 |x| with c = 8 * 6.  Derived, not measured: a Cholesky solve is backward stable
+    (Higham, Accuracy and Stability of Numerical Algorithms, 10.1), so its forward error is of order cond(A^T A) u |x| like
+    that of the host's elimination, but the two differ from each other and from lstsq by that much; six unknowns and a handful
+    of roundings each give the constant.  ``ata``: the oracle's A^T A at that pose, |x| the max norm of its lstsq twist."""
+    lam = np.linalg.eigvalsh(ata)
+    return 8 * 6 * lam[-1] / lam[0] * 2.0 ** -52 * np.abs(x).max()
+
+
 def check_estep(ctx, pi, mu, cov, L, X, R, t, scale, label):
     """ctx.tree_reg_estep with (R, t, scale) on the device, and the drop-in gmmTreeRegESTep on the pre-moved cloud, against
     hgmm_tree.reg_e_step of the moved target (the L = 2 bounds: rtol 1e-10, atol 1e-12; for m2 the atol is the larger of
@@ -297,10 +307,11 @@ def test_reg_normal_equations_synthetic_L6(ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. the registration loop, one oracle step at a time
 # ---------------------------------------------------------------------------------------------------------------------
-def oracle_step(target, pi, mu, cov, L, rot, t):
+def oracle_step(target, pi, mu, cov, L, rot, t, device_solve=0):
     """One reference iteration from pose (rot, t), no near-tie allowed: -> (rot', t', q, tolerances of rot' / t' / q for the
     library's result (solution_tolerance carried through the twist: t' = dR t + v moves by |dw| |t| + |dv|; q = btb - x.Atb
-    by |dx| |Atb|), pairs at nodes >= 584).  No node with mass (the target left the tree): x = 0, the pose stays."""
+    by |dx| |Atb|), pairs at nodes >= 584).  No node with mass (the target left the tree): x = 0, the pose stays.
+    ``device_solve``: the library's solve was the device's -- cholesky_gap on top of solution_tolerance."""
     Y = target @ rot.T + t
     desc = hgmm_tree.reg_descent(Y, pi, mu, cov, L, LC)
     assert not hgmm_tree.reg_near_ties(desc, TIE).any()
@@ -313,50 +324,72 @@ def oracle_step(target, pi, mu, cov, L, rot, t):
     x = np.linalg.lstsq(A, b, rcond=-1)[0]
     D, F = encoding(target, rot, t, 1.0, mu)
     tol = solution_tolerance(m0, m1, mu, cov, np.bincount(desc.node[desc.contrib], minlength=len(pi)), D, F, x)
+    if device_solve:
+        tol += cholesky_gap(ata, x)
     return r1, t1, q, (tol, tol * (1 + np.linalg.norm(t)), tol * np.linalg.norm(atb)), deep
 
 
-def shadow_loop(ctx, pi, mu, cov, L, target, budget, label):
-    """ctx.tree_register(..., tol=0, want_trace=True): every iteration k from the device's pose k-1 through one oracle
-    E-step + reg_m_step == the device's pose k ((R, t) within 1e-9 plus the oracle's own normal-equations-vs-lstsq gap at
-    that pose, see check_normal; q rtol 1e-7).  An iteration the library hands to the host (status 2) is followed through
-    GMMTree's Python path with callbacks."""
-    from hgmm_amd.hgmm.hgmm_gpu import GMMTree
+def library_loop(ctx, pi, mu, cov, L, target, budget, device_solve):
+    """ctx.tree_register from the identity with tol 0 and a trace, under reg_device_solve = ``device_solve``"""
     ctx.tree_set_nodes(L, pi, mu, cov)
     ctx.tree_set_target(target)
-    rot, t, done, q, status, trace = ctx.tree_register(np.identity(3), np.zeros(3), 1.0, LC, budget, 0.0, want_trace=True)
-    poses = [(trace[k, :9].reshape(3, 3), trace[k, 9:12], trace[k, 12]) for k in range(done)]
-    if status == 2:
-        gt = GMMTree(None, tree_level=L, lambda_c=LC, ctx=ctx)
-        gt.set_nodes(pi, mu, cov)
-        rec = []
-        gt.set_callbacks([lambda tf: rec.append((tf.rot.T.copy(), -(tf.rot.T @ tf.t)))])
-        gt.registration(target, budget, 0.0)
-        poses = [(r, tt, None) for r, tt in rec]
-        print("%s: the library handed iteration %d to the host; the Python path is shadowed instead" % (label, done + 1))
-    assert len(poses) == budget
+    with ctx.config(reg_device_solve=device_solve):
+        return ctx.tree_register(np.identity(3), np.zeros(3), 1.0, LC, budget, 0.0, want_trace=True)
+
+
+def shadow_poses(poses, target, pi, mu, cov, L, label, device_solve):
+    """Every pose k from pose k-1 (the identity first) through one oracle_step == pose k.  -> (largest pose difference, largest
+    difference / tolerance, deep pairs per iteration)"""
     r_prev, t_prev = np.identity(3), np.zeros(3)
-    worst, deep = 0.0, []
+    worst, ratio, deep = 0.0, 0.0, []
     for k, (r_k, t_k, q_k) in enumerate(poses):
-        o_r, o_t, o_q, (tol_r, tol_t, tol_q), n_deep = oracle_step(target, pi, mu, cov, L, r_prev, t_prev)
+        o_r, o_t, o_q, (tol_r, tol_t, tol_q), n_deep = oracle_step(target, pi, mu, cov, L, r_prev, t_prev, device_solve)
         deep.append(n_deep)
+        ratio = max(ratio, np.abs(r_k - o_r).max() / tol_r, np.abs(t_k - o_t).max() / tol_t)
         np.testing.assert_allclose(r_k, o_r, rtol=0, atol=tol_r, err_msg="%s iteration %d" % (label, k))
         np.testing.assert_allclose(t_k, o_t, rtol=0, atol=tol_t, err_msg="%s iteration %d" % (label, k))
         if q_k is not None and np.size(o_q):
             np.testing.assert_allclose(q_k, o_q[0], rtol=1e-7, atol=tol_q, err_msg="%s iteration %d" % (label, k))
         worst = max(worst, np.abs(r_k - o_r).max(), np.abs(t_k - o_t).max())
         r_prev, t_prev = r_k, t_k
-    print("%s: %d iterations shadowed (status %d after %d in the library), largest pose difference %.3g, deep pairs per "
-          "iteration %s" % (label, budget, status, done, worst, deep[:4] + ["..."]))
+    return worst, ratio, deep
+
+
+def shadow_loop(ctx, pi, mu, cov, L, target, budget, label, device_solve=0):
+    """ctx.tree_register(..., tol=0, want_trace=True): every iteration k from the device's pose k-1 through one oracle
+    E-step + reg_m_step == the device's pose k ((R, t) within 1e-9 plus the oracle's own normal-equations-vs-lstsq gap at
+    that pose, see check_normal; q rtol 1e-7).  An iteration the library hands to the host (status 2) is followed through
+    GMMTree's Python path with callbacks.  ``device_solve``: the library calls run under reg_device_solve = 1 and the
+    tolerances carry cholesky_gap; the iterations the device did before it handed one over are shadowed as well.
+    -> (status, iterations done in the library)"""
+    from hgmm_amd.hgmm.hgmm_gpu import GMMTree
+    rot, t, done, q, status, trace = library_loop(ctx, pi, mu, cov, L, target, budget, device_solve)
+    poses = [(trace[k, :9].reshape(3, 3), trace[k, 9:12], trace[k, 12]) for k in range(done)]
+    if status == 2:
+        if device_solve:
+            shadow_poses(poses, target, pi, mu, cov, L, label + " (before the hand-over)", device_solve)
+        with ctx.config(reg_device_solve=device_solve):
+            gt = GMMTree(None, tree_level=L, lambda_c=LC, ctx=ctx)
+            gt.set_nodes(pi, mu, cov)
+            rec = []
+            gt.set_callbacks([lambda tf: rec.append((tf.rot.T.copy(), -(tf.rot.T @ tf.t)))])
+            gt.registration(target, budget, 0.0)
+        poses = [(r, tt, None) for r, tt in rec]
+        print("%s: the library handed iteration %d to the host; the Python path is shadowed instead" % (label, done + 1))
+        device_solve = 0                                      # (the Python path solves on the host)
+    assert len(poses) == budget
+    worst, ratio, deep = shadow_poses(poses, target, pi, mu, cov, L, label, device_solve)
+    print("%s: %d iterations shadowed (status %d after %d in the library), largest pose difference %.3g = %.3g of its bound, "
+          "deep pairs per iteration %s" % (label, budget, status, done, worst, ratio, deep[:4] + ["..."]))
     if L >= 4:
         assert deep[0] > 0
-    return status
+    return status, done
 
 
-def assert_no_ties_along(target, pi, mu, cov, L, o_tr):
+def assert_no_ties_along(target, pi, mu, cov, L, o_tr, device_solve=0):
     """No near-tie at any pose the oracle's registration visited (identity, then every pose but the last).  -> the sum over
-    its iterations of solution_tolerance carried to the pose (see oracle_step): what the final pose may differ by on top of
-    the L = 2 bound."""
+    its iterations of solution_tolerance (with ``device_solve`` plus cholesky_gap) carried to the pose (see oracle_step):
+    what the final pose may differ by on top of the L = 2 bound."""
     poses = [(np.identity(3), np.zeros(3))] + [(e[0], e[1]) for e in o_tr[:-1]]
     total = 0.0
     for k, ((r, t), e) in enumerate(zip(poses, o_tr)):
@@ -364,9 +397,12 @@ def assert_no_ties_along(target, pi, mu, cov, L, o_tr):
         assert not hgmm_tree.reg_near_ties(desc, TIE).any(), k
         m0, m1 = e[3], e[4]
         if (~(m0 < hgmm_tree.F32_EPS)).any():
-            x = np.linalg.lstsq(*hgmm_tree.reg_normal_equations(m0, m1, mu, cov)[3:], rcond=-1)[0]
+            ata, _, _, A, b = hgmm_tree.reg_normal_equations(m0, m1, mu, cov)
+            x = np.linalg.lstsq(A, b, rcond=-1)[0]
             D, F = encoding(target, r, t, 1.0, mu)
             tol = solution_tolerance(m0, m1, mu, cov, np.bincount(desc.node[desc.contrib], minlength=len(pi)), D, F, x) - 1e-9
+            if device_solve:
+                tol += cholesky_gap(ata, x)
             total += tol * (1 + np.linalg.norm(t))
     return total
 
@@ -378,16 +414,18 @@ def stop_rule_close(o_tr, tol):
     return bool(np.any(np.abs(dq - tol) <= 1e-6 * tol)), dq
 
 
-def check_stop_rule(ctx, pi, mu, cov, L, target, label, maxiter=20, tol=1e-4):
+def check_stop_rule(ctx, pi, mu, cov, L, target, label, maxiter=20, tol=1e-4, device_solve=0):
     """GMMTree.registration without callbacks (the library's loop; an iteration it hands to the host runs there) with the
     reference's stop rule == hgmm_tree.register: same iteration count (unless |dq| came within 1e-6 relative of tol on the
-    oracle's path) and final (R, t) within 1e-8 (the L = 2 bound)."""
+    oracle's path) and final (R, t) within 1e-8 (the L = 2 bound).  ``device_solve``: under reg_device_solve = 1, with
+    cholesky_gap per iteration on top."""
     from hgmm_amd.hgmm.hgmm_gpu import GMMTree
     o_rot, o_t, o_q, o_tr = hgmm_tree.register(target, pi, mu, cov, L, LC, maxiter, tol)
-    extra = assert_no_ties_along(target, pi, mu, cov, L, o_tr)
+    extra = assert_no_ties_along(target, pi, mu, cov, L, o_tr, device_solve)
     gt = GMMTree(None, tree_level=L, lambda_c=LC, ctx=ctx)
     gt.set_nodes(pi, mu, cov)
-    res = gt.registration(target, maxiter, tol)
+    with ctx.config(reg_device_solve=device_solve):
+        res = gt.registration(target, maxiter, tol)
     close, dq = stop_rule_close(o_tr, tol)
     print("%s: %d iterations (oracle %d), |dq| %s" % (label, gt.n_iter_, len(o_tr), np.array2string(dq, precision=3)))
     if not close:
@@ -411,13 +449,17 @@ def scan_pair_target(bunny):
     return world @ rot_about([0.3, 1.0, 0.2], 8.0).T + np.array([0.005, -0.00375, 0.00625])
 
 
+@pytest.mark.parametrize("device_solve", [0, 1])
 @pytest.mark.parametrize("key", ["4", "5", "4far"])
-def test_registration_loop_shadows_oracle(ctx, bun_trees, bunny, key):
+def test_registration_loop_shadows_oracle(ctx, bun_trees, bunny, key, device_solve):
     """``4far``: the reference linearises the rotation about the ORIGIN (twist x = (w, v)), so a cloud 47 m away takes a
     second-order error of ~|w|^2 |c| / 2 per step -- 18 cm at 5 deg, more than the bunny's size.  The oracle itself then
     overshoots: after one or two iterations no node of the tree receives mass, the system is empty, the library hands that
     iteration to the host (status 2), and the Python path with callbacks has to follow the oracle from there on.  A 0.5 deg
-    motion (second-order error ~2 mm) converges far from the origin as well, through the library's own loop."""
+    motion (second-order error ~2 mm) converges far from the origin as well, through the library's own loop.
+    ``device_solve`` = 1: the same under reg_device_solve (reg_device_step solves, composes the twist, applies the stop rule
+    and gives the verdict); an empty system ends the library's loop with status 2 at the iteration at which it ends the
+    host path's."""
     P, L, pi, mu, cov = bun_trees[key]
     off = P[0] - bunny[0].astype(np.float64)
     pairs = {"bunny 5 deg": moved(P[::4], 5.0, [0.2, 1.0, 0.3], [0.003, -0.002, 0.001]),
@@ -427,8 +469,11 @@ def test_registration_loop_shadows_oracle(ctx, bun_trees, bunny, key):
     statuses = {}
     for name, target in pairs.items():
         label = "L=%s %s" % (key, name)
-        statuses[name] = shadow_loop(ctx, pi, mu, cov, L, target, 12, label)
-        check_stop_rule(ctx, pi, mu, cov, L, target, label)
+        statuses[name], done = shadow_loop(ctx, pi, mu, cov, L, target, 12, label, device_solve)
+        if device_solve:
+            host = library_loop(ctx, pi, mu, cov, L, target, 12, 0)
+            assert (statuses[name], done) == (host[4], host[2]), (label, statuses[name], done, host[4], host[2])
+        check_stop_rule(ctx, pi, mu, cov, L, target, label, device_solve=device_solve)
     if key == "4far":
         assert statuses["bunny 5 deg"] == 2 and statuses["bun.conf scans"] == 2
     else:
@@ -489,6 +534,34 @@ def test_registration_L4_matches_reference_golden(ctx):
             np.testing.assert_allclose(res.transformation.rot, g[tag + "final_rot"], atol=1e-8)
             np.testing.assert_allclose(res.transformation.t, g[tag + "final_t"], atol=1e-8)
             np.testing.assert_allclose(res.q, g[tag + "final_q"], rtol=1e-6)
+
+
+@pytest.mark.parametrize("device_solve", [0, 1])
+def test_split_budget_is_one_call_with_the_stop_rule_across_calls(ctx, device_solve):
+    """tree_register with budgets 3 + 3, the pose and q handed on, == one call with budget 6, bit for bit: pose, q, iteration
+    count, status and trace rows -- on the host path and under reg_device_solve (has_q of the device's table entry comes
+    from the caller's q_prev).  tol = 1000 on the reference's L = 4 records: the oracle's |dq| on rot10_target is 12 589,
+    2 033, 380.5, 132, ... (hgmm_tree.register), so the one call stops at its FOURTH iteration -- the first of the second
+    half, which stops only if the first half's q reached it; on rot30_target |dq| stays above 1 278 and nothing stops.
+    (q agrees with the oracle's to 1e-7 relative, test_registration_L4_matches_reference_golden: 380.5 and 1 278 are far
+    from 1000.)"""
+    g = load_golden("hgmm_reg_L4.npz")
+    L, lc, tol = int(g["L"]), float(g["lambda_c"]), 1000.0
+    ctx.tree_set_nodes(L, g["pi"], g["mu"], g["cov"])
+    I3, Z3 = np.identity(3), np.zeros(3)
+    expect = {"rot10_": (4, 1), "rot30_": (6, 0)}
+    for tag, (n_iter, st) in expect.items():
+        ctx.tree_set_target(g[tag + "target"])
+        with ctx.config(reg_device_solve=device_solve):
+            r6, t6, d6, q6, s6, tr6 = ctx.tree_register(I3, Z3, 1.0, lc, 6, tol, want_trace=True)
+            r1, t1, d1, q1, s1, tr1 = ctx.tree_register(I3, Z3, 1.0, lc, 3, tol, want_trace=True)
+            r2, t2, d2, q2, s2, tr2 = ctx.tree_register(r1, t1, 1.0, lc, 3, tol, q_prev=q1, want_trace=True)
+        print("%s reg_device_solve %d: one call %d iterations (status %d), split %d + %d (status %d, %d)"
+              % (tag, device_solve, d6, s6, d1, d2, s1, s2))
+        assert (d6, s6) == (n_iter, st)
+        assert (d1, s1) == (3, 0) and (d1 + d2, s2) == (d6, s6)
+        assert np.array_equal(r2, r6) and np.array_equal(t2, t6) and q2 == q6
+        assert np.array_equal(np.concatenate([tr1, tr2]), tr6)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
