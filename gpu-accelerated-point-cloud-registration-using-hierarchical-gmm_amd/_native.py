@@ -169,6 +169,8 @@ def load_library(path: str = LIB_PATH):
         _sig(lib, "hgmm_gauss_transform", [ctx, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp])
         _sig(lib, "hgmm_l2_set_pairs", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp])
         _sig(lib, "hgmm_l2_cost", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp])
+        _sig(lib, "hgmm_l2_solve", [ctx, C.c_int, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp])
+        _sig(lib, "hgmm_l2_solve_each", [ctx, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
         _sig(lib, "hgmm_comm_unique_id", [_vp])
         _sig(lib, "hgmm_comm_init_rank", [ctx, C.c_int, C.c_int, _vp])
         _sig(lib, "hgmm_comm_destroy", [ctx])
@@ -1792,6 +1794,33 @@ class Context:
         out = np.empty((R, 13))
         self._check(self.lib.hgmm_l2_cost(self.h, R, _ptr(pair_ids), _ptr(rots), _ptr(ts), _ptr(sigmas), _ptr(out)))
         return out
+
+    def l2_solve(self, pair_ids, thetas, sigmas, max_iter=10, gtol=1e-5):
+        """The whole BFGS solve of R hypotheses on the resident pairs, on the device and in lock-step (hgmm_l2_solve):
+        ``pair_ids`` [R], ``thetas`` [R,7] start points (qw, qx, qy, qz, tx, ty, tz), ``sigmas`` [R] (or one for all);
+        ``max_iter`` and ``gtol`` are SciPy's ``maxiter`` and ``gtol`` -- one for all, or [R] of each hypothesis' own
+        (hgmm_l2_solve_each).  -> ``(x [R,7], f [R], grad [R,7], nit [R], nfev [R], status [R])``; status 0 gtol met,
+        1 max_iter reached, 2 line search failed, 3 NaN.  The optimiser is SciPy 1.15's BFGS with its first line search
+        (dcsrch); where SciPy would try a second line search after dcsrch failed, the solve ends at once with status 2, so
+        ``nfev`` differs from SciPy's by design.  Row r does not depend on R or on the other rows."""
+        pair_ids = np.ascontiguousarray(pair_ids, dtype=np.int32).reshape(-1)
+        R = len(pair_ids)
+        thetas = np.ascontiguousarray(thetas, dtype=np.float64).reshape(-1, 7)
+        sigmas = np.ascontiguousarray(np.broadcast_to(np.asarray(sigmas, dtype=np.float64), (R,)))
+        if len(thetas) != R:
+            raise ValueError("l2_solve: %d pair ids, %d start points" % (R, len(thetas)))
+        x, f, grad = np.empty((R, 7)), np.empty(R), np.empty((R, 7))
+        nit, nfev, status = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
+        outs = (_ptr(x), _ptr(f), _ptr(grad), _ptr(nit), _ptr(nfev), _ptr(status))
+        if np.ndim(max_iter) == 0 and np.ndim(gtol) == 0:
+            self._check(self.lib.hgmm_l2_solve(self.h, R, _ptr(pair_ids), _ptr(thetas), _ptr(sigmas), int(max_iter), float(gtol),
+                                               *outs))
+        else:
+            each_iter = np.ascontiguousarray(np.broadcast_to(np.asarray(max_iter, dtype=np.int32), (R,)))
+            each_gtol = np.ascontiguousarray(np.broadcast_to(np.asarray(gtol, dtype=np.float64), (R,)))
+            self._check(self.lib.hgmm_l2_solve_each(self.h, R, _ptr(pair_ids), _ptr(thetas), _ptr(sigmas), _ptr(each_iter),
+                                                    _ptr(each_gtol), *outs))
+        return x, f, grad, nit, nfev, status
 
     # -- multi-GPU ------------------------------------------------------------------------
     @staticmethod

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhgmm_hip.so")
 SOURCES = ["hgmm_api.hip", "flat_kernels.hip", "flat_batch_weighted.hip", "tree_kernels.hip", "tree_batch.hip", "fullcov_kernels.hip", "kmeans_kernels.hip", "gmmreg_kernels.hip", "gmmreg_l2_kernels.hip",
            "voxel_kernels.hip", "voxel_sort.hip", "voxel_handover.hip"]
-HEADERS = ["hgmm_ctx.h", "flat_pace.h", "point_weights.h", "wave_ops.h", "tree_device.h", "tree_host.h", "voxel_sort.h", "flat_fused_body.h", "flat_fused_device.h", "fullcov_body.h", "kmeans_body.h", "kmeans_batch.h", "kmeans_batch_plan.h", "fullcov_batch.h", "fullcov_batch_plan.h", os.path.join("..", "..", "include", "hgmm.h")]
+HEADERS = ["hgmm_ctx.h", "flat_pace.h", "point_weights.h", "wave_ops.h", "tree_device.h", "tree_host.h", "voxel_sort.h", "flat_fused_body.h", "flat_fused_device.h", "fullcov_body.h", "kmeans_body.h", "kmeans_batch.h", "kmeans_batch_plan.h", "fullcov_batch.h", "fullcov_batch_plan.h", "l2_device.h", "l2_cost_body.h", os.path.join("..", "..", "include", "hgmm.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -16,8 +16,21 @@
 // step -- the same divisions where the host divides, differences taken axis by axis, no contraction into fused
 // multiply-adds except the pose's own dot products -- so that what remains between the two is the summation order and the
 // exponential's last bit.
+//
+// THE DEVICE SOLVE (hgmm_l2_solve): the whole BFGS solve of R hypotheses on the resident mixtures, in lock-step, two
+// launches per evaluation and no host between them:
+//   l2_solve_cost_kernel  l2_cost_kernel's body (l2_cost_body.h) over the hypotheses' CURRENT trial poses; the workgroups
+//                         of a hypothesis that has left the loop return at their first load
+//   l2_solve_step_kernel  one wave per hypothesis: adds its records as l2_finish_kernel does -- the 13 sums have the bits
+//                         hgmm_l2_cost returns for that pose -- then lane 0 does the serial part (l2_device.h: pose and
+//                         dR/dq from the quaternion, the 7-gradient, one transition of SciPy's dcsrch / BFGS state machine,
+//                         the next trial pose) and stores the progress word (left << 32 | evaluations) into pinned host
+//                         memory at system scope.  The state (L2SolveState) never leaves the device before the end.
+// The host enqueues a few evaluations ahead of the slowest running hypothesis (tree_host.h: follow_ahead).
 #include "hgmm_ctx.h"
+#include "tree_host.h"
 #include "wave_ops.h"
+#include "l2_device.h"
 
 #include <cmath>
 #include <cstring>
@@ -25,25 +38,7 @@
 
 namespace hgmm {
 
-constexpr int L2_BLOCK = 64;          // source centres per workgroup (one wave)
-constexpr int L2_TILE = 128;          // target centres per LDS tile
-constexpr int L2_SPLIT = 256;         // target centres per workgroup (two tiles)
-constexpr int L2_NOUT = HGMM_L2_NOUT;
-constexpr int L2_ROW = 8;             // doubles per tile row: mu (3), phi / z, phi mu / z (3), one pad (16-byte rows)
-constexpr unsigned long long L2_MAX_RECORD_BYTES = 1ull << 30;
-
-// one hypothesis as it travels to the device: everything that depends on sigma is worked out once, on the host
-struct L2Hyp {
-    double rot[9], t[3];
-    double neg_h2;                    // -(h h), h = sqrt(2) sigma: the exponent is d2 / neg_h2 (transforms.py: kernel_matrix)
-    double z;                         // (2 pi sigma^2)^(3/2)
-    double two_s2;                    // 2 sigma^2
-    int pair, pad;
-};
-static_assert(sizeof(L2Hyp) == 128, "L2Hyp is 16 words");
-
-inline int l2_blocks(int Js) { return (Js + L2_BLOCK - 1) / L2_BLOCK; }
-__host__ __device__ inline int l2_splits(int Jt) { return (Jt + L2_SPLIT - 1) / L2_SPLIT; }
+static_assert(L2_NOUT == HGMM_L2_NOUT, "l2_device.h");
 
 __global__ __launch_bounds__(L2_BLOCK) void l2_cost_kernel(
     const double* __restrict__ mu_s, const double* __restrict__ phi_s, const double* __restrict__ mu_t,
@@ -53,64 +48,7 @@ __global__ __launch_bounds__(L2_BLOCK) void l2_cost_kernel(
     __shared__ double tile[L2_TILE][L2_ROW];
     const int r = blockIdx.y;
     const L2Hyp& h = hyps[r];
-    const L2Pair p = pairs[h.pair];
-    const int nsp = l2_splits(p.Jt);
-    const int w = blockIdx.x;
-    if (w >= ((p.Js + L2_BLOCK - 1) / L2_BLOCK) * nsp) return;      // (uniform: the whole workgroup leaves)
-    const int sb = w / nsp, sp = w - sb * nsp;
-    const int i = sb * L2_BLOCK + (int)threadIdx.x;
-    const bool live = i < p.Js;
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0, ps = 0.0;
-    if (live) {
-        const double* x = mu_s + 3 * (size_t)(p.s_first + i);
-        x0 = x[0]; x1 = x[1]; x2 = x[2];
-        ps = phi_s[p.s_first + i];
-    }
-    // y = rot x + t, each dot product one multiply and two fused multiply-adds in the order of the columns
-    const double y0 = fma(x2, h.rot[2], fma(x1, h.rot[1], x0 * h.rot[0])) + h.t[0];
-    const double y1 = fma(x2, h.rot[5], fma(x1, h.rot[4], x0 * h.rot[3])) + h.t[1];
-    const double y2 = fma(x2, h.rot[8], fma(x1, h.rot[7], x0 * h.rot[6])) + h.t[2];
-    const double neg_h2 = h.neg_h2, z = h.z;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;                  // g0, g1[3] of this split
-    const int c_begin = sp * L2_SPLIT;
-    const int c_end = min(p.Jt, c_begin + L2_SPLIT);
-    for (int base = c_begin; base < c_end; base += L2_TILE) {
-        const int cnt = min(L2_TILE, c_end - base);
-        __syncthreads();
-        for (int j = (int)threadIdx.x; j < cnt; j += L2_BLOCK) {
-            const double* m = mu_t + 3 * (size_t)(p.t_first + base + j);
-            const double ph = phi_t[p.t_first + base + j];
-            const double m0 = m[0], m1 = m[1], m2 = m[2];
-            tile[j][0] = m0; tile[j][1] = m1; tile[j][2] = m2;
-            tile[j][3] = ph / z;
-            tile[j][4] = (ph * m0) / z; tile[j][5] = (ph * m1) / z; tile[j][6] = (ph * m2) / z;
-        }
-        __syncthreads();
-        for (int j = 0; j < cnt; ++j) {
-            const double d0 = y0 - tile[j][0], d1 = y1 - tile[j][1], d2 = y2 - tile[j][2];
-            const double e = exp((d0 * d0 + d1 * d1 + d2 * d2) / neg_h2);
-            a0 += tile[j][3] * e;
-            a1 += tile[j][4] * e;
-            a2 += tile[j][5] * e;
-            a3 += tile[j][6] * e;
-        }
-    }
-    // a lane without a centre adds exact zeros, whatever the pose is (0 x NaN would not)
-    double v[L2_NOUT];
-    const double g0 = live ? (ps * (a0 * y0 - a1)) / h.two_s2 : 0.0;
-    const double g1 = live ? (ps * (a0 * y1 - a2)) / h.two_s2 : 0.0;
-    const double g2 = live ? (ps * (a0 * y2 - a3)) / h.two_s2 : 0.0;
-    v[0] = live ? -(ps * a0) : 0.0;
-    v[1] = g0; v[2] = g1; v[3] = g2;
-    v[4] = g0 * x0; v[5] = g0 * x1; v[6] = g0 * x2;
-    v[7] = g1 * x0; v[8] = g1 * x1; v[9] = g1 * x2;
-    v[10] = g2 * x0; v[11] = g2 * x1; v[12] = g2 * x2;
-    double* rec = records + ((size_t)r * wg_max + w) * L2_NOUT;
-#pragma unroll
-    for (int k = 0; k < L2_NOUT; ++k) {
-        const double s = wave_sum_f64(v[k]);
-        if (threadIdx.x == 0) rec[k] = s;
-    }
+#include "l2_cost_body.h"
 }
 
 // one thread per (hypothesis, output): the hypothesis' records in (source block, target split) order
@@ -127,6 +65,68 @@ __global__ __launch_bounds__(256) void l2_finish_kernel(const L2Pair* __restrict
     double s = rec[0];
     for (int w = 1; w < nwg; ++w) s += rec[(size_t)w * L2_NOUT];
     out[e] = s;
+}
+
+// ---- the device solve --------------------------------------------------------------------------------------------------
+// l2_cost_kernel over the trial poses the step kernel left in `hyps`; L2Hyp::pad != 0: the hypothesis has left the loop
+__global__ __launch_bounds__(L2_BLOCK) void l2_solve_cost_kernel(
+    const double* __restrict__ mu_s, const double* __restrict__ phi_s, const double* __restrict__ mu_t,
+    const double* __restrict__ phi_t, const L2Pair* __restrict__ pairs, const L2Hyp* __restrict__ hyps, int wg_max,
+    double* __restrict__ records /*[R][wg_max][13]*/) {
+#pragma clang fp contract(off)
+    __shared__ double tile[L2_TILE][L2_ROW];
+    const int r = blockIdx.y;
+    const L2Hyp& h = hyps[r];
+    if (h.pad != 0) return;                                         // (uniform: the whole workgroup leaves)
+#include "l2_cost_body.h"
+}
+
+// the pose of a quaternion into a hypothesis' slot
+__device__ inline void l2_solve_pose(const double* theta, L2Hyp* h) {
+    L2Quat qt;
+    l2_quat_terms(theta, false, qt);
+    for (int i = 0; i < 9; ++i) h->rot[i] = qt.rot[i];
+    for (int i = 0; i < 3; ++i) h->t[i] = theta[4 + i];
+}
+
+// the start poses: one thread per hypothesis (the same code that forms every later trial pose)
+__global__ __launch_bounds__(L2_BLOCK) void l2_solve_init_kernel(L2Hyp* hyps, const L2SolveState* __restrict__ states, int R) {
+    const int r = blockIdx.x * L2_BLOCK + (int)threadIdx.x;
+    if (r < R) l2_solve_pose(states[r].x, hyps + r);
+}
+
+// one wave per hypothesis: lanes 0..12 add its records in (source block, target split) order, as l2_finish_kernel does;
+// lane 0 then does the serial part of the evaluation (l2_solve_step) on a copy of the state, writes the next trial pose or
+// the "left" mark, and stores the progress word for the host
+__global__ __launch_bounds__(L2_BLOCK) void l2_solve_step_kernel(const L2Pair* __restrict__ pairs, L2Hyp* hyps,
+                                                                 L2SolveState* states, int wg_max,
+                                                                 const double* __restrict__ records,
+                                                                 unsigned long long* host_words) {
+#pragma clang fp contract(off)
+    __shared__ double sums[L2_NOUT];
+    const int r = blockIdx.x;
+    L2Hyp* h = hyps + r;
+    if (h->pad != 0) return;
+    const int k = (int)threadIdx.x;
+    if (k < L2_NOUT) {
+        const L2Pair p = pairs[h->pair];
+        const int nwg = ((p.Js + L2_BLOCK - 1) / L2_BLOCK) * l2_splits(p.Jt);
+        const double* rec = records + (size_t)r * wg_max * L2_NOUT + k;
+        double s = rec[0];
+        for (int w = 1; w < nwg; ++w) s += rec[(size_t)w * L2_NOUT];
+        sums[k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double out[L2_NOUT];
+    for (int i = 0; i < L2_NOUT; ++i) out[i] = sums[i];
+    L2SolveState s = states[r];
+    l2_solve_step(s, out);
+    states[r] = s;
+    if (s.left) h->pad = 1;
+    else l2_solve_pose(s.xt, h);
+    __hip_atomic_store(host_words + r, ((unsigned long long)(s.left ? 1 : 0) << 32) | (unsigned long long)(unsigned)s.nfev,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace hgmm
@@ -233,4 +233,124 @@ extern "C" int hgmm_l2_cost(hgmm_ctx* c, int R, const int32_t* pair, const doubl
     HGMM_HIP(c, ctx_stream_sync(c));
     std::memcpy(out, c->l2.pin + out_off, sizeof(double) * L2_NOUT * (size_t)R);
     return HGMM_OK;
+}
+
+// ---- hgmm_l2_solve / hgmm_l2_solve_each -----------------------------------------------------------------------------------
+namespace hgmm {
+
+constexpr int L2_SOLVE_AHEAD = 4;      // evaluations the host keeps enqueued beyond the slowest hypothesis still running
+
+// max_iter_of(r), gtol_of(r): the hypothesis' own limits (hgmm_l2_solve: the same for all)
+template <class MaxIterOf, class GtolOf>
+static int l2_solve_run(hgmm_ctx* c, int R, const int32_t* pair, const double* theta0, const double* sigma, MaxIterOf&& max_iter_of,
+                        GtolOf&& gtol_of, double* theta_out, double* f_out, double* grad_out, int32_t* nit_out, int32_t* nfev_out,
+                        int32_t* status_out) {
+    if (c->l2.B < 1) return fail(c, HGMM_ERR_STATE, "l2 solve: no resident pairs (call hgmm_l2_set_pairs first)");
+    if (R < 1 || R > HGMM_L2_MAX_HYP) return fail(c, HGMM_ERR_ARG, "l2 solve: R = %d outside 1..%d", R, HGMM_L2_MAX_HYP);
+    long long budget = 1;
+    for (int r = 0; r < R; ++r) {
+        if (pair[r] < 0 || pair[r] >= c->l2.B)
+            return fail(c, HGMM_ERR_ARG, "l2 solve: pair out of range (hypothesis %d names pair %d of %d)", r, (int)pair[r], c->l2.B);
+        if (!(sigma[r] > 0.0))
+            return fail(c, HGMM_ERR_ARG, "l2 solve: sigma not positive (hypothesis %d: %g)", r, sigma[r]);
+        if (max_iter_of(r) < 1)
+            return fail(c, HGMM_ERR_ARG, "l2 solve: max_iter < 1 (hypothesis %d: %d)", r, (int)max_iter_of(r));
+        if (!(gtol_of(r) >= 0.0))
+            return fail(c, HGMM_ERR_ARG, "l2 solve: gtol negative or NaN (hypothesis %d: %g)", r, gtol_of(r));
+        // a line search that has not ended after L2_LS_MAX evaluations has failed: the budget is exact
+        budget = std::max(budget, 1 + (long long)L2_LS_MAX * max_iter_of(r));
+    }
+    const int wg_max = c->l2.wg_max;
+    const unsigned long long rec_bytes = (unsigned long long)R * (unsigned long long)wg_max * L2_NOUT * sizeof(double);
+    if (rec_bytes > L2_MAX_RECORD_BYTES)
+        return fail(c, HGMM_ERR_ARG, "l2 solve: the records of %d hypotheses x %d workgroups exceed %llu bytes; call with fewer",
+                    R, wg_max, L2_MAX_RECORD_BYTES);
+    const size_t head_bytes = (sizeof(L2Hyp) + sizeof(L2SolveState)) * (size_t)R;
+    HGMM_TRY(ensure(c, c->l2.work, head_bytes + (size_t)rec_bytes));
+    HandOver* hand = nullptr;
+    HGMM_TRY(hand_over(c, R, &hand));
+    const HostDev<unsigned long long> words = hand->progress(0);
+    L2Hyp* hyp_host = reinterpret_cast<L2Hyp*>(c->l2.pin);
+    std::vector<L2SolveState> states((size_t)R);
+    std::memset(states.data(), 0, sizeof(L2SolveState) * (size_t)R);
+    for (int r = 0; r < R; ++r) {
+        L2Hyp& h = hyp_host[r];
+        std::memset(&h, 0, sizeof h);
+        const double s = sigma[r], hh = std::sqrt(2.0) * s;             // (as hgmm_l2_cost forms them)
+        h.neg_h2 = -(hh * hh);
+        h.z = std::pow((2.0 * M_PI) * (s * s), 1.5);
+        h.two_s2 = 2.0 * (s * s);
+        h.pair = pair[r];
+        h.pad = 0;
+        std::memcpy(states[r].x, theta0 + 7 * (size_t)r, sizeof states[r].x);
+        states[r].max_iter = max_iter_of(r);
+        states[r].gtol = gtol_of(r);
+        __atomic_store_n(words.host + r, 0ull, __ATOMIC_RELAXED);
+    }
+    L2Hyp* d_hyp = c->l2.work.as<L2Hyp>();
+    L2SolveState* d_state = reinterpret_cast<L2SolveState*>(d_hyp + R);
+    double* d_rec = reinterpret_cast<double*>(d_state + R);
+    HGMM_HIP(c, hipMemcpyAsync(d_hyp, hyp_host, sizeof(L2Hyp) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+    HGMM_HIP(c, hipMemcpyAsync(d_state, states.data(), sizeof(L2SolveState) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+    long long ns = 0, nt = 0;
+    for (const L2Pair& p : c->l2.pairs) { ns += p.Js; nt += p.Jt; }
+    const double* d_mu_s = c->l2.mix.as<double>();
+    const double* d_phi_s = d_mu_s + 3 * (size_t)ns;
+    const double* d_mu_t = d_phi_s + (size_t)ns;
+    const double* d_phi_t = d_mu_t + 3 * (size_t)nt;
+    const L2Pair* d_pairs = reinterpret_cast<const L2Pair*>(d_phi_t + (size_t)nt);
+    l2_solve_init_kernel<<<(R + L2_BLOCK - 1) / L2_BLOCK, L2_BLOCK, 0, c->stream>>>(d_hyp, d_state, R);
+    HGMM_HIP(c, hipGetLastError());
+    HGMM_HIP(c, ctx_stream_sync(c));                     // (`states` and the pinned hypotheses are free again)
+    const auto enqueue = [&](int) -> int {
+        l2_solve_cost_kernel<<<dim3((unsigned)wg_max, (unsigned)R), L2_BLOCK, 0, c->stream>>>(d_mu_s, d_phi_s, d_mu_t, d_phi_t,
+                                                                                            d_pairs, d_hyp, wg_max, d_rec);
+        l2_solve_step_kernel<<<R, L2_BLOCK, 0, c->stream>>>(d_pairs, d_hyp, d_state, wg_max, d_rec, words.dev);
+        HGMM_HIP(c, hipGetLastError());
+        return HGMM_OK;
+    };
+    const int budget_int = (int)std::min(budget, 2147483647LL);
+    const int rc = follow_ahead(c, words.host, R, budget_int, L2_SOLVE_AHEAD, enqueue, nothing_at_budget, nullptr,
+                                "l2 solve");
+    if (rc != HGMM_OK) {
+        (void)ctx_stream_sync(c);                        // nothing of this call is left in flight
+        return rc;
+    }
+    {
+        StagedDownloads dl(c);
+        dl.add(states.data(), d_state, sizeof(L2SolveState) * (size_t)R);
+        HGMM_HIP(c, dl.finish());
+    }
+    for (int r = 0; r < R; ++r) {
+        const L2SolveState& s = states[r];
+        std::memcpy(theta_out + 7 * (size_t)r, s.x, sizeof s.x);
+        f_out[r] = s.f;
+        if (grad_out) std::memcpy(grad_out + 7 * (size_t)r, s.g, sizeof s.g);
+        nit_out[r] = s.nit;
+        nfev_out[r] = s.nfev;
+        status_out[r] = s.status;
+    }
+    return HGMM_OK;
+}
+
+}  // namespace hgmm
+
+extern "C" int hgmm_l2_solve_each(hgmm_ctx* c, int R, const int32_t* pair, const double* theta0, const double* sigma,
+                                  const int32_t* max_iter, const double* gtol, double* theta_out, double* f_out, double* grad_out,
+                                  int32_t* nit_out, int32_t* nfev_out, int32_t* status_out) {
+    HGMM_ENTER(c);
+    if (!pair || !theta0 || !sigma || !max_iter || !gtol || !theta_out || !f_out || !nit_out || !nfev_out || !status_out)
+        return fail(c, HGMM_ERR_ARG, "l2 solve: NULL argument");
+    return l2_solve_run(c, R, pair, theta0, sigma, [&](int r) { return (int)max_iter[r]; }, [&](int r) { return gtol[r]; },
+                        theta_out, f_out, grad_out, nit_out, nfev_out, status_out);
+}
+
+extern "C" int hgmm_l2_solve(hgmm_ctx* c, int R, const int32_t* pair, const double* theta0, const double* sigma, int max_iter,
+                             double gtol, double* theta_out, double* f_out, double* grad_out, int32_t* nit_out, int32_t* nfev_out,
+                             int32_t* status_out) {
+    HGMM_ENTER(c);
+    if (!pair || !theta0 || !sigma || !theta_out || !f_out || !nit_out || !nfev_out || !status_out)
+        return fail(c, HGMM_ERR_ARG, "l2 solve: NULL argument");
+    return l2_solve_run(c, R, pair, theta0, sigma, [&](int) { return max_iter; }, [&](int) { return gtol; }, theta_out, f_out,
+                        grad_out, nit_out, nfev_out, status_out);
 }

@@ -204,7 +204,8 @@ struct L2Set {
     int wg_max = 0;                   // the largest workgroup count of one hypothesis among the resident pairs (grid.x)
     std::vector<L2Pair> pairs;        // host copy of the device table (hgmm_l2_cost's checks and launch shape)
     DevBuf mix;                       // double mu_s [sum Js][3] | phi_s [sum Js] | mu_t [sum Jt][3] | phi_t [sum Jt], then L2Pair [B]
-    DevBuf work;                      // per call: L2Hyp [R], then double records [R][wg_max][13]
+    DevBuf work;                      // per call: L2Hyp [R], then double records [R][wg_max][13]; hgmm_l2_solve: L2Hyp [R],
+                                      // L2SolveState [R] (l2_device.h), then the records
     char* pin = nullptr;              // pinned, device-visible: L2Hyp [HGMM_L2_MAX_HYP] on their way in, then double
     char* pin_dev = nullptr;          // [HGMM_L2_MAX_HYP][13] the finish kernel writes (hipHostFree: hgmm_destroy)
 };

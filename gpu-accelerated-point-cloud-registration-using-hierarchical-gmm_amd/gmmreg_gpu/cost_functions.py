@@ -8,7 +8,8 @@ of ONE kernel matrix here (the reference evaluates it 1 + 3 times, cost_function
 context it is `hgmm_gauss_transform`.  The 7-parameter chain rule stays in NumPy.
 ``RigidCostFunction.evaluate_many`` evaluates R hypotheses at once over mixtures that stay resident on the device
 (`hgmm_l2_set_pairs` / `hgmm_l2_cost`: the fused kernel returns f, the column sums of the gradient and g.T @ mu_source);
-``__call__`` is the path it always was.
+``__call__`` is the path it always was.  ``RigidCostFunction.solve_many`` runs the whole BFGS solve of R hypotheses on the
+device (`hgmm_l2_solve`): chain rule, line search and inverse-Hessian update included, no Python between two evaluations.
 """
 import numpy as np
 
@@ -134,3 +135,32 @@ class RigidCostFunction(CostFunction):
         for r in range(R):
             grad[r, :4] = np.einsum('ab,kab->k', out[r, 4:].reshape(3, 3), so.diff_rot_from_quaternion(thetas[r, :4]))
         return f, grad
+
+    SOLVE_MESSAGES = ("Optimization terminated successfully.", "Maximum number of iterations has been exceeded.",
+                      "Desired error not necessarily achieved due to precision loss.", "NaN result encountered.")
+
+    def solve_many(self, thetas, pair_ids, sigmas, maxiter=10, tol=1.0e-5):
+        """The whole BFGS solve of R hypotheses on the device, in lock-step (``Context.l2_solve`` / ``hgmm_l2_solve``):
+        hypothesis r starts at ``thetas[r]`` on pair ``pair_ids[r]`` of :meth:`set_pairs` at kernel width ``sigmas[r]``;
+        ``maxiter`` and ``tol`` are what ``gmmreg.bfgs_round`` hands SciPy.  -> list of ``OptimizeResult`` with ``x, fun, jac,
+        nit, nfev, status, success, message``, each the solve of that hypothesis run alone.
+
+        The optimiser is SciPy's BFGS with its first line search (dcsrch), restated on the device.  One deliberate
+        difference: where SciPy tries a second line search after dcsrch has failed, the solve ends at once with status 2
+        ("precision loss") at the last accepted iterate -- ``nfev`` differs from SciPy's by design, ``x, fun, nit, status`` are
+        what compare.  Needs a context: this project has no CPU fallback."""
+        from scipy.optimize import OptimizeResult
+        thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, 7)
+        R = len(thetas)
+        pair_ids = np.broadcast_to(np.asarray(pair_ids, dtype=np.int64), (R,))
+        sigmas = np.broadcast_to(np.asarray(sigmas, dtype=np.float64), (R,))
+        if not self._pairs:
+            raise ValueError("solve_many: no mixtures (call set_pairs first)")
+        if self._ctx is None:
+            raise RuntimeError("solve_many: the device solve needs a context (there is no CPU fallback)")
+        if self._ctx.l2_owner is not self._resident:
+            self._make_resident()
+        x, f, grad, nit, nfev, status = self._ctx.l2_solve(pair_ids, thetas, sigmas, maxiter, tol)
+        return [OptimizeResult(x=x[r].copy(), fun=float(f[r]), jac=grad[r].copy(), nit=int(nit[r]), nfev=int(nfev[r]),
+                               status=int(status[r]), success=bool(status[r] == 0), message=self.SOLVE_MESSAGES[int(status[r])])
+                for r in range(R)]

@@ -17,6 +17,8 @@ No counterpart in the reference: the multi-start and the batch.  :func:`lockstep
 ``RigidCostFunction.evaluate_many`` over mixtures that stay on the device (``hgmm_l2_set_pairs`` / ``hgmm_l2_cost``);
 ``L2DistRegistration.optimise_multistart`` / ``registration_multistart``, ``registration_gmmreg(..., starts=)`` and
 :func:`registration_gmmreg_batch` are built on it.  ``registration_gmmreg(...)`` without ``starts`` is what it was.
+Each of them takes ``solver="device"`` (default "scipy"): the solves then run as ONE ``RigidCostFunction.solve_many`` -- the
+whole BFGS loop of every hypothesis on the device (``hgmm_l2_solve``), no Python between two evaluations (:func:`solve_jobs`).
 """
 import threading
 import time
@@ -153,6 +155,22 @@ def lockstep_solve(evaluate_many, jobs, maxiter, tol):
     return results
 
 
+def solve_jobs(cost_fn, jobs, maxiter, tol, solver="scipy"):
+    """The solves of ``jobs`` (``(x0, pair_id, sigma)`` on the mixtures of ``cost_fn.set_pairs``) -> list of ``OptimizeResult``.
+    ``solver="scipy"``: :func:`lockstep_solve` over ``cost_fn.evaluate_many``, SciPy's own BFGS per job.  ``solver="device"``:
+    ONE ``cost_fn.solve_many`` -- the whole solve of every job on the device (``hgmm_l2_solve``), SciPy's BFGS restated there
+    with one deliberate difference: a failed dcsrch line search ends the solve at once (status 2) where SciPy would try a
+    second one first."""
+    jobs = list(jobs)
+    if solver == "scipy":
+        return lockstep_solve(cost_fn.evaluate_many, jobs, maxiter, tol)
+    if solver != "device":
+        raise ValueError("solver = %r (expected 'scipy' or 'device')" % (solver,))
+    if not jobs:
+        return []
+    return cost_fn.solve_many([j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs], maxiter, tol)
+
+
 def _start_thetas(starts):
     """Start poses -> list of theta: a ``RigidTransformation`` goes through ``theta_from_transformation``, a 7-vector is
     taken as it is.  An empty list is refused."""
@@ -236,24 +254,26 @@ class L2DistRegistration(object):
             print("Overall Time taken: ", time.time() - t0)
         return out
 
-    def optimise_multistart(self, mu_source, phi_source, mu_target, phi_target, starts, opt_maxiter=10, opt_tol=1.0e-5):
+    def optimise_multistart(self, mu_source, phi_source, mu_target, phi_target, starts, opt_maxiter=10, opt_tol=1.0e-5,
+                            solver="scipy"):
         """:meth:`optimise` from every pose of ``starts`` (``RigidTransformation`` objects or 7-vectors), all solves in
         lock-step (:func:`lockstep_solve`): one ``evaluate_many`` of the cost function serves every solve that is still
         running.  -> list of ``OptimizeResult``, each the solve from that start run alone.  The per-step callbacks of
-        :meth:`optimise` are not called: the solves do not run one after the other."""
+        :meth:`optimise` are not called: the solves do not run one after the other.  ``solver="device"``: the solves run on
+        the device instead (:func:`solve_jobs`)."""
         thetas = _start_thetas(starts)
         self._cost_fn.set_pairs([(mu_source, phi_source, mu_target, phi_target)])
-        res = lockstep_solve(self._cost_fn.evaluate_many, [(x0, 0, self._sigma) for x0 in thetas], opt_maxiter, opt_tol)
+        res = solve_jobs(self._cost_fn, [(x0, 0, self._sigma) for x0 in thetas], opt_maxiter, opt_tol, solver)
         self.best_index_ = _lowest([float(r.fun) for r in res])
         return res
 
     def registration_multistart(self, target, starts, maxiter=1, tol=1.0e-3, opt_maxiter=10, opt_tol=1.0e-5,
-                                return_all=False):
+                                return_all=False, solver="scipy"):
         """:meth:`registration` from every pose of ``starts`` at once.  The outer rounds are those of :func:`l2_register`:
         per round the source is summarised ONCE for all starts and the kernel width is annealed ONCE; a start stops when its
         own cost moved by less than ``tol`` between two rounds.  The winner is the start with the lowest final cost (ties:
         the lowest index); ``best_index_`` names it and its ``RigidTransformation`` is returned -- with ``return_all=True``,
-        ``(winner, [transformation of every start], [final cost of every start])``."""
+        ``(winner, [transformation of every start], [final cost of every start])``.  ``solver``: :func:`solve_jobs`."""
         thetas = _start_thetas(starts)
         self._feature_gen.init()
         target_mix = summarise(self._feature_gen, target)
@@ -262,8 +282,7 @@ class L2DistRegistration(object):
         for _ in range(maxiter):
             source_mix = summarise(self._feature_gen, self._source)
             self._cost_fn.set_pairs([(*source_mix, *target_mix)])
-            res = lockstep_solve(self._cost_fn.evaluate_many, [(thetas[k], 0, self._sigma) for k in running], opt_maxiter,
-                                 opt_tol)
+            res = solve_jobs(self._cost_fn, [(thetas[k], 0, self._sigma) for k in running], opt_maxiter, opt_tol, solver)
             self._annealing()
             self._feature_gen.annealing()
             still = []
@@ -319,30 +338,39 @@ def _run(kind, source, target, tf_type_name, callbacks, reg_args, kargs):
     return reg.registration(_points(target), *reg_args)
 
 
-def registration_gmmreg(source, target, tf_type_name='rigid', callbacks=[], starts=None, **kargs):
+def registration_gmmreg(source, target, tf_type_name='rigid', callbacks=[], starts=None, solver="scipy", **kargs):
     """reference gmmreg.py:149-157: returns the RigidTransformation mapping source onto target.
 
     ``starts`` (no counterpart in the reference; default None: the reference's single solve from the identity): a list
-    of start poses -- the result is ``RigidGMMReg.registration_multistart``'s winner."""
-    if starts is None:
+    of start poses -- the result is ``RigidGMMReg.registration_multistart``'s winner.  ``solver`` ("scipy", the default, or
+    "device": :func:`solve_jobs`): with "device" the solves run on the device; without ``starts`` that is the one solve from
+    the identity.  Without ``starts`` and with the default solver this is the reference's path, as it was."""
+    if solver not in ("scipy", "device"):
+        raise ValueError("solver = %r (expected 'scipy' or 'device')" % (solver,))
+    if starts is None and solver == "scipy":
         return _run(RigidGMMReg, source, target, tf_type_name, callbacks, (), kargs)
     if tf_type_name != 'rigid':
         raise ValueError('Unknown transform type %s' % tf_type_name)
     reg = RigidGMMReg(_points(source), **kargs)
     reg.set_callbacks(callbacks)
-    return reg.registration_multistart(_points(target), starts)
+    if starts is None:
+        starts = [reg._cost_fn.initial()]
+    return reg.registration_multistart(_points(target), starts, solver=solver)
 
 
-def registration_gmmreg_batch(pairs, starts=None, ctx=None, maxiter=1, **kargs):
+def registration_gmmreg_batch(pairs, starts=None, ctx=None, maxiter=1, solver="scipy", **kargs):
     """``registration_gmmreg(source, target, **kargs)`` for every ``(source, target)`` of ``pairs`` through one launch set
     per stage.  The 2B mixtures are fitted by ONE ``fit_batch`` in the order t0, s0, t1, s1, ... -- the order in which a
     loop of ``registration_gmmreg`` draws from NumPy's random stream; if the pairs' component counts differ (a small cloud
     caps its own at 0.8 N) the fits run one by one in that same order.  All pairs' mixtures then become resident with one
     ``set_pairs`` and every pair's solve (with ``starts``: every start of every pair) runs in lock-step
-    (:func:`lockstep_solve`), each at its own pair's kernel width.
+    (:func:`lockstep_solve`), each at its own pair's kernel width -- with ``solver="device"`` in ONE ``solve_many`` on the device
+    (:func:`solve_jobs`).
 
     Only the single outer round ``registration_gmmreg`` uses is offered: ``maxiter`` other than 1 is refused.
     -> list of ``RigidTransformation``; with ``starts``, ``(list, winners' indices)``."""
+    if solver not in ("scipy", "device"):
+        raise ValueError("solver = %r (expected 'scipy' or 'device')" % (solver,))
     if maxiter != 1:
         raise ValueError("registration_gmmreg_batch: outer maxiter = %r is not supported (only maxiter = 1, which is "
                          "what registration_gmmreg uses); register the pairs one by one" % (maxiter,))
@@ -365,7 +393,7 @@ def registration_gmmreg_batch(pairs, starts=None, ctx=None, maxiter=1, **kargs):
         thetas = [cost.initial()]
     K = len(thetas)
     # (opt_maxiter = 10, opt_tol = 1e-5: the defaults of L2DistRegistration.registration, which registration_gmmreg runs with)
-    res = lockstep_solve(cost.evaluate_many, [(x0, b, reg._sigma) for b, reg in enumerate(regs) for x0 in thetas], 10, 1.0e-5)
+    res = solve_jobs(cost, [(x0, b, reg._sigma) for b, reg in enumerate(regs) for x0 in thetas], 10, 1.0e-5, solver)
     tfs, winners = [], []
     for b in range(len(regs)):
         mine = res[b * K:(b + 1) * K]

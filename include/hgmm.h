@@ -881,6 +881,41 @@ int hgmm_l2_set_pairs(hgmm_ctx* ctx, int B, const int32_t* Js /* [B] */, const d
 int hgmm_l2_cost(hgmm_ctx* ctx, int R, const int32_t* pair /* [R] */, const double* rot /* [R][9] */,
                  const double* t /* [R][3] */, const double* sigma /* [R] */, double* out /* [R][13] */);
 
+/* ---- L2 GMMReg: the whole BFGS solve of R hypotheses on the device, in lock-step (float64) --------------------------------
+ * The reference solves theta = (qw, qx, qy, qz, tx, ty, tz) with SciPy's BFGS (gmmreg.py:98-107: method='BFGS', jac=True,
+ * tol=opt_tol, options={'maxiter': opt_maxiter}) on RigidCostFunction (cost_functions.py:43-68).  hgmm_l2_solve runs that
+ * solve for R hypotheses on the resident pairs of hgmm_l2_set_pairs without the host between two launches: hypothesis r
+ * starts at theta0[r] on pair[r] at kernel width sigma[r].  One evaluation is two launches -- the fused cost kernel over the
+ * current trial poses, then one wave per hypothesis that adds its records (the 13 sums have the bits hgmm_l2_cost returns for
+ * that pose), does the quaternion chain rule (so.quaternion_matrix with its identity rule for |q|^2 < 4 eps,
+ * so.diff_rot_from_quaternion with the reference's quirks), one transition of the line search / BFGS state machine and the next
+ * trial pose, and stores a progress word the host follows.  The state stays on the device; the outputs are downloaded once.
+ * THE OPTIMISER is SciPy 1.15's: _minimize_bfgs over line_search_wolfe1 (dcsrch, c1 = 1e-4, c2 = 0.9, xtol = 1e-14, steps in
+ * 1e-100..1e100, at most 100 evaluations per line search), gtol on the infinity norm, old_old_fval = f0 + |g|_2 / 2, rhok = 1000
+ * when yk.sk == 0, its NaN and non-finite-f endings -- restated in float64 with + - x / sqrt only, contraction off, in ONE
+ * written-down order (csrc/l2_device.h; tests/_l2_solve_model.py is the same in scalar Python, which the device meets bit for
+ * bit).  ONE DELIBERATE DIFFERENCE: when dcsrch fails SciPy tries a second line search (line_search_wolfe2) and ends with
+ * status 2 at the last accepted iterate only if that fails too; here the solve ends there at once with status 2 (on the
+ * multi-start scenario the second search rescued 0 of 25 failures at 12-14 evaluations each: profiles/l2_device_solve.md).
+ * nfev therefore differs from SciPy's by design; x, f, nit and status are what compare.
+ * OUTPUTS per hypothesis: theta_out the last accepted iterate, f_out its cost, grad_out (may be NULL) its gradient, nit_out the
+ * accepted steps, nfev_out the evaluations, status_out: 0 gtol met, 1 max_iter reached, 2 line search failed (or f not finite),
+ * 3 NaN.  INDEPENDENT: hypothesis r of any call has the bits of the R = 1 call; no floating-point atomics.  The result is a
+ * function of the arguments and the resident set alone, which the entry leaves untouched.
+ * hgmm_l2_solve_each is the same with max_iter [R] and gtol [R] of each hypothesis' own.
+ * REFUSALS (hgmm_last_error names each; nothing resident is touched).  HGMM_ERR_ARG: a NULL argument (grad_out excepted); R outside
+ * 1..HGMM_L2_MAX_HYP; pair[r] out of range; sigma[r] not positive (NaN included); max_iter < 1; gtol negative or NaN; the
+ * records of one call above 1 GiB.  HGMM_ERR_STATE: no resident pairs.  A NON-FINITE OR ZERO-LENGTH START QUATERNION IS NOT
+ * REFUSED: that hypothesis ends with status 3 after its first evaluation, the others are what they would have been. */
+int hgmm_l2_solve(hgmm_ctx* ctx, int R, const int32_t* pair /* [R] */, const double* theta0 /* [R][7] */,
+                  const double* sigma /* [R] */, int max_iter, double gtol, double* theta_out /* [R][7] */,
+                  double* f_out /* [R] */, double* grad_out /* [R][7] | NULL */, int32_t* nit_out /* [R] */,
+                  int32_t* nfev_out /* [R] */, int32_t* status_out /* [R] */);
+int hgmm_l2_solve_each(hgmm_ctx* ctx, int R, const int32_t* pair /* [R] */, const double* theta0 /* [R][7] */,
+                       const double* sigma /* [R] */, const int32_t* max_iter /* [R] */, const double* gtol /* [R] */,
+                       double* theta_out /* [R][7] */, double* f_out /* [R] */, double* grad_out /* [R][7] | NULL */,
+                       int32_t* nit_out /* [R] */, int32_t* nfev_out /* [R] */, int32_t* status_out /* [R] */);
+
 /* ---- voxel-grid down-sample: centroids + counts, one cloud or B clouds per launch set -----------------------------------
  * Every pipeline of the reference voxel-down-samples its scans first -- o3.voxel_down_sample at hgmm/hgmm_gpu.py:786 and
  * 829-830, run_gmm_static.py:28, waymoutils.py:99, gmmreg.py:203-204 -- and the counts are what the weight entries above

@@ -9,10 +9,11 @@ the same device:
   (a) one cost evaluation at J = 30, 100, 800 (random mixtures in the unit cube, sigma = 0.15): R = 1 and R = 27 hypotheses,
       R calls of ``__call__`` against one ``evaluate_many``; ``l2_cost`` alone is the library call without the chain rule
   (b) the 27-start solve of the multi-start scenario (tests/l2_scenario.py): a loop of ``optimise`` against
-      ``optimise_multistart``
+      ``optimise_multistart`` on SciPy (lock-step threads over ``evaluate_many``) and on the device solver
+      (``solver="device"``: hgmm_l2_solve), with the evaluations of its longest hypothesis
   (c) ``registration_gmmreg_batch`` of --pairs pairs of bun000 / bun045 size (tests/golden; pair b's target is bun045 turned
       by b degrees about z) against the loop of ``registration_gmmreg``, each split into the time of the mixture fits and
-      the rest (set-up, solve)
+      the rest (set-up, solve), the batch through both solvers
 
 Every figure is the median of --reps warmed-up calls (minimum - maximum in brackets) of a host clock around calls that end in
 a stream synchronisation.  Markdown on stdout (and into --out)."""
@@ -60,6 +61,10 @@ def timed(fn, reps=args.reps, warm=2):
     return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
+def fmt2(t, unit=1e6):
+    return "%.2f (%.2f - %.2f)" % (t[0] * unit, t[1] * unit, t[2] * unit)
+
+
 def fmt(t, unit=1e6):
     return "%.0f (%.0f - %.0f)" % (t[0] * unit, t[1] * unit, t[2] * unit)
 
@@ -98,6 +103,12 @@ serial = [old_reg.optimise(*mixes, x0, l2s.OPT_MAXITER, l2s.OPT_TOL) for x0 in x
 multi = new_reg.optimise_multistart(*mixes, sc["starts"], l2s.OPT_MAXITER, l2s.OPT_TOL)
 t_old = timed(lambda: [old_reg.optimise(*mixes, x0, l2s.OPT_MAXITER, l2s.OPT_TOL) for x0 in x0s], warm=1)
 t_new = timed(lambda: new_reg.optimise_multistart(*mixes, sc["starts"], l2s.OPT_MAXITER, l2s.OPT_TOL), warm=1)
+dev_reg = l2s.registration(cf.RigidCostFunction(ctx=ctx), sc)
+dev = dev_reg.optimise_multistart(*mixes, sc["starts"], l2s.OPT_MAXITER, l2s.OPT_TOL, solver="device")
+longest = max(int(r.nfev) for r in dev)
+t_dev = timed(lambda: dev_reg.optimise_multistart(*mixes, sc["starts"], l2s.OPT_MAXITER, l2s.OPT_TOL, solver="device"), warm=1)
+ids27, sig27 = np.zeros(27, np.int32), np.full(27, sc["sigma"])
+t_lib = timed(lambda: ctx.l2_solve(ids27, x0s, sig27, l2s.OPT_MAXITER, l2s.OPT_TOL), warm=1)
 say("| path | evaluations | device round trips | ms | winner | degrees from the truth |")
 say("|---|---|---|---|---|---|")
 best = int(np.argmin([r.fun for r in serial]))
@@ -107,8 +118,18 @@ say("| loop of `optimise` | %d | %d | %s | %d | %.1f |" % (
 say("| `optimise_multistart` | %d | %d | %s | %d | %.1f |" % (
     sum(r.nfev for r in multi), max(r.nfev for r in multi), fmt(t_new, 1e3), new_reg.best_index_,
     l2s.angle_deg(new_reg._cost_fn.to_transformation(multi[new_reg.best_index_].x).rot, sc["truth_rot"])))
+say("| `optimise_multistart(solver=\"device\")` | %d | %d evaluations deep, 1 waited for | %s | %d | %.1f |" % (
+    sum(r.nfev for r in dev), longest, fmt2(t_dev, 1e3), dev_reg.best_index_,
+    l2s.angle_deg(dev_reg._cost_fn.to_transformation(dev[dev_reg.best_index_].x).rot, sc["truth_rot"])))
+say("| `Context.l2_solve` alone | %d | %d evaluations deep, 1 waited for | %s | | |" % (sum(r.nfev for r in dev), longest, fmt2(t_lib, 1e3)))
 say()
-say("Ratio of the medians: %.2f." % (t_old[0] / t_new[0]))
+say("Ratios of the medians: loop / SciPy multi-start %.2f, SciPy multi-start / device solver %.1f." % (
+    t_old[0] / t_new[0], t_new[0] / t_dev[0]))
+say("The device solve: the longest hypothesis takes %d evaluations of two launches each (the host enqueues at most 3 more behind "
+    "its end), %.1f microseconds per evaluation of the longest in `Context.l2_solve`; nfev per start %s." % (
+        longest, t_lib[0] * 1e6 / longest, [int(r.nfev) for r in dev]))
+say("nit and status equal to SciPy's multi-start in %d of 27 starts." % sum(
+    (int(a.nit), int(a.status)) == (int(b.nit), int(b.status)) for a, b in zip(dev, multi)))
 
 say()
 say("## (c) %d pairs of bun000 / bun045 size, n_gmm_components = 50, milliseconds for all pairs" % args.pairs)
@@ -153,12 +174,15 @@ def run_split(fn):
 
 loop = run_split(lambda: [gmmreg.registration_gmmreg(s, t) for s, t in pairs])
 batch = run_split(lambda: gmmreg.registration_gmmreg_batch(pairs))
+batch_dev = run_split(lambda: gmmreg.registration_gmmreg_batch(pairs, solver="device"))
 say("| path | whole call | mixture fits | the rest (set-up, solve) |")
 say("|---|---|---|---|")
 say("| loop of `registration_gmmreg` | %s | %s | %s |" % tuple(fmt(t, 1e3) for t in loop))
 say("| `registration_gmmreg_batch` | %s | %s | %s |" % tuple(fmt(t, 1e3) for t in batch))
+say("| `registration_gmmreg_batch(solver=\"device\")` | %s | %s | %s |" % tuple(fmt(t, 1e3) for t in batch_dev))
 say()
 say("Ratios of the medians: whole %.2f, fits %.2f, rest %.2f." % tuple(a[0] / b[0] for a, b in zip(loop, batch)))
+say("SciPy batch / device batch: whole %.2f, fits %.2f, rest %.2f." % tuple(a[0] / b[0] for a, b in zip(batch, batch_dev)))
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
